@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Throughput of the window optimiser on MI355X: optimised windows per second.
 
-    python bench.py --gpus N --steps K --warmup W [--workload seq2k|w8192|<n_chunks>]
+    python bench.py --gpus N --steps K --warmup W [--workload seq2k|w8192|<n_chunks>] [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path over one batch of windows: local stage -> float64
 relative-global transform -> global stage -> global pose (the loop body of the reference's `main()`,
@@ -10,9 +10,13 @@ Default workload = BASELINE.json configs[1]: one 2000-frame sequence = 20 chunks
 windows per GPU, fp32 (weak scaling: every rank gets its own sequence; with N > 1 the refined poses are
 all-gathered over RCCL inside the step).
 
-Rank 0 prints ONE JSON line (contract in the task statement) with `roofline` for the dominant kernel
-(the decoder_input products, timed with HIP events on the launch stream inside the timed region) and
-`cpu_baseline` (the PyTorch-CPU port of the reference timed on this box's host cores, rank 0, N=1).
+A plain run sets up, warms up, times the K steps and prints ONE JSON line on rank 0 (`value`, `ms_per_step`, ...).
+--dump-outputs DIR also writes what the last timed step returned as DIR/<name>.npy (float32 / float64, at most
+64 MB in all).  --full adds everything else to the line: `roofline` for the dominant kernel (the decoder_input
+products, timed with HIP events on the launch stream in the first timed steps), `cpu_baseline` (the PyTorch-CPU
+port of the reference timed on the host cores, rank 0, N=1) and the side records (other precisions, the
+configs[2] / [3] / [4] sizes, partitions, host-inclusive legs, post-processing, lifting, training, and with N > 1
+the strong-scaling legs).
 """
 import argparse
 import json
@@ -57,7 +61,7 @@ def parse():
     p.add_argument("--cpu-windows", type=int, default=12, help="windows of the CPU baseline sample (0 = skip)")
     p.add_argument("--no-extra", action="store_true", help="skip the bf16x3 / bf16 side measurements")
     p.add_argument("--in-flight", action="store_true", help="also measure 1-3 sequences in flight on separate streams, eager and graph replay "
-                   "(`sequences_in_flight`; twelve entries, off by default to keep the line short)")
+                   "(`sequences_in_flight`; twelve entries, off by default to keep the line short; with --full)")
     p.add_argument("--no-partition", action="store_true", help="skip the full-size 8-way partitions of configs[3] / configs[4] (`partition8`)")
     p.add_argument("--full-record", default=None, help="also write the whole JSON line, indented, to this file")
     p.add_argument("--no-graphs", action="store_true", help="configs4: eager launches instead of hipGraph replay (diagnosis)")
@@ -73,10 +77,50 @@ def parse():
                         "reference golden (no fitting kernels: profiling runs)")
     p.add_argument("--weights-cache", default=None, help="torch file to load/store the fitted synthetic VAEs (keeps the "
                    "fitting kernels out of a rocprof trace)")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, rank 0 writes what the last timed step "
+                   "returned as DIR/<name>.npy (float32 / float64; above 64 MB in all, the same fixed seeded sample of rows of each array)")
+    p.add_argument("--full", action="store_true", help="measure and check everything beside the headline as well: HIP-event roofline, "
+                   "cpu_baseline, the side records (--no-extra, --no-profile, --cpu-windows, --in-flight, --no-partition act on these). "
+                   "Without it a run sets up, warms up, times --steps steps, writes --dump-outputs and prints the line")
     a = p.parse_args()
+    if a.steps < 1:
+        p.error("--steps must be >= 1")
     if a.precision is None:
         a.precision = "bf16" if a.workload in ("configs3", "configs4") else "f32"      # BASELINE.json: configs[3] and [4] are bf16
+    if not a.full:
+        # a plain run: only what `value` needs (no HIP events in the timed steps, no CPU baseline, no side legs)
+        a.no_extra, a.no_profile, a.cpu_windows, a.in_flight, a.no_partition = True, True, 0, False, True
     return a
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(d, arrays, seed=0):
+    """--dump-outputs: every array (torch or numpy; None skipped) as d/<name>.npy, float64 kept, float32 kept, anything else
+    (integer counters, flags) as float64.  Above DUMP_BYTES in all, every array keeps the same fraction of its rows: a sorted sample
+    drawn with `seed`, the same rows from run to run (and in arrays of the same length)."""
+    out = {}
+    for k, v in arrays.items():
+        if v is None:
+            continue
+        v = np.asarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v)
+        out[k] = v if v.dtype in (np.float32, np.float64) else v.astype(np.float64)
+    total = sum(v.nbytes for v in out.values())
+    os.makedirs(d, exist_ok=True)
+    for k, v in out.items():
+        if total > DUMP_BYTES and v.ndim and v.shape[0] > 1:
+            n = v.shape[0]
+            keep = max(1, int(n * (DUMP_BYTES / total)))
+            v = v[np.sort(np.random.default_rng(seed).choice(n, keep, replace=False))]
+        np.save(os.path.join(d, k + ".npy"), np.ascontiguousarray(v))
+
+
+def stats_arrays(st, prefix="stats_"):
+    """The [2B, 4] int32 window stats (stats_to_numpy) as separate named arrays for dump_outputs."""
+    if st is None:
+        return {}
+    return {prefix + k: st[k] for k in ("n_iter", "func_evals", "final_loss", "status")}
 
 
 def fit_weights(shape, seed, device, steps, relative, on_device=False):
@@ -91,9 +135,41 @@ def fit_weights(shape, seed, device, steps, relative, on_device=False):
         win = win.reshape(-1, shape.seq_len, 15, 3).copy()
         win[..., 0] += (0.004 * np.arange(shape.seq_len))[None, :, None]
         win = win.reshape(-1, shape.seq_len, 45)
-    sd, err = fit_vae(shape, win, steps=steps, batch=128, lr=2e-3, kl_weight=0.01, seed=seed, device=device,
-                      latent_gain=LATENT_GAIN)
+    import torch
+    # the same weights from run to run (so that runs with the same arguments get the same inputs): MIOpen convolutions in
+    # immediate mode with deterministic solvers, never an algorithm picked by timing it
+    prev = torch.backends.cudnn.deterministic, torch.backends.cudnn.benchmark
+    torch.backends.cudnn.deterministic, torch.backends.cudnn.benchmark = True, False
+    try:
+        sd, err = fit_vae(shape, win, steps=steps, batch=128, lr=2e-3, kl_weight=0.01, seed=seed, device=device,
+                          latent_gain=LATENT_GAIN)
+    finally:
+        torch.backends.cudnn.deterministic, torch.backends.cudnn.benchmark = prev
     return sd, err
+
+
+def fit_weights_in_child(seed, dev_index, steps, relative, on_device=False):
+    """fit_weights(VAEShape(), seed, ...) in a fresh child process on the same device, started now; returns a function that waits
+    for it and returns (state_dict, err).  The fits are bound by kernel launches: two of them overlap almost completely."""
+    import subprocess
+    import tempfile
+    fd, path = tempfile.mkstemp(prefix="gem_bench_vae_", suffix=".pt")
+    os.close(fd)
+    code = ("import sys, torch; sys.path.insert(0, %r); import bench; from globalegomocap_amd import vae; torch.cuda.set_device(%d); "
+            "torch.save(bench.fit_weights(vae.VAEShape(), %d, torch.device('cuda', %d), %d, %r, %r), %r)"
+            % (ROOT, dev_index, seed, dev_index, steps, relative, on_device, path))
+    p = subprocess.Popen([sys.executable, "-c", code], stdout=sys.stderr)       # (stdout carries the JSON line only)
+
+    def result():
+        import torch
+        try:
+            if p.wait():
+                raise RuntimeError("fitting the synthetic VAE of seed %d in a child process failed (exit status %d, its stderr above)"
+                                   % (seed, p.returncode))
+            return torch.load(path, weights_only=False)
+        finally:
+            os.remove(path)
+    return result
 
 
 def cpu_baseline(sd_local, sd_global, cam, seqd, starts, mean_bone, eps_l, eps_g, w_local, w_global, n_windows):
@@ -471,6 +547,9 @@ def run_sharded(a, world, rank, device, rehearsal, sd_local, sd_global, vae_note
             st0 = stats_of[my_ranks[0]]
             np.savez(a.dump, glob=full.cpu().numpy(), merged=merged.cpu().numpy() if merged is not None else np.zeros(0),
                      **({"stats_" + k: np.asarray(st0[k]) for k in st0.dtype.names} if st0 is not None else {}))
+        if a.dump_outputs:
+            # the gathered [n,10,15,3] poses in window order (+ the merged sequence of the stream) and rank 0's window stats
+            dump_outputs(a.dump_outputs, dict(glob=full, merged=merged, **stats_arrays(stats_of[my_ranks[0]])))
         gs = eng.graph_stats() if stream else None
         ev = [float(p["evaluations"]) for p in per_rank]
         tm = [float(p.get("ms_best_step", p["ms_per_step"])) for p in per_rank]
@@ -520,6 +599,7 @@ def run_sharded(a, world, rank, device, rehearsal, sd_local, sd_global, vae_note
 
 
 def main():
+    t_start = time.perf_counter()
     a = parse()
     if a.gpus < 1:
         sys.exit("bench.py: --gpus must be >= 1")
@@ -551,6 +631,11 @@ def main():
         ge.build()
     if world > 1:
         dist.barrier()
+
+    def say(what):
+        if a.verbose:
+            print("[bench rank %d] %.2f s: %s" % (rank, time.perf_counter() - t_start, what), file=sys.stderr, flush=True)
+    say("library built and loaded")
     from globalegomocap_amd import synth, vae as vae_schema
     from globalegomocap_amd.camera import FisheyeCamera, DEFAULT_CALIBRATION
     from globalegomocap_amd.engine import WindowEngine, energy_weights, stats_to_numpy, LOCAL_STAGE, GLOBAL_STAGE
@@ -571,10 +656,15 @@ def main():
     elif a.weights_cache and os.path.exists(a.weights_cache):
         sd_local, err_l, sd_global, err_g = torch.load(a.weights_cache, weights_only=False)
     else:
-        sd_local, err_l = fit_weights(shape, 101, device, a.fit_steps, relative=False, on_device=a.vae == "fit-device")
-        sd_global, err_g = fit_weights(shape, 102, device, a.fit_steps, relative=True, on_device=a.vae == "fit-device")
+        fit_dev = a.vae == "fit-device"
+        # one rank: the global VAE is fitted by a child process on the same device meanwhile (the same call, deterministic
+        # kernels: the same weights as in this process)
+        child = fit_weights_in_child(102, dev_index, a.fit_steps, True, fit_dev) if world == 1 else None
+        sd_local, err_l = fit_weights(shape, 101, device, a.fit_steps, relative=False, on_device=fit_dev)
+        sd_global, err_g = child() if child else fit_weights(shape, 102, device, a.fit_steps, relative=True, on_device=fit_dev)
         if a.weights_cache and rank == 0:
             torch.save((sd_local, err_l, sd_global, err_g), a.weights_cache)
+    say("VAE weights ready")
     if a.workload in ("configs3", "configs4"):
         note = ("synthetic, fitted %d Adam steps (recon %.1f / %.1f mm)" % (a.fit_steps, err_l * 1e3, err_g * 1e3)) if a.vae != "structured" else "synthetic, structured"
         return run_sharded(a, world, rank, device, rehearsal, sd_local, sd_global, note)
@@ -606,13 +696,14 @@ def main():
     def step():
         mid, glob, stats = eng.optimize_windows(seqd["est_local"], seqd["cams"], seqd["heat"], f0, mb_w, eps_l, eps_g,
                                                 w_local, w_global, want_stats=True)
-        if world > 1:
-            all_gather_windows(glob, B * world)      # refined global poses of every shard, on every rank
-        return mid, glob, stats
+        gathered = all_gather_windows(glob, B * world) if world > 1 else None     # refined global poses of every shard, on every rank
+        return mid, glob, stats, gathered
 
+    say("inputs resident, engine ready")
     for _ in range(a.warmup):
         step()
     torch.cuda.synchronize()
+    say("warm-up done")
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
@@ -622,7 +713,7 @@ def main():
     t0 = time.perf_counter()
     for i in range(a.steps):
         eng.profile_enable(profile and i < PROFILE_STEPS)
-        mid, glob, stats = step()
+        mid, glob, stats, gathered = step()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -633,6 +724,12 @@ def main():
         t = torch.tensor([elapsed], device=device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    say("%d timed steps done" % a.steps)
+    if a.dump_outputs and rank == 0:
+        # what a caller of the timed call receives: local-stage poses [B,10,15,3] f32, global poses [B,10,15,3] f64 (with N > 1
+        # also the all-gathered [N*B,10,15,3]), and the per-window L-BFGS stats of both stages ([2B]: local rows, then global)
+        dump_outputs(a.dump_outputs, dict(mid_local=mid, glob=glob, glob_all_ranks=gathered, **stats_arrays(stats_to_numpy(stats))))
+        say("outputs written to %s" % a.dump_outputs)
 
     # ---- side measurement (not `value`): the same workload in the faster arithmetic modes of the wide products
     other = {}
@@ -645,7 +742,7 @@ def main():
                 dist.barrier()
             t1 = time.perf_counter()
             for _ in range(a.steps):
-                m2, g2, s2 = step()
+                m2, g2, s2, _ = step()
             torch.cuda.synchronize()
             if world > 1:
                 dist.barrier()
@@ -958,7 +1055,7 @@ def main():
         import copy
         for wl_name, n_def in (("configs3", 65536), ("configs4", 12499)):
             a2 = copy.copy(a)
-            a2.workload, a2.precision, a2.dump, a2.emulate_ranks = wl_name, "bf16", None, 0
+            a2.workload, a2.precision, a2.dump, a2.dump_outputs, a2.emulate_ranks = wl_name, "bf16", None, None, 0
             a2.windows = a.windows or (max(64 * world, n_def // 16) if rehearsal else n_def)
             a2.steps, a2.warmup = max(2, min(a.steps, 5)), 1
             strong[wl_name] = run_sharded(a2, world, rank, device, rehearsal, sd_local, sd_global,
@@ -974,7 +1071,7 @@ def main():
         partition8 = {}
         for wl_name in ("configs3", "configs4"):
             a2 = copy.copy(a)
-            a2.workload, a2.precision, a2.dump, a2.emulate_ranks, a2.windows = wl_name, "bf16", None, 8, 0
+            a2.workload, a2.precision, a2.dump, a2.dump_outputs, a2.emulate_ranks, a2.windows = wl_name, "bf16", None, None, 8, 0
             a2.steps, a2.warmup = max(2, min(a.steps, 3)), 2
             partition8[wl_name] = run_sharded(a2, world, rank, device, rehearsal, sd_local, sd_global, "as the headline", emit=False)
 
@@ -1261,6 +1358,10 @@ def main():
             "cpu_baseline": cpu,
             "summary": summary,
         }
+        if not a.full:          # (a plain run measured none of them)
+            for k in ("other_precisions", "configs2", "configs3", "configs4", "partition8", "sequences_in_flight", "host_inclusive", "post",
+                      "lift", "train", "roofline", "cpu_baseline", "summary"):
+                del line[k]
         if a.full_record:
             with open(a.full_record, "w") as f:
                 json.dump(line, f, indent=1)

@@ -84,11 +84,11 @@ def test_two_rank_rehearsal_of_the_sharded_bench_legs_is_bitwise_the_emulated_sh
 
 
 def test_default_two_rank_line_carries_the_strong_scaling_legs():
-    """`bench.py --gpus 2` with default flags (what the driver runs with N > 1): the weak-scaling `value` of BASELINE configs[1]
+    """`bench.py --gpus 2 --full`: the weak-scaling `value` of BASELINE configs[1]
     PLUS, as side records of the same JSON line, configs[3] and configs[4] as ONE job each sharded over the two ranks (scaling
     "strong", ranks 2, the per-rank evaluation sums = the load-imbalance term of SURVEY.md 8e).  Two real ranks on the one card
     of the test box over gloo (GEM_BENCH_REHEARSAL=1; the rehearsal takes a sixteenth of the windows)."""
-    line = _run_bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--vae", "structured", "--cpu-windows", "0", "--no-profile"],
+    line = _run_bench(["--gpus", "2", "--full", "--steps", "2", "--warmup", "1", "--vae", "structured", "--cpu-windows", "0", "--no-profile"],
                       {"GEM_BENCH_REHEARSAL": "1"}, timeout=1500)
     assert line["n_gpus"] == 2 and line["scaling"] == "weak" and line["config"]["ranks"] == 2 and line["value"] > 0
     for key, n_windows in (("configs3", 65536 // 16), ("configs4", 12499 // 16)):
