@@ -8,8 +8,6 @@
 // split-K slabs, its output gradient leaves as bf16); large batches run every layer as a batched bf16 GEMM.
 // Reference semantics: ConvVAE.decode_to_bodypose (SeqConvVAE.py:131-140) + total_loss.backward() (optimizer.py:226-240,
 // 264-268), backward-DATA only (the VAE is frozen).
-#include <cstdlib>
-
 #include "gem_internal.h"
 #include "gemm_glds.h"
 #include "gemm_big.h"
@@ -127,40 +125,6 @@ static int launch_big(gem_handle* h, const Layer& L, int epi, const uint16_t* A,
     return 0;
 }
 
-// Mid-size batches in the evaluation rounds (round 5): the same 256 x 256 tile with the K range CUT so that the launch is one round of
-// ~one workgroup per CU -- 1536 rows: 6 x 10 tiles x 4 slices (forward), 6 x 8 x 5 (backward) = 240 workgroups of eight 64-deep K-steps
-// -- writing raw fp32 slabs that the consumer sums anyway (the tail while staging, lbfgs_advance while reading its gradient).  128
-// FLOP per byte moved L2 -> LDS instead of the 128 x 128 tile's 64: the fill rate (~30 B/clk/CU) that bounds the small kernel at these
-// sizes allows twice the rate.  Only with a device row count and a consumer that takes slabs; the two-lane mode (whose bitwise test
-// needs a batch and its halves to be cut alike) keeps the old kernels.
-constexpr int BIG_SPLIT_MIN_ROWS = 1024;
-static bool launch_big_split(gem_handle* h, const Layer& L, const uint16_t* A, int lda, int ldc, int M, hipStream_t s, const int* row_map,
-                             int m_max, int* n_split_out) {
-    Workspace& w = h->ws;
-    const int tiles = ((M + 255) / 256) * (L.N / 256), k_tiles = L.K / 64;
-    int sk = h->n_cu / tiles;
-    if (const char* fs = dev_env("GEM_BIG_SPLIT_SK")) sk = atoi(fs);          // developer override (A/B runs)
-    if (sk > k_tiles / 4) sk = k_tiles / 4;
-    if (sk > 8) sk = 8;
-    while (sk > 1 && (size_t)sk * M * ldc > w.splitk_elems) --sk;
-    if (sk < 2) return false;
-    big::Args a{};
-    a.A = A; a.W = L.wb_hi; a.bias = nullptr; a.C = w.splitk; a.zero16 = w.zero16;
-    a.m_dev = w.n_active; a.row_map = row_map;
-    a.lda = lda; a.ldc = ldc; a.M = M; a.N = L.N; a.K = L.K; a.m_min = 1; a.m_max = m_max;
-    a.tiles_per_split = (k_tiles + sk - 1) / sk;
-    a.n_split = (k_tiles + a.tiles_per_split - 1) / a.tiles_per_split;
-    a.slab_stride = (size_t)M * ldc;
-    static PerDeviceOnce once;
-    if (once.need(h->cfg.device))
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(big::gemm_big_kernel<4, 4, 4, 4, big::EPI_NONE, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    note_kernel(h, reinterpret_cast<const void*>(big::gemm_big_kernel<4, 4, 4, 4, big::EPI_NONE, false>));
-    hipLaunchKernelGGL((big::gemm_big_kernel<4, 4, 4, 4, big::EPI_NONE, false>), dim3(tiles * a.n_split), dim3(1024), 2 * (256 + 256) * 128, s, a);
-    if (hipGetLastError() != hipSuccess) return false;
-    *n_split_out = a.n_split;
-    return true;
-}
-
 // C = epi(conv/linear(A)) with bf16 operands.  `out_bf16`: activation / gradient for the next bf16 layer; otherwise fp32.
 // allow_split: small row counts cut K over several workgroups (fp32 slabs in ws.splitk); with `defer` the slabs are left to
 // the consumer (described in ws.deferred), otherwise a reduce pass applies the epilogue.
@@ -170,11 +134,7 @@ static int gemm_bf16a(gem_handle* h, const Layer& L, int epi, const uint16_t* A,
     if (M <= 0) return 0;
     if (L.K % 64 != 0 || L.N % 64 != 0 || !L.wb_hi) { set_error("gemm_bf16a: layer is not padded to 64 or has no bf16 weights"); return 1; }
     w.deferred = SlabSrc{};
-    // developer switch (round 6 A/B): the forward front product as 128 x 64 tiles (1) or 128 x 128 tiles (2) over the WHOLE of K, so
-    // that it hands the tail one bf16 activation instead of fp32 split-K slabs
-    const char* ffm = (family == 0 && out_bf16 && epi == EPI_BIAS_LRELU && L.taps == 1) ? dev_env("GEM_FRONT_FWD_MODE") : nullptr;
-    if (ffm && ffm[0] != '0') allow_split = false;
-    const bool bn128 = L.N % 128 == 0 && !(ffm && ffm[0] == '1');
+    const bool bn128 = L.N % 128 == 0;
     const int BN = bn128 ? 128 : 64;
     const int tiles = ((M + 127) / 128) * (L.N / BN);
     const int k_tiles = L.taps * (L.K / 64);
@@ -185,40 +145,12 @@ static int gemm_bf16a(gem_handle* h, const Layer& L, int epi, const uint16_t* A,
     a.lda = lda; a.ldc = ldc; a.M = M; a.N = L.N; a.K = L.K; a.T = h->T;
     a.n_split = 1; a.tiles_per_split = k_tiles; a.slab_stride = (size_t)M * ldc;
     // the front products at large batch: gemm_big.h takes the launches with >= BIG_MIN_ROWS rows (family 0 only)
-    static const bool no_big = dev_env("GEM_NO_BIG_GEMM") != nullptr;
-    static const int big_min = dev_env("GEM_BIG_MIN") ? atoi(dev_env("GEM_BIG_MIN")) : BIG_MIN_ROWS;          // developer override (A/B runs)
-    const bool use_big = family == 0 && !no_big && M >= big_min && big_fits(L, epi, out_bf16);
-    if (use_big) a.m_max = big_min;
-    // mid-size rounds: the K-cut one-round kernel (see launch_big_split); the consumer takes the slabs
-    // MEASURED AND NOT ADOPTED (round 5, tools/r05_exp5.sh, windows/s with the 128 x 128 kernel | with this): 1536 windows 182.7 | 175.6 k,
-    // 2052: 180.4 | 186.4 k, 3072: 229.5 | 227.4 k, 4092: 235.1 | 232.0 k, 768: 123.6 | 114.4 k -- the four-pass fp32 epilogue of a 256 x 256
-    // tile and twice the slab traffic eat what the better FLOP-per-byte ratio gives.  Off unless GEM_DEV=1 GEM_BIG_SPLIT=1.
-    static const bool no_big_split = dev_env("GEM_BIG_SPLIT") == nullptr;
-    static const int big_split_min = dev_env("GEM_BIG_SPLIT_MIN") ? atoi(dev_env("GEM_BIG_SPLIT_MIN")) : BIG_SPLIT_MIN_ROWS;
-    if (family == 0 && !no_big && !no_big_split && !use_big && h->lanes_min == 0 && w.dyn && defer && allow_split && L.taps == 1 && M >= big_split_min &&
-        L.N % 256 == 0 && L.K % 64 == 0 && (epi == EPI_NONE || epi == EPI_BIAS_LRELU)) {
-        Profile::Rec rec2;
-        const bool prof2 = h->prof.on;
-        if (prof2) {
-            GEM_HIP(hipEventCreate(&rec2.a)); GEM_HIP(hipEventCreate(&rec2.b));
-            rec2.family = family; rec2.flops = 2.0 * M * (double)L.N * L.K;
-            rec2.log_idx = w.cur_log; rec2.flops_per_window = 2.0 * (double)L.N * L.K;
-            GEM_HIP(hipEventRecord(rec2.a, s));
-        }
-        int ns = 0;
-        if (launch_big_split(h, L, A, lda, ldc, M, s, row_map, 0, &ns)) {
-            SlabSrc& d = w.deferred;
-            d.base = w.splitk; d.nslab = ns; d.stride = (size_t)M * ldc; d.dyn_W = 0; d.m_dev = w.n_active;
-            if (prof2) { GEM_HIP(hipEventRecord(rec2.b, s)); h->prof.recs.push_back(rec2); }
-            commit_kernel_names(h, prof2 ? family : -1);
-            return 0;
-        }
-    }
+    const bool use_big = family == 0 && M >= BIG_MIN_ROWS && big_fits(L, epi, out_bf16);
+    if (use_big) a.m_max = BIG_MIN_ROWS;
     if (allow_split && epi != EPI_MASK) {
         // fill the chip: about two workgroups per CU (the number co-resident with this kernel's 64 KB of LDS; measured at 768 ..
         // 3072 rows, tools/gemm_glds_bench split: the best cut of every shape) while every slice keeps >= 4 k-tiles and the slabs fit
         int sk = (2 * h->n_cu) / tiles;
-        if (const char* fs = dev_env("GEM_BF16_SK")) sk = atoi(fs);          // developer override (A/B runs)
         if (sk > k_tiles / 4) sk = k_tiles / 4;
         if (sk > 8) sk = 8;
         while (sk > 1 && (size_t)sk * a.slab_stride > w.splitk_elems) --sk;
@@ -242,7 +174,7 @@ static int gemm_bf16a(gem_handle* h, const Layer& L, int epi, const uint16_t* A,
     int rc = 1;
     if (use_big) {
         if (a.n_split != 1) { set_error("gemm_bf16a: the one-round kernel's row range must not be cut along K"); return 1; }
-        if (launch_big(h, L, epi, A, lda, C, ldc, M, s, row_map, w.dyn ? big_min : 1)) return 1;
+        if (launch_big(h, L, epi, A, lda, C, ldc, M, s, row_map, w.dyn ? BIG_MIN_ROWS : 1)) return 1;
     }
     if (use_big && !w.dyn) {
         rc = 0;                    // the row count is known here: the big kernel alone
@@ -291,10 +223,10 @@ bool bf16_rounds_take_slots_atomically(const gem_handle* h, int stage, int B) {
     // (no cap on B: one same-address atomic per window and round is spread over the advance kernel's duration -- 8192 windows: 289.0 k
     // against 282.3 k windows/s with compact_kernel's 12 us single-workgroup scan per round; 6144: +0.4 %)
     (void)B;
-    if (h->precision != GEM_PRECISION_BF16 || dev_env("GEM_NO_ATOMIC_COMPACT")) return false;
+    if (h->precision != GEM_PRECISION_BF16) return false;
     const char* t16_env = dev_env("GEM_TAIL16");
     if (!net.tb_stream || net.tail_start != 1 || dev_env("GEM_BATCHED_NARROW") || (t16_env && t16_env[0] == '0')) return false;
-    return net.front.wb_hi && net.dec.size() > 1 && !dev_env("GEM_NO_FRONT_BF16");
+    return net.front.wb_hi && net.dec.size() > 1;
 }
 
 // One evaluation in the bf16 decoder mode: decodes ws.trial_b, leaves the pose in ws.dec_act.back() (fp32), the energies in
@@ -303,21 +235,18 @@ int evaluate_bf16(gem_handle* h, int stage, int B, const EnergyArgs& ea_in, hipS
     StageNet& net = h->net[stage];
     Workspace& w = h->ws;
     const int T = h->T, rows = B * T, n_dec = (int)net.dec.size();
-    static const bool force_tail = dev_env("GEM_FORCE_TAIL") != nullptr;
     const int tail_g = T <= 16 ? 16 / T : 1;
     const int tail_wgs = (B + tail_g - 1) / tail_g;
     // Three ways to run the narrow layers + energies: the bf16 multi-window tail (tail_bf16.hip: 1 .. 8 windows per workgroup, one
     // launch), the fp32 one-window tail (tail.hip; GEM_TAIL16=0 or networks the bf16 tail does not cover), or batched bf16 GEMMs + the
-    // stand-alone energy kernel (networks the tails do not cover).  GEM_TAIL16=1 / 0 forces / forbids the first (GEM_DEV=1).
+    // stand-alone energy kernel (networks the tails do not cover).  GEM_TAIL16=0 forbids the first (GEM_DEV=1).
     const char* t16_env = dev_env("GEM_TAIL16");       // (read per call: the tests flip it inside one process)
     const bool batched_narrow = dev_env("GEM_BATCHED_NARROW") != nullptr;      // neither tail: every layer a batched GEMM (A/B runs, tests)
     // (round 3 sent batches below 256 windows to the fp32 one-window tail; with ONE row tile per workgroup -- one window of ten frames,
     // every window its own CU like the fp32 tail, round 4 -- the bf16 tail wins at every size: 60 / 120 / 240 windows 14.9 / 26.1 /
     // 47.8 k windows/s against 11.1 / 20.6 / 38.7 k)
-    const int t16_min = 1;
-    const bool use_tail16 = net.tb_stream && net.tail_start >= 1 && !batched_narrow && !(t16_env && t16_env[0] == '0') &&
-                            (B >= t16_min || (t16_env && t16_env[0] == '1'));
-    const bool use_tail = !use_tail16 && !batched_narrow && net.tail_start >= 1 && (tail_wgs <= 5 * h->n_cu || force_tail);
+    const bool use_tail16 = net.tb_stream && net.tail_start >= 1 && !batched_narrow && !(t16_env && t16_env[0] == '0');
+    const bool use_tail = !use_tail16 && !batched_narrow && net.tail_start >= 1 && tail_wgs <= 5 * h->n_cu;
     const int* perm = w.dyn ? w.perm : nullptr;
     if (w.next_count && !(use_tail16 && net.front.wb_hi && net.tail_start == 1)) {
         set_error("evaluate_bf16: slots are handed out by lbfgs_advance but this evaluation does not run front products + fused tail");
@@ -326,8 +255,7 @@ int evaluate_bf16(gem_handle* h, int stage, int B, const EnergyArgs& ea_in, hipS
     w.grad_slab = SlabSrc{};
     // decoder_input o conv 0 as ONE product where the weights were composed (compose_front in gem_api.hip), else
     // decoder_input: [B, Dp] x [Dp, T*topp] -> h0 [B*T, topp] bf16 (rows of finished windows are skipped through perm)
-    static const bool no_front = dev_env("GEM_NO_FRONT_BF16") != nullptr;          // developer override (A/B runs)
-    const bool front = net.front.wb_hi && n_dec > 1 && !no_front && ((!use_tail && !use_tail16) || net.tail_start == 1);
+    const bool front = net.front.wb_hi && n_dec > 1 && ((!use_tail && !use_tail16) || net.tail_start == 1);
     const uint16_t* in = w.h0_b;
     EnergyArgs ea = ea_in;
     int back_from;                     // first layer of the batched backward chain
@@ -368,7 +296,6 @@ int evaluate_bf16(gem_handle* h, int stage, int B, const EnergyArgs& ea_in, hipS
         ta.e = ea;
         if (launch_tail_bf16(h, ta, tb_lds, s)) return 1;
         if (forward_only) return 0;
-        if (record_mid(h, s)) return 1;
         back_from = st - 1;
         gin = w.dec_grad_b[st];
     } else
@@ -408,7 +335,6 @@ int evaluate_bf16(gem_handle* h, int stage, int B, const EnergyArgs& ea_in, hipS
         ta.e = ea;
         if (launch_tail(h, ta, net.tail_lds, s)) return 1;
         if (forward_only) return 0;
-        if (record_mid(h, s)) return 1;
         back_from = st - 1;
         gin = w.dec_grad_b[st];
     } else {
@@ -432,7 +358,6 @@ int evaluate_bf16(gem_handle* h, int stage, int B, const EnergyArgs& ea_in, hipS
         ea.Xp = w.dec_act.back();
         ea.dXp_b = w.dXp_b;
         if (launch_energy(h, ea, B, s)) return 1;
-        if (record_mid(h, s)) return 1;
         back_from = n_dec - 1;
         gin = w.dXp_b;
     }

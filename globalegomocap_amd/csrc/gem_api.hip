@@ -262,7 +262,6 @@ int gem_create(const gem_config* cfg, gem_handle** out) {
     h->D = cfg->latent_dim; h->Dp = pad64(cfg->latent_dim);
     h->top = cfg->hidden[cfg->n_hidden - 1]; h->topp = pad64(h->top);
     GEM_HIP(hipDeviceGetAttribute(&h->n_cu, hipDeviceAttributeMultiprocessorCount, cfg->device));
-    if (const char* lm = dev_env("GEM_LANES_MIN")) h->lanes_min = atoi(lm);          // developer override of gem_set_lanes' default (A/B runs)
     Workspace& w = h->ws;
     const int B = cfg->max_windows, T = h->T;
     const size_t rows = (size_t)B * T;
@@ -324,8 +323,6 @@ int gem_create(const gem_config* cfg, gem_handle** out) {
     if (dev_alloc(w.allocs, &w.pose_b, rows * h->C)) return 1;
     if (dev_alloc(w.allocs, &w.n_log, (size_t)N_LOG)) return 1;
     if (dev_alloc(w.allocs, &w.perm2, (size_t)B) || dev_alloc(w.allocs, &w.slot_of2, (size_t)B)) return 1;
-    if (dev_alloc(w.allocs, &w.grid_bar, 1)) return 1;
-    GEM_HIP(hipMemset(w.grid_bar, 0, sizeof(unsigned)));
     if (dev_alloc(w.allocs, &w.perm, (size_t)B) || dev_alloc(w.allocs, &w.slot_of, (size_t)B) || dev_alloc(w.allocs, &w.n_active, 2))
         return 1;
     w.perm_home = w.perm; w.slot_of_home = w.slot_of; w.n_active_home = w.n_active;
@@ -361,13 +358,6 @@ void gem_destroy(gem_handle* h) {
         }
     }
     drop_graphs(h);
-    if (h->lane2) { gem_destroy(h->lane2); h->lane2 = nullptr; }          // (its nets own nothing: the weights are freed below)
-    if (h->lane_stream) (void)hipStreamDestroy(h->lane_stream);
-    if (h->lane_stream_a) (void)hipStreamDestroy(h->lane_stream_a);
-    if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
-    if (h->ev_join) (void)hipEventDestroy(h->ev_join);
-    if (h->ev_join_a) (void)hipEventDestroy(h->ev_join_a);
-    for (hipEvent_t e : h->ev_pool) (void)hipEventDestroy(e);
     free_all(h->net[0].allocs);
     free_all(h->net[1].allocs);
     free_all(h->ws.allocs);
@@ -400,7 +390,6 @@ int gem_load_vae(gem_handle* h, int stage, int n_blobs, const float* const* blob
     StageNet& net = h->net[stage];
     if (net.loaded) GEM_HIP(hipDeviceSynchronize());      // reloading: launches that still read the old weights must be done
     drop_graphs(h);                                       // captured calls hold pointers to the weights freed below
-    ++h->cfg_gen;                                         // a second lane mirrors the new StageNet on its next call
     free_all(net.allocs);
     net = StageNet();
     int bi = 0;
@@ -471,11 +460,10 @@ int gem_load_vae(gem_handle* h, int stage, int n_blobs, const float* const* blob
     if (add_dec(c.hidden[0], C, false, false)) return 1;
     // fuse as many trailing decoder convs as fit the LDS of one CU (tail.hip); GEM_NO_TAIL=1 disables it
     net.tail_start = -1;
-    // The chain may start at conv 0 (GEM_TAIL_START=0), but its 512x256 weights (3 MB per workgroup and round from
-    // L2) cost more than the batched GEMM they replace: 13.4 k vs 14.3 k windows/s at 240 windows.
-    const int first = dev_env("GEM_TAIL_START") ? atoi(dev_env("GEM_TAIL_START")) : 1;
+    // The chain starts at conv 1 at the earliest: from conv 0, its 512x256 weights (3 MB per workgroup and round from L2) cost
+    // more than the batched GEMM they replace (measured: 13.4 k vs 14.3 k windows/s at 240 windows).
     if (!dev_env("GEM_NO_TAIL"))
-        for (int st = first; st < (int)net.dec.size(); ++st) {
+        for (int st = 1; st < (int)net.dec.size(); ++st) {
             const size_t bytes = plan_tail(net.dec, st, T, h->J, nullptr);
             if (bytes && bytes <= 160 * 1024) { net.tail_start = st; net.tail_lds = bytes; break; }
         }
@@ -582,17 +570,16 @@ static int evaluate(gem_handle* h, int stage, int B, const float* zp, const Ener
     Workspace& w = h->ws;
     // The fused tail trades throughput for latency (~45 us per workgroup whatever the batch, one or two workgroups per CU at a
     // time): measured against the batched GEMMs for the narrow layers it wins up to ten workgroups per CU in its two-per-CU
-    // shape, five otherwise (tail_cap_workgroups, tail.hip, has the table).  GEM_FORCE_TAIL=1 keeps it on for any batch.
+    // shape, five otherwise (tail_cap_workgroups, tail.hip, has the table).
     if (h->precision == GEM_PRECISION_BF16) return evaluate_bf16(h, stage, B, ea, s, forward_only);      // zp == ws.trial, mirrored in ws.trial_b
-    static const bool force_tail = dev_env("GEM_FORCE_TAIL") != nullptr;
     const int tail_g = h->T <= 16 ? 16 / h->T : 1;
     const int tail_wgs = (B + tail_g - 1) / tail_g;
     const int tail_cap = net.tail_start >= 0 ? tail_cap_workgroups(h, net.dec, net.tail_start) : 0;
-    if (net.tail_start < 0 || (tail_wgs > tail_cap && !force_tail)) {
+    if (net.tail_start < 0 || tail_wgs > tail_cap) {
         if (w.next_count) { set_error("evaluate: the batched layers need compact_kernel's slot order (stage_begin chose otherwise)"); return 1; }
         if (decoder_forward(h, stage, B, zp, s)) return 1;
         if (forward_only) return 0;
-        if (launch_energy(h, ea, B, s) || record_mid(h, s)) return 1;
+        if (launch_energy(h, ea, B, s)) return 1;
         return decoder_backward(h, stage, B, s, (int)net.dec.size() - 1, w.dXp);
     }
     // wide layers as batched GEMMs, the narrow tail + energy + its adjoints in one kernel
@@ -625,7 +612,7 @@ static int evaluate(gem_handle* h, int stage, int B, const float* zp, const Ener
     TailArgs ta;
     const size_t tail_lds = plan_tail_for(h, net.dec, st, tail_wgs, &ta);
     ta.B = B; ta.forward_only = forward_only ? 1 : 0; ta.dbg_ts = nullptr;
-    ta.in_slab = in_slab; ta.in_bias = front ? net.front.bias : (st > 0 ? net.dec[st - 1].bias : nullptr);
+    ta.in_slab = in_slab; ta.in_bias = front ? net.front.bias : net.dec[st - 1].bias;
     ta.in_bias_ld = front ? net.dec[0].N : 0;
     for (int i = 0; i < ta.n; ++i) {
         const Layer& f = net.dec[st + i];
@@ -633,18 +620,15 @@ static int evaluate(gem_handle* h, int stage, int B, const float* zp, const Ener
         ta.fwd[i] = TailLayerDev{f.w4, f.bias, f.K, f.N};
         ta.bwd[i] = TailLayerDev{g.w4, nullptr, g.K, g.N};
     }
-    ta.a_in = st > 0 ? w.dec_act[st - 1] : w.h0; ta.g_out = w.dec_grad[st]; ta.g_out_b = nullptr; ta.Xp = (w.dyn && !forward_only) ? nullptr : w.dec_act.back();     // the pose is only read back outside the rounds
+    ta.a_in = w.dec_act[st - 1]; ta.g_out = w.dec_grad[st]; ta.g_out_b = nullptr; ta.Xp = (w.dyn && !forward_only) ? nullptr : w.dec_act.back();     // the pose is only read back outside the rounds
     ta.e = ea;
     if (launch_tail(h, ta, tail_lds, s)) return 1;
     if (forward_only) return 0;
-    if (record_mid(h, s)) return 1;
     if (front) {
         // dE/dz = Wf^T . (gradient w.r.t. the pre-activation of conv 0): replaces the conv adjoint, its reduce pass and the
         // decoder_input backward product; in the rounds lbfgs_advance sums the slabs of this product itself (its bias is zero)
         w.defer_reduce = w.dyn;
-        w.fuse_lbfgs = w.fuse_lbfgs_req;          // (experiment: THIS launch may carry lbfgs_advance behind a device-wide barrier)
         const int rc = launch_gemm(h, net.front_bwd, EPI_BIAS, w.dec_grad[st], net.front_bwd.K, nullptr, w.dz, h->Dp, B, h->T, s, 0);
-        w.fuse_lbfgs = nullptr;
         w.grad_slab = w.defer_reduce ? w.deferred : SlabSrc{};
         w.defer_reduce = false;
         return rc;
@@ -652,9 +636,8 @@ static int evaluate(gem_handle* h, int stage, int B, const float* zp, const Ener
     return decoder_backward(h, stage, B, s, st - 1, w.dec_grad[st]);
 }
 
-// One stage of B windows as three host steps, so that two half-batches ("lanes", below) can be driven round by round from one
-// loop: begin (encode, initial state), round r (one evaluation + one L-BFGS advance for every window still iterating), finish
-// (decode the result).  optimize_stage_impl runs them back to back.
+// One stage of B windows as three host steps: begin (encode, initial state), round r (one evaluation + one L-BFGS advance for
+// every window still iterating), finish (decode the result).  optimize_stage_impl runs them back to back.
 struct StageRun {
     gem_handle* h = nullptr;
     int stage = 0, B = 0;
@@ -695,9 +678,7 @@ static int stage_begin(StageRun& r) {
     if (launch_lbfgs_init(h, B, r.opt, s)) return 1;
     // Rounds run on the windows that are still iterating: after every advance they are re-packed to the front
     // (perm / n_active on the device) and the kernels of the next round read their row count from there.
-    static const bool no_compact = dev_env("GEM_NO_COMPACT") != nullptr;
     compaction_home(w);
-    r.atomic_slots = false;
     // The active windows are re-packed between the rounds: inside the decoder_input forward launch of the next round (one sequence in
     // fp32: gemm_rows.h, FUSE), by lbfgs_advance handing out the next round's slots itself (atomic_slots: every path whose kernels
     // address rows through perm / slot_of only and do not depend on the slot ORDER -- the bf16 fused path, and the fp32 composed front
@@ -707,23 +688,20 @@ static int stage_begin(StageRun& r) {
     const Layer& first_ = front_ ? net_.front : net_.dec_in;
     const int tail_g_ = h->T <= 16 ? 16 / h->T : 1;
     const bool tail_path_ = net_.tail_start >= 0 && (B + tail_g_ - 1) / tail_g_ <= tail_cap_workgroups(h, net_.dec, net_.tail_start);
-    const bool fuse_ = !no_compact && tail_path_ && rows_can_fuse_compaction(h, first_, h->Dp, first_.N, B, /*slabs=*/front_);
-    if (!no_compact) {
-        r.atomic_slots = bf16_rounds_take_slots_atomically(h, stage, B) ||
-                         (h->precision == GEM_PRECISION_F32 && front_ && tail_path_ && !fuse_ && !dev_env("GEM_NO_ATOMIC_COMPACT"));
-        if (r.atomic_slots) {
-            // rounds + 2 consecutive n_log entries: round 0's count (written by the compaction below), then one zeroed counter per round
-            if ((w.log_pos % N_LOG) + r.rounds + 2 > N_LOG) w.log_pos += N_LOG - (w.log_pos % N_LOG);
-            r.log0 = w.log_pos;
-        }
-        // identity: every window takes part in round 0 (logs B at n_log[log0]); with atomic slots the kernel also zeroes the rounds' counters
-        if (launch_compact(h, B, 1, s, r.atomic_slots ? r.rounds + 1 : 0)) return 1;
-        if (r.atomic_slots) w.log_pos = r.log0 + r.rounds + 2;
-        w.dyn = true;
+    const bool fuse_ = tail_path_ && rows_can_fuse_compaction(h, first_, h->Dp, first_.N, B, /*slabs=*/front_);
+    r.atomic_slots = bf16_rounds_take_slots_atomically(h, stage, B) ||
+                     (h->precision == GEM_PRECISION_F32 && front_ && tail_path_ && !fuse_);
+    if (r.atomic_slots) {
+        // rounds + 2 consecutive n_log entries: round 0's count (written by the compaction below), then one zeroed counter per round
+        if ((w.log_pos % N_LOG) + r.rounds + 2 > N_LOG) w.log_pos += N_LOG - (w.log_pos % N_LOG);
+        r.log0 = w.log_pos;
     }
+    // identity: every window takes part in round 0 (logs B at n_log[log0]); with atomic slots the kernel also zeroes the rounds' counters
+    if (launch_compact(h, B, 1, s, r.atomic_slots ? r.rounds + 1 : 0)) return 1;
+    if (r.atomic_slots) w.log_pos = r.log0 + r.rounds + 2;
+    w.dyn = true;
     // texel-block cache of the reprojection term: valid for this stage's heat-maps / windows only
-    static const bool no_tex = dev_env("GEM_NO_TEXCACHE") != nullptr;
-    w.tex_on = !no_tex && h->tex_cache && w.tex_key && r.wt.reproj != 0.0;
+    w.tex_on = h->tex_cache && w.tex_key && r.wt.reproj != 0.0;
     // (a fill KERNEL, not hipMemsetAsync: inside a captured graph a memset node was seen to run out of order with the kernels around it
     // once two graphs replayed side by side on two streams -- round 5, ROCm 7.2; a late invalidation here would hand the stage texels
     // of the previous contents of the heat-maps)
@@ -732,7 +710,7 @@ static int stage_begin(StageRun& r) {
     w.tex_on = false;
     // closure values of this stage, one row per round (0xFF bytes = NaN: "window took no evaluation in this round")
     if (launch_fill_u32(reinterpret_cast<uint32_t*>(w.trace), 0xFFFFFFFFu, (size_t)TRACE_ROUNDS * w.Bmax * 2, s)) return 1;
-    r.fuse = w.dyn && fuse_;
+    r.fuse = fuse_;
     return 0;
 }
 
@@ -742,8 +720,7 @@ static int stage_round(StageRun& r, int k) {
     if (r.B == 0) return 0;
     int rc = 0;
     w.round = k;
-    // (dyn / tex state of THIS lane's workspace: another lane may have run in between)
-    if (w.dyn && r.atomic_slots) {
+    if (r.atomic_slots) {
         // this round's set and the set lbfgs_advance fills for the next one
         int* cnt = w.n_log + (r.log0 + k) % N_LOG;
         w.perm = (k & 1) ? w.perm2 : w.perm_home;       w.next_perm = (k & 1) ? w.perm_home : w.perm2;
@@ -752,7 +729,7 @@ static int stage_round(StageRun& r, int k) {
         w.cur_log = r.log0 + k;
         r.ea.n_dev = w.n_active; r.ea.perm = w.perm;
     } else
-    if (k > 0 && w.dyn) {
+    if (k > 0) {
         if (r.fuse) {
             w.fuse_compact = true;
             w.fuse_log = w.n_log + (w.log_pos % N_LOG);
@@ -761,19 +738,9 @@ static int stage_round(StageRun& r, int k) {
             rc = launch_compact(h, r.B, 0, r.s);
         }
     }
-    // (experiment, GEM_DEV=1 GEM_FUSE_BWD_LBFGS=1: the backward front product carries the advance behind a device-wide barrier)
-    const bool fuse_exp = dev_env("GEM_FUSE_BWD_LBFGS") != nullptr;          // (read per round: a test flips it inside one process)
-    w.lbfgs_fused_done = false;
-    w.fuse_lbfgs_req = (fuse_exp && w.dyn && r.fuse && !h->graphs_on && !h->prof.on && h->precision == GEM_PRECISION_F32) ? &r.opt : nullptr;
     rc = rc || evaluate(h, r.stage, r.B, w.trial, r.ea, r.s);
-    w.fuse_lbfgs_req = nullptr;
-    if (!rc && !w.lbfgs_fused_done) rc = launch_lbfgs_advance(h, r.B, r.opt, r.s);
-    w.lbfgs_fused_done = false;
+    if (!rc) rc = launch_lbfgs_advance(h, r.B, r.opt, r.s);
     if (w.fuse_compact) { set_error("optimize: the fused compaction was not picked up"); rc = 1; w.fuse_compact = false; }
-    if (w.mid_event) {          // (no evaluation path picked the half-round marker up: record it now rather than never)
-        GEM_HIP(hipEventRecord(w.mid_event, r.s));
-        w.mid_event = nullptr;
-    }
     w.round = -1;
     return rc;
 }
@@ -806,7 +773,7 @@ static int optimize_stage_impl(gem_handle* h, int stage, int B, const float* d_p
     return stage_finish(r);
 }
 
-// ---- both stages of the window loop for one lane (optimizer.py:370-423), as host steps around the stage rounds ---------------
+// ---- both stages of the window loop (optimizer.py:370-423), as host steps around the stage rounds ---------------------------
 struct WindowsRun {
     gem_handle* h = nullptr;
     int B = 0;
@@ -847,7 +814,7 @@ static int windows_end(WindowsRun& r) {
     if (stage_finish(r.st)) return 1;
     return launch_to_global(h->ws.pose_b, r.cams, r.frame0, r.global, r.B, h->T, h->J, r.s);
 }
-static void windows_abort(WindowsRun& r) { r.h->ws.round = -1; r.h->ws.dyn = false; r.h->ws.mid_event = nullptr; compaction_home(r.h->ws); }
+static void windows_abort(WindowsRun& r) { r.h->ws.round = -1; r.h->ws.dyn = false; compaction_home(r.h->ws); }
 
 static int windows_single(WindowsRun& r) {
     int rc = windows_begin_local(r);
@@ -859,92 +826,6 @@ static int windows_single(WindowsRun& r) {
     return rc;
 }
 
-// ---- two lanes --------------------------------------------------------------------------------------------------------------
-// Windows are independent (optimizer.py:370), so a large batch can run as two half-batches on two streams, shifted by HALF an
-// evaluation round: while lane A runs its backward product and its HBM-bound L-BFGS advance, lane B runs its forward product and
-// its fused tail, and vice versa -- the memory-bound kernel of one lane shares the machine with the matrix-bound kernels of the
-// other instead of owning it alone.  The shift is enforced, not hoped for: every round of a lane waits for the event the other
-// lane records behind its tail kernel (B's round r for A's tail of round r, A's round r+1 for B's tail of round r), so the two
-// tails never run together and the lanes cannot drift back into step.  Inside a captured graph the events become edges between
-// the two chains.  Each lane has its own workspace (a second handle that shares the weights); a window's result does not depend
-// on which other windows share its batch as long as no product is cut along K (lanes are used from 4352 windows on, where
-// neither the full batch nor its halves are): bitwise the single-lane result (tests/test_hip_full_size.py).
-static int ensure_lane(gem_handle* h, int B_lane) {
-    if (h->lane2 && h->lane2->ws.Bmax >= B_lane) return 0;
-    if (h->lane2) { GEM_HIP(hipDeviceSynchronize()); gem_destroy(h->lane2); h->lane2 = nullptr; }
-    h->lane_gen = 0;                            // a fresh lane has mirrored nothing yet: the next sync_lane copies nets, precision, texel cache
-    gem_config cfg = h->cfg;
-    cfg.max_windows = std::max(B_lane, (h->ws.Bmax + 1) / 2 + 8);
-    gem_handle* l = nullptr;
-    if (gem_create(&cfg, &l)) return 1;
-    h->lane2 = l;
-    if (!h->lane_stream) GEM_HIP(hipStreamCreateWithFlags(&h->lane_stream, hipStreamNonBlocking));
-    if (!h->lane_stream_a) GEM_HIP(hipStreamCreateWithFlags(&h->lane_stream_a, hipStreamNonBlocking));
-    if (!h->ev_fork) {
-        GEM_HIP(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
-        GEM_HIP(hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
-        GEM_HIP(hipEventCreateWithFlags(&h->ev_join_a, hipEventDisableTiming));
-    }
-    return 0;
-}
-static void sync_lane(gem_handle* h) {          // the lane evaluates the same networks with the same settings (weights are shared, not copied)
-    gem_handle* l = h->lane2;
-    l->prof.on = false;
-    if (h->lane_gen == h->cfg_gen) return;      // nothing loaded or switched since the last two-lane call (incl. every graph replay)
-    h->lane_gen = h->cfg_gen;
-    for (int st = 0; st < 2; ++st) {
-        l->net[st] = h->net[st];
-        l->net[st].allocs.clear();              // owned by h
-    }
-    l->precision = h->precision; l->tex_cache = h->tex_cache; l->prof.on = false;
-}
-static hipEvent_t lane_event(gem_handle* h, size_t i) {
-    while (h->ev_pool.size() <= i) {
-        hipEvent_t e = nullptr;
-        if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return nullptr;
-        h->ev_pool.push_back(e);
-    }
-    return h->ev_pool[i];
-}
-
-static int windows_dual(WindowsRun& a, WindowsRun& b, gem_handle* h, hipStream_t caller) {
-    hipStream_t sa = a.s, sb = b.s;
-    GEM_HIP(hipEventRecord(h->ev_fork, caller));
-    if (sa != caller) GEM_HIP(hipStreamWaitEvent(sa, h->ev_fork, 0));
-    GEM_HIP(hipStreamWaitEvent(sb, h->ev_fork, 0));
-    int rc = windows_begin_local(a) || windows_begin_local(b);
-    size_t ev = 0;
-    hipEvent_t last_b = nullptr;
-    // (GEM_DEV=1 GEM_LANES_FREE=1, A/B runs: the two lanes run free on their streams, no half-round lock)
-    const bool free_run = dev_env("GEM_LANES_FREE") != nullptr;
-    auto rounds = [&]() {
-        for (int k = 0; k < a.st.rounds && !rc; ++k) {
-            if (free_run) {
-                rc = rc || stage_round(a.st, k) || stage_round(b.st, k);
-                continue;
-            }
-            hipEvent_t ea = lane_event(h, ev++), eb = lane_event(h, ev++);
-            if (!ea || !eb) { set_error("optimize: hipEventCreate failed"); rc = 1; break; }
-            if (last_b) rc = rc || !hip_ok(hipStreamWaitEvent(sa, last_b, 0), "hipStreamWaitEvent");
-            a.h->ws.mid_event = ea;
-            rc = rc || stage_round(a.st, k);
-            rc = rc || !hip_ok(hipStreamWaitEvent(sb, ea, 0), "hipStreamWaitEvent");
-            b.h->ws.mid_event = eb;
-            rc = rc || stage_round(b.st, k);
-            last_b = eb;
-        }
-    };
-    rounds();
-    rc = rc || windows_begin_global(a) || windows_begin_global(b);
-    rounds();
-    rc = rc || windows_end(a) || windows_end(b);
-    if (rc) { windows_abort(a); windows_abort(b); }
-    // join: the caller's stream continues when both lanes are done (also on an error: the capture, if any, must see the join)
-    if (hipEventRecord(h->ev_join, sb) != hipSuccess || hipStreamWaitEvent(caller, h->ev_join, 0) != hipSuccess) rc = 1;
-    if (sa != caller && (hipEventRecord(h->ev_join_a, sa) != hipSuccess || hipStreamWaitEvent(caller, h->ev_join_a, 0) != hipSuccess)) rc = 1;
-    return rc;
-}
-
 // ---- hipGraph replay of a whole call ------------------------------------------------------------------------------------
 // An optimisation call is a fixed sequence of ~700 launches whose grids and arguments do not depend on the data (row counts
 // live on the device, finished windows are skipped inside the kernels), i.e. it is capture-safe as it stands.  With graphs
@@ -952,8 +833,7 @@ static int windows_dual(WindowsRun& a, WindowsRun& b, gem_handle* h, hipStream_t
 // the second one is captured into a hipGraph and instantiated, every later one is a single hipGraphLaunch: the host cost of a
 // call drops from ~3 ms of launches to one launch (BASELINE configs[4]; several sequences in flight from one host thread).
 static bool same_key(const GraphKey& a, const GraphKey& b) {
-    if (a.kind != b.kind || a.stage != b.stage || a.B != b.B || a.precision != b.precision || a.stream != b.stream || a.tex_cache != b.tex_cache ||
-        a.lanes != b.lanes)
+    if (a.kind != b.kind || a.stage != b.stage || a.B != b.B || a.precision != b.precision || a.stream != b.stream || a.tex_cache != b.tex_cache)
         return false;
     for (int i = 0; i < 12; ++i)
         if (a.ptr[i] != b.ptr[i]) return false;
@@ -1057,7 +937,6 @@ int gem_optimize_stage(gem_handle* h, int stage, int B, const float* d_pose_in, 
     if (!d_pose_in || !d_mean_bone || !wt || !opt || !d_pose_out) { set_error("gem_optimize_stage: null argument"); return 1; }
     GraphKey key;
     key.kind = 1; key.stage = stage; key.B = B; key.precision = h->precision; key.stream = stream; key.tex_cache = h->tex_cache;
-    h->last_split = 0;
     const void* ptrs[] = {d_pose_in, d_heat, d_frame0, d_mean_bone, d_eps, d_pose_out, d_stats};
     for (int i = 0; i < 7; ++i) key.ptr[i] = ptrs[i];
     key.w[0] = *wt; key.opt = *opt;
@@ -1083,33 +962,12 @@ int gem_optimize_windows(gem_handle* h, int B, const float* d_local_pose, const 
     const void* ptrs[] = {d_local_pose, d_cams, d_heat, d_frame0, d_mean_bone, d_eps_local, d_eps_global, d_mid_local, d_global, d_stats};
     for (int i = 0; i < 10; ++i) key.ptr[i] = ptrs[i];
     key.w[0] = *w_local; key.w[1] = *w_global; key.opt = *opt;
-    // two lanes (windows_dual above) from lanes_min windows on; not while event profiling is on (the per-kernel timings would be
-    // those of kernels sharing the machine)
-    // (bf16 decoder mode only: that is where the products' K cuts were checked to be the same for a batch and its halves)
-    const bool dual = h->lanes_min > 0 && B >= h->lanes_min && !h->prof.on && h->precision == GEM_PRECISION_BF16;
-    const int BA = dual ? ((B + 1) / 2 + 7) / 8 * 8 : B;        // whole tail workgroups (8 windows) in the first lane
-    if (dual) {
-        if (ensure_lane(h, B - BA > BA ? B - BA : BA)) return 1;
-        sync_lane(h);
-    }
-    key.lanes = dual ? 2 : 1;
-    h->last_split = dual ? BA : 0;
     return run_graphed(h, key, s, [&]() -> int {
         WindowsRun a;
-        a.h = h; a.B = BA; a.local_pose = d_local_pose; a.cams = d_cams; a.heat = d_heat; a.frame0 = d_frame0; a.mean_bone = d_mean_bone;
+        a.h = h; a.B = B; a.local_pose = d_local_pose; a.cams = d_cams; a.heat = d_heat; a.frame0 = d_frame0; a.mean_bone = d_mean_bone;
         a.eps_local = d_eps_local; a.eps_global = d_eps_global; a.w_local = *w_local; a.w_global = *w_global; a.opt = *opt;
         a.mid_local = d_mid_local; a.global = d_global; a.stats_local = d_stats; a.stats_global = d_stats ? d_stats + B : nullptr; a.s = s;
-        if (!dual) return windows_single(a);
-        // lane A: the caller's stream, unless that is the legacy default stream -- its implicit synchronisation with every
-        // blocking stream of the process would sit between the two lanes' kernels (measured: 39.6 instead of 32.0 ms per
-        // 8196-window step as soon as other streams exist); then a private non-blocking stream, forked and joined by events
-        a.s = s ? s : h->lane_stream_a;
-        WindowsRun b = a;
-        b.h = h->lane2; b.B = B - BA; b.frame0 = d_frame0 + BA; b.mean_bone = d_mean_bone + (size_t)BA * h->J;
-        b.eps_local = d_eps_local ? d_eps_local + (size_t)BA * h->D : nullptr; b.eps_global = d_eps_global ? d_eps_global + (size_t)BA * h->D : nullptr;
-        b.mid_local = d_mid_local ? d_mid_local + (size_t)BA * h->T * h->C : nullptr; b.global = d_global + (size_t)BA * h->T * h->C;
-        b.stats_local = d_stats ? d_stats + BA : nullptr; b.stats_global = d_stats ? d_stats + B + BA : nullptr; b.s = h->lane_stream;
-        return windows_dual(a, b, h, s);
+        return windows_single(a);
     });
 }
 
@@ -1119,20 +977,14 @@ int gem_read_trace(gem_handle* h, int B, int n_rounds, double* d_out, void* stre
     }
     GEM_HIP(hipSetDevice(h->cfg.device));
     if (B == 0 || n_rounds == 0) return 0;
-    // (after a two-lane gem_optimize_windows call the windows [last_split, B) live in the second lane's workspace)
-    const int BA = (h->last_split > 0 && h->lane2 && h->last_split < B) ? h->last_split : B;
     GEM_HIP(hipMemcpy2DAsync(d_out, (size_t)B * sizeof(double), h->ws.trace, (size_t)h->ws.Bmax * sizeof(double),
-                             (size_t)BA * sizeof(double), (size_t)n_rounds, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    if (BA < B)
-        GEM_HIP(hipMemcpy2DAsync(d_out + BA, (size_t)B * sizeof(double), h->lane2->ws.trace, (size_t)h->lane2->ws.Bmax * sizeof(double),
-                                 (size_t)(B - BA) * sizeof(double), (size_t)n_rounds, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+                             (size_t)B * sizeof(double), (size_t)n_rounds, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return 0;
 }
 
 int gem_set_texel_cache(gem_handle* h, int on) {
     if (!h) { set_error("gem_set_texel_cache: null handle"); return 1; }
     h->tex_cache = on != 0;
-    ++h->cfg_gen;
     return 0;
 }
 
@@ -1166,16 +1018,15 @@ int gem_graph_stats(gem_handle* h, int64_t* n_captures, int64_t* n_replays) {
     return 0;
 }
 
+// accepted for compatibility: every call runs as one lane (include/gem_hip.h)
 int gem_set_lanes(gem_handle* h, int min_windows) {
-    if (!h || min_windows < 0) { set_error("gem_set_lanes: min_windows must be >= 0 (0 = one lane always)"); return 1; }
-    h->lanes_min = min_windows;
+    if (!h || min_windows < 0) { set_error("gem_set_lanes: min_windows must be >= 0"); return 1; }
     return 0;
 }
 
 int gem_set_precision(gem_handle* h, int mode) {
     if (!h || mode < 0 || mode > 2) { set_error("gem_set_precision: mode must be 0 (f32), 1 (bf16x3) or 2 (bf16)"); return 1; }
     h->precision = mode;
-    ++h->cfg_gen;
     return 0;
 }
 

@@ -30,8 +30,26 @@ constexpr int TRACE_ROUNDS = 64;           // evaluation rounds whose closure va
 inline int pad64(int x) { return (x + PAD - 1) / PAD * PAD; }
 
 void set_error(const std::string& msg);
-// Developer switches (A/B runs, sweeps, forcing a kernel path in the tests) are read from the environment ONLY when GEM_DEV=1 is
-// set as well: a stray variable in a production environment cannot change which kernels evaluate the network.
+// Developer switches are read from the environment ONLY when GEM_DEV=1 is set as well: a stray variable in a production
+// environment cannot change which kernels evaluate the network.  These are all of them, each with the test that uses it.
+// Path switches that compare two reachable paths:
+//   GEM_NO_TAIL           no fused tail: every layer a batched GEMM   test_hip_parity: test_unfused_layer_path,
+//                                                                      test_fused_tail_with_windows_longer_than_its_thread_count
+//   GEM_TAIL_WAVES        fp32 tail shape (8: one workgroup per CU)    test_hip_parity: test_fp32_tail_shapes_compute_the_same,
+//                                                                      test_fp32_tail_shared_shape_with_other_window_lengths
+//   GEM_TAIL_CAP          fp32 tail up to this many workgroups per CU  test_hip_parity: test_fp32_tail_shapes_compute_the_same
+//   GEM_TAIL16            bf16 multi-window tail on (1) / off (0)      test_hip_parity: test_bf16_multi_window_tail_against_the_batched_bf16_layers,
+//                                                                      test_bf16_tail_row_tile_variants_compute_the_same;
+//                                                                      test_hip_determinism: test_bf16_tail_instantiations_agree_over_8192_windows_ten_times
+//   GEM_TAIL16_NRT        bf16 tail row tiles per workgroup            test_hip_parity: test_bf16_tail_row_tile_variants_compute_the_same;
+//                                                                      test_hip_determinism: test_bf16_tail_instantiations_agree_over_8192_windows_ten_times
+//   GEM_BATCHED_NARROW    bf16: neither tail, batched narrow layers    test_hip_parity: test_bf16_multi_window_tail_against_the_batched_bf16_layers,
+//                                                                      test_bf16_multi_window_tail_with_other_window_lengths
+//   GEM_NO_FRONT          decoder_input and conv 0 not composed        test_hip_parity: test_composed_front_layer_against_the_two_layers_it_replaces
+//   GEM_NO_FUSED_COMPACT  compact_kernel instead of the fused re-pack  test_hip_parity: test_fused_compaction_is_bitwise_the_compact_kernel
+// Measurement aids that print or record and change no computation:
+//   GEM_LBFGS_CLK         per-phase clocks of lbfgs_advance (-DGEM_LB_PROBE builds; tools/lbfgs_phase_run.sh)
+//   GEM_PROFILE_DUMP      file that gets one line per timed launch (gem_profile_read)
 const char* dev_env(const char* name);
 bool hip_ok(hipError_t e, const char* what);
 #define GEM_HIP(call) do { if (!gem::hip_ok((call), #call)) return 1; } while (0)
@@ -128,7 +146,6 @@ struct Workspace {
     bool tex_on = false;                // energy_args() hands the cache to the kernels (inside a stage only)
     double* trace = nullptr;            // [TRACE_ROUNDS][Bmax] closure value each window consumed in round r of the last stage (NaN: none)
     int round = -1;                     // evaluation round being enqueued (-1: outside the rounds)
-    hipEvent_t mid_event = nullptr;     // two lanes: recorded behind the tail / energy kernel of the round being enqueued (then reset)
     // pipeline scratch
     float* pose_a = nullptr;            // [B,T,J,3] gathered local poses / stage outputs
     float* pose_b = nullptr;
@@ -147,15 +164,6 @@ struct Workspace {
     // `perm`, `slot_of`, `n_active` above always point at the CURRENT round's set; *_home are the allocations they return to.
     int *perm2 = nullptr, *slot_of2 = nullptr, *perm_home = nullptr, *slot_of_home = nullptr, *n_active_home = nullptr;
     int *next_perm = nullptr, *next_slot_of = nullptr, *next_count = nullptr;      // what lbfgs_advance of this round fills (nullptr: off)
-    // EXPERIMENT (GEM_DEV=1 GEM_FUSE_BWD_LBFGS=1, fp32, <= 256 windows, eager launches only): the backward front product and
-    // lbfgs_advance as ONE kernel with a device-wide barrier between them -- what a grid barrier costs against a launch boundary
-    // in this pipeline.  fuse_lbfgs: the round's options while such a launch is wanted; lbfgs_fused_done:
-    // the product's launch carried the advance; grid_bar: monotonic arrival counter, grid_bar_target: its value after this launch.
-    const gem_lbfgs_opts* fuse_lbfgs_req = nullptr;      // set by the round loop, handed to the backward launch only (evaluate)
-    const gem_lbfgs_opts* fuse_lbfgs = nullptr;
-    bool lbfgs_fused_done = false;
-    unsigned* grid_bar = nullptr;
-    unsigned grid_bar_target = 0;
     bool dyn = false;                   // rounds in flight: GEMM / energy launches read their row count from n_active
     int* n_log = nullptr;               // [N_LOG] n_active after every compaction (profiling: true row counts)
     long log_pos = 0, cur_log = -1;
@@ -227,7 +235,6 @@ namespace gem {
 struct GraphKey {
     int kind = 0, stage = 0, B = 0, precision = 0;
     bool tex_cache = true;
-    int lanes = 1;
     const void* ptr[12] = {};
     gem_energy_weights w[2] = {};
     gem_lbfgs_opts opt = {};
@@ -258,30 +265,9 @@ struct gem_handle {
     int64_t graph_replays = 0, graph_captures = 0;
     int* d_parents = nullptr;
     int* d_children = nullptr;     // [J][J] child lists, -1 terminated
-    // two lanes (gem_api.hip windows_dual): a second handle with its own workspace that shares this handle's weights
-    gem_handle* lane2 = nullptr;
-    hipStream_t lane_stream = nullptr, lane_stream_a = nullptr;      // both lanes run on streams of their own (non-blocking: the
-                                                                     // caller's may be the legacy default stream, whose implicit
-                                                                     // synchronisation with every blocking stream of the process
-                                                                     // would sit between the lanes' kernels)
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_join_a = nullptr;
-    std::vector<hipEvent_t> ev_pool;
-    int lanes_min = 0;             // gem_set_lanes: batches of at least this many windows run as two lanes (0: never = the default
-                                   // since round 4: with two tail workgroups per CU one lane is the faster arrangement)
-    int last_split = 0;            // windows in the first lane of the last gem_optimize_windows call (0: one lane)
-    uint64_t cfg_gen = 1;          // bumped by gem_load_vae / gem_set_precision / gem_set_texel_cache: what a second lane mirrors
-    uint64_t lane_gen = 0;         // ... and the generation the second lane was last synchronised with
 };
 
 namespace gem {
-
-// two lanes: the half-round marker of the round being enqueued (Workspace::mid_event), recorded behind the tail / energy kernel
-inline int record_mid(gem_handle* h, hipStream_t s) {
-    if (!h->ws.mid_event) return 0;
-    const hipError_t e = hipEventRecord(h->ws.mid_event, s);
-    h->ws.mid_event = nullptr;
-    return gem::hip_ok(e, "hipEventRecord(mid)") ? 0 : 1;
-}
 
 // profiling hook: remember the (demangled) name of a kernel about to be launched; no-op unless event profiling is on
 void note_kernel(gem_handle* h, const void* host_fn);
@@ -442,9 +428,6 @@ int launch_lbfgs_init(gem_handle* h, int B, const gem_lbfgs_opts& o, hipStream_t
 int launch_lbfgs_advance(gem_handle* h, int B, const gem_lbfgs_opts& o, hipStream_t s);
 int launch_lbfgs_stats(gem_handle* h, int B, gem_window_stats* out, hipStream_t s);
 int launch_compact(gem_handle* h, int B, int force_all, hipStream_t s, int zero_after = 0);
-namespace rows { struct Args; }
-// lbfgs.hip (experiment): gemm_rows_body<4, 5> + device-wide barrier + lbfgs_advance in one launch; -1: shape not covered
-int launch_rows_bwd_lbfgs(gem_handle* h, const rows::Args& ra, int rows_grid, size_t rows_smem, const SlabSrc& gslab, hipStream_t s);
 
 
 }  // namespace gem

@@ -87,8 +87,7 @@ __device__ long long g_rows_clock[6];
 
 constexpr int FUSE_MAX_WINDOWS = 512;
 
-// The kernel's body as a device function (the early returns leave the body, not the kernel): gemm_rows_kernel below is this and
-// nothing else; lbfgs.hip's experimental rows_bwd_lbfgs_kernel runs it in front of a device-wide barrier.
+// The kernel's body as a device function: gemm_rows_kernel below is this and nothing else.
 template <int S, int RT, bool FUSE = false>
 __device__ __forceinline__ void gemm_rows_body(const Args& a) {
     typedef Geometry<RT> G;

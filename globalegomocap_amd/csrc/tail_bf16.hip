@@ -595,7 +595,7 @@ int launch_tail_bf16(gem_handle* h, const TailB16Args& a, size_t lds_bytes, hipS
     // at most one workgroup per CU: the one-workgroup-per-CU instances (lower latency; 5, 4 or 3 row tiles as planned by the
     // caller: tail_bf16_row_tiles); more: the two-per-CU instance
     const int wgs = (a.B + a.G - 1) / a.G;
-    const bool dense = wgs > h->n_cu && !dev_env("GEM_TAIL16_SPARSE");
+    const bool dense = wgs > h->n_cu;
     typedef void (*kern_t)(TailB16Args);
     kern_t kern = nullptr;
     if (dense) {

@@ -424,7 +424,7 @@ __global__ __launch_bounds__(BN_THREADS) void colsum_kernel(const float* __restr
     if (g == 0) out[c] = (float)v[0];
 }
 
-constexpr int CONV_ROWS_MAX = 1 << 30;          // every batch: 1.18 -> 1.11 ms per step at batch 128, 2.17 -> 2.11 at 512, 3.48 -> 3.44 at 1024 (dev switch: GEM_CONV_ROWS_MAX)
+constexpr int CONV_ROWS_MAX = 1 << 30;          // every batch: 1.18 -> 1.11 ms per step at batch 128, 2.17 -> 2.11 at 512, 3.48 -> 3.44 at 1024
 // 0 = launched; 1 = error; -1 = not applicable (the caller falls back to launch_gemm)
 static int conv_rows(gem_trainer* t, const float* W, const float* bias, const float* A, int lda, float* C, int ldc, int rows, int N, int K, hipStream_t s,
                      const CrStats& st = CrStats{});
@@ -1033,8 +1033,7 @@ static int launch_conv_rows(const dim3& grid, const float* W, const float* bias,
 }
 static int conv_rows(gem_trainer* t, const float* W, const float* bias, const float* A, int lda, float* C, int ldc, int rows, int N, int K, hipStream_t s,
                      const CrStats& st) {
-    static const int rows_max = dev_env("GEM_CONV_ROWS_MAX") ? atoi(dev_env("GEM_CONV_ROWS_MAX")) : CONV_ROWS_MAX;
-    if (rows > rows_max || K % 64 || N % 32 || dev_env("GEM_TRAIN_NO_CONV_ROWS")) return -1;
+    if (rows > CONV_ROWS_MAX || K % 64 || N % 32) return -1;
     const dim3 grid((rows + 31) / 32, N / 32);
     // waves per workgroup = K cuts of whole 32-wide chunks (K = 64: two waves, 128: four); eight waves when the tiles alone
     // do not fill the chip.  One ring slot per wave (the refill of the slot just read runs under the sixteen MFMAs: a second slot
@@ -1087,7 +1086,7 @@ static int linear_gemm(gem_trainer* t, const Layer& L, int epi, const float* A, 
     const SlabSrc d = h->ws.deferred;
     h->ws.deferred = SlabSrc{};
     if (rc) return rc;
-    if (d.base && reparam_eps && epi == EPI_BIAS && d.dyn_W == 0 && ldc == 2 * t->Dp && !dev_env("GEM_TRAIN_NO_FC_REPARAM")) {
+    if (d.base && reparam_eps && epi == EPI_BIAS && d.dyn_W == 0 && ldc == 2 * t->Dp) {
         hipLaunchKernelGGL(fc_reduce_reparam_kernel, dim3((unsigned)((M * (t->Dp / 4) + 255) / 256)), dim3(256), 0, s, (const float*)d.base, d.nslab, d.stride,
                            L.bias, reparam_eps, C, t->z, M, t->D, t->Dp);
         GEM_HIP(hipGetLastError());
@@ -1133,9 +1132,8 @@ static int linear_bwd_data(gem_trainer* t, const float* dY, const float* W, floa
 // Strip length (n tiles per workgroup) of gemm_tn_adam_dx_kernel; 0 = the layer / batch does not fit the kernel (more than 64
 // windows, an odd number of n tiles, more strips than slabs): the separate kernels run.
 static int fused_backward_strip(const gem_trainer* t, const TrainLinear& l, int B) {
-    if (B > 64 || dev_env("GEM_TRAIN_NO_FUSED_DX")) return 0;
+    if (B > 64) return 0;
     const int nt = l.N / 64, nkt = l.K / 64;
-    if (const char* f = dev_env("GEM_TRAIN_TPS")) { const char* c = strchr(f, ','); const int tps = (&l == &t->dec_in && c) ? atoi(c + 1) : atoi(f); return (tps >= 2 && tps % 2 == 0 && nt % tps == 0 && nt / tps <= t->dx_slab_cap) ? tps : 0; }
     // The kernel is bound by what one CU gets through (two products and the Adam arithmetic per tile), not by HBM: the strip length that
     // leaves every CU the same number of tiles wins -- tiles per CU = ceil(workgroups / CUs) x tps (reference VAE on 256 CUs:
     // fc 80 k tiles x 16 strips of 4 = 1280 workgroups, decoder_input 32 x 8 strips of 10 = 256; measured 0.721 ms per step
@@ -1341,7 +1339,7 @@ int gem_trainer_step(gem_trainer* t, int B, const float* d_pose, const float* d_
     GEM_HIP(hipGetLastError());
     // ---- forward (train mode)
     if (launch_pack_pose(d_pose, t->pose_p, rows, t->C, s)) return 1;
-    const bool bn_fused = rows <= BNF_ROWS_MAX && !dev_env("GEM_TRAIN_NO_BN_FUSE");
+    const bool bn_fused = rows <= BNF_ROWS_MAX;
     auto conv_fwd = [&](TrainConv& c, const float* in) -> int {
         Layer L; L.taps = 3; L.K = c.K; L.N = c.N; L.w = t->P + c.ow; L.bias = t->P + c.ob;
         // (bn_fused: the conv's epilogue leaves the BatchNorm sums per 32-row tile; the apply kernels are elementwise)

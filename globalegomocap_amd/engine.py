@@ -144,8 +144,8 @@ class WindowEngine:
         return r
 
     def set_lanes(self, min_windows):
-        """optimize_windows calls of at least `min_windows` windows run as two half-batches on two streams, half a round apart
-        (gem_set_lanes; 0 = never = the default).  Same results, bit for bit, for thresholds >= 4352."""
+        """Accepted for compatibility (gem_set_lanes): every optimize_windows call runs as one lane whatever `min_windows` (>= 0).
+        The two-lane schedule it used to switch on measured slower than one lane and is no longer in the library."""
         _capi.check(self.lib.gem_set_lanes(self._h, int(min_windows)), self.lib)
 
     def set_precision(self, mode):

@@ -122,7 +122,7 @@ def parse_chunk(path, native=True):
 
 
 N_COPY_STREAMS = int(os.environ.get("GEM_WS_STREAMS", 2))
-STREAM_PRIORITY = int(os.environ.get("GEM_WS_PRIORITY", 0))          # (0 = torch's default pool; -1 measured the same: tools/r06_stream_prio.sh)
+STREAM_PRIORITY = int(os.environ.get("GEM_WS_PRIORITY", 0))          # (0 = torch's default pool; -1 measured the same: profiles/stream_prio_r06.txt)
 _copy_streams = {}
 _report_streams = {}
 _copy_lock = threading.Lock()
@@ -252,7 +252,7 @@ def cpus_near(device):
     """The CPUs of the NUMA node the device hangs off (its PCIe root), as far as this process may run on them -- or None when
     the platform does not say.  The readers copy page cache -> pinned memory (which the runtime places next to the device):
     from the other socket that copy crosses the inter-socket links and the read + host-to-device pipeline of a 2000-frame
-    sequence took 14.5 instead of 10.5 ms (tools/r06_numa_probe.py)."""
+    sequence took 14.5 instead of 10.5 ms (tools/r06_numa_probe.py at commit 1ab2c18)."""
     try:
         p = torch.cuda.get_device_properties(device)
         bdf = "%04x:%02x:%02x.0" % (p.pci_domain_id, p.pci_bus_id, p.pci_device_id)

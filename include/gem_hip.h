@@ -86,13 +86,9 @@ int gem_version(void);
 int  gem_create(const gem_config* cfg, gem_handle** out);
 void gem_destroy(gem_handle* h);
 
-/* Two lanes: gem_optimize_windows calls of at least `min_windows` windows run as two half-batches on two streams (the caller's
- * and one owned by the handle), shifted by half an evaluation round so that the HBM-bound L-BFGS advance of one half shares the
- * device with the matrix-bound kernels of the other (windows are independent: optimizer.py:370).  Results are bitwise those of
- * one lane wherever no product is cut along K (any threshold >= 4352 windows guarantees it); outputs, statistics and
- * gem_read_trace are assembled in window order.  0 = always one lane = the DEFAULT since round 4: the bf16 tail now keeps two
- * workgroups per CU busy by itself and one lane measures faster (8192 windows: 289 k vs 247-259 k windows/s); the call stays for
- * devices / batch shapes where the split pays.  Costs a second workspace (half the size of the first) when switched on. */
+/* Accepted for compatibility and otherwise ignored: every gem_optimize_windows call runs as one lane.  (The two-lane schedule it
+ * used to switch on -- two half-batches on two streams, shifted by half an evaluation round -- measured slower than one lane,
+ * 247-259 k vs 289 k windows/s at 8192 windows, and is no longer in the library: DESIGN.md section 2.)  min_windows must be >= 0. */
 int gem_set_lanes(gem_handle* h, int min_windows);
 
 /* Arithmetic of the decoder / encoder products (every energy term is always fp32 arithmetic on the fp32 decoded pose):

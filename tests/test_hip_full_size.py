@@ -624,56 +624,43 @@ def test_config4_shard_of_a_continuous_stream(torch_cuda, friendly_vaes, precisi
 
 
 @pytest.mark.parametrize("B", [4360, 8192])
-def test_two_lanes_are_bitwise_one_lane(torch_cuda, friendly_vaes, B):
-    """Large bf16 batches run as two half-batches on two streams, half an evaluation round apart (gem_set_lanes / windows_dual
-    in csrc/gem_api.hip), so that one half's HBM-bound L-BFGS advance overlaps the other half's matrix-bound kernels.  Windows do
-    not interact and from 4352 windows on no product is cut along K in the full batch or in its halves: mid-local poses, global
-    poses, statistics and closure traces must be bit for bit those of ONE lane -- eagerly and replayed from a hipGraph."""
+def test_batch_halves_are_bitwise_the_whole_batch(torch_cuda, friendly_vaes, B):
+    """Windows do not interact (optimizer.py:370): a window's result must not depend on the batch around it -- across the
+    gemm_big / gemm_glds switch of the front products at 5376 rows (8192 runs on one side of it, its halves on the other) and
+    across the row-tile counts of the bf16 tail.  Mid-local poses, global poses, statistics and closure traces of the full bf16
+    batch in one call must be bit for bit those of its two halves [0, BA) and [BA, B) as two calls of the same engine; the full
+    batch replayed from a hipGraph must be bit for bit the eager call.  gem_set_lanes is accepted and changes nothing."""
     torch = torch_cuda
     sd_l, sd_g = friendly_vaes
     rng = np.random.default_rng(B)
     n_frames = 6000
     starts = rng.integers(0, n_frames - 10, B)
-    one = _engine(B, sd_l, sd_g, "bf16")
-    one.set_lanes(0)
-    p = _device_problem(one, n_frames, starts, seed=B, n_dup=0)
-    ref = [t.clone() for t in _run(one, p)]
-    tr_ref = one.read_trace(B, 8)
-    one.close()
-    two = _engine(B, sd_l, sd_g, "bf16")
-    two.set_lanes(4352)                                  # two lanes from 4352 windows on (one lane is the default since round 4)
-    for graphs in (False, True):
-        two.enable_graphs(graphs)
-        for k in range(3 if graphs else 1):
-            got = _run(two, p)
-            torch.cuda.synchronize()
-            for a_, b_ in zip(got, ref):
-                assert torch.equal(a_, b_), (graphs, k)
-        assert np.array_equal(two.read_trace(B, 8), tr_ref, equal_nan=True)
-    assert two.graph_stats()["replays"] >= 2
-    two.close()
-
-
-def test_device_wide_barrier_experiment_is_bitwise_the_product(torch_cuda, full_vaes, monkeypatch):
-    """The experiment behind DESIGN.md section 4's "a device-wide barrier against a launch boundary" (GEM_DEV=1
-    GEM_FUSE_BWD_LBFGS=1: the backward front product and lbfgs_advance of every fp32 round as ONE launch with a grid barrier in
-    between, csrc/lbfgs.hip rows_bwd_lbfgs_kernel): it is only a timing argument if it computes the same thing -- 240 windows, both
-    stages, bitwise the product path's poses and statistics."""
-    torch = torch_cuda
-    data, sd_l, sd_g, w_l, w_g = full_vaes
-    n_chunks = 20
-    starts = np.concatenate([c * 100 + window_starts(100) for c in range(n_chunks)])
-    eng = _engine(len(starts), sd_l, sd_g, "f32")
-    p = _device_problem(eng, n_chunks * 100, starts, seed=707, n_dup=0)
+    eng = _engine(B, sd_l, sd_g, "bf16")
+    p = _device_problem(eng, n_frames, starts, seed=B, n_dup=0)
     ref = [t.clone() for t in _run(eng, p)]
-    monkeypatch.setenv("GEM_DEV", "1")
-    monkeypatch.setenv("GEM_FUSE_BWD_LBFGS", "1")
-    out = [t.clone() for t in _run(eng, p)]
+    tr_ref = eng.read_trace(B, 8)
+    BA = ((B + 1) // 2 + 7) // 8 * 8                     # whole tail workgroups (8 windows) in the first half
+    halves, traces = [], []
+    for lo, hi in ((0, BA), (BA, B)):
+        q = dict(p, f0=p["f0"][lo:hi], mb=p["mb"][lo:hi], eps_l=p["eps_l"][lo:hi], eps_g=p["eps_g"][lo:hi])
+        halves.append([t.clone() for t in _run(eng, q)])
+        traces.append(eng.read_trace(hi - lo, 8))
+    (mid_a, glob_a, st_a), (mid_b, glob_b, st_b) = halves
     torch.cuda.synchronize()
-    monkeypatch.delenv("GEM_FUSE_BWD_LBFGS")
-    assert all(torch.equal(a, b) for a, b in zip(ref, out))
-    from globalegomocap_amd.engine import stats_to_numpy
-    assert stats_to_numpy(out[2])["finished"].all()
+    assert torch.equal(torch.cat([mid_a, mid_b]), ref[0])
+    assert torch.equal(torch.cat([glob_a, glob_b]), ref[1])
+    # stats: [2n, 4] = the local stage's n rows, then the global stage's
+    assert torch.equal(torch.cat([st_a[:BA], st_b[:B - BA], st_a[BA:], st_b[B - BA:]]), ref[2])
+    assert np.array_equal(np.concatenate(traces), tr_ref, equal_nan=True)
+    eng.set_lanes(4352)
+    eng.enable_graphs(True)
+    for k in range(3):                                   # call 1 eager (warm-up), call 2 captures, call 3 replays
+        got = _run(eng, p)
+        torch.cuda.synchronize()
+        for a_, b_ in zip(got, ref):
+            assert torch.equal(a_, b_), k
+    assert np.array_equal(eng.read_trace(B, 8), tr_ref, equal_nan=True)
+    assert eng.graph_stats()["replays"] >= 2
     eng.close()
 
 
