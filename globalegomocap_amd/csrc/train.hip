@@ -29,6 +29,7 @@
 
 #include "gem_internal.h"
 #include "conv_rows.h"
+#include "motion_windows.h"
 
 namespace gem {
 

@@ -349,15 +349,11 @@ def save_checkpoint(path, state_dict):
     torch.save({"epoch": 19, "state_dict": sd}, path)
 
 
-def load_checkpoint_file(path, trust=None):
-    """The whole dict of a checkpoint file (networks/train.py:102-108: epoch, args, state_dict, eval_result, optimizer) through
-    torch's restricted unpickler: tensors, containers, primitives and numpy scalars / arrays only -- a downloaded file cannot run
-    code.  A file that needs more (the reference never writes one) is refused unless `trust=True` or GEM_TRUST_CHECKPOINTS=1."""
-    import os
-    import pickle
-    import torch
-    if trust is None:
-        trust = os.environ.get("GEM_TRUST_CHECKPOINTS") == "1"
+def numpy_pickle_globals():
+    """The globals a restricted unpickler may resolve for numpy content: np.dtype / np.ndarray, the dtype classes, and
+    multiarray.scalar / _reconstruct -- each also under the module path of the other numpy generation (entries (obj, "module.name")),
+    since the reference's files were written under numpy 1.x (numpy.core.multiarray) and may be read under 2.x (numpy._core) or the
+    other way round.  Shared by load_checkpoint_file (torch's weights_only unpickler) and motion_data's pickle reader."""
     allow = [np.dtype, np.ndarray]
     for name in (("_core",) if hasattr(np, "_core") else ("core",)):          # numpy 2.x / 1.x module layout
         mod = getattr(np, name, None)
@@ -374,6 +370,19 @@ def load_checkpoint_file(path, trust=None):
             target = next((a for a in allow if getattr(a, "__name__", None) == fn), None)
             if target is not None:
                 allow.append((target, "%s.%s" % (legacy, fn)))
+    return allow
+
+
+def load_checkpoint_file(path, trust=None):
+    """The whole dict of a checkpoint file (networks/train.py:102-108: epoch, args, state_dict, eval_result, optimizer) through
+    torch's restricted unpickler: tensors, containers, primitives and numpy scalars / arrays only -- a downloaded file cannot run
+    code.  A file that needs more (the reference never writes one) is refused unless `trust=True` or GEM_TRUST_CHECKPOINTS=1."""
+    import os
+    import pickle
+    import torch
+    if trust is None:
+        trust = os.environ.get("GEM_TRUST_CHECKPOINTS") == "1"
+    allow = numpy_pickle_globals()
     try:
         with torch.serialization.safe_globals(allow):
             return torch.load(path, map_location="cpu", weights_only=True)

@@ -417,14 +417,22 @@ class VAETrainer:
         reparameterisation of ConvVAE.forward and decodes; the mean over batches of the per-batch mean joint distance."""
         import torch
         from .engine import WindowEngine
+        from .motion_data import MotionWindows
         bs = int(batch_size or self.batch_size)
         eng = WindowEngine(self.shape, max_windows=bs, device=self.device.index)
         try:
             eng.load_vae(0, self.state_dict())
-            data = torch.as_tensor(np.asarray(windows), dtype=torch.float32)
+            if isinstance(windows, MotionWindows):        # (the ids in order, cut on the device)
+                self._check_windows(windows)
+                n = len(windows)
+                take = lambda i: windows.batch(torch.arange(i, min(i + bs, n), dtype=torch.int64, device=self.device))  # noqa: E731
+            else:
+                data = torch.as_tensor(np.asarray(windows), dtype=torch.float32)
+                n = data.shape[0]
+                take = lambda i: data[i:i + bs].to(self.device)          # noqa: E731
             errs = []
-            for i in range(0, data.shape[0], bs):
-                x = data[i:i + bs].to(self.device)
+            for i in range(0, n, bs):
+                x = take(i)
                 e = torch.randn(x.shape[0], self.shape.latent_dim, device=self.device, generator=self._gen)
                 z = eng.encode(0, x, eps=e)[2]
                 rec = eng.decode(0, z)
@@ -434,17 +442,30 @@ class VAETrainer:
         finally:
             eng.close()
 
+    def _check_windows(self, ds):
+        if ds.seq_len != self.shape.seq_len or ds.device != self.device:
+            raise ValueError("the MotionWindows cut windows of %d frames on %s; this trainer takes %d frames on %s"
+                             % (ds.seq_len, ds.device, self.shape.seq_len, self.device))
+
     def fit(self, train_windows, epochs=20, kl_weight=0.25, test_windows=None, log_step=100, checkpoint_dir=None, seed=0, log=print,
             args=None, group=None, data_parallel=False):
-        """Train.train(): `epochs` passes over a shuffled, drop_last DataLoader of `train_windows` [n,T,45].
+        """Train.train(): `epochs` passes over a shuffled, drop_last DataLoader of `train_windows` [n,T,45] -- an array, or a
+        `motion_data.MotionWindows`, whose batches are cut on the device from the permuted ids (the same batches as from its
+        `materialize()`); `test_windows` likewise.
 
         data_parallel=True (torch.distributed initialised, one process per GPU): every rank walks the same permutation (same
         seed) and takes the batches rank, rank + world, ... (a DistributedSampler's split); gradients are averaged over the
         ranks every step; rank 0 logs, evaluates and writes the checkpoints."""
         import torch
         from .vae import save_checkpoint  # noqa: F401  (same schema; the file below carries train.py's extra keys)
-        data = torch.as_tensor(np.asarray(train_windows), dtype=torch.float32, device=self.device)
-        n, bs = int(data.shape[0]), self.batch_size
+        from .motion_data import MotionWindows
+        if isinstance(train_windows, MotionWindows):
+            self._check_windows(train_windows)
+            n, gather = len(train_windows), train_windows.batch
+        else:
+            data = torch.as_tensor(np.asarray(train_windows), dtype=torch.float32, device=self.device)
+            n, gather = int(data.shape[0]), data.__getitem__
+        bs = self.batch_size
         if n < bs:
             raise ValueError("the dataset (%d windows) is smaller than one batch (%d): drop_last leaves nothing" % (n, bs))
         m_n = float(kl_weight) * bs / n
@@ -462,9 +483,9 @@ class VAETrainer:
             perm = torch.randperm(n, generator=g).to(self.device)
             for i in range(rank, (n // bs) // world * world, world):
                 if data_parallel:
-                    running += self.step_data_parallel(data[perm[i * bs:(i + 1) * bs]], m_n, group=group, sync=False)
+                    running += self.step_data_parallel(gather(perm[i * bs:(i + 1) * bs]), m_n, group=group, sync=False)
                 else:
-                    running += self.step(data[perm[i * bs:(i + 1) * bs]], m_n, sync=False, keep_gradients=False)
+                    running += self.step(gather(perm[i * bs:(i + 1) * bs]), m_n, sync=False, keep_gradients=False)
                 if count % log_step == 0 and count != 0:
                     r = running.cpu()
                     log("running loss is: {}".format(float(r[0])))
@@ -534,38 +555,93 @@ def fit_vae_device(shape, windows, steps=2000, batch=128, lr=2e-3, kl_weight=0.0
     return sd, err
 
 
-def _cli():
-    """`python -m globalegomocap_amd.vae_train`: the flags of networks/config.py:5-49 that `Train` reads, over a window file.
+def _flag(x):
+    """networks/config.py's boolean flags: `lambda x: str(x).lower() == 'true'`."""
+    return str(x).lower() == "true"
 
-    --train_data_path takes a .npy / .npz ('windows') of [n, seq_length, 45] relative-global pose windows (what AMASSDataset's
-    __getitem__ yields, networks/dataset/global_dataset.py:34-38; building them from AMASS pickles is data preparation and stays
-    with the reference) or `synthetic:<n>` for synthetic motion.  Checkpoints go to logs/<log_dir>/checkpoints/<e>.pth.tar
-    (train.py:19-33,102-108)."""
+
+def _parser():
     import argparse
-    import datetime
-    from . import synth
-    p = argparse.ArgumentParser(description="Train the motion VAE on MI355X (mirror of networks/train.py)")
-    p.add_argument("--train_data_path", required=True)
+    p = argparse.ArgumentParser(description="Train the motion VAE on MI355X (mirror of networks/train.py / train_local.py)")
+    p.add_argument("--train_data_path", required=True, help="directory of motion pickles, .npy / .npz of windows, or synthetic:<n>")
     p.add_argument("--test_data_path", default=None)
+    p.add_argument("--poses", choices=("global", "local"), default="global",
+                   help="from a directory: global windows (train.py) or camera-frame ones (train_local.py)")
+    p.add_argument("--seq_names", default=None, help=".npy of sequence names, required by --with_mo2cap2_data True")
+    p.add_argument("--network", default="cnn", help="only 'cnn' (the ConvVAE) is available")
+    p.add_argument("--attention", default=None, help="accepted, ignored (the ConvVAE has no attention)")
     p.add_argument("--latent_dim", type=int, required=True)
+    p.add_argument("--with_mo2cap2_data", type=_flag, default=False)
+    p.add_argument("--new_dataset", type=_flag, default=True, help="accepted, ignored (train.py does not read it)")
+    p.add_argument("--data_balance", type=_flag, default=False)
+    p.add_argument("--slide_window_step", type=int, default=1, help="the datasets' windows_size")
     p.add_argument("--seq_length", type=int, required=True)
+    p.add_argument("--fps", type=int, default=25)
     p.add_argument("--kl_weight", type=float, required=True)
     p.add_argument("--epoch", type=int, default=20)
     p.add_argument("--batch_size", type=int, default=64)
+    p.add_argument("--num_workers", type=int, default=8, help="accepted, ignored (windows are cut on the device)")
     p.add_argument("--learning_rate", type=float, default=1e-4)
     p.add_argument("--weight_decay", type=float, default=0.0)
     p.add_argument("--log_dir", default=None)
+    p.add_argument("--log_prefix", default=None, help="accepted, ignored (train.py does not read it)")
     p.add_argument("--log_step", type=int, default=100)
+    p.add_argument("--save_step", type=int, default=2000, help="accepted, ignored (train.py saves once per epoch)")
     p.add_argument("--seed", type=int, default=0)
-    a = p.parse_args()
+    return p
 
-    def load(path, seed):
+
+def _cli(argv=None):
+    """`python -m globalegomocap_amd.vae_train`: the flags of networks/config.py:5-49 (train_global.sh's argument list runs as it
+    is), plus --poses and --seq_names.
+
+    --train_data_path takes
+      a directory of motion pickles: the reference's AMASSDataset (networks/dataset/global_dataset.py, local_dataset.py with
+        --poses local) as a motion_data.MotionWindows -- split 'train' for training, 'test' for the evaluation pass unless
+        --test_data_path is given; frame_num = --seq_length, windows_size = --slide_window_step, sliding windows, --fps,
+        --data_balance, --with_mo2cap2_data (with --seq_names); every batch is cut on the device
+      a .npy / .npz ('windows') of [n, seq_length, 45] windows
+      synthetic:<n> for synthetic motion.
+    Checkpoints go to logs/<log_dir>/checkpoints/<e>.pth.tar (train.py:19-33,102-108)."""
+    import datetime
+    from . import synth
+    from .motion_data import MotionWindows
+    p = _parser()
+    a = p.parse_args(argv)
+    if a.network != "cnn":
+        p.error("--network %s is not available: only the ConvVAE ('cnn') is implemented (the reference's 'mlp' model is not in "
+                "its tree)" % a.network)
+    if a.with_mo2cap2_data and not a.seq_names:
+        p.error("--with_mo2cap2_data True needs --seq_names PATH (the .npy of sequence names; the reference's is a cluster path)")
+
+    def load(path, seed, split):
+        if os.path.isdir(path):
+            return MotionWindows.from_directory(path, poses=a.poses, frame_num=a.seq_length, windows_size=a.slide_window_step, fps=a.fps,
+                                                slide_window=True, split=split, balance=a.data_balance,
+                                                seq_names=a.seq_names if a.with_mo2cap2_data else None, seed=a.seed, device="cpu")
         if path.startswith("synthetic:"):
             return synth.make_training_windows(int(path.split(":", 1)[1]), a.seq_length, seed)
         d = np.load(path)
         return np.asarray(d["windows"] if hasattr(d, "files") else d, np.float32).reshape(-1, a.seq_length, 45)
-    train = load(a.train_data_path, a.seed)
-    test = load(a.test_data_path, a.seed + 1) if a.test_data_path else train[-min(len(train), 10 * a.batch_size):]
+    train = load(a.train_data_path, a.seed, "train")
+    if a.test_data_path:
+        test = load(a.test_data_path, a.seed + 1, "all")
+    elif isinstance(train, MotionWindows):
+        test = load(a.train_data_path, a.seed, "test")
+    else:
+        test = train[-min(len(train), 10 * a.batch_size):]
+    seq_len = train.seq_len if isinstance(train, MotionWindows) else a.seq_length
+    if seq_len != a.seq_length:
+        p.error("--poses local with --slide_window_step %d cuts windows of %d frames (local_dataset.py keeps every frame), but the "
+                "network takes --seq_length %d" % (a.slide_window_step, seq_len, a.seq_length))
+    if len(train) < a.batch_size:
+        p.error("%d training windows are fewer than one batch of %d (drop_last leaves nothing)" % (len(train), a.batch_size))
+    for ds in (train, test):
+        if isinstance(ds, MotionWindows):
+            ds.upload()
+    if isinstance(train, MotionWindows):
+        print("%d training windows from %d files (%d frames resident), %d test windows" % (len(train), len(train.names), train.n_frames,
+                                                                                          len(test)))
     log_dir = os.path.join("logs", a.log_dir or datetime.datetime.now().strftime("%m.%d-%H:%M:%S"))
     print("making save dir at: {}".format(log_dir))
     shape = VAEShape(latent_dim=a.latent_dim, seq_len=a.seq_length)

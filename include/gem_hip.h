@@ -348,6 +348,23 @@ int  gem_trainer_step(gem_trainer* t, int B, const float* d_pose, const float* d
 int  gem_trainer_arena(gem_trainer* t, int what, void** d_ptr, int64_t* n);
 int  gem_trainer_apply(gem_trainer* t, const gem_train_opts* opts, double grad_scale, void* stream);
 
+/* ---- Training windows of the motion VAEs cut on the device ----
+ * gem_motion_cameras: d_loc [n,3], d_quat [n,4] (x, y, z, w; any non-zero norm) float64 -> d_cam34 [n,3,4] float64 = [R | loc] with
+ * R = scipy's Rotation.from_quat(quat).as_matrix() (normalised first; utils/utils.py:33-42 of the reference).
+ * gem_motion_windows: S sequences packed in one frame arena: d_pose [F,15,3] float64; d_cam34 [F,3,4] from gem_motion_cameras for
+ * global windows or NULL for local (camera-frame) ones; d_seq_frame0 [S] the first arena frame of every sequence, d_seq_window0
+ * [S+1] the prefix of the windows per sequence (window0[S] = n_windows), d_seq_timer [S] its frame-rate timer.  For every id of
+ * d_ids [B] (int64, device), window w = id - window0[s] of sequence s starts at arena frame frame0[s] + w * interval (interval 0:
+ * w * frame_num * windows_size * timer[s], the reference's windows without sliding) and
+ * d_out [B,T,45] float32 receives
+ *   global (T = frame_num):              inv(C_start) . C_f . [x; 1] for f = start + t * windows_size * timer (float64, rounded once)
+ *   local  (T = frame_num * windows_size): the pose of frame f = start + t * timer
+ * An id outside [0, n_windows) gives NaN rows.  The host builds the prefix arrays; the kernel trusts them.  Nothing synchronises. */
+int gem_motion_cameras(const double* d_loc, const double* d_quat, int64_t n_frames, double* d_cam34, void* stream);
+int gem_motion_windows(const double* d_pose, const double* d_cam34, const int64_t* d_seq_frame0, const int64_t* d_seq_window0,
+                       const int32_t* d_seq_timer, int n_seq, int64_t interval, int frame_num, int windows_size,
+                       const int64_t* d_ids, int64_t B, float* d_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
