@@ -52,6 +52,17 @@ DT_F32, DT_F64 = 0, 1
 PICKLE_UNSUPPORTED = 2
 
 
+class GemMatArray(C.Structure):
+    _fields_ = [("offset", C.c_int64), ("nbytes", C.c_int64), ("next", C.c_int64), ("start", C.c_int64), ("bare", C.c_int32),
+                ("compressed", C.c_int32), ("mat_class", C.c_int32), ("storage", C.c_int32), ("ndim", C.c_int32),
+                ("reserved", C.c_int32), ("dims", C.c_int64 * 4)]
+
+
+MAT_UNSUPPORTED, MAT_NOT_FOUND = 2, 3
+MAT_HEAT_F64, MAT_DEPTH_F32 = 1, 2
+MI_SINGLE, MI_DOUBLE = 7, 9
+
+
 class GemWindowStats(C.Structure):
     _fields_ = [("n_iter", C.c_int32), ("func_evals", C.c_int32), ("final_loss", C.c_float), ("status", C.c_int32)]
 
@@ -93,6 +104,11 @@ SIGNATURES = {
     "gem_chunk_offsets": (C.c_int, [_P, C.c_int, _P, C.c_int64]),
     "gem_chunk_gather_f64": (C.c_int, [_P, C.c_int, _P, C.c_int64]),
     "gem_file_stage": (C.c_int, [C.c_char_p, C.c_int, _P, _P, C.c_int64, C.c_int64, C.POINTER(C.c_int64), _P]),
+    "gem_mat_scan": (C.c_int, [_P, C.c_int64, C.c_char_p, C.POINTER(GemMatArray)]),
+    "gem_files_sizes": (C.c_int, [C.POINTER(C.c_char_p), C.c_int64, _P]),
+    "gem_mat_read": (C.c_int, [C.POINTER(C.c_char_p), C.c_int64, _P, _P, C.c_char_p, _P, C.c_int64, C.POINTER(GemMatArray), _P]),
+    "gem_mat_frames": (C.c_int, [_P, C.c_int64, _P, _P, _P, C.c_int64, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+    "gem_prepare_global": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int, _P, _P, _P]),
     "gem_profile_enable": (C.c_int, [_P, C.c_int]),
     "gem_profile_read": (C.c_int, [_P, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
     "gem_profile_kernels": (C.c_int, [_P, C.c_int, C.c_char_p, C.c_int]),

@@ -621,3 +621,5 @@ int gem_file_stage(const char* path, int device, void* h_pinned, void* d_image, 
 }
 
 }  // extern "C"
+
+#include "mat_file.h"          // gem_mat_scan, gem_mat_read, gem_mat_frames, gem_prepare_global

@@ -1,0 +1,550 @@
+"""Recordings from the pose network's .mat files: the reference's `MakeDataForOptimization/process_test_data.py` on the device.
+
+The pose network leaves one `heatmap` .mat ([64,64,15]) and one `depth` .mat ([1,15]) per frame.  The reference walks them
+frame by frame (loadmat, a 1024 x 1280 x 15 upscale, argmax, un-projection), fits the SLAM scale against the ground truth and
+pickles five lists per 100-frame chunk.  Here the files of all chunks go as they are into one block of pinned memory and
+from there into HBM (`gem_mat_read`: the library reads and interprets them, no Python object per array), ONE kernel picks
+heat-maps and depths out (`gem_mat_frames`), the existing lifting kernel gives `estimated_local_skeleton`, the host fits
+the scale per chunk from the head joints alone (`slam.camera_pose_list_from_heads`) and one more kernel applies the scaled
+cameras (`gem_prepare_global`).  The result is a `Recording` on the device that `whole_sequence.optimize_recording` consumes
+directly; `Recording.write_chunks` writes the reference's `data_start_{a}_end_{b}/test_data.pkl` files when they are wanted.
+
+The reference's quirks are kept (process_test_data.py line numbers):
+
+  * frame files are `natsorted(os.listdir(dir))[start_frame:end_frame]` (:52-53): an index into the LISTING, not a frame id;
+  * ground truth is `pose_gt[i - mat_start_frame]` for i in range(start_frame, end_frame) (:44-45), passed through untouched;
+  * trajectory lines are selected by frame id round(t * fps) in [start_frame, end_frame) (slam_reader.py);
+  * every chunk is prepared on its own: cameras relative to the chunk's first frame, Umeyama scale over its frames only;
+  * the chunk loop is range(total_start, total_end - test_size, test_size) (:183): a span that is a multiple of test_size
+    loses its last chunk;
+  * the pickle: five keys in the order gt_global_skeleton, estimated_global_skeleton, estimated_local_skeleton,
+    camera_pose_list, heatmap_list; every value a list of per-frame arrays; estimated_local_skeleton Fortran-ordered float64,
+    heatmap_list what loadmat returned (the file's class, Fortran order); default pickle protocol.
+
+One documented difference: a trajectory file without a line for some frame id of [start_frame, end_frame) makes the reference
+write lists of different lengths, which its own optimiser cannot read; here that is a ValueError naming the ids.  So is a
+listing with fewer files than the range asks for.
+
+    python -m globalegomocap_amd.prepare --slam traj.txt --heatmaps DIR --depths DIR --gt gt.pkl --start 551 --end 3300 \\
+        --fps 25 --out DIR [--optimize]
+"""
+import ctypes as C
+import io
+import os
+import pickle
+import zlib
+
+import numpy as np
+
+from . import _capi
+from .whole_sequence import natural_key
+
+HEAT_NAME, DEPTH_NAME = "heatmap", "depth"
+PICKLE_KEYS = ("gt_global_skeleton", "estimated_global_skeleton", "estimated_local_skeleton", "camera_pose_list", "heatmap_list")
+N_READERS = 8
+_ALIGN = 16                      # file images are laid out on 16-byte boundaries, with at least 8 bytes of slack behind each
+
+
+# ------------------------------------------------------------------------------------------------------------------ host-side logic
+def list_frames(directory, start_frame, end_frame):
+    """`natsorted(os.listdir(directory))[start_frame:end_frame]` as full paths (process_test_data.py:52-53): the range indexes
+    the LISTING.  Every entry counts, whatever it is, as in the reference."""
+    names = sorted(os.listdir(directory), key=natural_key)[start_frame:end_frame]
+    return [os.path.join(directory, n) for n in names]
+
+
+def chunk_spans(total_start_frame, total_end_frame, test_size=100):
+    """The reference's chunk loop (:183-187): [(start, end)] for start in range(total_start, total_end - test_size, test_size).
+    A span that is a multiple of test_size does NOT produce its last chunk."""
+    return [(i, i + test_size) for i in range(total_start_frame, total_end_frame - test_size, test_size)]
+
+
+def read_gt(gt_path):
+    """The ground-truth pickle (a sequence of [J,3] arrays, or one [N,J,3] array) through the restricted unpickler: numpy arrays and
+    builtin containers only."""
+    from .motion_data import _RestrictedUnpickler, _allowed_globals
+    with open(gt_path, "rb") as f:
+        return _RestrictedUnpickler(io.BytesIO(f.read()), _allowed_globals()).load()
+
+
+def gt_clip(pose_gt, start_frame, end_frame, mat_start_frame):
+    """load_gt_data (:38-48): [pose_gt[i - mat_start_frame] for i in range(start_frame, end_frame)], the arrays untouched (a
+    negative index wraps round, as it does there)."""
+    return [pose_gt[i - mat_start_frame] for i in range(start_frame, end_frame)]
+
+
+def check_trajectory(text, start_frame, end_frame, fps):
+    """ValueError when the trajectory (its text, or its rows as `slam.trajectory_rows` parses them) has no line, or more than one,
+    for a frame id of [start_frame, end_frame)."""
+    from . import slam
+    ids = slam.frame_ids(text, fps)
+    ids = ids[(ids >= start_frame) & (ids < end_frame)]
+    missing = sorted(set(range(start_frame, end_frame)) - set(ids.tolist()))
+    if missing:
+        raise ValueError("the trajectory has no line for frame ids %s of [%d, %d) at %g fps (the reference would write lists of "
+                         "different lengths here)" % (missing, start_frame, end_frame, fps))
+    if len(ids) != end_frame - start_frame:
+        u, c = np.unique(ids, return_counts=True)
+        raise ValueError("the trajectory has several lines for frame ids %s" % u[c > 1].tolist())
+
+
+# ------------------------------------------------------------------------------------------------------------------ MAT files
+_NP_OF = {_capi.MI_SINGLE: np.float32, _capi.MI_DOUBLE: np.float64}
+
+
+def mat_scan(buf, name, start=0, bare=False):
+    """gem_mat_scan on a bytes-like object -> (return code, GemMatArray, reason)."""
+    lib = _capi.load_library()
+    view = np.frombuffer(buf, dtype=np.uint8)
+    out = _capi.GemMatArray(start=start, bare=1 if bare else 0)
+    rc = lib.gem_mat_scan(C.c_void_p(view.ctypes.data if view.size else 0), view.size, name.encode(), C.byref(out))
+    return rc, out, ("" if rc == 0 else (lib.gem_last_error() or b"").decode())
+
+
+def locate(buf, name):
+    """Where the array `name` lies in the MAT file image `buf`: (image, offset, numpy dtype, dims) -- `image` is `buf` itself, or
+    the inflated element when the variable was stored compressed -- or None when the file is outside the library's subset
+    (`mat_scan` tells why).  Compressed elements are inflated with the standard library's zlib."""
+    start = 0
+    for _ in range(4096):
+        rc, a, _why = mat_scan(buf, name, start)
+        if rc:
+            return None
+        if not a.compressed:
+            return buf, int(a.offset), _NP_OF[a.storage], tuple(int(d) for d in a.dims[:a.ndim])
+        try:
+            raw = zlib.decompress(bytes(memoryview(buf)[a.offset:a.offset + a.nbytes]))
+        except zlib.error:
+            return None
+        rc, b, _why = mat_scan(raw, name, 0, bare=True)
+        if rc == 0 and not b.compressed:
+            return raw, int(b.offset), _NP_OF[b.storage], tuple(int(d) for d in b.dims[:b.ndim])
+        if rc != _capi.MAT_NOT_FOUND:
+            return None
+        start = int(a.next)
+        if start >= len(buf):
+            return None
+    return None
+
+
+def array_at(image, offset, dtype, dims):
+    """The located array as numpy (a Fortran-ordered view of `image`, as loadmat's arrays are)."""
+    n = int(np.prod(dims, dtype=np.int64))
+    return np.frombuffer(image, dtype=dtype, count=n, offset=offset).reshape(dims, order="F")
+
+
+def read_mat_array(path, name):
+    """`scipy.io.loadmat(path)[name]`: through the library's reader where the file is inside its subset, else through loadmat
+    itself (which reproduces the reference by construction).  -> (array, "native" | "loadmat")."""
+    with open(path, "rb") as f:
+        buf = f.read()
+    hit = locate(buf, name)
+    if hit is not None:
+        return array_at(*hit), "native"
+    from scipy.io import loadmat
+    return loadmat(path)[name], "loadmat"
+
+
+# ------------------------------------------------------------------------------------------------------------------ the recording
+def _host(x):
+    return x.detach().cpu().numpy() if hasattr(x, "detach") else np.asarray(x)
+
+
+class RecordingChunk:
+    """One chunk [start_frame, end_frame): `heat` [n,H,W,J] f32, `est_local` / `est_global` / `gt` [n,J,3] f64, `cams` [n,4,4] f64
+    (device tensors; numpy arrays work for the host-side methods), `gt_list` the ground-truth arrays as the GT pickle holds
+    them, `heat_files` per frame None or the heat-map as loadmat returns it (kept for files that are not float32: the device
+    copy is float32), `initial_mpjpe`."""
+
+    def __init__(self, start_frame, end_frame, heat, est_local, est_global, cams, gt, gt_list=None, heat_files=None, initial_mpjpe=None):
+        self.start_frame, self.end_frame = int(start_frame), int(end_frame)
+        self.heat, self.est_local, self.est_global, self.cams, self.gt = heat, est_local, est_global, cams, gt
+        self.gt_list = gt_list
+        self.heat_files = heat_files
+        self.initial_mpjpe = initial_mpjpe
+        self.n = len(est_local)
+
+    @property
+    def name(self):
+        return "data_start_{}_end_{}".format(self.start_frame, self.end_frame)
+
+
+class Recording:
+    """The chunks of one recording, device-resident.  `heat`, `est_local`, `est_global`, `cams`, `gt`: one tensor per chunk."""
+
+    def __init__(self, chunks):
+        self.chunks = list(chunks)
+
+    def __len__(self):
+        return len(self.chunks)
+
+    heat = property(lambda self: [c.heat for c in self.chunks])
+    est_local = property(lambda self: [c.est_local for c in self.chunks])
+    est_global = property(lambda self: [c.est_global for c in self.chunks])
+    cams = property(lambda self: [c.cams for c in self.chunks])
+    gt = property(lambda self: [c.gt for c in self.chunks])
+
+    def chunk_dict(self, i):
+        """Chunk i as the reference pickles it (:149-155): five keys in its order, every value a list of per-frame arrays;
+        estimated_local_skeleton Fortran-ordered float64, estimated_global_skeleton and camera_pose_list C-ordered float64,
+        heatmap_list [H,W,J] Fortran-ordered in the file's class, the ground truth as the GT pickle held it."""
+        c = self.chunks[i]
+        heat = None
+        heats = []
+        for f in range(c.n):
+            kept = c.heat_files[f] if c.heat_files is not None else None
+            if kept is None:
+                if heat is None:
+                    heat = _host(c.heat)
+                kept = np.asfortranarray(heat[f])
+            heats.append(kept)
+        gt = c.gt_list if c.gt_list is not None else list(_host(c.gt))
+        return {PICKLE_KEYS[0]: gt,
+                PICKLE_KEYS[1]: [np.ascontiguousarray(a, dtype=np.float64) for a in _host(c.est_global)],
+                PICKLE_KEYS[2]: [np.asfortranarray(a, dtype=np.float64) for a in _host(c.est_local)],
+                PICKLE_KEYS[3]: [np.ascontiguousarray(a, dtype=np.float64) for a in _host(c.cams)],
+                PICKLE_KEYS[4]: heats}
+
+    def write_chunk(self, i, out_dir):
+        """`<out_dir>/test_data.pkl` of chunk i (:142-157; default pickle protocol)."""
+        if not os.path.isdir(out_dir):
+            os.makedirs(out_dir)
+        with open(os.path.join(out_dir, "test_data.pkl"), "wb") as f:
+            pickle.dump(self.chunk_dict(i), f)
+
+    def write_chunks(self, out_root):
+        """`<out_root>/data_start_{a}_end_{b}/test_data.pkl` for every chunk; returns the directories."""
+        dirs = []
+        for i, c in enumerate(self.chunks):
+            dirs.append(os.path.join(out_root, c.name))
+            self.write_chunk(i, dirs[-1])
+        return dirs
+
+
+# ------------------------------------------------------------------------------------------------------------------ the device path
+_engines = {}
+
+
+def _lift_engine(camera_model_path, device):
+    """The engine whose handle the lifting kernel runs under (one per calibration and device; its network is never used)."""
+    from .camera import FisheyeCamera
+    from .engine import WindowEngine
+    from .vae import VAEShape
+    key = (os.path.abspath(camera_model_path), device)
+    if key not in _engines:
+        _engines[key] = WindowEngine(VAEShape(latent_dim=64, hidden=(16, 16, 32, 32, 64)), FisheyeCamera.from_json(camera_model_path),
+                                     max_windows=1, device=device)
+    return _engines[key]
+
+
+def _lap(timings, name, t0):
+    """Developer timing (tools/prepare_bench.py): adds the wall time since t0 to timings[name]; returns the new t0."""
+    import time
+    if timings is None:
+        return t0
+    now = time.perf_counter()
+    timings[name] = timings.get(name, 0.0) + (now - t0)
+    return now
+
+
+def _c_paths(paths):
+    return (C.c_char_p * len(paths))(*[os.fsencode(p) for p in paths])
+
+
+def _read_range(lib, cpaths, lo, hi, at, sizes, names, block_ptr, block_len, found, rcs, paths, send=None):
+    """Reader thread: files [lo, hi) into the block (gem_mat_read: the GIL is free); `send(lo, hi)` then starts the range's copy to
+    the device, so that it crosses PCIe while other ranges are still being read.  Then the files the scanner could not take as
+    they are: compressed elements are inflated here (zlib releases the GIL too), files outside the subset go through loadmat.
+    -> ([(index, payload bytes, numpy dtype, dims, array as loadmat returns it or None)] for those, what `send` returned)."""
+    extra, sent = [], None
+    i = lo
+    while i < hi:          # (heat-map files and depth files form contiguous runs: one or two calls)
+        j = i
+        while j < hi and names[j] == names[i]:
+            j += 1
+        _capi.check(lib.gem_mat_read(C.cast(C.byref(cpaths, i * C.sizeof(C.c_char_p)), C.POINTER(C.c_char_p)), j - i,
+                                     C.c_void_p(at.ctypes.data + 8 * i), C.c_void_p(sizes.ctypes.data + 8 * i), names[i].encode(),
+                                     C.c_void_p(block_ptr), block_len,
+                                     C.cast(C.byref(found, i * C.sizeof(_capi.GemMatArray)), C.POINTER(_capi.GemMatArray)),
+                                     C.c_void_p(rcs.ctypes.data + 4 * i)), lib)
+        i = j
+    if send is not None and any(rcs[i] == 0 and not found[i].compressed for i in range(lo, hi)):
+        sent = send(lo, hi)
+    block = (C.c_uint8 * block_len).from_address(block_ptr) if block_len else b""
+    for i in range(lo, hi):
+        if rcs[i] == 0 and not found[i].compressed:
+            continue
+        hit = None
+        if rcs[i] == 0:
+            hit = locate(memoryview(block)[int(at[i]):int(at[i] + sizes[i])], names[i])
+        if hit is not None:
+            a = array_at(*hit)
+            extra.append((i, a.tobytes(order="F"), a.dtype.type, a.shape, None))
+        else:
+            from scipy.io import loadmat
+            a = loadmat(paths[i])[names[i]]
+            dev = a if a.dtype in (np.float32, np.float64) else a.astype(np.float32 if names[i] == HEAT_NAME else np.float64)
+            extra.append((i, dev.tobytes(order="F"), dev.dtype.type, a.shape, a))
+        rcs[i] = -1          # (its payload travels in the extra block)
+    return extra, sent
+
+
+def frames_to_device(heat_paths, depth_paths, device=None, readers=N_READERS, timings=None):
+    """The frames' .mat files -> (heat [n,H,W,J] f32, depth [n,J] f64, heat_files) on `device`: every file is read once into a
+    pinned block (reader threads, `gem_mat_read`), the block crosses PCIe range by range on the readers' two copy streams while
+    the other ranges are still being read (one more copy for inflated or loadmat'ed payloads), and ONE launch of `gem_mat_frames` picks all frames out.  heat_files[f]: None, or the heat-map as loadmat returns
+    it where the device copy (float32) is not the file's own class."""
+    import torch
+    from .whole_sequence import _pool, copy_stream
+    lib = _capi.load_library()
+    device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    n = len(heat_paths)
+    if len(depth_paths) != n:
+        raise ValueError("as many depth files as heat-map files are needed (%d / %d)" % (len(depth_paths), n))
+    if n == 0:
+        return torch.empty((0, 64, 64, 15), device=device), torch.empty((0, 15), dtype=torch.float64, device=device), []
+    import time
+    t0 = time.perf_counter()
+    paths = list(heat_paths) + list(depth_paths)
+    names = [HEAT_NAME] * n + [DEPTH_NAME] * n
+    cpaths = _c_paths(paths)
+    sizes = np.empty(2 * n, dtype=np.int64)
+    readers = max(1, min(readers, 2 * n))
+    pool = _pool("mat", readers)
+
+    def stat_range(lo, hi):
+        _capi.check(lib.gem_files_sizes(C.cast(C.byref(cpaths, lo * C.sizeof(C.c_char_p)), C.POINTER(C.c_char_p)), hi - lo,
+                                        C.c_void_p(sizes.ctypes.data + 8 * lo)), lib)
+    cut = [2 * n * k // readers for k in range(readers + 1)]
+    for j in [pool.submit(stat_range, lo, hi) for lo, hi in zip(cut[:-1], cut[1:]) if hi > lo]:
+        j.result()
+    room = (sizes + 8 + _ALIGN - 1) // _ALIGN * _ALIGN
+    at = np.concatenate([[0], np.cumsum(room)[:-1]]).astype(np.int64)
+    total = int(room.sum())
+    t0 = _lap(timings, "file sizes (one stat each)", t0)
+    block = torch.empty(total, dtype=torch.uint8, pin_memory=True)          # (torch keeps freed pinned blocks for the next call)
+    found = (_capi.GemMatArray * (2 * n))()
+    rcs = np.zeros(2 * n, dtype=np.int32)
+    t0 = _lap(timings, "pinned block", t0)
+    arena = torch.empty(total + 8, dtype=torch.uint8, device=device)
+    cur = torch.cuda.current_stream()
+    allocated = torch.cuda.Event()
+    allocated.record(cur)
+
+    def send(lo, hi):
+        """Files [lo, hi) of the block to their place in the arena, on one of the two copy streams -> the event behind the copy."""
+        st = copy_stream(device)
+        b0, b1 = int(at[lo]), int(at[hi - 1] + room[hi - 1])
+        st.wait_event(allocated)
+        with torch.cuda.stream(st):
+            arena[b0:b1].copy_(block[b0:b1], non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(st)
+        arena.record_stream(st)
+        return ev
+    # heat-map files are 2000 times the depth files: the ranges are cut by bytes, not by count; four ranges per reader, so that
+    # the first copies start early
+    cuts = np.searchsorted(np.cumsum(room), np.linspace(0, total, 4 * readers + 1)[1:-1]).tolist()
+    bounds = sorted(set([0] + [int(c) for c in cuts] + [2 * n]))
+    jobs = [pool.submit(_read_range, lib, cpaths, lo, hi, at, sizes, names, block.data_ptr(), total, found, rcs, paths, send)
+            for lo, hi in zip(bounds[:-1], bounds[1:]) if hi > lo]
+    extra = []
+    for j in jobs:
+        e, sent = j.result()
+        extra += e
+        if sent is not None:
+            cur.wait_event(sent)
+    t0 = _lap(timings, "read + scan (+ inflate / loadmat) on the reader threads", t0)
+    # tables: where every frame's payloads lie in the arena, and their types
+    where = np.zeros(2 * n, dtype=np.int64)
+    dtypes, dims = [None] * (2 * n), [None] * (2 * n)
+    heat_files = [None] * n
+    for i in range(2 * n):
+        if rcs[i] == 0:
+            a = found[i]
+            where[i], dtypes[i], dims[i] = at[i] + a.offset, _NP_OF[a.storage], tuple(int(d) for d in a.dims[:a.ndim])
+    extra_at, parts = total, []
+    for i, payload, dt, shape, kept in extra:
+        if i >= n and len(shape) == 2 and shape[0] != 1:          # depth = loadmat(...)['depth'][0]: the first ROW
+            payload, shape = np.frombuffer(payload, dtype=dt).reshape(shape, order="F")[:1].tobytes(), (1, shape[1])
+        where[i], dtypes[i], dims[i] = extra_at, dt, tuple(shape)
+        parts.append((extra_at, payload))
+        extra_at += (len(payload) + 8 + _ALIGN - 1) // _ALIGN * _ALIGN
+        if i < n and (kept is not None or dt is not np.float32):
+            heat_files[i] = kept if kept is not None else np.frombuffer(payload, dtype=dt).reshape(shape, order="F")
+    for i in range(n, 2 * n):          # a depth array of several rows inside the main block: its first row is strided there
+        if rcs[i] == 0 and (len(dims[i]) != 2 or dims[i][0] != 1):
+            if len(dims[i]) != 2:
+                raise ValueError("%s: 'depth' is not a [1,J] array" % paths[i])
+            row = array_at(memoryview((C.c_uint8 * total).from_address(block.data_ptr())), int(where[i]), dtypes[i], dims[i])[:1]
+            where[i], dims[i] = extra_at, (1, dims[i][1])
+            parts.append((extra_at, row.tobytes()))
+            extra_at += (row.nbytes + 8 + _ALIGN - 1) // _ALIGN * _ALIGN
+    for f in range(n):          # float64 heat-maps inside the main block: the pickle wants them as they are
+        if rcs[f] == 0 and dtypes[f] is np.float64:
+            heat_files[f] = array_at(memoryview((C.c_uint8 * total).from_address(block.data_ptr())), int(where[f]), np.float64, dims[f]).copy(order="F")
+    shapes = {dims[f] for f in range(n)}
+    if len(shapes) != 1 or len(next(iter(shapes))) != 3:
+        raise ValueError("the heat-maps must all be [H,W,J] arrays of one shape, found %s" % sorted(shapes))
+    H, W, J = next(iter(shapes))
+    if any(dims[i] != (1, J) for i in range(n, 2 * n)):
+        raise ValueError("every depth file must hold a [1,%d] array" % J)
+    kinds = np.zeros(n, dtype=np.int32)
+    for f in range(n):
+        kinds[f] = (_capi.MAT_HEAT_F64 if dtypes[f] is np.float64 else 0) | (_capi.MAT_DEPTH_F32 if dtypes[n + f] is np.float32 else 0)
+    t0 = _lap(timings, "payload tables", t0)
+    if parts:          # the payloads that are not in the files as they are land behind the block's image, in the same arena
+        whole = torch.empty(extra_at + 8, dtype=torch.uint8, device=device)
+        if (rcs == 0).any():
+            whole[:total].copy_(arena[:total])
+        side = torch.empty(extra_at - total, dtype=torch.uint8, pin_memory=True)
+        sv = side.numpy()
+        for o, payload in parts:
+            sv[o - total:o - total + len(payload)] = np.frombuffer(payload, dtype=np.uint8)
+        whole[total:extra_at].copy_(side, non_blocking=True)
+        arena = whole
+    tables = torch.from_numpy(np.concatenate([where, kinds.astype(np.int64)])).to(device)
+    kinds_d = tables[2 * n:].to(torch.int32)
+    heat = torch.empty((n, H, W, J), dtype=torch.float32, device=device)
+    depth = torch.empty((n, J), dtype=torch.float64, device=device)
+    mat_frames(arena, extra_at, tables[:n], tables[n:2 * n], kinds_d, heat, depth)
+    torch.cuda.current_stream().synchronize()          # (the pinned blocks are released on return)
+    _lap(timings, "copies' tail + gem_mat_frames", t0)
+    return heat, depth, heat_files
+
+
+def mat_frames(arena, image_len, heat_offsets, depth_offsets, kinds, heat, depth):
+    """gem_mat_frames on the current stream: arena (uint8 device tensor), int64 / int64 / int32 device tables -> heat, depth."""
+    import torch
+    lib = _capi.load_library()
+    n, H, W, J = heat.shape
+    _capi.check(lib.gem_mat_frames(C.c_void_p(arena.data_ptr()), int(image_len), C.c_void_p(heat_offsets.data_ptr()),
+                                   C.c_void_p(depth_offsets.data_ptr()), C.c_void_p(kinds.data_ptr()), n, H, W, J,
+                                   C.c_void_p(heat.data_ptr()), C.c_void_p(depth.data_ptr()),
+                                   C.c_void_p(torch.cuda.current_stream().cuda_stream)), lib)
+
+
+def prepare_global(est_local, cams, gt):
+    """gem_prepare_global on the current stream: -> (est_global [n,J,3] f64, per-frame mean joint distance to gt [n] f64)."""
+    import torch
+    lib = _capi.load_library()
+    n, J = est_local.shape[0], est_local.shape[1]
+    out = torch.empty_like(est_local)
+    err = torch.empty(n, dtype=torch.float64, device=est_local.device)
+    _capi.check(lib.gem_prepare_global(C.c_void_p(est_local.data_ptr()), C.c_void_p(cams.data_ptr()), C.c_void_p(gt.data_ptr()), n, J,
+                                       C.c_void_p(out.data_ptr()), C.c_void_p(err.data_ptr()),
+                                       C.c_void_p(torch.cuda.current_stream().cuda_stream)), lib)
+    return out, err
+
+
+def prepare_spans(slam_result_path, heatmap_dir, depth_dir, gt_path, spans, fps, mat_start_frame, camera_model_path=None, device=None,
+                  timings=None):
+    """Every (start_frame, end_frame) of `spans` as one chunk, each prepared on its own as `main` does, all of them through the
+    device together: stage -> gem_mat_frames -> lift -> head joints to the host -> per-chunk scale and cameras -> cameras up ->
+    gem_prepare_global.  -> Recording."""
+    import torch
+    from . import slam
+    from .camera import DEFAULT_CALIBRATION
+    import time
+    t0 = time.perf_counter()
+    device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    with open(slam_result_path) as f:
+        text = slam.trajectory_rows(f.read())          # (parsed once for all chunks)
+    pose_gt = read_gt(gt_path)
+    heat_names = sorted(os.listdir(heatmap_dir), key=natural_key)
+    depth_names = sorted(os.listdir(depth_dir), key=natural_key)
+    heat_paths, depth_paths, gts, bounds = [], [], [], []
+    for a, b in spans:
+        check_trajectory(text, a, b, fps)
+        hp, dp = heat_names[a:b], depth_names[a:b]
+        if len(hp) != b - a or len(dp) != b - a:
+            raise ValueError("frames [%d, %d) of the listings are asked for, but %s holds %d files and %s holds %d" %
+                             (a, b, heatmap_dir, len(heat_names), depth_dir, len(depth_names)))
+        bounds.append((len(heat_paths), len(heat_paths) + b - a))
+        heat_paths += [os.path.join(heatmap_dir, x) for x in hp]
+        depth_paths += [os.path.join(depth_dir, x) for x in dp]
+        gts.append(gt_clip(pose_gt, a, b, mat_start_frame))
+    if not spans:
+        return Recording([])
+    t0 = _lap(timings, "listings, ground truth, trajectory", t0)
+    with torch.cuda.device(device):
+        heat, depth, heat_files = frames_to_device(heat_paths, depth_paths, device, timings=timings)
+        t0 = time.perf_counter()
+        engine = _lift_engine(camera_model_path or DEFAULT_CALIBRATION, device.index)
+        if tuple(heat.shape[1:3]) != tuple(engine.heat_size):
+            raise ValueError("heat-maps of %d x %d: the lifting kernel is built for %d x %d" % (tuple(heat.shape[1:3]) + tuple(engine.heat_size)))
+        est_local, _ = engine.lift_skeleton(heat, depth)
+        heads = est_local[:, 0].cpu().numpy()
+        t0 = _lap(timings, "lift + head joints to the host", t0)
+        gt_all = np.concatenate([np.asarray(g, dtype=np.float64) for g in gts])
+        cams = np.concatenate([slam.camera_pose_list_from_heads(text, heads[lo:hi], gt_all[lo:hi, 0], a, b, fps)[0]
+                               for (a, b), (lo, hi) in zip(spans, bounds)])
+        t0 = _lap(timings, "per-chunk scale and cameras (host)", t0)
+        cams_d, gt_d = torch.from_numpy(cams).to(device), torch.from_numpy(gt_all).to(device)
+        est_global, err = prepare_global(est_local, cams_d, gt_d)
+        err = err.cpu().numpy()
+        _lap(timings, "cameras up + gem_prepare_global + errors back", t0)
+    chunks = []
+    for (a, b), (lo, hi), g in zip(spans, bounds, gts):
+        kept = heat_files[lo:hi]
+        chunks.append(RecordingChunk(a, b, heat[lo:hi], est_local[lo:hi], est_global[lo:hi], cams_d[lo:hi], gt_d[lo:hi], gt_list=g,
+                                     heat_files=kept if any(k is not None for k in kept) else None,
+                                     initial_mpjpe=float(np.mean(err[lo:hi]))))
+    return Recording(chunks)
+
+
+def main(slam_result_path, heatmap_dir, depth_dir, gt_path, start_frame, end_frame, out_dir, fps, mat_start_frame,
+         camera_model_path=None):
+    """The reference's `main` (:126-165): one chunk [start_frame, end_frame) -> `<out_dir>/test_data.pkl`, and the line
+    `The initial mpjpe is: ...`.  Returns the one-chunk Recording (the reference returns nothing)."""
+    rec = prepare_spans(slam_result_path, heatmap_dir, depth_dir, gt_path, [(start_frame, end_frame)], fps, mat_start_frame,
+                        camera_model_path)
+    rec.write_chunk(0, out_dir)
+    print("The initial mpjpe is: {}".format(rec.chunks[0].initial_mpjpe))
+    return rec
+
+
+def prepare_sequence(slam_result_path, heatmap_dir, depth_dir, gt_path, total_start_frame, total_end_frame, fps=25, mat_start_frame=None,
+                     test_size=100, out_root=None, camera_model_path=None, verbose=True):
+    """The reference's chunk loop (:176-190): chunks of `test_size` frames from `total_start_frame` (see `chunk_spans` for the
+    chunk it drops), `mat_start_frame` defaulting to `total_start_frame` as there.  All chunks go through the device together,
+    each prepared on its own.  Returns the Recording; with `out_root`, `data_start_{a}_end_{b}/test_data.pkl` are written too."""
+    spans = chunk_spans(total_start_frame, total_end_frame, test_size)
+    rec = prepare_spans(slam_result_path, heatmap_dir, depth_dir, gt_path, spans, fps,
+                        total_start_frame if mat_start_frame is None else mat_start_frame, camera_model_path)
+    for c in rec.chunks:
+        if verbose:
+            print("running test sequence from {} to {}".format(c.start_frame, c.end_frame))
+            print("The initial mpjpe is: {}".format(c.initial_mpjpe))
+    if out_root is not None:
+        rec.write_chunks(out_root)
+    return rec
+
+
+def _cli():
+    import argparse
+    from .camera import DEFAULT_CALIBRATION
+    p = argparse.ArgumentParser(description="recording (.mat files of the pose network) -> chunks for the optimiser")
+    p.add_argument("--slam", required=True, help="SLAM trajectory: lines `time tx ty tz qx qy qz qw`")
+    p.add_argument("--heatmaps", required=True, help="directory of per-frame heatmap .mat files")
+    p.add_argument("--depths", required=True, help="directory of per-frame depth .mat files")
+    p.add_argument("--gt", required=True, help="ground-truth pickle (it fixes the SLAM scale)")
+    p.add_argument("--start", required=True, type=int)
+    p.add_argument("--end", required=True, type=int)
+    p.add_argument("--fps", type=float, default=25)
+    p.add_argument("--mat_start", type=int, default=None, help="frame id of the GT pickle's first entry (default: --start)")
+    p.add_argument("--test_size", type=int, default=100)
+    p.add_argument("--out", default=None, help="directory for data_start_{a}_end_{b}/test_data.pkl")
+    p.add_argument("--camera", default=DEFAULT_CALIBRATION)
+    p.add_argument("--optimize", action="store_true", help="optimise the recording right away (no pickle in between)")
+    a = p.parse_args()
+    if a.out is None and not a.optimize:
+        p.error("nothing to do: give --out, --optimize or both")
+    rec = prepare_sequence(a.slam, a.heatmaps, a.depths, a.gt, a.start, a.end, a.fps, a.mat_start, a.test_size, a.out, a.camera)
+    if a.optimize:
+        from .whole_sequence import optimize_recording
+        optimize_recording(rec, a.camera)
+
+
+if __name__ == "__main__":
+    _cli()

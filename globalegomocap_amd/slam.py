@@ -29,12 +29,18 @@ def pose_matrix(trans, quat):
 
 def parse_trajectory(lines, start_frame, end_frame, fps=30):
     """-> (trans [n,3], quat [n,4]) of the lines whose frame id round(t * fps) lies in [start_frame, end_frame).
-    `lines`: an iterable of text lines `time tx ty tz qx qy qz qw` (blank lines are skipped) or the whole file as one string."""
-    text = lines if isinstance(lines, str) else "\n".join(lines)
-    rows = np.array(text.split(), dtype=np.float64).reshape(-1, 8)
+    `lines`: an iterable of text lines `time tx ty tz qx qy qz qw` (blank lines are skipped), the whole file as one string, or
+    the rows already parsed (`trajectory_rows`: a float64 array [m,8])."""
+    rows = lines if isinstance(lines, np.ndarray) else trajectory_rows(lines)
     frame = np.rint(rows[:, 0] * fps)                   # python's round(): half to even, like rint
     keep = (frame >= start_frame) & (frame < end_frame)
     return rows[keep, 1:4].copy(), rows[keep, 4:8].copy()
+
+
+def trajectory_rows(lines):
+    """The trajectory's numbers as a float64 array [m,8] (parsed once by callers that select several ranges from one file)."""
+    text = lines if isinstance(lines, str) else "\n".join(lines)
+    return np.array(text.split(), dtype=np.float64).reshape(-1, 8)
 
 
 def relative_poses(trans, quat):
@@ -61,6 +67,27 @@ def camera_pose_list(lines, local_pose_list, gt_global_pose, start_frame, end_fr
     head_local = np.asarray(local_pose_list, dtype=np.float64)[:n, 0]
     slam_head = np.einsum("nij,nj->ni", pose_matrix(rt, rq)[:, :3, :3], head_local) + rt
     gt_head = gt[:n, 0]
+    c, _, _ = umeyama(slam_head, gt_head)
+    _, R_1, t_1 = umeyama(gt_head, slam_head)
+    return pose_matrix(rt * c, rq), R_1, t_1
+
+
+def frame_ids(lines, fps=30):
+    """The frame id round(t * fps) of every trajectory line, in file order (what `parse_trajectory` selects by)."""
+    rows = lines if isinstance(lines, np.ndarray) else trajectory_rows(lines)
+    return np.rint(rows[:, 0] * fps).astype(np.int64)
+
+
+def camera_pose_list_from_heads(lines, head_local, gt_head, start_frame, end_frame, fps=30):
+    """`camera_pose_list` for callers that hold the lifted skeletons on the device: the Umeyama scale needs the head joint only,
+    so this takes `head_local` [n,3] (estimated_local_skeleton[:, 0]) and `gt_head` [n,3] (gt_global_skeleton[:, 0]) instead of
+    the whole skeletons.  Same arithmetic, same result -> ([n,4,4], R_1, t_1)."""
+    trans, quat = parse_trajectory(lines, start_frame, end_frame, fps)
+    rt, rq = relative_poses(trans, quat)
+    n = len(rt)
+    head_local = np.asarray(head_local, dtype=np.float64)[:n]
+    slam_head = np.einsum("nij,nj->ni", pose_matrix(rt, rq)[:, :3, :3], head_local) + rt
+    gt_head = np.asarray(gt_head, dtype=np.float64)[:n]
     c, _, _ = umeyama(slam_head, gt_head)
     _, R_1, t_1 = umeyama(gt_head, slam_head)
     return pose_matrix(rt * c, rq), R_1, t_1

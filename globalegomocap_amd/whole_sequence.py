@@ -393,7 +393,8 @@ class _Batch:
 def optimize_sequences(data_dirs, camera_model_path, vae_weight=0.0, gmm_weight=0.0, smoothness_weight=0.001,
                        bone_length_weight=0.01, weight_3d=0.01, reproj_weight=0.01, final_smooth=True, merge=True,
                        global_vae_path=GLOBAL_VAE_PATH, local_vae_path=LOCAL_VAE_PATH, chunks_per_batch=None, optimizer=None,
-                       device_metrics=True, verbose=True, seq_len=SEQ_LEN, overlap=OVERLAP, timings=None, per_sequence=False):
+                       device_metrics=True, verbose=True, seq_len=SEQ_LEN, overlap=OVERLAP, timings=None, per_sequence=False,
+                       _recordings=None):
     """Several sequences through the device: the chunks of every directory of `data_dirs`, `chunks_per_batch` per device call
     (default: all of them in ONE call -- BASELINE configs[2]: all test sequences concurrently on one GPU; per_sequence=True: one
     call per directory), the reports per sequence.  Returns a list of (summary, per-chunk error dicts, estimated_pose,
@@ -419,9 +420,13 @@ def optimize_sequences(data_dirs, camera_model_path, vae_weight=0.0, gmm_weight=
             timings[name] = timings.get(name, 0.0) + (now - tick[0])
             timings.setdefault("_log", []).append((round((now - t_begin) * 1e3, 2), name))
             tick[0] = now
-    groups, group_of = [], {}
+    groups, group_of, resident = [], {}, {}
+    if _recordings is not None:          # (optimize_recordings: the chunks are on the device already, nothing is read or parsed)
+        data_dirs = ["recording_%d" % gi for gi in range(len(_recordings))]
+        for d, rec in zip(data_dirs, _recordings):
+            resident.update((os.path.join(d, c.name), c) for c in rec.chunks)
     for gi, d in enumerate(data_dirs):
-        ps = list_chunks(d)
+        ps = list_chunks(d) if _recordings is None else [os.path.join(d, c.name) for c in _recordings[gi].chunks]
         if not ps:
             raise FileNotFoundError("no chunk directories under %s" % d)
         for q in ps:
@@ -444,6 +449,10 @@ def optimize_sequences(data_dirs, camera_model_path, vae_weight=0.0, gmm_weight=
     def start(b):
         """Batch b's files start moving: read tasks (they need the files' sizes only) and, beside them, the parse tasks."""
         if b.reading is not None:
+            return
+        if resident:
+            b.sizes, b.images, b.reading = [0] * len(b.paths), [None] * len(b.paths), []
+            b.parsing = [_Ready(_resident_chunk(resident[q], q)) for q in b.paths]
             return
         b.sizes = [os.path.getsize(f) for f in b.files]          # (FileNotFoundError here, like the reference's open())
         at, total = [], 0
@@ -483,7 +492,7 @@ def optimize_sequences(data_dirs, camera_model_path, vae_weight=0.0, gmm_weight=
                              (n_win, opt[0].engine.max_windows))
         b.noise = noise_pool.submit(_draw_noise, [2 * len(c["starts"]) for c in b.chunks], opt[0].engine.D, b.index % N_BUFFERS)
         submitted.append(b.noise)
-        b.listed = [(i, read_pool.submit(stage_list, c, device)) for i, c in enumerate(b.chunks) if "heat_offsets" not in c]
+        b.listed = [(i, read_pool.submit(stage_list, c, device)) for i, c in enumerate(b.chunks) if "heat_list" in c]
         submitted.extend(f for _, f in b.listed)      # (files the library's reader declined: stacked on the host)
         b.weights = opt[0].stage_weights(vae_weight, smoothness_weight, bone_length_weight, weight_3d, reproj_weight)
         b.est_cat = np.concatenate([c["est_local"] for c in b.chunks])
@@ -562,6 +571,9 @@ def optimize_sequences(data_dirs, camera_model_path, vae_weight=0.0, gmm_weight=
             cur.wait_event(ev)
             t.record_stream(cur)
             parts[i] = b.dests[i].copy_(t) if b.dests[i] is not None else t
+        for i, c in enumerate(b.chunks):
+            if "heat" in c:                           # a Recording's chunk: device to device
+                parts[i] = b.dests[i].copy_(c["heat"]) if b.dests[i] is not None else c["heat"]
         lap("wait for the readers")
         if b.index + 1 < len(batches):               # the next batch's files start moving behind this batch's last copy: they arrive
             start(batches[b.index + 1])              # while this batch is on the device
@@ -691,6 +703,42 @@ def optimize_sequences(data_dirs, camera_model_path, vae_weight=0.0, gmm_weight=
         out.append((summary, results[gi]) + tuple(np.concatenate(x) if x else np.empty((0, 15, 3)) for x in (est_all[gi], opt_all[gi], gt_all[gi])))
     lap("summaries")
     return out
+
+
+class _Ready:
+    """A result that is there already, where the pipeline expects a future."""
+
+    def __init__(self, value):
+        self._value = value
+
+    def result(self):
+        return self._value
+
+
+def _resident_chunk(c, path):
+    """A `prepare.RecordingChunk` as the pipeline's ParsedChunk: the small arrays on the host (float64, the very values a pickle of
+    them would hold), the heat-maps where they are."""
+    host = lambda t: np.ascontiguousarray(t.detach().cpu().numpy() if hasattr(t, "detach") else t, dtype=np.float64)      # noqa: E731
+    heat = c.heat if hasattr(c.heat, "detach") else torch.as_tensor(np.asarray(c.heat, dtype=np.float32))
+    heat = heat.to(torch.device("cuda", torch.cuda.current_device()), dtype=torch.float32).contiguous()
+    return ParsedChunk(path=path, est_local=host(c.est_local), gt=host(c.gt), cams=host(c.cams), n=int(heat.shape[0]),
+                       heat_shape=tuple(heat.shape[1:]), heat=heat)
+
+
+def optimize_recordings(recordings, camera_model_path, *args, **kwargs):
+    """`optimize_sequences` for recordings that `prepare.prepare_sequence` left on the device: same keyword arguments, return
+    value and printed summary, one entry per `Recording`; no pickle is written or read.  The optimiser is handed the same
+    float32 heat-maps, float64 skeletons and cameras that `Recording.write_chunks` + `optimize_sequences` would hand it, so
+    the results are bitwise those."""
+    for r in recordings:
+        if not len(r):
+            raise FileNotFoundError("a recording without chunks")
+    return optimize_sequences(None, camera_model_path, *args, _recordings=list(recordings), **kwargs)
+
+
+def optimize_recording(recording, camera_model_path, *args, **kwargs):
+    """One `prepare.Recording` = `optimize_directory` on the chunks it would write.  Arguments and result as there."""
+    return optimize_recordings([recording], camera_model_path, *args, **kwargs)[0]
 
 
 def release_pools():

@@ -284,6 +284,60 @@ int     gem_chunk_gather_f64(const gem_chunk* c, int key, double* h_out, int64_t
 int gem_file_stage(const char* path, int device, void* h_pinned, void* d_image, int64_t buffer_bytes, int64_t slice_bytes,
                    int64_t* file_bytes, void* stream);
 
+/* ---- recordings as the pose network writes them: one `heatmap` .mat and one `depth` .mat per frame ----
+ * What MakeDataForOptimization/process_test_data.py:52-68 reads with scipy.io.loadmat, frame by frame.  The host-side calls need no
+ * GPU and no gem_handle. */
+enum { GEM_MAT_UNSUPPORTED = 2, GEM_MAT_NOT_FOUND = 3 };  /* return codes: outside the subset -- use scipy.io.loadmat; no such variable */
+enum { GEM_MAT_HEAT_F64 = 1, GEM_MAT_DEPTH_F32 = 2 };     /* bits of gem_mat_frames' per-frame `kinds` */
+
+typedef struct gem_mat_array {
+    int64_t offset;         /* out: of the real part's raw data in the image (compressed = 1: of the zlib stream) */
+    int64_t nbytes;         /* out: its length = product of dims * item size (compressed = 1: of the zlib stream) */
+    int64_t next;           /* out: where the element after the reported one starts */
+    int64_t start;          /* IN:  where to resume (0: at the first element) */
+    int32_t bare;           /* IN:  1 = the image is a run of data elements without the 128-byte file header (an inflated element) */
+    int32_t compressed;     /* out: 1 = an miCOMPRESSED element was met before the variable was found */
+    int32_t mat_class;      /* out: 6 = mxDOUBLE_CLASS, 7 = mxSINGLE_CLASS */
+    int32_t storage;        /* out: 7 = miSINGLE, 9 = miDOUBLE */
+    int32_t ndim;           /* out: 1..4 */
+    int32_t reserved;
+    int64_t dims[4];        /* out: unused trailing dimensions are 1; the data are column-major */
+} gem_mat_array;
+
+/* Interprets the Level-5 MAT file in h_image[0, len) and LOCATES the numeric array called `name`; copies nothing.  Accepted:
+ * little-endian files of version 0x0100; class single stored as miSINGLE, class double stored as miDOUBLE; small data elements;
+ * other variables in front (of several variables of that name the last one is reported, as loadmat's dict keeps it).  When an
+ * miCOMPRESSED element is met first, it is reported instead (compressed = 1, offset / nbytes of its zlib stream): the caller
+ * inflates it, scans the result with bare = 1 and, on GEM_MAT_NOT_FOUND, resumes in the file with start = next.
+ * GEM_MAT_UNSUPPORTED, always with a reason in gem_last_error: big-endian, v4 and v7.3 (HDF5) files, complex, sparse, logical,
+ * character, cell, struct and object arrays, integer classes, a double array stored in a narrower type (loadmat returns that one in
+ * its storage type), more than four dimensions, and any length or offset that does not fit its container. */
+int gem_mat_scan(const void* h_image, int64_t len, const char* name, gem_mat_array* out);
+
+/* sizes[i] = size of paths[i] in bytes (one stat each; fails on the first missing file). */
+int gem_files_sizes(const char* const* paths, int64_t n, int64_t* sizes);
+
+/* n files into one block of host memory (pinned, for the copy that follows): paths[i] is read to h_block + at[i] (sizes[i] bytes, as
+ * gem_files_sizes reported them) and scanned for `name` there: out[i] as gem_mat_scan fills it (offsets relative to the file's own
+ * start), rc_out[i] its return code.  Returns non-zero only when a file cannot be read.  Holds no lock: call it from several threads
+ * on disjoint ranges of one block. */
+int gem_mat_read(const char* const* paths, int64_t n, const int64_t* at, const int64_t* sizes, const char* name, void* h_block,
+                 int64_t block_bytes, gem_mat_array* out, int32_t* rc_out);
+
+/* ONE launch: the device image d_image[0, image_len) of such a block -> d_heat [n,heat_h,heat_w,n_joints] f32, bit for bit
+ * `torch.from_numpy(loadmat(f)['heatmap']).float()`, and d_depth [n,n_joints] f64 = `loadmat(f)['depth'][0]`.  d_heat_offsets /
+ * d_depth_offsets [n]: byte position of every frame's payloads in the image (any alignment; bytes outside the image read as zero);
+ * d_kinds [n]: GEM_MAT_HEAT_F64 when the frame's heat-map is stored as double (rounded to nearest even), GEM_MAT_DEPTH_F32 when its
+ * depths are stored as single (widened exactly).  Alignment requirements as gem_heat_gather. */
+int gem_mat_frames(const void* d_image, int64_t image_len, const int64_t* d_heat_offsets, const int64_t* d_depth_offsets,
+                   const int32_t* d_kinds, int64_t n, int heat_h, int heat_w, int n_joints, float* d_heat, double* d_depth, void* stream);
+
+/* process_test_data.py:70-79 for all frames of a batch of chunks: d_est_global [n,J,3] = R_f . d_est_local[f] + t_f with
+ * d_cams [n,4,4] (row-major camera-to-world, the SCALED trajectory), float64, no fused multiply-adds; d_frame_error [n] (may be
+ * NULL) = mean_j |d_gt - d_est_global| per frame, the terms of main()'s "initial mpjpe" (:160-165). */
+int gem_prepare_global(const double* d_est_local, const double* d_cams, const double* d_gt, int64_t n_frames, int n_joints,
+                       double* d_est_global, double* d_frame_error, void* stream);
+
 /* Timing hook for bench.py's roofline: average device time (ms) of the launches of the dominant
  * kernel family since the last reset, measured with HIP events on the launch stream.
  * family: 0 = decoder_input GEMMs (forward + backward-data), 1 = fused tail / energy kernel, 2 = L-BFGS advance,
