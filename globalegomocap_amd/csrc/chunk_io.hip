@@ -360,13 +360,14 @@ __device__ __forceinline__ uint32_t word_at(const HeatArgs& a, int64_t at) {
     return __builtin_amdgcn_alignbyte(hi, lo, m);
 }
 
+// the double whose two words start at BYTE address `at`, whatever its alignment
+__device__ __forceinline__ double double_at(const HeatArgs& a, int64_t at) {
+    return __longlong_as_double((long long)((uint64_t)word_at(a, at) | ((uint64_t)word_at(a, at + 4) << 32)));
+}
+
 template <bool F64>
 __device__ __forceinline__ float element_at(const HeatArgs& a, int64_t payload, int64_t e) {
-    if (F64) {
-        const int64_t at = payload + 8 * e;
-        const uint64_t bits = (uint64_t)word_at(a, at) | ((uint64_t)word_at(a, at + 4) << 32);
-        return (float)__longlong_as_double((long long)bits);          // round to nearest even, as ndarray.astype / Tensor.float do
-    }
+    if (F64) return (float)double_at(a, payload + 8 * e);          // round to nearest even, as ndarray.astype / Tensor.float do
     return __uint_as_float(word_at(a, payload + 4 * e));
 }
 
@@ -394,20 +395,25 @@ __global__ __launch_bounds__(256) void heat_copy_kernel(HeatArgs a) {
 // H + 1 per (j, w) run and WT * (H + 1) + 5 per joint keep both sides at two-way bank conflicts at most.  HC / WC / JC / WTC: the geometry as constants (0 = from the arguments;
 // the 64 x 64 x 15 maps of the path divide by constants only).
 constexpr int TR_PAD_J = 5;
+
+// The way in: columns [w0, w0 + wn) of the frame whose payload starts at byte `payload` of the image -> the LDS tile.
 template <bool F64, int HC, int WC, int JC, int WTC>
-__global__ __launch_bounds__(256) void heat_transpose_kernel(HeatArgs a) {
-    extern __shared__ float tile[];
+__device__ __forceinline__ void tile_in(const HeatArgs& a, float* tile, int64_t payload, int w0, int wn) {
     const int H = HC ? HC : a.H, W = WC ? WC : a.W, J = JC ? JC : a.J, WT = WTC ? WTC : a.TH;
-    const int f = blockIdx.y, w0 = blockIdx.x * WT, wn = WTC ? WTC : min(WT, W - w0);
     const int PH = H + 1, PJ = WT * PH + TR_PAD_J;
-    const int64_t payload = a.offsets[f];
     const int run = wn * H;                           // elements of one joint's run
 #pragma unroll 4
     for (int r = threadIdx.x; r < J * run; r += 256) {
         const int j = r / run, rem = r - j * run, w = rem / H, h = rem - w * H;
         tile[j * PJ + w * PH + h] = element_at<F64>(a, payload, ((int64_t)j * W + w0) * H + rem);
     }
-    __syncthreads();
+}
+
+// The way out: the LDS tile -> columns [w0, w0 + wn) of frame f of a.out.
+template <int HC, int WC, int JC, int WTC>
+__device__ __forceinline__ void tile_out(const HeatArgs& a, const float* tile, int f, int w0, int wn) {
+    const int H = HC ? HC : a.H, W = WC ? WC : a.W, J = JC ? JC : a.J, WT = WTC ? WTC : a.TH;
+    const int PH = H + 1, PJ = WT * PH + TR_PAD_J;
     float* dst = a.out + ((int64_t)f * H * W + w0) * J;
     const int orun = wn * J;                          // floats of one output row's run
 #pragma unroll 4
@@ -415,6 +421,40 @@ __global__ __launch_bounds__(256) void heat_transpose_kernel(HeatArgs a) {
         const int h = r / orun, rem = r - h * orun, w = rem / J, j = rem - w * J;
         dst[(int64_t)h * W * J + rem] = tile[j * PJ + w * PH + h];
     }
+}
+
+template <bool F64, int HC, int WC, int JC, int WTC>
+__global__ __launch_bounds__(256) void heat_transpose_kernel(HeatArgs a) {
+    extern __shared__ float tile[];
+    const int W = WC ? WC : a.W, WT = WTC ? WTC : a.TH;
+    const int f = blockIdx.y, w0 = blockIdx.x * WT, wn = WTC ? WTC : min(WT, W - w0);
+    tile_in<F64, HC, WC, JC, WTC>(a, tile, a.offsets[f], w0, wn);
+    __syncthreads();
+    tile_out<HC, WC, JC, WTC>(a, tile, f, w0, wn);
+}
+
+// The launchers' choice of columns per workgroup and the LDS bytes that go with it: 8 columns (31 KB of LDS at 64 x 64 x 15: five
+// workgroups per CU hide the loads' latency; 16 columns -- two workgroups per CU -- measured 0.71 against 0.34 ms for 2000 frames,
+// 2.9 TB/s), fewer where the tile would not fit 64 KB.  -> the LDS bytes, or 0: not even one column of H * J floats fits.
+size_t transpose_tile(int heat_h, int heat_w, int n_joints, int& WT) {
+    auto lds_of = [&](int wt) { return (size_t)n_joints * ((size_t)wt * (heat_h + 1) + TR_PAD_J) * 4; };
+    WT = 8;
+    while (WT > 1 && (WT > heat_w || lds_of(WT) > 64 * 1024)) WT >>= 1;
+    return lds_of(WT) <= 64 * 1024 ? lds_of(WT) : 0;
+}
+
+// pread until `want` bytes from position `from` of the file lie at `dst`: -> want; fewer where the file ended before; -errno where
+// a read failed.
+int64_t pread_all(int fd, uint8_t* dst, int64_t want, int64_t from) {
+    int64_t got = 0;
+    while (got < want) {
+        const ssize_t r = pread(fd, dst + got, (size_t)(want - got), (off_t)(from + got));
+        if (r < 0 && errno == EINTR) continue;
+        if (r < 0) return -(int64_t)errno;
+        if (r == 0) break;
+        got += r;
+    }
+    return got;
 }
 
 }  // namespace
@@ -486,15 +526,11 @@ int gem_heat_gather(const void* d_image, int64_t image_len, const int64_t* d_off
         if (dtype == GEM_DT_F64) hipLaunchKernelGGL(heat_copy_kernel<true>, grid, dim3(256), 0, s, a);
         else hipLaunchKernelGGL(heat_copy_kernel<false>, grid, dim3(256), 0, s, a);
     } else {
-        // columns per workgroup: 8 (31 KB of LDS at 64 x 64 x 15: five workgroups per CU hide the loads' latency; 16 columns -- two
-        // workgroups per CU -- measured 0.71 against 0.34 ms for 2000 frames, 2.9 TB/s), fewer where the tile would not fit 64 KB
-        int WT = 8;
-        auto lds_of = [&](int wt) { return (size_t)n_joints * ((size_t)wt * (heat_h + 1) + TR_PAD_J) * 4; };
-        while (WT > 1 && (WT > heat_w || lds_of(WT) > 64 * 1024)) WT >>= 1;
-        if (lds_of(WT) > 64 * 1024) { set_error("gem_heat_gather: a heat-map column of H * J floats does not fit the transposing tile"); return 1; }
+        int WT;
+        const size_t lds = transpose_tile(heat_h, heat_w, n_joints, WT);
+        if (!lds) { set_error("gem_heat_gather: a heat-map column of H * J floats does not fit the transposing tile"); return 1; }
         a.TH = WT;
         const dim3 grid((unsigned)((heat_w + WT - 1) / WT), (unsigned)n);
-        const size_t lds = lds_of(WT);
         if (heat_h == 64 && heat_w == 64 && n_joints == 15) {
             if (dtype == GEM_DT_F64) hipLaunchKernelGGL((heat_transpose_kernel<true, 64, 64, 15, 8>), grid, dim3(256), lds, s, a);
             else hipLaunchKernelGGL((heat_transpose_kernel<false, 64, 64, 15, 8>), grid, dim3(256), lds, s, a);
@@ -607,12 +643,8 @@ int gem_file_stage(const char* path, int device, void* h_pinned, void* d_image, 
     if (!rc && !hip_ok(hipSetDevice(device), "hipSetDevice")) rc = 1;
     for (int64_t o = 0; !rc && o < len; o += slice_bytes) {
         const int64_t want = len - o < slice_bytes ? len - o : slice_bytes;
-        for (int64_t got = 0; got < want;) {
-            const ssize_t r = pread(fd, host + o + got, (size_t)(want - got), (off_t)(o + got));
-            if (r < 0 && errno == EINTR) continue;
-            if (r <= 0) { set_error(std::string("gem_file_stage: short read: ") + (r < 0 ? strerror(errno) : "the file shrank")); rc = 1; break; }
-            got += r;
-        }
+        const int64_t got = pread_all(fd, host + o, want, o);
+        if (got < want) { set_error(std::string("gem_file_stage: short read: ") + (got < 0 ? strerror((int)-got) : "the file shrank")); rc = 1; }
         // (the copy takes whole words: the slice's last word may reach a few bytes past the file, inside the buffers)
         if (!rc && !hip_ok(hipMemcpyAsync(image + o, host + o, (size_t)((want + 3) & ~3ll), hipMemcpyHostToDevice, s), "hipMemcpyAsync")) rc = 1;
     }

@@ -1,6 +1,6 @@
 // Recordings as the pose network leaves them: one `heatmap` .mat and one `depth` .mat per frame
 // (MakeDataForOptimization/process_test_data.py:52-68 reads them with scipy.io.loadmat, one by one).  Included at the end of
-// chunk_io.hip: it shares that file's unaligned word reader and its LDS transpose.
+// chunk_io.hip: it shares that file's unaligned word reader, its LDS transpose (tile_in / tile_out / transpose_tile) and pread_all.
 //
 //   gem_mat_scan        host, no GIL: a bounds-checked interpreter of a Level-5 MAT file that LOCATES the numeric array of a given
 //                       name and copies nothing (the pickle scanner's sibling)
@@ -156,50 +156,27 @@ struct MatArgs {
     int tiles;                      // workgroups per frame
 };
 
-template <bool F64, int HC, int WC, int JC, int WTC>
-__device__ __forceinline__ void mat_tile_in(const HeatArgs& a, float* tile, int64_t payload, int w0, int wn) {
-    const int H = HC ? HC : a.H, W = WC ? WC : a.W, J = JC ? JC : a.J, WT = WTC ? WTC : a.TH;
-    const int PH = H + 1, PJ = WT * PH + TR_PAD_J;
-    const int run = wn * H;
-#pragma unroll 4
-    for (int r = threadIdx.x; r < J * run; r += 256) {
-        const int j = r / run, rem = r - j * run, w = rem / H, h = rem - w * H;
-        tile[j * PJ + w * PH + h] = element_at<F64>(a, payload, ((int64_t)j * W + w0) * H + rem);
-    }
-}
-
-// heat_transpose_kernel (chunk_io.hip) with the payload type read from a per-frame table -- uniform per workgroup, so the choice
-// costs one scalar branch -- and the frame's J depths converted by the frame's first workgroup.  1-D grid: frame = block / tiles.
+// The LDS transpose of heat_transpose_kernel (chunk_io.hip: tile_in / tile_out) with the payload type read from a per-frame table
+// -- uniform per workgroup, so the choice costs one scalar branch -- and the frame's J depths converted by the frame's first
+// workgroup.  1-D grid: frame = block / tiles.
 template <int HC, int WC, int JC, int WTC>
 __global__ __launch_bounds__(256) void mat_frames_kernel(MatArgs m) {
     extern __shared__ float tile[];
     const HeatArgs& a = m.h;
-    const int H = HC ? HC : a.H, W = WC ? WC : a.W, J = JC ? JC : a.J, WT = WTC ? WTC : a.TH;
+    const int W = WC ? WC : a.W, J = JC ? JC : a.J, WT = WTC ? WTC : a.TH;
     const int f = blockIdx.x / m.tiles, t = blockIdx.x - f * m.tiles;
     const int w0 = t * WT, wn = WTC ? WTC : min(WT, W - w0);
-    const int PH = H + 1, PJ = WT * PH + TR_PAD_J;
     const int kind = m.kinds[f];
     const int64_t payload = a.offsets[f];
-    if (kind & GEM_MAT_HEAT_F64) mat_tile_in<true, HC, WC, JC, WTC>(a, tile, payload, w0, wn);
-    else mat_tile_in<false, HC, WC, JC, WTC>(a, tile, payload, w0, wn);
+    if (kind & GEM_MAT_HEAT_F64) tile_in<true, HC, WC, JC, WTC>(a, tile, payload, w0, wn);
+    else tile_in<false, HC, WC, JC, WTC>(a, tile, payload, w0, wn);
     if (t == 0 && (int)threadIdx.x < J) {
         const int64_t at = m.depth_offsets[f];
-        double v;
-        if (kind & GEM_MAT_DEPTH_F32) v = (double)__uint_as_float(word_at(a, at + 4 * threadIdx.x));          // widened exactly
-        else {
-            const int64_t e = at + 8 * threadIdx.x;
-            v = __longlong_as_double((long long)((uint64_t)word_at(a, e) | ((uint64_t)word_at(a, e + 4) << 32)));
-        }
-        m.depth[(int64_t)f * J + threadIdx.x] = v;
+        m.depth[(int64_t)f * J + threadIdx.x] = (kind & GEM_MAT_DEPTH_F32) ? (double)__uint_as_float(word_at(a, at + 4 * threadIdx.x))      // widened exactly
+                                                                            : double_at(a, at + 8 * threadIdx.x);
     }
     __syncthreads();
-    float* dst = a.out + ((int64_t)f * H * W + w0) * J;
-    const int orun = wn * J;
-#pragma unroll 4
-    for (int r = threadIdx.x; r < H * orun; r += 256) {
-        const int h = r / orun, rem = r - h * orun, w = rem / J, j = rem - w * J;
-        dst[(int64_t)h * W * J + rem] = tile[j * PJ + w * PH + h];
-    }
+    tile_out<HC, WC, JC, WTC>(a, tile, f, w0, wn);
 }
 
 // est_global[f][j] = R_f . est_local[f][j] + t_f, every product and sum rounded on its own (no fused multiply-add: __dmul_rn /
@@ -255,13 +232,7 @@ int gem_mat_read(const char* const* paths, int64_t n, const int64_t* at, const i
         if (at[i] < 0 || sizes[i] < 0 || at[i] > block_bytes || sizes[i] > block_bytes - at[i]) { set_error("gem_mat_read: a file's place lies outside the block"); return 1; }
         const int fd = open(paths[i], O_RDONLY | O_CLOEXEC);
         if (fd < 0) { set_error(std::string("gem_mat_read: ") + paths[i] + ": " + strerror(errno)); return 1; }
-        int64_t got = 0;
-        while (got < sizes[i]) {
-            const ssize_t r = pread(fd, block + at[i] + got, (size_t)(sizes[i] - got), (off_t)got);
-            if (r < 0 && errno == EINTR) continue;
-            if (r <= 0) break;
-            got += r;
-        }
+        const int64_t got = pread_all(fd, block + at[i], sizes[i], 0);
         close(fd);
         if (got != sizes[i]) { set_error(std::string("gem_mat_read: ") + paths[i] + ": short read (the file shrank)"); return 1; }
         memset(&out[i], 0, sizeof out[i]);
@@ -284,17 +255,16 @@ int gem_mat_frames(const void* d_image, int64_t image_len, const int64_t* d_heat
     m.h.image = static_cast<const uint32_t*>(d_image); m.h.offsets = d_heat_offsets; m.h.out = d_heat; m.h.image_len = (image_len + 3) & ~3ll;
     m.h.H = heat_h; m.h.W = heat_w; m.h.J = n_joints;
     m.depth_offsets = d_depth_offsets; m.kinds = d_kinds; m.depth = d_depth;
-    int WT = 8;                                       // as gem_heat_gather's Fortran path (measured there)
-    auto lds_of = [&](int wt) { return (size_t)n_joints * ((size_t)wt * (heat_h + 1) + TR_PAD_J) * 4; };
-    while (WT > 1 && (WT > heat_w || lds_of(WT) > 64 * 1024)) WT >>= 1;
-    if (lds_of(WT) > 64 * 1024) { set_error("gem_mat_frames: a heat-map column of H * J floats does not fit the transposing tile"); return 1; }
+    int WT;
+    const size_t lds = transpose_tile(heat_h, heat_w, n_joints, WT);
+    if (!lds) { set_error("gem_mat_frames: a heat-map column of H * J floats does not fit the transposing tile"); return 1; }
     m.h.TH = WT;
     m.tiles = (heat_w + WT - 1) / WT;
     if (n * m.tiles > 0x7fffffffll) { set_error("gem_mat_frames: too many frames for one launch"); return 1; }
     const dim3 grid((unsigned)(n * m.tiles));
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (heat_h == 64 && heat_w == 64 && n_joints == 15) hipLaunchKernelGGL((mat_frames_kernel<64, 64, 15, 8>), grid, dim3(256), lds_of(WT), s, m);
-    else hipLaunchKernelGGL((mat_frames_kernel<0, 0, 0, 0>), grid, dim3(256), lds_of(WT), s, m);
+    if (heat_h == 64 && heat_w == 64 && n_joints == 15) hipLaunchKernelGGL((mat_frames_kernel<64, 64, 15, 8>), grid, dim3(256), lds, s, m);
+    else hipLaunchKernelGGL((mat_frames_kernel<0, 0, 0, 0>), grid, dim3(256), lds, s, m);
     GEM_HIP(hipGetLastError());
     return 0;
 }

@@ -24,6 +24,7 @@ from .errors import calculate_errors
 from .sequence import (SEQ_LEN, OVERLAP, window_starts, cut_windows, merge_batches, final_smooth,
                        relative_global_numpy, to_global_numpy)
 from .skeleton import KINEMATIC_PARENTS
+from .staging import Laps
 from .vae import infer_shape, load_checkpoint
 
 # hard-coded in the reference's main() (optimizer.py:334,344)
@@ -117,14 +118,7 @@ class SequenceOptimizer:
         dev = e.device
         B = len(starts)
         n_frames = len(est_local)
-        import time
-        tick = [time.perf_counter()]
-
-        def lap(name):          # developer timing (tools/whole_sequence_timing.py)
-            if timings is not None:
-                now = time.perf_counter()
-                timings[name] = timings.get(name, 0.0) + (now - tick[0])
-                tick[0] = now
+        lap = Laps(timings)          # developer timing (tools/whole_sequence_timing.py)
         if len(cams) != n_frames:
             raise ValueError("est_local and cams must cover the same frames (%d / %d)" % (n_frames, len(cams)))
         if B and (int(np.min(starts)) < 0 or int(np.max(starts)) + self.seq_len > n_frames):
@@ -150,8 +144,7 @@ class SequenceOptimizer:
         B = prep["B"]
         if len(heat) != prep["frames"]:
             raise ValueError("est_local, cams and heat must cover the same frames (%d / %d)" % (prep["frames"], len(heat)))
-        import time
-        t0 = time.perf_counter()
+        lap = Laps(timings)
         heat_d = (heat if torch.is_tensor(heat) else torch.as_tensor(np.asarray(heat))).to(dev, dtype=torch.float32).contiguous()
         if eps is None:
             eps = torch.randn(2 * B, e.D)
@@ -160,8 +153,7 @@ class SequenceOptimizer:
         eps_l, eps_g = eps_d[:, 0].contiguous(), eps_d[:, 1].contiguous()
         pending = e.optimize_windows(prep["pose"], prep["cams"], heat_d, prep["frame0"], prep["mean_bone"], eps_l, eps_g, w_local, w_global,
                                      self.opts)
-        if timings is not None:
-            timings["run: noise upload + enqueue"] = timings.get("run: noise upload + enqueue", 0.0) + time.perf_counter() - t0
+        lap("run: noise upload + enqueue")
         return pending
 
     def enqueue(self, est_local, cams, heat, starts, chunk_of_window, chunk_bounds, w_local, w_global, eps=None, timings=None):

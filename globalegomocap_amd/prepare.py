@@ -37,7 +37,7 @@ import zlib
 import numpy as np
 
 from . import _capi
-from .whole_sequence import natural_key
+from .staging import Laps, copy_stream, natural_key, padded, reader_pool, side_by_side
 
 HEAT_NAME, DEPTH_NAME = "heatmap", "depth"
 PICKLE_KEYS = ("gt_global_skeleton", "estimated_global_skeleton", "estimated_local_skeleton", "camera_pose_list", "heatmap_list")
@@ -237,65 +237,156 @@ def _lift_engine(camera_model_path, device):
     return _engines[key]
 
 
-def _lap(timings, name, t0):
-    """Developer timing (tools/prepare_bench.py): adds the wall time since t0 to timings[name]; returns the new t0."""
-    import time
-    if timings is None:
-        return t0
-    now = time.perf_counter()
-    timings[name] = timings.get(name, 0.0) + (now - t0)
-    return now
-
-
 def _c_paths(paths):
     return (C.c_char_p * len(paths))(*[os.fsencode(p) for p in paths])
 
 
-def _read_range(lib, cpaths, lo, hi, at, sizes, names, block_ptr, block_len, found, rcs, paths, send=None):
-    """Reader thread: files [lo, hi) into the block (gem_mat_read: the GIL is free); `send(lo, hi)` then starts the range's copy to
-    the device, so that it crosses PCIe while other ranges are still being read.  Then the files the scanner could not take as
-    they are: compressed elements are inflated here (zlib releases the GIL too), files outside the subset go through loadmat.
+def _element(array, i):
+    """Pointer to element i of a ctypes array: what a C function sees as the array from there on."""
+    return C.cast(C.byref(array, i * C.sizeof(array._type_)), C.POINTER(array._type_))
+
+
+def _file_sizes(lib, pool, cpaths, readers):
+    """The files' sizes (int64 array), one stat each, on the reader threads (gem_files_sizes: the GIL is free)."""
+    count = len(cpaths)
+    sizes = np.empty(count, dtype=np.int64)
+
+    def stat_range(lo, hi):
+        _capi.check(lib.gem_files_sizes(_element(cpaths, lo), hi - lo, C.c_void_p(sizes.ctypes.data + 8 * lo)), lib)
+    cut = [count * k // readers for k in range(readers + 1)]
+    for j in [pool.submit(stat_range, lo, hi) for lo, hi in zip(cut[:-1], cut[1:]) if hi > lo]:
+        j.result()
+    return sizes
+
+
+def _read_range(lib, cpaths, lo, hi, at, sizes, n, block, found, rcs, paths, send=None):
+    """Reader thread: files [lo, hi) of the n heat-map files and the n depth files behind them into `block` (a uint8 numpy array; gem_mat_read: the GIL is free); `send(lo, hi)` then starts
+    the range's copy to the device, so that it crosses PCIe while other ranges are still being read.  Then the files the scanner
+    could not take as they are: compressed elements are inflated here (zlib releases the GIL too), files outside the subset go
+    through loadmat.
     -> ([(index, payload bytes, numpy dtype, dims, array as loadmat returns it or None)] for those, what `send` returned)."""
     extra, sent = [], None
-    i = lo
-    while i < hi:          # (heat-map files and depth files form contiguous runs: one or two calls)
-        j = i
-        while j < hi and names[j] == names[i]:
-            j += 1
-        _capi.check(lib.gem_mat_read(C.cast(C.byref(cpaths, i * C.sizeof(C.c_char_p)), C.POINTER(C.c_char_p)), j - i,
-                                     C.c_void_p(at.ctypes.data + 8 * i), C.c_void_p(sizes.ctypes.data + 8 * i), names[i].encode(),
-                                     C.c_void_p(block_ptr), block_len,
-                                     C.cast(C.byref(found, i * C.sizeof(_capi.GemMatArray)), C.POINTER(_capi.GemMatArray)),
-                                     C.c_void_p(rcs.ctypes.data + 4 * i)), lib)
-        i = j
+    names = (HEAT_NAME, DEPTH_NAME)          # names[i >= n]: the array that file i holds
+    for i, j in ((lo, min(hi, n)), (max(lo, n), hi)):          # (the range's heat-map files, then its depth files: one or two calls)
+        if i < j:
+            _capi.check(lib.gem_mat_read(_element(cpaths, i), j - i, C.c_void_p(at.ctypes.data + 8 * i), C.c_void_p(sizes.ctypes.data + 8 * i),
+                                         names[i >= n].encode(), C.c_void_p(block.ctypes.data), block.size, _element(found, i),
+                                         C.c_void_p(rcs.ctypes.data + 4 * i)), lib)
     if send is not None and any(rcs[i] == 0 and not found[i].compressed for i in range(lo, hi)):
         sent = send(lo, hi)
-    block = (C.c_uint8 * block_len).from_address(block_ptr) if block_len else b""
     for i in range(lo, hi):
         if rcs[i] == 0 and not found[i].compressed:
             continue
         hit = None
         if rcs[i] == 0:
-            hit = locate(memoryview(block)[int(at[i]):int(at[i] + sizes[i])], names[i])
+            hit = locate(block[int(at[i]):int(at[i] + sizes[i])], names[i >= n])
         if hit is not None:
             a = array_at(*hit)
             extra.append((i, a.tobytes(order="F"), a.dtype.type, a.shape, None))
         else:
             from scipy.io import loadmat
-            a = loadmat(paths[i])[names[i]]
-            dev = a if a.dtype in (np.float32, np.float64) else a.astype(np.float32 if names[i] == HEAT_NAME else np.float64)
+            a = loadmat(paths[i])[names[i >= n]]
+            dev = a if a.dtype in (np.float32, np.float64) else a.astype(np.float32 if i < n else np.float64)
             extra.append((i, dev.tobytes(order="F"), dev.dtype.type, a.shape, a))
         rcs[i] = -1          # (its payload travels in the extra block)
     return extra, sent
 
 
+def _read_files(lib, pool, readers, cpaths, at, room, sizes, n, block, found, rcs, paths, send, sent):
+    """The reader fan-out: every file into its place in `block`, range by range on the pool's threads (`_read_range`); `sent` is
+    handed what each range's `send` returned, in range order.  -> the extra payloads of all ranges."""
+    # heat-map files are 2000 times the depth files: the ranges are cut by bytes, not by count; four ranges per reader, so that
+    # the first copies start early
+    cuts = np.searchsorted(np.cumsum(room), np.linspace(0, block.size, 4 * readers + 1)[1:-1]).tolist()
+    bounds = sorted(set([0] + [int(c) for c in cuts] + [len(paths)]))
+    jobs = [pool.submit(_read_range, lib, cpaths, lo, hi, at, sizes, n, block, found, rcs, paths, send)
+            for lo, hi in zip(bounds[:-1], bounds[1:]) if hi > lo]
+    extra = []
+    for j in jobs:
+        e, ev = j.result()
+        extra += e
+        if ev is not None:
+            sent(ev)
+    return extra
+
+
+def payload_tables(n, paths, at, found, rcs, extra, block):
+    """Where every frame's payloads lie and what they are -- host data only.  Files [0, n) hold the heat-maps, [n, 2n) the depths;
+    `found` / `rcs` are what gem_mat_read left for the files at `at` in `block` (uint8 numpy array: the main block), `extra` the
+    payloads `_read_range` made itself (rcs -1).  Payloads that are not in the files as they are get a place BEHIND the block:
+    the extra ones, and the first row of a several-row depth (depth = loadmat(...)['depth'][0]).
+    -> (where int64 [2n]: byte offsets; kinds int32 [n]: MAT_HEAT_F64 | MAT_DEPTH_F32; (H, W, J); heat_files [n]: None, or the
+    heat-map as loadmat returns it where that is not float32 -- the pickle wants it as it is; parts [(offset, bytes)]: what goes
+    behind the block; end: the block's length with them)."""
+    total = block.size
+    where = np.zeros(2 * n, dtype=np.int64)
+    dtypes, dims = [None] * (2 * n), [None] * (2 * n)
+    heat_files = [None] * n
+    for i in range(2 * n):
+        if rcs[i] == 0:
+            a = found[i]
+            where[i], dtypes[i], dims[i] = at[i] + a.offset, _NP_OF[a.storage], tuple(int(d) for d in a.dims[:a.ndim])
+    end, parts = total, []
+    for i, payload, dt, shape, kept in extra:
+        if i >= n and len(shape) == 2 and shape[0] != 1:          # depth = loadmat(...)['depth'][0]: the first ROW
+            payload, shape = np.frombuffer(payload, dtype=dt).reshape(shape, order="F")[:1].tobytes(), (1, shape[1])
+        where[i], dtypes[i], dims[i] = end, dt, tuple(shape)
+        parts.append((end, payload))
+        end += padded(len(payload), _ALIGN)
+        if i < n and (kept is not None or dt is not np.float32):
+            heat_files[i] = kept if kept is not None else np.frombuffer(payload, dtype=dt).reshape(shape, order="F")
+    for i in range(n, 2 * n):          # a depth array of several rows inside the main block: its first row is strided there
+        if rcs[i] == 0 and (len(dims[i]) != 2 or dims[i][0] != 1):
+            if len(dims[i]) != 2:
+                raise ValueError("%s: 'depth' is not a [1,J] array" % paths[i])
+            row = array_at(block, int(where[i]), dtypes[i], dims[i])[:1]
+            where[i], dims[i] = end, (1, dims[i][1])
+            parts.append((end, row.tobytes()))
+            end += padded(row.nbytes, _ALIGN)
+    for f in range(n):          # float64 heat-maps inside the main block: the pickle wants them as they are
+        if rcs[f] == 0 and dtypes[f] is np.float64:
+            heat_files[f] = array_at(block, int(where[f]), np.float64, dims[f]).copy(order="F")
+    shapes = {dims[f] for f in range(n)}
+    if len(shapes) != 1 or len(next(iter(shapes))) != 3:
+        raise ValueError("the heat-maps must all be [H,W,J] arrays of one shape, found %s" % sorted(shapes))
+    J = next(iter(shapes))[2]
+    if any(dims[i] != (1, J) for i in range(n, 2 * n)):
+        raise ValueError("every depth file must hold a [1,%d] array" % J)
+    kinds = np.array([(_capi.MAT_HEAT_F64 if dtypes[f] is np.float64 else 0) | (_capi.MAT_DEPTH_F32 if dtypes[n + f] is np.float32 else 0)
+                      for f in range(n)], dtype=np.int32)
+    return where, kinds, next(iter(shapes)), heat_files, parts, end
+
+
+def _frames_from_arena(arena, total, in_block, where, kinds, shape, parts, end, device):
+    """Upload + launch: the payloads of `parts` land behind the block's image (`total` bytes of `arena`; `in_block`: whether any
+    frame is read from it), in the same arena; the tables go up and ONE gem_mat_frames picks all frames out.  -> (heat, depth)."""
+    import torch
+    n, (H, W, J) = len(kinds), shape
+    if parts:
+        whole = torch.empty(end + 8, dtype=torch.uint8, device=device)
+        if in_block:
+            whole[:total].copy_(arena[:total])
+        side = torch.empty(end - total, dtype=torch.uint8, pin_memory=True)
+        sv = side.numpy()
+        for o, payload in parts:
+            sv[o - total:o - total + len(payload)] = np.frombuffer(payload, dtype=np.uint8)
+        whole[total:end].copy_(side, non_blocking=True)
+        arena = whole
+    tables = torch.from_numpy(np.concatenate([where, kinds.astype(np.int64)])).to(device)
+    kinds_d = tables[2 * n:].to(torch.int32)
+    heat = torch.empty((n, H, W, J), dtype=torch.float32, device=device)
+    depth = torch.empty((n, J), dtype=torch.float64, device=device)
+    mat_frames(arena, end, tables[:n], tables[n:2 * n], kinds_d, heat, depth)
+    return heat, depth
+
+
 def frames_to_device(heat_paths, depth_paths, device=None, readers=N_READERS, timings=None):
     """The frames' .mat files -> (heat [n,H,W,J] f32, depth [n,J] f64, heat_files) on `device`: every file is read once into a
     pinned block (reader threads, `gem_mat_read`), the block crosses PCIe range by range on the readers' two copy streams while
-    the other ranges are still being read (one more copy for inflated or loadmat'ed payloads), and ONE launch of `gem_mat_frames` picks all frames out.  heat_files[f]: None, or the heat-map as loadmat returns
-    it where the device copy (float32) is not the file's own class."""
+    the other ranges are still being read (one more copy for inflated or loadmat'ed payloads), and ONE launch of `gem_mat_frames`
+    picks all frames out.  heat_files[f]: None, or the heat-map as loadmat returns it where the device copy (float32) is not the
+    file's own class."""
     import torch
-    from .whole_sequence import _pool, copy_stream
     lib = _capi.load_library()
     device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     n = len(heat_paths)
@@ -303,29 +394,19 @@ def frames_to_device(heat_paths, depth_paths, device=None, readers=N_READERS, ti
         raise ValueError("as many depth files as heat-map files are needed (%d / %d)" % (len(depth_paths), n))
     if n == 0:
         return torch.empty((0, 64, 64, 15), device=device), torch.empty((0, 15), dtype=torch.float64, device=device), []
-    import time
-    t0 = time.perf_counter()
+    lap = Laps(timings)          # developer timing (tools/prepare_bench.py)
     paths = list(heat_paths) + list(depth_paths)
-    names = [HEAT_NAME] * n + [DEPTH_NAME] * n
     cpaths = _c_paths(paths)
-    sizes = np.empty(2 * n, dtype=np.int64)
     readers = max(1, min(readers, 2 * n))
-    pool = _pool("mat", readers)
-
-    def stat_range(lo, hi):
-        _capi.check(lib.gem_files_sizes(C.cast(C.byref(cpaths, lo * C.sizeof(C.c_char_p)), C.POINTER(C.c_char_p)), hi - lo,
-                                        C.c_void_p(sizes.ctypes.data + 8 * lo)), lib)
-    cut = [2 * n * k // readers for k in range(readers + 1)]
-    for j in [pool.submit(stat_range, lo, hi) for lo, hi in zip(cut[:-1], cut[1:]) if hi > lo]:
-        j.result()
-    room = (sizes + 8 + _ALIGN - 1) // _ALIGN * _ALIGN
-    at = np.concatenate([[0], np.cumsum(room)[:-1]]).astype(np.int64)
-    total = int(room.sum())
-    t0 = _lap(timings, "file sizes (one stat each)", t0)
-    block = torch.empty(total, dtype=torch.uint8, pin_memory=True)          # (torch keeps freed pinned blocks for the next call)
+    pool = reader_pool("mat", readers)
+    sizes = _file_sizes(lib, pool, cpaths, readers)
+    at, room, total = side_by_side(sizes, _ALIGN)
+    lap("file sizes (one stat each)")
+    pinned = torch.empty(total, dtype=torch.uint8, pin_memory=True)          # (torch keeps freed pinned blocks for the next call)
+    block = pinned.numpy()
     found = (_capi.GemMatArray * (2 * n))()
     rcs = np.zeros(2 * n, dtype=np.int32)
-    t0 = _lap(timings, "pinned block", t0)
+    lap("pinned block")
     arena = torch.empty(total + 8, dtype=torch.uint8, device=device)
     cur = torch.cuda.current_stream()
     allocated = torch.cuda.Event()
@@ -337,79 +418,18 @@ def frames_to_device(heat_paths, depth_paths, device=None, readers=N_READERS, ti
         b0, b1 = int(at[lo]), int(at[hi - 1] + room[hi - 1])
         st.wait_event(allocated)
         with torch.cuda.stream(st):
-            arena[b0:b1].copy_(block[b0:b1], non_blocking=True)
+            arena[b0:b1].copy_(pinned[b0:b1], non_blocking=True)
             ev = torch.cuda.Event()
             ev.record(st)
         arena.record_stream(st)
         return ev
-    # heat-map files are 2000 times the depth files: the ranges are cut by bytes, not by count; four ranges per reader, so that
-    # the first copies start early
-    cuts = np.searchsorted(np.cumsum(room), np.linspace(0, total, 4 * readers + 1)[1:-1]).tolist()
-    bounds = sorted(set([0] + [int(c) for c in cuts] + [2 * n]))
-    jobs = [pool.submit(_read_range, lib, cpaths, lo, hi, at, sizes, names, block.data_ptr(), total, found, rcs, paths, send)
-            for lo, hi in zip(bounds[:-1], bounds[1:]) if hi > lo]
-    extra = []
-    for j in jobs:
-        e, sent = j.result()
-        extra += e
-        if sent is not None:
-            cur.wait_event(sent)
-    t0 = _lap(timings, "read + scan (+ inflate / loadmat) on the reader threads", t0)
-    # tables: where every frame's payloads lie in the arena, and their types
-    where = np.zeros(2 * n, dtype=np.int64)
-    dtypes, dims = [None] * (2 * n), [None] * (2 * n)
-    heat_files = [None] * n
-    for i in range(2 * n):
-        if rcs[i] == 0:
-            a = found[i]
-            where[i], dtypes[i], dims[i] = at[i] + a.offset, _NP_OF[a.storage], tuple(int(d) for d in a.dims[:a.ndim])
-    extra_at, parts = total, []
-    for i, payload, dt, shape, kept in extra:
-        if i >= n and len(shape) == 2 and shape[0] != 1:          # depth = loadmat(...)['depth'][0]: the first ROW
-            payload, shape = np.frombuffer(payload, dtype=dt).reshape(shape, order="F")[:1].tobytes(), (1, shape[1])
-        where[i], dtypes[i], dims[i] = extra_at, dt, tuple(shape)
-        parts.append((extra_at, payload))
-        extra_at += (len(payload) + 8 + _ALIGN - 1) // _ALIGN * _ALIGN
-        if i < n and (kept is not None or dt is not np.float32):
-            heat_files[i] = kept if kept is not None else np.frombuffer(payload, dtype=dt).reshape(shape, order="F")
-    for i in range(n, 2 * n):          # a depth array of several rows inside the main block: its first row is strided there
-        if rcs[i] == 0 and (len(dims[i]) != 2 or dims[i][0] != 1):
-            if len(dims[i]) != 2:
-                raise ValueError("%s: 'depth' is not a [1,J] array" % paths[i])
-            row = array_at(memoryview((C.c_uint8 * total).from_address(block.data_ptr())), int(where[i]), dtypes[i], dims[i])[:1]
-            where[i], dims[i] = extra_at, (1, dims[i][1])
-            parts.append((extra_at, row.tobytes()))
-            extra_at += (row.nbytes + 8 + _ALIGN - 1) // _ALIGN * _ALIGN
-    for f in range(n):          # float64 heat-maps inside the main block: the pickle wants them as they are
-        if rcs[f] == 0 and dtypes[f] is np.float64:
-            heat_files[f] = array_at(memoryview((C.c_uint8 * total).from_address(block.data_ptr())), int(where[f]), np.float64, dims[f]).copy(order="F")
-    shapes = {dims[f] for f in range(n)}
-    if len(shapes) != 1 or len(next(iter(shapes))) != 3:
-        raise ValueError("the heat-maps must all be [H,W,J] arrays of one shape, found %s" % sorted(shapes))
-    H, W, J = next(iter(shapes))
-    if any(dims[i] != (1, J) for i in range(n, 2 * n)):
-        raise ValueError("every depth file must hold a [1,%d] array" % J)
-    kinds = np.zeros(n, dtype=np.int32)
-    for f in range(n):
-        kinds[f] = (_capi.MAT_HEAT_F64 if dtypes[f] is np.float64 else 0) | (_capi.MAT_DEPTH_F32 if dtypes[n + f] is np.float32 else 0)
-    t0 = _lap(timings, "payload tables", t0)
-    if parts:          # the payloads that are not in the files as they are land behind the block's image, in the same arena
-        whole = torch.empty(extra_at + 8, dtype=torch.uint8, device=device)
-        if (rcs == 0).any():
-            whole[:total].copy_(arena[:total])
-        side = torch.empty(extra_at - total, dtype=torch.uint8, pin_memory=True)
-        sv = side.numpy()
-        for o, payload in parts:
-            sv[o - total:o - total + len(payload)] = np.frombuffer(payload, dtype=np.uint8)
-        whole[total:extra_at].copy_(side, non_blocking=True)
-        arena = whole
-    tables = torch.from_numpy(np.concatenate([where, kinds.astype(np.int64)])).to(device)
-    kinds_d = tables[2 * n:].to(torch.int32)
-    heat = torch.empty((n, H, W, J), dtype=torch.float32, device=device)
-    depth = torch.empty((n, J), dtype=torch.float64, device=device)
-    mat_frames(arena, extra_at, tables[:n], tables[n:2 * n], kinds_d, heat, depth)
-    torch.cuda.current_stream().synchronize()          # (the pinned blocks are released on return)
-    _lap(timings, "copies' tail + gem_mat_frames", t0)
+    extra = _read_files(lib, pool, readers, cpaths, at, room, sizes, n, block, found, rcs, paths, send, cur.wait_event)
+    lap("read + scan (+ inflate / loadmat) on the reader threads")
+    where, kinds, shape, heat_files, parts, end = payload_tables(n, paths, at, found, rcs, extra, block)
+    lap("payload tables")
+    heat, depth = _frames_from_arena(arena, total, bool((rcs == 0).any()), where, kinds, shape, parts, end, device)
+    torch.cuda.current_stream().synchronize()          # (the pinned block is released on return)
+    lap("copies' tail + gem_mat_frames")
     return heat, depth, heat_files
 
 
@@ -445,8 +465,7 @@ def prepare_spans(slam_result_path, heatmap_dir, depth_dir, gt_path, spans, fps,
     import torch
     from . import slam
     from .camera import DEFAULT_CALIBRATION
-    import time
-    t0 = time.perf_counter()
+    lap = Laps(timings)          # developer timing (tools/prepare_bench.py)
     device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     with open(slam_result_path) as f:
         text = slam.trajectory_rows(f.read())          # (parsed once for all chunks)
@@ -466,24 +485,24 @@ def prepare_spans(slam_result_path, heatmap_dir, depth_dir, gt_path, spans, fps,
         gts.append(gt_clip(pose_gt, a, b, mat_start_frame))
     if not spans:
         return Recording([])
-    t0 = _lap(timings, "listings, ground truth, trajectory", t0)
+    lap("listings, ground truth, trajectory")
     with torch.cuda.device(device):
         heat, depth, heat_files = frames_to_device(heat_paths, depth_paths, device, timings=timings)
-        t0 = time.perf_counter()
+        lap = Laps(timings)          # (frames_to_device has timed its own phases)
         engine = _lift_engine(camera_model_path or DEFAULT_CALIBRATION, device.index)
         if tuple(heat.shape[1:3]) != tuple(engine.heat_size):
             raise ValueError("heat-maps of %d x %d: the lifting kernel is built for %d x %d" % (tuple(heat.shape[1:3]) + tuple(engine.heat_size)))
         est_local, _ = engine.lift_skeleton(heat, depth)
         heads = est_local[:, 0].cpu().numpy()
-        t0 = _lap(timings, "lift + head joints to the host", t0)
+        lap("lift + head joints to the host")
         gt_all = np.concatenate([np.asarray(g, dtype=np.float64) for g in gts])
         cams = np.concatenate([slam.camera_pose_list_from_heads(text, heads[lo:hi], gt_all[lo:hi, 0], a, b, fps)[0]
                                for (a, b), (lo, hi) in zip(spans, bounds)])
-        t0 = _lap(timings, "per-chunk scale and cameras (host)", t0)
+        lap("per-chunk scale and cameras (host)")
         cams_d, gt_d = torch.from_numpy(cams).to(device), torch.from_numpy(gt_all).to(device)
         est_global, err = prepare_global(est_local, cams_d, gt_d)
         err = err.cpu().numpy()
-        _lap(timings, "cameras up + gem_prepare_global + errors back", t0)
+        lap("cameras up + gem_prepare_global + errors back")
     chunks = []
     for (a, b), (lo, hi), g in zip(spans, bounds, gts):
         kept = heat_files[lo:hi]

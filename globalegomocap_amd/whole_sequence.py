@@ -6,7 +6,9 @@ The reference's `optimize_whole_sequence.py` walks the chunk directories of a se
 `gather_heat`: the heat-maps go file -> pinned memory -> HBM without becoming Python objects, loadmat's Fortran order and
 float64 are undone by a kernel), all windows of a batch of chunks go through the optimiser together (BASELINE configs[1]: a
 2000-frame sequence = 20 chunks = 240 windows per call), batches are pipelined (the next one's files arrive while this one
-computes), and the per-chunk merge / smoothing / error report run on the device as well.  Results, keys, printed summary and the order in which the reparameterisation noise is
+computes), and the per-chunk merge / smoothing / error report run on the device as well.  How bytes reach the device -- reader
+threads, copy streams, pinned buffers -- is `staging`'s business; this module holds the chunk-file reader, the batch pipeline
+(`_Pipeline`) and the report.  Results, keys, printed summary and the order in which the reparameterisation noise is
 drawn (chunk by chunk, window by window, local then global) follow the reference.
 
     python -m globalegomocap_amd.whole_sequence --data_path data/jian3
@@ -14,17 +16,19 @@ drawn (chunk by chunk, window by window, local then global) follow the reference
 import ctypes as C
 import os
 import pickle
-import re
-import threading
-from collections import OrderedDict
+from collections import OrderedDict, namedtuple
+from types import SimpleNamespace
 
 import numpy as np
 import torch
 
-from . import _capi
+from . import _capi, staging
+from .staging import (Laps, Scratch, cpus_near, drain, natural_key, reader_pool, report_stream, side_by_side, staging_buffer,      # noqa: F401  (cpus_near, natural_key: part of this module's interface)
+                      thread_state)
 from .optimizer import SequenceOptimizer, GLOBAL_VAE_PATH, LOCAL_VAE_PATH
-from .sequence import (SEQ_LEN, OVERLAP, window_starts, cut_windows, merge_batches, merge_chunks, relative_global_numpy,
-                       to_global_numpy)
+from .errors import calculate_errors
+from .sequence import (SEQ_LEN, OVERLAP, window_starts, cut_windows, merge_batches, merge_chunks, final_smooth,
+                       relative_global_numpy, to_global_numpy)
 
 SUMMARY_LINES = (          # (label printed by the reference, key) in print order, None = separator
     ("Average original global pose mpjpe", "original_global_mpjpe"), ("Average mid global pose mpjpe", "mid_global_mpjpe"),
@@ -43,33 +47,35 @@ SUMMARY_LINES = (          # (label printed by the reference, key) in print orde
 )
 
 
-def natural_key(name):
-    """Sort key equivalent to natsort.natsorted (default algorithm: case-sensitive text, unsigned integers) for directory
-    names like chunk_2 < chunk_10 (optimize_whole_sequence.py:48)."""
-    return [int(t) if t.isdigit() else t for t in re.split(r"(\d+)", name)]
-
-
 def list_chunks(data_dir):
     """Chunk directories in the reference's order (`natsorted(os.listdir(data_dir))`, directories only)."""
     names = sorted(os.listdir(data_dir), key=natural_key)
     return [os.path.join(data_dir, n) for n in names if os.path.isdir(os.path.join(data_dir, n))]
 
 
+# ------------------------------------------------------------------------------------------------------------------ the chunk-file reader
 KEYS = ("estimated_local_skeleton", "gt_global_skeleton", "camera_pose_list", "heatmap_list")     # read at optimizer.py:318-324, in this order
 _K_EST, _K_GT, _K_CAM, _K_HEAT = range(4)
-SLICE_BYTES = int(os.environ.get("GEM_WS_SLICE_MB", 8)) << 20            # a file crosses PCIe in slices of this size: the next one is read while the last one is on its way
+# A file crosses PCIe in slices of this size: the next one is read while the last one is on its way (DESIGN.md section 8: 4 and
+# 32 MB slices measured within noise of 8).
+SLICE_BYTES = 8 << 20
 _PAD = 4096                      # file images are laid out on 4 KB boundaries, with at least 8 bytes of slack behind each
+LOCATED, LISTED, RESIDENT = "located", "listed", "resident"          # how a chunk's heat-maps travel: ParsedChunk["heat_via"]
 
-_reader_local = threading.local()      # per reader thread: two pinned staging buffers, (load_chunk only) a device image of the file
-_heat_pool = {}                        # device -> per batch in flight: [frame buffer, file-image arena] (kept between calls)
 _C_KEYS = None
 
 
 class ParsedChunk(dict):
-    """What `parse_chunk` found in `<chunk>/test_data.pkl`: "path", "est_local" / "gt" / "cams" (dense float64 arrays), "n" frames,
-    "heat_shape" (H, W, J), and EITHER "heat_offsets" (int64 [n]: where every heat-map's raw data lie in the file) with
-    "heat_dtype" / "heat_fortran" -- the library located them, they reach the device without passing through Python (`read_file` +
-    `gather_heat`) -- OR "heat_list", the un-pickled list (files outside the library reader's subset)."""
+    """One chunk as the pipeline sees it: "est_local" / "gt" / "cams" (dense float64 arrays), "n" frames, "heat_shape" (H, W, J)
+    and "heat_via", which says how the heat-maps reach the device:
+
+      LOCATED   `parse_chunk` found them in the file: "heat_offsets" (int64 [n]: where every heat-map's raw data lie),
+                "heat_dtype", "heat_fortran", "file_bytes" -- they go file -> pinned memory -> HBM without passing through Python
+                (`read_file` + `gather_heat`);
+      LISTED    "heat_list", the un-pickled list (files outside the library reader's subset): stacked on the host (`stage_list`);
+      RESIDENT  "heat", a float32 device tensor [n,H,W,J] (a `prepare.RecordingChunk`).
+
+    Chunks read from a file also carry "path"."""
 
 
 def parse_chunk(path, native=True):
@@ -87,7 +93,7 @@ def parse_chunk(path, native=True):
         if lib.gem_chunk_open(os.fsencode(file), _C_KEYS, len(KEYS), C.byref(h)) == 0:
             try:
                 info = (C.c_int64 * 8)()
-                c, ok = ParsedChunk(path=path), True
+                c, ok = ParsedChunk(path=path, heat_via=LOCATED), True
                 for k, name in ((_K_EST, "est_local"), (_K_GT, "gt"), (_K_CAM, "cams"), (_K_HEAT, None)):
                     _capi.check(lib.gem_chunk_info(h, k, info), lib)
                     n, ndim = int(info[0]), int(info[1])
@@ -111,7 +117,7 @@ def parse_chunk(path, native=True):
                 lib.gem_chunk_close(h)
     with open(file, "rb") as f:
         d = pickle.load(f)
-    c = ParsedChunk(path=path,
+    c = ParsedChunk(path=path, heat_via=LISTED,
                     est_local=np.asarray(d["estimated_local_skeleton"], dtype=np.float64),
                     gt=np.asarray(d["gt_global_skeleton"], dtype=np.float64),
                     cams=np.asarray(d["camera_pose_list"], dtype=np.float64))
@@ -121,55 +127,14 @@ def parse_chunk(path, native=True):
     return c
 
 
-N_COPY_STREAMS = int(os.environ.get("GEM_WS_STREAMS", 2))
-STREAM_PRIORITY = int(os.environ.get("GEM_WS_PRIORITY", 0))          # (0 = torch's default pool; -1 measured the same: profiles/stream_prio_r06.txt)
-_copy_streams = {}
-_report_streams = {}
-_copy_lock = threading.Lock()
-
-
-def copy_stream(device):
-    """The stream this reader thread copies on: the threads share N_COPY_STREAMS streams per device (handed out round-robin).
-    Few, not one per thread: the runtime maps streams onto a handful of hardware queues, and a compute stream that lands in
-    the same queue as a copying stream has its kernels held up behind that stream's copies (measured: a 7.6 ms optimiser call
-    took 13.6 ms beside eight copying streams).  More than one, because copies of one stream run strictly one after the
-    other with a gap between them."""
-    with _copy_lock:
-        st = _copy_streams.setdefault(device, [[], 0])
-        if len(st[0]) < N_COPY_STREAMS:
-            st[0].append(torch.cuda.Stream(device=device, priority=STREAM_PRIORITY))
-        st[1] += 1
-        return st[0][(st[1] - 1) % len(st[0])]
-
-
-def _thread_state(device):
-    tl = _reader_local
-    if getattr(tl, "stream", None) is None or tl.device != device:
-        tl.stream, tl.device = copy_stream(device), device
-        tl.stage, tl.copied, tl.turn, tl.image = [None, None], [None, None], 0, None
-    return tl
-
-
-def _staging(tl, nbytes):
-    """One of this reader thread's two pinned staging buffers (uint8, at least nbytes), free to be written: the copy that last
-    used it has left it.  Two alternate, so that the next file is read while the last one is still crossing PCIe."""
-    k = tl.turn
-    tl.turn ^= 1
-    if tl.stage[k] is None or tl.stage[k].numel() < nbytes:
-        tl.stage[k] = torch.empty(nbytes + (1 << 20), dtype=torch.uint8).pin_memory()
-    if tl.copied[k] is not None:
-        tl.copied[k].synchronize()
-    return k, tl.stage[k]
-
-
 def read_file(file, device, image, size=None):
     """`file` -> this reader thread's pinned staging buffer -> `image` (uint8 device tensor of at least the file's size + 8), in
     slices, on the thread's own stream (gem_file_stage; the GIL is free for the whole call).  Returns (event, file size): the
     image is complete once the event has passed."""
     lib = _capi.load_library()
-    tl = _thread_state(device)
+    tl = thread_state(device)
     size = os.path.getsize(file) if size is None else size
-    k, stage = _staging(tl, size + 8)
+    k, stage = staging_buffer(tl, size + 8)
     got = C.c_int64()
     rc = lib.gem_file_stage(os.fsencode(file), device.index if device.index is not None else torch.cuda.current_device(),
                             C.c_void_p(stage.data_ptr()), C.c_void_p(image.data_ptr()), min(stage.numel(), image.numel()), SLICE_BYTES,
@@ -181,25 +146,25 @@ def read_file(file, device, image, size=None):
     return ev, got.value
 
 
-def gather_heat(c, image, offsets_d, dest, stream=None):
-    """The heat-maps of parsed chunk `c` out of the device image of its file: ONE kernel (gem_heat_gather) on the current stream
-    picks the arrays out at `offsets_d` (int64 device tensor [n]), undoes loadmat's Fortran order and rounds float64 to float32
-    -> dest [n,H,W,J] float32."""
+def gather_heat(image, image_len, offsets_d, n, shape, dtype, fortran, dest, stream=None):
+    """`n` heat-maps of `shape` (H, W, J) out of a device image of their file(s), `image_len` bytes of it valid: ONE kernel
+    (gem_heat_gather) on `stream` (default: the current one) picks the arrays out at `offsets_d` (int64 device tensor [n]), undoes
+    loadmat's Fortran order (`fortran`) and rounds float64 (`dtype` 1) to float32 -> dest [n,H,W,J] float32."""
     lib = _capi.load_library()
-    H, W, J = c["heat_shape"]
+    H, W, J = shape
     st = stream if stream is not None else torch.cuda.current_stream()
-    _capi.check(lib.gem_heat_gather(C.c_void_p(image.data_ptr()), c["file_bytes"], C.c_void_p(offsets_d.data_ptr()), c["n"], H, W, J,
-                                    c["heat_dtype"], c["heat_fortran"], C.c_void_p(dest.data_ptr()), C.c_void_p(st.cuda_stream)), lib)
+    _capi.check(lib.gem_heat_gather(C.c_void_p(image.data_ptr()), image_len, C.c_void_p(offsets_d.data_ptr()), n, H, W, J,
+                                    dtype, fortran, C.c_void_p(dest.data_ptr()), C.c_void_p(st.cuda_stream)), lib)
 
 
 def stage_list(c, device, dest=None):
     """The ordinary way for files the library's reader declined: the un-pickled heat-map list is stacked into this thread's pinned
     staging buffer and copied to `dest` (or a fresh tensor) on the thread's stream.  Returns (tensor, event)."""
     shape = (c["n"],) + tuple(c["heat_shape"])
-    tl = _thread_state(device)
+    tl = thread_state(device)
     numel = int(np.prod(shape))
     heat = c.pop("heat_list")
-    k, stage = _staging(tl, numel * 4)
+    k, stage = staging_buffer(tl, numel * 4)
     view = stage[:numel * 4].view(torch.float32).view(shape)
     if numel:
         if isinstance(heat, (list, tuple)):
@@ -227,10 +192,10 @@ def load_chunk(path, device=None, dest=None):
         c["heat"] = np.asarray(heat, dtype=np.float32).reshape((c["n"],) + tuple(c["heat_shape"]))
         return c
     c = parse_chunk(path)
-    if "heat_offsets" not in c:
+    if c["heat_via"] == LISTED:
         c["heat"], c["heat_ready"] = stage_list(c, device, dest)
         return c
-    tl = _thread_state(device)
+    tl = thread_state(device)
     shape = (c["n"],) + tuple(c["heat_shape"])
     with torch.cuda.stream(tl.stream):
         if tl.image is None or tl.image.numel() < c["file_bytes"] + 8:
@@ -238,52 +203,12 @@ def load_chunk(path, device=None, dest=None):
         read_file(os.path.join(path, "test_data.pkl"), device, tl.image, c["file_bytes"])
         t = dest if (dest is not None and tuple(dest.shape) == shape and dest.is_contiguous() and dest.dtype == torch.float32) else \
             torch.empty(shape, dtype=torch.float32, device=device)
-        gather_heat(c, tl.image, torch.from_numpy(c["heat_offsets"]).to(device), t, tl.stream)
+        gather_heat(tl.image, c["file_bytes"], torch.from_numpy(c["heat_offsets"]).to(device), c["n"], c["heat_shape"], c["heat_dtype"],
+                    c["heat_fortran"], t, tl.stream)
         ev = torch.cuda.Event()
         ev.record(tl.stream)
     c["heat"], c["heat_ready"] = t, ev
     return c
-
-
-_pools = {}
-
-
-def cpus_near(device):
-    """The CPUs of the NUMA node the device hangs off (its PCIe root), as far as this process may run on them -- or None when
-    the platform does not say.  The readers copy page cache -> pinned memory (which the runtime places next to the device):
-    from the other socket that copy crosses the inter-socket links and the read + host-to-device pipeline of a 2000-frame
-    sequence took 14.5 instead of 10.5 ms (tools/r06_numa_probe.py at commit 1ab2c18)."""
-    try:
-        p = torch.cuda.get_device_properties(device)
-        bdf = "%04x:%02x:%02x.0" % (p.pci_domain_id, p.pci_bus_id, p.pci_device_id)
-        node = int(open("/sys/bus/pci/devices/%s/numa_node" % bdf).read())
-        if node < 0:
-            return None
-        cpus = set()
-        for part in open("/sys/devices/system/node/node%d/cpulist" % node).read().strip().split(","):
-            lo, _, hi = part.partition("-")
-            cpus.update(range(int(lo), int(hi or lo) + 1))
-        cpus &= os.sched_getaffinity(0)
-        return cpus or None
-    except (OSError, ValueError, AttributeError, RuntimeError):
-        return None
-
-
-def _pool(name, workers, cpus=None):
-    """The process's pools of reader threads (thread start-up costs milliseconds here; the readers also keep their pinned
-    staging buffers between calls).  `cpus`: the threads of a NEW pool are confined to these."""
-    p = _pools.get(name)
-    if p is None or p[1] < workers:
-        from concurrent.futures import ThreadPoolExecutor
-
-        def confine():
-            if cpus:
-                try:
-                    os.sched_setaffinity(0, cpus)
-                except OSError:
-                    pass
-        p = _pools[name] = (ThreadPoolExecutor(max_workers=max(1, workers), thread_name_prefix="gem-" + name, initializer=confine), workers)
-    return p[0]
 
 
 class ChunkStream:
@@ -292,7 +217,7 @@ class ChunkStream:
 
     def __init__(self, paths, depth=8, workers=8, device=None):
         self._paths, self._depth, self._device = list(paths), max(1, depth), device
-        self._pool = _pool("read", workers)
+        self._readers = reader_pool("read", workers)
         self._pending, self._it = [], iter(self._paths)
 
     def prime(self):
@@ -300,7 +225,7 @@ class ChunkStream:
             p = next(self._it, None)
             if p is None:
                 break
-            self._pending.append(self._pool.submit(load_chunk, p, self._device))
+            self._pending.append(self._readers.submit(load_chunk, p, self._device))
         return self
 
     def __iter__(self):
@@ -312,23 +237,115 @@ class ChunkStream:
                     return
                 yield pending.pop(0).result()          # a reader's exception (e.g. KeyError) surfaces here
         finally:
-            _drain(pending)
+            drain(pending)
 
 
-def _drain(futures):
-    """Cancel what has not started, wait for what has (its buffers are about to be reused or released)."""
-    futures[:] = [f for f in futures if not f.done()]          # (the normal way out: everything has long finished)
-    for f in futures:
-        f.cancel()
-    for f in futures:
-        if not f.cancelled():
-            try:
-                f.result()
-            except Exception:
-                pass
-    del futures[:]
+def _resident_chunk(c):
+    """A `prepare.RecordingChunk` as the pipeline's ParsedChunk: the small arrays on the host (float64, the very values a pickle of
+    them would hold), the heat-maps where they are."""
+    host = lambda t: np.ascontiguousarray(t.detach().cpu().numpy() if hasattr(t, "detach") else t, dtype=np.float64)      # noqa: E731
+    heat = c.heat if hasattr(c.heat, "detach") else torch.as_tensor(np.asarray(c.heat, dtype=np.float32))
+    heat = heat.to(torch.device("cuda", torch.cuda.current_device()), dtype=torch.float32).contiguous()
+    return ParsedChunk(heat_via=RESIDENT, est_local=host(c.est_local), gt=host(c.gt), cams=host(c.cams), n=int(heat.shape[0]),
+                       heat_shape=tuple(heat.shape[1:]), heat=heat)
 
 
+# ------------------------------------------------------------------------------------------------------------------ the report
+def _report_inputs(chunks, starts, est_cat, cams_cat, seq_len, overlap, upload):
+    """The report's half that does not depend on the optimiser's result (equal chunks -- the reference's 100-frame chunks: the
+    sequences main() returns besides the optimised one, for ALL windows of the batch at once, the overlap merges vectorised over
+    the chunks), computed and uploaded while the files are still arriving."""
+    gt_cat = np.concatenate([c["gt"] for c in chunks])
+    idx = np.concatenate(starts)[:, None] + np.arange(seq_len)[None]
+    cam_w = cams_cat[idx]
+    est_m = merge_chunks(to_global_numpy(relative_global_numpy(est_cat[idx], cam_w), cam_w), len(chunks), overlap)
+    gt_m = merge_chunks(gt_cat[idx], len(chunks), overlap)
+    # (stage one's global sequence: C0 (C0^-1 C_t) X as ONE transform per frame, composed here in the reference's order --
+    # utils/utils.py:99-112 then optimizer.py:302-308 -- so that the result-dependent half is a multiply-add)
+    A = np.matmul(cam_w[:, :1], np.matmul(np.linalg.inv(cam_w[:, 0])[:, None], cam_w))
+    return {"mid_A": np.ascontiguousarray(np.moveaxis(A[..., :3, :], (-2, -1), (0, 1))[..., None]), "est_m": est_m, "gt_m": gt_m,      # mid_A [3,4,W,T,1]
+            "est_d": upload(est_m.reshape(-1, 15, 3), torch.float64), "gt_d": upload(gt_m.reshape(-1, 15, 3), torch.float64)}
+
+
+def _report_batched(engine, report, mid_np, opt_global, n_chunks, overlap, smooth, upload, lap):
+    """The error reports of all chunks of a batch as ONE library call, read back with ONE synchronisation (`report`: what
+    `_report_inputs` prepared).  -> per chunk (error dict, estimated / optimised / ground-truth sequence, the report's raw row)."""
+    A, X = report["mid_A"], np.ascontiguousarray(np.moveaxis(mid_np.astype(np.float64), -1, 0))          # X [3,W,T,J]
+    mid_g = np.empty(mid_np.shape, dtype=np.float64)
+    for d in range(3):
+        mid_g[..., d] = A[d, 0] * X[0] + A[d, 1] * X[1] + A[d, 2] * X[2] + A[d, 3]
+    mid_m = merge_chunks(mid_g, n_chunks, overlap)
+    fpc = report["est_m"].shape[1]
+    lap("report: stage-one sequences (host float64)")
+    opt_d = engine.merge_windows(opt_global, n_chunks, overlap=overlap, smooth=smooth)          # [n_chunks*fpc,15,3] f64, device
+    mid_d = upload(mid_m.reshape(n_chunks * fpc, 15, 3), torch.float64)
+    reps = engine.calculate_errors_chunks(report["est_d"], mid_d, opt_d, report["gt_d"], n_chunks)
+    lap("report: merge + error kernels enqueued")
+    reps = reps.cpu().numpy()
+    opt_m = opt_d.cpu().numpy().reshape(n_chunks, fpc, 15, 3)
+    lap("report: read-back")
+    rows = []
+    for k in range(n_chunks):
+        res = OrderedDict(zip(engine.ERROR_KEYS, reps[k, :17].tolist()))
+        res["joints_error"] = reps[k, 17:].copy()
+        rows.append((res, report["est_m"][k], opt_m[k], report["gt_m"][k], reps[k]))
+    return rows
+
+
+def _report_per_chunk(engine, chunks, mid_np, opt_global, seq_len, overlap, smooth, device_metrics):
+    """The reports chunk by chunk (chunks of different lengths, or device_metrics=False).  -> per chunk (error dict, estimated /
+    optimised / ground-truth sequence, None), or None for a chunk too short for a window."""
+    rows, w0 = [], 0
+    for c in chunks:
+        nw = len(c["starts"])
+        sl = slice(w0, w0 + nw)
+        w0 += nw
+        if nw == 0:
+            rows.append(None)
+            continue
+        loc_w, cam_w = cut_windows(c["est_local"], c["starts"], seq_len), cut_windows(c["cams"], c["starts"], seq_len)
+        est_seq = merge_batches(to_global_numpy(relative_global_numpy(loc_w, cam_w), cam_w), overlap)
+        mid_seq = merge_batches(to_global_numpy(relative_global_numpy(mid_np[sl], cam_w), cam_w), overlap)
+        gt_seq = merge_batches(cut_windows(c["gt"], c["starts"], seq_len), overlap)
+        if device_metrics:
+            opt_seq_d = engine.merge_windows(opt_global[sl], 1, overlap=overlap, smooth=smooth)
+            res = engine.calculate_errors(est_seq, mid_seq, opt_seq_d, gt_seq)
+            opt_seq = opt_seq_d.cpu().numpy()
+        else:
+            opt_seq = merge_batches(opt_global[sl].cpu().numpy(), overlap)
+            if smooth:
+                opt_seq = final_smooth(opt_seq)
+            res = calculate_errors(est_seq, mid_seq, opt_seq, gt_seq)
+        rows.append((res, np.asarray(est_seq), np.asarray(opt_seq), np.asarray(gt_seq), None))
+    return rows
+
+
+def _sequence_result(rows, title, verbose):
+    """One sequence's return value from its chunks' report rows: (summary, per-chunk error dicts, estimated_pose, optimized_pose,
+    gt_pose), the summary printed as the reference prints it (under `title` when there is one)."""
+    results, raw = [r[0] for r in rows], [r[4] for r in rows]
+    summary = OrderedDict()
+    if all(x is not None for x in raw):          # (every chunk of the sequence came as a row of the device report: one mean)
+        mean = np.mean(np.stack(raw), axis=0)
+        for i, k in enumerate(results[0]):
+            summary[k] = mean[17:].copy() if k == "joints_error" else float(mean[i])
+    else:
+        for k in results[0]:
+            summary[k] = (np.mean([r[k] for r in results], axis=0) if k == "joints_error"
+                          else float(np.average([r[k] for r in results])))
+    if verbose:
+        if title is not None:
+            print("sequence: {}".format(title))
+        for line in SUMMARY_LINES:
+            print("-----------------------------------------" if line is None else "{}: {}".format(line[0], summary[line[1]]))
+        print("joints error is: {}".format(summary["joints_error"]))
+        print("-------------------------------------------------------------")
+    # the three pose sequences as arrays [frames,15,3] (iterating them yields the [15,3] frames the reference's lists hold)
+    return (summary, results) + tuple(np.concatenate([r[i] for r in rows]) if rows else np.empty((0, 15, 3)) for i in (1, 2, 3))
+
+
+# ------------------------------------------------------------------------------------------------------------------ the batch pipeline
+_heat_pool = {}                   # device -> per batch in flight: [frame buffer, file-image arena, Scratch] (kept between calls)
 _noise_pool = {}
 N_BUFFERS = 3                     # batches in flight: one computing, one arriving, one being reported
 
@@ -355,46 +372,232 @@ def _draw_noise(rows, D, slot=0):
     return buf[:total]
 
 
-class _Scratch:
-    """A pinned block per batch in flight for the SMALL arrays (poses, cameras, window tables, payload offsets, report inputs):
-    they go to the device with asynchronous copies from it.  (A pageable copy blocks the calling thread until the copy engines
-    get to it -- behind the readers' 4 MB slices that is milliseconds per array.)"""
-
-    def __init__(self, device):
-        self.device, self.buf, self.at = device, None, 0
-
-    def reset(self, nbytes):
-        if self.buf is None or self.buf.numel() < nbytes:
-            self.buf = torch.empty(2 * nbytes, dtype=torch.uint8).pin_memory()
-        self.at = 0
-
-    def upload(self, a, dtype):
-        a = np.asarray(a)
-        n = int(a.size) * torch.empty(0, dtype=dtype).element_size()
-        if self.buf is None or self.at + n + 64 > self.buf.numel():          # (more than reset() was told: an ordinary copy)
-            return torch.as_tensor(a, dtype=dtype).to(self.device).contiguous()
-        view = self.buf[self.at:self.at + n].view(dtype).view(a.shape)
-        self.at += (n + 63) // 64 * 64
-        np.copyto(view.numpy(), a, casting="unsafe")
-        return view.to(self.device, non_blocking=True)
+_Source = namedtuple("_Source", "group what name")          # a chunk of sequence `group`: a chunk directory or a prepare.RecordingChunk; `name` is what verbose=True prints
 
 
 class _Batch:
-    """One device call's worth of chunks on its way through the pipeline (see optimize_sequences)."""
-    __slots__ = ("index", "paths", "files", "sizes", "parsing", "chunks", "reading", "images", "noise", "pending", "starts", "bounds",
-                 "counts", "est_cat", "cams_cat", "prep", "heat", "dests", "listed", "offsets", "report", "weights", "done")
+    """One device call's worth of chunks on its way through the pipeline (see _Pipeline)."""
+    __slots__ = ("index", "sources", "parsing", "chunks", "reading", "images", "noise", "pending", "counts", "prep", "heat", "dests",
+                 "listed", "offsets", "report", "weights", "done")
 
-    def __init__(self, index, paths):
-        self.index, self.paths = index, paths
-        self.files = [os.path.join(q, "test_data.pkl") for q in paths]
-        self.sizes = self.parsing = self.chunks = self.reading = self.images = self.noise = self.pending = self.report = None
+    def __init__(self, index, sources):
+        self.index, self.sources = index, sources
+        self.parsing = self.chunks = self.reading = self.images = self.noise = self.pending = self.report = None
 
 
-def optimize_sequences(data_dirs, camera_model_path, vae_weight=0.0, gmm_weight=0.0, smoothness_weight=0.001,
-                       bone_length_weight=0.01, weight_3d=0.01, reproj_weight=0.01, final_smooth=True, merge=True,
-                       global_vae_path=GLOBAL_VAE_PATH, local_vae_path=LOCAL_VAE_PATH, chunks_per_batch=None, optimizer=None,
-                       device_metrics=True, verbose=True, seq_len=SEQ_LEN, overlap=OVERLAP, timings=None, per_sequence=False,
-                       _recordings=None):
+def _settings(camera_model_path, vae_weight=0.0, gmm_weight=0.0, smoothness_weight=0.001, bone_length_weight=0.01, weight_3d=0.01,
+              reproj_weight=0.01, final_smooth=True, merge=True, global_vae_path=GLOBAL_VAE_PATH, local_vae_path=LOCAL_VAE_PATH,
+              chunks_per_batch=None, optimizer=None, device_metrics=True, verbose=True, seq_len=SEQ_LEN, overlap=OVERLAP, timings=None,
+              per_sequence=False):
+    """The arguments of `optimize_sequences` / `optimize_recordings` behind the sequences themselves, as one object.
+    (`gmm_weight` and `merge` are accepted and unused, as in the reference: SURVEY D4.)"""
+    return SimpleNamespace(**locals())
+
+
+class _Pipeline:
+    """The private driver behind `optimize_sequences` and `optimize_recordings`: `groups[g]` are the chunk sources (_Source) of
+    sequence g.  It holds one call's batches and what their stages share: the settings, the optimiser, the device's buffers
+    (`slots`: one set per batch in flight), the reader pools, every future handed to a pool, and the report rows filed per
+    sequence.
+
+    Per batch: `start` (its files start moving), `prepare` (everything that needs neither the heat-maps nor the device's
+    attention), `fire` (gathers + the optimiser's call enqueued), `finish` (results read back and reported).  `run` interleaves
+    them so that the device never waits for the host."""
+
+    def __init__(self, groups, cfg, lap):
+        self.cfg, self.lap, self.opt = cfg, lap, cfg.optimizer
+        n = cfg.chunks_per_batch
+        spans = groups if cfg.per_sequence else [[s for g in groups for s in g]]          # a batch does not cross these
+        lists = [g[i:i + (n or len(g))] for g in spans for i in range(0, len(g), n or len(g))]
+        self.batches = [_Batch(i, l) for i, l in enumerate(lists)]
+        self.rows = [[] for _ in groups]
+        self.device = torch.device("cuda", torch.cuda.current_device())
+        self.parse_pool, self.read_pool = reader_pool("parse", 8), reader_pool("read", 8, cpus_near(self.device))
+        self.noise_pool = reader_pool("noise", 1)
+        self.slots = _heat_pool.setdefault(self.device, [[None, None, Scratch(self.device)] for _ in range(N_BUFFERS)])
+        self.submitted = []                          # every future handed to a pool (drained on the way out, whatever happens)
+
+    def slot(self, b):
+        return self.slots[b.index % N_BUFFERS]
+
+    def start(self, b):
+        """Batch b's files start moving: read tasks (they need the files' sizes only) and, beside them, the parse tasks.  A
+        Recording's chunks are on the device already: nothing is read or parsed."""
+        if b.reading is not None:
+            return
+        if not isinstance(b.sources[0].what, str):
+            b.reading, b.images, b.chunks = [], [], [_resident_chunk(s.what) for s in b.sources]
+            return
+        files = [os.path.join(s.what, "test_data.pkl") for s in b.sources]
+        sizes = [os.path.getsize(f) for f in files]          # (FileNotFoundError here, like the reference's open())
+        at, room, total = side_by_side(sizes, _PAD)
+        slot = self.slot(b)
+        if slot[1] is None or slot[1].numel() < total:
+            slot[1] = None
+            slot[1] = torch.empty(total, dtype=torch.uint8, device=self.device)
+        b.images = [slot[1][o:o + r] for o, r in zip(at.tolist(), room.tolist())]
+        b.reading = [self.read_pool.submit(read_file, f, self.device, img, sz) for f, img, sz in zip(files, b.images, sizes)]
+        b.parsing = [self.parse_pool.submit(parse_chunk, s.what) for s in b.sources]
+        self.submitted.extend(b.reading + b.parsing)
+
+    def prepare(self, b):
+        """Everything of batch b that needs neither its heat-maps nor the device's attention: parses awaited, window tables, the
+        small arrays on their way to the device, the noise being drawn, the report's result-independent half."""
+        cfg, lap = self.cfg, self.lap
+        self.start(b)
+        if b.parsing is not None:
+            b.chunks = [f.result() for f in b.parsing]            # (KeyError etc. surface here)
+        lap("wait for the parses")
+        starts, chunk_of, bounds, f_off = [], [], [], 0
+        for ci, (c, src) in enumerate(zip(b.chunks, b.sources)):
+            if cfg.verbose:
+                print("running data: {}".format(src.name))
+            s = window_starts(len(c["est_local"]), cfg.seq_len, cfg.overlap)
+            c["starts"] = s
+            starts.append(s + f_off)
+            chunk_of.append(np.full(len(s), ci, dtype=np.int64))
+            bounds.append((f_off, f_off + len(c["est_local"])))
+            f_off += len(c["est_local"])
+        n_win = int(sum(len(s) for s in starts))
+        if self.opt is None:
+            self.opt = SequenceOptimizer(cfg.camera_model_path, cfg.global_vae_path, cfg.local_vae_path, max_windows=max(n_win, 1),
+                                         seq_len=cfg.seq_len)
+        if n_win > self.opt.engine.max_windows:
+            raise ValueError("%d windows in one batch exceed the engine's max_windows=%d: pass chunks_per_batch" %
+                             (n_win, self.opt.engine.max_windows))
+        b.noise = self.noise_pool.submit(_draw_noise, [2 * len(c["starts"]) for c in b.chunks], self.opt.engine.D, b.index % N_BUFFERS)
+        self.submitted.append(b.noise)
+        b.listed = [(i, self.read_pool.submit(stage_list, c, self.device)) for i, c in enumerate(b.chunks) if c["heat_via"] == LISTED]
+        self.submitted.extend(f for _, f in b.listed)      # (files the library's reader declined: stacked on the host)
+        b.weights = self.opt.stage_weights(cfg.vae_weight, cfg.smoothness_weight, cfg.bone_length_weight, cfg.weight_3d, cfg.reproj_weight)
+        est_cat = np.concatenate([c["est_local"] for c in b.chunks])
+        cams_cat = np.concatenate([c["cams"] for c in b.chunks])
+        b.counts = [len(c["starts"]) for c in b.chunks]
+        lap("window tables")
+        slot = self.slot(b)
+        slot[2].reset(len(est_cat) * (45 * 4 + 16 * 8 + 8 + 3 * 45 * 8) + 16 * n_win + 8192)
+        b.prep = self.opt.prepare(est_cat, cams_cat, np.concatenate(starts), np.concatenate(chunk_of), bounds, timings=cfg.timings,
+                                  upload=slot[2].upload)
+        # the batch's frame buffer (one shape of heat-map: the chunks' frames side by side)
+        frames = sum(c["n"] for c in b.chunks)
+        shapes = {tuple(c["heat_shape"]) for c in b.chunks}
+        b.heat, b.dests = None, [None] * len(b.chunks)
+        if len(shapes) == 1 and frames:
+            hs = next(iter(shapes))
+            if slot[0] is None or slot[0].shape[0] < frames or tuple(slot[0].shape[1:]) != hs:
+                slot[0] = None
+                slot[0] = torch.empty((frames,) + hs, dtype=torch.float32, device=self.device)
+            b.heat = slot[0][:frames]
+            b.dests = [b.heat[lo:hi] for lo, hi in bounds]
+        # (where every heat-map's raw data lie in the ARENA of file images: the file's place in the arena + the array's place in the file)
+        located = [c["heat_offsets"] + (b.images[i].data_ptr() - slot[1].data_ptr()) for i, c in enumerate(b.chunks) if c["heat_via"] == LOCATED]
+        b.offsets = slot[2].upload(np.concatenate(located), torch.int64) if located else None
+        lap("small uploads")
+        b.report = None
+        if cfg.device_metrics and b.counts and min(b.counts) == max(b.counts) and b.counts[0] > 0:
+            b.report = _report_inputs(b.chunks, starts, est_cat, cams_cat, cfg.seq_len, cfg.overlap, slot[2].upload)
+        lap("report preparation")
+
+    def fire(self, b):
+        """Batch b goes to the device: its files' last copies awaited (issued, not finished), the heat-maps gathered into the frame
+        buffer by the way they travel, the optimiser's call enqueued behind them.  Nothing waits for the device."""
+        lap, timings = self.lap, self.cfg.timings
+        eps = b.noise.result()
+        lap("wait for the noise")
+        cur = torch.cuda.current_stream()
+        at, parts = 0, [None] * len(b.chunks)
+        located = [i for i, c in enumerate(b.chunks) if c["heat_via"] == LOCATED]
+        for i in located:
+            ev, _ = b.reading[i].result()             # (the file's last copy has been issued: its event is recorded)
+            cur.wait_event(ev)
+        arena = self.slot(b)[1]
+        kinds = {(b.chunks[i]["heat_dtype"], b.chunks[i]["heat_fortran"], tuple(b.chunks[i]["heat_shape"])) for i in located}
+        if b.heat is not None and len(located) == len(b.chunks) and len(kinds) == 1 and len(b.heat) <= 65535:
+            # every chunk's file image lies in ONE arena and their frames side by side in the batch's frame buffer: one launch picks all
+            # heat-maps out (b.offsets was built relative to the arena in prepare())
+            dtype, fortran, shape = next(iter(kinds))
+            gather_heat(arena, arena.numel(), b.offsets, len(b.heat), shape, dtype, fortran, b.heat, cur)
+        else:
+            for i in located:
+                c = b.chunks[i]
+                parts[i] = b.dests[i] if b.dests[i] is not None else torch.empty((c["n"],) + tuple(c["heat_shape"]), dtype=torch.float32, device=self.device)
+                base = b.images[i].data_ptr() - arena.data_ptr()
+                gather_heat(arena, base + c["file_bytes"], b.offsets[at:at + c["n"]], c["n"], c["heat_shape"], c["heat_dtype"], c["heat_fortran"],
+                            parts[i], cur)
+                at += c["n"]
+        for i, f in b.listed:
+            t, ev = f.result()
+            cur.wait_event(ev)
+            t.record_stream(cur)
+            parts[i] = b.dests[i].copy_(t) if b.dests[i] is not None else t
+        for i, c in enumerate(b.chunks):
+            if c["heat_via"] == RESIDENT:             # device to device
+                parts[i] = b.dests[i].copy_(c["heat"]) if b.dests[i] is not None else c["heat"]
+        lap("wait for the readers")
+        if b.index + 1 < len(self.batches):          # the next batch's files start moving behind this batch's last copy: they arrive
+            self.start(self.batches[b.index + 1])    # while this batch is on the device
+        if timings is not None and timings.get("_synchronise"):          # developer timing only: separates the PCIe tail from the optimiser's time
+            cur.synchronize()
+            lap("h2d tail (timing runs only: synchronised)")
+        heat_d = b.heat if b.heat is not None else (parts[0] if len(parts) == 1 else torch.cat(parts))
+        b.pending = self.opt.fire(b.prep, heat_d, b.weights[0], b.weights[1], eps=eps, timings=timings)
+        b.done = torch.cuda.Event()
+        b.done.record(cur)
+        lap("enqueue")
+
+    def finish(self, b):
+        """Batch b's results: waits for the device, merges / smooths / scores on it, files the report rows per sequence."""
+        # on a stream of its own, behind the batch's LAST kernel only: on the optimiser's stream the read-back would queue up
+        # behind the next batch's whole device call, which is already enqueued there
+        cfg, lap, e = self.cfg, self.lap, self.opt.engine
+        rs = report_stream(self.device)
+        rs.wait_event(b.done)
+        for t in b.pending:
+            if t is not None:
+                t.record_stream(rs)
+        with torch.cuda.stream(rs):
+            mid_local, opt_global, _ = self.opt.collect(b.pending, keep_device=True)
+            b.pending = None
+            lap("wait for the device + stats")
+            mid_np = mid_local.cpu().numpy()
+            lap("report: stage-one poses to the host")
+            if b.report is not None:
+                rows = _report_batched(e, b.report, mid_np, opt_global, len(b.chunks), cfg.overlap, bool(cfg.final_smooth),
+                                       self.slot(b)[2].upload, lap)
+            else:
+                rows = _report_per_chunk(e, b.chunks, mid_np, opt_global, cfg.seq_len, cfg.overlap, bool(cfg.final_smooth), cfg.device_metrics)
+            for src, row in zip(b.sources, rows):
+                if row is not None:
+                    self.rows[src.group].append(row)
+                    if cfg.verbose and row[0]["bone_length_aligned_optimized_mpjpe"] > row[0]["bone_length_aligned_mid_optimized_mpjpe"]:
+                        print(row[0])
+            lap("report: result dicts" if b.report is not None else "sequences + reports")
+
+    def run(self, titles):
+        """Every batch through its stages.  -> one `optimize_directory` result per sequence (`titles[g]`: sequence g's name in the
+        printed summary)."""
+        self.lap("plan")
+        try:
+            prev = None
+            for b in self.batches:
+                self.prepare(b)               # while batch k-1 is on the device and batch k's files are arriving ...
+                self.fire(b)                  # ... batch k is enqueued behind it as soon as its last file has been sent ...
+                if prev is not None:
+                    self.finish(prev)         # ... and only then batch k-1's report is read back: the device never waits for the host
+                    prev.chunks = prev.reading = prev.parsing = prev.images = prev.report = prev.prep = None
+                prev = b
+            self.finish(prev)
+        finally:
+            drain(self.submitted)
+            if any(b.pending is not None for b in self.batches):
+                torch.cuda.synchronize()      # (an exception left device work behind that reads this call's buffers)
+        self.lap("readers drained")
+        out = [_sequence_result(rows, title if len(titles) > 1 else None, self.cfg.verbose) for rows, title in zip(self.rows, titles)]
+        self.lap("summaries")
+        return out
+
+
+def optimize_sequences(data_dirs, camera_model_path, *args, **kwargs):
     """Several sequences through the device: the chunks of every directory of `data_dirs`, `chunks_per_batch` per device call
     (default: all of them in ONE call -- BASELINE configs[2]: all test sequences concurrently on one GPU; per_sequence=True: one
     call per directory), the reports per sequence.  Returns a list of (summary, per-chunk error dicts, estimated_pose,
@@ -408,321 +611,26 @@ def optimize_sequences(data_dirs, camera_model_path, vae_weight=0.0, gmm_weight=
     behind batch k's, so they arrive while batch k is on the device, and batch k+1 is enqueued before batch k's report is read
     back.  The frame buffers, file-image arenas, noise blocks and reader threads this module keeps between calls (about 1 GB
     of HBM and 0.4 GB of pinned host memory per 2000-frame batch in flight, at most three) are shared by all calls of the
-    process without locking -- one call at a time -- and are given back by `release_pools()`."""
-    del gmm_weight, merge                       # accepted and unused, as in the reference (SURVEY D4)
-    import time
-    tick = [time.perf_counter()]
-    t_begin = tick[0]
+    process without locking -- one call at a time -- and are given back by `release_pools()`.
 
-    def lap(name):          # developer timing (tools/whole_sequence_timing.py): wall time of the main thread's phases
-        if timings is not None:
-            now = time.perf_counter()
-            timings[name] = timings.get(name, 0.0) + (now - tick[0])
-            timings.setdefault("_log", []).append((round((now - t_begin) * 1e3, 2), name))
-            tick[0] = now
-    groups, group_of, resident = [], {}, {}
-    if _recordings is not None:          # (optimize_recordings: the chunks are on the device already, nothing is read or parsed)
-        data_dirs = ["recording_%d" % gi for gi in range(len(_recordings))]
-        for d, rec in zip(data_dirs, _recordings):
-            resident.update((os.path.join(d, c.name), c) for c in rec.chunks)
+    Further arguments, positional or by keyword, in this order (defaults: `_settings`): vae_weight, gmm_weight, smoothness_weight,
+    bone_length_weight, weight_3d, reproj_weight, final_smooth, merge, global_vae_path, local_vae_path, chunks_per_batch, optimizer,
+    device_metrics, verbose, seq_len, overlap, timings, per_sequence."""
+    cfg = _settings(camera_model_path, *args, **kwargs)
+    lap = Laps(cfg.timings, log=True)          # developer timing (tools/whole_sequence_timing.py): wall time of the main thread's phases
+    groups = []
     for gi, d in enumerate(data_dirs):
-        ps = list_chunks(d) if _recordings is None else [os.path.join(d, c.name) for c in _recordings[gi].chunks]
-        if not ps:
+        groups.append([_Source(gi, q, q) for q in list_chunks(d)])
+        if not groups[-1]:
             raise FileNotFoundError("no chunk directories under %s" % d)
-        for q in ps:
-            group_of[q] = gi
-        groups.append(ps)
-    if per_sequence:
-        lists = [g[i:i + (chunks_per_batch or len(g))] for g in groups for i in range(0, len(g), chunks_per_batch or len(g))]
-    else:
-        flat = [q for g in groups for q in g]
-        lists = [flat[i:i + (chunks_per_batch or len(flat))] for i in range(0, len(flat), chunks_per_batch or len(flat))]
-    batches = [_Batch(i, l) for i, l in enumerate(lists)]
-    n_groups = len(data_dirs)
-    opt = [optimizer]
-    results, est_all, opt_all, gt_all, raw_rows = ([[] for _ in range(n_groups)] for _ in range(5))
-    device = torch.device("cuda", torch.cuda.current_device())
-    parse_pool, read_pool, noise_pool = _pool("parse", 8), _pool("read", 8, cpus_near(device)), _pool("noise", 1)
-    slots = _heat_pool.setdefault(device, [[None, None, _Scratch(device)] for _ in range(N_BUFFERS)])
-    submitted = []                               # every future handed to a pool (drained on the way out, whatever happens)
-
-    def start(b):
-        """Batch b's files start moving: read tasks (they need the files' sizes only) and, beside them, the parse tasks."""
-        if b.reading is not None:
-            return
-        if resident:
-            b.sizes, b.images, b.reading = [0] * len(b.paths), [None] * len(b.paths), []
-            b.parsing = [_Ready(_resident_chunk(resident[q], q)) for q in b.paths]
-            return
-        b.sizes = [os.path.getsize(f) for f in b.files]          # (FileNotFoundError here, like the reference's open())
-        at, total = [], 0
-        for sz in b.sizes:
-            at.append(total)
-            total += (sz + 8 + _PAD - 1) // _PAD * _PAD
-        slot = slots[b.index % N_BUFFERS]
-        if slot[1] is None or slot[1].numel() < total:
-            slot[1] = None
-            slot[1] = torch.empty(total, dtype=torch.uint8, device=device)
-        b.images = [slot[1][o:o + (sz + 8 + _PAD - 1) // _PAD * _PAD] for o, sz in zip(at, b.sizes)]
-        b.reading = [read_pool.submit(read_file, f, device, img, sz) for f, img, sz in zip(b.files, b.images, b.sizes)]
-        b.parsing = [parse_pool.submit(parse_chunk, q) for q in b.paths]
-        submitted.extend(b.reading + b.parsing)
-
-    def prepare(b):
-        """Everything of batch b that needs neither its heat-maps nor the device's attention: parses awaited, window tables, the
-        small arrays on their way to the device, the noise being drawn, the report's result-independent half."""
-        start(b)
-        b.chunks = [f.result() for f in b.parsing]                # (KeyError etc. surface here)
-        lap("wait for the parses")
-        starts, chunk_of, bounds, f_off = [], [], [], 0
-        for ci, c in enumerate(b.chunks):
-            if verbose:
-                print("running data: {}".format(c["path"]))
-            s = window_starts(len(c["est_local"]), seq_len, overlap)
-            c["starts"] = s
-            starts.append(s + f_off)
-            chunk_of.append(np.full(len(s), ci, dtype=np.int64))
-            bounds.append((f_off, f_off + len(c["est_local"])))
-            f_off += len(c["est_local"])
-        n_win = int(sum(len(s) for s in starts))
-        if opt[0] is None:
-            opt[0] = SequenceOptimizer(camera_model_path, global_vae_path, local_vae_path, max_windows=max(n_win, 1), seq_len=seq_len)
-        if n_win > opt[0].engine.max_windows:
-            raise ValueError("%d windows in one batch exceed the engine's max_windows=%d: pass chunks_per_batch" %
-                             (n_win, opt[0].engine.max_windows))
-        b.noise = noise_pool.submit(_draw_noise, [2 * len(c["starts"]) for c in b.chunks], opt[0].engine.D, b.index % N_BUFFERS)
-        submitted.append(b.noise)
-        b.listed = [(i, read_pool.submit(stage_list, c, device)) for i, c in enumerate(b.chunks) if "heat_list" in c]
-        submitted.extend(f for _, f in b.listed)      # (files the library's reader declined: stacked on the host)
-        b.weights = opt[0].stage_weights(vae_weight, smoothness_weight, bone_length_weight, weight_3d, reproj_weight)
-        b.est_cat = np.concatenate([c["est_local"] for c in b.chunks])
-        b.cams_cat = np.concatenate([c["cams"] for c in b.chunks])
-        b.starts, b.bounds, b.counts = starts, bounds, [len(c["starts"]) for c in b.chunks]
-        lap("window tables")
-        slot = slots[b.index % N_BUFFERS]
-        slot[2].reset(len(b.est_cat) * (45 * 4 + 16 * 8 + 8 + 3 * 45 * 8) + 16 * n_win + 8192)
-        b.prep = opt[0].prepare(b.est_cat, b.cams_cat, np.concatenate(starts), np.concatenate(chunk_of), bounds, timings=timings,
-                                upload=slot[2].upload)
-        # the batch's frame buffer (one shape of heat-map: the chunks' frames side by side) and the table of payload offsets
-        frames = sum(c["n"] for c in b.chunks)
-        shapes = {tuple(c["heat_shape"]) for c in b.chunks}
-        b.heat, b.dests = None, [None] * len(b.chunks)
-        if len(shapes) == 1 and frames:
-            hs = next(iter(shapes))
-            if slot[0] is None or slot[0].shape[0] < frames or tuple(slot[0].shape[1:]) != hs:
-                slot[0] = None
-                slot[0] = torch.empty((frames,) + hs, dtype=torch.float32, device=device)
-            b.heat = slot[0][:frames]
-            b.dests = [b.heat[lo:hi] for lo, hi in bounds]
-        # (where every heat-map's raw data lie in the ARENA of file images: the file's place in the arena + the array's place in the file)
-        native = [c["heat_offsets"] + (img.data_ptr() - slot[1].data_ptr()) for c, img in zip(b.chunks, b.images) if "heat_offsets" in c]
-        b.offsets = slot[2].upload(np.concatenate(native), torch.int64) if native else None
-        lap("small uploads")
-        # the report's half that does not depend on the optimiser's result (equal chunks -- the reference's 100-frame chunks:
-        # the sequences main() returns besides the optimised one, for ALL windows of the batch at once, the overlap merges
-        # vectorised over the chunks), computed and uploaded while the files are still arriving
-        counts = b.counts
-        b.report = None
-        if device_metrics and counts and min(counts) == max(counts) and counts[0] > 0:
-            gt_cat = np.concatenate([c["gt"] for c in b.chunks])
-            idx = np.concatenate(starts)[:, None] + np.arange(seq_len)[None]
-            cam_w = b.cams_cat[idx]
-            est_m = merge_chunks(to_global_numpy(relative_global_numpy(b.est_cat[idx], cam_w), cam_w), len(b.chunks), overlap)
-            gt_m = merge_chunks(gt_cat[idx], len(b.chunks), overlap)
-            # (stage one's global sequence: C0 (C0^-1 C_t) X as ONE transform per frame, composed here in the reference's order --
-            # utils/utils.py:99-112 then optimizer.py:302-308 -- so that the result-dependent half is a multiply-add)
-            A = np.matmul(cam_w[:, :1], np.matmul(np.linalg.inv(cam_w[:, 0])[:, None], cam_w))
-            b.report = {"mid_A": np.ascontiguousarray(np.moveaxis(A[..., :3, :], (-2, -1), (0, 1))[..., None]), "est_m": est_m, "gt_m": gt_m,      # mid_A [3,4,W,T,1]
-                        "est_d": slot[2].upload(est_m.reshape(-1, 15, 3), torch.float64),
-                        "gt_d": slot[2].upload(gt_m.reshape(-1, 15, 3), torch.float64)}
-        lap("report preparation")
-
-    def fire(b):
-        """Batch b goes to the device: its files' last copies awaited (issued, not finished), one gather kernel per chunk, the
-        optimiser's call enqueued behind them.  Nothing waits for the device."""
-        eps = b.noise.result()
-        lap("wait for the noise")
-        cur = torch.cuda.current_stream()
-        at, parts = 0, [None] * len(b.chunks)
-        native = [i for i, c in enumerate(b.chunks) if "heat_offsets" in c]
-        for i in native:
-            ev, _ = b.reading[i].result()             # (the file's last copy has been issued: its event is recorded)
-            cur.wait_event(ev)
-        kinds = {(b.chunks[i]["heat_dtype"], b.chunks[i]["heat_fortran"], tuple(b.chunks[i]["heat_shape"])) for i in native}
-        if b.heat is not None and len(native) == len(b.chunks) and len(kinds) == 1 and sum(c["n"] for c in b.chunks) <= 65535:
-            # every chunk's file image lies in ONE arena and their frames side by side in the batch's frame buffer: one launch picks all
-            # heat-maps out (b.offsets was built relative to the arena in prepare())
-            arena = slots[b.index % N_BUFFERS][1]
-            c0 = b.chunks[0]
-            whole = ParsedChunk(n=sum(c["n"] for c in b.chunks), heat_shape=c0["heat_shape"], heat_dtype=c0["heat_dtype"], heat_fortran=c0["heat_fortran"],
-                                file_bytes=arena.numel())
-            gather_heat(whole, arena, b.offsets, b.heat, cur)
-            for i in native:
-                parts[i] = b.dests[i]
-        else:
-            for i in native:
-                c = b.chunks[i]
-                parts[i] = b.dests[i] if b.dests[i] is not None else torch.empty((c["n"],) + tuple(c["heat_shape"]), dtype=torch.float32, device=device)
-                base = b.images[i].data_ptr() - slots[b.index % N_BUFFERS][1].data_ptr()
-                gather_heat(ParsedChunk(c, file_bytes=base + c["file_bytes"]), slots[b.index % N_BUFFERS][1], b.offsets[at:at + c["n"]], parts[i], cur)
-                at += c["n"]
-        for i, f in b.listed:
-            t, ev = f.result()
-            cur.wait_event(ev)
-            t.record_stream(cur)
-            parts[i] = b.dests[i].copy_(t) if b.dests[i] is not None else t
-        for i, c in enumerate(b.chunks):
-            if "heat" in c:                           # a Recording's chunk: device to device
-                parts[i] = b.dests[i].copy_(c["heat"]) if b.dests[i] is not None else c["heat"]
-        lap("wait for the readers")
-        if b.index + 1 < len(batches):               # the next batch's files start moving behind this batch's last copy: they arrive
-            start(batches[b.index + 1])              # while this batch is on the device
-        if timings is not None and timings.get("_synchronise"):          # developer timing only: separates the PCIe tail from the optimiser's time
-            cur.synchronize()
-            lap("h2d tail (timing runs only: synchronised)")
-        heat_d = b.heat if b.heat is not None else (parts[0] if len(parts) == 1 else torch.cat(parts))
-        b.pending = opt[0].fire(b.prep, heat_d, b.weights[0], b.weights[1], eps=eps, timings=timings)
-        b.done = torch.cuda.Event()
-        b.done.record(cur)
-        lap("enqueue")
-
-    def finish(b):
-        """Batch b's results: waits for the device, merges / smooths / scores on it, fills the per-sequence lists."""
-        # on a stream of its own, behind the batch's LAST kernel only: on the optimiser's stream the read-back would queue up
-        # behind the next batch's whole device call, which is already enqueued there
-        rs = _report_streams.get(device)
-        if rs is None:
-            rs = _report_streams[device] = torch.cuda.Stream(device=device, priority=STREAM_PRIORITY)
-        rs.wait_event(b.done)
-        for t in b.pending:
-            if t is not None:
-                t.record_stream(rs)
-        with torch.cuda.stream(rs):
-            _finish(b)
-
-    def _finish(b):
-        batch, counts = b.chunks, b.counts
-        mid_local, opt_global, _ = opt[0].collect(b.pending, keep_device=True)
-        b.pending = None
-        lap("wait for the device + stats")
-        mid_np = mid_local.cpu().numpy()
-        lap("report: stage-one poses to the host")
-        e = opt[0].engine
-        if b.report is not None:
-            # ... the error reports of all chunks are ONE library call and are read back with ONE synchronisation
-            nb, r = len(batch), b.report
-            A, X = r["mid_A"], np.ascontiguousarray(np.moveaxis(mid_np.astype(np.float64), -1, 0))          # X [3,W,T,J]
-            mid_g = np.empty(mid_np.shape, dtype=np.float64)
-            for d in range(3):
-                mid_g[..., d] = A[d, 0] * X[0] + A[d, 1] * X[1] + A[d, 2] * X[2] + A[d, 3]
-            mid_m = merge_chunks(mid_g, nb, overlap)
-            fpc = r["est_m"].shape[1]
-            lap("report: stage-one sequences (host float64)")
-            opt_d = e.merge_windows(opt_global, nb, overlap=overlap, smooth=bool(final_smooth))          # [nb*fpc,15,3] f64, device
-            mid_d = slots[b.index % N_BUFFERS][2].upload(mid_m.reshape(nb * fpc, 15, 3), torch.float64)
-            reps = e.calculate_errors_chunks(r["est_d"], mid_d, opt_d, r["gt_d"], nb)
-            lap("report: merge + error kernels enqueued")
-            reps = reps.cpu().numpy()
-            opt_m = opt_d.cpu().numpy().reshape(nb, fpc, 15, 3)
-            lap("report: read-back")
-            for k, c in enumerate(batch):
-                res = OrderedDict(zip(e.ERROR_KEYS, reps[k, :17].tolist()))
-                res["joints_error"] = reps[k, 17:].copy()
-                gi = group_of[c["path"]]
-                results[gi].append(res)
-                raw_rows[gi].append(reps[k])
-                est_all[gi].append(r["est_m"][k]); opt_all[gi].append(opt_m[k]); gt_all[gi].append(r["gt_m"][k])
-                if verbose and res["bone_length_aligned_optimized_mpjpe"] > res["bone_length_aligned_mid_optimized_mpjpe"]:
-                    print(res)
-            lap("report: result dicts")
-            return
-        w0 = 0
-        for c in batch:
-            nw = len(c["starts"])
-            sl = slice(w0, w0 + nw)
-            w0 += nw
-            if nw == 0:
-                continue
-            loc_w, cam_w = cut_windows(c["est_local"], c["starts"], seq_len), cut_windows(c["cams"], c["starts"], seq_len)
-            est_seq = merge_batches(to_global_numpy(relative_global_numpy(loc_w, cam_w), cam_w), overlap)
-            mid_seq = merge_batches(to_global_numpy(relative_global_numpy(mid_np[sl], cam_w), cam_w), overlap)
-            gt_seq = merge_batches(cut_windows(c["gt"], c["starts"], seq_len), overlap)
-            if device_metrics:
-                opt_seq_d = e.merge_windows(opt_global[sl], 1, overlap=overlap, smooth=bool(final_smooth))
-                res = e.calculate_errors(est_seq, mid_seq, opt_seq_d, gt_seq)
-                opt_seq = opt_seq_d.cpu().numpy()
-            else:
-                from .errors import calculate_errors
-                from .sequence import final_smooth as _smooth
-                opt_seq = merge_batches(opt_global[sl].cpu().numpy(), overlap)
-                if final_smooth:
-                    opt_seq = _smooth(opt_seq)
-                res = calculate_errors(est_seq, mid_seq, opt_seq, gt_seq)
-            gi = group_of[c["path"]]
-            results[gi].append(res)
-            est_all[gi].append(np.asarray(est_seq)); opt_all[gi].append(np.asarray(opt_seq)); gt_all[gi].append(np.asarray(gt_seq))
-            if verbose and res["bone_length_aligned_optimized_mpjpe"] > res["bone_length_aligned_mid_optimized_mpjpe"]:
-                print(res)
-        lap("sequences + reports")
-
-    lap("plan")
-    try:
-        prev = None
-        for b in batches:
-            prepare(b)                    # while batch k-1 is on the device and batch k's files are arriving ...
-            fire(b)                       # ... batch k is enqueued behind it as soon as its last file has been sent ...
-            if prev is not None:
-                finish(prev)              # ... and only then batch k-1's report is read back: the device never waits for the host
-                prev.chunks = prev.reading = prev.parsing = prev.images = prev.report = prev.prep = None
-            prev = b
-        finish(prev)
-    finally:
-        _drain(submitted)
-        if any(b.pending is not None for b in batches):
-            torch.cuda.synchronize()      # (an exception left device work behind that reads this call's buffers)
-    lap("readers drained")
-    out = []
-    for gi in range(n_groups):
-        summary = OrderedDict()
-        if len(raw_rows[gi]) == len(results[gi]):          # (every chunk of the sequence came as a row of the device report: one mean)
-            mean = np.mean(np.stack(raw_rows[gi]), axis=0)
-            for i, k in enumerate(results[gi][0]):
-                summary[k] = mean[17:].copy() if k == "joints_error" else float(mean[i])
-        else:
-            for k in results[gi][0]:
-                summary[k] = (np.mean([r[k] for r in results[gi]], axis=0) if k == "joints_error"
-                              else float(np.average([r[k] for r in results[gi]])))
-        if verbose:
-            if n_groups > 1:
-                print("sequence: {}".format(data_dirs[gi]))
-            for line in SUMMARY_LINES:
-                print("-----------------------------------------" if line is None else "{}: {}".format(line[0], summary[line[1]]))
-            print("joints error is: {}".format(summary["joints_error"]))
-            print("-------------------------------------------------------------")
-        # the three pose sequences as arrays [frames,15,3] (iterating them yields the [15,3] frames the reference's lists hold)
-        out.append((summary, results[gi]) + tuple(np.concatenate(x) if x else np.empty((0, 15, 3)) for x in (est_all[gi], opt_all[gi], gt_all[gi])))
-    lap("summaries")
-    return out
+    return _Pipeline(groups, cfg, lap).run(data_dirs)
 
 
-class _Ready:
-    """A result that is there already, where the pipeline expects a future."""
-
-    def __init__(self, value):
-        self._value = value
-
-    def result(self):
-        return self._value
-
-
-def _resident_chunk(c, path):
-    """A `prepare.RecordingChunk` as the pipeline's ParsedChunk: the small arrays on the host (float64, the very values a pickle of
-    them would hold), the heat-maps where they are."""
-    host = lambda t: np.ascontiguousarray(t.detach().cpu().numpy() if hasattr(t, "detach") else t, dtype=np.float64)      # noqa: E731
-    heat = c.heat if hasattr(c.heat, "detach") else torch.as_tensor(np.asarray(c.heat, dtype=np.float32))
-    heat = heat.to(torch.device("cuda", torch.cuda.current_device()), dtype=torch.float32).contiguous()
-    return ParsedChunk(path=path, est_local=host(c.est_local), gt=host(c.gt), cams=host(c.cams), n=int(heat.shape[0]),
-                       heat_shape=tuple(heat.shape[1:]), heat=heat)
+def optimize_directory(data_dir, camera_model_path, *args, **kwargs):
+    """One sequence = the reference's `optimize_whole_sequence.py`.  Returns (summary OrderedDict, per-chunk error
+    dicts, estimated_pose, optimized_pose, gt_pose) -- the three pose sequences are the concatenations
+    `optimize_whole_sequence.py:65-67` builds, as arrays [frames,15,3].  Arguments as `optimize_sequences`."""
+    return optimize_sequences([data_dir], camera_model_path, *args, **kwargs)[0]
 
 
 def optimize_recordings(recordings, camera_model_path, *args, **kwargs):
@@ -730,10 +638,15 @@ def optimize_recordings(recordings, camera_model_path, *args, **kwargs):
     value and printed summary, one entry per `Recording`; no pickle is written or read.  The optimiser is handed the same
     float32 heat-maps, float64 skeletons and cameras that `Recording.write_chunks` + `optimize_sequences` would hand it, so
     the results are bitwise those."""
-    for r in recordings:
+    cfg = _settings(camera_model_path, *args, **kwargs)
+    lap = Laps(cfg.timings, log=True)
+    titles = ["recording_%d" % gi for gi in range(len(recordings))]
+    groups = []
+    for gi, r in enumerate(recordings):
         if not len(r):
             raise FileNotFoundError("a recording without chunks")
-    return optimize_sequences(None, camera_model_path, *args, _recordings=list(recordings), **kwargs)
+        groups.append([_Source(gi, c, os.path.join(titles[gi], c.name)) for c in r.chunks])
+    return _Pipeline(groups, cfg, lap).run(titles)
 
 
 def optimize_recording(recording, camera_model_path, *args, **kwargs):
@@ -742,26 +655,14 @@ def optimize_recording(recording, camera_model_path, *args, **kwargs):
 
 
 def release_pools():
-    """Give back what this module keeps between calls: the per-device frame buffers the readers fill, the pinned noise blocks
-    and the reader threads (with their pinned staging buffers and device images).  Not to be called while another call is in
-    flight."""
+    """Give back what this module keeps between calls: the per-device frame buffers the readers fill and the pinned noise
+    blocks, then (`staging.release`) the streams and the reader threads with their pinned staging buffers and device images.
+    Not to be called while another call is in flight."""
     _heat_pool.clear()
     _noise_pool.clear()
-    _copy_streams.clear()
-    _report_streams.clear()
-    pools = list(_pools.values())
-    _pools.clear()
-    for p, _ in pools:
-        p.shutdown(wait=True)
+    staging.release()
     if torch.cuda.is_available():
         torch.cuda.empty_cache()
-
-
-def optimize_directory(data_dir, camera_model_path, *args, **kwargs):
-    """One sequence = the reference's `optimize_whole_sequence.py`.  Returns (summary OrderedDict, per-chunk error
-    dicts, estimated_pose, optimized_pose, gt_pose) -- the three pose sequences are the concatenations
-    `optimize_whole_sequence.py:65-67` builds, as arrays [frames,15,3].  Arguments as `optimize_sequences`."""
-    return optimize_sequences([data_dir], camera_model_path, *args, **kwargs)[0]
 
 
 def _cli():

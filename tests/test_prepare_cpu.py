@@ -238,6 +238,53 @@ for k in range(first, last):
 
 
 # ------------------------------------------------------------------------------------------------ host-side logic against the golden
+def test_payload_tables_special_cases(P, tmp_path):
+    """`payload_tables` on host data alone: where every frame's payloads lie after the reader threads' pass.  The special cases: a
+    float64 heat-map (kept for the pickle), a compressed and a loadmat'ed heat-map (they travel behind the block), a depth of several
+    rows inside the block and one that came through loadmat (first row only).  Reading the tables back must give loadmat's arrays."""
+    from globalegomocap_amd import _capi, staging
+    rng = np.random.default_rng(5)
+    heats =[rng.random((8, 6, 15), dtype=np.float32), rng.random((8, 6, 15)), rng.random((8, 6, 15), dtype=np.float32),
+             rng.integers(0, 200, (8, 6, 15)).astype(np.uint8)]                       # (uint8: outside the scanner's subset -> loadmat)
+    depths = [rng.random((1, 15)), rng.random((3, 15)), rng.random((1, 15)).astype(np.float32), rng.integers(0, 9, (2, 15)).astype(np.int32)]
+    n, paths = len(heats), []
+    for k, (name, arrays) in enumerate(((P.HEAT_NAME, heats), (P.DEPTH_NAME, depths))):
+        for f, a in enumerate(arrays):
+            paths.append(str(tmp_path / ("%s_%d.mat" % (name, f))))
+            sio.savemat(paths[-1], {name: a}, do_compression=(k == 0 and f == 2))
+    sizes = np.array([os.path.getsize(q) for q in paths], dtype=np.int64)
+    at, room, total = staging.side_by_side(sizes, 16)
+    assert (at % 16 == 0).all() and (room >= sizes + 8).all() and total == at[-1] + room[-1]
+    block = np.zeros(total, dtype=np.uint8)
+    found, rcs = (_capi.GemMatArray * (2 * n))(), np.zeros(2 * n, dtype=np.int32)
+    extra, sent = P._read_range(_capi.load_library(), P._c_paths(paths), 0, 2 * n, at, sizes, n, block, found, rcs, paths)
+    assert sent is None and sorted(e[0] for e in extra) == [2, 3, 7] and rcs.tolist() == [0, 0, -1, -1, 0, 0, 0, -1]
+    where, kinds, shape, heat_files, parts, end = P.payload_tables(n, paths, at, found, rcs, extra, block)
+    assert shape == (8, 6, 15) and end >= total and all(total <= o and o + len(b) <= end for o, b in parts)
+    image = np.zeros(end, dtype=np.uint8)
+    image[:total] = block
+    for o, b in parts:
+        image[o:o + len(b)] = np.frombuffer(b, dtype=np.uint8)
+    for f in range(n):
+        ref_h, ref_d = sio.loadmat(paths[f])[P.HEAT_NAME], sio.loadmat(paths[n + f])[P.DEPTH_NAME][0]
+        dt = np.float64 if kinds[f] & _capi.MAT_HEAT_F64 else np.float32
+        got = np.frombuffer(image, dtype=dt, count=ref_h.size, offset=int(where[f])).reshape(ref_h.shape, order="F")
+        assert np.array_equal(got.astype(np.float32), ref_h.astype(np.float32)), f
+        dt = np.float32 if kinds[f] & _capi.MAT_DEPTH_F32 else np.float64
+        assert np.array_equal(np.frombuffer(image, dtype=dt, count=15, offset=int(where[n + f])).astype(np.float64), ref_d.astype(np.float64)), f
+        if ref_h.dtype == np.float32:
+            assert heat_files[f] is None
+        else:
+            _assert_same(heat_files[f], ref_h)
+    assert kinds.tolist() == [0, _capi.MAT_HEAT_F64, _capi.MAT_DEPTH_F32, 0]
+    sio.savemat(paths[0], {P.HEAT_NAME: heats[0][:, :5]})          # one heat-map of another shape (a smaller file: its room still holds it)
+    sizes[0] = os.path.getsize(paths[0])
+    rcs[:] = 0
+    extra, _ = P._read_range(_capi.load_library(), P._c_paths(paths), 0, 2 * n, at, sizes, n, block, found, rcs, paths)
+    with pytest.raises(ValueError, match="one shape"):
+        P.payload_tables(n, paths, at, found, rcs, extra, block)
+
+
 def test_listing_order_and_slice(P, golden, tmp_path):
     g = golden("prepare")
     names = [str(x) for x in g["names"]]

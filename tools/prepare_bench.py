@@ -131,7 +131,7 @@ def main():
     ge.build()
     if a.kernels_only:
         return kernels_only(a.frames)
-    from globalegomocap_amd import prepare as P, vae as V, whole_sequence as ws
+    from globalegomocap_amd import prepare as P, staging, vae as V, whole_sequence as ws
     from globalegomocap_amd.camera import DEFAULT_CALIBRATION
     sync = torch.cuda.synchronize
     work = a.work or tempfile.mkdtemp(prefix="gem_prepare_bench_")
@@ -168,7 +168,7 @@ def main():
                 paths = ws.list_chunks(chunks)
 
                 def read_stage():
-                    pool = ws._pool("read", 8, ws.cpus_near(dev))
+                    pool = staging.reader_pool("read", 8, staging.cpus_near(dev))
                     for c in [f.result() for f in [pool.submit(ws.load_chunk, q, dev) for q in paths]]:
                         c["heat_ready"].synchronize()
                 read_stage()
