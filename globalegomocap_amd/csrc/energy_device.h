@@ -82,6 +82,57 @@ __device__ __forceinline__ void energy_prefetch(const EnergyArgs& a, int b, int 
     }
 }
 
+// The reference's fp32 fisheye projection of a camera-frame point (FishEyeCalibrated.py:96-129): the image point (u, v) and the
+// intermediates its Jacobian needs.  nn == 0 (a point on the optical axis) leaves u, v not finite: the caller decides what that means.
+struct FisheyeUV { float zz, nn, inv, rho, drho, ux, uy, u, v; };
+__device__ __forceinline__ FisheyeUV fisheye_uv(const float* poly, int n_poly, float cx, float cy, float x, float y, float z) {
+    FisheyeUV q;
+    q.zz = -z;
+    q.nn = sqrtf(x * x + y * y);
+    q.inv = 1.f / q.nn;
+    const float theta = atanf(q.zz / q.nn);
+    float rho = poly[0], drho = 0.f, ti = 1.f;
+    for (int i = 1; i < n_poly; ++i) {
+        drho += (float)i * poly[i] * ti;
+        ti *= theta;
+        rho += ti * poly[i];
+    }
+    q.rho = rho; q.drho = drho;
+    q.ux = x * q.inv; q.uy = y * q.inv;
+    q.u = q.ux * rho + cx; q.v = q.uy * rho + cy;
+    return q;
+}
+
+// Where the image point (u, v) falls in an H x W heat-map (optimizer.py:143-147 + grid_sample(align_corners=True) un-normalisation):
+// the bilinear weights and the 2x2 texel block under it.  A projection that is not finite (or far outside) samples nothing, like
+// zeros padding.  Branch-free: the four texels are fetched together from the clamped (always valid) addresses (ya | yc, xa | xb) and
+// masked afterwards (heat_bilinear).
+struct HeatTap { float fx, fy; bool in, xl, xr, yt, yb; int xa, xb, ya, yc; };
+__device__ __forceinline__ HeatTap heat_tap(float u, float v, int H, int W) {
+    HeatTap k;
+    const float gxn = ((u - 128.f) - 512.f) / 512.f, gyn = (v - 512.f) / 512.f;
+    const float ix = ((gxn + 1.f) / 2.f) * (float)(W - 1);
+    const float iy = ((gyn + 1.f) / 2.f) * (float)(H - 1);
+    const float fx0 = floorf(ix), fy0 = floorf(iy);
+    k.fx = ix - fx0; k.fy = iy - fy0;
+    k.in = fx0 >= -1.f && fx0 < (float)W && fy0 >= -1.f && fy0 < (float)H;
+    const int x0i = k.in ? (int)fx0 : 0, y0i = k.in ? (int)fy0 : 0;
+    k.xl = k.in && x0i >= 0; k.xr = k.in && x0i + 1 < W; k.yt = y0i >= 0; k.yb = y0i + 1 < H;
+    k.xa = x0i < 0 ? 0 : x0i; k.xb = x0i + 1 < W ? x0i + 1 : W - 1;
+    k.ya = y0i < 0 ? 0 : y0i; k.yc = y0i + 1 < H ? y0i + 1 : H - 1;
+    return k;
+}
+
+// the bilinear sample of the block's four raw texels (nw, ne, sw, se): those outside the map are zeroed in place first
+__device__ __forceinline__ float heat_bilinear(const HeatTap& k, float& nw, float& ne, float& sw, float& se) {
+    nw = (k.yt && k.xl) ? nw : 0.f;
+    ne = (k.yt && k.xr) ? ne : 0.f;
+    sw = (k.yb && k.xl) ? sw : 0.f;
+    se = (k.yb && k.xr) ? se : 0.f;
+    const float gxw = 1.f - k.fx, gyw = 1.f - k.fy;
+    return nw * gxw * gyw + ne * k.fx * gyw + sw * gxw * k.fy + se * k.fx * k.fy;
+}
+
 // xsrc: decoded pose rows [T][ldx] (global or LDS); xs/gs/bs/as: LDS scratch of ENERGY_SCRATCH floats each (xs may BE xsrc
 // when that is already the dense [T][J*3] image: XS_IS_SRC); gdst: gradient rows [T][ldg], columns [J*3, gcols) are zero-filled.
 // NT threads work on the window (`lane` = 0..NT-1): 64 = one wavefront; more = the whole workgroup (BLOCK_SYNC), so
@@ -169,36 +220,17 @@ __device__ __forceinline__ void energy_window(const EnergyArgs& a, int b, int la
         // reprojection (only joints of frames whose heat-map exists)
         if (a.wr != 0.f) {
             const float x = xs[p * 3 + 0], y = xs[p * 3 + 1], z = xs[p * 3 + 2];
-            const float zz = -z;
-            const float nn = sqrtf(x * x + y * y);
             // nn == 0 (joint on the optical axis) is rejected by the reference: Exception("norm is zero!"),
             // FishEyeCalibrated.py:124-127.  Here it poisons the window's energy with NaN explicitly (the masked texels
             // alone would leave f finite); lbfgs_advance latches a NaN closure value into the window's status, which the
             // host wrapper turns into the same exception.
+            const FisheyeUV q = fisheye_uv(a.poly, a.n_poly, a.cx, a.cy, x, y, z);
+            const float zz = q.zz, nn = q.nn, inv = q.inv, rho = q.rho, drho = q.drho, ux = q.ux, uy = q.uy;
             if (nn == 0.f) erep = __builtin_nan("");
-            const float inv = 1.f / nn;
-            const float theta = atanf(zz / nn);
-            float rho = a.poly[0], drho = 0.f, ti = 1.f;
-            for (int i = 1; i < a.n_poly; ++i) {
-                drho += (float)i * a.poly[i] * ti;
-                ti *= theta;
-                rho += ti * a.poly[i];
-            }
-            const float ux = x * inv, uy = y * inv;
-            const float u = ux * rho + a.cx, v = uy * rho + a.cy;
-            // optimizer.py:143-147 + grid_sample(align_corners=True) un-normalisation
-            const float gxn = ((u - 128.f) - 512.f) / 512.f, gyn = (v - 512.f) / 512.f;
-            const float ix = ((gxn + 1.f) / 2.f) * (float)(a.W - 1);
-            const float iy = ((gyn + 1.f) / 2.f) * (float)(a.H - 1);
-            const float fx0 = floorf(ix), fy0 = floorf(iy);
-            const float fx = ix - fx0, fy = iy - fy0;
-            // a projection that is not finite (or far outside) samples nothing, like zeros padding.  Branch-free: the
-            // four texels are fetched together from clamped (always valid) addresses and masked afterwards.
-            const bool in = fx0 >= -1.f && fx0 < (float)a.W && fy0 >= -1.f && fy0 < (float)a.H;
-            const int x0i = in ? (int)fx0 : 0, y0i = in ? (int)fy0 : 0;
-            const bool xl = in && x0i >= 0, xr = in && x0i + 1 < a.W, yt = y0i >= 0, yb = y0i + 1 < a.H;
-            const int xa = x0i < 0 ? 0 : x0i, xb = x0i + 1 < a.W ? x0i + 1 : a.W - 1;
-            const int ya = y0i < 0 ? 0 : y0i, yc = y0i + 1 < a.H ? y0i + 1 : a.H - 1;
+            const HeatTap k = heat_tap(q.u, q.v, a.H, a.W);
+            const float fx = k.fx, fy = k.fy;
+            const bool in = k.in;
+            const int xa = k.xa, xb = k.xb, ya = k.ya, yc = k.yc;
             // The 2x2 texel block under a joint rarely changes from one evaluation to the next (the joint moves by a fraction
             // of a texel): the four raw texels of the last evaluation are kept per (window, frame, joint) and re-read as ONE
             // coalesced 20-byte record instead of up to four scattered cache lines of the [frame][y][x][joint] heat-maps
@@ -231,12 +263,8 @@ __device__ __forceinline__ void energy_window(const EnergyArgs& a, int b, int la
                     *reinterpret_cast<f32x4_t*>(a.tex_val + ci * 4) = f32x4_t{nw, ne, sw, se};
                 }
             }
-            nw = (yt && xl) ? nw : 0.f;
-            ne = (yt && xr) ? ne : 0.f;
-            sw = (yb && xl) ? sw : 0.f;
-            se = (yb && xr) ? se : 0.f;
+            const float val = heat_bilinear(k, nw, ne, sw, se);
             const float gxw = 1.f - fx, gyw = 1.f - fy;
-            const float val = nw * gxw * gyw + ne * fx * gyw + sw * gxw * fy + se * fx * fy;
             erep -= (double)val;
             const float dix = (ne - nw) * gyw + (se - sw) * fy;
             const float diy = (sw - nw) * gxw + (se - ne) * fx;

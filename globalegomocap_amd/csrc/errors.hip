@@ -556,3 +556,5 @@ int launch_lift(gem_handle* h, const float* heat, const double* depth, int F, co
 }
 
 }  // namespace gem
+
+#include "sequence_quality.h"          // gem_sequence_quality

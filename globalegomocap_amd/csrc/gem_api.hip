@@ -880,6 +880,16 @@ static int run_graphed(gem_handle* h, const GraphKey& key, hipStream_t s, Body b
     return 0;
 }
 
+int post_scratch(gem_handle* h, size_t elems) {
+    if (elems <= h->post_work_elems) return 0;
+    GEM_HIP(hipDeviceSynchronize());                 // a previous call may still be reading the old buffer
+    if (h->post_work) GEM_HIP(hipFree(h->post_work));
+    h->post_work = nullptr; h->post_work_elems = 0;
+    GEM_HIP(hipMalloc((void**)&h->post_work, elems * sizeof(double)));
+    h->post_work_elems = elems;
+    return 0;
+}
+
 }  // namespace gem
 
 extern "C" {
@@ -1027,16 +1037,6 @@ int gem_set_lanes(gem_handle* h, int min_windows) {
 int gem_set_precision(gem_handle* h, int mode) {
     if (!h || mode < 0 || mode > 2) { set_error("gem_set_precision: mode must be 0 (f32), 1 (bf16x3) or 2 (bf16)"); return 1; }
     h->precision = mode;
-    return 0;
-}
-
-static int post_scratch(gem_handle* h, size_t elems) {
-    if (elems <= h->post_work_elems) return 0;
-    GEM_HIP(hipDeviceSynchronize());                 // a previous call may still be reading the old buffer
-    if (h->post_work) GEM_HIP(hipFree(h->post_work));
-    h->post_work = nullptr; h->post_work_elems = 0;
-    GEM_HIP(hipMalloc((void**)&h->post_work, elems * sizeof(double)));
-    h->post_work_elems = elems;
     return 0;
 }
 

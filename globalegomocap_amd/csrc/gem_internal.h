@@ -421,6 +421,7 @@ int launch_errors(gem_handle* h, const double* est, const double* mid, const dou
 int launch_merge(const double* win, double* tmp, double* out, int n_chunks, int wpc, int T, int JC, int overlap, int smooth,
                  hipStream_t s);
 size_t errors_frame_lds_bytes(int J);
+int post_scratch(gem_handle* h, size_t elems);      // gem_api.hip: h->post_work holds at least `elems` doubles afterwards
 int launch_lift(gem_handle* h, const float* heat, const double* depth, int F, const double* poly, int n_poly, int up, int pad_x,
                 int pad_y, double* out64, float* out32, hipStream_t s);
 

@@ -355,6 +355,32 @@ class WindowEngine:
                                                          bone.ctypes.data_as(C.POINTER(C.c_double)), _ptr(out), _stream()), self.lib)
         return out
 
+    QUALITY_KEYS = ("heatmap_response", "bone_length_rms", "acceleration", "displacement")
+
+    def sequence_quality(self, seq, cams, heat, frame0, mean_bone, n_chunks, ref=None):
+        """The report that needs no ground truth (gem_sequence_quality) for `n_chunks` equally long merged sequences laid end to end:
+        seq (and ref, optional) [n_chunks*fpc,J,3] f64, cams [F,4,4] f64 and heat [F,H,W,J] f32 the frame buffers, frame0 [n_chunks]
+        i64 each chunk's first frame in them, mean_bone [n_chunks,J] f32 -- contiguous device tensors.  -> [n_chunks,4] f64 on the
+        device in the order of QUALITY_KEYS (displacement NaN without `ref`), one library call, no synchronisation."""
+        for x, dt in ((seq, torch.float64), (ref, torch.float64), (cams, torch.float64), (heat, torch.float32), (frame0, torch.int64),
+                      (mean_bone, torch.float32)):
+            if x is not None and not (torch.is_tensor(x) and x.is_cuda and x.dtype == dt and x.is_contiguous()):
+                raise TypeError("sequence_quality wants contiguous device tensors of the documented dtypes")
+        total = seq.numel() // (N_JOINTS * 3)
+        if n_chunks < 1 or total % n_chunks or total == 0 or seq.numel() != total * N_JOINTS * 3:
+            raise ValueError("sequence_quality: %d frames do not split into %d chunks" % (total, n_chunks))
+        if ref is not None and ref.shape != seq.shape:
+            raise ValueError("sequence_quality: ref must have the shape of seq")
+        F = cams.shape[0]
+        if tuple(cams.shape[1:]) != (4, 4) or tuple(heat.shape) != (F, self.heat_size[0], self.heat_size[1], N_JOINTS):
+            raise ValueError("sequence_quality: cams must be [F,4,4] and heat [F,%d,%d,%d] over the same frames" % (self.heat_size + (N_JOINTS,)))
+        if tuple(frame0.shape) != (n_chunks,) or tuple(mean_bone.shape) != (n_chunks, N_JOINTS):
+            raise ValueError("sequence_quality: frame0 must be [%d] and mean_bone [%d,%d]" % (n_chunks, n_chunks, N_JOINTS))
+        out = torch.empty(n_chunks, 4, device=self.device, dtype=torch.float64)
+        _capi.check(self.lib.gem_sequence_quality(self._h, _ptr(seq), _ptr(cams), _ptr(heat), F, _ptr(frame0), _ptr(mean_bone), _ptr(ref),
+                                                  n_chunks, total // n_chunks, _ptr(out), _stream()), self.lib)
+        return out
+
     def calculate_errors(self, est, mid, opt, gt):
         """Same keys and definitions as the reference's calculate_errors (calculate_errors.py:114-179)."""
         from collections import OrderedDict

@@ -135,7 +135,7 @@ class SequenceOptimizer:
         mb_w = mb[upload(chunk_of_window, torch.long)].contiguous()
         f0 = upload(starts, torch.int32)
         lap("run: mean bone lengths")
-        return {"pose": pose_d, "cams": cams_d, "mean_bone": mb_w, "frame0": f0, "B": B, "frames": n_frames}
+        return {"pose": pose_d, "cams": cams_d, "mean_bone": mb_w, "mean_bone_chunks": mb, "frame0": f0, "B": B, "frames": n_frames}
 
     def fire(self, prep, heat, w_local, w_global, eps=None, timings=None):
         """Enqueues both stages for every window of a `prepare`d call; returns without waiting for the device (-> `collect`)."""

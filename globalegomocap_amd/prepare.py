@@ -27,6 +27,15 @@ listing with fewer files than the range asks for.
 
     python -m globalegomocap_amd.prepare --slam traj.txt --heatmaps DIR --depths DIR --gt gt.pkl --start 551 --end 3300 \\
         --fps 25 --out DIR [--optimize]
+
+A recording without ground truth gives the SLAM scale instead -- 1 for a metric SLAM, else what the user
+calibrated: `--scale S` in place of `--gt`, `scale=` in place of `gt_path=`.  The cameras of a chunk are then the reference's
+`SLAMReader.read_trajectory(path, start, end, scale)` (`slam.scaled_trajectory`), the chunks carry no ground truth, their pickles
+no `gt_global_skeleton`, and since one scale holds for the whole recording its chunks share a world: `Recording.origins`,
+`to_recording_frame`.
+
+    python -m globalegomocap_amd.prepare --slam traj.txt --heatmaps DIR --depths DIR --scale 1.0 --start 551 --end 3300 \\
+        --fps 25 --out DIR [--optimize]
 """
 import ctypes as C
 import io
@@ -86,6 +95,43 @@ def check_trajectory(text, start_frame, end_frame, fps):
     if len(ids) != end_frame - start_frame:
         u, c = np.unique(ids, return_counts=True)
         raise ValueError("the trajectory has several lines for frame ids %s" % u[c > 1].tolist())
+
+
+def gt_or_scale(gt_path, scale):
+    """Exactly one of the ground-truth pickle and the SLAM scale must be given: ValueError otherwise.  -> the scale as a float, or
+    None on the ground-truth route."""
+    if (gt_path is None) == (scale is None):
+        raise ValueError("give exactly one of gt_path (the ground truth fixes the SLAM scale) and scale (a recording without ground truth)")
+    if scale is None:
+        return None
+    scale = float(scale)
+    if not (np.isfinite(scale) and scale > 0):
+        raise ValueError("the SLAM scale must be a positive number, got %r" % scale)
+    return scale
+
+
+def scaled_cameras(rows, spans, fps, scale):
+    """The cameras of a recording without ground truth from the trajectory's rows (`slam.trajectory_rows`): per chunk [a, b) of `spans`
+    `slam.scaled_trajectory(*slam.parse_trajectory(rows, a, b, fps), scale)` -- the reference's `read_trajectory`, relative to the
+    chunk's first frame -- and `origins` [n_chunks,4,4]: each chunk's first camera relative to the first frame of the first chunk,
+    at that scale, so that origins[k] @ cams[k][f] is frame f of chunk k in the recording's frame.  -> ([cams per chunk], origins)."""
+    from . import slam
+    cams = [slam.scaled_trajectory(*slam.parse_trajectory(rows, a, b, fps), scale) for a, b in spans]
+    firsts = [slam.parse_trajectory(rows, a, a + 1, fps) for a, _ in spans]
+    origins = slam.scaled_trajectory(np.concatenate([t for t, _ in firsts]), np.concatenate([q for _, q in firsts]), scale) if spans \
+        else np.empty((0, 4, 4))
+    return cams, origins
+
+
+def to_recording_frame(recording, poses_per_chunk):
+    """Per-chunk results (one [n,J,3] array per chunk, each in its chunk's global frame: what the optimiser returns) in the ONE frame
+    a recording without ground truth has: R_k X + t_k with `recording.origins[k]`, float64 on the host.  -> a list of arrays."""
+    if recording.origins is None:
+        raise ValueError("a recording with ground truth has no common frame: every chunk has its own SLAM scale")
+    parts = list(poses_per_chunk)
+    if len(parts) != len(recording):
+        raise ValueError("%d chunks of poses for a recording of %d chunks" % (len(parts), len(recording)))
+    return [np.asarray(p, dtype=np.float64) @ o[:3, :3].T + o[:3, 3] for p, o in zip(parts, np.asarray(recording.origins, dtype=np.float64))]
 
 
 # ------------------------------------------------------------------------------------------------------------------ MAT files
@@ -154,7 +200,7 @@ class RecordingChunk:
     """One chunk [start_frame, end_frame): `heat` [n,H,W,J] f32, `est_local` / `est_global` / `gt` [n,J,3] f64, `cams` [n,4,4] f64
     (device tensors; numpy arrays work for the host-side methods), `gt_list` the ground-truth arrays as the GT pickle holds
     them, `heat_files` per frame None or the heat-map as loadmat returns it (kept for files that are not float32: the device
-    copy is float32), `initial_mpjpe`."""
+    copy is float32), `initial_mpjpe`.  A chunk of a recording without ground truth has `gt`, `gt_list` and `initial_mpjpe` None."""
 
     def __init__(self, start_frame, end_frame, heat, est_local, est_global, cams, gt, gt_list=None, heat_files=None, initial_mpjpe=None):
         self.start_frame, self.end_frame = int(start_frame), int(end_frame)
@@ -170,10 +216,13 @@ class RecordingChunk:
 
 
 class Recording:
-    """The chunks of one recording, device-resident.  `heat`, `est_local`, `est_global`, `cams`, `gt`: one tensor per chunk."""
+    """The chunks of one recording, device-resident.  `heat`, `est_local`, `est_global`, `cams`, `gt`: one tensor per chunk.
+    `origins` [n_chunks,4,4] float64 (numpy) for a recording without ground truth, whose chunks share a world (`scaled_cameras`,
+    `to_recording_frame`); None for a recording with ground truth."""
 
-    def __init__(self, chunks):
+    def __init__(self, chunks, origins=None):
         self.chunks = list(chunks)
+        self.origins = origins
 
     def __len__(self):
         return len(self.chunks)
@@ -187,7 +236,8 @@ class Recording:
     def chunk_dict(self, i):
         """Chunk i as the reference pickles it (:149-155): five keys in its order, every value a list of per-frame arrays;
         estimated_local_skeleton Fortran-ordered float64, estimated_global_skeleton and camera_pose_list C-ordered float64,
-        heatmap_list [H,W,J] Fortran-ordered in the file's class, the ground truth as the GT pickle held it."""
+        heatmap_list [H,W,J] Fortran-ordered in the file's class, the ground truth as the GT pickle held it.  A chunk without
+        ground truth gives the other four keys, unchanged."""
         c = self.chunks[i]
         heat = None
         heats = []
@@ -198,12 +248,14 @@ class Recording:
                     heat = _host(c.heat)
                 kept = np.asfortranarray(heat[f])
             heats.append(kept)
-        gt = c.gt_list if c.gt_list is not None else list(_host(c.gt))
-        return {PICKLE_KEYS[0]: gt,
-                PICKLE_KEYS[1]: [np.ascontiguousarray(a, dtype=np.float64) for a in _host(c.est_global)],
-                PICKLE_KEYS[2]: [np.asfortranarray(a, dtype=np.float64) for a in _host(c.est_local)],
-                PICKLE_KEYS[3]: [np.ascontiguousarray(a, dtype=np.float64) for a in _host(c.cams)],
-                PICKLE_KEYS[4]: heats}
+        d = {}
+        if c.gt_list is not None or c.gt is not None:
+            d[PICKLE_KEYS[0]] = c.gt_list if c.gt_list is not None else list(_host(c.gt))
+        d[PICKLE_KEYS[1]] = [np.ascontiguousarray(a, dtype=np.float64) for a in _host(c.est_global)]
+        d[PICKLE_KEYS[2]] = [np.asfortranarray(a, dtype=np.float64) for a in _host(c.est_local)]
+        d[PICKLE_KEYS[3]] = [np.ascontiguousarray(a, dtype=np.float64) for a in _host(c.cams)]
+        d[PICKLE_KEYS[4]] = heats
+        return d
 
     def write_chunk(self, i, out_dir):
         """`<out_dir>/test_data.pkl` of chunk i (:142-157; default pickle protocol)."""
@@ -445,23 +497,27 @@ def mat_frames(arena, image_len, heat_offsets, depth_offsets, kinds, heat, depth
 
 
 def prepare_global(est_local, cams, gt):
-    """gem_prepare_global on the current stream: -> (est_global [n,J,3] f64, per-frame mean joint distance to gt [n] f64)."""
+    """gem_prepare_global on the current stream: -> (est_global [n,J,3] f64, per-frame mean joint distance to gt [n] f64; None
+    without `gt`)."""
     import torch
     lib = _capi.load_library()
     n, J = est_local.shape[0], est_local.shape[1]
     out = torch.empty_like(est_local)
-    err = torch.empty(n, dtype=torch.float64, device=est_local.device)
-    _capi.check(lib.gem_prepare_global(C.c_void_p(est_local.data_ptr()), C.c_void_p(cams.data_ptr()), C.c_void_p(gt.data_ptr()), n, J,
-                                       C.c_void_p(out.data_ptr()), C.c_void_p(err.data_ptr()),
+    err = torch.empty(n, dtype=torch.float64, device=est_local.device) if gt is not None else None
+    _capi.check(lib.gem_prepare_global(C.c_void_p(est_local.data_ptr()), C.c_void_p(cams.data_ptr()),
+                                       C.c_void_p(gt.data_ptr() if gt is not None else 0), n, J,
+                                       C.c_void_p(out.data_ptr()), C.c_void_p(err.data_ptr() if err is not None else 0),
                                        C.c_void_p(torch.cuda.current_stream().cuda_stream)), lib)
     return out, err
 
 
 def prepare_spans(slam_result_path, heatmap_dir, depth_dir, gt_path, spans, fps, mat_start_frame, camera_model_path=None, device=None,
-                  timings=None):
+                  timings=None, scale=None):
     """Every (start_frame, end_frame) of `spans` as one chunk, each prepared on its own as `main` does, all of them through the
     device together: stage -> gem_mat_frames -> lift -> head joints to the host -> per-chunk scale and cameras -> cameras up ->
-    gem_prepare_global.  -> Recording."""
+    gem_prepare_global.  -> Recording.  `gt_path` None and `scale` given: a recording without ground truth -- the cameras come from
+    `scaled_cameras`, nothing goes to the host in between, `mat_start_frame` is not used."""
+    scale = gt_or_scale(gt_path, scale)
     import torch
     from . import slam
     from .camera import DEFAULT_CALIBRATION
@@ -469,7 +525,7 @@ def prepare_spans(slam_result_path, heatmap_dir, depth_dir, gt_path, spans, fps,
     device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     with open(slam_result_path) as f:
         text = slam.trajectory_rows(f.read())          # (parsed once for all chunks)
-    pose_gt = read_gt(gt_path)
+    pose_gt = read_gt(gt_path) if scale is None else None
     heat_names = sorted(os.listdir(heatmap_dir), key=natural_key)
     depth_names = sorted(os.listdir(depth_dir), key=natural_key)
     heat_paths, depth_paths, gts, bounds = [], [], [], []
@@ -482,9 +538,9 @@ def prepare_spans(slam_result_path, heatmap_dir, depth_dir, gt_path, spans, fps,
         bounds.append((len(heat_paths), len(heat_paths) + b - a))
         heat_paths += [os.path.join(heatmap_dir, x) for x in hp]
         depth_paths += [os.path.join(depth_dir, x) for x in dp]
-        gts.append(gt_clip(pose_gt, a, b, mat_start_frame))
+        gts.append(gt_clip(pose_gt, a, b, mat_start_frame) if scale is None else None)
     if not spans:
-        return Recording([])
+        return Recording([], None if scale is None else np.empty((0, 4, 4)))
     lap("listings, ground truth, trajectory")
     with torch.cuda.device(device):
         heat, depth, heat_files = frames_to_device(heat_paths, depth_paths, device, timings=timings)
@@ -493,6 +549,15 @@ def prepare_spans(slam_result_path, heatmap_dir, depth_dir, gt_path, spans, fps,
         if tuple(heat.shape[1:3]) != tuple(engine.heat_size):
             raise ValueError("heat-maps of %d x %d: the lifting kernel is built for %d x %d" % (tuple(heat.shape[1:3]) + tuple(engine.heat_size)))
         est_local, _ = engine.lift_skeleton(heat, depth)
+        if scale is not None:
+            cams, origins = scaled_cameras(text, spans, fps, scale)
+            lap("lift enqueued + cameras at the given scale (host)")
+            cams_d = torch.from_numpy(np.concatenate(cams)).to(device)
+            est_global, _ = prepare_global(est_local, cams_d, None)
+            lap("cameras up + gem_prepare_global")
+            return Recording([RecordingChunk(a, b, heat[lo:hi], est_local[lo:hi], est_global[lo:hi], cams_d[lo:hi], None,
+                                             heat_files=heat_files[lo:hi] if any(k is not None for k in heat_files[lo:hi]) else None)
+                              for (a, b), (lo, hi) in zip(spans, bounds)], origins)
         heads = est_local[:, 0].cpu().numpy()
         lap("lift + head joints to the host")
         gt_all = np.concatenate([np.asarray(g, dtype=np.float64) for g in gts])
@@ -512,42 +577,51 @@ def prepare_spans(slam_result_path, heatmap_dir, depth_dir, gt_path, spans, fps,
     return Recording(chunks)
 
 
-def main(slam_result_path, heatmap_dir, depth_dir, gt_path, start_frame, end_frame, out_dir, fps, mat_start_frame,
-         camera_model_path=None):
+def main(slam_result_path, heatmap_dir, depth_dir, gt_path, start_frame, end_frame, out_dir, fps, mat_start_frame=None,
+         camera_model_path=None, scale=None):
     """The reference's `main` (:126-165): one chunk [start_frame, end_frame) -> `<out_dir>/test_data.pkl`, and the line
-    `The initial mpjpe is: ...`.  Returns the one-chunk Recording (the reference returns nothing)."""
-    rec = prepare_spans(slam_result_path, heatmap_dir, depth_dir, gt_path, [(start_frame, end_frame)], fps, mat_start_frame,
-                        camera_model_path)
+    `The initial mpjpe is: ...`.  Returns the one-chunk Recording (the reference returns nothing).  Without ground truth (`gt_path`
+    None, `scale` given) the pickle has four keys and there is no such line."""
+    gt_or_scale(gt_path, scale)
+    rec = prepare_spans(slam_result_path, heatmap_dir, depth_dir, gt_path, [(start_frame, end_frame)], fps,
+                        start_frame if mat_start_frame is None else mat_start_frame, camera_model_path, scale=scale)
     rec.write_chunk(0, out_dir)
-    print("The initial mpjpe is: {}".format(rec.chunks[0].initial_mpjpe))
+    if scale is None:
+        print("The initial mpjpe is: {}".format(rec.chunks[0].initial_mpjpe))
     return rec
 
 
 def prepare_sequence(slam_result_path, heatmap_dir, depth_dir, gt_path, total_start_frame, total_end_frame, fps=25, mat_start_frame=None,
-                     test_size=100, out_root=None, camera_model_path=None, verbose=True):
+                     test_size=100, out_root=None, camera_model_path=None, verbose=True, scale=None):
     """The reference's chunk loop (:176-190): chunks of `test_size` frames from `total_start_frame` (see `chunk_spans` for the
     chunk it drops), `mat_start_frame` defaulting to `total_start_frame` as there.  All chunks go through the device together,
-    each prepared on its own.  Returns the Recording; with `out_root`, `data_start_{a}_end_{b}/test_data.pkl` are written too."""
+    each prepared on its own.  Returns the Recording; with `out_root`, `data_start_{a}_end_{b}/test_data.pkl` are written too.
+    Exactly one of `gt_path` and `scale` is given (else ValueError, before anything else happens): with `scale` the recording has no
+    ground truth (`prepare_spans`)."""
+    gt_or_scale(gt_path, scale)
     spans = chunk_spans(total_start_frame, total_end_frame, test_size)
     rec = prepare_spans(slam_result_path, heatmap_dir, depth_dir, gt_path, spans, fps,
-                        total_start_frame if mat_start_frame is None else mat_start_frame, camera_model_path)
+                        total_start_frame if mat_start_frame is None else mat_start_frame, camera_model_path, scale=scale)
     for c in rec.chunks:
         if verbose:
             print("running test sequence from {} to {}".format(c.start_frame, c.end_frame))
-            print("The initial mpjpe is: {}".format(c.initial_mpjpe))
+            if c.initial_mpjpe is not None:
+                print("The initial mpjpe is: {}".format(c.initial_mpjpe))
     if out_root is not None:
         rec.write_chunks(out_root)
     return rec
 
 
-def _cli():
+def _parser():
     import argparse
     from .camera import DEFAULT_CALIBRATION
     p = argparse.ArgumentParser(description="recording (.mat files of the pose network) -> chunks for the optimiser")
     p.add_argument("--slam", required=True, help="SLAM trajectory: lines `time tx ty tz qx qy qz qw`")
     p.add_argument("--heatmaps", required=True, help="directory of per-frame heatmap .mat files")
     p.add_argument("--depths", required=True, help="directory of per-frame depth .mat files")
-    p.add_argument("--gt", required=True, help="ground-truth pickle (it fixes the SLAM scale)")
+    how = p.add_mutually_exclusive_group(required=True)
+    how.add_argument("--gt", default=None, help="ground-truth pickle (it fixes the SLAM scale)")
+    how.add_argument("--scale", type=float, default=None, help="the SLAM scale of a recording without ground truth (a metric SLAM: 1)")
     p.add_argument("--start", required=True, type=int)
     p.add_argument("--end", required=True, type=int)
     p.add_argument("--fps", type=float, default=25)
@@ -556,13 +630,22 @@ def _cli():
     p.add_argument("--out", default=None, help="directory for data_start_{a}_end_{b}/test_data.pkl")
     p.add_argument("--camera", default=DEFAULT_CALIBRATION)
     p.add_argument("--optimize", action="store_true", help="optimise the recording right away (no pickle in between)")
-    a = p.parse_args()
+    return p
+
+
+def _cli(argv=None):
+    p = _parser()
+    a = p.parse_args(argv)
     if a.out is None and not a.optimize:
         p.error("nothing to do: give --out, --optimize or both")
-    rec = prepare_sequence(a.slam, a.heatmaps, a.depths, a.gt, a.start, a.end, a.fps, a.mat_start, a.test_size, a.out, a.camera)
+    rec = prepare_sequence(a.slam, a.heatmaps, a.depths, a.gt, a.start, a.end, a.fps, a.mat_start, a.test_size, a.out, a.camera,
+                           scale=a.scale)
     if a.optimize:
         from .whole_sequence import optimize_recording
-        optimize_recording(rec, a.camera)
+        if a.scale is None:
+            optimize_recording(rec, a.camera)
+        else:
+            optimize_recording(rec, a.camera, ground_truth=False)
 
 
 if __name__ == "__main__":

@@ -12,6 +12,11 @@ threads, copy streams, pinned buffers -- is `staging`'s business; this module ho
 drawn (chunk by chunk, window by window, local then global) follow the reference.
 
     python -m globalegomocap_amd.whole_sequence --data_path data/jian3
+
+Chunks without ground truth (`prepare --scale`) go the same way with `ground_truth=False` /
+`--ground_truth false`: nothing asks for `gt_global_skeleton`, and in place of the 18 errors every chunk gets the seven entries of
+QUALITY_LINES from the device (`WindowEngine.sequence_quality`).  `save_pose=DIR` / `--save_pose DIR` writes the poses of every
+chunk to `DIR/<chunk name>/result_pose.pkl` on either route.
 """
 import ctypes as C
 import os
@@ -47,6 +52,15 @@ SUMMARY_LINES = (          # (label printed by the reference, key) in print orde
 )
 
 
+QUALITY_LINES = (          # the report without ground truth, in the order of its keys: (label, key), None = separator
+    ("Average estimated heatmap response", "estimated_heatmap_response"), ("Average optimized heatmap response", "optimized_heatmap_response"), None,
+    ("Average estimated bone length rms", "estimated_bone_length_rms"), ("Average optimized bone length rms", "optimized_bone_length_rms"), None,
+    ("Average estimated acceleration", "estimated_acceleration"), ("Average optimized acceleration", "optimized_acceleration"), None,
+    ("Average optimized displacement", "optimized_displacement"), None,
+)
+QUALITY_KEYS = tuple(line[1] for line in QUALITY_LINES if line is not None)
+
+
 def list_chunks(data_dir):
     """Chunk directories in the reference's order (`natsorted(os.listdir(data_dir))`, directories only)."""
     names = sorted(os.listdir(data_dir), key=natural_key)
@@ -78,27 +92,30 @@ class ParsedChunk(dict):
     Chunks read from a file also carry "path"."""
 
 
-def parse_chunk(path, native=True):
+def parse_chunk(path, native=True, ground_truth=True):
     """`<chunk>/test_data.pkl` (optimizer.py:315-324) without its heat-maps' data: the small arrays dense, the heat-maps located.
     The library interprets the pickle itself (gem_chunk_open: no Python object per array, no GIL while it runs, nothing the file
     names is imported or called); a file outside its subset -- protocol 2, an entry that is no list of equally shaped float
-    arrays -- is un-pickled the ordinary way instead.  KeyError on a missing key, like the reference."""
+    arrays -- is un-pickled the ordinary way instead.  KeyError on a missing key, like the reference.  ground_truth=False: the
+    ground-truth key is not asked for (a file that has one is fine) and there is no "gt" entry."""
     global _C_KEYS
     file = os.path.join(path, "test_data.pkl")
     if native:
         lib = _capi.load_library()
         if _C_KEYS is None:
-            _C_KEYS = (C.c_char_p * len(KEYS))(*[k.encode() for k in KEYS])
+            _C_KEYS = {True: (C.c_char_p * len(KEYS))(*[k.encode() for k in KEYS]),
+                       False: (C.c_char_p * (len(KEYS) - 1))(*[k.encode() for k in KEYS if k != KEYS[_K_GT]])}
+        wanted = [(key, name) for key, name in zip(KEYS, ("est_local", "gt", "cams", None)) if ground_truth or name != "gt"]
         h = C.c_void_p()
-        if lib.gem_chunk_open(os.fsencode(file), _C_KEYS, len(KEYS), C.byref(h)) == 0:
+        if lib.gem_chunk_open(os.fsencode(file), _C_KEYS[bool(ground_truth)], len(wanted), C.byref(h)) == 0:
             try:
                 info = (C.c_int64 * 8)()
                 c, ok = ParsedChunk(path=path, heat_via=LOCATED), True
-                for k, name in ((_K_EST, "est_local"), (_K_GT, "gt"), (_K_CAM, "cams"), (_K_HEAT, None)):
+                for k, (key, name) in enumerate(wanted):
                     _capi.check(lib.gem_chunk_info(h, k, info), lib)
                     n, ndim = int(info[0]), int(info[1])
                     if n < 0:
-                        raise KeyError(KEYS[k])
+                        raise KeyError(key)
                     if ndim < 0 or (name is None and (n == 0 or ndim != 3)):
                         ok = False                    # ragged, or heat-maps that are not [H,W,J] arrays: the ordinary way
                         break
@@ -117,10 +134,10 @@ def parse_chunk(path, native=True):
                 lib.gem_chunk_close(h)
     with open(file, "rb") as f:
         d = pickle.load(f)
-    c = ParsedChunk(path=path, heat_via=LISTED,
-                    est_local=np.asarray(d["estimated_local_skeleton"], dtype=np.float64),
-                    gt=np.asarray(d["gt_global_skeleton"], dtype=np.float64),
-                    cams=np.asarray(d["camera_pose_list"], dtype=np.float64))
+    c = ParsedChunk(path=path, heat_via=LISTED, est_local=np.asarray(d["estimated_local_skeleton"], dtype=np.float64))
+    if ground_truth:
+        c["gt"] = np.asarray(d["gt_global_skeleton"], dtype=np.float64)
+    c["cams"] = np.asarray(d["camera_pose_list"], dtype=np.float64)
     heat = d["heatmap_list"]
     c["heat_list"], c["n"] = heat, len(heat)
     c["heat_shape"] = tuple(np.shape(heat[0])) if len(heat) else (64, 64, 15)
@@ -240,41 +257,83 @@ class ChunkStream:
             drain(pending)
 
 
-def _resident_chunk(c):
+def _resident_chunk(c, ground_truth=True):
     """A `prepare.RecordingChunk` as the pipeline's ParsedChunk: the small arrays on the host (float64, the very values a pickle of
-    them would hold), the heat-maps where they are."""
+    them would hold), the heat-maps where they are.  ground_truth=False: `c.gt` is not looked at (it may be None)."""
     host = lambda t: np.ascontiguousarray(t.detach().cpu().numpy() if hasattr(t, "detach") else t, dtype=np.float64)      # noqa: E731
     heat = c.heat if hasattr(c.heat, "detach") else torch.as_tensor(np.asarray(c.heat, dtype=np.float32))
     heat = heat.to(torch.device("cuda", torch.cuda.current_device()), dtype=torch.float32).contiguous()
-    return ParsedChunk(heat_via=RESIDENT, est_local=host(c.est_local), gt=host(c.gt), cams=host(c.cams), n=int(heat.shape[0]),
-                       heat_shape=tuple(heat.shape[1:]), heat=heat)
+    p = ParsedChunk(heat_via=RESIDENT, est_local=host(c.est_local), cams=host(c.cams), n=int(heat.shape[0]),
+                    heat_shape=tuple(heat.shape[1:]), heat=heat)
+    if ground_truth:
+        if c.gt is None:
+            raise KeyError(KEYS[_K_GT])          # (what the chunk's pickle would raise)
+        p["gt"] = host(c.gt)
+    return p
 
 
 # ------------------------------------------------------------------------------------------------------------------ the report
-def _report_inputs(chunks, starts, est_cat, cams_cat, seq_len, overlap, upload):
+def _report_inputs(chunks, starts, est_cat, cams_cat, seq_len, overlap, upload, ground_truth=True):
     """The report's half that does not depend on the optimiser's result (equal chunks -- the reference's 100-frame chunks: the
     sequences main() returns besides the optimised one, for ALL windows of the batch at once, the overlap merges vectorised over
-    the chunks), computed and uploaded while the files are still arriving."""
-    gt_cat = np.concatenate([c["gt"] for c in chunks])
+    the chunks), computed and uploaded while the files are still arriving.  ground_truth=False: no "gt_m" / "gt_d"."""
     idx = np.concatenate(starts)[:, None] + np.arange(seq_len)[None]
     cam_w = cams_cat[idx]
     est_m = merge_chunks(to_global_numpy(relative_global_numpy(est_cat[idx], cam_w), cam_w), len(chunks), overlap)
-    gt_m = merge_chunks(gt_cat[idx], len(chunks), overlap)
+    gt_m = merge_chunks(np.concatenate([c["gt"] for c in chunks])[idx], len(chunks), overlap) if ground_truth else None
     # (stage one's global sequence: C0 (C0^-1 C_t) X as ONE transform per frame, composed here in the reference's order --
     # utils/utils.py:99-112 then optimizer.py:302-308 -- so that the result-dependent half is a multiply-add)
     A = np.matmul(cam_w[:, :1], np.matmul(np.linalg.inv(cam_w[:, 0])[:, None], cam_w))
-    return {"mid_A": np.ascontiguousarray(np.moveaxis(A[..., :3, :], (-2, -1), (0, 1))[..., None]), "est_m": est_m, "gt_m": gt_m,      # mid_A [3,4,W,T,1]
-            "est_d": upload(est_m.reshape(-1, 15, 3), torch.float64), "gt_d": upload(gt_m.reshape(-1, 15, 3), torch.float64)}
+    rep = {"mid_A": np.ascontiguousarray(np.moveaxis(A[..., :3, :], (-2, -1), (0, 1))[..., None]), "est_m": est_m,      # mid_A [3,4,W,T,1]
+           "est_d": upload(est_m.reshape(-1, 15, 3), torch.float64)}
+    if ground_truth:
+        rep.update(gt_m=gt_m, gt_d=upload(gt_m.reshape(-1, 15, 3), torch.float64))
+    return rep
 
 
-def _report_batched(engine, report, mid_np, opt_global, n_chunks, overlap, smooth, upload, lap):
-    """The error reports of all chunks of a batch as ONE library call, read back with ONE synchronisation (`report`: what
-    `_report_inputs` prepared).  -> per chunk (error dict, estimated / optimised / ground-truth sequence, the report's raw row)."""
+def _mid_sequences(report, mid_np, n_chunks, overlap):
+    """Stage one's merged global sequences [n_chunks,fpc,J,3] (host float64) from its local poses and `report["mid_A"]`."""
     A, X = report["mid_A"], np.ascontiguousarray(np.moveaxis(mid_np.astype(np.float64), -1, 0))          # X [3,W,T,J]
     mid_g = np.empty(mid_np.shape, dtype=np.float64)
     for d in range(3):
         mid_g[..., d] = A[d, 0] * X[0] + A[d, 1] * X[1] + A[d, 2] * X[2] + A[d, 3]
-    mid_m = merge_chunks(mid_g, n_chunks, overlap)
+    return merge_chunks(mid_g, n_chunks, overlap)
+
+
+def _quality_dict(row):
+    """One chunk's seven report entries from its raw row (the order of QUALITY_KEYS)."""
+    return OrderedDict(zip(QUALITY_KEYS, row.tolist()))
+
+
+def _quality_rows(engine, est_d, opt_d, frames, n_chunks):
+    """`sequence_quality` of the estimated sequences and of the optimised ones (those also against the estimated ones), enqueued on the
+    current stream: a device tensor [n_chunks,7] in the order of QUALITY_KEYS.  `frames`: (cams, heat, frame0, mean_bone) of the
+    batch, see `WindowEngine.sequence_quality`."""
+    q_est = engine.sequence_quality(est_d, *frames, n_chunks)
+    q_opt = engine.sequence_quality(opt_d, *frames, n_chunks, ref=est_d)
+    return torch.stack([q_est[:, 0], q_opt[:, 0], q_est[:, 1], q_opt[:, 1], q_est[:, 2], q_opt[:, 2], q_opt[:, 3]], dim=1)
+
+
+def _quality_batched(engine, report, mid_np, opt_global, n_chunks, overlap, smooth, frames, want_mid, lap):
+    """`_report_batched` for chunks without ground truth: the reports of all chunks of a batch as two `sequence_quality` calls, read
+    back with the optimised sequences.  -> per chunk (report dict, estimated / optimised sequence, None, the raw row, stage one's
+    sequence when `want_mid`)."""
+    fpc = report["est_m"].shape[1]
+    mid_m = _mid_sequences(report, mid_np, n_chunks, overlap) if want_mid else None
+    opt_d = engine.merge_windows(opt_global, n_chunks, overlap=overlap, smooth=smooth)          # [n_chunks*fpc,15,3] f64, device
+    q = _quality_rows(engine, report["est_d"], opt_d, frames, n_chunks)
+    lap("report: merge + quality kernels enqueued")
+    q = q.cpu().numpy()
+    opt_m = opt_d.cpu().numpy().reshape(n_chunks, fpc, 15, 3)
+    lap("report: read-back")
+    return [(_quality_dict(q[k]), report["est_m"][k], opt_m[k], None, q[k], None if mid_m is None else mid_m[k]) for k in range(n_chunks)]
+
+
+def _report_batched(engine, report, mid_np, opt_global, n_chunks, overlap, smooth, upload, lap):
+    """The error reports of all chunks of a batch as ONE library call, read back with ONE synchronisation (`report`: what
+    `_report_inputs` prepared).  -> per chunk (error dict, estimated / optimised / ground-truth sequence, the report's raw row,
+    stage one's sequence)."""
+    mid_m = _mid_sequences(report, mid_np, n_chunks, overlap)
     fpc = report["est_m"].shape[1]
     lap("report: stage-one sequences (host float64)")
     opt_d = engine.merge_windows(opt_global, n_chunks, overlap=overlap, smooth=smooth)          # [n_chunks*fpc,15,3] f64, device
@@ -288,13 +347,15 @@ def _report_batched(engine, report, mid_np, opt_global, n_chunks, overlap, smoot
     for k in range(n_chunks):
         res = OrderedDict(zip(engine.ERROR_KEYS, reps[k, :17].tolist()))
         res["joints_error"] = reps[k, 17:].copy()
-        rows.append((res, report["est_m"][k], opt_m[k], report["gt_m"][k], reps[k]))
+        rows.append((res, report["est_m"][k], opt_m[k], report["gt_m"][k], reps[k], mid_m[k]))
     return rows
 
 
-def _report_per_chunk(engine, chunks, mid_np, opt_global, seq_len, overlap, smooth, device_metrics):
+def _report_per_chunk(engine, chunks, mid_np, opt_global, seq_len, overlap, smooth, device_metrics, frames=None):
     """The reports chunk by chunk (chunks of different lengths, or device_metrics=False).  -> per chunk (error dict, estimated /
-    optimised / ground-truth sequence, None), or None for a chunk too short for a window."""
+    optimised / ground-truth sequence, None, stage one's sequence), or None for a chunk too short for a window.  `frames` (cams,
+    heat, first frame of every chunk, mean_bone of the batch): the chunks have no ground truth -- (report dict, estimated /
+    optimised sequence, None, the raw row, stage one's sequence), each chunk's row read back before the next is enqueued."""
     rows, w0 = [], 0
     for c in chunks:
         nw = len(c["starts"])
@@ -306,6 +367,13 @@ def _report_per_chunk(engine, chunks, mid_np, opt_global, seq_len, overlap, smoo
         loc_w, cam_w = cut_windows(c["est_local"], c["starts"], seq_len), cut_windows(c["cams"], c["starts"], seq_len)
         est_seq = merge_batches(to_global_numpy(relative_global_numpy(loc_w, cam_w), cam_w), overlap)
         mid_seq = merge_batches(to_global_numpy(relative_global_numpy(mid_np[sl], cam_w), cam_w), overlap)
+        if frames is not None:
+            ci = len(rows)
+            est_d = engine._f64(np.asarray(est_seq))
+            opt_seq_d = engine.merge_windows(opt_global[sl], 1, overlap=overlap, smooth=smooth)
+            q = _quality_rows(engine, est_d, opt_seq_d, (frames[0], frames[1], frames[2][ci:ci + 1], frames[3][ci:ci + 1]), 1).cpu().numpy()[0]
+            rows.append((_quality_dict(q), np.asarray(est_seq), opt_seq_d.cpu().numpy(), None, q, np.asarray(mid_seq)))
+            continue
         gt_seq = merge_batches(cut_windows(c["gt"], c["starts"], seq_len), overlap)
         if device_metrics:
             opt_seq_d = engine.merge_windows(opt_global[sl], 1, overlap=overlap, smooth=smooth)
@@ -316,8 +384,20 @@ def _report_per_chunk(engine, chunks, mid_np, opt_global, seq_len, overlap, smoo
             if smooth:
                 opt_seq = final_smooth(opt_seq)
             res = calculate_errors(est_seq, mid_seq, opt_seq, gt_seq)
-        rows.append((res, np.asarray(est_seq), np.asarray(opt_seq), np.asarray(gt_seq), None))
+        rows.append((res, np.asarray(est_seq), np.asarray(opt_seq), np.asarray(gt_seq), None, np.asarray(mid_seq)))
     return rows
+
+
+def _save_pose(out_dir, row, smooth):
+    """`<out_dir>/result_pose.pkl` of one chunk: the reference's keys and containers (optimizer.py:469-483 -- merge_batches' lists of
+    [15,3] frames; the optimised sequence an ndarray after the final smoothing), `gt_pose` only where there is a ground truth."""
+    os.makedirs(out_dir, exist_ok=True)
+    d = {"estimated_pose": list(row[1]), "optimized_pose": np.asarray(row[2]) if smooth else list(np.asarray(row[2])),
+         "mid_optimized_pose": list(row[5])}
+    if row[3] is not None:
+        d["gt_pose"] = list(row[3])
+    with open(os.path.join(out_dir, "result_pose.pkl"), "wb") as f:
+        pickle.dump(d, f)
 
 
 def _sequence_result(rows, title, verbose):
@@ -325,6 +405,16 @@ def _sequence_result(rows, title, verbose):
     gt_pose), the summary printed as the reference prints it (under `title` when there is one)."""
     results, raw = [r[0] for r in rows], [r[4] for r in rows]
     summary = OrderedDict()
+    if rows and rows[0][3] is None:          # chunks without ground truth: the mean of the seven report entries, no ground-truth sequence
+        mean = np.mean(np.stack(raw), axis=0)
+        summary.update(zip(QUALITY_KEYS, mean.tolist()))
+        if verbose:
+            if title is not None:
+                print("sequence: {}".format(title))
+            for line in QUALITY_LINES:
+                print("-----------------------------------------" if line is None else "{}: {}".format(line[0], summary[line[1]]))
+            print("-------------------------------------------------------------")
+        return (summary, results, np.concatenate([r[1] for r in rows]), np.concatenate([r[2] for r in rows]), None)
     if all(x is not None for x in raw):          # (every chunk of the sequence came as a row of the device report: one mean)
         mean = np.mean(np.stack(raw), axis=0)
         for i, k in enumerate(results[0]):
@@ -378,7 +468,7 @@ _Source = namedtuple("_Source", "group what name")          # a chunk of sequenc
 class _Batch:
     """One device call's worth of chunks on its way through the pipeline (see _Pipeline)."""
     __slots__ = ("index", "sources", "parsing", "chunks", "reading", "images", "noise", "pending", "counts", "prep", "heat", "dests",
-                 "listed", "offsets", "report", "weights", "done")
+                 "listed", "offsets", "report", "weights", "done", "heat_d", "frame_lo")
 
     def __init__(self, index, sources):
         self.index, self.sources = index, sources
@@ -388,9 +478,11 @@ class _Batch:
 def _settings(camera_model_path, vae_weight=0.0, gmm_weight=0.0, smoothness_weight=0.001, bone_length_weight=0.01, weight_3d=0.01,
               reproj_weight=0.01, final_smooth=True, merge=True, global_vae_path=GLOBAL_VAE_PATH, local_vae_path=LOCAL_VAE_PATH,
               chunks_per_batch=None, optimizer=None, device_metrics=True, verbose=True, seq_len=SEQ_LEN, overlap=OVERLAP, timings=None,
-              per_sequence=False):
+              per_sequence=False, ground_truth=True, save_pose=None):
     """The arguments of `optimize_sequences` / `optimize_recordings` behind the sequences themselves, as one object.
     (`gmm_weight` and `merge` are accepted and unused, as in the reference: SURVEY D4.)"""
+    if not ground_truth and not device_metrics:
+        raise ValueError("ground_truth=False: the report without ground truth is computed on the device only (device_metrics=True)")
     return SimpleNamespace(**locals())
 
 
@@ -426,7 +518,7 @@ class _Pipeline:
         if b.reading is not None:
             return
         if not isinstance(b.sources[0].what, str):
-            b.reading, b.images, b.chunks = [], [], [_resident_chunk(s.what) for s in b.sources]
+            b.reading, b.images, b.chunks = [], [], [_resident_chunk(s.what, self.cfg.ground_truth) for s in b.sources]
             return
         files = [os.path.join(s.what, "test_data.pkl") for s in b.sources]
         sizes = [os.path.getsize(f) for f in files]          # (FileNotFoundError here, like the reference's open())
@@ -437,7 +529,7 @@ class _Pipeline:
             slot[1] = torch.empty(total, dtype=torch.uint8, device=self.device)
         b.images = [slot[1][o:o + r] for o, r in zip(at.tolist(), room.tolist())]
         b.reading = [self.read_pool.submit(read_file, f, self.device, img, sz) for f, img, sz in zip(files, b.images, sizes)]
-        b.parsing = [self.parse_pool.submit(parse_chunk, s.what) for s in b.sources]
+        b.parsing = [self.parse_pool.submit(parse_chunk, s.what, True, self.cfg.ground_truth) for s in b.sources]
         self.submitted.extend(b.reading + b.parsing)
 
     def prepare(self, b):
@@ -473,6 +565,7 @@ class _Pipeline:
         est_cat = np.concatenate([c["est_local"] for c in b.chunks])
         cams_cat = np.concatenate([c["cams"] for c in b.chunks])
         b.counts = [len(c["starts"]) for c in b.chunks]
+        b.frame_lo = np.array([lo for lo, _ in bounds], dtype=np.int64)
         lap("window tables")
         slot = self.slot(b)
         slot[2].reset(len(est_cat) * (45 * 4 + 16 * 8 + 8 + 3 * 45 * 8) + 16 * n_win + 8192)
@@ -495,7 +588,7 @@ class _Pipeline:
         lap("small uploads")
         b.report = None
         if cfg.device_metrics and b.counts and min(b.counts) == max(b.counts) and b.counts[0] > 0:
-            b.report = _report_inputs(b.chunks, starts, est_cat, cams_cat, cfg.seq_len, cfg.overlap, slot[2].upload)
+            b.report = _report_inputs(b.chunks, starts, est_cat, cams_cat, cfg.seq_len, cfg.overlap, slot[2].upload, cfg.ground_truth)
         lap("report preparation")
 
     def fire(self, b):
@@ -540,6 +633,7 @@ class _Pipeline:
             cur.synchronize()
             lap("h2d tail (timing runs only: synchronised)")
         heat_d = b.heat if b.heat is not None else (parts[0] if len(parts) == 1 else torch.cat(parts))
+        b.heat_d = heat_d
         b.pending = self.opt.fire(b.prep, heat_d, b.weights[0], b.weights[1], eps=eps, timings=timings)
         b.done = torch.cuda.Event()
         b.done.record(cur)
@@ -561,15 +655,31 @@ class _Pipeline:
             lap("wait for the device + stats")
             mid_np = mid_local.cpu().numpy()
             lap("report: stage-one poses to the host")
-            if b.report is not None:
+            frames = None
+            if not cfg.ground_truth:
+                # the report without ground truth reads the batch's frame buffers (slot[0], which batch k+3 fills again): its rows
+                # are read back here, like the error rows
+                heat_d, mb = b.heat_d.contiguous(), b.prep["mean_bone_chunks"].contiguous()
+                frames = (b.prep["cams"], heat_d, torch.from_numpy(b.frame_lo).to(self.device), mb)
+                for t in (heat_d, mb):
+                    t.record_stream(rs)
+            if b.report is not None and frames is not None:
+                rows = _quality_batched(e, b.report, mid_np, opt_global, len(b.chunks), cfg.overlap, bool(cfg.final_smooth), frames,
+                                        cfg.save_pose is not None, lap)
+            elif b.report is not None:
                 rows = _report_batched(e, b.report, mid_np, opt_global, len(b.chunks), cfg.overlap, bool(cfg.final_smooth),
                                        self.slot(b)[2].upload, lap)
             else:
-                rows = _report_per_chunk(e, b.chunks, mid_np, opt_global, cfg.seq_len, cfg.overlap, bool(cfg.final_smooth), cfg.device_metrics)
+                rows = _report_per_chunk(e, b.chunks, mid_np, opt_global, cfg.seq_len, cfg.overlap, bool(cfg.final_smooth), cfg.device_metrics,
+                                         frames)
+            b.heat_d = None
             for src, row in zip(b.sources, rows):
                 if row is not None:
                     self.rows[src.group].append(row)
-                    if cfg.verbose and row[0]["bone_length_aligned_optimized_mpjpe"] > row[0]["bone_length_aligned_mid_optimized_mpjpe"]:
+                    if cfg.save_pose is not None:
+                        _save_pose(os.path.join(cfg.save_pose, os.path.basename(os.path.normpath(src.name))), row, bool(cfg.final_smooth))
+                    if cfg.ground_truth and cfg.verbose and \
+                            row[0]["bone_length_aligned_optimized_mpjpe"] > row[0]["bone_length_aligned_mid_optimized_mpjpe"]:
                         print(row[0])
             lap("report: result dicts" if b.report is not None else "sequences + reports")
 
@@ -615,7 +725,13 @@ def optimize_sequences(data_dirs, camera_model_path, *args, **kwargs):
 
     Further arguments, positional or by keyword, in this order (defaults: `_settings`): vae_weight, gmm_weight, smoothness_weight,
     bone_length_weight, weight_3d, reproj_weight, final_smooth, merge, global_vae_path, local_vae_path, chunks_per_batch, optimizer,
-    device_metrics, verbose, seq_len, overlap, timings, per_sequence."""
+    device_metrics, verbose, seq_len, overlap, timings, per_sequence, ground_truth, save_pose.
+
+    ground_truth=False: the chunks carry no ground truth (`prepare` with a scale).  Their pickles are not asked for
+    `gt_global_skeleton`, every chunk's report is the seven entries of QUALITY_KEYS (`WindowEngine.sequence_quality` on the estimated
+    and on the optimised sequence, device only), the summary their mean over the chunks, and `gt_pose` is None.
+    save_pose=DIR: `DIR/<chunk name>/result_pose.pkl` per chunk with the reference's keys and containers (optimizer.py:469-483):
+    estimated_pose, optimized_pose, mid_optimized_pose and, where there is one, gt_pose."""
     cfg = _settings(camera_model_path, *args, **kwargs)
     lap = Laps(cfg.timings, log=True)          # developer timing (tools/whole_sequence_timing.py): wall time of the main thread's phases
     groups = []
@@ -682,11 +798,14 @@ def _cli():
     p.add_argument("--final_smooth", default=True, type=truthy)
     p.add_argument("--merge", default=True, type=truthy)
     p.add_argument("--chunks_per_batch", type=int, default=None, help="chunks optimised per device call (default: all)")
+    p.add_argument("--ground_truth", default=True, type=truthy, help="false: chunks without gt_global_skeleton, the report without ground truth")
+    p.add_argument("--save_pose", default=None, metavar="DIR", help="write DIR/<chunk name>/result_pose.pkl per chunk")
     a = p.parse_args()
     if a.save:
         raise NotImplementedError("--save writes open3d meshes (optimizer.py:452-504): outside the hot path")
     optimize_directory(a.data_path, a.camera, a.vae, a.gmm, a.smooth, a.bone_length, a.weight_3d, a.reproj_weight,
-                       final_smooth=a.final_smooth, merge=a.merge, chunks_per_batch=a.chunks_per_batch)
+                       final_smooth=a.final_smooth, merge=a.merge, chunks_per_batch=a.chunks_per_batch, ground_truth=a.ground_truth,
+                       save_pose=a.save_pose)
 
 
 if __name__ == "__main__":

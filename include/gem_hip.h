@@ -210,6 +210,28 @@ int gem_calculate_errors(gem_handle* h, const double* d_est, const double* d_mid
 int gem_calculate_errors_chunks(gem_handle* h, const double* d_est, const double* d_mid, const double* d_opt, const double* d_gt,
                                 int n_chunks, int frames_per_chunk, const double* h_bone_mm, double* d_out, void* stream);
 
+/* A per-chunk report that needs no ground truth: what the reference's energy terms (optimizer.py:139-149,
+ * 172-177,202-213) say about merged sequences.  For n_chunks chunks of frames_per_chunk merged frames each (merged frame f of a
+ * chunk is the chunk's frame f):
+ *   d_seq       [n_chunks*frames_per_chunk,J,3] f64   the sequences in their chunks' global frames (e.g. what gem_merge_windows wrote)
+ *   d_cams      [n_frames,4,4] f64, d_heat [n_frames,H,W,J] f32   the frame buffers the optimiser was given
+ *   d_frame0    [n_chunks] i64    each chunk's first frame in those buffers; a frame outside [0, n_frames) is not read and
+ *                                 makes column 0 NaN
+ *   d_mean_bone [n_chunks,J] f32  the chunks' mean bone lengths (gem_mean_bone_length)
+ *   d_ref       like d_seq, or NULL
+ * d_out [n_chunks][4] f64:
+ *   0 heatmap_response  mean over frames and joints of the bilinear heat-map sample (zeros outside, align_corners=True) at the
+ *                       projection of X_cam = C_f^-1 X (rigid inverse in f64, rounded once to f32; projection, heat-map coordinates
+ *                       and sample in the fp32 arithmetic of the optimiser's reprojection term); NaN when a joint lies exactly on
+ *                       the optical axis
+ *   1 bone_length_rms   sqrt(mean over frames and the bones j with parent(j) != j of (|X_j - X_parent(j)| - mean_bone_j)^2), metres
+ *   2 acceleration      mean over frames 1 .. frames_per_chunk-2 and joints of |X[f-1] - 2 X[f] + X[f+1]|
+ *   3 displacement      mean over frames and joints of |X - ref|; NaN when d_ref is NULL
+ * Sums are f64 in a fixed order: two calls give the same bits.  Two launches whatever n_chunks; may grow the scratch buffer. */
+int gem_sequence_quality(gem_handle* h, const double* d_seq, const double* d_cams, const float* d_heat, int64_t n_frames,
+                         const int64_t* d_frame0, const float* d_mean_bone, const double* d_ref, int n_chunks, int frames_per_chunk,
+                         double* d_out, void* stream);
+
 /* ---- input lifting: raw network outputs -> estimated_local_skeleton ----
  * Skeleton.set_skeleton_from_file + set_skeleton + get_max_preds (utils/skeleton.py:74-90,32-45,176-204) followed by
  * FishEyeCameraCalibrated.camera2world (utils/fisheye/FishEyeCalibrated.py:18-33), without the bone-length resize
