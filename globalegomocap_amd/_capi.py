@@ -92,6 +92,10 @@ SIGNATURES = {
     "gem_calculate_errors": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.POINTER(C.c_double), _P, _P]),
     "gem_calculate_errors_chunks": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.POINTER(C.c_double), _P, _P]),
     "gem_sequence_quality": (C.c_int, [_P, _P, _P, _P, C.c_int64, _P, _P, _P, C.c_int, C.c_int, _P, _P]),
+    "gem_skeleton_mesh_layout": (C.c_int, [C.POINTER(C.c_int64)]),
+    "gem_skeleton_mesh_constant": (C.c_int, [_P, _P]),
+    "gem_sequence_align": (C.c_int, [_P, _P, C.c_int64, _P, _P]),
+    "gem_skeleton_mesh": (C.c_int, [_P, C.c_int64, _P, _P, C.c_int64, _P]),
     "gem_lift_skeleton": (C.c_int, [_P, _P, _P, C.c_int, C.POINTER(C.c_double), C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     "gem_set_lanes": (C.c_int, [_P, C.c_int]),
     "gem_pickle_scan": (C.c_int, [_P, C.c_int64, C.POINTER(C.c_char_p), C.c_int, C.POINTER(GemPickleArray), C.c_int64, C.POINTER(C.c_int64)]),

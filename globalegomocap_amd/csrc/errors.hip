@@ -11,91 +11,9 @@
 // frame and alignment: ~1 s of numpy per 2000 frames).  Reductions are fixed-order trees: results are
 // bitwise reproducible.
 #include "gem_internal.h"
+#include "umeyama_device.h"      // svd3, Sim3, umeyama_moments, block_sums, sequence_moments
 
 namespace gem {
-
-// ---------------------------------------------------------------------------------------------------
-// 3x3 SVD by one-sided Jacobi (Hestenes): A = U diag(S) V^T, columns of U/V orthonormal, S >= 0 unsorted.
-// Accurate to eps * cond(A) (no A^T A squaring).  Row-major 3x3 arrays.
-__device__ inline void svd3(const double* A, double* U, double* S, double* V) {
-    double a[9];
-    for (int i = 0; i < 9; ++i) { a[i] = A[i]; V[i] = (i % 4 == 0) ? 1.0 : 0.0; }
-    for (int sweep = 0; sweep < 30; ++sweep) {
-        double off = 0.0;
-        for (int p = 0; p < 2; ++p)
-            for (int q = p + 1; q < 3; ++q) {
-                const double alpha = a[p] * a[p] + a[3 + p] * a[3 + p] + a[6 + p] * a[6 + p];
-                const double beta = a[q] * a[q] + a[3 + q] * a[3 + q] + a[6 + q] * a[6 + q];
-                const double gamma = a[p] * a[q] + a[3 + p] * a[3 + q] + a[6 + p] * a[6 + q];
-                if (gamma == 0.0 || fabs(gamma) <= 1e-300) continue;
-                const double rel = fabs(gamma) / sqrt(alpha * beta);
-                off = rel > off ? rel : off;
-                if (!(rel > 1e-17)) continue;
-                const double zeta = (beta - alpha) / (2.0 * gamma);
-                const double t = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-                const double c = 1.0 / sqrt(1.0 + t * t), s = c * t;
-                for (int r = 0; r < 3; ++r) {
-                    const double ap = a[3 * r + p], aq = a[3 * r + q];
-                    a[3 * r + p] = c * ap - s * aq;
-                    a[3 * r + q] = s * ap + c * aq;
-                    const double vp = V[3 * r + p], vq = V[3 * r + q];
-                    V[3 * r + p] = c * vp - s * vq;
-                    V[3 * r + q] = s * vp + c * vq;
-                }
-            }
-        if (off < 1e-16) break;
-    }
-    double smax = 0.0;
-    for (int k = 0; k < 3; ++k) {
-        S[k] = sqrt(a[k] * a[k] + a[3 + k] * a[3 + k] + a[6 + k] * a[6 + k]);
-        smax = S[k] > smax ? S[k] : smax;
-    }
-    int bad = -1;
-    for (int k = 0; k < 3; ++k) {
-        if (S[k] > 1e-14 * smax && S[k] > 0.0) {
-            for (int r = 0; r < 3; ++r) U[3 * r + k] = a[3 * r + k] / S[k];
-        } else {
-            bad = k;
-        }
-    }
-    if (bad >= 0) {          // rank-deficient (coplanar points): complete U with the cross product of the other two
-        const int i = (bad + 1) % 3, j = (bad + 2) % 3;
-        U[bad] = U[3 + i] * U[6 + j] - U[6 + i] * U[3 + j];
-        U[3 + bad] = U[6 + i] * U[j] - U[i] * U[6 + j];
-        U[6 + bad] = U[i] * U[3 + j] - U[3 + i] * U[j];
-        S[bad] = 0.0;
-    }
-}
-
-__device__ inline double det3(const double* m) {
-    return m[0] * (m[4] * m[8] - m[5] * m[7]) - m[1] * (m[3] * m[8] - m[5] * m[6]) + m[2] * (m[3] * m[7] - m[4] * m[6]);
-}
-
-struct Sim3 {
-    double cR[9];      // c * R, row-major: aligned = p @ cR + t  (row vector convention of the reference)
-    double t[3];
-};
-
-// rigid_transform_3D from moments: cov = (P-mp)^T (Q-mq) / n, var = sum_d var(P_d).
-__device__ inline void umeyama_moments(const double* mp, const double* mq, const double* cov, double var, Sim3* out) {
-    double U[9], S[3], V[9];
-    svd3(cov, U, S, V);
-    // numpy: cov = Vn diag(S) Wn, R = Vn @ Wn with (S[-1], Vn[:, -1]) negated when det(Vn) det(Wn) < 0; here
-    // Vn = U, Wn = V^T, and "last" = the smallest singular value.
-    int kmin = 0;
-    for (int k = 1; k < 3; ++k)
-        if (S[k] < S[kmin]) kmin = k;
-    double d[3] = {1.0, 1.0, 1.0};
-    if (det3(U) * det3(V) < 0.0) d[kmin] = -1.0;
-    const double c = (d[0] * S[0] + d[1] * S[1] + d[2] * S[2]) / var;
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) {
-            double r = 0.0;
-            for (int k = 0; k < 3; ++k) r += U[3 * i + k] * d[k] * V[3 * j + k];
-            out->cR[3 * i + j] = c * r;
-        }
-    for (int j = 0; j < 3; ++j) out->t[j] = mq[j] - (mp[0] * out->cR[j] + mp[1] * out->cR[3 + j] + mp[2] * out->cR[6 + j]);
-}
 
 // ---------------------------------------------------------------------------------------------------
 // Per-frame metrics: six threads per frame (one per source and variant), each with its three J x 3 working sets
@@ -219,28 +137,6 @@ __global__ __launch_bounds__(ERR_FT) void errors_frame_kernel(ErrArgs a) {
 // Sequence-level part: three workgroups, one per source sequence (est, mid, opt).  Each does its similarity
 // alignment over all F*J points (means, centred moments, SVD by thread 0, aligned errors) with ONE barrier per
 // group of sums, and a third of the column sums of the per-frame table.
-constexpr int ERR_ST = 1024;
-constexpr int ERR_NW = ERR_ST / 64;
-
-// K sums at once: wavefront DPP reductions, [K][16] partials in LDS, every thread adds the 16 partials of each value
-// in the same order.  Alternating LDS halves: one barrier per call is enough (see lbfgs.hip's BlockRed).
-template <int K>
-__device__ inline void block_sums(double (&v)[K], double* lds, int& parity) {
-    double* r = lds + parity * (16 * ERR_NW);
-    parity ^= 1;
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        const double w = wave_sum_dpp(v[k]);
-        if ((threadIdx.x & 63) == 0) r[k * ERR_NW + (threadIdx.x >> 6)] = w;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        double t = 0.0;
-        for (int i = 0; i < ERR_NW; ++i) t += r[k * ERR_NW + i];
-        v[k] = t;
-    }
-}
 
 __global__ __launch_bounds__(ERR_ST) void errors_sequence_kernel(ErrArgs a) {
     __shared__ double red[2 * 16 * ERR_NW];
@@ -253,22 +149,8 @@ __global__ __launch_bounds__(ERR_ST) void errors_sequence_kernel(ErrArgs a) {
     {
         const double* P = a.src[s];
         const double* Q = a.gt;
-        double m[6] = {0, 0, 0, 0, 0, 0};
-        for (size_t i = tid; i < N; i += ERR_ST)
-            for (int d = 0; d < 3; ++d) { m[d] += P[i * 3 + d]; m[3 + d] += Q[i * 3 + d]; }
-        block_sums<6>(m, red, parity);
-        for (int k = 0; k < 6; ++k) m[k] /= (double)N;
-        double c[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-        for (size_t i = tid; i < N; i += ERR_ST) {
-            double p[3], q[3];
-            for (int d = 0; d < 3; ++d) { p[d] = P[i * 3 + d] - m[d]; q[d] = Q[i * 3 + d] - m[3 + d]; }
-            for (int x = 0; x < 3; ++x) {
-                c[9] += p[x] * p[x];
-                for (int y = 0; y < 3; ++y) c[3 * x + y] += p[x] * q[y];
-            }
-        }
-        block_sums<10>(c, red, parity);
-        for (int k = 0; k < 10; ++k) c[k] /= (double)N;
+        double m[6], c[10];
+        sequence_moments(P, Q, N, tid, red, parity, m, c);
         if (tid == 0) umeyama_moments(m, m + 3, c, c[9], &sim_s);
         __syncthreads();
         const Sim3 sim = sim_s;
@@ -558,3 +440,4 @@ int launch_lift(gem_handle* h, const float* heat, const double* depth, int F, co
 }  // namespace gem
 
 #include "sequence_quality.h"          // gem_sequence_quality
+#include "skeleton_mesh.h"             // gem_skeleton_mesh, gem_sequence_align

@@ -381,6 +381,39 @@ class WindowEngine:
                                                   n_chunks, total // n_chunks, _ptr(out), _stream()), self.lib)
         return out
 
+    def sequence_align(self, src, dst):
+        """The similarity of `errors.align_sequence` / the reference's global_align_skeleton_seq on the device (gem_sequence_align):
+        src, dst [F,J,3] (or [N,3]) f64 contiguous device tensors of one shape -> [13] f64 on the device: c, R (row-major), t with
+        dst ~ c * (src @ R) + t.  No synchronisation; the same bits on every call."""
+        for x in (src, dst):
+            if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float64 and x.is_contiguous()):
+                raise TypeError("sequence_align wants contiguous float64 device tensors")
+        if src.shape != dst.shape or src.numel() == 0 or src.shape[-1] != 3:
+            raise ValueError("sequence_align: src and dst must be equally shaped, non-empty [...,3], got %s and %s" % (tuple(src.shape), tuple(dst.shape)))
+        out = torch.empty(13, device=self.device, dtype=torch.float64)
+        _capi.check(self.lib.gem_sequence_align(_ptr(src), _ptr(dst), src.numel() // 3, _ptr(out), _stream()), self.lib)
+        return out
+
+    def skeleton_mesh(self, seq, crt=None, out=None):
+        """The vertex blocks of the skeleton meshes of `seq` [F,J,3] f64 (contiguous device tensor), every joint moved by `crt`
+        ([13] from `sequence_align`) first when given (gem_skeleton_mesh) -> uint8 [F, stride] on the device, `out` when given (its
+        row stride is the frame stride: at least the vertex block, a multiple of 16, 16-byte aligned rows).  No synchronisation."""
+        from . import meshes
+        if not (torch.is_tensor(seq) and seq.is_cuda and seq.dtype == torch.float64 and seq.is_contiguous()):
+            raise TypeError("skeleton_mesh wants a contiguous float64 device tensor")
+        if seq.dim() != 3 or tuple(seq.shape[1:]) != (N_JOINTS, 3):
+            raise ValueError("skeleton_mesh: seq must be [F,%d,3], got %s" % (N_JOINTS, tuple(seq.shape)))
+        if crt is not None and not (torch.is_tensor(crt) and crt.is_cuda and crt.dtype == torch.float64 and crt.is_contiguous() and crt.numel() == 13):
+            raise TypeError("skeleton_mesh: crt must be a contiguous float64 device tensor of 13 values")
+        F, block = seq.shape[0], meshes.layout().vertex_bytes
+        if out is None:
+            out = torch.empty(F, block, device=self.device, dtype=torch.uint8)
+        if not (torch.is_tensor(out) and out.is_cuda and out.dtype == torch.uint8 and out.dim() == 2 and out.shape[0] == F
+                and out.shape[1] >= block and out.stride(1) == 1):
+            raise ValueError("skeleton_mesh: out must be a uint8 device tensor [%d, >= %d] with contiguous rows" % (F, block))
+        _capi.check(self.lib.gem_skeleton_mesh(_ptr(seq), F, _ptr(crt), _ptr(out), out.stride(0), _stream()), self.lib)
+        return out
+
     def calculate_errors(self, est, mid, opt, gt):
         """Same keys and definitions as the reference's calculate_errors (calculate_errors.py:114-179)."""
         from collections import OrderedDict

@@ -9,7 +9,8 @@ library behind `WindowEngine`.  Differences that the reference's own interface h
   torch's global CPU generator in the reference's order (window i: local stage, then global stage),
   or passed explicitly with `eps=`;
 * `smoothed_pose`, `gmm_weight`, `windows_size`, `slide_window` are accepted and ignored exactly as
-  the reference ignores them; `visualization`/`save` need open3d and are refused.
+  the reference ignores them; `save` writes the reference's meshes as PLY files from the device (`meshes`),
+  `visualization` needs open3d's viewer and is refused.
 """
 import os
 import pickle
@@ -187,16 +188,19 @@ class SequenceOptimizer:
 def main(data_id, camera_model_path, vae_weight, gmm_weight, smoothness_weight, bone_length_weight, weight_3d,
          reproj_weight, visualization=False, final_smooth=False, merge=True, save=False, save_pose=False,
          global_vae_path=GLOBAL_VAE_PATH, local_vae_path=LOCAL_VAE_PATH, eps=None, optimizer=None, return_stats=False,
-         device_metrics=False):
+         device_metrics=False, mesh_root="out"):
     """pickle in, poses out -- the reference's `main` (optimizer.py:311-507) for one chunk directory.
 
     Returns (errors OrderedDict[18], final_estimated_seq, mid_local_pose_seq, final_optimized_seq, final_gt_seq): lists of [15,3]
     frames like the reference's merge_batches, final_optimized_seq an ndarray [N',15,3] when final_smooth is True (list otherwise).
     device_metrics=True keeps the optimised windows on the device and runs the overlap merge, the Gaussian
     smoothing and `calculate_errors` there (gem_merge_windows / gem_calculate_errors) instead of in numpy.
+    save=True writes the reference's skeleton meshes (optimizer.py:485-504) under `mesh_root` (default: the reference's `out` under
+    the working directory): <mesh_root>/<dataset>/<chunk>/{optimized,input,gt}_global_aligned/out_%04d.ply (`meshes.write_meshes`).
     """
-    if visualization or save:
-        raise NotImplementedError("visualization/save write open3d meshes (optimizer.py:452-504): outside the hot path")
+    if visualization:
+        raise NotImplementedError("visualization opens open3d's viewer (optimizer.py:452-467), which this package does not have: "
+                                  "save=True / --save true writes the same meshes as PLY files for any viewer")
     with open("{}/test_data.pkl".format(data_id), "rb") as f:
         data = pickle.load(f)
     est_local = np.asarray(data["estimated_local_skeleton"])
@@ -238,6 +242,11 @@ def main(data_id, camera_model_path, vae_weight, gmm_weight, smoothness_weight, 
             pickle.dump({"estimated_pose": list(final_estimated_seq),
                          "optimized_pose": final_optimized_seq if final_smooth is True else list(np.asarray(final_optimized_seq)),
                          "mid_optimized_pose": list(mid_estimated_seq), "gt_pose": list(final_gt_seq)}, f)
+    if save:
+        from .meshes import write_result_meshes
+        dataset_dir, seq_name = os.path.split(data_id)
+        write_result_meshes(opt.engine, os.path.join(mesh_root, os.path.split(dataset_dir)[1], seq_name), np.asarray(final_estimated_seq),
+                            final_optimized_d if device_metrics else np.asarray(final_optimized_seq), np.asarray(final_gt_seq))
     if device_metrics:
         errors = opt.engine.calculate_errors(final_estimated_seq, mid_estimated_seq, final_optimized_d, final_gt_seq)
     else:

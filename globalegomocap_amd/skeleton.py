@@ -15,6 +15,11 @@ JOINT_NAMES = (
 # parent of joint j; joint 0 is its own parent (zero-length "bone", optimizer.py:34)
 KINEMATIC_PARENTS = (0, 0, 1, 2, 0, 4, 5, 1, 7, 8, 9, 4, 11, 12, 13)
 
+# The lines the reference draws between joints (`Skeleton.lines`, utils/skeleton.py:20-21): the 14 bones and (7, 11), the hip line.
+# The cylinders of a skeleton mesh, in this order (meshes.py; csrc/skeleton_mesh.h holds the same table).
+MESH_LINES = ((0, 1), (0, 4), (1, 2), (2, 3), (4, 5), (5, 6), (1, 7), (4, 11), (7, 8), (8, 9), (9, 10), (11, 12), (12, 13), (13, 14),
+              (7, 11))
+
 # Mean skeleton in millimetres, 3 x 15 (x, y, z rows). These are the values of the reference's
 # data file utils/fisheye/mean3D.mat (key 'mean3D'), which calculate_errors.py:149-156 uses for the
 # bone-length-normalised MPJPE. Data, not code.

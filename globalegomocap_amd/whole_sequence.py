@@ -16,7 +16,8 @@ drawn (chunk by chunk, window by window, local then global) follow the reference
 Chunks without ground truth (`prepare --scale`) go the same way with `ground_truth=False` /
 `--ground_truth false`: nothing asks for `gt_global_skeleton`, and in place of the 18 errors every chunk gets the seven entries of
 QUALITY_LINES from the device (`WindowEngine.sequence_quality`).  `save_pose=DIR` / `--save_pose DIR` writes the poses of every
-chunk to `DIR/<chunk name>/result_pose.pkl` on either route.
+chunk to `DIR/<chunk name>/result_pose.pkl` on either route; `save=True` / `--save true` writes every chunk's skeleton meshes under
+`mesh_root` (`meshes`).
 """
 import ctypes as C
 import os
@@ -314,6 +315,14 @@ def _quality_rows(engine, est_d, opt_d, frames, n_chunks):
     return torch.stack([q_est[:, 0], q_opt[:, 0], q_est[:, 1], q_opt[:, 1], q_est[:, 2], q_opt[:, 2], q_opt[:, 3]], dim=1)
 
 
+def _chunk_views(n_chunks, est_d, opt_d, gt_d):
+    """Per chunk the (estimated, optimised, ground-truth or None) merged sequences as they lie on the device: what `_save_meshes`
+    reads, so that no sequence goes up again."""
+    fpc = est_d.shape[0] // n_chunks
+    cut = lambda t, k: None if t is None else t[k * fpc:(k + 1) * fpc]          # noqa: E731
+    return [(cut(est_d, k), cut(opt_d, k), cut(gt_d, k)) for k in range(n_chunks)]
+
+
 def _quality_batched(engine, report, mid_np, opt_global, n_chunks, overlap, smooth, frames, want_mid, lap):
     """`_report_batched` for chunks without ground truth: the reports of all chunks of a batch as two `sequence_quality` calls, read
     back with the optimised sequences.  -> per chunk (report dict, estimated / optimised sequence, None, the raw row, stage one's
@@ -326,7 +335,8 @@ def _quality_batched(engine, report, mid_np, opt_global, n_chunks, overlap, smoo
     q = q.cpu().numpy()
     opt_m = opt_d.cpu().numpy().reshape(n_chunks, fpc, 15, 3)
     lap("report: read-back")
-    return [(_quality_dict(q[k]), report["est_m"][k], opt_m[k], None, q[k], None if mid_m is None else mid_m[k]) for k in range(n_chunks)]
+    on_device = _chunk_views(n_chunks, report["est_d"], opt_d, None)
+    return [(_quality_dict(q[k]), report["est_m"][k], opt_m[k], None, q[k], None if mid_m is None else mid_m[k], on_device[k]) for k in range(n_chunks)]
 
 
 def _report_batched(engine, report, mid_np, opt_global, n_chunks, overlap, smooth, upload, lap):
@@ -343,11 +353,11 @@ def _report_batched(engine, report, mid_np, opt_global, n_chunks, overlap, smoot
     reps = reps.cpu().numpy()
     opt_m = opt_d.cpu().numpy().reshape(n_chunks, fpc, 15, 3)
     lap("report: read-back")
-    rows = []
+    rows, on_device = [], _chunk_views(n_chunks, report["est_d"], opt_d, report["gt_d"])
     for k in range(n_chunks):
         res = OrderedDict(zip(engine.ERROR_KEYS, reps[k, :17].tolist()))
         res["joints_error"] = reps[k, 17:].copy()
-        rows.append((res, report["est_m"][k], opt_m[k], report["gt_m"][k], reps[k], mid_m[k]))
+        rows.append((res, report["est_m"][k], opt_m[k], report["gt_m"][k], reps[k], mid_m[k], on_device[k]))
     return rows
 
 
@@ -398,6 +408,16 @@ def _save_pose(out_dir, row, smooth):
         d["gt_pose"] = list(row[3])
     with open(os.path.join(out_dir, "result_pose.pkl"), "wb") as f:
         pickle.dump(d, f)
+
+
+def _save_meshes(engine, mesh_root, name, row):
+    """One chunk's mesh folders, named as at optimizer.py:486-498: <mesh_root>/<dataset>/<chunk>/..., from the sequences on the
+    device where the report left them there (row[6]), else from the row's host arrays.  With a ground truth the estimated and the
+    optimised sequence are aligned to it, as in the reference; without, nothing is aligned and there is no third folder."""
+    from .meshes import write_result_meshes
+    dataset_dir, seq_name = os.path.split(os.path.normpath(name))
+    est, opt, gt = row[6] if len(row) > 6 and row[6] is not None else (row[1], row[2], row[3])
+    write_result_meshes(engine, os.path.join(mesh_root, os.path.split(dataset_dir)[1], seq_name), est, opt, gt)
 
 
 def _sequence_result(rows, title, verbose):
@@ -478,7 +498,7 @@ class _Batch:
 def _settings(camera_model_path, vae_weight=0.0, gmm_weight=0.0, smoothness_weight=0.001, bone_length_weight=0.01, weight_3d=0.01,
               reproj_weight=0.01, final_smooth=True, merge=True, global_vae_path=GLOBAL_VAE_PATH, local_vae_path=LOCAL_VAE_PATH,
               chunks_per_batch=None, optimizer=None, device_metrics=True, verbose=True, seq_len=SEQ_LEN, overlap=OVERLAP, timings=None,
-              per_sequence=False, ground_truth=True, save_pose=None):
+              per_sequence=False, ground_truth=True, save_pose=None, save=False, mesh_root="out"):
     """The arguments of `optimize_sequences` / `optimize_recordings` behind the sequences themselves, as one object.
     (`gmm_weight` and `merge` are accepted and unused, as in the reference: SURVEY D4.)"""
     if not ground_truth and not device_metrics:
@@ -675,6 +695,9 @@ class _Pipeline:
             b.heat_d = None
             for src, row in zip(b.sources, rows):
                 if row is not None:
+                    if cfg.save:
+                        _save_meshes(e, cfg.mesh_root, src.name, row)
+                    row = row[:6]
                     self.rows[src.group].append(row)
                     if cfg.save_pose is not None:
                         _save_pose(os.path.join(cfg.save_pose, os.path.basename(os.path.normpath(src.name))), row, bool(cfg.final_smooth))
@@ -725,13 +748,17 @@ def optimize_sequences(data_dirs, camera_model_path, *args, **kwargs):
 
     Further arguments, positional or by keyword, in this order (defaults: `_settings`): vae_weight, gmm_weight, smoothness_weight,
     bone_length_weight, weight_3d, reproj_weight, final_smooth, merge, global_vae_path, local_vae_path, chunks_per_batch, optimizer,
-    device_metrics, verbose, seq_len, overlap, timings, per_sequence, ground_truth, save_pose.
+    device_metrics, verbose, seq_len, overlap, timings, per_sequence, ground_truth, save_pose, save, mesh_root.
 
     ground_truth=False: the chunks carry no ground truth (`prepare` with a scale).  Their pickles are not asked for
     `gt_global_skeleton`, every chunk's report is the seven entries of QUALITY_KEYS (`WindowEngine.sequence_quality` on the estimated
     and on the optimised sequence, device only), the summary their mean over the chunks, and `gt_pose` is None.
     save_pose=DIR: `DIR/<chunk name>/result_pose.pkl` per chunk with the reference's keys and containers (optimizer.py:469-483):
-    estimated_pose, optimized_pose, mid_optimized_pose and, where there is one, gt_pose."""
+    estimated_pose, optimized_pose, mid_optimized_pose and, where there is one, gt_pose.
+    save=True: every chunk's skeleton meshes (optimizer.py:485-504) as `<mesh_root>/<dataset>/<chunk>/{optimized_global_aligned,
+    input_global_aligned,gt_global_aligned}/out_%04d.ply`, one file per merged frame, the first two sequences aligned to the third
+    over the chunk (`meshes.write_meshes`; mesh_root defaults to the reference's `out` under the working directory).  With
+    ground_truth=False: `optimized_global` and `input_global`, unaligned.  Results and reports do not depend on it."""
     cfg = _settings(camera_model_path, *args, **kwargs)
     lap = Laps(cfg.timings, log=True)          # developer timing (tools/whole_sequence_timing.py): wall time of the main thread's phases
     groups = []
@@ -771,11 +798,13 @@ def optimize_recording(recording, camera_model_path, *args, **kwargs):
 
 
 def release_pools():
-    """Give back what this module keeps between calls: the per-device frame buffers the readers fill and the pinned noise
-    blocks, then (`staging.release`) the streams and the reader threads with their pinned staging buffers and device images.
+    """Give back what this module keeps between calls: the per-device frame buffers the readers fill, the pinned noise
+    blocks and the mesh writer's buffers, then (`staging.release`) the streams and the reader threads with their pinned staging buffers and device images.
     Not to be called while another call is in flight."""
+    from . import meshes
     _heat_pool.clear()
     _noise_pool.clear()
+    meshes.release()
     staging.release()
     if torch.cuda.is_available():
         torch.cuda.empty_cache()
@@ -794,18 +823,17 @@ def _cli():
     p.add_argument("--bone_length", type=float, default=0.01)
     p.add_argument("--weight_3d", type=float, default=0.01)
     p.add_argument("--reproj_weight", type=float, default=0.01)
-    p.add_argument("--save", default=False, type=truthy)
+    p.add_argument("--save", default=False, type=truthy, help="true: write every chunk's skeleton meshes (PLY) under --mesh_root")
+    p.add_argument("--mesh_root", default="out", metavar="DIR", help="where --save true writes <dataset>/<chunk>/<folder>/out_%%04d.ply")
     p.add_argument("--final_smooth", default=True, type=truthy)
     p.add_argument("--merge", default=True, type=truthy)
     p.add_argument("--chunks_per_batch", type=int, default=None, help="chunks optimised per device call (default: all)")
     p.add_argument("--ground_truth", default=True, type=truthy, help="false: chunks without gt_global_skeleton, the report without ground truth")
     p.add_argument("--save_pose", default=None, metavar="DIR", help="write DIR/<chunk name>/result_pose.pkl per chunk")
     a = p.parse_args()
-    if a.save:
-        raise NotImplementedError("--save writes open3d meshes (optimizer.py:452-504): outside the hot path")
     optimize_directory(a.data_path, a.camera, a.vae, a.gmm, a.smooth, a.bone_length, a.weight_3d, a.reproj_weight,
                        final_smooth=a.final_smooth, merge=a.merge, chunks_per_batch=a.chunks_per_batch, ground_truth=a.ground_truth,
-                       save_pose=a.save_pose)
+                       save_pose=a.save_pose, save=a.save, mesh_root=a.mesh_root)
 
 
 if __name__ == "__main__":

@@ -360,6 +360,29 @@ int gem_mat_frames(const void* d_image, int64_t image_len, const int64_t* d_heat
 int gem_prepare_global(const double* d_est_local, const double* d_cams, const double* d_gt, int64_t n_frames, int n_joints,
                        double* d_est_global, double* d_frame_error, void* stream);
 
+/* ---- Skeleton meshes as PLY files: what the reference's --save writes with open3d, frame by frame ----
+ * One file per frame: 15 spheres (radius 0.02 m, 762 vertices, 1520 triangles) on the joints, then 15 cylinders (radius 0.005 m, 102
+ * vertices, 200 triangles) along Skeleton.lines -- binary little-endian PLY as open3d's writer lays it out: a text header, 12 960
+ * vertex records of 27 bytes (3 x float64 position + 3 x uint8 colour, no padding), 25 800 face records of 13 bytes (uint8 3 + 3 x
+ * uint32).  Header and face block are the same for every frame; only the vertex block is made on the device.
+ * gem_skeleton_mesh_layout: out[6] = vertices, triangles, header bytes, vertex-block bytes, face-block bytes, file bytes.
+ * gem_skeleton_mesh_constant: fills h_header (header bytes) and h_faces (face-block bytes).  Both need no GPU. */
+int gem_skeleton_mesh_layout(int64_t* out);
+int gem_skeleton_mesh_constant(void* h_header, void* h_faces);
+
+/* The similarity of calculate_errors.global_align_skeleton_seq: Umeyama (with the reflection fix) of d_src [n_points,3] onto d_dst
+ * [n_points,3], float64 -> d_crt [13] = c, R (row-major), t with dst ~ c * (src . R) + t for row vectors.  One workgroup, sums in a
+ * fixed order, no floating-point atomics: the same bits on every call. */
+int gem_sequence_align(const double* d_src, const double* d_dst, int64_t n_points, double* d_crt, void* stream);
+
+/* The vertex blocks of n_frames meshes: d_seq [n_frames,15,3] float64; d_crt [13] from gem_sequence_align (every joint p becomes
+ * c * (p . R) + t first) or NULL; frame f's block is written at d_vertex_blocks + f * frame_stride_bytes.  The stride must be at
+ * least the block (349 920 bytes) and a multiple of 16, the base 16-byte aligned: anything else is refused before the launch.  A
+ * bone along -z (1 + b_z <= 2^-40) is turned by diag(1,-1,-1), a bone of length zero is not turned (the reference gives NaN for
+ * both); a NaN joint gives NaN vertices in its sphere and its bones only.  Works on the current device. */
+int gem_skeleton_mesh(const double* d_seq, int64_t n_frames, const double* d_crt, void* d_vertex_blocks, int64_t frame_stride_bytes,
+                      void* stream);
+
 /* Timing hook for bench.py's roofline: average device time (ms) of the launches of the dominant
  * kernel family since the last reset, measured with HIP events on the launch stream.
  * family: 0 = decoder_input GEMMs (forward + backward-data), 1 = fused tail / energy kernel, 2 = L-BFGS advance,
