@@ -58,6 +58,11 @@ class GemMatArray(C.Structure):
                 ("reserved", C.c_int32), ("dims", C.c_int64 * 4)]
 
 
+class GemView(C.Structure):
+    _fields_ = [("right", C.c_double * 3), ("down", C.c_double * 3), ("forward", C.c_double * 3), ("centre", C.c_double * 3),
+                ("half_width", C.c_double), ("width", C.c_int32), ("height", C.c_int32)]
+
+
 MAT_UNSUPPORTED, MAT_NOT_FOUND = 2, 3
 MAT_HEAT_F64, MAT_DEPTH_F32 = 1, 2
 MI_SINGLE, MI_DOUBLE = 7, 9
@@ -96,6 +101,9 @@ SIGNATURES = {
     "gem_skeleton_mesh_constant": (C.c_int, [_P, _P]),
     "gem_sequence_align": (C.c_int, [_P, _P, C.c_int64, _P, _P]),
     "gem_skeleton_mesh": (C.c_int, [_P, C.c_int64, _P, _P, C.c_int64, _P]),
+    "gem_render_layout": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int64)]),
+    "gem_skeleton_capsules": (C.c_int, [_P, C.c_int64, _P, C.c_uint32, C.c_uint32, _P, _P, _P]),
+    "gem_render_capsules": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int, C.POINTER(GemView), _P, C.c_int64, _P, _P, _P]),
     "gem_lift_skeleton": (C.c_int, [_P, _P, _P, C.c_int, C.POINTER(C.c_double), C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     "gem_set_lanes": (C.c_int, [_P, C.c_int]),
     "gem_pickle_scan": (C.c_int, [_P, C.c_int64, C.POINTER(C.c_char_p), C.c_int, C.POINTER(GemPickleArray), C.c_int64, C.POINTER(C.c_int64)]),

@@ -414,6 +414,52 @@ class WindowEngine:
         _capi.check(self.lib.gem_skeleton_mesh(_ptr(seq), F, _ptr(crt), _ptr(out), out.stride(0), _stream()), self.lib)
         return out
 
+    def skeleton_capsules(self, seq, crt=None, rgb_joint=0, rgb_line=0):
+        """The 30 capsules of every frame of `seq` [F,J,3] f64 (contiguous device tensor), behind `crt` ([13] from `sequence_align`)
+        when given (gem_skeleton_capsules): geometry [F*30,7] f64 (a, b, r) and colours [F*30] int32 (0x00BBGGRR; `rgb_joint` for the
+        15 joints, `rgb_line` for the 15 lines), on the device.  No synchronisation."""
+        if not (torch.is_tensor(seq) and seq.is_cuda and seq.dtype == torch.float64 and seq.is_contiguous()):
+            raise TypeError("skeleton_capsules wants a contiguous float64 device tensor")
+        if seq.dim() != 3 or tuple(seq.shape[1:]) != (N_JOINTS, 3):
+            raise ValueError("skeleton_capsules: seq must be [F,%d,3], got %s" % (N_JOINTS, tuple(seq.shape)))
+        if crt is not None and not (torch.is_tensor(crt) and crt.is_cuda and crt.dtype == torch.float64 and crt.is_contiguous() and crt.numel() == 13):
+            raise TypeError("skeleton_capsules: crt must be a contiguous float64 device tensor of 13 values")
+        F = seq.shape[0]
+        geom = torch.empty(F * 30, 7, device=self.device, dtype=torch.float64)
+        rgb = torch.empty(F * 30, device=self.device, dtype=torch.int32)
+        _capi.check(self.lib.gem_skeleton_capsules(_ptr(seq), F, _ptr(crt), int(rgb_joint) & 0xFFFFFF, int(rgb_line) & 0xFFFFFF,
+                                                   _ptr(geom), _ptr(rgb), _stream()), self.lib)
+        return geom, rgb
+
+    def render_capsules(self, geom, rgb, first, view, out=None, want_ids=False):
+        """Image i = the capsules first[i] .. first[i+1] of `geom` [n,7] f64 / `rgb` [n] int32 through `view` (a `_capi.GemView`), as
+        PNG scanline streams (gem_render_capsules) -> uint8 [n_images, stride] on the device, `out` when given
+        (rows at least the image's bytes, 16-byte aligned, a row stride that is a multiple of 16).  `first`: ascending integers
+        (a sequence, or an int32 device tensor).  want_ids: -> (out, ids int32 [n_images,H,W], depth f64 [n_images,H,W]).  Waits for
+        the stream once (the library reads `first` back before it launches)."""
+        if not (torch.is_tensor(geom) and geom.is_cuda and geom.dtype == torch.float64 and geom.is_contiguous() and geom.dim() == 2
+                and geom.shape[1] == 7):
+            raise TypeError("render_capsules: geom must be a contiguous float64 device tensor [n,7]")
+        if not (torch.is_tensor(rgb) and rgb.is_cuda and rgb.dtype == torch.int32 and rgb.is_contiguous() and tuple(rgb.shape) == (geom.shape[0],)):
+            raise TypeError("render_capsules: rgb must be a contiguous int32 device tensor [n]")
+        if not torch.is_tensor(first):
+            first = torch.tensor([int(f) for f in first], dtype=torch.int32).to(self.device)
+        if not (first.is_cuda and first.dtype == torch.int32 and first.is_contiguous() and first.dim() == 1 and first.numel() >= 1):
+            raise TypeError("render_capsules: first must be a contiguous int32 device tensor [n_images + 1]")
+        n = first.numel() - 1
+        lay = (C.c_int64 * 3)()
+        _capi.check(self.lib.gem_render_layout(view.width, view.height, lay), self.lib)
+        if out is None:
+            out = torch.empty(n, lay[2], device=self.device, dtype=torch.uint8)
+        if not (torch.is_tensor(out) and out.is_cuda and out.dtype == torch.uint8 and out.dim() == 2 and out.shape[0] == n
+                and out.shape[1] >= lay[1] and out.stride(1) == 1):
+            raise ValueError("render_capsules: out must be a uint8 device tensor [%d, >= %d] with contiguous rows" % (n, lay[1]))
+        ids = torch.empty(n, view.height, view.width, device=self.device, dtype=torch.int32) if want_ids else None
+        depth = torch.empty(n, view.height, view.width, device=self.device, dtype=torch.float64) if want_ids else None
+        _capi.check(self.lib.gem_render_capsules(_ptr(geom), _ptr(rgb), geom.shape[0], _ptr(first), n, C.byref(view), _ptr(out),
+                                                 out.stride(0), _ptr(ids), _ptr(depth), _stream()), self.lib)
+        return (out, ids, depth) if want_ids else out
+
     def calculate_errors(self, est, mid, opt, gt):
         """Same keys and definitions as the reference's calculate_errors (calculate_errors.py:114-179)."""
         from collections import OrderedDict

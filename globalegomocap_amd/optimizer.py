@@ -10,7 +10,7 @@ library behind `WindowEngine`.  Differences that the reference's own interface h
   or passed explicitly with `eps=`;
 * `smoothed_pose`, `gmm_weight`, `windows_size`, `slide_window` are accepted and ignored exactly as
   the reference ignores them; `save` writes the reference's meshes as PLY files from the device (`meshes`),
-  `visualization` needs open3d's viewer and is refused.
+  `visualization` needs open3d's viewer and is refused; `render` writes the sequences as PNG frames instead (`render`).
 """
 import os
 import pickle
@@ -188,7 +188,7 @@ class SequenceOptimizer:
 def main(data_id, camera_model_path, vae_weight, gmm_weight, smoothness_weight, bone_length_weight, weight_3d,
          reproj_weight, visualization=False, final_smooth=False, merge=True, save=False, save_pose=False,
          global_vae_path=GLOBAL_VAE_PATH, local_vae_path=LOCAL_VAE_PATH, eps=None, optimizer=None, return_stats=False,
-         device_metrics=False, mesh_root="out"):
+         device_metrics=False, mesh_root="out", render=None):
     """pickle in, poses out -- the reference's `main` (optimizer.py:311-507) for one chunk directory.
 
     Returns (errors OrderedDict[18], final_estimated_seq, mid_local_pose_seq, final_optimized_seq, final_gt_seq): lists of [15,3]
@@ -197,6 +197,8 @@ def main(data_id, camera_model_path, vae_weight, gmm_weight, smoothness_weight, 
     smoothing and `calculate_errors` there (gem_merge_windows / gem_calculate_errors) instead of in numpy.
     save=True writes the reference's skeleton meshes (optimizer.py:485-504) under `mesh_root` (default: the reference's `out` under
     the working directory): <mesh_root>/<dataset>/<chunk>/{optimized,input,gt}_global_aligned/out_%04d.ply (`meshes.write_meshes`).
+    render=DIR writes the three sequences overlaid, the first two aligned to the ground truth, as PNG frames rendered on the device:
+    DIR/<dataset>/<chunk>/frame_%04d.png and overview_{estimated,optimized,gt}.png (`render.write_result_frames`).
     """
     if visualization:
         raise NotImplementedError("visualization opens open3d's viewer (optimizer.py:452-467), which this package does not have: "
@@ -246,6 +248,11 @@ def main(data_id, camera_model_path, vae_weight, gmm_weight, smoothness_weight, 
         from .meshes import write_result_meshes
         dataset_dir, seq_name = os.path.split(data_id)
         write_result_meshes(opt.engine, os.path.join(mesh_root, os.path.split(dataset_dir)[1], seq_name), np.asarray(final_estimated_seq),
+                            final_optimized_d if device_metrics else np.asarray(final_optimized_seq), np.asarray(final_gt_seq))
+    if render is not None:
+        from .render import write_result_frames
+        dataset_dir, seq_name = os.path.split(data_id)
+        write_result_frames(opt.engine, os.path.join(render, os.path.split(dataset_dir)[1], seq_name), np.asarray(final_estimated_seq),
                             final_optimized_d if device_metrics else np.asarray(final_optimized_seq), np.asarray(final_gt_seq))
     if device_metrics:
         errors = opt.engine.calculate_errors(final_estimated_seq, mid_estimated_seq, final_optimized_d, final_gt_seq)

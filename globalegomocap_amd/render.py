@@ -1,0 +1,380 @@
+"""Skeleton sequences as PNG frames, rendered on the device: something to look at without a mesh viewer.
+
+A skeleton frame is 30 capsules -- the 15 joints as spheres of radius 0.02 m, the 15 lines of `skeleton.MESH_LINES` with radius
+0.005 m, the meshes' figure -- drawn through one orthographic camera (`fit_view`: one view per call, shared by all frames and all
+overlaid sequences, so the figure does not jump).  A kernel rasterises every image into the bytes a PNG holds before deflate
+(`scanlines`: gem_skeleton_capsules + gem_render_capsules), and `write_frames` moves them device -> pinned memory -> files with the
+writer threads `meshes.write_meshes` uses; the host only deflates (zlib, level 1) and frames them.  `write_frames` writes one
+`frame_%04d.png` per frame with all given sequences overlaid and one `overview_<name>.png` per sequence with all its frames in one
+scene -- what the reference's viewer shows first (optimizer.py:452-467).  `read_png` reads such a file back.
+
+    python -m globalegomocap_amd.render out/<dataset>/<chunk>/result_pose.pkl --out DIR [--align true] [--size WxH] [--view side|front|top]
+"""
+import ctypes as C
+import os
+import pickle
+import struct
+import zlib
+from collections import namedtuple
+
+import numpy as np
+
+from . import _capi
+from .skeleton import N_JOINTS
+
+Layout = namedtuple("Layout", "row_bytes image_bytes stride")
+PINNED_BYTES = 64 << 20          # each of the two pinned buffers the scanlines cross PCIe through (69 images of 640 x 480)
+MAX_WRITERS = 16
+VIEWS = ("side", "front", "top")
+PALETTE = {"estimated": (214, 39, 40), "optimized": (31, 119, 180), "gt": (44, 160, 44)}
+DEFAULT_SIZE = (640, 480)        # (width, height) wherever a caller gives none
+MARGIN = 0.1                     # metres around the joints' bounding box
+PNG_SIGNATURE = b"\x89PNG\r\n\x1a\n"
+
+_buffers = {}          # device -> (stride, [pinned, pinned, device buffer])
+
+
+def layout(width, height):
+    """Row bytes, image bytes and image stride of a width x height image (gem_render_layout); needs no GPU."""
+    lib = _capi.load_library()
+    out = (C.c_int64 * 3)()
+    _capi.check(lib.gem_render_layout(int(width), int(height), out), lib)
+    return Layout(*[int(v) for v in out])
+
+
+def _host(seq):
+    a = seq.detach().cpu().numpy() if hasattr(seq, "detach") else np.asarray(seq)
+    a = np.asarray(a, dtype=np.float64)
+    if a.ndim != 3 or a.shape[1:] != (N_JOINTS, 3):
+        raise ValueError("a pose sequence must be [F,%d,3], got %s" % (N_JOINTS, a.shape))
+    return a
+
+
+def fit_view(sequences, width, height, view="side"):
+    """The orthographic camera (`_capi.GemView`) that shows every joint of `sequences` (arrays [F,15,3]) in a width x height image.
+    `up` is the normalised mean over all frames of neck - (right foot + left foot) / 2 -- (0,-1,0) when that is shorter than
+    1e-6 -- and `down` = -up.  "side" looks along the world axis that is most nearly level (smallest |e . up|, the lowest index
+    on ties), made orthogonal to up; "front" along that vector turned by 90 degrees about up; "top" looks along `down`, with the
+    side vector as the image's down.  right = down x forward.  The centre is the middle of the joints' bounding box in view
+    coordinates; half_width the larger of its half extent in x and its half extent in y times W / H, plus 0.1 m.  numpy, no GPU."""
+    if view not in VIEWS:
+        raise ValueError("view must be one of %s, got %r" % (", ".join(VIEWS), view))
+    width, height = int(width), int(height)
+    if width < 1 or height < 1:
+        raise ValueError("an image needs at least one pixel each way, got %d x %d" % (width, height))
+    pts = np.concatenate([_host(s) for s in sequences], axis=0)
+    if pts.shape[0] == 0:
+        raise ValueError("no frame to fit a view to")
+    up = (pts[:, 0] - 0.5 * (pts[:, 10] + pts[:, 14])).mean(axis=0)
+    n = np.linalg.norm(up)
+    up = up / n if n >= 1e-6 else np.array([0.0, -1.0, 0.0])
+    e = np.eye(3)[int(np.argmin(np.abs(up)))]          # (argmin: the lowest index on ties)
+    side = e - (e @ up) * up
+    side /= np.linalg.norm(side)
+    if view == "side":
+        down, forward = -up, side
+    elif view == "front":
+        down, forward = -up, np.cross(up, side)
+    else:
+        down, forward = side, -up
+    right = np.cross(down, forward)
+    axes = np.stack([right, down, forward])
+    q = pts.reshape(-1, 3) @ axes.T
+    lo, hi = q.min(axis=0), q.max(axis=0)
+    mid, half = 0.5 * (lo + hi), 0.5 * (hi - lo)
+    v = _capi.GemView()
+    for name, vec in (("right", right), ("down", down), ("forward", forward), ("centre", mid @ axes)):
+        for i in range(3):
+            getattr(v, name)[i] = float(vec[i])
+    v.half_width = float(max(half[0], half[1] * width / height) + MARGIN)
+    v.width, v.height = width, height
+    return v
+
+
+def _sequence(engine, seq):
+    import torch
+    t = seq if torch.is_tensor(seq) else torch.from_numpy(np.array(seq, dtype=np.float64))
+    t = t.to(device=engine.device, dtype=torch.float64).contiguous()
+    if t.dim() != 3 or tuple(t.shape[1:]) != (N_JOINTS, 3):
+        raise ValueError("a pose sequence must be [F,%d,3], got %s" % (N_JOINTS, tuple(t.shape)))
+    return t
+
+
+def _prepare(engine, sequences, align_to):
+    """The sequences on the device and, per sequence, the similarity (`WindowEngine.sequence_align`, [13] on the device) onto its
+    entry of `align_to`: None, one sequence for all, or a list with a sequence or None for each."""
+    seqs = [_sequence(engine, s) for s in sequences]
+    if not seqs:
+        raise ValueError("no sequence to draw")
+    if any(s.shape != seqs[0].shape for s in seqs):
+        raise ValueError("overlaid sequences must have the same number of frames, got %s" % [tuple(s.shape) for s in seqs])
+    targets = list(align_to) if isinstance(align_to, (list, tuple)) else [align_to] * len(seqs)
+    if len(targets) != len(seqs):
+        raise ValueError("align_to lists %d targets for %d sequences" % (len(targets), len(seqs)))
+    crts = []
+    for s, to in zip(seqs, targets):
+        if to is None:
+            crts.append(None)
+            continue
+        to_d = _sequence(engine, to)
+        if to_d.shape != s.shape:
+            raise ValueError("align_to must have the sequence's shape %s, got %s" % (tuple(s.shape), tuple(to_d.shape)))
+        crts.append(engine.sequence_align(s, to_d))
+    return seqs, crts
+
+
+def frames_view(engine, sequences, align_to=None, size=None, view="side"):
+    """The view `write_frames` draws these sequences through: `fit_view` of the sequences as drawn, that is behind their alignment."""
+    seqs, crts = _prepare(engine, sequences, align_to)
+    return _view_of(seqs, crts, size, view)
+
+
+def _view_of(seqs, crts, size, view):
+    size = DEFAULT_SIZE if size is None else size
+    drawn = []
+    for s, crt in zip(seqs, crts):
+        p = s.cpu().numpy()
+        if crt is not None:          # c * (p . R) + t, as the kernel moves the joints
+            k = crt.cpu().numpy()
+            p = k[0] * (p @ k[1:10].reshape(3, 3)) + k[10:13]
+        drawn.append(p)
+    return fit_view(drawn, size[0], size[1], view)
+
+
+def _rgb_word(c):
+    r, g, b = (int(x) for x in c)
+    if not all(0 <= x <= 255 for x in (r, g, b)):
+        raise ValueError("a colour is three integers 0 .. 255, got %r" % (c,))
+    return r | (g << 8) | (b << 16)
+
+
+def _scene(engine, seqs, crts, colours, overview):
+    """(geometry, colours, first) of the images: per frame the capsules of all sequences, or per sequence those of all its frames."""
+    import torch
+    if len(colours) != len(seqs):
+        raise ValueError("%d colours for %d sequences" % (len(colours), len(seqs)))
+    S, F = len(seqs), seqs[0].shape[0]
+    parts = [engine.skeleton_capsules(s, crt, _rgb_word(c), _rgb_word(c)) for s, crt, c in zip(seqs, crts, colours)]
+    geom = torch.stack([p[0].view(F, 30, 7) for p in parts])          # [S,F,30,7]
+    rgb = torch.stack([p[1].view(F, 30) for p in parts])
+    if overview:
+        n, per = S, F * 30
+    else:
+        geom, rgb = geom.permute(1, 0, 2, 3), rgb.permute(1, 0, 2)
+        n, per = F, S * 30
+    first = torch.arange(n + 1, dtype=torch.int32) * per
+    return geom.reshape(-1, 7).contiguous(), rgb.reshape(-1).contiguous(), first.to(engine.device)
+
+
+def scanlines(engine, sequences, view, colours, overview=False, align_to=None):
+    """The images of `sequences` (each [F,15,3], array or tensor; one RGB colour each) through `view`, as the bytes their PNG files
+    hold before deflate: a uint8 device tensor [n, stride], an image's bytes first in its row (`layout`).  One image per frame with
+    all sequences overlaid, or (overview=True) one per sequence with all its frames.  align_to: see `write_frames`."""
+    seqs, crts = _prepare(engine, sequences, align_to)
+    geom, rgb, first = _scene(engine, seqs, crts, colours, overview)
+    return engine.render_capsules(geom, rgb, first, view)
+
+
+def _chunk(kind, data):
+    return struct.pack(">I", len(data)) + kind + data + struct.pack(">I", zlib.crc32(kind + data) & 0xFFFFFFFF)
+
+
+def write_png(path, scanline_bytes, width, height):
+    """An 8-bit RGB, non-interlaced PNG from its scanline stream (height rows of filter byte 0 + 3 * width bytes): IHDR, one IDAT
+    (zlib level 1), IEND.  Standard library only; zlib releases the GIL while it deflates."""
+    data = memoryview(scanline_bytes).cast("B")
+    if len(data) != height * (1 + 3 * width):
+        raise ValueError("%d x %d pixels are %d scanline bytes, got %d" % (width, height, height * (1 + 3 * width), len(data)))
+    body = PNG_SIGNATURE + _chunk(b"IHDR", struct.pack(">IIBBBBB", width, height, 8, 2, 0, 0, 0)) + \
+        _chunk(b"IDAT", zlib.compress(data, 1)) + _chunk(b"IEND", b"")
+    with open(path, "wb") as f:
+        f.write(body)
+
+
+def read_png(path):
+    """A PNG of this module's making -> uint8 [H,W,3].  Strict: the signature, then exactly IHDR, one IDAT and IEND with good CRCs
+    and nothing behind them; 8-bit RGB, not interlaced; the inflated stream as long as the header says, every filter byte 0.
+    ValueError otherwise."""
+    with open(path, "rb") as f:
+        data = f.read()
+    if data[:8] != PNG_SIGNATURE:
+        raise ValueError("%s: no PNG signature" % path)
+    at, chunks = 8, []
+    while at < len(data):
+        if at + 12 > len(data):
+            raise ValueError("%s: truncated inside a chunk header" % path)
+        n, kind = struct.unpack(">I", data[at:at + 4])[0], data[at + 4:at + 8]
+        if at + 12 + n > len(data):
+            raise ValueError("%s: truncated inside its %s chunk" % (path, kind.decode("latin-1")))
+        body = data[at + 8:at + 8 + n]
+        if struct.unpack(">I", data[at + 8 + n:at + 12 + n])[0] != zlib.crc32(kind + body) & 0xFFFFFFFF:
+            raise ValueError("%s: bad CRC in its %s chunk" % (path, kind.decode("latin-1")))
+        chunks.append((kind, body))
+        at += 12 + n
+    if [k for k, _ in chunks] != [b"IHDR", b"IDAT", b"IEND"] or len(chunks[0][1]) != 13 or chunks[2][1]:
+        raise ValueError("%s: not exactly IHDR, one IDAT, IEND (got %s)" % (path, b" ".join(k for k, _ in chunks).decode("latin-1")))
+    W, H, depth, colour, compression, filt, interlace = struct.unpack(">IIBBBBB", chunks[0][1])
+    if (depth, colour, compression, filt, interlace) != (8, 2, 0, 0, 0) or W < 1 or H < 1:
+        raise ValueError("%s: not an 8-bit RGB, non-interlaced image (bit depth %d, colour type %d, interlace %d)" % (path, depth, colour, interlace))
+    try:
+        raw = zlib.decompress(chunks[1][1])
+    except zlib.error as e:
+        raise ValueError("%s: its IDAT does not inflate: %s" % (path, e))
+    if len(raw) != H * (1 + 3 * W):
+        raise ValueError("%s: %d scanline bytes for %d x %d pixels" % (path, len(raw), W, H))
+    rows = np.frombuffer(raw, dtype=np.uint8).reshape(H, 1 + 3 * W)
+    if rows[:, 0].any():
+        raise ValueError("%s: a scanline with a filter other than 0" % path)
+    return rows[:, 1:].reshape(H, W, 3).copy()
+
+
+def _write_images(engine, geom, rgb, first, view, paths):
+    """Image i of the scene -> paths[i].  The scanlines are made on the device, at most PINNED_BYTES of them at a time, and cross
+    PCIe through two alternating pinned buffers: while one is being deflated and written by the writer threads, the next batch
+    arrives in the other (`meshes.write_meshes`' route).  Every file is complete and closed when this returns."""
+    import torch
+    from .staging import cpus_near, reader_pool
+    n_images = len(paths)
+    if n_images == 0:
+        return
+    W, H = view.width, view.height
+    lay = layout(W, H)
+    per = max(1, PINNED_BYTES // lay.stride)
+    dev = engine.device
+    kept = _buffers.get(dev)
+    if kept is None or kept[0] != (lay.stride, per):
+        kept = _buffers[dev] = ((lay.stride, per), [torch.empty(per, lay.stride, dtype=torch.uint8).pin_memory() for _ in range(2)] +
+                                [torch.empty(per, lay.stride, dtype=torch.uint8, device=dev)])
+    bufs = kept[1]
+    pool = reader_pool("mesh", min(MAX_WRITERS, os.cpu_count() or 1), cpus_near(dev))          # (the meshes' writer threads)
+    writing, arrived = [[], []], None          # per pinned buffer: its files' futures; the batch whose copy has been enqueued
+
+    def hand_over(batch):
+        lo, n, slot, ev = batch
+        ev.synchronize()
+        rows = bufs[slot].numpy()
+        writing[slot] = [pool.submit(write_png, paths[lo + i], rows[i, :lay.image_bytes], W, H) for i in range(n)]
+
+    def settle(futures):
+        for f in futures:
+            f.result()          # (an OSError of a writer surfaces here)
+        del futures[:]
+
+    try:
+        for k, lo in enumerate(range(0, n_images, per)):
+            n, slot = min(per, n_images - lo), k % 2
+            settle(writing[slot])
+            engine.render_capsules(geom, rgb, first[lo:lo + n + 1], view, out=bufs[2][:n])
+            bufs[slot][:n].copy_(bufs[2][:n], non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(torch.cuda.current_stream())
+            if arrived is not None:
+                hand_over(arrived)
+            arrived = (lo, n, slot, ev)
+        hand_over(arrived)
+        arrived = None
+        settle(writing[0])
+        settle(writing[1])
+    finally:
+        if arrived is not None:
+            arrived[3].synchronize()
+        for futures in writing:          # (on the way out of an exception: nothing may still read the pinned buffers)
+            for f in futures:
+                f.cancel()
+            for f in futures:
+                if not f.cancelled():
+                    try:
+                        f.result()
+                    except Exception:
+                        pass
+
+
+def write_frames(engine, sequences, out_dir, colours=None, align_to=None, size=None, view="side", overview=True, names=None):
+    """`out_dir/frame_%04d.png` for every frame, all `sequences` (each [F,15,3]) overlaid in their `colours` (default: the palette's
+    order estimated, optimised, ground truth), and -- overview=True -- `out_dir/overview_<name>.png` per sequence with all its
+    frames in one scene (`names`, default: the palette's names).  align_to: None, one sequence [F,15,3] for all, or a list with one
+    target or None per sequence; a sequence with a target is first moved by the one similarity transform that takes it onto the
+    target (`errors.align_sequence`).  size = (width, height), default DEFAULT_SIZE; `view` as in `fit_view`, fitted once to everything that is drawn.
+    Runs on the current stream; every file is complete and closed on return; returns the number of files."""
+    seqs, crts = _prepare(engine, sequences, align_to)
+    S, F = len(seqs), seqs[0].shape[0]
+    default = list(PALETTE)
+    if colours is None:
+        if S > len(default):
+            raise ValueError("more than %d sequences need their colours given" % len(default))
+        colours = [PALETTE[k] for k in default[:S]]
+    if names is None:
+        names = default[:S] if S <= len(default) else ["%d" % i for i in range(S)]
+    if len(names) != S:
+        raise ValueError("%d names for %d sequences" % (len(names), S))
+    os.makedirs(out_dir, exist_ok=True)
+    if F == 0:
+        return 0
+    v = _view_of(seqs, crts, size, view)
+    geom, rgb, first = _scene(engine, seqs, crts, colours, False)
+    _write_images(engine, geom, rgb, first, v, [os.path.join(out_dir, "frame_%04d.png" % f) for f in range(F)])
+    if not overview:
+        return F
+    geom, rgb, first = _scene(engine, seqs, crts, colours, True)
+    _write_images(engine, geom, rgb, first, v, [os.path.join(out_dir, "overview_%s.png" % n) for n in names])
+    return F + S
+
+
+def write_result_frames(engine, out_dir, estimated, optimized, gt=None, align=None, size=None, view="side"):
+    """One result's frames under `out_dir`: the estimated, the optimised and, where there is one, the ground-truth sequence overlaid
+    (red, blue, green), the first two aligned to the third (`align`, default: whenever there is one) as `meshes.write_result_meshes`
+    aligns the meshes."""
+    align = gt is not None if align is None else align
+    if align and gt is None:
+        raise ValueError("aligned frames need a ground-truth sequence to align to")
+    sequences = [estimated, optimized] + ([gt] if gt is not None else [])
+    to = [gt if align else None] * 2 + ([None] if gt is not None else [])
+    return write_frames(engine, sequences, out_dir, align_to=to, size=size, view=view)
+
+
+def release():
+    """Give back the pinned and device buffers `write_frames` keeps between calls."""
+    _buffers.clear()
+
+
+def _size(text):
+    try:
+        w, h = (int(x) for x in str(text).lower().split("x"))
+    except ValueError:
+        w = h = 0
+    if w < 1 or h < 1:
+        import argparse
+        raise argparse.ArgumentTypeError("a size is WIDTHxHEIGHT, for instance 640x480; got %r" % text)
+    return w, h
+
+
+def main(argv=None):
+    import argparse
+    from .camera import DEFAULT_CALIBRATION
+    truthy = lambda x: str(x).lower() == "true"          # noqa: E731  (the reference's own flag parser)
+    p = argparse.ArgumentParser(description="Skeleton frames (PNG, one per frame, and one overview per sequence) from a saved result_pose.pkl")
+    p.add_argument("pose_pickle", help="result_pose.pkl as --save_pose writes it: estimated_pose, optimized_pose and, optionally, gt_pose")
+    p.add_argument("--out", required=True, metavar="DIR")
+    p.add_argument("--align", default=False, type=truthy, help="true: align both sequences to gt_pose first")
+    p.add_argument("--size", default=DEFAULT_SIZE, type=_size, metavar="WxH")
+    p.add_argument("--view", default="side", choices=VIEWS)
+    a = p.parse_args(argv)
+    with open(a.pose_pickle, "rb") as f:
+        d = pickle.load(f)
+    for key in ("estimated_pose", "optimized_pose"):
+        if key not in d:
+            p.error("%s has no %s" % (a.pose_pickle, key))
+    gt = d.get("gt_pose")
+    if a.align and gt is None:
+        p.error("--align true needs a gt_pose in %s" % a.pose_pickle)
+    from .prepare import _lift_engine
+    import torch
+    if not torch.cuda.is_available():
+        raise _capi.GemError("no HIP device visible: the frames are rendered on the device")
+    n = write_result_frames(_lift_engine(DEFAULT_CALIBRATION, torch.cuda.current_device()), a.out, np.asarray(d["estimated_pose"]),
+                            np.asarray(d["optimized_pose"]), None if gt is None else np.asarray(gt), align=a.align, size=a.size, view=a.view)
+    print("{} images written under {}".format(n, a.out))
+
+
+if __name__ == "__main__":
+    main()

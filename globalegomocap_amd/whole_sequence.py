@@ -17,7 +17,8 @@ Chunks without ground truth (`prepare --scale`) go the sam
 `--ground_truth false`: nothing asks for `gt_global_skeleton`, and in place of the 18 errors every chunk gets the seven entries of
 QUALITY_LINES from the device (`WindowEngine.sequence_quality`).  `save_pose=DIR` / `--save_pose DIR` writes the poses of every
 chunk to `DIR/<chunk name>/result_pose.pkl` on either route; `save=True` / `--save true` writes every chunk's skeleton meshes under
-`mesh_root` (`meshes`).
+`mesh_root` (`meshes`); `render=DIR` / `--render DIR` writes every chunk's frames as PNG images under DIR
+(`render`).
 """
 import ctypes as C
 import os
@@ -420,6 +421,15 @@ def _save_meshes(engine, mesh_root, name, row):
     write_result_meshes(engine, os.path.join(mesh_root, os.path.split(dataset_dir)[1], seq_name), est, opt, gt)
 
 
+def _save_frames(engine, render_root, name, row):
+    """One chunk's rendered frames, <render_root>/<dataset>/<chunk>/frame_%04d.png and overview_*.png (`_save_meshes`' naming and
+    sequences): with a ground truth the estimated and the optimised sequence are aligned to it and all three are overlaid."""
+    from .render import write_result_frames
+    dataset_dir, seq_name = os.path.split(os.path.normpath(name))
+    est, opt, gt = row[6] if len(row) > 6 and row[6] is not None else (row[1], row[2], row[3])
+    write_result_frames(engine, os.path.join(render_root, os.path.split(dataset_dir)[1], seq_name), est, opt, gt)
+
+
 def _sequence_result(rows, title, verbose):
     """One sequence's return value from its chunks' report rows: (summary, per-chunk error dicts, estimated_pose, optimized_pose,
     gt_pose), the summary printed as the reference prints it (under `title` when there is one)."""
@@ -498,7 +508,7 @@ class _Batch:
 def _settings(camera_model_path, vae_weight=0.0, gmm_weight=0.0, smoothness_weight=0.001, bone_length_weight=0.01, weight_3d=0.01,
               reproj_weight=0.01, final_smooth=True, merge=True, global_vae_path=GLOBAL_VAE_PATH, local_vae_path=LOCAL_VAE_PATH,
               chunks_per_batch=None, optimizer=None, device_metrics=True, verbose=True, seq_len=SEQ_LEN, overlap=OVERLAP, timings=None,
-              per_sequence=False, ground_truth=True, save_pose=None, save=False, mesh_root="out"):
+              per_sequence=False, ground_truth=True, save_pose=None, save=False, mesh_root="out", render=None):
     """The arguments of `optimize_sequences` / `optimize_recordings` behind the sequences themselves, as one object.
     (`gmm_weight` and `merge` are accepted and unused, as in the reference: SURVEY D4.)"""
     if not ground_truth and not device_metrics:
@@ -697,6 +707,8 @@ class _Pipeline:
                 if row is not None:
                     if cfg.save:
                         _save_meshes(e, cfg.mesh_root, src.name, row)
+                    if cfg.render is not None:
+                        _save_frames(e, cfg.render, src.name, row)
                     row = row[:6]
                     self.rows[src.group].append(row)
                     if cfg.save_pose is not None:
@@ -748,7 +760,7 @@ def optimize_sequences(data_dirs, camera_model_path, *args, **kwargs):
 
     Further arguments, positional or by keyword, in this order (defaults: `_settings`): vae_weight, gmm_weight, smoothness_weight,
     bone_length_weight, weight_3d, reproj_weight, final_smooth, merge, global_vae_path, local_vae_path, chunks_per_batch, optimizer,
-    device_metrics, verbose, seq_len, overlap, timings, per_sequence, ground_truth, save_pose, save, mesh_root.
+    device_metrics, verbose, seq_len, overlap, timings, per_sequence, ground_truth, save_pose, save, mesh_root, render.
 
     ground_truth=False: the chunks carry no ground truth (`prepare` with a scale).  Their pickles are not asked for
     `gt_global_skeleton`, every chunk's report is the seven entries of QUALITY_KEYS (`WindowEngine.sequence_quality` on the estimated
@@ -758,7 +770,11 @@ def optimize_sequences(data_dirs, camera_model_path, *args, **kwargs):
     save=True: every chunk's skeleton meshes (optimizer.py:485-504) as `<mesh_root>/<dataset>/<chunk>/{optimized_global_aligned,
     input_global_aligned,gt_global_aligned}/out_%04d.ply`, one file per merged frame, the first two sequences aligned to the third
     over the chunk (`meshes.write_meshes`; mesh_root defaults to the reference's `out` under the working directory).  With
-    ground_truth=False: `optimized_global` and `input_global`, unaligned.  Results and reports do not depend on it."""
+    ground_truth=False: `optimized_global` and `input_global`, unaligned.  Results and reports do not depend on it.
+    render=DIR: every chunk's frames as `DIR/<dataset>/<chunk>/frame_%04d.png`, the estimated (red), the optimised (blue) and the
+    ground-truth sequence (green) overlaid, the first two aligned to the third, and one `overview_<name>.png` per sequence with all
+    its frames (`render.write_result_frames`, rendered on the device).  With ground_truth=False: two sequences, unaligned.  Results
+    and reports do not depend on it."""
     cfg = _settings(camera_model_path, *args, **kwargs)
     lap = Laps(cfg.timings, log=True)          # developer timing (tools/whole_sequence_timing.py): wall time of the main thread's phases
     groups = []
@@ -799,12 +815,13 @@ def optimize_recording(recording, camera_model_path, *args, **kwargs):
 
 def release_pools():
     """Give back what this module keeps between calls: the per-device frame buffers the readers fill, the pinned noise
-    blocks and the mesh writer's buffers, then (`staging.release`) the streams and the reader threads with their pinned staging buffers and device images.
+    blocks and the mesh and frame writers' buffers, then (`staging.release`) the streams and the reader threads with their pinned staging buffers and device images.
     Not to be called while another call is in flight."""
-    from . import meshes
+    from . import meshes, render
     _heat_pool.clear()
     _noise_pool.clear()
     meshes.release()
+    render.release()
     staging.release()
     if torch.cuda.is_available():
         torch.cuda.empty_cache()
@@ -825,6 +842,7 @@ def _cli():
     p.add_argument("--reproj_weight", type=float, default=0.01)
     p.add_argument("--save", default=False, type=truthy, help="true: write every chunk's skeleton meshes (PLY) under --mesh_root")
     p.add_argument("--mesh_root", default="out", metavar="DIR", help="where --save true writes <dataset>/<chunk>/<folder>/out_%%04d.ply")
+    p.add_argument("--render", default=None, metavar="DIR", help="write every chunk's frames as DIR/<dataset>/<chunk>/frame_%%04d.png")
     p.add_argument("--final_smooth", default=True, type=truthy)
     p.add_argument("--merge", default=True, type=truthy)
     p.add_argument("--chunks_per_batch", type=int, default=None, help="chunks optimised per device call (default: all)")
@@ -833,7 +851,7 @@ def _cli():
     a = p.parse_args()
     optimize_directory(a.data_path, a.camera, a.vae, a.gmm, a.smooth, a.bone_length, a.weight_3d, a.reproj_weight,
                        final_smooth=a.final_smooth, merge=a.merge, chunks_per_batch=a.chunks_per_batch, ground_truth=a.ground_truth,
-                       save_pose=a.save_pose, save=a.save, mesh_root=a.mesh_root)
+                       save_pose=a.save_pose, save=a.save, mesh_root=a.mesh_root, render=a.render)
 
 
 if __name__ == "__main__":

@@ -383,6 +383,41 @@ int gem_sequence_align(const double* d_src, const double* d_dst, int64_t n_point
 int gem_skeleton_mesh(const double* d_seq, int64_t n_frames, const double* d_crt, void* d_vertex_blocks, int64_t frame_stride_bytes,
                       void* stream);
 
+/* ---- Skeleton sequences as PNG frames: `render=DIR` / `--render DIR` ----
+ * A scene is a list of capsules -- all points within r of a segment [a, b] -- each with one colour 0x00BBGGRR.  An image draws a
+ * contiguous range of the list through one orthographic view: pixel (px, py) looks along `forward` through
+ * centre + u right + v down with u = (px + 0.5 - W/2) s, v = (py + 0.5 - H/2) s, s = 2 half_width / W; one sample per pixel; the
+ * nearest entry into a capsule wins (the lower index on equal depth), shaded 0.3 + 0.7 max(0, -n . forward); background white.
+ * All arithmetic float64. */
+typedef struct gem_view {
+    double right[3], down[3], forward[3];       /* orthonormal (checked to 1e-9) */
+    double centre[3];
+    double half_width;                          /* metres from the image's centre to its left and right edge */
+    int32_t width, height;                      /* pixels; width at most 1024 */
+} gem_view;
+
+/* out[3] = bytes of one scanline (1 + 3 width: PNG filter byte 0, then RGB), bytes of one image (height scanlines: what the file's
+ * IDAT holds before deflate), and the distance of two images in gem_render_capsules' output (the image's bytes rounded up to 16).
+ * Needs no GPU. */
+int gem_render_layout(int width, int height, int64_t* out);
+
+/* The 30 capsules of every frame of d_seq [n_frames,15,3] float64, moved by d_crt [13] (gem_sequence_align) first unless NULL: the
+ * 15 joints (a == b, r = 0.02 m, rgb_joint), then the 15 lines of Skeleton.lines (r = 0.005 m, rgb_line), in the meshes' order.
+ * d_geom [n_frames*30,7] float64 = a, b, r in world coordinates; d_rgb [n_frames*30] uint32. */
+int gem_skeleton_capsules(const double* d_seq, int64_t n_frames, const double* d_crt, uint32_t rgb_joint, uint32_t rgb_line,
+                          double* d_geom, uint32_t* d_rgb, void* stream);
+
+/* n_images images of view->width x view->height pixels: image i draws the capsules d_first[i] .. d_first[i+1] (int32, device) of
+ * d_geom [n_capsules,7] / d_rgb [n_capsules] and is written at d_out + i * image_stride_bytes as its PNG scanline stream.
+ * d_ids [n_images,H,W] int32 (may be NULL): the winning capsule's index within the image's range, -1 where nothing is hit;
+ * d_depth [n_images,H,W] float64 (may be NULL): the hit's t along `forward` from the plane through the centre, +inf where nothing
+ * is hit.  A capsule with a NaN is never hit.  Refused before any launch, with the reason in gem_last_error: d_out not 16-byte
+ * aligned; a stride below the image's bytes or no multiple of 16; d_first not ascending or leaving [0, n_capsules] (the call reads
+ * d_first back for this: it waits for the stream); a view that is not orthonormal; width or height below 1, width above 1024.
+ * One workgroup per band of 16 rows; no floating-point atomics: the same bytes on every call.  Works on the current device. */
+int gem_render_capsules(const double* d_geom, const uint32_t* d_rgb, int64_t n_capsules, const int32_t* d_first, int n_images,
+                        const gem_view* view, void* d_out, int64_t image_stride_bytes, int32_t* d_ids, double* d_depth, void* stream);
+
 /* Timing hook for bench.py's roofline: average device time (ms) of the launches of the dominant
  * kernel family since the last reset, measured with HIP events on the launch stream.
  * family: 0 = decoder_input GEMMs (forward + backward-data), 1 = fused tail / energy kernel, 2 = L-BFGS advance,
