@@ -63,6 +63,11 @@ class GemView(C.Structure):
                 ("half_width", C.c_double), ("width", C.c_int32), ("height", C.c_int32)]
 
 
+class GemCameraView(C.Structure):
+    _fields_ = [("size", C.c_int32), ("joint_mask", C.c_uint32), ("rgb_heat", C.c_uint32), ("reserved", C.c_uint32),
+                ("joint_radius", C.c_double), ("line_radius", C.c_double)]
+
+
 MAT_UNSUPPORTED, MAT_NOT_FOUND = 2, 3
 MAT_HEAT_F64, MAT_DEPTH_F32 = 1, 2
 MI_SINGLE, MI_DOUBLE = 7, 9
@@ -104,6 +109,8 @@ SIGNATURES = {
     "gem_render_layout": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int64)]),
     "gem_skeleton_capsules": (C.c_int, [_P, C.c_int64, _P, C.c_uint32, C.c_uint32, _P, _P, _P]),
     "gem_render_capsules": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int, C.POINTER(GemView), _P, C.c_int64, _P, _P, _P]),
+    "gem_project_sequence": (C.c_int, [_P, _P, _P, _P, C.c_int64, _P, _P]),
+    "gem_render_camera": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.POINTER(GemCameraView), _P, C.c_int64, _P, _P, _P]),
     "gem_lift_skeleton": (C.c_int, [_P, _P, _P, C.c_int, C.POINTER(C.c_double), C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     "gem_set_lanes": (C.c_int, [_P, C.c_int]),
     "gem_pickle_scan": (C.c_int, [_P, C.c_int64, C.POINTER(C.c_char_p), C.c_int, C.POINTER(GemPickleArray), C.c_int64, C.POINTER(C.c_int64)]),

@@ -460,6 +460,57 @@ class WindowEngine:
                                                  out.stride(0), _ptr(ids), _ptr(depth), _stream()), self.lib)
         return (out, ids, depth) if want_ids else out
 
+    def project_sequence(self, seq, cams=None, crt=None):
+        """The fisheye image points of `seq` [n,J,3] f64 (contiguous device tensor), moved by `crt` ([13] from `sequence_align`) first
+        when given, seen through `cams` [n,4,4] f64 (rigid camera-to-world; None: the points are in the camera's frame) with the
+        arithmetic of the reprojection term (gem_project_sequence) -> [n,J,2] f32 on the device, pixels of the
+        1280 x 1024 image; a joint on the optical axis gives a pair that is not finite.  No synchronisation."""
+        if not (torch.is_tensor(seq) and seq.is_cuda and seq.dtype == torch.float64 and seq.is_contiguous()):
+            raise TypeError("project_sequence wants a contiguous float64 device tensor")
+        if seq.dim() != 3 or tuple(seq.shape[1:]) != (N_JOINTS, 3):
+            raise ValueError("project_sequence: seq must be [n,%d,3], got %s" % (N_JOINTS, tuple(seq.shape)))
+        if crt is not None and not (torch.is_tensor(crt) and crt.is_cuda and crt.dtype == torch.float64 and crt.is_contiguous() and crt.numel() == 13):
+            raise TypeError("project_sequence: crt must be a contiguous float64 device tensor of 13 values")
+        n = seq.shape[0]
+        if cams is not None:
+            if not (torch.is_tensor(cams) and cams.is_cuda and cams.dtype == torch.float64 and cams.is_contiguous()):
+                raise TypeError("project_sequence: cams must be a contiguous float64 device tensor")
+            if tuple(cams.shape) != (n, 4, 4):
+                raise ValueError("project_sequence: cams must be [%d,4,4], got %s" % (n, tuple(cams.shape)))
+        uv = torch.empty(n, N_JOINTS, 2, device=self.device, dtype=torch.float32)
+        _capi.check(self.lib.gem_project_sequence(self._h, _ptr(seq), _ptr(crt), _ptr(cams), n, _ptr(uv), _stream()), self.lib)
+        return uv
+
+    def render_camera(self, heat, uv, rgb, view, out=None, want_ids=False):
+        """The camera's view (gem_render_camera): image i = heat-maps `heat`[i] ([n,H,W,J] f32, or None: white)
+        under the skeletons whose image points are `uv` [S,n,J,2] f32 (`project_sequence`), sequence s flat in `rgb`[s] ([S] int32,
+        0x00BBGGRR), through `view` (a `_capi.GemCameraView`), as PNG scanline streams -> uint8 [n, stride] on the device, `out` when
+        given (rows at least the image's bytes, 16-byte aligned, a row stride that is a multiple of 16).  want_ids: -> (out, ids
+        int32 [n,N,N], response f32 [n,N,N]).  No synchronisation."""
+        if not (torch.is_tensor(uv) and uv.is_cuda and uv.dtype == torch.float32 and uv.is_contiguous() and uv.dim() == 4
+                and tuple(uv.shape[2:]) == (N_JOINTS, 2)):
+            raise TypeError("render_camera: uv must be a contiguous float32 device tensor [S,n,%d,2]" % N_JOINTS)
+        S, n = uv.shape[0], uv.shape[1]
+        if not (torch.is_tensor(rgb) and rgb.is_cuda and rgb.dtype == torch.int32 and rgb.is_contiguous() and tuple(rgb.shape) == (S,)):
+            raise TypeError("render_camera: rgb must be a contiguous int32 device tensor [%d]" % S)
+        if heat is not None:
+            if not (torch.is_tensor(heat) and heat.is_cuda and heat.dtype == torch.float32 and heat.is_contiguous()):
+                raise TypeError("render_camera: heat must be a contiguous float32 device tensor")
+            if tuple(heat.shape) != (n, self.heat_size[0], self.heat_size[1], N_JOINTS):
+                raise ValueError("render_camera: heat must be [%d,%d,%d,%d], got %s" % ((n,) + tuple(self.heat_size) + (N_JOINTS, tuple(heat.shape))))
+        lay = (C.c_int64 * 3)()
+        _capi.check(self.lib.gem_render_layout(view.size, view.size, lay), self.lib)
+        if out is None:
+            out = torch.empty(n, lay[2], device=self.device, dtype=torch.uint8)
+        if not (torch.is_tensor(out) and out.is_cuda and out.dtype == torch.uint8 and out.dim() == 2 and out.shape[0] == n
+                and out.shape[1] >= lay[1] and out.stride(1) == 1):
+            raise ValueError("render_camera: out must be a uint8 device tensor [%d, >= %d] with contiguous rows" % (n, lay[1]))
+        ids = torch.empty(n, view.size, view.size, device=self.device, dtype=torch.int32) if want_ids else None
+        response = torch.empty(n, view.size, view.size, device=self.device, dtype=torch.float32) if want_ids else None
+        _capi.check(self.lib.gem_render_camera(self._h, _ptr(heat), _ptr(uv), _ptr(rgb), S, n, C.byref(view), _ptr(out), out.stride(0),
+                                               _ptr(ids), _ptr(response), _stream()), self.lib)
+        return (out, ids, response) if want_ids else out
+
     def calculate_errors(self, est, mid, opt, gt):
         """Same keys and definitions as the reference's calculate_errors (calculate_errors.py:114-179)."""
         from collections import OrderedDict

@@ -9,6 +9,12 @@ writer threads `meshes.write_meshes` uses; the host only deflates (zlib, level 1
 scene -- what the reference's viewer shows first (optimizer.py:452-467).  `read_png` reads such a file back.
 
     python -m globalegomocap_amd.render out/<dataset>/<chunk>/result_pose.pkl --out DIR [--align true] [--size WxH] [--view side|front|top]
+
+The camera's view is the picture from where the evidence lives: the frame's heat-maps, tinted, with the
+sequences projected through the frame's camera by the reprojection term's own arithmetic and drawn flat on top (`camera_scanlines`:
+gem_project_sequence + gem_render_camera; `write_camera_frames` writes one `camera_%04d.png` per frame by the same route).
+
+    python -m globalegomocap_amd.render out/<dataset>/<chunk>/result_pose.pkl --out DIR --camera <chunk directory> [--size N]
 """
 import ctypes as C
 import os
@@ -28,6 +34,8 @@ MAX_WRITERS = 16
 VIEWS = ("side", "front", "top")
 PALETTE = {"estimated": (214, 39, 40), "optimized": (31, 119, 180), "gt": (44, 160, 44)}
 DEFAULT_SIZE = (640, 480)        # (width, height) wherever a caller gives none
+CAMERA_SIZE = 512                # pixels each way of a camera view wherever a caller gives none
+HEAT_COLOUR = (148, 103, 189)    # the background's colour where the heat-maps say 1
 MARGIN = 0.1                     # metres around the joints' bounding box
 PNG_SIGNATURE = b"\x89PNG\r\n\x1a\n"
 
@@ -229,15 +237,20 @@ def read_png(path):
 
 
 def _write_images(engine, geom, rgb, first, view, paths):
-    """Image i of the scene -> paths[i].  The scanlines are made on the device, at most PINNED_BYTES of them at a time, and cross
-    PCIe through two alternating pinned buffers: while one is being deflated and written by the writer threads, the next batch
-    arrives in the other (`meshes.write_meshes`' route).  Every file is complete and closed when this returns."""
+    """Image i of the scene -> paths[i] (`_write_scanlines`)."""
+    _write_scanlines(engine, lambda lo, n, out: engine.render_capsules(geom, rgb, first[lo:lo + n + 1], view, out=out), view.width, view.height, paths)
+
+
+def _write_scanlines(engine, draw, W, H, paths):
+    """Image i -> paths[i], W x H pixels each; `draw(lo, n, out)` renders the images lo .. lo + n into the rows of `out`.  The
+    scanlines are made on the device, at most PINNED_BYTES of them at a time, and cross PCIe through two alternating pinned
+    buffers: while one is being deflated and written by the writer threads, the next batch arrives in the other
+    (`meshes.write_meshes`' route).  Every file is complete and closed when this returns."""
     import torch
     from .staging import cpus_near, reader_pool
     n_images = len(paths)
     if n_images == 0:
         return
-    W, H = view.width, view.height
     lay = layout(W, H)
     per = max(1, PINNED_BYTES // lay.stride)
     dev = engine.device
@@ -264,7 +277,7 @@ def _write_images(engine, geom, rgb, first, view, paths):
         for k, lo in enumerate(range(0, n_images, per)):
             n, slot = min(per, n_images - lo), k % 2
             settle(writing[slot])
-            engine.render_capsules(geom, rgb, first[lo:lo + n + 1], view, out=bufs[2][:n])
+            draw(lo, n, bufs[2][:n])
             bufs[slot][:n].copy_(bufs[2][:n], non_blocking=True)
             ev = torch.cuda.Event()
             ev.record(torch.cuda.current_stream())
@@ -332,6 +345,85 @@ def write_result_frames(engine, out_dir, estimated, optimized, gt=None, align=No
     return write_frames(engine, sequences, out_dir, align_to=to, size=size, view=view)
 
 
+# ------------------------------------------------------------------------------------------------------------------ the camera's view
+def camera_view(size=None, joint_radius=8.0, line_radius=3.0, heat_joints=None, heat_colour=HEAT_COLOUR):
+    """The `_capi.GemCameraView` of size x size pixels (default CAMERA_SIZE) over the 1024 x 1024 crop the heat-maps cover: radii in
+    pixels of the 1280 x 1024 image, `heat_joints` the joints whose heat-maps make the background (default: all), tinted
+    `heat_colour`.  Needs no GPU."""
+    size = CAMERA_SIZE if size is None else int(size)
+    if not 1 <= size <= 1024:
+        raise ValueError("a camera view is 1 .. 1024 pixels each way, got %d" % size)
+    joints = range(N_JOINTS) if heat_joints is None else [int(j) for j in heat_joints]
+    if not all(0 <= j < N_JOINTS for j in joints):
+        raise ValueError("heat_joints are joint indices 0 .. %d, got %r" % (N_JOINTS - 1, list(joints)))
+    for r in (joint_radius, line_radius):
+        if not (np.isfinite(r) and r >= 0):
+            raise ValueError("a radius is a finite number of pixels, not negative; got %r" % (r,))
+    v = _capi.GemCameraView()
+    v.size, v.joint_mask, v.rgb_heat, v.reserved = size, sum({1 << j for j in joints}), _rgb_word(heat_colour), 0
+    v.joint_radius, v.line_radius = float(joint_radius), float(line_radius)
+    return v
+
+
+def _camera_scene(engine, sequences, cams, heat, colours, align_to):
+    """What `gem_render_camera` reads, on the device: the heat-maps [F,H,W,15] (or None), the image points [S,F,15,2] of the
+    global-frame sequences seen through `cams` [F,4,4], and the sequences' colour words."""
+    import torch
+    seqs, crts = _prepare(engine, sequences, align_to)
+    if len(colours) != len(seqs):
+        raise ValueError("%d colours for %d sequences" % (len(colours), len(seqs)))
+    F = seqs[0].shape[0]
+    cams_d = (cams if torch.is_tensor(cams) else torch.from_numpy(np.array(cams, dtype=np.float64))).to(device=engine.device, dtype=torch.float64).contiguous()
+    if tuple(cams_d.shape) != (F, 4, 4):
+        raise ValueError("the cameras must be [%d,4,4], one per frame, got %s" % (F, tuple(cams_d.shape)))
+    if heat is not None:
+        heat = (heat if torch.is_tensor(heat) else torch.from_numpy(np.array(heat, dtype=np.float32))).to(device=engine.device, dtype=torch.float32).contiguous()
+        if heat.dim() != 4 or heat.shape[0] != F:
+            raise ValueError("the heat-maps must be [%d,H,W,%d], one set per frame, got %s" % (F, N_JOINTS, tuple(heat.shape)))
+    uv = torch.stack([engine.project_sequence(s, cams_d, crt) for s, crt in zip(seqs, crts)])
+    rgb = torch.tensor([_rgb_word(c) for c in colours], dtype=torch.int32).to(engine.device)
+    return heat, uv, rgb
+
+
+def camera_scanlines(engine, sequences, cams, heat, colours, size=None, joint_radius=8.0, line_radius=3.0, heat_joints=None, align_to=None):
+    """The camera's view of every frame: `heat` [F,H,W,15] (or None: white) tinted under the `sequences` (each
+    [F,15,3] in the frame the cameras `cams` [F,4,4] live in; one RGB colour each, a later sequence over an earlier one), projected
+    with the reprojection term's arithmetic, as the bytes their PNG files hold before deflate: a uint8 device tensor [F, stride]
+    (`layout(size, size)`).  Further arguments: `camera_view`; align_to: see `write_frames`."""
+    heat, uv, rgb = _camera_scene(engine, sequences, cams, heat, colours, align_to)
+    return engine.render_camera(heat, uv, rgb, camera_view(size, joint_radius, line_radius, heat_joints))
+
+
+def write_camera_frames(engine, sequences, cams, heat, out_dir, colours=None, size=None, joint_radius=8.0, line_radius=3.0, heat_joints=None,
+                        align_to=None):
+    """`out_dir/camera_%04d.png` for every frame: `camera_scanlines` (colours default: the palette's order) through `write_frames`'
+    pinned buffers and writer threads.  Runs on the current stream; every file is complete and closed on return; returns the
+    number of files."""
+    default = list(PALETTE)
+    if colours is None:
+        if len(sequences) > len(default):
+            raise ValueError("more than %d sequences need their colours given" % len(default))
+        colours = [PALETTE[k] for k in default[:len(sequences)]]
+    heat, uv, rgb = _camera_scene(engine, sequences, cams, heat, colours, align_to)
+    view = camera_view(size, joint_radius, line_radius, heat_joints)
+    os.makedirs(out_dir, exist_ok=True)
+    F = uv.shape[1]
+
+    def draw(lo, n, out):
+        engine.render_camera(None if heat is None else heat[lo:lo + n], uv[:, lo:lo + n].contiguous(), rgb, view, out=out)
+    _write_scanlines(engine, draw, view.size, view.size, [os.path.join(out_dir, "camera_%04d.png" % f) for f in range(F)])
+    return F
+
+
+def write_result_camera_frames(engine, out_dir, estimated, optimized, cams, heat, gt=None, size=None):
+    """One result as the camera saw it, `out_dir/camera_%04d.png`: the estimated (red), the optimised (blue) and, where there is one,
+    the ground-truth sequence (green) over the frames' heat-maps.  The ground truth lives in the studio's frame, not in the
+    cameras': it is first moved by the one similarity that takes it onto the optimised sequence."""
+    sequences = [estimated, optimized] + ([gt] if gt is not None else [])
+    to = [None, None] + ([optimized] if gt is not None else [])
+    return write_camera_frames(engine, sequences, cams, heat, out_dir, align_to=to, size=size)
+
+
 def release():
     """Give back the pinned and device buffers `write_frames` keeps between calls."""
     _buffers.clear()
@@ -348,6 +440,18 @@ def _size(text):
     return w, h
 
 
+def _size_or_side(text):
+    """`--size`: WIDTHxHEIGHT (a pair) or, for `--camera`, one number of pixels (an int)."""
+    try:
+        n = int(str(text))
+    except ValueError:
+        return _size(text)
+    if n < 1:
+        import argparse
+        raise argparse.ArgumentTypeError("a size is WIDTHxHEIGHT, for instance 640x480, or with --camera one number 1 .. 1024; got %r" % text)
+    return n
+
+
 def main(argv=None):
     import argparse
     from .camera import DEFAULT_CALIBRATION
@@ -356,9 +460,19 @@ def main(argv=None):
     p.add_argument("pose_pickle", help="result_pose.pkl as --save_pose writes it: estimated_pose, optimized_pose and, optionally, gt_pose")
     p.add_argument("--out", required=True, metavar="DIR")
     p.add_argument("--align", default=False, type=truthy, help="true: align both sequences to gt_pose first")
-    p.add_argument("--size", default=DEFAULT_SIZE, type=_size, metavar="WxH")
+    p.add_argument("--size", default=None, type=_size_or_side, metavar="WxH", help="default 640x480; with --camera one number N (default 512)")
     p.add_argument("--view", default="side", choices=VIEWS)
+    p.add_argument("--camera", default=None, metavar="CHUNK_DIR",
+                   help="draw the camera's view instead (camera_%%04d.png): the directory whose test_data.pkl holds the cameras and "
+                        "heat-maps the poses belong to (merged frame f is the chunk's frame f); gt_pose is aligned onto optimized_pose")
     a = p.parse_args(argv)
+    if a.camera is None and isinstance(a.size, int):
+        p.error("argument --size: a size is WIDTHxHEIGHT, for instance 640x480; got %r" % str(a.size))
+    if a.camera is not None:
+        if isinstance(a.size, tuple) or (a.size is not None and a.size > 1024):
+            p.error("argument --size: with --camera a size is one number of pixels 1 .. 1024")
+        if not os.path.isfile(os.path.join(a.camera, "test_data.pkl")):
+            p.error("--camera %s: no test_data.pkl in that directory" % a.camera)
     with open(a.pose_pickle, "rb") as f:
         d = pickle.load(f)
     for key in ("estimated_pose", "optimized_pose"):
@@ -371,8 +485,19 @@ def main(argv=None):
     import torch
     if not torch.cuda.is_available():
         raise _capi.GemError("no HIP device visible: the frames are rendered on the device")
-    n = write_result_frames(_lift_engine(DEFAULT_CALIBRATION, torch.cuda.current_device()), a.out, np.asarray(d["estimated_pose"]),
-                            np.asarray(d["optimized_pose"]), None if gt is None else np.asarray(gt), align=a.align, size=a.size, view=a.view)
+    engine = _lift_engine(DEFAULT_CALIBRATION, torch.cuda.current_device())
+    est, opt = np.asarray(d["estimated_pose"]), np.asarray(d["optimized_pose"])
+    if a.camera is not None:
+        from .whole_sequence import parse_chunk
+        c = parse_chunk(a.camera, native=False, ground_truth=False)
+        F = len(est)
+        if c["n"] < F or len(c["cams"]) < F:
+            p.error("--camera %s holds %d frames, the poses %d" % (a.camera, min(c["n"], len(c["cams"])), F))
+        heat = np.asarray(c["heat_list"][:F], dtype=np.float32).reshape((F,) + tuple(c["heat_shape"]))
+        n = write_result_camera_frames(engine, a.out, est, opt, c["cams"][:F], heat, None if gt is None else np.asarray(gt), size=a.size)
+    else:
+        n = write_result_frames(engine, a.out, est, opt, None if gt is None else np.asarray(gt), align=a.align,
+                                size=DEFAULT_SIZE if a.size is None else a.size, view=a.view)
     print("{} images written under {}".format(n, a.out))
 
 

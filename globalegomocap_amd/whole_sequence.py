@@ -18,7 +18,8 @@ Chunks without ground truth (`prepare --scale`) go the sam
 QUALITY_LINES from the device (`WindowEngine.sequence_quality`).  `save_pose=DIR` / `--save_pose DIR` writes the poses of every
 chunk to `DIR/<chunk name>/result_pose.pkl` on either route; `save=True` / `--save true` writes every chunk's skeleton meshes under
 `mesh_root` (`meshes`); `render=DIR` / `--render DIR` writes every chunk's frames as PNG images under DIR
-(`render`).
+(`render`); `render_camera=DIR` / `--render_camera DIR` writes every chunk as its camera saw it, the heat-maps
+under the reprojected skeletons.
 """
 import ctypes as C
 import os
@@ -430,6 +431,16 @@ def _save_frames(engine, render_root, name, row):
     write_result_frames(engine, os.path.join(render_root, os.path.split(dataset_dir)[1], seq_name), est, opt, gt)
 
 
+def _save_camera_frames(engine, render_root, name, row, cams, heat):
+    """One chunk as its camera saw it, <render_root>/<dataset>/<chunk>/camera_%04d.png (`_save_frames`' naming and sequences):
+    `cams` / `heat` are the chunk's frames on the device; merged frame f is the chunk's frame f."""
+    from .render import write_result_camera_frames
+    dataset_dir, seq_name = os.path.split(os.path.normpath(name))
+    est, opt, gt = row[6] if len(row) > 6 and row[6] is not None else (row[1], row[2], row[3])
+    F = len(est)
+    write_result_camera_frames(engine, os.path.join(render_root, os.path.split(dataset_dir)[1], seq_name), est, opt, cams[:F], heat[:F], gt)
+
+
 def _sequence_result(rows, title, verbose):
     """One sequence's return value from its chunks' report rows: (summary, per-chunk error dicts, estimated_pose, optimized_pose,
     gt_pose), the summary printed as the reference prints it (under `title` when there is one)."""
@@ -508,7 +519,7 @@ class _Batch:
 def _settings(camera_model_path, vae_weight=0.0, gmm_weight=0.0, smoothness_weight=0.001, bone_length_weight=0.01, weight_3d=0.01,
               reproj_weight=0.01, final_smooth=True, merge=True, global_vae_path=GLOBAL_VAE_PATH, local_vae_path=LOCAL_VAE_PATH,
               chunks_per_batch=None, optimizer=None, device_metrics=True, verbose=True, seq_len=SEQ_LEN, overlap=OVERLAP, timings=None,
-              per_sequence=False, ground_truth=True, save_pose=None, save=False, mesh_root="out", render=None):
+              per_sequence=False, ground_truth=True, save_pose=None, save=False, mesh_root="out", render=None, render_camera=None):
     """The arguments of `optimize_sequences` / `optimize_recordings` behind the sequences themselves, as one object.
     (`gmm_weight` and `merge` are accepted and unused, as in the reference: SURVEY D4.)"""
     if not ground_truth and not device_metrics:
@@ -702,13 +713,23 @@ class _Pipeline:
             else:
                 rows = _report_per_chunk(e, b.chunks, mid_np, opt_global, cfg.seq_len, cfg.overlap, bool(cfg.final_smooth), cfg.device_metrics,
                                          frames)
+            view_heat, view_cams = None, None
+            if cfg.render_camera is not None:
+                # the camera's view reads the batch's frame buffers too; its files are complete (the device has read the frames) before
+                # this returns, three batches before slot[0] is filled again
+                view_heat, view_cams = b.heat_d.contiguous(), b.prep["cams"]
+                for t in (view_heat, view_cams):
+                    t.record_stream(rs)
             b.heat_d = None
-            for src, row in zip(b.sources, rows):
+            for ci, (src, row) in enumerate(zip(b.sources, rows)):
                 if row is not None:
                     if cfg.save:
                         _save_meshes(e, cfg.mesh_root, src.name, row)
                     if cfg.render is not None:
                         _save_frames(e, cfg.render, src.name, row)
+                    if cfg.render_camera is not None:
+                        lo = int(b.frame_lo[ci])
+                        _save_camera_frames(e, cfg.render_camera, src.name, row, view_cams[lo:], view_heat[lo:])
                     row = row[:6]
                     self.rows[src.group].append(row)
                     if cfg.save_pose is not None:
@@ -760,7 +781,7 @@ def optimize_sequences(data_dirs, camera_model_path, *args, **kwargs):
 
     Further arguments, positional or by keyword, in this order (defaults: `_settings`): vae_weight, gmm_weight, smoothness_weight,
     bone_length_weight, weight_3d, reproj_weight, final_smooth, merge, global_vae_path, local_vae_path, chunks_per_batch, optimizer,
-    device_metrics, verbose, seq_len, overlap, timings, per_sequence, ground_truth, save_pose, save, mesh_root, render.
+    device_metrics, verbose, seq_len, overlap, timings, per_sequence, ground_truth, save_pose, save, mesh_root, render, render_camera.
 
     ground_truth=False: the chunks carry no ground truth (`prepare` with a scale).  Their pickles are not asked for
     `gt_global_skeleton`, every chunk's report is the seven entries of QUALITY_KEYS (`WindowEngine.sequence_quality` on the estimated
@@ -774,7 +795,11 @@ def optimize_sequences(data_dirs, camera_model_path, *args, **kwargs):
     render=DIR: every chunk's frames as `DIR/<dataset>/<chunk>/frame_%04d.png`, the estimated (red), the optimised (blue) and the
     ground-truth sequence (green) overlaid, the first two aligned to the third, and one `overview_<name>.png` per sequence with all
     its frames (`render.write_result_frames`, rendered on the device).  With ground_truth=False: two sequences, unaligned.  Results
-    and reports do not depend on it."""
+    and reports do not depend on it.
+    render_camera=DIR: every chunk as its camera saw it, `DIR/<dataset>/<chunk>/camera_%04d.png`: the frame's heat-maps under the
+    estimated (red), the optimised (blue) and the ground-truth sequence (green, moved onto the optimised one by one similarity: it
+    lives in the studio's frame), projected with the reprojection term's arithmetic (`render.write_result_camera_frames`, from the
+    batch's frame buffers on the device).  DIR may be `render`'s DIR.  Results and reports do not depend on it."""
     cfg = _settings(camera_model_path, *args, **kwargs)
     lap = Laps(cfg.timings, log=True)          # developer timing (tools/whole_sequence_timing.py): wall time of the main thread's phases
     groups = []
@@ -827,7 +852,7 @@ def release_pools():
         torch.cuda.empty_cache()
 
 
-def _cli():
+def _parser():
     import argparse
     from .camera import DEFAULT_CALIBRATION
     truthy = lambda x: str(x).lower() == "true"          # noqa: E731  (the reference's own flag parser)
@@ -843,15 +868,21 @@ def _cli():
     p.add_argument("--save", default=False, type=truthy, help="true: write every chunk's skeleton meshes (PLY) under --mesh_root")
     p.add_argument("--mesh_root", default="out", metavar="DIR", help="where --save true writes <dataset>/<chunk>/<folder>/out_%%04d.ply")
     p.add_argument("--render", default=None, metavar="DIR", help="write every chunk's frames as DIR/<dataset>/<chunk>/frame_%%04d.png")
+    p.add_argument("--render_camera", default=None, metavar="DIR",
+                   help="write every chunk as its camera saw it, DIR/<dataset>/<chunk>/camera_%%04d.png: heat-maps under the reprojected skeletons")
     p.add_argument("--final_smooth", default=True, type=truthy)
     p.add_argument("--merge", default=True, type=truthy)
     p.add_argument("--chunks_per_batch", type=int, default=None, help="chunks optimised per device call (default: all)")
     p.add_argument("--ground_truth", default=True, type=truthy, help="false: chunks without gt_global_skeleton, the report without ground truth")
     p.add_argument("--save_pose", default=None, metavar="DIR", help="write DIR/<chunk name>/result_pose.pkl per chunk")
-    a = p.parse_args()
+    return p
+
+
+def _cli(argv=None):
+    a = _parser().parse_args(argv)
     optimize_directory(a.data_path, a.camera, a.vae, a.gmm, a.smooth, a.bone_length, a.weight_3d, a.reproj_weight,
                        final_smooth=a.final_smooth, merge=a.merge, chunks_per_batch=a.chunks_per_batch, ground_truth=a.ground_truth,
-                       save_pose=a.save_pose, save=a.save, mesh_root=a.mesh_root, render=a.render)
+                       save_pose=a.save_pose, save=a.save, mesh_root=a.mesh_root, render=a.render, render_camera=a.render_camera)
 
 
 if __name__ == "__main__":

@@ -418,6 +418,47 @@ int gem_skeleton_capsules(const double* d_seq, int64_t n_frames, const double* d
 int gem_render_capsules(const double* d_geom, const uint32_t* d_rgb, int64_t n_capsules, const int32_t* d_first, int n_images,
                         const gem_view* view, void* d_out, int64_t image_stride_bytes, int32_t* d_ids, double* d_depth, void* stream);
 
+/* ---- The camera's view: `render_camera=DIR` / `--render_camera DIR` ----
+ * The fisheye image points of a sequence, and images of the 1024 x 1024 crop of the 1280 x 1024 fisheye image that the heat-maps
+ * cover (columns 128 .. 1152): the heat-maps as a tinted background, the reprojected skeletons flat on top. */
+
+/* d_seq [n_frames,J,3] float64 -> d_uv [n_frames,J,2] float32, pixels of the 1280 x 1024 image.  d_crt [13] (gem_sequence_align) or
+ * NULL: every joint p becomes c * (p . R) + t first, exactly as in gem_skeleton_capsules.  d_cams [n_frames,4,4] float64, rigid
+ * camera-to-world, or NULL when the points are in the camera's frame already: X_cam = R^T (X - t) in float64, rounded once to
+ * float32, then the fp32 projection of the optimiser's reprojection term with the handle's polynomial, cx and cy -- the arithmetic
+ * of gem_sequence_quality's column 0.  A joint on the optical axis gives a pair that is not finite, and no error. */
+int gem_project_sequence(gem_handle* h, const double* d_seq, const double* d_crt, const double* d_cams, int64_t n_frames, float* d_uv,
+                         void* stream);
+
+typedef struct gem_camera_view {
+    int32_t  size;          /* N: N x N pixels over the 1024 x 1024 crop the heat-maps cover; 1 .. 1024 */
+    uint32_t joint_mask;    /* bit j set: heat-map j takes part in the background */
+    uint32_t rgb_heat;      /* 0x00BBGGRR */
+    uint32_t reserved;
+    double   joint_radius, line_radius;   /* in pixels of the 1280 x 1024 image */
+} gem_camera_view;
+
+/* n_images images of N x N pixels, image i written at d_out + i * image_stride_bytes as its PNG scanline stream, in the layout of
+ * gem_render_layout(N, N).  d_heat [n_images,H,W,J] float32 (NULL: a white background, response 0); d_uv [n_sequences,n_images,J,2]
+ * float32 (gem_project_sequence); d_rgb [n_sequences] 0x00BBGGRR; d_ids [n_images,N,N] int32 and d_response [n_images,N,N] float32
+ * may be NULL.  Pixel (px, py) stands at u = 128 + (px + 0.5) (1024 / N), v = (py + 0.5) (1024 / N), in fp32 for the background and
+ * in float64 for the overlay (the same numbers when N is a power of two).
+ *   Background: m = the largest, over the joints of joint_mask, of the bilinear heat-map sample at (u, v) (zeros outside, the fp32
+ *   arithmetic of the reprojection term), clamped to [0, 1] -- d_response receives it; every colour byte is
+ *   floor(255 + (c - 255) m + 0.5) in float64 with c that byte of rgb_heat.
+ *   Overlay: sequence s has 30 primitives in gem_skeleton_capsules' order: the 15 joints as discs of joint_radius about their
+ *   (u, v), then the 15 lines as all points within line_radius of the straight segment between their joints' (u, v).  A primitive
+ *   covers a pixel whose centre lies within its radius (<=, float64 on the widened fp32 points).  Of the covering primitives the
+ *   higher s wins, within a sequence a joint beats a line, within a class the lower index; the pixel takes d_rgb[s] flat and d_ids
+ *   receives s * 30 + c (-1: none).  A primitive with a coordinate that is not finite is never drawn.
+ * Refused before any launch, with the reason in gem_last_error: a handle whose n_joints is not 15; size outside 1 .. 1024;
+ * joint_mask bits at or above 15; a radius that is negative or not finite; n_sequences outside 0 .. 8; n_images outside 0 .. 65535;
+ * d_out not 16-byte aligned, a stride below the image's bytes or no multiple of 16; NULL where data are needed.  n_images == 0
+ * returns 0.  One workgroup per band of 16 rows; no atomics: the same bytes on every call. */
+int gem_render_camera(gem_handle* h, const float* d_heat, const float* d_uv, const uint32_t* d_rgb, int n_sequences, int n_images,
+                      const gem_camera_view* view, void* d_out, int64_t image_stride_bytes, int32_t* d_ids, float* d_response,
+                      void* stream);
+
 /* Timing hook for bench.py's roofline: average device time (ms) of the launches of the dominant
  * kernel family since the last reset, measured with HIP events on the launch stream.
  * family: 0 = decoder_input GEMMs (forward + backward-data), 1 = fused tail / energy kernel, 2 = L-BFGS advance,

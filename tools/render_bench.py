@@ -88,14 +88,16 @@ def kernels_only(frames, size, repeats):
     torch.cuda.synchronize()
 
 
-def kernel_times(frames, size, repeats, work):
-    """(frames launch, overview launch) best device times in seconds from a rocprofv3 run of this script, or (None, reason)."""
+def kernel_times(frames, size, repeats, work, script=None, kernels=("render_capsules_kernel",), groups=2):
+    """(frames launch, overview launch) best device times in seconds from a rocprofv3 run of this script, or (None, reason).
+    `script`: a sibling tool (tools/camera_view_bench.py) that under --kernels-only launches each of `kernels` groups * (repeats + 1)
+    times; the best time of every group of every kernel, in that order."""
     exe = shutil.which("rocprofv3") or "/opt/rocm/bin/rocprofv3"
     if not os.path.exists(exe):
         return None, "rocprofv3 not found"
     d = tempfile.mkdtemp(prefix="render_prof_", dir=work)
     try:
-        r = subprocess.run([exe, "--kernel-trace", "--output-format", "csv", "-d", d, "--", sys.executable, os.path.abspath(__file__),
+        r = subprocess.run([exe, "--kernel-trace", "--output-format", "csv", "-d", d, "--", sys.executable, script or os.path.abspath(__file__),
                             "--kernels-only", "--frames", str(frames), "--size", "%dx%d" % size, "--repeats", str(repeats)],
                            capture_output=True, text=True, timeout=600)
         if r.returncode:
@@ -103,12 +105,15 @@ def kernel_times(frames, size, repeats, work):
         files = sorted(glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True))
         if not files:
             return None, "no kernel_trace.csv under %s" % d
-        rows = [row for row in csv.DictReader(open(files[0])) if "render_capsules_kernel" in row["Kernel_Name"]]
-        rows.sort(key=lambda row: int(row["Start_Timestamp"]))
-        if len(rows) != 2 * (repeats + 1):
-            return None, "%d render launches in the trace, expected %d" % (len(rows), 2 * (repeats + 1))
-        ns = [int(row["End_Timestamp"]) - int(row["Start_Timestamp"]) for row in rows]
-        return (min(ns[:repeats + 1]) * 1e-9, min(ns[repeats + 1:]) * 1e-9), None
+        trace, best = list(csv.DictReader(open(files[0]))), []
+        for kernel in kernels:
+            rows = [row for row in trace if kernel in row["Kernel_Name"]]
+            rows.sort(key=lambda row: int(row["Start_Timestamp"]))
+            if len(rows) != groups * (repeats + 1):
+                return None, "%d %s launches in the trace, expected %d" % (len(rows), kernel, groups * (repeats + 1))
+            ns = [int(row["End_Timestamp"]) - int(row["Start_Timestamp"]) for row in rows]
+            best += [min(ns[g * (repeats + 1):(g + 1) * (repeats + 1)]) * 1e-9 for g in range(groups)]
+        return tuple(best), None
     finally:
         shutil.rmtree(d, ignore_errors=True)
 
