@@ -77,6 +77,12 @@ class GemWindowStats(C.Structure):
     _fields_ = [("n_iter", C.c_int32), ("func_evals", C.c_int32), ("final_loss", C.c_float), ("status", C.c_int32)]
 
 
+class GemLbfgsDebugState(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("phase", "n_iter", "evals", "ls_iter", "ls_evals", "hist_count", "hist_start", "low", "high",
+                                          "insuf", "nan_seen", "pad_nonzero")] + \
+               [(k, C.c_double) for k in ("t", "loss", "gtd", "d_norm", "H_diag")]
+
+
 # name -> (restype, argtypes); every symbol include/gem_hip.h declares
 _P = C.c_void_p
 SIGNATURES = {
@@ -98,6 +104,9 @@ SIGNATURES = {
     "gem_graph_enable": (C.c_int, [_P, C.c_int]),
     "gem_graph_stats": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "gem_read_trace": (C.c_int, [_P, C.c_int, C.c_int, _P, _P]),
+    "gem_lbfgs_debug_begin": (C.c_int, [_P, C.c_int, _P, C.c_int, _P]),
+    "gem_lbfgs_debug_advance": (C.c_int, [_P, C.c_int, C.POINTER(GemLbfgsOpts), _P, _P, C.c_int, _P]),
+    "gem_lbfgs_debug_read": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, _P]),
     "gem_merge_windows": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
     "gem_calculate_errors": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.POINTER(C.c_double), _P, _P]),
     "gem_calculate_errors_chunks": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.POINTER(C.c_double), _P, _P]),

@@ -671,6 +671,7 @@ static int stage_begin(StageRun& r) {
     // (the per-round counters of a stage are zeroed by one 1024-thread workgroup, and the trace keeps TRACE_ROUNDS rounds)
     if (r.opt.max_eval > 1021) { set_error("optimize: max_eval must be at most 1021 (torch's default for max_iter = 25 is 31)"); return 1; }
     r.rounds = r.opt.max_eval + 1;          // upper bound on evaluations per window (see lbfgs.hip)
+    w.dbg_slots = -1;                       // (a debug run of the solver alone ends where a stage begins)
     if (B == 0) return 0;
     if (encoder_forward(h, stage, B, r.pose_in, s)) return 1;
     if (launch_reparam(w.mulv, r.eps, nullptr, nullptr, nullptr, w.trial, B, h->D, h->Dp, s)) return 1;
@@ -989,6 +990,105 @@ int gem_read_trace(gem_handle* h, int B, int n_rounds, double* d_out, void* stre
     if (B == 0 || n_rounds == 0) return 0;
     GEM_HIP(hipMemcpy2DAsync(d_out, (size_t)B * sizeof(double), h->ws.trace, (size_t)h->ws.Bmax * sizeof(double),
                              (size_t)B * sizeof(double), (size_t)n_rounds, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return 0;
+}
+
+// ---- for parity tests: the L-BFGS state machine stepped alone (include/gem_hip.h) ---------------------------------------------
+// The caller plays the decoder and the energy.  Every launch goes through the launchers of the stage rounds; between the calls
+// the workspace is left as stage_finish leaves it (dyn off, compaction pointers home, no deferred gradient slabs).
+static const int DBG_MAX_ROUNDS = 1022;          // max_eval <= 1021 (stage_begin): at most max_eval + 1 rounds
+
+static int check_lbfgs_opts(const Workspace& w, const gem_lbfgs_opts& o, const char* who) {
+    if (o.max_iter < 1 || o.max_eval < 1 || o.max_iter - 1 > w.hist_cap || o.max_iter > MAX_HIST) {
+        set_error(std::string(who) + ": max_iter must be 1.." + std::to_string(w.hist_cap + 1)); return 1;
+    }
+    if (o.max_eval > 1021) { set_error(std::string(who) + ": max_eval must be at most 1021"); return 1; }
+    return 0;
+}
+
+int gem_lbfgs_debug_begin(gem_handle* h, int B, const float* d_x0, int slots, void* stream) {
+    if (!h) { set_error("gem_lbfgs_debug_begin: null handle"); return 1; }
+    Workspace& w = h->ws;
+    if (B < 1 || B > w.Bmax) { set_error("gem_lbfgs_debug_begin: B exceeds max_windows (or is < 1)"); return 1; }
+    if (!d_x0 || slots < 0 || slots > 2) { set_error("gem_lbfgs_debug_begin: null x0 or slots not 0, 1 or 2"); return 1; }
+    GEM_HIP(hipSetDevice(h->cfg.device));
+    hipStream_t s = (hipStream_t)stream;
+    w.dbg_slots = -1;
+    w.round = -1; w.dyn = false;
+    if (launch_pad_latent(d_x0, w.trial, B, h->D, h->Dp, s)) return 1;
+    if (h->precision == GEM_PRECISION_BF16 && launch_f32_to_bf16(w.trial, w.trial_b, (size_t)B * h->Dp, s)) return 1;
+    gem_lbfgs_opts none{};
+    if (launch_lbfgs_init(h, B, none, s)) return 1;
+    compaction_home(w);
+    w.grad_slab = SlabSrc{};
+    const int counters = slots == 2 ? DBG_MAX_ROUNDS + 1 : 0;        // as stage_begin: round 0's count, then one zeroed counter per round
+    if (counters) {
+        if ((w.log_pos % N_LOG) + counters + 2 > N_LOG) w.log_pos += N_LOG - (w.log_pos % N_LOG);
+        w.dbg_log0 = w.log_pos;
+    }
+    if (launch_compact(h, B, 1, s, counters)) return 1;
+    if (counters) w.log_pos = w.dbg_log0 + counters + 2;
+    w.dbg_slots = slots; w.dbg_B = B; w.dbg_round = 0;
+    return 0;
+}
+
+int gem_lbfgs_debug_advance(gem_handle* h, int B, const gem_lbfgs_opts* opt, const double* d_f, const float* d_g, int n_slabs,
+                            void* stream) {
+    if (!h) { set_error("gem_lbfgs_debug_advance: null handle"); return 1; }
+    Workspace& w = h->ws;
+    if (B < 1 || B > w.Bmax) { set_error("gem_lbfgs_debug_advance: B exceeds max_windows (or is < 1)"); return 1; }
+    if (w.dbg_slots < 0 || B != w.dbg_B) { set_error("gem_lbfgs_debug_advance: no gem_lbfgs_debug_begin with this B came before"); return 1; }
+    if (!opt || !d_f || !d_g) { set_error("gem_lbfgs_debug_advance: null argument"); return 1; }
+    if (check_lbfgs_opts(w, *opt, "gem_lbfgs_debug_advance")) return 1;
+    const size_t slab = (size_t)B * h->Dp;
+    if (n_slabs < 0 || (size_t)n_slabs * slab > w.splitk_elems) {
+        set_error("gem_lbfgs_debug_advance: n_slabs must be 0.." + std::to_string(w.splitk_elems / slab) + " (the split-K scratch)"); return 1;
+    }
+    if (w.dbg_round >= DBG_MAX_ROUNDS) { set_error("gem_lbfgs_debug_advance: more rounds than any max_eval allows"); return 1; }
+    GEM_HIP(hipSetDevice(h->cfg.device));
+    hipStream_t s = (hipStream_t)stream;
+    GEM_HIP(hipMemcpyAsync(w.f, d_f, (size_t)B * sizeof(double), hipMemcpyDeviceToDevice, s));
+    float* rows = n_slabs ? w.splitk : w.dz;
+    for (int z = 0; z < (n_slabs ? n_slabs : 1); ++z)
+        if (launch_pad_latent(d_g + (size_t)z * B * h->D, rows + z * slab, B, h->D, h->Dp, s)) return 1;
+    const int k = w.dbg_round;
+    w.dyn = true;          // make_args: slot table, slot hand-out and slabs are what the rounds of a stage use
+    if (w.dbg_slots == 0) {
+        w.slot_of = nullptr;
+    } else if (w.dbg_slots == 2) {          // stage_round: this round's set and the set lbfgs_advance fills for the next one
+        int* cnt = w.n_log + (w.dbg_log0 + k) % N_LOG;
+        w.perm = (k & 1) ? w.perm2 : w.perm_home;          w.next_perm = (k & 1) ? w.perm_home : w.perm2;
+        w.slot_of = (k & 1) ? w.slot_of2 : w.slot_of_home; w.next_slot_of = (k & 1) ? w.slot_of_home : w.slot_of2;
+        w.n_active = cnt; w.next_count = cnt + 1;
+    }
+    if (n_slabs) { w.grad_slab = SlabSrc{}; w.grad_slab.base = w.splitk; w.grad_slab.nslab = n_slabs; w.grad_slab.stride = slab; }
+    else w.grad_slab = SlabSrc{};
+    int rc = launch_lbfgs_advance(h, B, *opt, s);
+    w.dyn = false;
+    compaction_home(w);
+    w.grad_slab = SlabSrc{};
+    // slot mode 1: the compaction between this round and the next (a stage runs it at the head of the next round)
+    if (!rc && w.dbg_slots == 1) rc = launch_compact(h, B, 0, s);
+    if (rc) { w.dbg_slots = -1; return 1; }
+    w.dbg_round = k + 1;
+    return 0;
+}
+
+int gem_lbfgs_debug_read(gem_handle* h, int B, gem_lbfgs_debug_state* d_state, float* d_x, float* d_d, float* d_trial,
+                         int32_t* d_slot_of, int32_t* d_count, void* stream) {
+    if (!h) { set_error("gem_lbfgs_debug_read: null handle"); return 1; }
+    Workspace& w = h->ws;
+    if (B < 1 || B > w.Bmax) { set_error("gem_lbfgs_debug_read: B exceeds max_windows (or is < 1)"); return 1; }
+    if (w.dbg_slots < 0 || B != w.dbg_B) { set_error("gem_lbfgs_debug_read: no gem_lbfgs_debug_begin with this B came before"); return 1; }
+    GEM_HIP(hipSetDevice(h->cfg.device));
+    hipStream_t s = (hipStream_t)stream;
+    if (launch_lbfgs_debug_read(h, B, d_state, d_x, d_d, d_trial, s)) return 1;
+    const int k = w.dbg_round;
+    // slot mode 0 never touches the identity table of the begin call; mode 1 compacts into the home set; mode 2 alternates
+    const int* slot_of = (w.dbg_slots == 2 && (k & 1)) ? w.slot_of2 : w.slot_of_home;
+    const int* count = w.dbg_slots == 2 ? w.n_log + (w.dbg_log0 + k) % N_LOG : w.n_active_home;
+    if (d_slot_of) GEM_HIP(hipMemcpyAsync(d_slot_of, slot_of, (size_t)B * sizeof(int), hipMemcpyDeviceToDevice, s));
+    if (d_count) GEM_HIP(hipMemcpyAsync(d_count, count, sizeof(int), hipMemcpyDeviceToDevice, s));
     return 0;
 }
 

@@ -170,6 +170,10 @@ struct Workspace {
     bool fuse_compact = false;          // next decoder_input forward launch re-packs the active windows itself (gemm_rows.h)
     int* fuse_log = nullptr;            // ... and logs n_active here
     int done_phase = 3;                 // lbfgs.hip PH_DONE
+    // the solver stepped alone (gem_lbfgs_debug_*, parity tests): slot mode of the run in progress (-1: none), its batch size,
+    // the round the next advance call enqueues, and the n_log entry of round 0's count (slot mode 2)
+    int dbg_slots = -1, dbg_B = 0, dbg_round = 0;
+    long dbg_log0 = 0;
     std::vector<void*> allocs;
 };
 
@@ -429,6 +433,7 @@ int launch_lbfgs_init(gem_handle* h, int B, const gem_lbfgs_opts& o, hipStream_t
 int launch_lbfgs_advance(gem_handle* h, int B, const gem_lbfgs_opts& o, hipStream_t s);
 int launch_lbfgs_stats(gem_handle* h, int B, gem_window_stats* out, hipStream_t s);
 int launch_compact(gem_handle* h, int B, int force_all, hipStream_t s, int zero_after = 0);
+int launch_lbfgs_debug_read(gem_handle* h, int B, gem_lbfgs_debug_state* out, float* x, float* d, float* trial, hipStream_t s);
 
 
 }  // namespace gem

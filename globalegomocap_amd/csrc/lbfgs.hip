@@ -665,6 +665,53 @@ __global__ void lbfgs_stats_kernel(const LbfgsState* st, gem_window_stats* out, 
     out[i].status = (st[i].phase == PH_DONE ? 1 : 0) | (st[i].nan_seen ? 2 : 0);
 }
 
+// For parity tests (gem_lbfgs_debug_read): one window per workgroup; the scalars of its state as a plain record, x / d / trial
+// without their padding columns, and the number of padding columns that are not zero.  With trial_b the trial point is the bf16
+// copy (the only one lbfgs_advance writes in bf16 precision), widened.
+__global__ __launch_bounds__(256) void lbfgs_debug_read_kernel(const LbfgsState* __restrict__ st, gem_lbfgs_debug_state* __restrict__ out,
+                                                               const float* __restrict__ x, const float* __restrict__ d,
+                                                               const float* __restrict__ trial, const uint16_t* __restrict__ trial_b,
+                                                               float* __restrict__ ox, float* __restrict__ od, float* __restrict__ otrial,
+                                                               int D, int Dp) {
+    __shared__ int bad;
+    const int b = blockIdx.x;
+    if (threadIdx.x == 0) bad = 0;
+    __syncthreads();
+    int mine = 0;
+    for (int k = threadIdx.x; k < Dp; k += blockDim.x) {
+        const size_t i = (size_t)b * Dp + k;
+        const float xv = x[i], dv = d[i];
+        const float tv = trial_b ? __builtin_bit_cast(float, (unsigned)trial_b[i] << 16) : trial[i];
+        if (k < D) {
+            const size_t o = (size_t)b * D + k;
+            if (ox) ox[o] = xv;
+            if (od) od[o] = dv;
+            if (otrial) otrial[o] = tv;
+        } else {
+            mine += (xv != 0.f) + (dv != 0.f) + (tv != 0.f);
+        }
+    }
+    if (mine) atomicAdd(&bad, mine);
+    __syncthreads();
+    if (threadIdx.x == 0 && out) {
+        const LbfgsState& s = st[b];
+        gem_lbfgs_debug_state r;
+        r.phase = s.phase; r.n_iter = s.n_iter; r.evals = s.evals; r.ls_iter = s.ls_iter; r.ls_evals = s.ls_evals;
+        r.hist_count = s.hist_count; r.hist_start = s.hist_start; r.low = s.low; r.high = s.high; r.insuf = s.insuf;
+        r.nan_seen = s.nan_seen; r.pad_nonzero = bad;
+        r.t = s.t; r.loss = s.loss; r.gtd = s.gtd; r.d_norm = s.d_norm; r.H_diag = s.H_diag;
+        out[b] = r;
+    }
+}
+
+int launch_lbfgs_debug_read(gem_handle* h, int B, gem_lbfgs_debug_state* out, float* x, float* d, float* trial, hipStream_t s) {
+    const Workspace& w = h->ws;
+    hipLaunchKernelGGL(lbfgs_debug_read_kernel, dim3(B), dim3(256), 0, s, w.state, out, w.x, w.d, w.trial,
+                       h->precision == GEM_PRECISION_BF16 ? w.trial_b : nullptr, x, d, trial, h->D, h->Dp);
+    GEM_HIP(hipGetLastError());
+    return 0;
+}
+
 static AdvArgs make_args(gem_handle* h, const gem_lbfgs_opts& o) {
     Workspace& w = h->ws;
     AdvArgs a;

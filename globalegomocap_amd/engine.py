@@ -303,6 +303,44 @@ class WindowEngine:
         _capi.check(self.lib.gem_read_trace(self._h, B, n_rounds, _ptr(out), _stream()), self.lib)
         return out.cpu().numpy().T.copy()
 
+    # ------------------------------------------------------------------ the L-BFGS kernels stepped alone (parity tests)
+    def lbfgs_debug_begin(self, x0, slots=0):
+        """Start B = x0.shape[0] solvers at x0 [B,D] (gem_lbfgs_debug_begin); slots: 0 no slot table, 1 compact_kernel between
+        the rounds, 2 slots handed out by lbfgs_advance.  Needs no weights; a test hook, not part of the reference's surface."""
+        x0 = self._f32(x0).reshape(-1, self.D)
+        self._check_B(x0.shape[0])
+        _capi.check(self.lib.gem_lbfgs_debug_begin(self._h, x0.shape[0], _ptr(x0), int(slots), _stream()), self.lib)
+
+    def lbfgs_debug_advance(self, f, g, opts=None, n_slabs=0):
+        """One evaluation round: f [B] f64 by window, g [max(n_slabs,1),B,D] f32 with window b's row at slot_of[b]."""
+        f = torch.as_tensor(f).to(device=self.device, dtype=torch.float64).contiguous()
+        B = f.shape[0]
+        self._check_B(B)
+        g = self._f32(g)
+        if g.numel() != max(int(n_slabs), 1) * B * self.D:
+            raise ValueError("lbfgs_debug_advance: g must be [max(n_slabs,1), %d, %d]" % (B, self.D))
+        opts = opts or _capi.default_lbfgs_opts()
+        _capi.check(self.lib.gem_lbfgs_debug_advance(self._h, B, C.byref(opts), _ptr(f), _ptr(g), int(n_slabs), _stream()), self.lib)
+
+    def lbfgs_debug_read(self, B):
+        """State of the B solvers (gem_lbfgs_debug_read): dict with one numpy array [B] per field of gem_lbfgs_debug_state,
+        device tensors x, d, trial [B,D] (bf16 precision: trial is the bf16 trial point widened), slot_of [B] and count of the
+        next advance call."""
+        self._check_B(B)
+        words = C.sizeof(_capi.GemLbfgsDebugState) // 8
+        st = torch.zeros(B, words, device=self.device, dtype=torch.int64)
+        x, d, trial = (torch.empty(B, self.D, device=self.device) for _ in range(3))
+        slot_of = torch.empty(B, device=self.device, dtype=torch.int32)
+        count = torch.empty(1, device=self.device, dtype=torch.int32)
+        _capi.check(self.lib.gem_lbfgs_debug_read(self._h, B, _ptr(st), _ptr(x), _ptr(d), _ptr(trial), _ptr(slot_of), _ptr(count),
+                                                  _stream()), self.lib)
+        raw = st.cpu().numpy()
+        ints, dbl = raw[:, :6].copy().view(np.int32), raw[:, 6:].copy().view(np.float64)
+        out = {k: ints[:, i].copy() for i, k in enumerate(n for n, _ in _capi.GemLbfgsDebugState._fields_[:12])}
+        out.update({k: dbl[:, i].copy() for i, k in enumerate(n for n, _ in _capi.GemLbfgsDebugState._fields_[12:])})
+        out.update(x=x, d=d, trial=trial, slot_of=slot_of.cpu().numpy(), count=int(count.item()))
+        return out
+
     # ------------------------------------------------------------------ sequence post-processing (SURVEY 8f.1)
     def _f64(self, a):
         t = torch.as_tensor(np.asarray(a) if not torch.is_tensor(a) else a)

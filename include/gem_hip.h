@@ -147,6 +147,45 @@ int gem_optimize_stage(gem_handle* h, int stage, int B, const float* d_pose_in, 
  * tests against the reference's closure traces; after gem_optimize_windows it holds the global stage's values. */
 int gem_read_trace(gem_handle* h, int B, int n_rounds, double* d_out, void* stream);
 
+/* ---- For parity tests: the L-BFGS / strong-Wolfe state machine (csrc/lbfgs.hip) stepped alone -------------------------------
+ * These three calls launch the kernels of the evaluation rounds exactly as a stage does (same launchers, same arguments),
+ * but the caller plays the decoder and the energy: it reads the trial points, evaluates whatever objective it likes and hands
+ * (f, g) back.  They need no VAE weights.  They are test hooks, not part of the reference's surface.
+ *
+ * gem_lbfgs_debug_begin: d_x0 [B,D] f32 becomes the trial point of every window (padded to pad64(D) with zeros; in bf16
+ * precision the bf16 copy is written too), the states are reset and the identity compaction runs, as at the start of a stage.
+ * `slots` selects how the later rounds address gradient rows:
+ *   0  no slot table (slot_of == nullptr in the kernel): row b belongs to window b;
+ *   1  compact_kernel runs between the rounds: windows still iterating take slots [0, count) in window order;
+ *   2  lbfgs_advance hands out the next round's slots itself (two alternating perm / slot_of sets and one zeroed counter per
+ *      round, as a stage with atomic slots arranges them): slots [0, count) in arrival order.
+ *
+ * gem_lbfgs_debug_advance: one evaluation round.  d_f [B] f64 is indexed by window.  d_g is [max(n_slabs,1)][B][D] f32: row
+ * slot_of[b] (gem_lbfgs_debug_read) belongs to window b, and the slabs sum to the gradient.  n_slabs == 0: the rows are the
+ * finished gradient (the kernel reads them where the decoder's backward product leaves dE/dz); n_slabs >= 1: the rows go to the
+ * split-K scratch as that many slabs with a STATIC cut (slab z at z * B * pad64(D)) and the kernel sums them, in slab order.
+ * The device-adaptive cut of the stage rounds (a slab count computed on the device from the live row count) is out of scope
+ * here.  `opt` is checked as gem_optimize_stage checks it; B must be the B of the begin call; n_slabs * B * pad64(D) must fit
+ * the scratch.  At most max_eval + 1 calls are ever needed; a call for a finished window changes nothing.
+ *
+ * gem_lbfgs_debug_read: every pointer may be NULL.  d_state [B] gem_lbfgs_debug_state; d_x, d_d, d_trial [B,D] f32 (unpadded).
+ * In bf16 precision the kernel writes only the bf16 trial point: d_trial then holds those bf16 values widened to f32.
+ * d_slot_of [B] int32 and d_count [1] int32: the slot table and the live count of the NEXT advance call (slots == 0: the
+ * identity and B; entries of finished windows are meaningless).
+ *
+ * A stage call after a debug run behaves as on a fresh handle. */
+typedef struct gem_lbfgs_debug_state {
+    int32_t phase;          /* 0 INIT, 1 BRACKET, 2 ZOOM, 3 DONE */
+    int32_t n_iter, evals, ls_iter, ls_evals, hist_count, hist_start, low, high, insuf, nan_seen;
+    int32_t pad_nonzero;    /* padding columns D..pad64(D)-1 of x, d and the trial point (bf16 precision: the bf16 one) that are not zero */
+    double  t, loss, gtd, d_norm, H_diag;
+} gem_lbfgs_debug_state;
+int gem_lbfgs_debug_begin(gem_handle* h, int B, const float* d_x0, int slots, void* stream);
+int gem_lbfgs_debug_advance(gem_handle* h, int B, const gem_lbfgs_opts* opt, const double* d_f, const float* d_g, int n_slabs,
+                            void* stream);
+int gem_lbfgs_debug_read(gem_handle* h, int B, gem_lbfgs_debug_state* d_state, float* d_x, float* d_d, float* d_trial,
+                         int32_t* d_slot_of, int32_t* d_count, void* stream);
+
 /* The window loop body of main() (optimizer.py:370-423) for B windows at once: local stage,
  * relative-global transform X_rel[t] = C0^-1 C_t X_loc[t] in float64 (utils/utils.py:99-112), global
  * stage, X_glob = C0 X_rel (optimizer.py:302-308).

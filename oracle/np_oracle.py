@@ -332,6 +332,9 @@ class LBFGSOptions:
 
 
 def cubic_interpolate(x1, f1, g1, x2, f2, g2, bounds=None):
+    """torch/optim/lbfgs.py `_cubic_interpolate` on python floats.  Known difference: where the denominator of `m` is exactly zero
+    (a purely linear objective: g1 == g2 and d2 == 0) python raises ZeroDivisionError while torch's 0-dim tensors yield inf or NaN
+    and carry on; the lock-step tests leave purely linear objectives out."""
     if bounds is not None:
         lo, hi = bounds
     else:
@@ -368,6 +371,31 @@ class LBFGSMachine:
         self.trace = []
 
     # -- helpers ----------------------------------------------------------------------
+    # The three methods below are the seams of tests/lbfgs_twin.py (the twins of the HIP kernel's bf16 ring and of its fp64
+    # reductions); the defaults are the arithmetic of torch.optim.LBFGS on float32 tensors.
+    @staticmethod
+    def _dot(a, b):
+        return _dot(a, b)
+
+    def _store_pair(self, s, y):
+        """The one place a curvature pair enters the memory (the oldest pair has been dropped already; ro and H_diag
+        come from the pair as it is handed in)."""
+        self.Y.append(y); self.S.append(s)
+
+    def _two_loop(self, g):
+        """d = -H g by the two-loop recursion over the stored pairs."""
+        k = len(self.S)
+        al = [0.0] * k
+        q = (-g).astype(F32)
+        for i in range(k - 1, -1, -1):
+            al[i] = self._dot(self.S[i], q) * self.ro[i]
+            q = (q - F32(al[i]) * self.Y[i]).astype(F32)
+        r = (q * F32(self.H_diag)).astype(F32)
+        for i in range(k):
+            be = self._dot(self.Y[i], r) * self.ro[i]
+            r = (r + F32(al[i] - be) * self.S[i]).astype(F32)
+        return r
+
     def _emit(self, t):
         self.t = float(t)
         self.trial = (self.x + F32(self.t) * self.d).astype(F32)
@@ -388,30 +416,21 @@ class LBFGSMachine:
         else:
             y = (g - self.prev_g).astype(F32)
             s = (self.d * F32(self.t)).astype(F32)
-            ys = _dot(y, s)
+            ys = self._dot(y, s)
             if ys > 1e-10:
                 if len(self.S) == o.history:
                     self.S.pop(0); self.Y.pop(0); self.ro.pop(0)
-                self.Y.append(y); self.S.append(s); self.ro.append(1.0 / ys)
-                self.H_diag = ys / _dot(y, y)
-            k = len(self.S)
-            al = [0.0] * k
-            q = (-g).astype(F32)
-            for i in range(k - 1, -1, -1):
-                al[i] = _dot(self.S[i], q) * self.ro[i]
-                q = (q - F32(al[i]) * self.Y[i]).astype(F32)
-            r = (q * F32(self.H_diag)).astype(F32)
-            for i in range(k):
-                be = _dot(self.Y[i], r) * self.ro[i]
-                r = (r + F32(al[i] - be) * self.S[i]).astype(F32)
-            self.d = r
+                self._store_pair(s, y)
+                self.ro.append(1.0 / ys)
+                self.H_diag = ys / self._dot(y, y)
+            self.d = self._two_loop(g)
         self.prev_g = g.copy()
         self.prev_loss = self.loss
         if self.n_iter == 1:
             t = min(1.0, 1.0 / float(np.sum(np.abs(g), dtype=F32))) * o.lr
         else:
             t = o.lr
-        self.gtd = _dot(g, self.d)
+        self.gtd = self._dot(g, self.d)
         if self.gtd > -o.tol_change:
             return self._finish()
         # _strong_wolfe prologue
@@ -482,7 +501,7 @@ class LBFGSMachine:
             if float(np.max(np.abs(g_new))) <= o.tol_grad:
                 return self._finish()
             return self._start_iteration()
-        gtd_new = _dot(g_new, self.d)
+        gtd_new = self._dot(g_new, self.d)
         t = self.t
         if self.phase == self.BRACKET:
             if not self.first_bracket_eval:
