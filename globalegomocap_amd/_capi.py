@@ -152,6 +152,8 @@ SIGNATURES = {
     "gem_trainer_apply": (C.c_int, [_P, C.POINTER(GemTrainOpts), C.c_double, _P]),
     "gem_motion_cameras": (C.c_int, [_P, _P, C.c_int64, _P, _P]),
     "gem_motion_windows": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int64, C.c_int, C.c_int, _P, C.c_int64, _P, _P]),
+    "gem_latent_paths": (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "gem_latent_report": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
 }
 
 _lib = None

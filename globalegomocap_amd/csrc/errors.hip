@@ -443,3 +443,4 @@ int launch_lift(gem_handle* h, const float* heat, const double* depth, int F, co
 #include "skeleton_mesh.h"             // gem_skeleton_mesh, gem_sequence_align
 #include "render.h"                    // gem_render_capsules, gem_skeleton_capsules
 #include "camera_view.h"               // gem_project_sequence, gem_render_camera
+#include "latent_tools.h"              // gem_latent_paths, gem_latent_report

@@ -549,6 +549,58 @@ class WindowEngine:
                                                _ptr(ids), _ptr(response), _stream()), self.lib)
         return (out, ids, response) if want_ids else out
 
+    # ------------------------------------------------------------------ looking at a trained VAE
+    PATH_MODES = {"linear": 0, "spherical": 1}
+    REPORT_KEYS = ("mu_error", "std_error", "kld", "mpjpe", "max_joint_error")
+
+    def latent_paths(self, za, zb, steps, mode="linear"):
+        """`steps` latent points from za to zb for each of P pairs (gem_latent_paths): za, zb [P,D] (or [D]) f32 -> [P,steps,D] f32
+        on the device.  The end points are za and zb themselves; mode "linear" is numpy's float32 arithmetic of the reference's
+        interpolant.py:126, "spherical" walks the great circle between the two directions.  P is not limited by max_windows.  No
+        synchronisation."""
+        if mode not in self.PATH_MODES:
+            raise ValueError("latent_paths: mode must be one of %s, got %r" % (sorted(self.PATH_MODES), mode))
+        a = self._f32(za).reshape(-1, self.D)
+        b = self._f32(zb).reshape(-1, self.D)
+        if a.shape != b.shape or a.shape[0] < 1:
+            raise ValueError("latent_paths: za and zb must be equally shaped [P,%d] with P >= 1, got %s and %s" % (self.D, tuple(a.shape), tuple(b.shape)))
+        if int(steps) < 2:
+            raise ValueError("latent_paths: a path has at least its two end points (steps >= 2), got %d" % steps)
+        out = torch.empty(a.shape[0], int(steps), self.D, device=self.device, dtype=torch.float32)
+        _capi.check(self.lib.gem_latent_paths(_ptr(a), _ptr(b), a.shape[0], self.D, int(steps), self.PATH_MODES[mode], _ptr(out), _stream()),
+                    self.lib)
+        return out
+
+    def latent_report(self, mu, logvar, x=None, rec=None, cols=None, count=None, out=None):
+        """What a batch of encoded (and reconstructed) windows says about the VAE (gem_latent_report): mu, logvar [B,D] f32, x and
+        rec [B,T,45] f32 or both None -> [B,5] f64 on the device in the order of REPORT_KEYS (`out` when given: a contiguous f64
+        device tensor [B,5]; the last two NaN without x / rec).  cols [3,D] f64 and count [1] i64 are device accumulators the
+        caller zeroes once: every call adds the batch's sum mu_d, sum mu_d^2, sum exp(logvar_d) and B.  B is not limited by
+        max_windows.  No synchronisation."""
+        if (x is None) != (rec is None):
+            raise ValueError("latent_report: x and rec come together")
+        for t, dt in ((mu, torch.float32), (logvar, torch.float32), (x, torch.float32), (rec, torch.float32), (cols, torch.float64),
+                      (count, torch.int64), (out, torch.float64)):
+            if t is not None and not (torch.is_tensor(t) and t.is_cuda and t.dtype == dt and t.is_contiguous()):
+                raise TypeError("latent_report wants contiguous device tensors of the documented dtypes")
+        B = mu.shape[0]
+        if mu.dim() != 2 or tuple(mu.shape) != (B, self.D) or tuple(logvar.shape) != (B, self.D) or B < 1:
+            raise ValueError("latent_report: mu and logvar must be [B,%d] with B >= 1, got %s and %s" % (self.D, tuple(mu.shape), tuple(logvar.shape)))
+        n_coords = self.T * N_JOINTS * 3
+        if x is not None and not (x.numel() == B * n_coords and rec.numel() == B * n_coords):
+            raise ValueError("latent_report: x and rec must hold %d windows of %d x %d x 3 values" % (B, self.T, N_JOINTS))
+        if cols is not None and tuple(cols.shape) != (3, self.D):
+            raise ValueError("latent_report: cols must be [3,%d]" % self.D)
+        if count is not None and count.numel() != 1:
+            raise ValueError("latent_report: count must hold one int64")
+        if out is None:
+            out = torch.empty(B, 5, device=self.device, dtype=torch.float64)
+        if tuple(out.shape) != (B, 5):
+            raise ValueError("latent_report: out must be [%d,5]" % B)
+        _capi.check(self.lib.gem_latent_report(_ptr(mu), _ptr(logvar), _ptr(x), _ptr(rec), B, self.D, n_coords, N_JOINTS, _ptr(out),
+                                               _ptr(cols), _ptr(count), _stream()), self.lib)
+        return out
+
     def calculate_errors(self, est, mid, opt, gt):
         """Same keys and definitions as the reference's calculate_errors (calculate_errors.py:114-179)."""
         from collections import OrderedDict

@@ -579,6 +579,33 @@ int gem_motion_windows(const double* d_pose, const double* d_cam34, const int64_
                        const int32_t* d_seq_timer, int n_seq, int64_t interval, int frame_num, int windows_size,
                        const int64_t* d_ids, int64_t B, float* d_out, void* stream);
 
+/* ---- Looking at a trained motion VAE ----
+ * Neither function takes a handle: the batch is not limited by a handle's max_windows.  Caller-owned device pointers, nothing
+ * synchronises, sums are f64 in a fixed order (two calls give the same bits), no atomics.
+ *
+ * gem_latent_paths: for each of n_pairs pairs, n_steps >= 2 latent points from d_za [n_pairs,D] to d_zb [n_pairs,D] into
+ * d_out [n_pairs,n_steps,D], all f32.  Step 0 is za and step n_steps-1 is zb, copied.  Interior step i, t = i / (n_steps-1):
+ *   GEM_PATH_LINEAR     numpy's float32 arithmetic of `first_z + (i / (S - 1.)) * (second_z - first_z)` (the reference's
+ *                       networks/interpolant.py:126): t rounded to f32, then the difference, the product and the sum rounded once each
+ *   GEM_PATH_SPHERICAL  w = acos(clamp(<a,b> / (|a| |b|), -1, 1)) from f64 sums; (sin((1-t) w) a + sin(t w) b) / sin w in f64,
+ *                       rounded once to f32.  A pair with |a| = 0, |b| = 0 or sin w < 1e-6 takes the linear formula.
+ *
+ * gem_latent_report: d_mu, d_logvar [n_windows,D] f32 (what the encoder returns); d_x, d_rec [n_windows,n_coords] f32 with
+ * n_coords = frames * n_joints * 3 (a window and its reconstruction), or NULL.  d_rows [n_windows][5] f64 per window:
+ *   0 mu_error         sum_d mu^2                                  (networks/get_latent.py:57)
+ *   1 std_error        sum_d (exp(logvar / 2) - 1)^2               (get_latent.py:58)
+ *   2 kld              -1/2 sum_d (1 + logvar - mu^2 - exp(logvar))  (the summand of SeqConvVAE.loss_function's batch mean)
+ *   3 mpjpe            mean over frames and joints of |rec - x|     (networks/train.py:127-129); NaN without d_x / d_rec
+ *   4 max_joint_error  the largest of those distances; NaN without d_x / d_rec
+ * f64 arithmetic on the f32 inputs.  d_cols [3][D] f64 (or NULL) are accumulators the caller zeroes once; every call adds the
+ * batch's sum_n mu_d, sum_n mu_d^2 and sum_n exp(logvar_d), summed in an order that depends on a row's index in the batch only.
+ * d_count (or NULL): *d_count += n_windows. */
+enum { GEM_PATH_LINEAR = 0, GEM_PATH_SPHERICAL = 1 };
+int gem_latent_paths(const float* d_za, const float* d_zb, int64_t n_pairs, int latent_dim, int n_steps, int mode, float* d_out,
+                     void* stream);
+int gem_latent_report(const float* d_mu, const float* d_logvar, const float* d_x, const float* d_rec, int64_t n_windows, int latent_dim,
+                      int n_coords, int n_joints, double* d_rows, double* d_cols, int64_t* d_count, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
