@@ -68,6 +68,13 @@ class GemCameraView(C.Structure):
                 ("joint_radius", C.c_double), ("line_radius", C.c_double)]
 
 
+class GemLiveBuffers(C.Structure):
+    _fields_ = [("ring_pose", C.c_void_p), ("ring_cams", C.c_void_p), ("ring_times", C.c_void_p), ("ring_heat", C.c_void_p),
+                ("state", C.c_void_p)]
+
+
+LIVE_WINDOW, LIVE_STRIDE, LIVE_RING, LIVE_PUSH_MAX, LIVE_STATE_DOUBLES = 10, 8, 32, 8, 320
+
 MAT_UNSUPPORTED, MAT_NOT_FOUND = 2, 3
 MAT_HEAT_F64, MAT_DEPTH_F32 = 1, 2
 MI_SINGLE, MI_DOUBLE = 7, 9
@@ -154,6 +161,10 @@ SIGNATURES = {
     "gem_motion_windows": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int64, C.c_int, C.c_int, _P, C.c_int64, _P, _P]),
     "gem_latent_paths": (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_int, C.c_int, _P, _P]),
     "gem_latent_report": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
+    "gem_live_push": (C.c_int, [_P, C.POINTER(GemLiveBuffers), C.c_int64, C.c_int, C.c_int64, _P, _P, _P, _P, _P]),
+    "gem_live_window": (C.c_int, [_P, C.POINTER(GemLiveBuffers), C.c_int64, C.c_int64, _P, _P, _P, _P, _P, _P]),
+    "gem_live_emit": (C.c_int, [_P, C.POINTER(GemLiveBuffers), C.c_int64, C.c_int, _P, _P, _P, C.POINTER(C.c_double), _P, _P]),
+    "gem_one_euro": (C.c_int, [_P, _P, C.c_int, C.c_int64, C.c_int, C.POINTER(C.c_double), _P, _P]),
 }
 
 _lib = None

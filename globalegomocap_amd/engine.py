@@ -601,6 +601,78 @@ class WindowEngine:
                                                _ptr(cols), _ptr(count), _stream()), self.lib)
         return out
 
+    # ------------------------------------------------------------------ live mode
+    def live_buffers(self):
+        """The device memory of one live session (gem_live_buffers): the frame rings and the zeroed state block, as a dict of
+        tensors plus "c", the struct the library is handed (it holds their addresses: keep the dict alive)."""
+        H, W = self.heat_size
+        t = {"ring_pose": torch.zeros(_capi.LIVE_RING, N_JOINTS, 3, device=self.device, dtype=torch.float32),
+             "ring_cams": torch.zeros(_capi.LIVE_RING, 4, 4, device=self.device, dtype=torch.float64),
+             "ring_times": torch.zeros(_capi.LIVE_RING, device=self.device, dtype=torch.float64),
+             "ring_heat": torch.zeros(_capi.LIVE_RING, H, W, N_JOINTS, device=self.device, dtype=torch.float32),
+             "state": torch.zeros(_capi.LIVE_STATE_DOUBLES, device=self.device, dtype=torch.float64)}
+        t["c"] = _capi.GemLiveBuffers(*[t[k].data_ptr() for k, _ in _capi.GemLiveBuffers._fields_])
+        return t
+
+    def _live_check(self, what, *pairs):
+        for x, dt, shape in pairs:
+            if x is None:
+                continue
+            if not (torch.is_tensor(x) and x.is_cuda and x.dtype == dt and x.is_contiguous()):
+                raise TypeError("%s wants contiguous device tensors of the documented dtypes" % what)
+            if tuple(x.shape) != tuple(shape):
+                raise ValueError("%s: a tensor of shape %s where %s is expected" % (what, tuple(x.shape), tuple(shape)))
+
+    def live_push(self, bufs, first_frame, oldest_needed, heat, pose, cams, times):
+        """k <= 8 frames into the rings of `bufs` (`live_buffers`) as the frames first_frame .. first_frame + k - 1 (gem_live_push):
+        heat [k,H,W,15] f32, pose [k,15,3] f32, cams [k,4,4] f64, times [k] f64, contiguous device tensors.  oldest_needed: the
+        oldest frame a window still to come reads.  No synchronisation."""
+        k = int(times.shape[0]) if torch.is_tensor(times) and times.dim() == 1 else -1
+        self._live_check("live_push", (heat, torch.float32, (k,) + self.heat_size + (N_JOINTS,)), (pose, torch.float32, (k, N_JOINTS, 3)),
+                         (cams, torch.float64, (k, 4, 4)), (times, torch.float64, (k,)))
+        _capi.check(self.lib.gem_live_push(self._h, C.byref(bufs["c"]), int(first_frame), k, int(oldest_needed), _ptr(heat), _ptr(pose),
+                                           _ptr(cams), _ptr(times), _stream()), self.lib)
+
+    def live_window(self, bufs, window, n_pushed, win_pose, win_cams, win_heat, mean_bone, bone_fixed=None):
+        """The frames [8 window, 8 window + 10) from the rings into the window buffers win_pose [10,15,3] f32, win_cams [10,4,4] f64,
+        win_heat [10,H,W,15] f32, and the call's mean bone lengths into mean_bone [1,15] f32: `bone_fixed` [15] f32 when given, else
+        the running mean over the frames pushed so far (gem_live_window).  No synchronisation."""
+        self._live_check("live_window", (win_pose, torch.float32, (self.T, N_JOINTS, 3)), (win_cams, torch.float64, (self.T, 4, 4)),
+                         (win_heat, torch.float32, (self.T,) + self.heat_size + (N_JOINTS,)), (mean_bone, torch.float32, (1, N_JOINTS)),
+                         (bone_fixed, torch.float32, (N_JOINTS,)))
+        _capi.check(self.lib.gem_live_window(self._h, C.byref(bufs["c"]), int(window), int(n_pushed), _ptr(bone_fixed), _ptr(win_pose),
+                                             _ptr(win_cams), _ptr(win_heat), _ptr(mean_bone), _stream()), self.lib)
+
+    def live_emit(self, bufs, window, out, glob=None, win_pose=None, win_cams=None, final=False, one_euro=None):
+        """The window's result `glob` [1,10,15,3] f64 (optimize_windows on the window buffers) -> out [2,8,15,3] f64: the 8 frames
+        the window makes final, optimised (out[0]; merged with the two held frames, One-Euro filtered when `one_euro` = (min_cutoff,
+        beta, d_cutoff)) and estimated (out[1]); the window's last two frames are held (gem_live_emit).  final=True: the two held
+        frames into out[:, :2] instead.  No synchronisation."""
+        self._live_check("live_emit", (out, torch.float64, (2, _capi.LIVE_STRIDE, N_JOINTS, 3)), (glob, torch.float64, (1, self.T, N_JOINTS, 3)),
+                         (win_pose, torch.float32, (self.T, N_JOINTS, 3)), (win_cams, torch.float64, (self.T, 4, 4)))
+        euro = (C.c_double * 3)(*[float(v) for v in one_euro]) if one_euro is not None else None
+        _capi.check(self.lib.gem_live_emit(self._h, C.byref(bufs["c"]), int(window), 1 if final else 0, _ptr(glob), _ptr(win_pose),
+                                           _ptr(win_cams), euro, _ptr(out), _stream()), self.lib)
+        return out
+
+    def one_euro_filter(self, seq, times, n_chunks, params):
+        """The reference's utils/one_euro_filter.py over `n_chunks` equally long sequences laid end to end (gem_one_euro): seq
+        [n_chunks*F,15,3] f64 (any trailing shape), times [n_chunks*F] f64, params (min_cutoff, beta, d_cutoff) -> a device tensor
+        of seq's shape; every chunk starts with fresh state.  No synchronisation."""
+        s, t = self._f64(seq), self._f64(times).reshape(-1)
+        total = t.shape[0]
+        if n_chunks < 1 or total % n_chunks or s.dim() < 2 or s.shape[0] != total:
+            raise ValueError("one_euro_filter: %d timestamps for a sequence of shape %s in %d chunks" % (total, tuple(s.shape), n_chunks))
+        if len(params) != 3:
+            raise ValueError("one_euro_filter: params are (min_cutoff, beta, d_cutoff)")
+        out = torch.empty_like(s)
+        if total == 0:
+            return out
+        euro = (C.c_double * 3)(*[float(v) for v in params])
+        _capi.check(self.lib.gem_one_euro(_ptr(s), _ptr(t), int(n_chunks), total // n_chunks, s.numel() // total, euro, _ptr(out), _stream()),
+                    self.lib)
+        return out
+
     def calculate_errors(self, est, mid, opt, gt):
         """Same keys and definitions as the reference's calculate_errors (calculate_errors.py:114-179)."""
         from collections import OrderedDict

@@ -1,0 +1,372 @@
+"""Live mode: a stream optimised window by window as its frames arrive.
+
+A `LiveOptimizer` takes frames as they come, optimises each 10-frame window the moment its tenth frame is there -- both stages of
+`WindowEngine.optimize_windows` with B = 1, one captured-graph replay per window -- and hands back finished global poses eight
+frames at a time:
+
+    live = LiveOptimizer(camera_json, global_vae, local_vae, scale=1.0)
+    for frame in rig:                                   # a head-mounted rig calls push itself
+        got = live.push(heat=frame.heat, depth=frame.depth, rows=frame.trajectory_row)
+        use(got["frames"], got["optimized"])            # 8 frames whenever a window completed, else none
+    tail = live.flush()                                 # the two frames still held, and how many frames were left over
+
+Frames are numbered n = 0, 1, 2, ... in arrival order and the session's frame is the first frame's camera.  Window w covers the
+frames [8w, 8w + 10) (`sequence.SEQ_LEN`, `sequence.OVERLAP`: the reference's `main()` values) and makes the frames [8w, 8w + 8)
+final: its first two are averaged with the last two of window w - 1 by `sequence.merge_batches`' expression, its last two are held
+for window w + 1.  Two sequences come out: `optimized`, and `estimated` = cams[n] . est_local[n] in float64.  The mid (local-stage)
+sequence is not produced in live mode.  The offline Gaussian `final_smooth` needs four frames of look-ahead and has no place
+here; `one_euro=(min_cutoff, beta, d_cutoff)` runs the causal One-Euro filter of the reference's `utils/one_euro_filter.py` over
+`optimized` instead (off by default, as the reference's `main()` never calls it: with the filter off a session reproduces the
+engine's own window results bit for bit).
+
+`replay` / `python -m globalegomocap_amd.live` push the frames of a prepared recording one at a time: a replay of a recording, for
+looking at live mode's results and step times.
+"""
+import os
+import pickle
+import time
+
+import numpy as np
+import torch
+
+from . import _capi
+from .camera import FisheyeCamera
+from .engine import WindowEngine, stats_to_numpy, raise_if_degenerate, LOCAL_STAGE, GLOBAL_STAGE
+from .optimizer import SequenceOptimizer, GLOBAL_VAE_PATH, LOCAL_VAE_PATH, _as_state_dict
+from .sequence import SEQ_LEN, OVERLAP
+from .skeleton import N_JOINTS
+from .vae import infer_shape
+
+STRIDE = SEQ_LEN - OVERLAP
+# the defaults of whole_sequence._settings, as SequenceOptimizer.stage_weights takes them
+DEFAULT_WEIGHTS = dict(vae_weight=0.0, smoothness_weight=0.001, bone_length_weight=0.01, weight_3d=0.01, reproj_weight=0.01)
+
+
+def dropped_frames(n_pushed):
+    """How many of `n_pushed` frames belong to no complete window (the reference's range(0, len - 10 + 1, 8) drops them)."""
+    n_windows = (n_pushed - SEQ_LEN) // STRIDE + 1 if n_pushed >= SEQ_LEN else 0
+    return n_pushed - (n_windows * STRIDE + OVERLAP if n_windows else 0)
+
+
+def _pieces(n_pushed, k):
+    """A push of k frames behind n_pushed, cut into pieces of at most 8 frames none of which goes past the frame that completes a
+    window: the window is optimised -- and its mean bone length taken -- before the frames behind it arrive."""
+    out, at = [], 0
+    while at < k:
+        n = n_pushed + at
+        completing = SEQ_LEN - 1 if n < SEQ_LEN else n + (SEQ_LEN - 1 - n) % STRIDE          # the next frame 8w + 9 at or behind n
+        step = min(k - at, _capi.LIVE_PUSH_MAX, completing - n + 1)
+        out.append((at, at + step))
+        at += step
+    return out
+
+
+def check_push(n_pushed_times, heat, depth, est_local, rows, cams, times, heat_size=(64, 64)):
+    """The host-side checks of `LiveOptimizer.push`, before anything is enqueued: exactly one of depth / est_local and of rows /
+    cams + times, shapes that agree on k >= 1 frames, timestamps that increase strictly (also past `n_pushed_times`, the last
+    timestamp of the pushes before; None on the first).  -> (k, timestamps as a float64 array, the five other arguments as arrays or tensors).  ValueError otherwise."""
+    if heat is None:
+        raise ValueError("push: heat= is needed")
+    heat, depth, est_local, rows, cams, times = (x if x is None or torch.is_tensor(x) else np.asarray(x) for x in (heat, depth, est_local, rows, cams, times))
+    if (depth is None) == (est_local is None):
+        raise ValueError("push: give exactly one of depth= (lifted here) and est_local= (already lifted)")
+    if (rows is None) == (cams is None):
+        raise ValueError("push: give exactly one of rows= (trajectory rows) and cams= with times=")
+    if (cams is None) != (times is None):
+        raise ValueError("push: cams= and times= come together (rows= carry their own timestamps)")
+    k = int(heat.shape[0]) if len(heat.shape) == 4 else -1
+    want = (k,) + tuple(heat_size) + (N_JOINTS,)
+    if k < 1 or tuple(heat.shape) != want:
+        raise ValueError("push: heat must be [k,%d,%d,%d] with k >= 1, got %s" % (tuple(heat_size) + (N_JOINTS, tuple(heat.shape))))
+    for name, x, shape in (("depth", depth, (k, N_JOINTS)), ("est_local", est_local, (k, N_JOINTS, 3)), ("rows", rows, (k, 8)),
+                           ("cams", cams, (k, 4, 4)), ("times", times, (k,))):
+        if x is not None and tuple(x.shape) != shape:
+            raise ValueError("push: %s must be %s for these %d frames, got %s" % (name, list(shape), k, tuple(x.shape)))
+    t = rows[:, 0] if rows is not None else times
+    t = np.ascontiguousarray(t.detach().cpu().numpy() if torch.is_tensor(t) else t, dtype=np.float64)
+    chain = t if n_pushed_times is None else np.concatenate([[n_pushed_times], t])
+    if not np.isfinite(t).all() or not (np.diff(chain) > 0).all():
+        raise ValueError("push: timestamps must be finite and increase strictly")
+    return k, t, (heat, depth, est_local, rows, cams)
+
+
+class LiveOptimizer:
+    """One live session on the current device.
+
+    weights: the arguments of `SequenceOptimizer.stage_weights` (default: DEFAULT_WEIGHTS, the defaults of `whole_sequence`).
+    bone: "running" -- every window is given the mean, over all frames pushed up to and including its last one, of the float32 lifted
+      skeleton's bone lengths (the reference takes the chunk's mean, optimizer.py:42-43; a stream has no chunk) -- or an array [15]: a
+      calibrated value.
+    one_euro: None, or (min_cutoff, beta, d_cutoff): the causal filter over the 45 coordinates of `optimized`, after the merge, with
+      the frames' own timestamps; its state is carried across windows and across `flush()`.
+    eps: None -- torch.randn(2, D) per window (local stage, then global) from a generator seeded by `seed` -- or callable(w) -> [2,D].
+    graphs: replay one captured `optimize_windows` call for every window (the window's inputs lie in buffers of fixed address).
+    scale: the SLAM scale applied to the translations of `rows=`.
+    """
+
+    def __init__(self, camera_model_path, global_vae=GLOBAL_VAE_PATH, local_vae=LOCAL_VAE_PATH, *, scale=1.0, weights=None, bone="running",
+                 one_euro=None, eps=None, seed=0, graphs=True, lr=2, max_iter=25, heat_size=(64, 64)):
+        sd_g, sd_l = _as_state_dict(global_vae), _as_state_dict(local_vae)
+        shape = infer_shape(sd_l, seq_len=SEQ_LEN)
+        if infer_shape(sd_g, seq_len=SEQ_LEN) != shape:
+            raise RuntimeError("local and global VAE checkpoints have different architectures")
+        if one_euro is not None:
+            one_euro = tuple(float(v) for v in one_euro)
+            if len(one_euro) == 2:
+                one_euro += (1.0,)
+            if len(one_euro) != 3 or not all(np.isfinite(v) and v >= 0 for v in one_euro) or one_euro[0] <= 0 or one_euro[2] <= 0:
+                raise ValueError("one_euro is (min_cutoff > 0, beta >= 0, d_cutoff > 0), got %r" % (one_euro,))
+        self.one_euro, self.scale = one_euro, float(scale)
+        self.engine = e = WindowEngine(shape, FisheyeCamera.from_json(camera_model_path), max_windows=1, heat_size=heat_size)
+        e.load_vae(LOCAL_STAGE, sd_l)
+        e.load_vae(GLOBAL_STAGE, sd_g)
+        if graphs:
+            e.enable_graphs(True)
+        self.opts = _capi.default_lbfgs_opts(lr, max_iter)
+        self.w_local, self.w_global = SequenceOptimizer.stage_weights(None, **dict(DEFAULT_WEIGHTS, **(weights or {})))          # (the method reads no attribute)
+        dev, H, W = e.device, e.heat_size[0], e.heat_size[1]
+        self._bone_fixed = None
+        if not (isinstance(bone, str) and bone == "running"):
+            b = np.asarray(bone, dtype=np.float32)
+            if b.shape != (N_JOINTS,):
+                raise ValueError('bone is "running" or an array of %d bone lengths' % N_JOINTS)
+            self._bone_fixed = torch.from_numpy(b.copy()).to(dev)
+        self._eps, self._gen = eps, torch.Generator().manual_seed(int(seed))
+        # the session's device memory: rings + state, the window buffers of fixed address, the call's small inputs, the output block
+        self._bufs = e.live_buffers()
+        self._win_pose = torch.zeros(SEQ_LEN, N_JOINTS, 3, device=dev, dtype=torch.float32)
+        self._win_cams = torch.zeros(SEQ_LEN, 4, 4, device=dev, dtype=torch.float64)
+        self._win_heat = torch.zeros(SEQ_LEN, H, W, N_JOINTS, device=dev, dtype=torch.float32)
+        self._frame0 = torch.zeros(1, device=dev, dtype=torch.int32)
+        self._mean_bone = torch.zeros(1, N_JOINTS, device=dev, dtype=torch.float32)
+        self._eps_l, self._eps_g = (torch.zeros(1, e.D, device=dev, dtype=torch.float32) for _ in range(2))
+        self._out = torch.zeros(2, STRIDE, N_JOINTS, 3, device=dev, dtype=torch.float64)
+        self.n_pushed = self.n_windows = self.n_emitted = 0
+        self._last_time, self._row0, self._flushed = None, None, False
+        self.window_log, self._optimized, self._estimated = [], [], []
+
+    # ------------------------------------------------------------------ state
+    def close(self):
+        """Releases the engine and the session's device memory; `push` and `flush` raise GemError afterwards."""
+        if self.engine is not None:
+            torch.cuda.synchronize(self.engine.device)
+            self.engine.close()
+        self.engine = self._bufs = self._win_pose = self._win_cams = self._win_heat = self._out = None
+        self._mean_bone = self._eps_l = self._eps_g = self._frame0 = self._bone_fixed = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def graph_stats(self):
+        return self._engine().graph_stats()
+
+    def _engine(self):
+        if self.engine is None:
+            raise _capi.GemError("this live session has been closed")
+        return self.engine
+
+    def result(self):
+        """Everything emitted so far: {"frames": 0, "optimized", "estimated"} with numpy f64 arrays [n_emitted,15,3]."""
+        cat = lambda parts: np.concatenate(parts) if parts else np.empty((0, N_JOINTS, 3))          # noqa: E731
+        return {"frames": 0, "optimized": cat(self._optimized), "estimated": cat(self._estimated)}
+
+    def save_pose(self, out_dir):
+        """`<out_dir>/result_pose.pkl` with `estimated_pose` and `optimized_pose` (lists of [15,3] frames): the schema of the
+        no-ground-truth `--save_pose`, minus the mid sequence that live mode does not produce; `render` and `meshes` read it."""
+        os.makedirs(out_dir, exist_ok=True)
+        r = self.result()
+        path = os.path.join(out_dir, "result_pose.pkl")
+        with open(path, "wb") as f:
+            pickle.dump({"estimated_pose": list(r["estimated"]), "optimized_pose": list(r["optimized"])}, f)
+        return path
+
+    # ------------------------------------------------------------------ frames in
+    def _device(self, x, dtype):
+        t = x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x))
+        return t.to(device=self.engine.device, dtype=dtype).contiguous()
+
+    def _cameras(self, rows):
+        """Trajectory rows -> cameras in the session's frame: `slam.scaled_trajectory` of (the session's first row, these rows)."""
+        from . import slam
+        rows = np.ascontiguousarray(rows.detach().cpu().numpy() if torch.is_tensor(rows) else rows, dtype=np.float64)
+        if self._row0 is None:
+            self._row0 = rows[:1].copy()
+        both = np.concatenate([self._row0, rows])
+        return slam.scaled_trajectory(both[:, 1:4], both[:, 4:8], self.scale)[1:]
+
+    def push(self, *, heat=None, depth=None, est_local=None, rows=None, cams=None, times=None):
+        """k >= 1 new frames: heat [k,H,W,15]; either depth [k,15] (lifted with `WindowEngine.lift_skeleton`) or est_local [k,15,3]
+        (already lifted); either rows [k,8] trajectory rows `time tx ty tz qx qy qz qw` (made cameras by `slam`'s functions, relative
+        to the session's first frame, translations times `scale`) or cams [k,4,4] with times [k].  Host or device arrays.  Every window
+        these frames complete is optimised at once; the call blocks until they are done, reads their statistics and raises the
+        reference's Exception("norm is zero!") for a degenerate one.  -> {"frames": index of the first returned frame, "optimized",
+        "estimated"}: numpy f64 [m,15,3], m = 8 x the windows completed (possibly 0).  ValueError (before anything is enqueued) for
+        timestamps that do not increase strictly, wrong shapes, or contradictory arguments."""
+        e = self._engine()
+        if self._flushed:
+            raise _capi.GemError("this live session has been flushed: its held frames are out, a new stream needs a new session")
+        k, t, (heat, depth, est_local, rows, cams) = check_push(self._last_time, heat, depth, est_local, rows, cams, times, e.heat_size)
+        heat_d = self._device(heat, torch.float32)
+        pose_d = self._device(est_local, torch.float32) if est_local is not None else e.lift_skeleton(heat_d, depth, want_f64=False)[1]
+        cams_d = self._device(self._cameras(rows) if rows is not None else cams, torch.float64)
+        times_d = self._device(t, torch.float64)
+        self._last_time = float(t[-1])
+        first, done = self.n_emitted, []
+        for a, b in _pieces(self.n_pushed, k):
+            t0 = time.perf_counter()
+            e.live_push(self._bufs, self.n_pushed, self.n_windows * STRIDE, heat_d[a:b], pose_d[a:b], cams_d[a:b], times_d[a:b])
+            self.n_pushed += b - a
+            if self.n_pushed == self.n_windows * STRIDE + SEQ_LEN:
+                done.append(self._window(t0))
+        return self._emitted(first, done, STRIDE)
+
+    def _window(self, t0):
+        """Window self.n_windows is complete: gather, optimise (both stages, B = 1), emit; blocks on the statistics."""
+        e, w = self.engine, self.n_windows
+        e.live_window(self._bufs, w, self.n_pushed, self._win_pose, self._win_cams, self._win_heat, self._mean_bone, self._bone_fixed)
+        eps = self._eps(w) if self._eps is not None else torch.randn(2, e.D, generator=self._gen)
+        eps = torch.as_tensor(np.asarray(eps) if not torch.is_tensor(eps) else eps, dtype=torch.float32).reshape(2, e.D)
+        self._eps_l.copy_(eps[0:1])
+        self._eps_g.copy_(eps[1:2])
+        _, glob, stats = e.optimize_windows(self._win_pose, self._win_cams, self._win_heat, self._frame0, self._mean_bone, self._eps_l,
+                                            self._eps_g, self.w_local, self.w_global, self.opts)
+        e.live_emit(self._bufs, w, self._out, glob, self._win_pose, self._win_cams, one_euro=self.one_euro)
+        out = self._out.cpu().numpy()                                   # (behind the emit kernel: the window is done)
+        st = stats_to_numpy(stats)
+        self.window_log.append({"window": w, "local": st[0].copy(), "global": st[1].copy(), "mean_bone": self._mean_bone[0].cpu().numpy(),
+                                "step_ms": (time.perf_counter() - t0) * 1e3})
+        self.n_windows += 1
+        raise_if_degenerate(st)
+        return out
+
+    def _emitted(self, first, done, n):
+        opt = np.concatenate([o[0, :n] for o in done]) if done else np.empty((0, N_JOINTS, 3))
+        est = np.concatenate([o[1, :n] for o in done]) if done else np.empty((0, N_JOINTS, 3))
+        if done:
+            self._optimized.append(opt)
+            self._estimated.append(est)
+            self.n_emitted += len(opt)
+        return {"frames": first, "optimized": opt, "estimated": est}
+
+    def flush(self):
+        """The end of the stream: emits the two frames still held, as they are (`merge_batches`' last window; filtered when the filter
+        is on), and reports as "dropped" how many pushed frames belonged to no complete window.  -> push's dict plus "dropped"."""
+        e = self._engine()
+        first, done = self.n_emitted, []
+        if self.n_windows and not self._flushed:
+            e.live_emit(self._bufs, self.n_windows, self._out, final=True, one_euro=self.one_euro)
+            done.append(self._out.cpu().numpy())
+        self._flushed = True
+        return dict(self._emitted(first, done, OVERLAP), dropped=dropped_frames(self.n_pushed))
+
+
+# ---------------------------------------------------------------------------------------------------------------------- replay
+def step_summary(window_log):
+    """Median / 99th percentile / maximum of the per-window step times (ms) and the L-BFGS counts of a session's `window_log`."""
+    if not window_log:
+        return {"windows": 0}
+    ms = np.array([r["step_ms"] for r in window_log])
+    out = {"windows": len(ms), "step_ms_median": float(np.median(ms)), "step_ms_p99": float(np.percentile(ms, 99)), "step_ms_max": float(ms.max())}
+    for stage in ("local", "global"):
+        out[stage + "_iters_mean"] = float(np.mean([r[stage]["n_iter"] for r in window_log]))
+        out[stage + "_evals_mean"] = float(np.mean([r[stage]["func_evals"] for r in window_log]))
+    return out
+
+
+def replay(slam_result_path, heatmap_dir, depth_dir, start_frame, end_frame, camera_model_path, fps=25, pace="max", save_pose=None,
+           verbose=True, **session):
+    """A prepared recording pushed through a `LiveOptimizer` one frame at a time: the frames [start_frame, end_frame) of the listings
+    come to the device with `prepare`'s reader, the trajectory's rows of those frame ids are the cameras.  pace "realtime" sleeps to
+    the timestamps, "max" does not.  `session`: the keyword arguments of `LiveOptimizer`.  -> (result dict with "dropped", the
+    session's window_log).  A replay of a recording: a rig calls `push` itself."""
+    from . import prepare, slam
+    if pace not in ("max", "realtime"):
+        raise ValueError('pace is "max" or "realtime"')
+    with open(slam_result_path) as f:
+        rows = slam.trajectory_rows(f.read())
+    prepare.check_trajectory(rows, start_frame, end_frame, fps)
+    ids = slam.frame_ids(rows, fps)
+    rows = rows[(ids >= start_frame) & (ids < end_frame)]
+    heat_paths, depth_paths = prepare.list_frames(heatmap_dir, start_frame, end_frame), prepare.list_frames(depth_dir, start_frame, end_frame)
+    if len(heat_paths) != end_frame - start_frame or len(depth_paths) != end_frame - start_frame:
+        raise ValueError("frames [%d, %d) of the listings are asked for, but there are %d heat-map and %d depth files"
+                         % (start_frame, end_frame, len(heat_paths), len(depth_paths)))
+    heat, depth, _ = prepare.frames_to_device(heat_paths, depth_paths)
+    live = LiveOptimizer(camera_model_path, heat_size=tuple(heat.shape[1:3]), **session)
+    try:
+        wall0 = time.perf_counter()
+        for i in range(len(rows)):
+            if pace == "realtime":
+                wait = (rows[i, 0] - rows[0, 0]) - (time.perf_counter() - wall0)
+                if wait > 0:
+                    time.sleep(wait)
+            live.push(heat=heat[i:i + 1], depth=depth[i:i + 1], rows=rows[i:i + 1])
+        tail = live.flush()
+        res = dict(live.result(), dropped=tail["dropped"])
+        if save_pose is not None:
+            live.save_pose(save_pose)
+        if verbose:
+            s = step_summary(live.window_log)
+            print("live: {} frames pushed, {} emitted, {} dropped, {} windows".format(live.n_pushed, live.n_emitted, tail["dropped"], s["windows"]))
+            if s["windows"]:
+                print("step time per window (ms): median {:.3f}, 99th percentile {:.3f}, max {:.3f}; budget {:.1f} ms at {:g} fps".format(
+                    s["step_ms_median"], s["step_ms_p99"], s["step_ms_max"], 1e3 * STRIDE / fps, fps))
+                print("L-BFGS per window: local {:.1f} iterations / {:.1f} evaluations, global {:.1f} / {:.1f}".format(
+                    s["local_iters_mean"], s["local_evals_mean"], s["global_iters_mean"], s["global_evals_mean"]))
+        return res, live.window_log
+    finally:
+        live.close()
+
+
+def _one_euro_arg(text):
+    v = tuple(float(x) for x in text.split(","))
+    if len(v) not in (2, 3):
+        raise ValueError("--one_euro takes MIN,BETA[,DCUT]")
+    return v if len(v) == 3 else v + (1.0,)
+
+
+def _bone_arg(text):
+    return text if text == "running" else np.load(text)
+
+
+def _parser():
+    import argparse
+    from .camera import DEFAULT_CALIBRATION
+    p = argparse.ArgumentParser(description="Replay a prepared recording through live mode, one frame at a time. This replays a "
+                                            "recording; a head-mounted rig calls LiveOptimizer.push itself.")
+    p.add_argument("--slam", required=True, metavar="TRAJ", help="the trajectory: lines `time tx ty tz qx qy qz qw`")
+    p.add_argument("--heatmaps", required=True, metavar="DIR")
+    p.add_argument("--depths", required=True, metavar="DIR")
+    p.add_argument("--scale", type=float, default=1.0, help="the SLAM scale applied to the trajectory's translations")
+    p.add_argument("--start", type=int, required=True, metavar="A")
+    p.add_argument("--end", type=int, required=True, metavar="B")
+    p.add_argument("--fps", type=float, default=25)
+    p.add_argument("--pace", choices=("max", "realtime"), default="max", help="realtime: sleep to the frames' timestamps")
+    p.add_argument("--one_euro", type=_one_euro_arg, default=None, metavar="MIN,BETA[,DCUT]", help="the causal One-Euro filter over the optimised poses (default: off)")
+    p.add_argument("--bone", type=_bone_arg, default="running", metavar="running|FILE.npy", help="mean bone lengths: the running mean, or 15 calibrated values")
+    p.add_argument("--save_pose", default=None, metavar="DIR", help="write DIR/result_pose.pkl (estimated_pose, optimized_pose)")
+    p.add_argument("--camera", type=str, default=DEFAULT_CALIBRATION)
+    p.add_argument("--global_vae", type=str, default=GLOBAL_VAE_PATH)
+    p.add_argument("--local_vae", type=str, default=LOCAL_VAE_PATH)
+    p.add_argument("--vae", type=float, default=DEFAULT_WEIGHTS["vae_weight"])
+    p.add_argument("--smooth", type=float, default=DEFAULT_WEIGHTS["smoothness_weight"])
+    p.add_argument("--bone_length", type=float, default=DEFAULT_WEIGHTS["bone_length_weight"])
+    p.add_argument("--weight_3d", type=float, default=DEFAULT_WEIGHTS["weight_3d"])
+    p.add_argument("--reproj_weight", type=float, default=DEFAULT_WEIGHTS["reproj_weight"])
+    p.add_argument("--seed", type=int, default=0)
+    return p
+
+
+def _cli(argv=None):
+    a = _parser().parse_args(argv)
+    weights = dict(vae_weight=a.vae, smoothness_weight=a.smooth, bone_length_weight=a.bone_length, weight_3d=a.weight_3d,
+                   reproj_weight=a.reproj_weight)
+    replay(a.slam, a.heatmaps, a.depths, a.start, a.end, a.camera, fps=a.fps, pace=a.pace, save_pose=a.save_pose, global_vae=a.global_vae,
+           local_vae=a.local_vae, scale=a.scale, weights=weights, bone=a.bone, one_euro=a.one_euro, seed=a.seed)
+
+
+if __name__ == "__main__":
+    _cli()

@@ -606,6 +606,60 @@ int gem_latent_paths(const float* d_za, const float* d_zb, int64_t n_pairs, int 
 int gem_latent_report(const float* d_mu, const float* d_logvar, const float* d_x, const float* d_rec, int64_t n_windows, int latent_dim,
                       int n_coords, int n_joints, double* d_rows, double* d_cols, int64_t* d_count, void* stream);
 
+/* ---- Live mode: a stream optimised window by window as its frames arrive ----
+ * Frames are numbered n = 0, 1, 2, ... in arrival order; window w covers the frames [8w, 8w + 10) (seq_len 10, overlap 2: the
+ * handle must have been made with seq_len = GEM_LIVE_WINDOW).  All memory is the caller's: the frame rings of GEM_LIVE_RING frames
+ * (frame n lives in slot n mod GEM_LIVE_RING) and one block of GEM_LIVE_STATE_DOUBLES doubles that the caller zeroes once:
+ *     0..15   sum over the pushed frames of every joint's bone length (the f32 length, added in frame order)
+ *     16      the number of frames in those sums      17  frames pushed      18  windows emitted      19  frames emitted
+ *     20      t_prev of the filter                     21  1 once the filter has seen a frame
+ *     22..23  the timestamps of the two held frames    24  1 while two frames are held
+ *     32..79  x_prev [48]     80..127  dx_prev [48]     128..223  held optimised frames [2][48]     224..319  held estimated frames [2][48]
+ * The four launch functions allocate nothing, copy nothing to the host and never synchronise; the host passes the stream position
+ * (first_frame, n_pushed, window) because it knows it, and the functions check it against the ring before they launch.
+ *
+ * gem_live_push: k <= GEM_LIVE_PUSH_MAX frames (d_heat [k,H,W,J] f32, d_pose [k,J,3] f32 the lifted local skeleton, d_cams [k,4,4] f64,
+ * d_times [k] f64) become the frames first_frame .. first_frame + k - 1 of the rings, and their bone lengths are added to the sums.
+ * oldest_needed: the oldest frame a window still to come reads; a push that would overwrite it is refused.
+ *
+ * gem_live_window: the frames of window `window` from the rings into the buffers of fixed address that the optimiser's call reads
+ * (d_win_pose [10,J,3] f32, d_win_cams [10,4,4] f64, d_win_heat [10,H,W,J] f32), and d_mean_bone [J] f32: d_bone_fixed when given, else
+ * the running mean (f64 sum / count, rounded once).  n_pushed: frames pushed so far; the window must be complete and still in the rings.
+ *
+ * gem_live_emit: d_global [10,J,3] f64 is the window's result (gem_optimize_windows with B = 1 on the window buffers).  Writes
+ * d_out [2][8][J*3] f64: the 8 frames [8w, 8w + 8) of the optimised sequence -- its first two (w > 0) the held frames plus the
+ * window's, halved -- and of the estimated one, cams . pose in f64; holds the window's last two frames.  final != 0: writes the two
+ * held frames to d_out [2][0..1] instead and releases them (d_global, d_win_pose, d_win_cams are not read).  h_one_euro (host, 3
+ * doubles: min_cutoff, beta, d_cutoff; or NULL: off): the optimised frames pass the One-Euro filter in frame order, per coordinate,
+ * with the frames' own timestamps; its state lives in the state block.
+ *
+ * gem_one_euro: the same filter over whole sequences.  d_seq [n_chunks*frames_per_chunk, n_coords] f64, d_times [n_chunks*frames_per_chunk]
+ * f64 -> d_out of d_seq's shape; every chunk starts with fresh state (its first frame passes through).  The arithmetic is the
+ * reference's utils/one_euro_filter.py in f64, operation by operation:
+ *     t_e = t - t_prev;  a_d = r / (r + 1) with r = 2 pi d_cutoff t_e;  dx = (x - x_prev) / t_e;  dx_hat = a_d dx + (1 - a_d) dx_prev;
+ *     cutoff = min_cutoff + beta |dx_hat|;  a likewise from cutoff;  x_hat = a x + (1 - a) x_prev.
+ * Timestamps must increase strictly (the caller checks: the device never reports). */
+#define GEM_LIVE_WINDOW 10
+#define GEM_LIVE_STRIDE 8
+#define GEM_LIVE_RING 32
+#define GEM_LIVE_PUSH_MAX 8
+#define GEM_LIVE_STATE_DOUBLES 320
+typedef struct gem_live_buffers {
+    float* ring_pose;      /* [GEM_LIVE_RING,J,3] */
+    double* ring_cams;     /* [GEM_LIVE_RING,4,4] */
+    double* ring_times;    /* [GEM_LIVE_RING] */
+    float* ring_heat;      /* [GEM_LIVE_RING,H,W,J] */
+    double* state;         /* [GEM_LIVE_STATE_DOUBLES] */
+} gem_live_buffers;
+int gem_live_push(gem_handle* h, const gem_live_buffers* b, int64_t first_frame, int k, int64_t oldest_needed, const float* d_heat,
+                  const float* d_pose, const double* d_cams, const double* d_times, void* stream);
+int gem_live_window(gem_handle* h, const gem_live_buffers* b, int64_t window, int64_t n_pushed, const float* d_bone_fixed,
+                    float* d_win_pose, double* d_win_cams, float* d_win_heat, float* d_mean_bone, void* stream);
+int gem_live_emit(gem_handle* h, const gem_live_buffers* b, int64_t window, int final, const double* d_global, const float* d_win_pose,
+                  const double* d_win_cams, const double* h_one_euro, double* d_out, void* stream);
+int gem_one_euro(const double* d_seq, const double* d_times, int n_chunks, int64_t frames_per_chunk, int n_coords, const double* h_params,
+                 double* d_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

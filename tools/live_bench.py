@@ -1,0 +1,193 @@
+#!/usr/bin/env python3
+"""What live mode costs per window, one JSON line per variant.  Runs ON THE GPU BOX.
+
+    python tools/live_bench.py [--frames 1000] [--fit-steps 2000] [--precisions f32 bf16] [--out profiles/live_bench.json]
+
+Full-size synthetic VAEs fitted as bench.py fits them (its `fit_weights`, seeds 101 / 102), a stream of `--frames` synthetic frames
+resident on the device (`synth.make_sequence_device`, bench.py's camera noise), pushed ONE frame at a time through a `LiveOptimizer`
+(graphs on, running bone length).  Per variant (the fp32 path and the bf16 decoder mode):
+
+  `step_ms`         host-clock time of every push that completes a window: median, 99th percentile, maximum.  The push ends in the
+                    read-back of the window's result and statistics, so the time is synchronised.
+  `push_ms`         a push that completes no window, with a device synchronise behind it
+  `floor_ms`        the same window through a direct `optimize_windows` call with B = 1 and graphs on (a second engine, buffers of
+                    fixed address filled outside the timed region, the mean bone length the live session logged), ending in the
+                    same read-back of the statistics.  Alternating with the live pushes, in the same process.
+  `bookkeeping_ms`  median step - median floor: what live mode adds around the optimiser's call (the completing push, the window
+                    gather, the emit kernel, the result's read-back), and the same in percent of the floor
+  `headroom`        the budget 8 / fps = 320 ms at 25 fps over the median step
+  `offline_diff_mm` the largest difference between a live session's output (filter off, the chunk's mean bone length) and the offline
+                    route on the same frames as one chunk: `SequenceOptimizer.run` on all windows at once, `merge_batches`, no final
+                    smoothing.  B = 1 and B = 124 may choose different GEMM slices: an observation, not an assertion.
+
+The parent process never opens the GPU: the fit and every variant run in a fresh child process with a time limit of its own, once,
+and nothing is started after a child that failed.
+"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+
+FPS, SEED = 25, 3100
+LIMITS = {"fit": 600, "variant": 300}          # seconds per child
+
+
+def pct(a):
+    a = np.asarray(a, dtype=np.float64)
+    return {"median": float(np.median(a)), "p99": float(np.percentile(a, 99)), "max": float(a.max()), "n": int(a.size)}
+
+
+def child_fit(a):
+    import torch
+    import bench
+    from globalegomocap_amd import vae as vae_schema
+    dev = torch.device("cuda", 0)
+    t = time.perf_counter()
+    wait = bench.fit_weights_in_child(102, 0, a.fit_steps, True)
+    sd_l, err_l = bench.fit_weights(vae_schema.VAEShape(), 101, dev, a.fit_steps, relative=False)
+    sd_g, err_g = wait()
+    torch.save((sd_l, err_l, sd_g, err_g), a.weights)
+    print(json.dumps({"leg": "fit", "fit_steps": a.fit_steps, "recon_mm": [err_l * 1e3, err_g * 1e3], "seconds": time.perf_counter() - t}), flush=True)
+
+
+def child_variant(a):
+    import torch
+    import bench
+    from globalegomocap_amd import synth
+    from globalegomocap_amd.camera import FisheyeCamera, DEFAULT_CALIBRATION
+    from globalegomocap_amd.engine import WindowEngine, stats_to_numpy
+    from globalegomocap_amd.live import LiveOptimizer, STRIDE
+    from globalegomocap_amd.optimizer import SequenceOptimizer
+    from globalegomocap_amd.sequence import window_starts, merge_batches
+    torch.cuda.set_device(0)
+    dev = torch.device("cuda", 0)
+    sd_l, _, sd_g, _ = torch.load(a.weights, weights_only=False)
+    cam = FisheyeCamera.from_json(DEFAULT_CALIBRATION)
+    n = a.frames
+    seq = synth.make_sequence_device(n, seed=SEED, device=dev, camera=cam, cam_jitter=bench.CAM_JITTER)
+    est, cams, heat = seq["est_local"], seq["cams"], seq["heat"]
+    rng = np.random.default_rng(SEED)
+    times = np.arange(n) / FPS + rng.uniform(-0.004, 0.004, n)          # on the host, where a rig's clock is
+    starts = window_starts(n)
+    B = len(starts)
+    eps = torch.randn(B, 2, 2048, generator=torch.Generator().manual_seed(SEED))
+
+    # ---- the timed session and, alternating with it, the floor
+    live = LiveOptimizer(DEFAULT_CALIBRATION, sd_g, sd_l, eps=lambda w: eps[w], graphs=True)
+    live.engine.set_precision(a.variant)
+    floor = WindowEngine(live.engine.shape, cam, max_windows=1)
+    floor.load_vae(0, sd_l)
+    floor.load_vae(1, sd_g)
+    floor.set_precision(a.variant)
+    floor.enable_graphs(True)
+    fb = {"pose": torch.zeros(10, 15, 3, device=dev), "cams": torch.zeros(10, 4, 4, device=dev, dtype=torch.float64),
+          "heat": torch.zeros(10, 64, 64, 15, device=dev), "f0": torch.zeros(1, device=dev, dtype=torch.int32),
+          "mb": torch.zeros(1, 15, device=dev), "el": torch.zeros(1, 2048, device=dev), "eg": torch.zeros(1, 2048, device=dev)}
+    step_ms, push_ms, floor_ms, mismatches = [], [], [], 0          # mismatches: windows on which the floor ran another optimisation
+    for i in range(n):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        got = live.push(heat=heat[i:i + 1], est_local=est[i:i + 1], cams=cams[i:i + 1], times=times[i:i + 1])
+        if not len(got["optimized"]):
+            torch.cuda.synchronize()
+            push_ms.append((time.perf_counter() - t0) * 1e3)
+            continue
+        step_ms.append((time.perf_counter() - t0) * 1e3)
+        w = live.n_windows - 1
+        sl = slice(STRIDE * w, STRIDE * w + 10)
+        fb["pose"].copy_(est[sl]); fb["cams"].copy_(cams[sl]); fb["heat"].copy_(heat[sl])          # noqa: E702
+        fb["mb"].copy_(torch.from_numpy(live.window_log[w]["mean_bone"]).reshape(1, 15))
+        fb["el"].copy_(eps[w, 0:1]); fb["eg"].copy_(eps[w, 1:2])          # noqa: E702
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        _, _, st = floor.optimize_windows(fb["pose"], fb["cams"], fb["heat"], fb["f0"], fb["mb"], fb["el"], fb["eg"], live.w_local, live.w_global,
+                                          live.opts)
+        st = stats_to_numpy(st)
+        floor_ms.append((time.perf_counter() - t0) * 1e3)
+        row = live.window_log[w]
+        mismatches += int((st["func_evals"] != [row["local"]["func_evals"], row["global"]["func_evals"]]).any())
+    live.flush()
+    log, gs, gs_floor = live.window_log, live.graph_stats(), floor.graph_stats()
+    live.close()
+    floor.close()
+    # (the first two windows run eagerly and capture the graph: left out of the percentiles, reported beside them)
+    steady, steady_floor = step_ms[2:], floor_ms[2:]
+    rec = {"leg": a.variant, "frames": n, "windows": len(step_ms), "fps": FPS, "graphs": gs, "graphs_floor": gs_floor,
+           "step_ms": pct(steady), "floor_ms": pct(steady_floor), "push_ms": pct(push_ms), "first_two_steps_ms": step_ms[:2], "floor_mismatches": mismatches,
+           "local_evals_mean": float(np.mean([r["local"]["func_evals"] for r in log])),
+           "global_evals_mean": float(np.mean([r["global"]["func_evals"] for r in log]))}
+    book = rec["step_ms"]["median"] - rec["floor_ms"]["median"]
+    rec["bookkeeping_ms"], rec["bookkeeping_percent"] = book, 100.0 * book / rec["floor_ms"]["median"]
+    rec["budget_ms"] = 1e3 * STRIDE / FPS
+    rec["headroom"] = rec["budget_ms"] / rec["step_ms"]["median"]
+
+    # ---- live against the offline route on the same frames as one chunk (untimed)
+    off = SequenceOptimizer(DEFAULT_CALIBRATION, sd_g, sd_l, max_windows=B)
+    off.engine.set_precision(a.variant)
+    bone = off.engine.mean_bone_length(est).cpu().numpy()
+    est_np, cams_np = seq["est_local_np"], seq["cams_np"]
+    _, glob, _ = off.run(est_np, cams_np, heat, starts, np.zeros(B, dtype=np.int64), [(0, n)], live.w_local, live.w_global, eps=eps.reshape(2 * B, -1))
+    offline = np.asarray(merge_batches(glob, 2))
+    off.engine.close()
+    live = LiveOptimizer(DEFAULT_CALIBRATION, sd_g, sd_l, eps=lambda w: eps[w], graphs=True, bone=bone)
+    live.engine.set_precision(a.variant)
+    for i in range(0, n, STRIDE):
+        live.push(heat=heat[i:i + STRIDE], est_local=est[i:i + STRIDE], cams=cams[i:i + STRIDE], times=times[i:i + STRIDE])
+    tail = live.flush()
+    got = live.result()["optimized"]
+    live.close()
+    d = np.linalg.norm(got - offline[:len(got)], axis=-1)
+    rec.update(offline_windows=B, offline_frames=int(len(offline)), live_frames=int(len(got)), dropped=tail["dropped"],
+               offline_diff_mm={"max": float(d.max() * 1e3), "median": float(np.median(d) * 1e3), "frames_beyond_1mm": int((d.max(axis=1) > 1e-3).sum())})
+    print(json.dumps(rec), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--frames", type=int, default=1000)
+    ap.add_argument("--fit-steps", type=int, default=2000)
+    ap.add_argument("--precisions", nargs="+", default=["f32", "bf16"], choices=["f32", "bf16x3", "bf16"])
+    ap.add_argument("--out", default=None, help="also write the records, as one JSON document, to this file")
+    ap.add_argument("--weights", default=None, help=argparse.SUPPRESS)
+    ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
+    ap.add_argument("--variant", default=None, help=argparse.SUPPRESS)
+    a = ap.parse_args()
+    if a.child == "fit":
+        return child_fit(a)
+    if a.child == "variant":
+        return child_variant(a)
+    records = []
+    with tempfile.TemporaryDirectory(prefix="live_bench_") as tmp:
+        weights = os.path.join(tmp, "vae.pt")
+        base = [sys.executable, os.path.abspath(__file__), "--frames", str(a.frames), "--fit-steps", str(a.fit_steps), "--weights", weights]
+        legs = [("fit", ["--child", "fit"], LIMITS["fit"])] + [(p, ["--child", "variant", "--variant", p], LIMITS["variant"]) for p in a.precisions]
+        for name, extra, limit in legs:
+            try:
+                r = subprocess.run(base + extra, stdout=subprocess.PIPE, text=True, timeout=limit, cwd=REPO)
+            except subprocess.TimeoutExpired:
+                print(json.dumps({"leg": name, "error": "time limit of %d s" % limit}), flush=True)
+                return 1
+            lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+            for l in lines:
+                print(l, flush=True)
+                records.append(json.loads(l))
+            if r.returncode != 0 or not lines:
+                print(json.dumps({"leg": name, "error": "exit status %d" % r.returncode}), flush=True)
+                return 1          # nothing more is started on the device after a leg that failed
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump({"tool": "tools/live_bench.py", "records": records}, f, indent=1)
+            f.write("\n")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
