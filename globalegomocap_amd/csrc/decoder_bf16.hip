@@ -102,11 +102,11 @@ static bool big_fits(const Layer& L, int epi, bool out_bf16) {
     return false;
 }
 static int launch_big(gem_handle* h, const Layer& L, int epi, const uint16_t* A, int lda, void* C, int ldc, int M, hipStream_t s,
-                      const int* row_map, int m_min) {
+                      const GemmOpts& o, int m_min) {
     Workspace& w = h->ws;
     big::Args a{};
     a.A = A; a.W = L.wb_hi; a.bias = L.bias; a.C = C; a.zero16 = w.zero16;
-    a.m_dev = w.dyn ? w.n_active : nullptr; a.row_map = row_map;
+    a.m_dev = o.rs ? o.rs->n_active : nullptr; a.row_map = o.row_map;
     a.lda = lda; a.ldc = ldc; a.M = M; a.N = L.N; a.K = L.K; a.m_min = m_min;
     static PerDeviceOnce once;
     if (once.need(h->cfg.device)) {
@@ -126,22 +126,23 @@ static int launch_big(gem_handle* h, const Layer& L, int epi, const uint16_t* A,
 }
 
 // C = epi(conv/linear(A)) with bf16 operands.  `out_bf16`: activation / gradient for the next bf16 layer; otherwise fp32.
-// allow_split: small row counts cut K over several workgroups (fp32 slabs in ws.splitk); with `defer` the slabs are left to
-// the consumer (described in ws.deferred), otherwise a reduce pass applies the epilogue.
+// allow_split: small row counts cut K over several workgroups (fp32 slabs in ws.splitk); with o.defer the slabs are left to
+// the consumer (described in *o.defer), otherwise a reduce pass applies the epilogue.
 static int gemm_bf16a(gem_handle* h, const Layer& L, int epi, const uint16_t* A, int lda, const uint16_t* aux, void* C, bool out_bf16,
-                      int ldc, int M, hipStream_t s, int family, const int* row_map, bool allow_split, bool defer) {
+                      int ldc, int M, hipStream_t s, int family, bool allow_split, const GemmOpts& o = GemmOpts()) {
     Workspace& w = h->ws;
+    if (o.defer) *o.defer = SlabSrc{};
     if (M <= 0) return 0;
     if (L.K % 64 != 0 || L.N % 64 != 0 || !L.wb_hi) { set_error("gemm_bf16a: layer is not padded to 64 or has no bf16 weights"); return 1; }
-    w.deferred = SlabSrc{};
+    if (o.repack_log) { set_error("gemm_bf16a: fused compaction on a launch that cannot carry it"); return 1; }
     const bool bn128 = L.N % 128 == 0;
     const int BN = bn128 ? 128 : 64;
     const int tiles = ((M + 127) / 128) * (L.N / BN);
     const int k_tiles = L.taps * (L.K / 64);
     Args a{};
     a.A = A; a.W = L.wb_hi; a.bias = L.bias; a.aux = aux; a.C = C; a.zero16 = w.zero16;
-    a.m_dev = w.dyn ? w.n_active + (L.taps == 3 ? 1 : 0) : nullptr;
-    a.row_map = row_map;
+    a.m_dev = o.rs ? o.rs->n_active + (L.taps == 3 ? 1 : 0) : nullptr;
+    a.row_map = o.row_map;
     a.lda = lda; a.ldc = ldc; a.M = M; a.N = L.N; a.K = L.K; a.T = h->T;
     a.n_split = 1; a.tiles_per_split = k_tiles; a.slab_stride = (size_t)M * ldc;
     // the front products at large batch: gemm_big.h takes the launches with >= BIG_MIN_ROWS rows (family 0 only)
@@ -166,7 +167,7 @@ static int gemm_bf16a(gem_handle* h, const Layer& L, int epi, const uint16_t* A,
         GEM_HIP(hipEventCreate(&rec.a)); GEM_HIP(hipEventCreate(&rec.b));
         rec.family = family;
         rec.flops = 2.0 * M * (double)L.N * L.K * L.taps;
-        if (w.dyn && L.taps == 1) { rec.log_idx = w.cur_log; rec.flops_per_window = 2.0 * (double)L.N * L.K; }
+        if (o.rs && L.taps == 1) { rec.log_idx = o.rs->log_idx; rec.flops_per_window = 2.0 * (double)L.N * L.K; }
         GEM_HIP(hipEventRecord(rec.a, s));
     }
     const int grid = tiles * a.n_split;
@@ -174,9 +175,9 @@ static int gemm_bf16a(gem_handle* h, const Layer& L, int epi, const uint16_t* A,
     int rc = 1;
     if (use_big) {
         if (a.n_split != 1) { set_error("gemm_bf16a: the one-round kernel's row range must not be cut along K"); return 1; }
-        if (launch_big(h, L, epi, A, lda, C, ldc, M, s, row_map, w.dyn ? BIG_MIN_ROWS : 1)) return 1;
+        if (launch_big(h, L, epi, A, lda, C, ldc, M, s, o, o.rs ? BIG_MIN_ROWS : 1)) return 1;
     }
-    if (use_big && !w.dyn) {
+    if (use_big && !o.rs) {
         rc = 0;                    // the row count is known here: the big kernel alone
     } else
     if (L.taps == 1) {
@@ -194,8 +195,8 @@ static int gemm_bf16a(gem_handle* h, const Layer& L, int epi, const uint16_t* A,
     }
     if (rc) return rc;
     if (a.n_split > 1) {
-        if (defer) {
-            SlabSrc& d = w.deferred;
+        if (o.defer) {
+            SlabSrc& d = *o.defer;
             d.base = w.splitk; d.nslab = a.n_split; d.stride = a.slab_stride; d.dyn_W = 0; d.m_dev = a.m_dev;
         } else if (out_bf16) {
             const size_t n4 = (size_t)M * (L.N / 4);
@@ -214,147 +215,87 @@ static int gemm_bf16a(gem_handle* h, const Layer& L, int epi, const uint16_t* A,
     return 0;
 }
 
-// The rounds of a stage need no compact_kernel launch when every kernel of a round addresses its rows through perm / slot_of and
-// nothing depends on the ORDER of the slots: the composed front products (rows gathered through perm) + the fused bf16 tail (windows
-// independent of their position in a workgroup: test_bf16_tail_row_tile_variants_compute_the_same) + lbfgs_advance (slot_of).  The
-// batched narrow layers (taps = 3) read n_active[1] = rows and are not covered.
-bool bf16_rounds_take_slots_atomically(const gem_handle* h, int stage, int B) {
-    const StageNet& net = h->net[stage];
-    // (no cap on B: one same-address atomic per window and round is spread over the advance kernel's duration -- 8192 windows: 289.0 k
-    // against 282.3 k windows/s with compact_kernel's 12 us single-workgroup scan per round; 6144: +0.4 %)
-    (void)B;
-    if (h->precision != GEM_PRECISION_BF16) return false;
-    const char* t16_env = dev_env("GEM_TAIL16");
-    if (!net.tb_stream || net.tail_start != 1 || dev_env("GEM_BATCHED_NARROW") || (t16_env && t16_env[0] == '0')) return false;
-    return net.front.wb_hi && net.dec.size() > 1;
-}
-
 // One evaluation in the bf16 decoder mode: decodes ws.trial_b, leaves the pose in ws.dec_act.back() (fp32), the energies in
-// ws.f / ws.parts and dE/dz in ws.dz (or in ws.grad_slab for lbfgs_advance, in the rounds).
-int evaluate_bf16(gem_handle* h, int stage, int B, const EnergyArgs& ea_in, hipStream_t s, bool forward_only) {
+// ws.f / ws.parts and dE/dz in ws.dz -- or, in the rounds (rs != nullptr), as the slabs *grad describes, for lbfgs_advance to sum.
+// Three ways to run the narrow layers + energies (rt.narrow, plan_route): the bf16 multi-window tail (tail_bf16.hip: 1 .. 8 windows
+// per workgroup, one launch), the fp32 one-window tail (tail.hip; GEM_TAIL16=0 or networks the bf16 tail does not cover), or batched
+// bf16 GEMMs + the stand-alone energy kernel.
+int evaluate_bf16(gem_handle* h, const Route& rt, int stage, int B, const EnergyArgs& ea_in, hipStream_t s, bool forward_only,
+                  const RoundSet* rs, SlabSrc* grad) {
     StageNet& net = h->net[stage];
     Workspace& w = h->ws;
-    const int T = h->T, rows = B * T, n_dec = (int)net.dec.size();
-    const int tail_g = T <= 16 ? 16 / T : 1;
-    const int tail_wgs = (B + tail_g - 1) / tail_g;
-    // Three ways to run the narrow layers + energies: the bf16 multi-window tail (tail_bf16.hip: 1 .. 8 windows per workgroup, one
-    // launch), the fp32 one-window tail (tail.hip; GEM_TAIL16=0 or networks the bf16 tail does not cover), or batched bf16 GEMMs + the
-    // stand-alone energy kernel (networks the tails do not cover).  GEM_TAIL16=0 forbids the first (GEM_DEV=1).
-    const char* t16_env = dev_env("GEM_TAIL16");       // (read per call: the tests flip it inside one process)
-    const bool batched_narrow = dev_env("GEM_BATCHED_NARROW") != nullptr;      // neither tail: every layer a batched GEMM (A/B runs, tests)
-    // (round 3 sent batches below 256 windows to the fp32 one-window tail; with ONE row tile per workgroup -- one window of ten frames,
-    // every window its own CU like the fp32 tail, round 4 -- the bf16 tail wins at every size: 60 / 120 / 240 windows 14.9 / 26.1 /
-    // 47.8 k windows/s against 11.1 / 20.6 / 38.7 k)
-    const bool use_tail16 = net.tb_stream && net.tail_start >= 1 && !batched_narrow && !(t16_env && t16_env[0] == '0');
-    const bool use_tail = !use_tail16 && !batched_narrow && net.tail_start >= 1 && tail_wgs <= 5 * h->n_cu;
-    const int* perm = w.dyn ? w.perm : nullptr;
-    if (w.next_count && !(use_tail16 && net.front.wb_hi && net.tail_start == 1)) {
-        set_error("evaluate_bf16: slots are handed out by lbfgs_advance but this evaluation does not run front products + fused tail");
-        return 1;
-    }
-    w.grad_slab = SlabSrc{};
-    // decoder_input o conv 0 as ONE product where the weights were composed (compose_front in gem_api.hip), else
-    // decoder_input: [B, Dp] x [Dp, T*topp] -> h0 [B*T, topp] bf16 (rows of finished windows are skipped through perm)
-    const bool front = net.front.wb_hi && n_dec > 1 && ((!use_tail && !use_tail16) || net.tail_start == 1);
+    const int T = h->T, rows = B * T, n_dec = (int)net.dec.size(), st = net.tail_start;
+    const bool front = rt.front, tail = rt.narrow != NARROW_BATCHED, tail16 = rt.narrow == NARROW_TAIL_BF16;
+    const GemmOpts in_rounds(rs, nullptr), gathered(rs, rs ? rs->perm : nullptr);       // rows of finished windows are skipped through perm
+    *grad = SlabSrc{};
+    // decoder_input o conv 0 as ONE product where the weights were composed (compose_front in weights.hip), else
+    // decoder_input: [B, Dp] x [Dp, T*topp] -> h0 [B*T, topp] bf16
     const uint16_t* in = w.h0_b;
-    EnergyArgs ea = ea_in;
     int back_from;                     // first layer of the batched backward chain
     const uint16_t* gin;
-    if (!front && gemm_bf16a(h, net.dec_in, EPI_BIAS, w.trial_b, h->Dp, nullptr, w.h0_b, true, net.dec_in.N, B, s, 0, perm, true, false)) return 1;
-    if (use_tail16) {
-        const int st = net.tail_start;
+    if (!front && gemm_bf16a(h, net.dec_in, EPI_BIAS, w.trial_b, h->Dp, nullptr, w.h0_b, true, net.dec_in.N, B, s, 0, true, gathered)) return 1;
+    if (tail) {
+        // The layer in front of the tail: in the rounds its fp32 split-K slabs (if it was cut) go straight to the tail, which sums
+        // them and applies bias + LeakyReLU while staging; otherwise it writes the activation itself -- bf16 for the bf16 tail, fp32
+        // for the fp32 one.
         SlabSrc in_slab;
-        // the layer in front of the tail: in the rounds its fp32 split-K slabs (if it was cut) go straight to the tail, which sums
-        // them and applies bias + LeakyReLU while staging; otherwise it writes the bf16 activation itself
-        if (front) {
-            if (gemm_bf16a(h, net.front, EPI_BIAS_LRELU, w.trial_b, h->Dp, nullptr, w.dec_act_b[0], true, net.front.N, B, s, 0, perm, true, w.dyn))
-                return 1;
-            in_slab = w.deferred;
-        }
+        const GemmOpts to_tail(rs, nullptr, rs ? &in_slab : nullptr), front_to_tail(rs, gathered.row_map, rs ? &in_slab : nullptr);
+        void* a_in = tail16 ? (void*)w.dec_act_b[st - 1] : (void*)w.dec_act[st - 1];
+        if (front && gemm_bf16a(h, net.front, EPI_BIAS_LRELU, w.trial_b, h->Dp, nullptr, a_in, tail16, net.front.N, B, s, 0, true, front_to_tail))
+            return 1;
         for (int i = 0; i < st && !front; ++i) {
             const bool last_wide = i == st - 1;
-            if (gemm_bf16a(h, net.dec[i], EPI_BIAS_LRELU, in, net.dec[i].K, nullptr, w.dec_act_b[i], true, net.dec[i].N, rows, s, -1, nullptr,
-                           true, last_wide && w.dyn)) return 1;
-            if (last_wide) in_slab = w.deferred;
+            if (gemm_bf16a(h, net.dec[i], EPI_BIAS_LRELU, in, net.dec[i].K, nullptr, last_wide ? a_in : (void*)w.dec_act_b[i], tail16 || !last_wide,
+                           net.dec[i].N, rows, s, -1, true, last_wide ? to_tail : in_rounds)) return 1;
             in = w.dec_act_b[i];
         }
-        TailB16Args ta;
-        const size_t tb_lds = plan_tail_bf16(net.dec, st, T, h->J, &ta, tail_bf16_row_tiles(h, B, T));
-        if (!tb_lds) { set_error("evaluate_bf16: the bf16 tail's LDS plan failed"); return 1; }
-        ta.B = B; ta.forward_only = forward_only ? 1 : 0; ta.dbg_ts = nullptr;
-        ta.in_slab = in_slab; ta.in_bias = front ? net.front.bias : net.dec[st - 1].bias;
-        ta.in_bias_ld = front ? net.dec[0].N : 0;
-        for (int i = 0; i < ta.n; ++i) {
-            const Layer& f = net.dec[st + i];
-            const Layer& g = net.dec_bwd[st + i];
-            ta.fwd[i] = TailB16Layer{f.K, f.N, f.bias};
-            ta.bwd[i] = TailB16Layer{g.K, g.N, nullptr};
-        }
-        ta.a_in_b = w.dec_act_b[st - 1]; ta.g_out_b = w.dec_grad_b[st];
-        ta.Xp = (w.dyn && !forward_only) ? nullptr : w.dec_act.back();
-        ta.wstream = net.tb_stream; ta.steps_f = net.tb_steps_f; ta.steps_total = net.tb_steps_f + net.tb_steps_b;
-        ta.e = ea;
-        if (launch_tail_bf16(h, ta, tb_lds, s)) return 1;
-        if (forward_only) return 0;
-        back_from = st - 1;
-        gin = w.dec_grad_b[st];
-    } else
-    if (use_tail) {
-        const int st = net.tail_start;
-        SlabSrc in_slab;
-        if (front) {                   // feeds the fp32 tail: fp32 slabs in the rounds, a finished fp32 matrix otherwise
-            if (gemm_bf16a(h, net.front, EPI_BIAS_LRELU, w.trial_b, h->Dp, nullptr, w.dec_act[0], false, net.front.N, B, s, 0, perm, true, w.dyn))
-                return 1;
-            in_slab = w.deferred;
-        }
-        for (int i = 0; i < st && !front; ++i) {
-            const bool last_wide = i == st - 1;
-            if (last_wide) {           // feeds the fp32 tail: fp32 slabs in the rounds, a finished fp32 matrix otherwise
-                if (gemm_bf16a(h, net.dec[i], EPI_BIAS_LRELU, in, net.dec[i].K, nullptr, w.dec_act[i], false, net.dec[i].N, rows, s, -1,
-                               nullptr, true, w.dyn)) return 1;
-                in_slab = w.deferred;
-            } else {
-                if (gemm_bf16a(h, net.dec[i], EPI_BIAS_LRELU, in, net.dec[i].K, nullptr, w.dec_act_b[i], true, net.dec[i].N, rows, s, -1,
-                               nullptr, true, false)) return 1;
-                in = w.dec_act_b[i];
+        if (tail16) {
+            TailB16Args ta;
+            const size_t tb_lds = plan_tail_bf16(net.dec, st, T, h->J, &ta, tail_bf16_row_tiles(h, B, T));
+            if (!tb_lds) { set_error("evaluate_bf16: the bf16 tail's LDS plan failed"); return 1; }
+            ta.B = B; ta.forward_only = forward_only ? 1 : 0; ta.dbg_ts = nullptr;
+            ta.in_slab = in_slab; ta.in_bias = front ? net.front.bias : net.dec[st - 1].bias;
+            ta.in_bias_ld = front ? net.dec[0].N : 0;
+            for (int i = 0; i < ta.n; ++i) {
+                const Layer& f = net.dec[st + i];
+                const Layer& g = net.dec_bwd[st + i];
+                ta.fwd[i] = TailB16Layer{f.K, f.N, f.bias};
+                ta.bwd[i] = TailB16Layer{g.K, g.N, nullptr};
             }
+            ta.a_in_b = w.dec_act_b[st - 1]; ta.g_out_b = w.dec_grad_b[st];
+            ta.Xp = (rs && !forward_only) ? nullptr : w.dec_act.back();
+            ta.wstream = net.tb_stream; ta.steps_f = net.tb_steps_f; ta.steps_total = net.tb_steps_f + net.tb_steps_b;
+            ta.e = ea_in;
+            if (launch_tail_bf16(h, ta, tb_lds, s, rs)) return 1;
+        } else {
+            TailArgs ta;
+            plan_tail(net.dec, st, T, h->J, &ta);
+            fill_tail_args(h, net, rt, B, forward_only, in_slab, ea_in, rs, &ta);
+            ta.g_out = nullptr; ta.g_out_b = w.dec_grad_b[st];
+            if (launch_tail(h, ta, net.tail_lds, s, rs)) return 1;
         }
-        TailArgs ta;
-        plan_tail(net.dec, st, T, h->J, &ta);
-        ta.B = B; ta.forward_only = forward_only ? 1 : 0; ta.dbg_ts = nullptr;
-        ta.in_slab = in_slab; ta.in_bias = front ? net.front.bias : net.dec[st - 1].bias;
-        ta.in_bias_ld = front ? net.dec[0].N : 0;
-        for (int i = 0; i < ta.n; ++i) {
-            const Layer& f = net.dec[st + i];
-            const Layer& g = net.dec_bwd[st + i];
-            ta.fwd[i] = TailLayerDev{f.w4, f.bias, f.K, f.N};
-            ta.bwd[i] = TailLayerDev{g.w4, nullptr, g.K, g.N};
-        }
-        ta.a_in = w.dec_act[st - 1]; ta.g_out = nullptr; ta.g_out_b = w.dec_grad_b[st];
-        ta.Xp = (w.dyn && !forward_only) ? nullptr : w.dec_act.back();
-        ta.e = ea;
-        if (launch_tail(h, ta, net.tail_lds, s)) return 1;
         if (forward_only) return 0;
         back_from = st - 1;
         gin = w.dec_grad_b[st];
     } else {
         if (front) {
-            if (gemm_bf16a(h, net.front, EPI_BIAS_LRELU, w.trial_b, h->Dp, nullptr, w.dec_act_b[0], true, net.front.N, B, s, 0, perm, true, false))
+            if (gemm_bf16a(h, net.front, EPI_BIAS_LRELU, w.trial_b, h->Dp, nullptr, w.dec_act_b[0], true, net.front.N, B, s, 0, true, gathered))
                 return 1;
             in = w.dec_act_b[0];
         }
         for (int i = front ? 1 : 0; i < n_dec; ++i) {
             const bool last = i + 1 == n_dec;
             if (last) {                // the pose itself: fp32
-                if (gemm_bf16a(h, net.dec[i], EPI_BIAS, in, net.dec[i].K, nullptr, w.dec_act[i], false, net.dec[i].N, rows, s, -1, nullptr,
-                               false, false)) return 1;
+                if (gemm_bf16a(h, net.dec[i], EPI_BIAS, in, net.dec[i].K, nullptr, w.dec_act[i], false, net.dec[i].N, rows, s, -1, false, in_rounds))
+                    return 1;
             } else {
-                if (gemm_bf16a(h, net.dec[i], EPI_BIAS_LRELU, in, net.dec[i].K, nullptr, w.dec_act_b[i], true, net.dec[i].N, rows, s, -1,
-                               nullptr, false, false)) return 1;
+                if (gemm_bf16a(h, net.dec[i], EPI_BIAS_LRELU, in, net.dec[i].K, nullptr, w.dec_act_b[i], true, net.dec[i].N, rows, s, -1, false,
+                               in_rounds)) return 1;
                 in = w.dec_act_b[i];
             }
         }
         if (forward_only) return 0;
+        EnergyArgs ea = ea_in;
         ea.Xp = w.dec_act.back();
         ea.dXp_b = w.dXp_b;
         if (launch_energy(h, ea, B, s)) return 1;
@@ -365,14 +306,12 @@ int evaluate_bf16(gem_handle* h, int stage, int B, const EnergyArgs& ea_in, hipS
     for (int i = back_from; i >= (front ? 1 : 0); --i) {
         const Layer& L = net.dec_bwd[i];
         if (gemm_bf16a(h, L, i > 0 ? EPI_MASK : EPI_NONE, gin, L.K, i > 0 ? w.dec_act_b[i - 1] : nullptr, w.dec_grad_b[i], true, L.N, rows, s,
-                       -1, nullptr, i == 0, false)) return 1;
+                       -1, i == 0, in_rounds)) return 1;
         gin = w.dec_grad_b[i];
     }
     // decoder_input^T: dE/dz fp32; in the rounds lbfgs_advance sums the slabs itself
     const Layer& last_l = front ? net.front_bwd : net.dec_in_bwd;         // front: gin is the gradient w.r.t. conv 0's pre-activation
-    if (gemm_bf16a(h, last_l, EPI_NONE, gin, last_l.K, nullptr, w.dz, false, h->Dp, B, s, 0, nullptr, true, w.dyn)) return 1;
-    w.grad_slab = w.deferred;
-    return 0;
+    return gemm_bf16a(h, last_l, EPI_NONE, gin, last_l.K, nullptr, w.dz, false, h->Dp, B, s, 0, true, GemmOpts(rs, nullptr, rs ? grad : nullptr));
 }
 
 }  // namespace gem

@@ -78,7 +78,7 @@ struct StageNet {
     std::vector<Layer> dec_bwd;    // dec_bwd[i] is the adjoint of dec[i]
     // decoder_input followed by the first decoder conv (no activation in between: SeqConvVAE.py:62,67-75,131-135) composed into
     // ONE linear layer z -> pre-activation of conv 0, N = T * pad64(C1) (n = t * C1p + c), K = Dp, and its transpose
-    // (see compose_front in gem_api.hip).  Empty (w == nullptr) when the fused tail does not start at conv 1.
+    // (see compose_front in weights.hip).  Empty (w == nullptr) when the fused tail does not start at conv 1.
     Layer front, front_bwd;
     int tail_start = -1;           // decoder convs [tail_start, end) run in the fused tail kernel (-1: none)
     size_t tail_lds = 0;
@@ -143,32 +143,20 @@ struct Workspace {
     double* parts = nullptr;            // [B,5]
     int* tex_key = nullptr;             // [B, T*J] / float [B, T*J, 4]: heat-map texels of the last evaluation (energy_device.h)
     float* tex_val = nullptr;
-    bool tex_on = false;                // energy_args() hands the cache to the kernels (inside a stage only)
     double* trace = nullptr;            // [TRACE_ROUNDS][Bmax] closure value each window consumed in round r of the last stage (NaN: none)
-    int round = -1;                     // evaluation round being enqueued (-1: outside the rounds)
     // pipeline scratch
     float* pose_a = nullptr;            // [B,T,J,3] gathered local poses / stage outputs
     float* pose_b = nullptr;
     float* splitk = nullptr;            // partial slabs of the split-K GEMM launches
-    bool defer_reduce = false;          // next launch_gemm: leave the slabs to the consumer, describe them in `deferred`
-    SlabSrc deferred;
-    SlabSrc grad_slab;                  // dE/dz of the current round as left by the decoder_input backward product
     size_t splitk_elems = 0;
-    // active-window compaction (lbfgs.hip compact_kernel): windows still iterating occupy slots [0, n_active)
+    // active-window compaction: windows still iterating occupy slots [0, n_active).  Which of these buffers a round reads and
+    // which it fills for the next one is decided per round (RoundSet below); nothing here moves.
     int* perm = nullptr;                // [B] slot -> window
     int* slot_of = nullptr;             // [B] window -> slot
     int* n_active = nullptr;            // [2] = {n_active, n_active*T}
-    // Slots handed out by lbfgs_advance itself (bf16 decoder mode with the fused tail): a window
-    // that keeps iterating takes the next free slot of the coming round with one atomic add, so the rounds need no compact_kernel
-    // launch.  Two (perm, slot_of) buffer pairs alternate by round; a round's count lives in its n_log entry (zeroed at stage begin).
-    // `perm`, `slot_of`, `n_active` above always point at the CURRENT round's set; *_home are the allocations they return to.
-    int *perm2 = nullptr, *slot_of2 = nullptr, *perm_home = nullptr, *slot_of_home = nullptr, *n_active_home = nullptr;
-    int *next_perm = nullptr, *next_slot_of = nullptr, *next_count = nullptr;      // what lbfgs_advance of this round fills (nullptr: off)
-    bool dyn = false;                   // rounds in flight: GEMM / energy launches read their row count from n_active
-    int* n_log = nullptr;               // [N_LOG] n_active after every compaction (profiling: true row counts)
-    long log_pos = 0, cur_log = -1;
-    bool fuse_compact = false;          // next decoder_input forward launch re-packs the active windows itself (gemm_rows.h)
-    int* fuse_log = nullptr;            // ... and logs n_active here
+    int *perm2 = nullptr, *slot_of2 = nullptr;      // the second (perm, slot_of) pair of the rounds whose slots lbfgs_advance hands out
+    int* n_log = nullptr;               // [N_LOG] n_active after every compaction (profiling: true row counts; the counters of atomic slots)
+    long log_pos = 0;                   // next free n_log entry
     int done_phase = 3;                 // lbfgs.hip PH_DONE
     // the solver stepped alone (gem_lbfgs_debug_*, parity tests): slot mode of the run in progress (-1: none), its batch size,
     // the round the next advance call enqueues, and the n_log entry of round 0's count (slot mode 2)
@@ -176,6 +164,58 @@ struct Workspace {
     long dbg_log0 = 0;
     std::vector<void*> allocs;
 };
+
+// How the rounds of a stage re-pack the windows that are still iterating (decided once per call: Route, stage.hip).
+enum Repack {
+    REPACK_NONE = 0,       // no slot table at all (the solver stepped alone, slot mode 0)
+    REPACK_KERNEL = 1,     // compact_kernel at the head of every round
+    REPACK_FUSED = 2,      // by the first few-rows GEMM of the round (gemm_rows.h, FUSE)
+    REPACK_ATOMIC = 3      // lbfgs_advance hands out the next round's slots itself: two (perm, slot_of) pairs alternate by round,
+                           // a round's count is its n_log entry (zeroed at stage begin)
+};
+
+// One evaluation round as the launchers see it (round_set, stage.hip).  A null RoundSet* means "outside the rounds": all B rows,
+// identity order, the row count known on the host.
+struct RoundSet {
+    int* n_active = nullptr;            // device {rows of linear layers, rows of temporal convs} ([1] only with REPACK_KERNEL / FUSED)
+    int* perm = nullptr;                // slot -> window
+    int* slot_of = nullptr;             // window -> slot (nullptr: REPACK_NONE)
+    int *next_perm = nullptr, *next_slot_of = nullptr, *next_count = nullptr;      // what lbfgs_advance fills for the next round (REPACK_ATOMIC)
+    long log_idx = -1;                  // n_log entry holding this round's count (profiling)
+    double* trace = nullptr;            // [Bmax] row of Workspace::trace for this round, or nullptr
+};
+
+// Per-launch options of launch_gemm / launch_gemm_bf16 (a null pointer converts: `nullptr` in this position means "none").
+struct GemmOpts {
+    const RoundSet* rs = nullptr;       // the round this launch belongs to: row counts are read on the device
+    const int* row_map = nullptr;       // gathered A rows (linear layers)
+    SlabSrc* defer = nullptr;           // non-null: split-K slabs may be left to the consumer and are described here; base == nullptr on
+                                        // return: the launch reduced itself
+    int* repack_log = nullptr;          // non-null: this launch also re-packs the active windows (REPACK_FUSED) and logs the count here
+    GemmOpts() {}
+    GemmOpts(std::nullptr_t) {}
+    GemmOpts(const RoundSet* rs_, const int* row_map_, SlabSrc* defer_ = nullptr, int* repack_log_ = nullptr)
+        : rs(rs_), row_map(row_map_), defer(defer_), repack_log(repack_log_) {}
+};
+
+// device memory owned by a vector: zero-filled allocation, upload of a host array, release of everything
+template <typename T>
+inline int dev_alloc(std::vector<void*>& owner, T** p, size_t n) {
+    void* q = nullptr;
+    if (!hip_ok(hipMalloc(&q, (n ? n : 1) * sizeof(T)), "hipMalloc")) return 1;
+    owner.push_back(q);                 // owned from here on, whatever happens next
+    *p = static_cast<T*>(q);
+    return hip_ok(hipMemset(q, 0, (n ? n : 1) * sizeof(T)), "hipMemset") ? 0 : 1;
+}
+template <typename T>
+inline int upload(std::vector<void*>& owner, T** p, const std::vector<T>& v) {
+    if (dev_alloc(owner, p, v.size())) return 1;
+    return hip_ok(hipMemcpy(*p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice), "hipMemcpy") ? 0 : 1;
+}
+inline void free_all(std::vector<void*>& owner) {
+    for (void* p : owner) (void)hipFree(p);
+    owner.clear();
+}
 
 // "done once" flag per device ordinal: hipFuncSetAttribute is a per-device setting and a process may own handles on
 // several devices (one thread per handle; a handle itself is not thread-safe)
@@ -282,7 +322,7 @@ inline void commit_kernel_names(gem_handle* h, int family) {
 
 // ---- kernel launchers (each enqueues on `s`, returns 0/1) -------------------------------------------
 int launch_gemm(gem_handle* h, const Layer& L, int epi, const float* A, int lda, const float* aux, float* Cout, int ldc,
-                int M, int T, hipStream_t s, int family, const int* row_map = nullptr);
+                int M, int T, hipStream_t s, int family, const GemmOpts& o = GemmOpts());
 
 int pick_splitk(const gem_handle* h, long blocks, int n_tiles, size_t slab_elems);
 
@@ -315,16 +355,36 @@ __device__ inline void slab_layout(const SlabSrc& s, int& nslab, size_t& stride)
     }
 }
 bool rows_can_fuse_compaction(const gem_handle* h, const Layer& L, int lda, int ldc, int B, bool slabs);
-bool bf16_rounds_take_slots_atomically(const gem_handle* h, int stage, int B);      // decoder_bf16.hip: fused bf16 tail right behind the composed front layer
 int launch_splitk_reduce(gem_handle* h, int epi, int nslab, size_t slab, const float* bias, const float* aux, float* C, int M, int N,
                          int ldc, const int* m_dev, hipStream_t s, int dyn_W = 0, int n_tiles = 0);
 // bf16-input MFMA variant of launch_gemm (gemm_bf16.hip): nprod = 1 (plain bf16) or 3 (hi/lo split, fp32-grade)
 int launch_gemm_bf16(gem_handle* h, const Layer& L, int epi, int nprod, const float* A, int lda, const float* aux, float* Cout,
-                     int ldc, int M, int T, hipStream_t s, const int* row_map);
+                     int ldc, int M, int T, hipStream_t s, const GemmOpts& o);
 
 // bf16-activation decoder path (decoder_bf16.hip): one evaluation = decode + energies + backward-data, like evaluate()
+// Which kernels one call runs, decided once (plan_route, stage.hip) and handed to everything that enqueues for that call.
+enum Narrow {
+    NARROW_BATCHED = 0,      // every narrow decoder layer a batched GEMM, the energies in the stand-alone kernel
+    NARROW_TAIL_F32 = 1,     // fp32 fused tail (tail.hip)
+    NARROW_TAIL_BF16 = 2     // bf16 multi-window tail (tail_bf16.hip)
+};
+struct Route {
+    int precision = 0;       // GEM_PRECISION_*: the family of the wide products
+    Narrow narrow = NARROW_BATCHED;
+    bool front = false;      // decoder_input o conv 0 run as the one composed layer (compose_front, weights.hip)
+    int tail_wgs = 0;        // workgroups of the fp32 fused tail at this batch, and up to how many it is used
+    int tail_cap = 0;
+    Repack repack = REPACK_KERNEL;      // how the rounds re-pack the active windows
+};
+// What the route is for: a plain decode (gem_decode: the batched layers of the fp32 entry points whatever the batch), one evaluation,
+// or a stage's rounds (only these re-pack: Route::repack is decided for them alone).
+enum Call { CALL_DECODE = 0, CALL_EVALUATE = 1, CALL_ROUNDS = 2 };
+Route plan_route(const gem_handle* h, int stage, int B, Call call);
+
 struct EnergyArgs;
-int evaluate_bf16(gem_handle* h, int stage, int B, const EnergyArgs& ea, hipStream_t s, bool forward_only);
+// One evaluation in the bf16 decoder mode (decoder_bf16.hip); returns the gradient's slabs in *grad like evaluate() (stage.hip)
+int evaluate_bf16(gem_handle* h, const Route& rt, int stage, int B, const EnergyArgs& ea, hipStream_t s, bool forward_only, const RoundSet* rs,
+                  SlabSrc* grad);
 int launch_f32_to_bf16(const float* src, uint16_t* dst, size_t n, hipStream_t s);
 int launch_f32_split_bf16(const float* src, uint16_t* hi, uint16_t* lo, size_t n, hipStream_t s);
 
@@ -378,6 +438,10 @@ struct TailArgs {
     EnergyArgs e;
 };
 size_t plan_tail(const std::vector<Layer>& dec, int start, int T, int J, TailArgs* out, bool shared = false);
+// what both evaluates hand the planned fp32 tail: batch, input (finished matrix or slabs + the bias / LeakyReLU still to apply),
+// the fused layers' weights, the energy arguments; the caller sets the gradient outputs (g_out / g_out_b)
+void fill_tail_args(const gem_handle* h, const StageNet& net, const Route& rt, int B, bool forward_only, const SlabSrc& in_slab,
+                    const EnergyArgs& ea, const RoundSet* rs, TailArgs* ta);
 size_t plan_tail_for(const gem_handle* h, const std::vector<Layer>& dec, int start, int wgs, TailArgs* out);   // shape chosen for `wgs` workgroups
 
 // bf16 multi-window fused tail (tail_bf16.hip): nrt = 1 .. 5 row tiles of 16 rows = G = min(8, 16 nrt / T) windows per workgroup,
@@ -409,8 +473,8 @@ struct TailB16Args {
 size_t plan_tail_bf16(const std::vector<Layer>& dec, int start, int T, int J, TailB16Args* out, int nrt = 5);
 int tail_bf16_row_tiles(const gem_handle* h, int B, int T);
 int build_tail_bf16_stream(gem_handle* h, StageNet& net);
-int launch_tail_bf16(gem_handle* h, const TailB16Args& a, size_t lds_bytes, hipStream_t s);
-int launch_tail(gem_handle* h, const TailArgs& a, size_t lds_bytes, hipStream_t s);
+int launch_tail_bf16(gem_handle* h, const TailB16Args& a, size_t lds_bytes, hipStream_t s, const RoundSet* rs = nullptr);
+int launch_tail(gem_handle* h, const TailArgs& a, size_t lds_bytes, hipStream_t s, const RoundSet* rs = nullptr);
 int tail_cap_workgroups(const gem_handle* h, const std::vector<Layer>& dec, int start);   // fused tail up to this many workgroups
 int launch_mean_bone(gem_handle* h, const float* pose, int n_frames, float* out, hipStream_t s);
 int launch_gather_windows(const float* frames, const int32_t* frame0, float* out, int B, int T, int JC, hipStream_t s);
@@ -425,14 +489,15 @@ int launch_errors(gem_handle* h, const double* est, const double* mid, const dou
 int launch_merge(const double* win, double* tmp, double* out, int n_chunks, int wpc, int T, int JC, int overlap, int smooth,
                  hipStream_t s);
 size_t errors_frame_lds_bytes(int J);
+void drop_graphs(gem_handle* h);                    // gem_api.hip: forget every captured call (they hold weight / workspace / caller pointers)
 int post_scratch(gem_handle* h, size_t elems);      // gem_api.hip: h->post_work holds at least `elems` doubles afterwards
 int launch_lift(gem_handle* h, const float* heat, const double* depth, int F, const double* poly, int n_poly, int up, int pad_x,
                 int pad_y, double* out64, float* out32, hipStream_t s);
 
-int launch_lbfgs_init(gem_handle* h, int B, const gem_lbfgs_opts& o, hipStream_t s);
-int launch_lbfgs_advance(gem_handle* h, int B, const gem_lbfgs_opts& o, hipStream_t s);
+int launch_lbfgs_init(gem_handle* h, int B, hipStream_t s);
+int launch_lbfgs_advance(gem_handle* h, int B, const gem_lbfgs_opts& o, const RoundSet& rs, const SlabSrc& grad, hipStream_t s);
 int launch_lbfgs_stats(gem_handle* h, int B, gem_window_stats* out, hipStream_t s);
-int launch_compact(gem_handle* h, int B, int force_all, hipStream_t s, int zero_after = 0);
+int launch_compact(gem_handle* h, const RoundSet& rs, int B, int force_all, hipStream_t s, int zero_after = 0);      // fills rs.perm / slot_of / n_active, logs at rs.log_idx
 int launch_lbfgs_debug_read(gem_handle* h, int B, gem_lbfgs_debug_state* out, float* x, float* d, float* trial, hipStream_t s);
 
 

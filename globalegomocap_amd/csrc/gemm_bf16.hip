@@ -317,8 +317,8 @@ __global__ __launch_bounds__(256) void gemm_bf16_big_kernel(const float* __restr
 
 template <int TAPS, int EPI, int NPROD>
 static int launch_b(gem_handle* h, const Layer& L, const float* A, int lda, const float* aux, float* C, int ldc, int M, int T,
-                    hipStream_t s, const int* row_map) {
-    const int* m_dev = h->ws.dyn ? h->ws.n_active + (TAPS == 3 ? 1 : 0) : nullptr;
+                    hipStream_t s, const GemmOpts& o) {
+    const int* m_dev = o.rs ? o.rs->n_active + (TAPS == 3 ? 1 : 0) : nullptr;
     constexpr int BK = 64;
     // 128x128 tiles once they fill the chip
     const long big_blocks = (long)((M + 127) / 128) * (L.N / 128);
@@ -331,7 +331,7 @@ static int launch_b(gem_handle* h, const Layer& L, const float* A, int lda, cons
         }
         note_kernel(h, reinterpret_cast<const void*>(kb));
         hipLaunchKernelGGL(kb, dim3(L.N / 128, (M + 127) / 128, 1), dim3(256), smem, s, A, lda, L.wb_hi, L.wb_lo, L.bias, aux, C, ldc,
-                           M, L.N, L.K, T, m_dev, row_map);
+                           M, L.N, L.K, T, m_dev, o.row_map);
         GEM_HIP(hipGetLastError());
         return 0;
     }
@@ -356,11 +356,11 @@ static int launch_b(gem_handle* h, const Layer& L, const float* A, int lda, cons
     const int dyn_W = (m_dev && grid.z > 1 && (size_t)wgs * 64 * 64 <= h->ws.splitk_elems) ? (int)wgs : 0;
     note_kernel(h, reinterpret_cast<const void*>(k));
     hipLaunchKernelGGL(k, grid, dim3(256), shmem, s, A, lda, L.wb_hi, L.wb_lo, L.bias, aux, out, ldc, M, L.N, L.K, T,
-                       grid.z == 1 ? n_tiles : per, grid.z == 1 ? (size_t)0 : slab, m_dev, row_map, dyn_W);
+                       grid.z == 1 ? n_tiles : per, grid.z == 1 ? (size_t)0 : slab, m_dev, o.row_map, dyn_W);
     GEM_HIP(hipGetLastError());
     if (grid.z == 1) return 0;
-    if (h->ws.defer_reduce) {                       // the consumer sums the slabs (and applies the epilogue) itself
-        SlabSrc& d = h->ws.deferred;
+    if (o.defer) {                                  // the consumer sums the slabs (and applies the epilogue) itself
+        SlabSrc& d = *o.defer;
         d.base = h->ws.splitk; d.nslab = (int)grid.z; d.stride = slab;
         d.dyn_W = dyn_W; d.n_tiles = n_tiles; d.ldc = ldc; d.CT = L.N / 64; d.m_dev = m_dev;
         return 0;
@@ -370,25 +370,27 @@ static int launch_b(gem_handle* h, const Layer& L, const float* A, int lda, cons
 
 template <int TAPS, int EPI>
 static int launch_np(gem_handle* h, const Layer& L, int nprod, const float* A, int lda, const float* aux, float* C, int ldc, int M,
-                     int T, hipStream_t s, const int* row_map) {
-    if (nprod == 3) return launch_b<TAPS, EPI, 3>(h, L, A, lda, aux, C, ldc, M, T, s, row_map);
-    return launch_b<TAPS, EPI, 1>(h, L, A, lda, aux, C, ldc, M, T, s, row_map);
+                     int T, hipStream_t s, const GemmOpts& o) {
+    if (nprod == 3) return launch_b<TAPS, EPI, 3>(h, L, A, lda, aux, C, ldc, M, T, s, o);
+    return launch_b<TAPS, EPI, 1>(h, L, A, lda, aux, C, ldc, M, T, s, o);
 }
 
 int launch_gemm_bf16(gem_handle* h, const Layer& L, int epi, int nprod, const float* A, int lda, const float* aux, float* C, int ldc,
-                     int M, int T, hipStream_t s, const int* row_map) {
+                     int M, int T, hipStream_t s, const GemmOpts& o) {
     if (!L.wb_hi || (nprod == 3 && !L.wb_lo)) { set_error("launch_gemm_bf16: layer has no bf16 weights"); return 1; }
     if (L.K % 64 != 0 || L.N % 64 != 0 || lda % 4 != 0) { set_error("launch_gemm_bf16: dimensions must be padded to 64"); return 1; }
+    if (o.repack_log) { set_error("launch_gemm_bf16: fused compaction on a launch that cannot carry it"); return 1; }
+    if (o.defer) *o.defer = SlabSrc{};
     if (M <= 0) return 0;
     if (L.taps == 1) {
-        if (epi == EPI_BIAS) return launch_np<1, EPI_BIAS>(h, L, nprod, A, lda, aux, C, ldc, M, T, s, row_map);
-        if (epi == EPI_NONE) return launch_np<1, EPI_NONE>(h, L, nprod, A, lda, aux, C, ldc, M, T, s, row_map);
-        if (epi == EPI_BIAS_LRELU) return launch_np<1, EPI_BIAS_LRELU>(h, L, nprod, A, lda, aux, C, ldc, M, T, s, row_map);
+        if (epi == EPI_BIAS) return launch_np<1, EPI_BIAS>(h, L, nprod, A, lda, aux, C, ldc, M, T, s, o);
+        if (epi == EPI_NONE) return launch_np<1, EPI_NONE>(h, L, nprod, A, lda, aux, C, ldc, M, T, s, o);
+        if (epi == EPI_BIAS_LRELU) return launch_np<1, EPI_BIAS_LRELU>(h, L, nprod, A, lda, aux, C, ldc, M, T, s, o);
     } else if (L.taps == 3) {
-        if (epi == EPI_BIAS) return launch_np<3, EPI_BIAS>(h, L, nprod, A, lda, aux, C, ldc, M, T, s, row_map);
-        if (epi == EPI_BIAS_LRELU) return launch_np<3, EPI_BIAS_LRELU>(h, L, nprod, A, lda, aux, C, ldc, M, T, s, row_map);
-        if (epi == EPI_MASK) return launch_np<3, EPI_MASK>(h, L, nprod, A, lda, aux, C, ldc, M, T, s, row_map);
-        if (epi == EPI_NONE) return launch_np<3, EPI_NONE>(h, L, nprod, A, lda, aux, C, ldc, M, T, s, row_map);
+        if (epi == EPI_BIAS) return launch_np<3, EPI_BIAS>(h, L, nprod, A, lda, aux, C, ldc, M, T, s, o);
+        if (epi == EPI_BIAS_LRELU) return launch_np<3, EPI_BIAS_LRELU>(h, L, nprod, A, lda, aux, C, ldc, M, T, s, o);
+        if (epi == EPI_MASK) return launch_np<3, EPI_MASK>(h, L, nprod, A, lda, aux, C, ldc, M, T, s, o);
+        if (epi == EPI_NONE) return launch_np<3, EPI_NONE>(h, L, nprod, A, lda, aux, C, ldc, M, T, s, o);
     }
     set_error("launch_gemm_bf16: unsupported taps / epilogue");
     return 1;

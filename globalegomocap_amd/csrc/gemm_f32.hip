@@ -302,9 +302,9 @@ int launch_splitk_reduce(gem_handle* h, int epi, int nslab, size_t slab, const f
 
 template <int TAPS, int EPI, int RM, int RN, int TAG, int BK>
 static int launch_one(gem_handle* h, const Layer& L, const float* A, int lda, const float* aux, float* C, int ldc, int M, int T,
-                      hipStream_t s, const int* row_map) {
+                      hipStream_t s, const GemmOpts& o) {
     // during the evaluation rounds the row count lives on the device: {n_active, n_active*T}
-    const int* m_dev = h->ws.dyn ? h->ws.n_active + (TAPS == 3 ? 1 : 0) : nullptr;
+    const int* m_dev = o.rs ? o.rs->n_active + (TAPS == 3 ? 1 : 0) : nullptr;
     constexpr int BM = 64 * RM, BN = 64 * RN;
     size_t shmem = (RM * RN > 1 ? 2 : 1) * (size_t)(BM + BN) * (BK + 4) * sizeof(float);
     auto k = gemm_f32_kernel<TAPS, EPI, RM, RN, TAG, BK>;
@@ -332,16 +332,16 @@ static int launch_one(gem_handle* h, const Layer& L, const float* A, int lda, co
     if (grid.z == 1) {
         note_kernel(h, reinterpret_cast<const void*>(k));
         hipLaunchKernelGGL(k, grid, dim3(256), shmem, s, A, lda, L.w, L.bias, aux, C, ldc, M, L.N, L.K, T, n_tiles, (size_t)0, m_dev,
-                           row_map, 0);
+                           o.row_map, 0);
         GEM_HIP(hipGetLastError());
         return 0;
     }
     note_kernel(h, reinterpret_cast<const void*>(k));
     hipLaunchKernelGGL(k, grid, dim3(256), shmem, s, A, lda, L.w, L.bias, aux, h->ws.splitk, ldc, M, L.N, L.K, T, per, slab, m_dev,
-                       row_map, dyn ? (int)wgs : 0);
+                       o.row_map, dyn ? (int)wgs : 0);
     GEM_HIP(hipGetLastError());
-    if (h->ws.defer_reduce && BM == 64) {           // the consumer sums the slabs (and applies the epilogue) itself
-        SlabSrc& d = h->ws.deferred;
+    if (o.defer && BM == 64) {                      // the consumer sums the slabs (and applies the epilogue) itself
+        SlabSrc& d = *o.defer;
         d.base = h->ws.splitk; d.nslab = (int)grid.z; d.stride = slab;
         d.dyn_W = dyn ? (int)wgs : 0; d.n_tiles = n_tiles; d.ldc = ldc; d.CT = L.N / BN; d.m_dev = m_dev;
         return 0;
@@ -355,7 +355,7 @@ static int launch_one(gem_handle* h, const Layer& L, const float* A, int lda, co
 // 128x128 kernel above.  No split-K: only used when the launch has >= 1.5 tiles per CU (480 tiles at 1536 windows).
 template <int TAPS, int EPI>
 static int launch_glds_f32(gem_handle* h, const Layer& L, const float* A, int lda, const float* aux, float* C, int ldc, int M, int T,
-                           hipStream_t s, const int* row_map) {
+                           hipStream_t s, const GemmOpts& o) {
     constexpr int BM = 128, BN = 128;
     auto k = glds::gemm_glds_kernel<true, TAPS, EPI, BM, BN, false, 16>;
     constexpr size_t smem = (size_t)BM * BN * 4;
@@ -364,8 +364,8 @@ static int launch_glds_f32(gem_handle* h, const Layer& L, const float* A, int ld
         GEM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_PER_CU));
     glds::Args a{};
     a.A = A; a.W = L.w; a.bias = L.bias; a.aux = aux; a.C = C; a.zero16 = h->ws.zero16;
-    a.m_dev = h->ws.dyn ? h->ws.n_active + (TAPS == 3 ? 1 : 0) : nullptr;
-    a.row_map = row_map;
+    a.m_dev = o.rs ? o.rs->n_active + (TAPS == 3 ? 1 : 0) : nullptr;
+    a.row_map = o.row_map;
     a.lda = lda; a.ldc = ldc; a.M = M; a.N = L.N; a.K = L.K; a.T = T;
     a.n_split = 1; a.tiles_per_split = TAPS * (L.K / 32); a.slab_stride = 0;
     const int grid = ((M + BM - 1) / BM) * (L.N / BN);
@@ -381,7 +381,7 @@ static int launch_glds_f32(gem_handle* h, const Layer& L, const float* A, int ld
 // CUs' matrix time; otherwise (tiny batches, large batches) the tiled kernels below take over.
 template <int S, int RT, bool FUSE>
 static int launch_rows_as(gem_handle* h, const Layer& L, const float* A, int lda, float* C, int ldc, int M, hipStream_t s,
-                          const int* row_map, const rows::Plan& p, bool direct, bool with_bias, bool lrelu) {
+                          const GemmOpts& o, const rows::Plan& p, bool direct, bool with_bias, bool lrelu) {
     auto k = rows::gemm_rows_kernel<S, RT, FUSE>;
     static PerDeviceOnce once;
     if (once.need(h->cfg.device))          // (the fused-compaction variant also has 2 KB of static LDS: ask for the ring only)
@@ -390,13 +390,13 @@ static int launch_rows_as(gem_handle* h, const Layer& L, const float* A, int lda
     Workspace& w = h->ws;
     rows::Args a{};
     a.A = A; a.W = L.w; a.bias = direct && with_bias ? L.bias : nullptr; a.lrelu = lrelu ? 1 : 0; a.C = direct ? C : w.splitk;
-    a.m_dev = w.dyn ? w.n_active : nullptr;
-    a.row_map = row_map;
+    a.m_dev = o.rs ? o.rs->n_active : nullptr;
+    a.row_map = o.row_map;
     a.lda = lda; a.ldc = ldc; a.M = M; a.N = L.N; a.K = L.K;
     a.n_rb = p.n_rb; a.n_split = p.n_split; a.tiles_per_split = p.per; a.slab_stride = (size_t)M * ldc;
     if (FUSE) {          // this launch also re-packs the windows that are still iterating (see rows::Args)
         a.phase_arr = w.phase; a.n_windows = M; a.done_phase = w.done_phase; a.T = h->T;
-        a.perm_out = w.perm; a.slot_of_out = w.slot_of; a.n_active_out = w.n_active; a.log_slot = w.fuse_log;
+        a.perm_out = o.rs->perm; a.slot_of_out = o.rs->slot_of; a.n_active_out = o.rs->n_active; a.log_slot = o.repack_log;
     }
     const int grid = p.n_rb * (L.N / rows::BN) * p.n_split;
     note_kernel(h, reinterpret_cast<const void*>(k));
@@ -430,54 +430,55 @@ bool rows_can_fuse_compaction(const gem_handle* h, const Layer& L, int lda, int 
 // returns -1 when the shape is not one for this kernel (the caller falls through to the tiled kernels)
 template <int EPI>
 static int launch_rows(gem_handle* h, const Layer& L, const float* A, int lda, const float* aux, float* C, int ldc, int M,
-                       hipStream_t s, const int* row_map) {
+                       hipStream_t s, const GemmOpts& o) {
     // direct output unless the consumer takes slabs (decoder_input backward: lbfgs_advance_kernel sums them)
-    const bool slabs = h->ws.defer_reduce && h->ws.splitk;
+    const bool slabs = o.defer && h->ws.splitk;
     rows::Plan p;
     bool use8;
     if (!rows_plan(h, L, lda, ldc, M, slabs, &p, &use8)) return -1;
     const bool direct = p.n_split == 1;
-    if (!direct) {
-        SlabSrc& d = h->ws.deferred;
+    if (!direct) {          // (only planned when the consumer takes slabs)
+        SlabSrc& d = *o.defer;
         d.base = h->ws.splitk; d.nslab = p.n_split; d.stride = (size_t)M * ldc;
-        d.dyn_W = 0; d.n_tiles = 0; d.ldc = ldc; d.CT = L.N / 64; d.m_dev = h->ws.dyn ? h->ws.n_active : nullptr;
+        d.dyn_W = 0; d.n_tiles = 0; d.ldc = ldc; d.CT = L.N / 64; d.m_dev = o.rs ? o.rs->n_active : nullptr;
     }
     (void)aux;
     constexpr bool with_bias = EPI != EPI_NONE, lrelu = EPI == EPI_BIAS_LRELU;
-    if (h->ws.fuse_compact) {          // set by the round loop for the first launch of a round only
-        h->ws.fuse_compact = false;
-        if (!row_map || M > rows::FUSE_MAX_WINDOWS) { set_error("launch_rows: fused compaction on a launch that cannot carry it"); return 1; }
-        return use8 ? launch_rows_as<3, 8, true>(h, L, A, lda, C, ldc, M, s, row_map, p, direct, with_bias, lrelu)
-                    : launch_rows_as<4, 5, true>(h, L, A, lda, C, ldc, M, s, row_map, p, direct, with_bias, lrelu);
+    if (o.repack_log) {          // asked for by the round loop on the first launch of a round only
+        if (!o.rs || !o.row_map || M > rows::FUSE_MAX_WINDOWS) { set_error("launch_rows: fused compaction on a launch that cannot carry it"); return 1; }
+        return use8 ? launch_rows_as<3, 8, true>(h, L, A, lda, C, ldc, M, s, o, p, direct, with_bias, lrelu)
+                    : launch_rows_as<4, 5, true>(h, L, A, lda, C, ldc, M, s, o, p, direct, with_bias, lrelu);
     }
-    return use8 ? launch_rows_as<3, 8, false>(h, L, A, lda, C, ldc, M, s, row_map, p, direct, with_bias, lrelu)
-                : launch_rows_as<4, 5, false>(h, L, A, lda, C, ldc, M, s, row_map, p, direct, with_bias, lrelu);
+    return use8 ? launch_rows_as<3, 8, false>(h, L, A, lda, C, ldc, M, s, o, p, direct, with_bias, lrelu)
+                : launch_rows_as<4, 5, false>(h, L, A, lda, C, ldc, M, s, o, p, direct, with_bias, lrelu);
 }
 
 template <int TAPS, int EPI, int TAG>
 static int launch_tile(gem_handle* h, const Layer& L, const float* A, int lda, const float* aux, float* C, int ldc, int M, int T,
-                       hipStream_t s, const int* row_map) {
+                       hipStream_t s, const GemmOpts& o) {
     if (TAPS == 1 && (EPI == EPI_BIAS || EPI == EPI_NONE || EPI == EPI_BIAS_LRELU)) {
-        const int rc = launch_rows<EPI>(h, L, A, lda, aux, C, ldc, M, s, row_map);
+        const int rc = launch_rows<EPI>(h, L, A, lda, aux, C, ldc, M, s, o);
         if (rc >= 0) return rc;
     }
+    // (only the few-rows kernel can re-pack: a launch that asked for it and ends up on a tiled kernel is an error)
+    if (o.repack_log) { set_error("launch_rows: fused compaction on a launch that cannot carry it"); return 1; }
     if (L.N % 128 == 0 && L.K % 32 == 0 && (long)((M + 127) / 128) * (L.N / 128) >= 3L * h->n_cu / 2 && h->ws.zero16 &&
-        !h->ws.defer_reduce)
-        return launch_glds_f32<TAPS, EPI>(h, L, A, lda, aux, C, ldc, M, T, s, row_map);
+        !o.defer)
+        return launch_glds_f32<TAPS, EPI>(h, L, A, lda, aux, C, ldc, M, T, s, o);
     // 128x128 tiles only when they still fill the chip (>= 2 workgroups per CU) and divide N
     const long big_blocks = (long)((M + 127) / 128) * (L.N / 128);
-    if (L.N % 128 == 0 && big_blocks >= 512) return launch_one<TAPS, EPI, 2, 2, TAG, 32>(h, L, A, lda, aux, C, ldc, M, T, s, row_map);
-    return launch_one<TAPS, EPI, 1, 1, TAG, 32>(h, L, A, lda, aux, C, ldc, M, T, s, row_map);
+    if (L.N % 128 == 0 && big_blocks >= 512) return launch_one<TAPS, EPI, 2, 2, TAG, 32>(h, L, A, lda, aux, C, ldc, M, T, s, o);
+    return launch_one<TAPS, EPI, 1, 1, TAG, 32>(h, L, A, lda, aux, C, ldc, M, T, s, o);
 }
 
 int launch_gemm(gem_handle* h, const Layer& L, int epi, const float* A, int lda, const float* aux, float* C, int ldc, int M,
-                int T, hipStream_t s, int family, const int* row_map) {
+                int T, hipStream_t s, int family, const GemmOpts& o) {
     if (L.K % BK_MIN != 0 || L.N % 64 != 0 || lda % 4 != 0) {
         set_error("launch_gemm: dimensions must be padded (K%32, N%64, lda%4)");
         return 1;
     }
+    if (o.defer) *o.defer = SlabSrc{};
     if (M <= 0) return 0;
-    h->ws.deferred = SlabSrc{};
     Profile::Rec rec;
     const bool prof = h->prof.on && family >= 0;
     if (prof) {
@@ -485,27 +486,27 @@ int launch_gemm(gem_handle* h, const Layer& L, int epi, const float* A, int lda,
         GEM_HIP(hipEventCreate(&rec.b));
         rec.family = family;
         rec.flops = 2.0 * M * (double)L.N * L.K * L.taps;
-        if (h->ws.dyn && L.taps == 1) {      // rows = active windows of this round, known only on the device
-            rec.log_idx = h->ws.cur_log;
+        if (o.rs && L.taps == 1) {           // rows = active windows of this round, known only on the device
+            rec.log_idx = o.rs->log_idx;
             rec.flops_per_window = 2.0 * (double)L.N * L.K;
         }
         GEM_HIP(hipEventRecord(rec.a, s));
     }
     int rc = 1;
     if (h->precision != GEM_PRECISION_F32 && L.wb_hi && (h->precision == GEM_PRECISION_BF16 || L.wb_lo)) {
-        rc = launch_gemm_bf16(h, L, epi, h->precision == GEM_PRECISION_BF16 ? 1 : 3, A, lda, aux, C, ldc, M, T, s, row_map);
+        rc = launch_gemm_bf16(h, L, epi, h->precision == GEM_PRECISION_BF16 ? 1 : 3, A, lda, aux, C, ldc, M, T, s, o);
     } else if (L.taps == 1) {
         // TAG 1 = the decoder_input products (forward and backward-data): the dominant kernel gets its own symbol
-        if (family == 0 && epi == EPI_BIAS) rc = launch_tile<1, EPI_BIAS, 1>(h, L, A, lda, aux, C, ldc, M, T, s, row_map);
-        else if (epi == EPI_BIAS) rc = launch_tile<1, EPI_BIAS, 0>(h, L, A, lda, aux, C, ldc, M, T, s, row_map);
-        else if (epi == EPI_NONE) rc = launch_tile<1, EPI_NONE, 0>(h, L, A, lda, aux, C, ldc, M, T, s, row_map);
-        else if (epi == EPI_BIAS_LRELU) rc = launch_tile<1, EPI_BIAS_LRELU, 1>(h, L, A, lda, aux, C, ldc, M, T, s, row_map);
+        if (family == 0 && epi == EPI_BIAS) rc = launch_tile<1, EPI_BIAS, 1>(h, L, A, lda, aux, C, ldc, M, T, s, o);
+        else if (epi == EPI_BIAS) rc = launch_tile<1, EPI_BIAS, 0>(h, L, A, lda, aux, C, ldc, M, T, s, o);
+        else if (epi == EPI_NONE) rc = launch_tile<1, EPI_NONE, 0>(h, L, A, lda, aux, C, ldc, M, T, s, o);
+        else if (epi == EPI_BIAS_LRELU) rc = launch_tile<1, EPI_BIAS_LRELU, 1>(h, L, A, lda, aux, C, ldc, M, T, s, o);
         else set_error("launch_gemm: unsupported epilogue for a linear layer");
     } else if (L.taps == 3) {
-        if (epi == EPI_BIAS) rc = launch_tile<3, EPI_BIAS, 0>(h, L, A, lda, aux, C, ldc, M, T, s, row_map);
-        else if (epi == EPI_BIAS_LRELU) rc = launch_tile<3, EPI_BIAS_LRELU, 0>(h, L, A, lda, aux, C, ldc, M, T, s, row_map);
-        else if (epi == EPI_MASK) rc = launch_tile<3, EPI_MASK, 0>(h, L, A, lda, aux, C, ldc, M, T, s, row_map);
-        else if (epi == EPI_NONE) rc = launch_tile<3, EPI_NONE, 0>(h, L, A, lda, aux, C, ldc, M, T, s, row_map);
+        if (epi == EPI_BIAS) rc = launch_tile<3, EPI_BIAS, 0>(h, L, A, lda, aux, C, ldc, M, T, s, o);
+        else if (epi == EPI_BIAS_LRELU) rc = launch_tile<3, EPI_BIAS_LRELU, 0>(h, L, A, lda, aux, C, ldc, M, T, s, o);
+        else if (epi == EPI_MASK) rc = launch_tile<3, EPI_MASK, 0>(h, L, A, lda, aux, C, ldc, M, T, s, o);
+        else if (epi == EPI_NONE) rc = launch_tile<3, EPI_NONE, 0>(h, L, A, lda, aux, C, ldc, M, T, s, o);
     } else {
         set_error("launch_gemm: taps must be 1 or 3");
     }

@@ -1,7 +1,7 @@
 // fp32 MFMA GEMM for FEW rows (gfx950): the linear layers around the latent code for one sequence,
 //
 //   forward        pre0[M, T*256] = z[perm[M], 2048] . Wf^T + bf      decoder_input composed with the first decoder conv
-//                                                                     (compose_front, gem_api.hip; SeqConvVAE.py:62,67-75,131-135)
+//                                                                     (compose_front, weights.hip; SeqConvVAE.py:62,67-75,131-135)
 //   backward-data  dz[M, 2048]    = dpre0[M, T*256] . Wf              (its adjoint; the VAE is frozen, optimizer.py:261-270)
 //
 // (or the separate decoder_input products [M, 2048] x [2048, 5120] and back when the composition is off; the shapes quoted

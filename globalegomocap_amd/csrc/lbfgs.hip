@@ -712,24 +712,23 @@ int launch_lbfgs_debug_read(gem_handle* h, int B, gem_lbfgs_debug_state* out, fl
     return 0;
 }
 
-static AdvArgs make_args(gem_handle* h, const gem_lbfgs_opts& o) {
+static AdvArgs make_args(gem_handle* h, const gem_lbfgs_opts& o, const RoundSet& rs, const SlabSrc& grad) {
     Workspace& w = h->ws;
     AdvArgs a;
     a.state = w.state; a.f = w.f; a.gnew = w.dz;
-    a.trace = (w.round >= 0 && w.round < TRACE_ROUNDS) ? w.trace + (size_t)w.round * w.Bmax : nullptr;
+    a.trace = rs.trace;
     a.x = w.x; a.d = w.d; a.g = w.g; a.gp = w.gp; a.bg0 = w.bg0; a.bg1 = w.bg1; a.trial = w.trial; a.S = w.S; a.Y = w.Y;
     a.trial_b = h->precision == GEM_PRECISION_BF16 ? w.trial_b : nullptr;
     a.phase_arr = w.phase;
-    a.slot_of = w.dyn ? w.slot_of : nullptr;
-    a.next_perm = w.dyn ? w.next_perm : nullptr; a.next_slot_of = w.dyn ? w.next_slot_of : nullptr; a.next_count = w.dyn ? w.next_count : nullptr;
-    a.gslab = w.dyn ? w.grad_slab : SlabSrc{};
+    a.slot_of = rs.slot_of;
+    a.next_perm = rs.next_perm; a.next_slot_of = rs.next_slot_of; a.next_count = rs.next_count;
+    a.gslab = grad;
     a.clk = w.lbfgs_clk;
     a.Dp = h->Dp; a.hist_cap = w.hist_cap; a.o = o;        // hist_cap: power of two (gem_create)
     return a;
 }
 
-int launch_lbfgs_init(gem_handle* h, int B, const gem_lbfgs_opts& o, hipStream_t s) {
-    (void)o;
+int launch_lbfgs_init(gem_handle* h, int B, hipStream_t s) {
     const size_t n = (size_t)B * h->Dp;
     hipLaunchKernelGGL(lbfgs_init_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, h->ws.state, h->ws.phase, h->ws.trial, h->ws.x,
                        B, h->Dp);
@@ -737,8 +736,8 @@ int launch_lbfgs_init(gem_handle* h, int B, const gem_lbfgs_opts& o, hipStream_t
     return 0;
 }
 
-int launch_lbfgs_advance(gem_handle* h, int B, const gem_lbfgs_opts& o, hipStream_t s) {
-    AdvArgs a = make_args(h, o);
+int launch_lbfgs_advance(gem_handle* h, int B, const gem_lbfgs_opts& o, const RoundSet& rs, const SlabSrc& grad, hipStream_t s) {
+    AdvArgs a = make_args(h, o, rs, grad);
     Profile::Rec rec;
     const bool prof = h->prof.on;
     if (prof) {
@@ -768,7 +767,7 @@ int launch_lbfgs_advance(gem_handle* h, int B, const gem_lbfgs_opts& o, hipStrea
 // Stable partition of the windows: those still iterating first (slots [0, n)), finished ones behind.
 // One 1024-thread block; B is at most a few thousand.
 // zero_after: that many n_log entries BEHIND log_slot are zeroed here (the per-round counters of a stage whose rounds hand out their
-// slots atomically, gem_api.hip stage_begin) -- by this kernel rather than by a hipMemsetAsync node, so that inside a captured graph
+// slots atomically, stage.hip begin_rounds) -- by this kernel rather than by a hipMemsetAsync node, so that inside a captured graph
 // the zeroing is ordered like every other kernel of the call
 __global__ __launch_bounds__(1024) void compact_kernel(const int* __restrict__ phase_arr, int B, int T, int* __restrict__ perm,
                                                        int* __restrict__ slot_of, int* __restrict__ n_active, int force_all,
@@ -809,14 +808,14 @@ __global__ __launch_bounds__(1024) void compact_kernel(const int* __restrict__ p
     if (tid < zero_after) log_slot[1 + tid] = 0;
 }
 
-int launch_compact(gem_handle* h, int B, int force_all, hipStream_t s, int zero_after) {
+int launch_compact(gem_handle* h, const RoundSet& rs, int B, int force_all, hipStream_t s, int zero_after) {
     Workspace& w = h->ws;
     if (B > 65536) { set_error("compact: more than 65536 windows per call"); return 1; }      // (64 windows per thread of the scan)
-    if (zero_after < 0 || zero_after > 1024 || (w.log_pos % N_LOG) + zero_after >= N_LOG) { set_error("compact: bad counter range"); return 1; }
-    hipLaunchKernelGGL(compact_kernel, dim3(1), dim3(1024), 0, s, w.phase, B, h->T, w.perm, w.slot_of, w.n_active, force_all,
-                       w.n_log + (w.log_pos % N_LOG), zero_after);
+    const long slot = rs.log_idx % N_LOG;
+    if (zero_after < 0 || zero_after > 1024 || slot + zero_after >= N_LOG) { set_error("compact: bad counter range"); return 1; }
+    hipLaunchKernelGGL(compact_kernel, dim3(1), dim3(1024), 0, s, w.phase, B, h->T, rs.perm, rs.slot_of, rs.n_active, force_all,
+                       w.n_log + slot, zero_after);
     GEM_HIP(hipGetLastError());
-    w.cur_log = w.log_pos++;
     return 0;
 }
 

@@ -479,7 +479,7 @@ int tail_cap_workgroups(const gem_handle* h, const std::vector<Layer>& dec, int 
     return (tail_can_share_cu(dec, start, h->T, h->J) ? 10 : 5) * h->n_cu;
 }
 
-int launch_tail(gem_handle* h, const TailArgs& a, size_t lds_bytes, hipStream_t s) {
+int launch_tail(gem_handle* h, const TailArgs& a, size_t lds_bytes, hipStream_t s, const RoundSet* rs) {
     static PerDeviceOnce attr_once;
     if (attr_once.need(h->cfg.device)) {
         const void* ks[] = {reinterpret_cast<const void*>(decoder_tail_kernel<1, 8>), reinterpret_cast<const void*>(decoder_tail_kernel<2, 8>),
@@ -500,7 +500,7 @@ int launch_tail(gem_handle* h, const TailArgs& a, size_t lds_bytes, hipStream_t 
         for (int i = 0; i < a.n; ++i) per_window += 2.0 * 3.0 * a.fwd[i].K * a.fwd[i].N * a.e.T;
         if (!a.forward_only) per_window *= 2.0;
         rec.flops = per_window * a.B;
-        if (h->ws.dyn) { rec.log_idx = h->ws.cur_log; rec.flops_per_window = per_window; }      // rows = active windows of the round
+        if (rs) { rec.log_idx = rs->log_idx; rec.flops_per_window = per_window; }      // rows = active windows of the round
         GEM_HIP(hipEventRecord(rec.a, s));
     }
     const int wgs = (a.B + a.G - 1) / a.G;

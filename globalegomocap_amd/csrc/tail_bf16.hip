@@ -591,7 +591,7 @@ int build_tail_bf16_stream(gem_handle* h, StageNet& net) {
     return 0;
 }
 
-int launch_tail_bf16(gem_handle* h, const TailB16Args& a, size_t lds_bytes, hipStream_t s) {
+int launch_tail_bf16(gem_handle* h, const TailB16Args& a, size_t lds_bytes, hipStream_t s, const RoundSet* rs) {
     // at most one workgroup per CU: the one-workgroup-per-CU instances (lower latency; 5, 4 or 3 row tiles as planned by the
     // caller: tail_bf16_row_tiles); more: the two-per-CU instance
     const int wgs = (a.B + a.G - 1) / a.G;
@@ -636,7 +636,7 @@ int launch_tail_bf16(gem_handle* h, const TailB16Args& a, size_t lds_bytes, hipS
         for (int i = 0; i < a.n; ++i) per_window += 2.0 * 3.0 * a.fwd[i].K * a.fwd[i].N * a.e.T;
         if (!a.forward_only) per_window *= 2.0;
         rec.flops = per_window * a.B;
-        if (h->ws.dyn) { rec.log_idx = h->ws.cur_log; rec.flops_per_window = per_window; }
+        if (rs) { rec.log_idx = rs->log_idx; rec.flops_per_window = per_window; }
         GEM_HIP(hipEventRecord(rec.a, s));
     }
     note_kernel(h, kfn);

@@ -1081,12 +1081,8 @@ __global__ __launch_bounds__(256) void fc_reduce_reparam_kernel(const float* __r
 static int linear_gemm(gem_trainer* t, const Layer& L, int epi, const float* A, int lda, float* C, int ldc, int M, hipStream_t s,
                        const float* reparam_eps = nullptr) {
     gem_handle* h = t->h;
-    h->ws.defer_reduce = true;
-    const int rc = launch_gemm(h, L, epi, A, lda, nullptr, C, ldc, M, t->T, s, -1);
-    h->ws.defer_reduce = false;
-    const SlabSrc d = h->ws.deferred;
-    h->ws.deferred = SlabSrc{};
-    if (rc) return rc;
+    SlabSrc d;
+    if (launch_gemm(h, L, epi, A, lda, nullptr, C, ldc, M, t->T, s, -1, GemmOpts(nullptr, nullptr, &d))) return 1;
     if (d.base && reparam_eps && epi == EPI_BIAS && d.dyn_W == 0 && ldc == 2 * t->Dp) {
         hipLaunchKernelGGL(fc_reduce_reparam_kernel, dim3((unsigned)((M * (t->Dp / 4) + 255) / 256)), dim3(256), 0, s, (const float*)d.base, d.nslab, d.stride,
                            L.bias, reparam_eps, C, t->z, M, t->D, t->Dp);

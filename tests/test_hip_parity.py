@@ -1106,7 +1106,7 @@ def test_zero_weights_stop_at_the_first_evaluation_and_return_the_decoded_start(
 @pytest.mark.parametrize("mode,B,tol_x,tol_e,tol_g", [("f32", 64, 2e-5, 1e-4, 1e-3), ("f32", 1344, 2e-5, 1e-4, 1e-3), ("bf16", 64, 3e-3, 5e-2, 4e-1)])
 def test_composed_front_layer_against_the_two_layers_it_replaces(torch_cuda, monkeypatch, mode, B, tol_x, tol_e, tol_g):
     """decoder_input followed by the first decoder conv (no activation between them: SeqConvVAE.py:62,67-75,131-135) runs as ONE
-    composed linear layer (compose_front, gem_api.hip; weights composed in fp64 at load time).  The same engine with
+    composed linear layer (compose_front, weights.hip; weights composed in fp64 at load time).  The same engine with
     GEM_NO_FRONT=1 keeps the two layers: decoded pose, energies and dE/dz of both must agree to rounding (fp32: summation order;
     bf16: one rounding of the composed weights against two bf16 products with a bf16 intermediate), in the tail path (64
     windows) and in the all-batched path (1344 windows), and a whole stage must end at the same energies."""
@@ -1405,4 +1405,48 @@ def test_empty_batches_are_no_ops(torch_cuda):
     _, g2, st = eng.optimize_windows(seq["est_local"], seq["cams"], seq["heat"], f1, mb, e2, e2, wl, wg)
     torch.cuda.synchronize()
     assert torch.isfinite(g2).all()
+    eng.close()
+
+
+def test_no_call_leaves_state_behind_for_the_next(torch_cuda):
+    """One engine, the TINY network, B = 5: energy_grad returns the same bits (E, parts, dz, X) before anything else, after an
+    optimize_stage in f32, after an optimize_stage in bf16, and after a gem_lbfgs_debug_begin + one advance that is then abandoned.
+    What a call runs is decided by that call alone (its route and its rounds' sets are values handed down, stage.hip), so the
+    evaluation must not be able to tell what ran on the handle before it."""
+    import torch
+    B = 5
+    sd = vae_schema.synthetic_state_dict(TINY, 11)
+    eng = _engine(TINY, max_windows=8)
+    eng.load_vae(0, sd)
+    seq = synth.make_sequence(n_frames=8 * (B - 1) + 10, seed=21)
+    est = np.asarray(seq["estimated_local_skeleton"], dtype=np.float32)
+    heat = np.asarray(seq["heatmap_list"], dtype=np.float32)
+    starts = (8 * np.arange(B)).astype(np.int32)
+    pose = np.stack([est[s:s + 10] for s in starts])
+    mb = eng.mean_bone_length(est)
+    rng = np.random.default_rng(5)
+    z = rng.normal(size=(B, TINY.latent_dim)).astype(np.float32)
+    eps = rng.normal(size=(B, TINY.latent_dim)).astype(np.float32)
+
+    def evaluation():
+        out = eng.energy_grad(0, z, pose, mb, _ew(W_ALL), heat, starts)
+        torch.cuda.synchronize()
+        return [t.cpu().numpy().copy() for t in out]
+
+    def same(after, what):
+        for name, a, b in zip(("E", "parts", "dz", "X"), first, after):
+            assert np.isfinite(a).all() and a.tobytes() == b.tobytes(), (what, name, float(np.abs(a - b).max()))
+
+    first = evaluation()
+    assert np.abs(first[2]).max() > 0
+    eng.optimize_stage(0, pose, mb, eps, _ew(W_ALL), heat, starts)
+    same(evaluation(), "after an f32 stage")
+    eng.set_precision("bf16")
+    eng.optimize_stage(0, pose, mb, eps, _ew(W_ALL), heat, starts)
+    eng.set_precision("f32")
+    same(evaluation(), "after a bf16 stage")
+    for slots in (2, 1):          # slots handed out by lbfgs_advance (two alternating sets), then compact_kernel between the rounds
+        eng.lbfgs_debug_begin(z, slots)
+        eng.lbfgs_debug_advance(first[0], first[2], None, 0)
+        same(evaluation(), "after an abandoned run of the solver alone (slots = %d)" % slots)
     eng.close()
