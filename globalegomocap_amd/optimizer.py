@@ -23,6 +23,7 @@ from . import _capi
 from .camera import FisheyeCamera
 from .engine import WindowEngine, energy_weights, stats_to_numpy, raise_if_degenerate, LOCAL_STAGE, GLOBAL_STAGE
 from .errors import calculate_errors
+from .report import result_dir, result_pose_dict, write_result_outputs
 from .sequence import (SEQ_LEN, OVERLAP, window_starts, cut_windows, merge_batches, final_smooth,
                        relative_global_numpy, to_global_numpy)
 from .skeleton import KINEMATIC_PARENTS
@@ -238,32 +239,15 @@ def main(data_id, camera_model_path, vae_weight, gmm_weight, smoothness_weight, 
         from .sequence import final_smooth as _smooth
         final_optimized_seq = _smooth(final_optimized_seq)
     if save_pose:
-        # optimizer.py:469-483: out/<dataset>/<sequence>/result_pose.pkl under the working directory, the four sequences in the
-        # containers the reference pickles (merge_batches' lists of [15,3] frames; the optimised one an ndarray after the smoothing)
-        dataset_dir, seq_name = os.path.split(data_id)
-        out_dir = "out/{}/{}".format(os.path.split(dataset_dir)[1], seq_name)
+        # optimizer.py:469-483: out/<dataset>/<sequence>/result_pose.pkl under the working directory
+        out_dir = result_dir("out", data_id)
         os.makedirs(out_dir, exist_ok=True)
         with open(os.path.join(out_dir, "result_pose.pkl"), "wb") as f:
-            pickle.dump({"estimated_pose": list(final_estimated_seq),
-                         "optimized_pose": final_optimized_seq if final_smooth is True else list(np.asarray(final_optimized_seq)),
-                         "mid_optimized_pose": list(mid_estimated_seq), "gt_pose": list(final_gt_seq)}, f)
-    if save:
-        from .meshes import write_result_meshes
-        dataset_dir, seq_name = os.path.split(data_id)
-        write_result_meshes(opt.engine, os.path.join(mesh_root, os.path.split(dataset_dir)[1], seq_name), np.asarray(final_estimated_seq),
-                            final_optimized_d if device_metrics else np.asarray(final_optimized_seq), np.asarray(final_gt_seq))
-    if render is not None:
-        from .render import write_result_frames
-        dataset_dir, seq_name = os.path.split(data_id)
-        write_result_frames(opt.engine, os.path.join(render, os.path.split(dataset_dir)[1], seq_name), np.asarray(final_estimated_seq),
-                            final_optimized_d if device_metrics else np.asarray(final_optimized_seq), np.asarray(final_gt_seq))
-    if render_camera is not None:
-        from .render import write_result_camera_frames
-        dataset_dir, seq_name = os.path.split(data_id)
-        n = len(final_estimated_seq)
-        write_result_camera_frames(opt.engine, os.path.join(render_camera, os.path.split(dataset_dir)[1], seq_name), np.asarray(final_estimated_seq),
-                                   final_optimized_d if device_metrics else np.asarray(final_optimized_seq), cams[:n], heat[:n],
-                                   np.asarray(final_gt_seq))
+            pickle.dump(result_pose_dict(final_estimated_seq, final_optimized_seq, mid_estimated_seq, final_gt_seq, final_smooth is True), f)
+    if save or render is not None or render_camera is not None:
+        sequences = (np.asarray(final_estimated_seq), final_optimized_d if device_metrics else np.asarray(final_optimized_seq),
+                     np.asarray(final_gt_seq))
+        write_result_outputs(opt.engine, data_id, sequences, mesh_root if save else None, render, render_camera, cams, heat)
     if device_metrics:
         errors = opt.engine.calculate_errors(final_estimated_seq, mid_estimated_seq, final_optimized_d, final_gt_seq)
     else:

@@ -7,9 +7,9 @@ The reference's `optimize_whole_sequence.py` walks the chunk directories of a se
 float64 are undone by a kernel), all windows of a batch of chunks go through the optimiser together (BASELINE configs[1]: a
 2000-frame sequence = 20 chunks = 240 windows per call), batches are pipelined (the next one's files arrive while this one
 computes), and the per-chunk merge / smoothing / error report run on the device as well.  How bytes reach the device -- reader
-threads, copy streams, pinned buffers -- is `staging`'s business; this module holds the chunk-file reader, the batch pipeline
-(`_Pipeline`) and the report.  Results, keys, printed summary and the order in which the reparameterisation noise is
-drawn (chunk by chunk, window by window, local then global) follow the reference.
+threads, copy streams, pinned buffers -- is `staging`'s business; this module holds the chunk-file reader and the batch pipeline
+(`_Pipeline`); what a chunk's report is and the files it may be written to are `report`'s.  Results, keys, printed summary and
+the order in which the reparameterisation noise is drawn (chunk by chunk, window by window, local then global) follow the reference.
 
     python -m globalegomocap_amd.whole_sequence --data_path data/jian3
 
@@ -24,7 +24,7 @@ under the reprojected skeletons.
 import ctypes as C
 import os
 import pickle
-from collections import OrderedDict, namedtuple
+from collections import namedtuple
 from types import SimpleNamespace
 
 import numpy as np
@@ -34,34 +34,9 @@ from . import _capi, staging
 from .staging import (Laps, Scratch, cpus_near, drain, natural_key, reader_pool, report_stream, side_by_side, staging_buffer,      # noqa: F401  (cpus_near, natural_key: part of this module's interface)
                       thread_state)
 from .optimizer import SequenceOptimizer, GLOBAL_VAE_PATH, LOCAL_VAE_PATH
-from .errors import calculate_errors
-from .sequence import (SEQ_LEN, OVERLAP, window_starts, cut_windows, merge_batches, merge_chunks, final_smooth,
-                       relative_global_numpy, to_global_numpy)
-
-SUMMARY_LINES = (          # (label printed by the reference, key) in print order, None = separator
-    ("Average original global pose mpjpe", "original_global_mpjpe"), ("Average mid global pose mpjpe", "mid_global_mpjpe"),
-    ("Average optimized global pose mpjpe", "optimized_global_mpjpe"), None,
-    ("Average original cam pose error", "original_camera_pos_error"), ("Average optimized cam pose error", "optimized_camera_pos_error"), None,
-    ("Average original aligned cam pose error", "original_aligned_camera_pos_error"),
-    ("Average optimized aligned cam pose error", "optimized_aligned_camera_pos_error"), None,
-    ("Average original_aligned_global_mpjpe", "original_aligned_global_mpjpe"), ("Average aligned_mid_seq_mpjpe", "aligned_mid_seq_mpjpe"),
-    ("Average optimized_aligned_global_mpjpe", "optimized_aligned_global_mpjpe"), None,
-    ("Average aligned original global pose mpjpe", "aligned_original_mpjpe"),
-    ("Average aligned mid local pose mpjpe", "aligned_mid_optimized_mpjpe"),
-    ("Average aligned optimized global pose mpjpe", "aligned_optimized_mpjpe"), None,
-    ("Average bone length aligned original global pose mpjpe", "bone_length_aligned_original_mpjpe"),
-    ("Average bone length aligned mid local pose mpjpe", "bone_length_aligned_mid_optimized_mpjpe"),
-    ("Average bone length aligned optimized global pose mpjpe", "bone_length_aligned_optimized_mpjpe"), None,
-)
-
-
-QUALITY_LINES = (          # the report without ground truth, in the order of its keys: (label, key), None = separator
-    ("Average estimated heatmap response", "estimated_heatmap_response"), ("Average optimized heatmap response", "optimized_heatmap_response"), None,
-    ("Average estimated bone length rms", "estimated_bone_length_rms"), ("Average optimized bone length rms", "optimized_bone_length_rms"), None,
-    ("Average estimated acceleration", "estimated_acceleration"), ("Average optimized acceleration", "optimized_acceleration"), None,
-    ("Average optimized displacement", "optimized_displacement"), None,
-)
-QUALITY_KEYS = tuple(line[1] for line in QUALITY_LINES if line is not None)
+from .report import (QUALITY_LINES, QUALITY_KEYS, SUMMARY_LINES, batch_reports, chunk_reports, report_inputs, result_pose_dict,      # noqa: F401  (the three tables: part of this module's interface)
+                     sequence_result, write_result_outputs)
+from .sequence import SEQ_LEN, OVERLAP, window_starts
 
 
 def list_chunks(data_dir):
@@ -275,208 +250,17 @@ def _resident_chunk(c, ground_truth=True):
     return p
 
 
-# ------------------------------------------------------------------------------------------------------------------ the report
-def _report_inputs(chunks, starts, est_cat, cams_cat, seq_len, overlap, upload, ground_truth=True):
-    """The report's half that does not depend on the optimiser's result (equal chunks -- the reference's 100-frame chunks: the
-    sequences main() returns besides the optimised one, for ALL windows of the batch at once, the overlap merges vectorised over
-    the chunks), computed and uploaded while the files are still arriving.  ground_truth=False: no "gt_m" / "gt_d"."""
-    idx = np.concatenate(starts)[:, None] + np.arange(seq_len)[None]
-    cam_w = cams_cat[idx]
-    est_m = merge_chunks(to_global_numpy(relative_global_numpy(est_cat[idx], cam_w), cam_w), len(chunks), overlap)
-    gt_m = merge_chunks(np.concatenate([c["gt"] for c in chunks])[idx], len(chunks), overlap) if ground_truth else None
-    # (stage one's global sequence: C0 (C0^-1 C_t) X as ONE transform per frame, composed here in the reference's order --
-    # utils/utils.py:99-112 then optimizer.py:302-308 -- so that the result-dependent half is a multiply-add)
-    A = np.matmul(cam_w[:, :1], np.matmul(np.linalg.inv(cam_w[:, 0])[:, None], cam_w))
-    rep = {"mid_A": np.ascontiguousarray(np.moveaxis(A[..., :3, :], (-2, -1), (0, 1))[..., None]), "est_m": est_m,      # mid_A [3,4,W,T,1]
-           "est_d": upload(est_m.reshape(-1, 15, 3), torch.float64)}
-    if ground_truth:
-        rep.update(gt_m=gt_m, gt_d=upload(gt_m.reshape(-1, 15, 3), torch.float64))
-    return rep
-
-
-def _mid_sequences(report, mid_np, n_chunks, overlap):
-    """Stage one's merged global sequences [n_chunks,fpc,J,3] (host float64) from its local poses and `report["mid_A"]`."""
-    A, X = report["mid_A"], np.ascontiguousarray(np.moveaxis(mid_np.astype(np.float64), -1, 0))          # X [3,W,T,J]
-    mid_g = np.empty(mid_np.shape, dtype=np.float64)
-    for d in range(3):
-        mid_g[..., d] = A[d, 0] * X[0] + A[d, 1] * X[1] + A[d, 2] * X[2] + A[d, 3]
-    return merge_chunks(mid_g, n_chunks, overlap)
-
-
-def _quality_dict(row):
-    """One chunk's seven report entries from its raw row (the order of QUALITY_KEYS)."""
-    return OrderedDict(zip(QUALITY_KEYS, row.tolist()))
-
-
-def _quality_rows(engine, est_d, opt_d, frames, n_chunks):
-    """`sequence_quality` of the estimated sequences and of the optimised ones (those also against the estimated ones), enqueued on the
-    current stream: a device tensor [n_chunks,7] in the order of QUALITY_KEYS.  `frames`: (cams, heat, frame0, mean_bone) of the
-    batch, see `WindowEngine.sequence_quality`."""
-    q_est = engine.sequence_quality(est_d, *frames, n_chunks)
-    q_opt = engine.sequence_quality(opt_d, *frames, n_chunks, ref=est_d)
-    return torch.stack([q_est[:, 0], q_opt[:, 0], q_est[:, 1], q_opt[:, 1], q_est[:, 2], q_opt[:, 2], q_opt[:, 3]], dim=1)
-
-
-def _chunk_views(n_chunks, est_d, opt_d, gt_d):
-    """Per chunk the (estimated, optimised, ground-truth or None) merged sequences as they lie on the device: what `_save_meshes`
-    reads, so that no sequence goes up again."""
-    fpc = est_d.shape[0] // n_chunks
-    cut = lambda t, k: None if t is None else t[k * fpc:(k + 1) * fpc]          # noqa: E731
-    return [(cut(est_d, k), cut(opt_d, k), cut(gt_d, k)) for k in range(n_chunks)]
-
-
-def _quality_batched(engine, report, mid_np, opt_global, n_chunks, overlap, smooth, frames, want_mid, lap):
-    """`_report_batched` for chunks without ground truth: the reports of all chunks of a batch as two `sequence_quality` calls, read
-    back with the optimised sequences.  -> per chunk (report dict, estimated / optimised sequence, None, the raw row, stage one's
-    sequence when `want_mid`)."""
-    fpc = report["est_m"].shape[1]
-    mid_m = _mid_sequences(report, mid_np, n_chunks, overlap) if want_mid else None
-    opt_d = engine.merge_windows(opt_global, n_chunks, overlap=overlap, smooth=smooth)          # [n_chunks*fpc,15,3] f64, device
-    q = _quality_rows(engine, report["est_d"], opt_d, frames, n_chunks)
-    lap("report: merge + quality kernels enqueued")
-    q = q.cpu().numpy()
-    opt_m = opt_d.cpu().numpy().reshape(n_chunks, fpc, 15, 3)
-    lap("report: read-back")
-    on_device = _chunk_views(n_chunks, report["est_d"], opt_d, None)
-    return [(_quality_dict(q[k]), report["est_m"][k], opt_m[k], None, q[k], None if mid_m is None else mid_m[k], on_device[k]) for k in range(n_chunks)]
-
-
-def _report_batched(engine, report, mid_np, opt_global, n_chunks, overlap, smooth, upload, lap):
-    """The error reports of all chunks of a batch as ONE library call, read back with ONE synchronisation (`report`: what
-    `_report_inputs` prepared).  -> per chunk (error dict, estimated / optimised / ground-truth sequence, the report's raw row,
-    stage one's sequence)."""
-    mid_m = _mid_sequences(report, mid_np, n_chunks, overlap)
-    fpc = report["est_m"].shape[1]
-    lap("report: stage-one sequences (host float64)")
-    opt_d = engine.merge_windows(opt_global, n_chunks, overlap=overlap, smooth=smooth)          # [n_chunks*fpc,15,3] f64, device
-    mid_d = upload(mid_m.reshape(n_chunks * fpc, 15, 3), torch.float64)
-    reps = engine.calculate_errors_chunks(report["est_d"], mid_d, opt_d, report["gt_d"], n_chunks)
-    lap("report: merge + error kernels enqueued")
-    reps = reps.cpu().numpy()
-    opt_m = opt_d.cpu().numpy().reshape(n_chunks, fpc, 15, 3)
-    lap("report: read-back")
-    rows, on_device = [], _chunk_views(n_chunks, report["est_d"], opt_d, report["gt_d"])
-    for k in range(n_chunks):
-        res = OrderedDict(zip(engine.ERROR_KEYS, reps[k, :17].tolist()))
-        res["joints_error"] = reps[k, 17:].copy()
-        rows.append((res, report["est_m"][k], opt_m[k], report["gt_m"][k], reps[k], mid_m[k], on_device[k]))
-    return rows
-
-
-def _report_per_chunk(engine, chunks, mid_np, opt_global, seq_len, overlap, smooth, device_metrics, frames=None):
-    """The reports chunk by chunk (chunks of different lengths, or device_metrics=False).  -> per chunk (error dict, estimated /
-    optimised / ground-truth sequence, None, stage one's sequence), or None for a chunk too short for a window.  `frames` (cams,
-    heat, first frame of every chunk, mean_bone of the batch): the chunks have no ground truth -- (report dict, estimated /
-    optimised sequence, None, the raw row, stage one's sequence), each chunk's row read back before the next is enqueued."""
-    rows, w0 = [], 0
-    for c in chunks:
-        nw = len(c["starts"])
-        sl = slice(w0, w0 + nw)
-        w0 += nw
-        if nw == 0:
-            rows.append(None)
-            continue
-        loc_w, cam_w = cut_windows(c["est_local"], c["starts"], seq_len), cut_windows(c["cams"], c["starts"], seq_len)
-        est_seq = merge_batches(to_global_numpy(relative_global_numpy(loc_w, cam_w), cam_w), overlap)
-        mid_seq = merge_batches(to_global_numpy(relative_global_numpy(mid_np[sl], cam_w), cam_w), overlap)
-        if frames is not None:
-            ci = len(rows)
-            est_d = engine._f64(np.asarray(est_seq))
-            opt_seq_d = engine.merge_windows(opt_global[sl], 1, overlap=overlap, smooth=smooth)
-            q = _quality_rows(engine, est_d, opt_seq_d, (frames[0], frames[1], frames[2][ci:ci + 1], frames[3][ci:ci + 1]), 1).cpu().numpy()[0]
-            rows.append((_quality_dict(q), np.asarray(est_seq), opt_seq_d.cpu().numpy(), None, q, np.asarray(mid_seq)))
-            continue
-        gt_seq = merge_batches(cut_windows(c["gt"], c["starts"], seq_len), overlap)
-        if device_metrics:
-            opt_seq_d = engine.merge_windows(opt_global[sl], 1, overlap=overlap, smooth=smooth)
-            res = engine.calculate_errors(est_seq, mid_seq, opt_seq_d, gt_seq)
-            opt_seq = opt_seq_d.cpu().numpy()
-        else:
-            opt_seq = merge_batches(opt_global[sl].cpu().numpy(), overlap)
-            if smooth:
-                opt_seq = final_smooth(opt_seq)
-            res = calculate_errors(est_seq, mid_seq, opt_seq, gt_seq)
-        rows.append((res, np.asarray(est_seq), np.asarray(opt_seq), np.asarray(gt_seq), None, np.asarray(mid_seq)))
-    return rows
-
-
-def _save_pose(out_dir, row, smooth):
-    """`<out_dir>/result_pose.pkl` of one chunk: the reference's keys and containers (optimizer.py:469-483 -- merge_batches' lists of
-    [15,3] frames; the optimised sequence an ndarray after the final smoothing), `gt_pose` only where there is a ground truth."""
+def _save_pose(out_dir, report, smooth):
+    """`<out_dir>/result_pose.pkl` of one chunk (`report.result_pose_dict`)."""
     os.makedirs(out_dir, exist_ok=True)
-    d = {"estimated_pose": list(row[1]), "optimized_pose": np.asarray(row[2]) if smooth else list(np.asarray(row[2])),
-         "mid_optimized_pose": list(row[5])}
-    if row[3] is not None:
-        d["gt_pose"] = list(row[3])
     with open(os.path.join(out_dir, "result_pose.pkl"), "wb") as f:
-        pickle.dump(d, f)
-
-
-def _save_meshes(engine, mesh_root, name, row):
-    """One chunk's mesh folders, named as at optimizer.py:486-498: <mesh_root>/<dataset>/<chunk>/..., from the sequences on the
-    device where the report left them there (row[6]), else from the row's host arrays.  With a ground truth the estimated and the
-    optimised sequence are aligned to it, as in the reference; without, nothing is aligned and there is no third folder."""
-    from .meshes import write_result_meshes
-    dataset_dir, seq_name = os.path.split(os.path.normpath(name))
-    est, opt, gt = row[6] if len(row) > 6 and row[6] is not None else (row[1], row[2], row[3])
-    write_result_meshes(engine, os.path.join(mesh_root, os.path.split(dataset_dir)[1], seq_name), est, opt, gt)
-
-
-def _save_frames(engine, render_root, name, row):
-    """One chunk's rendered frames, <render_root>/<dataset>/<chunk>/frame_%04d.png and overview_*.png (`_save_meshes`' naming and
-    sequences): with a ground truth the estimated and the optimised sequence are aligned to it and all three are overlaid."""
-    from .render import write_result_frames
-    dataset_dir, seq_name = os.path.split(os.path.normpath(name))
-    est, opt, gt = row[6] if len(row) > 6 and row[6] is not None else (row[1], row[2], row[3])
-    write_result_frames(engine, os.path.join(render_root, os.path.split(dataset_dir)[1], seq_name), est, opt, gt)
-
-
-def _save_camera_frames(engine, render_root, name, row, cams, heat):
-    """One chunk as its camera saw it, <render_root>/<dataset>/<chunk>/camera_%04d.png (`_save_frames`' naming and sequences):
-    `cams` / `heat` are the chunk's frames on the device; merged frame f is the chunk's frame f."""
-    from .render import write_result_camera_frames
-    dataset_dir, seq_name = os.path.split(os.path.normpath(name))
-    est, opt, gt = row[6] if len(row) > 6 and row[6] is not None else (row[1], row[2], row[3])
-    F = len(est)
-    write_result_camera_frames(engine, os.path.join(render_root, os.path.split(dataset_dir)[1], seq_name), est, opt, cams[:F], heat[:F], gt)
-
-
-def _sequence_result(rows, title, verbose):
-    """One sequence's return value from its chunks' report rows: (summary, per-chunk error dicts, estimated_pose, optimized_pose,
-    gt_pose), the summary printed as the reference prints it (under `title` when there is one)."""
-    results, raw = [r[0] for r in rows], [r[4] for r in rows]
-    summary = OrderedDict()
-    if rows and rows[0][3] is None:          # chunks without ground truth: the mean of the seven report entries, no ground-truth sequence
-        mean = np.mean(np.stack(raw), axis=0)
-        summary.update(zip(QUALITY_KEYS, mean.tolist()))
-        if verbose:
-            if title is not None:
-                print("sequence: {}".format(title))
-            for line in QUALITY_LINES:
-                print("-----------------------------------------" if line is None else "{}: {}".format(line[0], summary[line[1]]))
-            print("-------------------------------------------------------------")
-        return (summary, results, np.concatenate([r[1] for r in rows]), np.concatenate([r[2] for r in rows]), None)
-    if all(x is not None for x in raw):          # (every chunk of the sequence came as a row of the device report: one mean)
-        mean = np.mean(np.stack(raw), axis=0)
-        for i, k in enumerate(results[0]):
-            summary[k] = mean[17:].copy() if k == "joints_error" else float(mean[i])
-    else:
-        for k in results[0]:
-            summary[k] = (np.mean([r[k] for r in results], axis=0) if k == "joints_error"
-                          else float(np.average([r[k] for r in results])))
-    if verbose:
-        if title is not None:
-            print("sequence: {}".format(title))
-        for line in SUMMARY_LINES:
-            print("-----------------------------------------" if line is None else "{}: {}".format(line[0], summary[line[1]]))
-        print("joints error is: {}".format(summary["joints_error"]))
-        print("-------------------------------------------------------------")
-    # the three pose sequences as arrays [frames,15,3] (iterating them yields the [15,3] frames the reference's lists hold)
-    return (summary, results) + tuple(np.concatenate([r[i] for r in rows]) if rows else np.empty((0, 15, 3)) for i in (1, 2, 3))
+        pickle.dump(result_pose_dict(report.est, report.opt, report.mid, report.gt, smooth), f)
 
 
 # ------------------------------------------------------------------------------------------------------------------ the batch pipeline
-_heat_pool = {}                   # device -> per batch in flight: [frame buffer, file-image arena, Scratch] (kept between calls)
+# device -> per batch in flight one slot, kept between calls: `frames`, the frame buffer its heat-maps are gathered into; `arena`, the
+# images of its files side by side; `scratch`, the Scratch of its small uploads
+_heat_pool = {}
 _noise_pool = {}
 N_BUFFERS = 3                     # batches in flight: one computing, one arriving, one being reported
 
@@ -530,7 +314,7 @@ def _settings(camera_model_path, vae_weight=0.0, gmm_weight=0.0, smoothness_weig
 class _Pipeline:
     """The private driver behind `optimize_sequences` and `optimize_recordings`: `groups[g]` are the chunk sources (_Source) of
     sequence g.  It holds one call's batches and what their stages share: the settings, the optimiser, the device's buffers
-    (`slots`: one set per batch in flight), the reader pools, every future handed to a pool, and the report rows filed per
+    (`slots`: one per batch in flight, see `_heat_pool`), the reader pools, every future handed to a pool, and the ChunkReports filed per
     sequence.
 
     Per batch: `start` (its files start moving), `prepare` (everything that needs neither the heat-maps nor the device's
@@ -543,11 +327,11 @@ class _Pipeline:
         spans = groups if cfg.per_sequence else [[s for g in groups for s in g]]          # a batch does not cross these
         lists = [g[i:i + (n or len(g))] for g in spans for i in range(0, len(g), n or len(g))]
         self.batches = [_Batch(i, l) for i, l in enumerate(lists)]
-        self.rows = [[] for _ in groups]
+        self.reports = [[] for _ in groups]
         self.device = torch.device("cuda", torch.cuda.current_device())
         self.parse_pool, self.read_pool = reader_pool("parse", 8), reader_pool("read", 8, cpus_near(self.device))
         self.noise_pool = reader_pool("noise", 1)
-        self.slots = _heat_pool.setdefault(self.device, [[None, None, Scratch(self.device)] for _ in range(N_BUFFERS)])
+        self.slots = _heat_pool.setdefault(self.device, [SimpleNamespace(frames=None, arena=None, scratch=Scratch(self.device)) for _ in range(N_BUFFERS)])
         self.submitted = []                          # every future handed to a pool (drained on the way out, whatever happens)
 
     def slot(self, b):
@@ -565,10 +349,10 @@ class _Pipeline:
         sizes = [os.path.getsize(f) for f in files]          # (FileNotFoundError here, like the reference's open())
         at, room, total = side_by_side(sizes, _PAD)
         slot = self.slot(b)
-        if slot[1] is None or slot[1].numel() < total:
-            slot[1] = None
-            slot[1] = torch.empty(total, dtype=torch.uint8, device=self.device)
-        b.images = [slot[1][o:o + r] for o, r in zip(at.tolist(), room.tolist())]
+        if slot.arena is None or slot.arena.numel() < total:
+            slot.arena = None
+            slot.arena = torch.empty(total, dtype=torch.uint8, device=self.device)
+        b.images = [slot.arena[o:o + r] for o, r in zip(at.tolist(), room.tolist())]
         b.reading = [self.read_pool.submit(read_file, f, self.device, img, sz) for f, img, sz in zip(files, b.images, sizes)]
         b.parsing = [self.parse_pool.submit(parse_chunk, s.what, True, self.cfg.ground_truth) for s in b.sources]
         self.submitted.extend(b.reading + b.parsing)
@@ -609,27 +393,27 @@ class _Pipeline:
         b.frame_lo = np.array([lo for lo, _ in bounds], dtype=np.int64)
         lap("window tables")
         slot = self.slot(b)
-        slot[2].reset(len(est_cat) * (45 * 4 + 16 * 8 + 8 + 3 * 45 * 8) + 16 * n_win + 8192)
+        slot.scratch.reset(len(est_cat) * (45 * 4 + 16 * 8 + 8 + 3 * 45 * 8) + 16 * n_win + 8192)
         b.prep = self.opt.prepare(est_cat, cams_cat, np.concatenate(starts), np.concatenate(chunk_of), bounds, timings=cfg.timings,
-                                  upload=slot[2].upload)
+                                  upload=slot.scratch.upload)
         # the batch's frame buffer (one shape of heat-map: the chunks' frames side by side)
         frames = sum(c["n"] for c in b.chunks)
         shapes = {tuple(c["heat_shape"]) for c in b.chunks}
         b.heat, b.dests = None, [None] * len(b.chunks)
         if len(shapes) == 1 and frames:
             hs = next(iter(shapes))
-            if slot[0] is None or slot[0].shape[0] < frames or tuple(slot[0].shape[1:]) != hs:
-                slot[0] = None
-                slot[0] = torch.empty((frames,) + hs, dtype=torch.float32, device=self.device)
-            b.heat = slot[0][:frames]
+            if slot.frames is None or slot.frames.shape[0] < frames or tuple(slot.frames.shape[1:]) != hs:
+                slot.frames = None
+                slot.frames = torch.empty((frames,) + hs, dtype=torch.float32, device=self.device)
+            b.heat = slot.frames[:frames]
             b.dests = [b.heat[lo:hi] for lo, hi in bounds]
         # (where every heat-map's raw data lie in the ARENA of file images: the file's place in the arena + the array's place in the file)
-        located = [c["heat_offsets"] + (b.images[i].data_ptr() - slot[1].data_ptr()) for i, c in enumerate(b.chunks) if c["heat_via"] == LOCATED]
-        b.offsets = slot[2].upload(np.concatenate(located), torch.int64) if located else None
+        located = [c["heat_offsets"] + (b.images[i].data_ptr() - slot.arena.data_ptr()) for i, c in enumerate(b.chunks) if c["heat_via"] == LOCATED]
+        b.offsets = slot.scratch.upload(np.concatenate(located), torch.int64) if located else None
         lap("small uploads")
         b.report = None
         if cfg.device_metrics and b.counts and min(b.counts) == max(b.counts) and b.counts[0] > 0:
-            b.report = _report_inputs(b.chunks, starts, est_cat, cams_cat, cfg.seq_len, cfg.overlap, slot[2].upload, cfg.ground_truth)
+            b.report = report_inputs(b.chunks, starts, est_cat, cams_cat, cfg.seq_len, cfg.overlap, slot.scratch.upload, cfg.ground_truth)
         lap("report preparation")
 
     def fire(self, b):
@@ -644,7 +428,7 @@ class _Pipeline:
         for i in located:
             ev, _ = b.reading[i].result()             # (the file's last copy has been issued: its event is recorded)
             cur.wait_event(ev)
-        arena = self.slot(b)[1]
+        arena = self.slot(b).arena
         kinds = {(b.chunks[i]["heat_dtype"], b.chunks[i]["heat_fortran"], tuple(b.chunks[i]["heat_shape"])) for i in located}
         if b.heat is not None and len(located) == len(b.chunks) and len(kinds) == 1 and len(b.heat) <= 65535:
             # every chunk's file image lies in ONE arena and their frames side by side in the batch's frame buffer: one launch picks all
@@ -681,7 +465,8 @@ class _Pipeline:
         lap("enqueue")
 
     def finish(self, b):
-        """Batch b's results: waits for the device, merges / smooths / scores on it, files the report rows per sequence."""
+        """Batch b's results: waits for the device, merges / smooths / scores on it, writes the files asked for and files the chunks'
+        reports per sequence."""
         # on a stream of its own, behind the batch's LAST kernel only: on the optimiser's stream the read-back would queue up
         # behind the next batch's whole device call, which is already enqueued there
         cfg, lap, e = self.cfg, self.lap, self.opt.engine
@@ -698,45 +483,38 @@ class _Pipeline:
             lap("report: stage-one poses to the host")
             frames = None
             if not cfg.ground_truth:
-                # the report without ground truth reads the batch's frame buffers (slot[0], which batch k+3 fills again): its rows
+                # the report without ground truth reads the batch's frame buffers (its slot's, which batch k+3 fills again): its rows
                 # are read back here, like the error rows
                 heat_d, mb = b.heat_d.contiguous(), b.prep["mean_bone_chunks"].contiguous()
                 frames = (b.prep["cams"], heat_d, torch.from_numpy(b.frame_lo).to(self.device), mb)
                 for t in (heat_d, mb):
                     t.record_stream(rs)
-            if b.report is not None and frames is not None:
-                rows = _quality_batched(e, b.report, mid_np, opt_global, len(b.chunks), cfg.overlap, bool(cfg.final_smooth), frames,
-                                        cfg.save_pose is not None, lap)
-            elif b.report is not None:
-                rows = _report_batched(e, b.report, mid_np, opt_global, len(b.chunks), cfg.overlap, bool(cfg.final_smooth),
-                                       self.slot(b)[2].upload, lap)
+            if b.report is not None:
+                reports = batch_reports(e, b.report, mid_np, opt_global, len(b.chunks), cfg.overlap, bool(cfg.final_smooth),
+                                        upload=self.slot(b).scratch.upload, lap=lap, frames=frames, want_mid=cfg.save_pose is not None)
             else:
-                rows = _report_per_chunk(e, b.chunks, mid_np, opt_global, cfg.seq_len, cfg.overlap, bool(cfg.final_smooth), cfg.device_metrics,
-                                         frames)
+                reports = chunk_reports(e, b.chunks, mid_np, opt_global, cfg.seq_len, cfg.overlap, bool(cfg.final_smooth), cfg.device_metrics,
+                                        frames)
             view_heat, view_cams = None, None
             if cfg.render_camera is not None:
                 # the camera's view reads the batch's frame buffers too; its files are complete (the device has read the frames) before
-                # this returns, three batches before slot[0] is filled again
+                # this returns, three batches before the slot's frame buffer is filled again
                 view_heat, view_cams = b.heat_d.contiguous(), b.prep["cams"]
                 for t in (view_heat, view_cams):
                     t.record_stream(rs)
             b.heat_d = None
-            for ci, (src, row) in enumerate(zip(b.sources, rows)):
-                if row is not None:
-                    if cfg.save:
-                        _save_meshes(e, cfg.mesh_root, src.name, row)
-                    if cfg.render is not None:
-                        _save_frames(e, cfg.render, src.name, row)
-                    if cfg.render_camera is not None:
-                        lo = int(b.frame_lo[ci])
-                        _save_camera_frames(e, cfg.render_camera, src.name, row, view_cams[lo:], view_heat[lo:])
-                    row = row[:6]
-                    self.rows[src.group].append(row)
+            for ci, (src, r) in enumerate(zip(b.sources, reports)):
+                if r is not None:
+                    name = os.path.normpath(src.name)
+                    write_result_outputs(e, name, r.sequences(), cfg.mesh_root if cfg.save else None, cfg.render, cfg.render_camera,
+                                         view_cams, view_heat, int(b.frame_lo[ci]))
+                    r.drop_views()          # (they alias this batch's slot, which batch k+3 fills again)
+                    self.reports[src.group].append(r)
                     if cfg.save_pose is not None:
-                        _save_pose(os.path.join(cfg.save_pose, os.path.basename(os.path.normpath(src.name))), row, bool(cfg.final_smooth))
+                        _save_pose(os.path.join(cfg.save_pose, os.path.basename(name)), r, bool(cfg.final_smooth))
                     if cfg.ground_truth and cfg.verbose and \
-                            row[0]["bone_length_aligned_optimized_mpjpe"] > row[0]["bone_length_aligned_mid_optimized_mpjpe"]:
-                        print(row[0])
+                            r.result["bone_length_aligned_optimized_mpjpe"] > r.result["bone_length_aligned_mid_optimized_mpjpe"]:
+                        print(r.result)
             lap("report: result dicts" if b.report is not None else "sequences + reports")
 
     def run(self, titles):
@@ -758,7 +536,7 @@ class _Pipeline:
             if any(b.pending is not None for b in self.batches):
                 torch.cuda.synchronize()      # (an exception left device work behind that reads this call's buffers)
         self.lap("readers drained")
-        out = [_sequence_result(rows, title if len(titles) > 1 else None, self.cfg.verbose) for rows, title in zip(self.rows, titles)]
+        out = [sequence_result(reports, title if len(titles) > 1 else None, self.cfg.verbose) for reports, title in zip(self.reports, titles)]
         self.lap("summaries")
         return out
 

@@ -11,6 +11,8 @@ import numpy as np
 import pytest
 
 import camera_view_twin as T
+from pipeline_checks import (CAMERA_N, IMG, SIZE, check_camera_tree as _check_camera_tree, check_folder, check_tree, same_bits as _same_bits,
+                             write_recording as _write_recording)
 from globalegomocap_amd.camera import DEFAULT_CALIBRATION
 
 pytestmark = pytest.mark.gpu
@@ -402,43 +404,6 @@ def test_write_camera_frames_through_small_buffers(env, tmp_path, monkeypatch):
 
 
 # ------------------------------------------------------------------------------------------------------------------ 7. end to end
-SIZE = 26
-CAMERA_N = 48
-IMG = (64, 48)
-
-
-def _write_recording(root, n, seed):
-    from globalegomocap_amd import synth_recording as S
-    par = S.random_parameters(n, seed=seed)
-    heat64 = S.paraboloid_heatmaps(par["centres"], par["radii"])
-    names = ["f_%d.mat" % k for k in range(n)]
-    return S.write_recording(str(root), heat64, par["depth"], names, np.arange(n) % 7 == 3, np.arange(n) % 5 == 1, par["rows"], par["gt"])
-
-
-def _same_bits(x, y):
-    assert list(x[0]) == list(y[0]) and len(x[1]) == len(y[1])
-    for rx, ry in zip([x[0]] + x[1], [y[0]] + y[1]):
-        for k in rx:
-            assert np.array_equal(np.asarray(rx[k], dtype=np.float64).view(np.uint64), np.asarray(ry[k], dtype=np.float64).view(np.uint64)), k
-    for i in (2, 3, 4):
-        assert (x[i] is None and y[i] is None) or np.array_equal(x[i], y[i]), i
-
-
-def _check_camera_tree(env, base, est, opt, gt, cams, heat, others=()):
-    """camera_%04d.png for every frame under `base` (beside `others`), CAMERA_N pixels each way (`small_images`); frame 3 equals
-    `camera_scanlines` of the sequences, the ground truth moved onto the optimised sequence where there is one."""
-    from globalegomocap_amd import render as R
-    n = len(est)
-    assert sorted(os.listdir(base)) == sorted(["camera_%04d.png" % f for f in range(n)] + list(others))
-    trio = [est, opt] + ([gt] if gt is not None else [])
-    colours = [R.PALETTE[k] for k in list(R.PALETTE)[:len(trio)]]
-    want = R.camera_scanlines(env, trio, cams[:n], heat[:n], colours, align_to=[None, None, opt][:len(trio)]).cpu().numpy()
-    got = R.read_png(os.path.join(base, "camera_0003.png"))
-    assert got.shape == (CAMERA_N, CAMERA_N, 3) and np.array_equal(got, _image_of(want, 3, CAMERA_N))
-    assert (got != 255).any()
-    return got
-
-
 @pytest.fixture
 def small_images(monkeypatch):
     """The pipeline's images are small where it asks for the default sizes."""
@@ -540,3 +505,74 @@ def test_main_writes_the_camera_view(env, chunk_dirs, small_images, tmp_path, mo
                              np.asarray(data_["camera_pose_list"]), np.asarray(data_["heatmap_list"], dtype=np.float32))
     tinted = (got[..., 0] >= 148) & (got[..., 0] < 255) & (got[..., 2] >= 189) & (got[..., 2] < 255)          # (no skeleton colour has that much blue)
     assert (got == np.array((31, 119, 180), dtype=np.uint8)).all(-1).any() and tinted.any()
+
+
+SHORT = 18          # frames of the shorter second chunk: two windows
+
+
+@pytest.fixture(scope="module")
+def two_chunk_dirs(env, golden, tmp_path_factory):
+    """Two chunks of one recording as pickles: <tmp>/equal/studio with 26 and 26 frames, <tmp>/unequal/studio with 26 and the first
+    18 of the second."""
+    from globalegomocap_amd import prepare as P
+    from helpers import sd_from_npz
+    tmp = tmp_path_factory.mktemp("outputs")
+    n = 2 * SIZE + 1
+    hd, dd, traj, gtp = _write_recording(tmp / "rec", n, seed=23)
+    rec = P.prepare_sequence(traj, hd, dd, gtp, 0, n, fps=25, test_size=SIZE, verbose=False)
+    assert len(rec) == 2
+    names = [c.name for c in rec.chunks]
+    rec.write_chunks(str(tmp / "equal" / "studio"))
+    rec.write_chunk(0, str(tmp / "unequal" / "studio" / names[0]))
+    os.makedirs(str(tmp / "unequal" / "studio" / names[1]))
+    with open(str(tmp / "unequal" / "studio" / names[1] / "test_data.pkl"), "wb") as f:
+        pickle.dump({k: v[:SHORT] for k, v in rec.chunk_dict(1).items()}, f)
+    lt = golden("lbfgs_tiny")
+    kw = dict(global_vae_path=sd_from_npz(lt, "global/"), local_vae_path=sd_from_npz(lt, "local/"), verbose=False)
+    return dict(tmp=tmp, kw=kw, names=names)
+
+
+@pytest.mark.parametrize("lengths", [(SIZE, SIZE), (SIZE, SHORT)], ids=["equal chunks: batched report", "unequal chunks: per-chunk report"])
+def test_every_output_of_two_chunks(env, two_chunk_dirs, small_images, lengths):
+    """One call with `save`, `render`, `render_camera` and `save_pose` on a directory of two chunks: the result is bit for bit that of
+    the call without them, and every chunk's files -- the second's too, whose sequences and frames lie behind the first's in the
+    batch's buffers -- hold that chunk's slices of the returned sequences, its camera views over its own cameras and heat-maps."""
+    import torch
+    from globalegomocap_amd import whole_sequence as ws
+    from globalegomocap_amd.errors import align_sequence
+    tmp, kw, names = two_chunk_dirs["tmp"], two_chunk_dirs["kw"], two_chunk_dirs["names"]
+    case = "equal" if lengths[0] == lengths[1] else "unequal"
+    root = str(tmp / case / "studio")
+    out = {k: tmp / ("%s_%s" % (case, k)) for k in ("mesh", "frames", "camera", "pose")}
+    torch.manual_seed(31)
+    off = ws.optimize_directory(root, DEFAULT_CALIBRATION, **kw)
+    assert not any(p.exists() for p in out.values())
+    torch.manual_seed(31)
+    on = ws.optimize_directory(root, DEFAULT_CALIBRATION, save=True, mesh_root=str(out["mesh"]), render=str(out["frames"]),
+                               render_camera=str(out["camera"]), save_pose=str(out["pose"]), **kw)
+    _same_bits(on, off)
+    assert len(on[1]) == 2 and on[2].shape == on[3].shape == on[4].shape == (sum(lengths), 15, 3)
+    for k in ("mesh", "frames", "camera"):
+        assert os.listdir(str(out[k])) == ["studio"] and sorted(os.listdir(str(out[k] / "studio"))) == sorted(names), k
+    assert sorted(os.listdir(str(out["pose"]))) == sorted(names)
+    lo = 0
+    for name, n in zip(names, lengths):
+        est, opt, gt = (on[i][lo:lo + n] for i in (2, 3, 4))
+        lo += n
+        base = out["mesh"] / "studio" / name
+        assert sorted(os.listdir(str(base))) == ["gt_global_aligned", "input_global_aligned", "optimized_global_aligned"]
+        check_folder(str(base / "optimized_global_aligned"), align_sequence(opt, gt))
+        check_folder(str(base / "input_global_aligned"), align_sequence(est, gt))
+        check_folder(str(base / "gt_global_aligned"), gt)
+        check_tree(env, str(out["frames"] / "studio" / name), est, opt, gt)
+        c = ws.load_chunk(os.path.join(root, name))
+        assert c["n"] == n
+        _check_camera_tree(env, str(out["camera"] / "studio" / name), est, opt, gt, c["cams"], c["heat"])
+        assert os.listdir(str(out["pose"] / name)) == ["result_pose.pkl"]
+        with open(str(out["pose"] / name / "result_pose.pkl"), "rb") as f:
+            saved = pickle.load(f)
+        assert list(saved) == ["estimated_pose", "optimized_pose", "mid_optimized_pose", "gt_pose"]
+        assert isinstance(saved["estimated_pose"], list) and isinstance(saved["optimized_pose"], np.ndarray) and isinstance(saved["gt_pose"], list)
+        for key, want in (("estimated_pose", est), ("optimized_pose", opt), ("gt_pose", gt)):
+            assert np.array_equal(np.asarray(saved[key]), want), (name, key)
+        assert np.asarray(saved["mid_optimized_pose"]).shape == (n, 15, 3)

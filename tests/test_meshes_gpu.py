@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import mesh_twin as T
+from pipeline_checks import SIZE, check_folder as _check_folder, same_bits as _same_bits, write_recording as _write_recording
 from globalegomocap_amd.camera import DEFAULT_CALIBRATION
 
 pytestmark = pytest.mark.gpu
@@ -211,38 +212,6 @@ def test_defined_corners(env, capsys):
 
 
 # ------------------------------------------------------------------------------------------------------------------ end to end
-SIZE = 26
-
-
-def _write_recording(root, n, seed):
-    from globalegomocap_amd import synth_recording as S
-    par = S.random_parameters(n, seed=seed)
-    heat64 = S.paraboloid_heatmaps(par["centres"], par["radii"])
-    names = ["f_%d.mat" % k for k in range(n)]
-    return S.write_recording(str(root), heat64, par["depth"], names, np.arange(n) % 7 == 3, np.arange(n) % 5 == 1, par["rows"], par["gt"])
-
-
-def _sphere_centres(path):
-    assert os.path.getsize(path) == len(T.HEADER) + 349920 + 335400, path
-    v, c, t = T.read_ply(path)
-    return v[:15 * 762].reshape(15, 762, 3).mean(axis=1)
-
-
-def _check_folder(folder, want):
-    assert sorted(os.listdir(folder)) == ["out_%04d.ply" % f for f in range(len(want))], folder
-    for f in range(len(want)):
-        np.testing.assert_allclose(_sphere_centres(os.path.join(folder, "out_%04d.ply" % f)), want[f], rtol=0, atol=1e-9, err_msg="%s %d" % (folder, f))
-
-
-def _same_bits(x, y):
-    assert list(x[0]) == list(y[0]) and len(x[1]) == len(y[1])
-    for rx, ry in zip([x[0]] + x[1], [y[0]] + y[1]):
-        for k in rx:
-            assert np.array_equal(np.asarray(rx[k], dtype=np.float64).view(np.uint64), np.asarray(ry[k], dtype=np.float64).view(np.uint64)), k
-    for i in (2, 3, 4):
-        assert (x[i] is None and y[i] is None) or np.array_equal(x[i], y[i]), i
-
-
 @pytest.fixture(scope="module")
 def chunk_dirs(env, golden, tmp_path_factory):
     """One chunk of 26 frames with ground truth and the same without, as pickles under <tmp>/with_gt/studio and <tmp>/no_gt/studio."""

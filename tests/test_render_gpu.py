@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import render_twin as T
+from pipeline_checks import IMG, SIZE, check_tree as _check_tree, same_bits as _same_bits, write_recording as _write_recording
 from globalegomocap_amd.camera import DEFAULT_CALIBRATION
 
 pytestmark = pytest.mark.gpu
@@ -350,44 +351,6 @@ def test_write_frames_through_small_buffers(env, tmp_path, monkeypatch):
 
 
 # ------------------------------------------------------------------------------------------------------------------ end to end
-SIZE = 26
-IMG = (64, 48)
-
-
-def _write_recording(root, n, seed):
-    from globalegomocap_amd import synth_recording as S
-    par = S.random_parameters(n, seed=seed)
-    heat64 = S.paraboloid_heatmaps(par["centres"], par["radii"])
-    names = ["f_%d.mat" % k for k in range(n)]
-    return S.write_recording(str(root), heat64, par["depth"], names, np.arange(n) % 7 == 3, np.arange(n) % 5 == 1, par["rows"], par["gt"])
-
-
-def _same_bits(x, y):
-    assert list(x[0]) == list(y[0]) and len(x[1]) == len(y[1])
-    for rx, ry in zip([x[0]] + x[1], [y[0]] + y[1]):
-        for k in rx:
-            assert np.array_equal(np.asarray(rx[k], dtype=np.float64).view(np.uint64), np.asarray(ry[k], dtype=np.float64).view(np.uint64)), k
-    for i in (2, 3, 4):
-        assert (x[i] is None and y[i] is None) or np.array_equal(x[i], y[i]), i
-
-
-def _check_tree(env, base, est, opt, gt, monkeypatch):
-    """frame_%04d.png for every frame and one overview per sequence under `base`, 64 x 48 pixels (`small_images`);
-    frame 3 and the last overview equal `scanlines` of the sequences, the first two aligned to the ground truth where there is one."""
-    from globalegomocap_amd import render as R
-    trio = [est, opt] + ([gt] if gt is not None else [])
-    names = list(R.PALETTE)[:len(trio)]
-    assert sorted(os.listdir(base)) == sorted(["frame_%04d.png" % f for f in range(len(est))] + ["overview_%s.png" % n for n in names])
-    to = [gt, gt, None] if gt is not None else None
-    view = R.frames_view(env, trio, align_to=to, size=IMG)
-    colours = [R.PALETTE[n] for n in names]
-    frames = R.scanlines(env, trio, view, colours, align_to=to).cpu().numpy()
-    assert np.array_equal(R.read_png(os.path.join(base, "frame_0003.png")), _image_of(frames, 3, *IMG))
-    assert (_image_of(frames, 3, *IMG) != 255).any()
-    overviews = R.scanlines(env, trio, view, colours, overview=True, align_to=to).cpu().numpy()
-    assert np.array_equal(R.read_png(os.path.join(base, "overview_%s.png" % names[-1])), _image_of(overviews, len(trio) - 1, *IMG))
-
-
 @pytest.fixture
 def small_images(monkeypatch):
     """`write_result_frames` draws 64 x 48 images where the pipeline asks for its default size."""
@@ -428,7 +391,7 @@ def test_render_from_the_pipeline(env, chunk_dirs, small_images, monkeypatch, gr
     _same_bits(on, off)
     assert os.listdir(str(out)) == ["studio"] and os.listdir(str(out / "studio")) == [chunk_dirs["name"]]
     assert on[2].shape == on[3].shape == (SIZE, 15, 3) and (on[4] is None) == (not ground_truth)
-    _check_tree(env, str(out / "studio" / chunk_dirs["name"]), on[2], on[3], on[4], monkeypatch)
+    _check_tree(env, str(out / "studio" / chunk_dirs["name"]), on[2], on[3], on[4])
 
 
 def test_main_renders_under_the_given_root(env, chunk_dirs, small_images, tmp_path, monkeypatch):
@@ -452,4 +415,4 @@ def test_main_renders_under_the_given_root(env, chunk_dirs, small_images, tmp_pa
         assert np.array_equal(np.asarray(on[0][k]), np.asarray(off[0][k])), k
     for i in (1, 2, 3, 4):
         assert np.array_equal(np.asarray(on[i]), np.asarray(off[i])), i
-    _check_tree(env, str(tmp_path / "seen" / "studio-x" / "chunk_7"), np.asarray(on[1]), np.asarray(on[3]), np.asarray(on[4]), monkeypatch)
+    _check_tree(env, str(tmp_path / "seen" / "studio-x" / "chunk_7"), np.asarray(on[1]), np.asarray(on[3]), np.asarray(on[4]))
