@@ -165,6 +165,11 @@ SIGNATURES = {
     "gem_live_window": (C.c_int, [_P, C.POINTER(GemLiveBuffers), C.c_int64, C.c_int64, _P, _P, _P, _P, _P, _P]),
     "gem_live_emit": (C.c_int, [_P, C.POINTER(GemLiveBuffers), C.c_int64, C.c_int, _P, _P, _P, C.POINTER(C.c_double), _P, _P]),
     "gem_one_euro": (C.c_int, [_P, _P, C.c_int, C.c_int64, C.c_int, C.POINTER(C.c_double), _P, _P]),
+    "gem_bvh_layout": (C.c_int, [C.POINTER(C.c_int64)]),
+    "gem_bvh_tables": (C.c_int, [C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
+    "gem_bvh_rest": (C.c_int, [_P, C.c_int64, _P, _P, _P]),
+    "gem_bvh_channels": (C.c_int, [_P, C.c_int64, _P, _P, C.c_double, _P, _P]),
+    "gem_format_fields": (C.c_int, [_P, C.c_int64, C.c_int64, _P, _P, _P]),
 }
 
 _lib = None

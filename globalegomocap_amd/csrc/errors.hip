@@ -445,3 +445,4 @@ int launch_lift(gem_handle* h, const float* heat, const double* depth, int F, co
 #include "camera_view.h"               // gem_project_sequence, gem_render_camera
 #include "latent_tools.h"              // gem_latent_paths, gem_latent_report
 #include "live.h"                      // gem_live_push, gem_live_window, gem_live_emit, gem_one_euro
+#include "bvh.h"                       // gem_bvh_rest, gem_bvh_channels, gem_format_fields

@@ -190,7 +190,7 @@ class SequenceOptimizer:
 def main(data_id, camera_model_path, vae_weight, gmm_weight, smoothness_weight, bone_length_weight, weight_3d,
          reproj_weight, visualization=False, final_smooth=False, merge=True, save=False, save_pose=False,
          global_vae_path=GLOBAL_VAE_PATH, local_vae_path=LOCAL_VAE_PATH, eps=None, optimizer=None, return_stats=False,
-         device_metrics=False, mesh_root="out", render=None, render_camera=None):
+         device_metrics=False, mesh_root="out", render=None, render_camera=None, bvh=None, bvh_fps=None):
     """pickle in, poses out -- the reference's `main` (optimizer.py:311-507) for one chunk directory.
 
     Returns (errors OrderedDict[18], final_estimated_seq, mid_local_pose_seq, final_optimized_seq, final_gt_seq): lists of [15,3]
@@ -203,6 +203,8 @@ def main(data_id, camera_model_path, vae_weight, gmm_weight, smoothness_weight, 
     DIR/<dataset>/<chunk>/frame_%04d.png and overview_{estimated,optimized,gt}.png (`render.write_result_frames`).
     render_camera=DIR writes the chunk as its camera saw it, DIR/<dataset>/<chunk>/camera_%04d.png: the pickle's heat-maps under the
     three sequences, the ground truth moved onto the optimised one (`render.write_result_camera_frames`).
+    bvh=DIR writes the three sequences as animation, DIR/<dataset>/<chunk>/{estimated,optimized,gt}.bvh at `bvh_fps` frames per second
+    (default 25), the first two aligned to the ground truth (`bvh.write_result_bvh`).
     """
     if visualization:
         raise NotImplementedError("visualization opens open3d's viewer (optimizer.py:452-467), which this package does not have: "
@@ -244,10 +246,11 @@ def main(data_id, camera_model_path, vae_weight, gmm_weight, smoothness_weight, 
         os.makedirs(out_dir, exist_ok=True)
         with open(os.path.join(out_dir, "result_pose.pkl"), "wb") as f:
             pickle.dump(result_pose_dict(final_estimated_seq, final_optimized_seq, mid_estimated_seq, final_gt_seq, final_smooth is True), f)
-    if save or render is not None or render_camera is not None:
+    if save or render is not None or render_camera is not None or bvh is not None:
         sequences = (np.asarray(final_estimated_seq), final_optimized_d if device_metrics else np.asarray(final_optimized_seq),
                      np.asarray(final_gt_seq))
-        write_result_outputs(opt.engine, data_id, sequences, mesh_root if save else None, render, render_camera, cams, heat)
+        write_result_outputs(opt.engine, data_id, sequences, mesh_root if save else None, render, render_camera, cams, heat, bvh=bvh,
+                             bvh_fps=bvh_fps)
     if device_metrics:
         errors = opt.engine.calculate_errors(final_estimated_seq, mid_estimated_seq, final_optimized_d, final_gt_seq)
     else:

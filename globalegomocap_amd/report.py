@@ -215,13 +215,16 @@ def result_dir(root, data_id):
     return os.path.join(root, os.path.split(dataset_dir)[1], seq_name)
 
 
-def write_result_outputs(engine, data_id, sequences, mesh_root=None, render=None, render_camera=None, cams=None, heat=None, first_frame=0):
+def write_result_outputs(engine, data_id, sequences, mesh_root=None, render=None, render_camera=None, cams=None, heat=None, first_frame=0,
+                         bvh=None, bvh_fps=None):
     """One chunk's output files from `sequences` = (estimated, optimised, ground truth or None), host arrays or device tensors, each
     under `result_dir` of its own root and only where that root is given:
       mesh_root      the skeleton meshes, <chunk>/{optimized,input,gt}_global_aligned/out_%04d.ply (`meshes.write_result_meshes`);
       render         the frames, <chunk>/frame_%04d.png and overview_*.png (`render.write_result_frames`);
       render_camera  the chunk as its camera saw it, <chunk>/camera_%04d.png (`render.write_result_camera_frames`): `cams` / `heat`
-                     hold the chunk's frames from `first_frame` on; merged frame f is the chunk's frame f.
+                     hold the chunk's frames from `first_frame` on; merged frame f is the chunk's frame f;
+      bvh            the sequences as animation, <chunk>/{estimated,optimized,gt}.bvh at `bvh_fps` frames per second (default 25;
+                     `bvh.write_result_bvh`).
     With a ground truth the estimated and the optimised sequence are aligned to it and all three are written, as in the reference;
     without, nothing is aligned and there is no third sequence."""
     est, opt, gt = sequences
@@ -232,6 +235,9 @@ def write_result_outputs(engine, data_id, sequences, mesh_root=None, render=None
     if render_camera is not None:
         frames = slice(first_frame, first_frame + len(est))
         rendering.write_result_camera_frames(engine, result_dir(render_camera, data_id), est, opt, cams[frames], heat[frames], gt)
+    if bvh is not None:
+        from . import bvh as animation          # (`bvh` is an argument's name here)
+        animation.write_result_bvh(engine, result_dir(bvh, data_id), est, opt, gt, fps=25 if bvh_fps is None else bvh_fps)
 
 
 def result_pose_dict(est, opt, mid, gt, smooth):

@@ -19,7 +19,8 @@ QUALITY_LINES from the device (`WindowEngine.sequence_quality`).  `save_pose=DIR
 chunk to `DIR/<chunk name>/result_pose.pkl` on either route; `save=True` / `--save true` writes every chunk's skeleton meshes under
 `mesh_root` (`meshes`); `render=DIR` / `--render DIR` writes every chunk's frames as PNG images under DIR
 (`render`); `render_camera=DIR` / `--render_camera DIR` writes every chunk as its camera saw it, the heat-maps
-under the reprojected skeletons.
+under the reprojected skeletons; `bvh=DIR` / `--bvh DIR` writes every chunk's sequences as BVH animation files
+(`bvh`).
 """
 import ctypes as C
 import os
@@ -303,7 +304,8 @@ class _Batch:
 def _settings(camera_model_path, vae_weight=0.0, gmm_weight=0.0, smoothness_weight=0.001, bone_length_weight=0.01, weight_3d=0.01,
               reproj_weight=0.01, final_smooth=True, merge=True, global_vae_path=GLOBAL_VAE_PATH, local_vae_path=LOCAL_VAE_PATH,
               chunks_per_batch=None, optimizer=None, device_metrics=True, verbose=True, seq_len=SEQ_LEN, overlap=OVERLAP, timings=None,
-              per_sequence=False, ground_truth=True, save_pose=None, save=False, mesh_root="out", render=None, render_camera=None):
+              per_sequence=False, ground_truth=True, save_pose=None, save=False, mesh_root="out", render=None, render_camera=None, bvh=None,
+              bvh_fps=None):
     """The arguments of `optimize_sequences` / `optimize_recordings` behind the sequences themselves, as one object.
     (`gmm_weight` and `merge` are accepted and unused, as in the reference: SURVEY D4.)"""
     if not ground_truth and not device_metrics:
@@ -507,7 +509,7 @@ class _Pipeline:
                 if r is not None:
                     name = os.path.normpath(src.name)
                     write_result_outputs(e, name, r.sequences(), cfg.mesh_root if cfg.save else None, cfg.render, cfg.render_camera,
-                                         view_cams, view_heat, int(b.frame_lo[ci]))
+                                         view_cams, view_heat, int(b.frame_lo[ci]), bvh=cfg.bvh, bvh_fps=cfg.bvh_fps)
                     r.drop_views()          # (they alias this batch's slot, which batch k+3 fills again)
                     self.reports[src.group].append(r)
                     if cfg.save_pose is not None:
@@ -559,7 +561,8 @@ def optimize_sequences(data_dirs, camera_model_path, *args, **kwargs):
 
     Further arguments, positional or by keyword, in this order (defaults: `_settings`): vae_weight, gmm_weight, smoothness_weight,
     bone_length_weight, weight_3d, reproj_weight, final_smooth, merge, global_vae_path, local_vae_path, chunks_per_batch, optimizer,
-    device_metrics, verbose, seq_len, overlap, timings, per_sequence, ground_truth, save_pose, save, mesh_root, render, render_camera.
+    device_metrics, verbose, seq_len, overlap, timings, per_sequence, ground_truth, save_pose, save, mesh_root, render, render_camera,
+    bvh, bvh_fps.
 
     ground_truth=False: the chunks carry no ground truth (`prepare` with a scale).  Their pickles are not asked for
     `gt_global_skeleton`, every chunk's report is the seven entries of QUALITY_KEYS (`WindowEngine.sequence_quality` on the estimated
@@ -577,7 +580,11 @@ def optimize_sequences(data_dirs, camera_model_path, *args, **kwargs):
     render_camera=DIR: every chunk as its camera saw it, `DIR/<dataset>/<chunk>/camera_%04d.png`: the frame's heat-maps under the
     estimated (red), the optimised (blue) and the ground-truth sequence (green, moved onto the optimised one by one similarity: it
     lives in the studio's frame), projected with the reprojection term's arithmetic (`render.write_result_camera_frames`, from the
-    batch's frame buffers on the device).  DIR may be `render`'s DIR.  Results and reports do not depend on it."""
+    batch's frame buffers on the device).  DIR may be `render`'s DIR.  Results and reports do not depend on it.
+    bvh=DIR: every chunk as animation, `DIR/<dataset>/<chunk>/{estimated,optimized,gt}.bvh` at `bvh_fps` frames per second (default
+    25): a 19-node skeleton with the chunk's mean bone lengths and every frame keyed, the first two sequences aligned to the third
+    (`bvh.write_result_bvh`, made on the device).  With ground_truth=False: two files, unaligned.  Results and reports do not
+    depend on it."""
     cfg = _settings(camera_model_path, *args, **kwargs)
     lap = Laps(cfg.timings, log=True)          # developer timing (tools/whole_sequence_timing.py): wall time of the main thread's phases
     groups = []
@@ -620,11 +627,12 @@ def release_pools():
     """Give back what this module keeps between calls: the per-device frame buffers the readers fill, the pinned noise
     blocks and the mesh and frame writers' buffers, then (`staging.release`) the streams and the reader threads with their pinned staging buffers and device images.
     Not to be called while another call is in flight."""
-    from . import meshes, render
+    from . import bvh, meshes, render
     _heat_pool.clear()
     _noise_pool.clear()
     meshes.release()
     render.release()
+    bvh.release()
     staging.release()
     if torch.cuda.is_available():
         torch.cuda.empty_cache()
@@ -648,6 +656,8 @@ def _parser():
     p.add_argument("--render", default=None, metavar="DIR", help="write every chunk's frames as DIR/<dataset>/<chunk>/frame_%%04d.png")
     p.add_argument("--render_camera", default=None, metavar="DIR",
                    help="write every chunk as its camera saw it, DIR/<dataset>/<chunk>/camera_%%04d.png: heat-maps under the reprojected skeletons")
+    p.add_argument("--bvh", default=None, metavar="DIR", help="write every chunk as animation, DIR/<dataset>/<chunk>/{estimated,optimized,gt}.bvh")
+    p.add_argument("--bvh_fps", default=None, type=float, metavar="F", help="frames per second of the --bvh files (default 25)")
     p.add_argument("--final_smooth", default=True, type=truthy)
     p.add_argument("--merge", default=True, type=truthy)
     p.add_argument("--chunks_per_batch", type=int, default=None, help="chunks optimised per device call (default: all)")
@@ -660,7 +670,8 @@ def _cli(argv=None):
     a = _parser().parse_args(argv)
     optimize_directory(a.data_path, a.camera, a.vae, a.gmm, a.smooth, a.bone_length, a.weight_3d, a.reproj_weight,
                        final_smooth=a.final_smooth, merge=a.merge, chunks_per_batch=a.chunks_per_batch, ground_truth=a.ground_truth,
-                       save_pose=a.save_pose, save=a.save, mesh_root=a.mesh_root, render=a.render, render_camera=a.render_camera)
+                       save_pose=a.save_pose, save=a.save, mesh_root=a.mesh_root, render=a.render, render_camera=a.render_camera, bvh=a.bvh,
+                       bvh_fps=a.bvh_fps)
 
 
 if __name__ == "__main__":

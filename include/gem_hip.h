@@ -660,6 +660,54 @@ int gem_live_emit(gem_handle* h, const gem_live_buffers* b, int64_t window, int 
 int gem_one_euro(const double* d_seq, const double* d_times, int n_chunks, int64_t frames_per_chunk, int n_coords, const double* h_params,
                  double* d_out, void* stream);
 
+/* ---- Skeleton sequences as BVH animation: `bvh=DIR` / `--bvh DIR` ----
+ * The file's skeleton has 19 nodes on the 15 joints (node: parent, rest direction, joint; Y up, Z forward, +X the character's left):
+ *    0 Hips            -   -   midpoint of joints 7 and 11      1 Spine          0   0  (helper, zero offset)       2 Neck  1  +Y  joint 0
+ *    3 Right_collar    2   0   (helper)                         7 Left_collar    2   0  (helper)
+ *    4 Right_shoulder  3  -X   joint 1                          8 Left_shoulder  7  +X  joint 4
+ *    5 Right_elbow     4  -X   joint 2                          9 Left_elbow     8  +X  joint 5
+ *    6 Right_wrist     5  -X   joint 3                         10 Left_wrist     9  +X  joint 6
+ *   11 Right_hip       0  -X   joint 7                         15 Left_hip       0  +X  joint 11
+ *   12 Right_knee     11  -Y   joint 8                         16 Left_knee     15  -Y  joint 12
+ *   13 Right_ankle    12  -Y   joint 9                         17 Left_ankle    16  -Y  joint 13
+ *   14 Right_foot     13  +Z   joint 10                        18 Left_foot     17  +Z  joint 14
+ * A helper sits on its parent.  A frame has 60 channels: Hips' Xposition Yposition Zposition, then Zrotation Xrotation Yrotation of every
+ * node in the order above; a node's local rotation is Rz(a) Rx(b) Ry(c), degrees.  In the text every channel is one 16-byte field,
+ * "%15.6f" and a space (a newline after the 60th): a frame is 960 bytes.
+ * gem_bvh_layout: out[4] = nodes, channels per frame, bytes per field, bytes per frame.
+ * gem_bvh_tables: parents [19] (-1: the root), joint_of_node [19] (-1: Hips and the helpers), rest_dirs [19,3].  Both need no GPU. */
+int gem_bvh_layout(int64_t* out);
+int gem_bvh_tables(int32_t* parents, int32_t* joint_of_node, double* rest_dirs);
+
+/* The rest lengths: d_rest [19] float64 = for every node with a rest direction the mean over the n_frames (>= 1) frames of d_seq
+ * [n_frames,15,3] float64 of |pos(node) - pos(parent)|, 0 for the others; every joint is first moved by d_crt [13] (gem_sequence_align:
+ * c * (p . R) + t) unless NULL.  One workgroup, sums in a fixed order, no floating-point atomics: the same bits on every call.  Works
+ * on the current device. */
+int gem_bvh_rest(const double* d_seq, int64_t n_frames, const double* d_crt, double* d_rest, void* stream);
+
+/* The channels: d_channels [n_frames,60] float64 from d_seq and d_crt as above, float64 without fused multiply-adds.  With X_j joint j,
+ * P = (X7 + X11) / 2 and unit(v) = v / |v|: the position channels are P * unit_scale.  The root's frame G0 has the columns
+ * x = unit(X11 - X7), z = unit(x cross (X0 - P)), y = z cross x; the Neck's is built the same way from unit(X4 - X1) and the Spine's y
+ * column.  Every other node with one child that has a rest direction r gets G = G_parent S, S the shortest-arc rotation from r to
+ * l = G_parent^T unit(pos(child) - pos(node)): Rodrigues about r cross l by atan2(|r cross l|, r . l).  The wrists and feet inherit
+ * their parent's frame (three zeros).  A node's local rotation is G_parent^T G, and from it b = asin(R21), a = atan2(-R01, R11),
+ * c = atan2(-R20, R22); where |R21| > 1 - 1e-10: b = +-90, a = atan2(R10, R00), c = 0.
+ * Defined corners: |r cross l| < 1e-12 is the identity where r . l >= 0 and else a half turn about unit(r cross X), about
+ * unit(r cross Y) where |r_x| >= 0.9; a bone of length zero is the identity; where the root's or the Neck's x or x cross hint is
+ * shorter than 1e-12 the node takes its parent's frame (the root: the identity).  A NaN joint gives NaN channels in its frame.
+ * d_rest [19] (gem_bvh_rest) is the skeleton the channels are for; it must not be NULL, and no formula reads it: the rotations
+ * reproduce directions, the file's OFFSET lines the lengths.  Works on the current device. */
+int gem_bvh_channels(const double* d_seq, int64_t n_frames, const double* d_crt, const double* d_rest, double unit_scale,
+                     double* d_channels, void* stream);
+
+/* d_values [n_values] float64 -> d_text [n_values * 16] bytes: field i is "%15.6f" of value i as C and Python print it -- rounded to
+ * the nearest millionth, ties to even, on the value's exact binary expansion; "-0.000000" for a negative value that rounds to zero --
+ * and one separator: a newline after every values_per_line-th value, else a space.  nan, inf and -inf are written as such.  They, and
+ * a value that rounds to more than 9999999.999999 in magnitude (its field is filled with asterisks), add one to d_bad[0] and lower
+ * d_bad[1] to their line's index i / values_per_line: the caller sets d_bad to {0, -1} beforehand; nothing synchronises or reads
+ * back.  d_text must be 16-byte aligned: anything else is refused before the launch.  Works on the current device. */
+int gem_format_fields(const double* d_values, int64_t n_values, int64_t values_per_line, void* d_text, int64_t* d_bad, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
