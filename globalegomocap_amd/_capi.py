@@ -170,6 +170,9 @@ SIGNATURES = {
     "gem_bvh_rest": (C.c_int, [_P, C.c_int64, _P, _P, _P]),
     "gem_bvh_channels": (C.c_int, [_P, C.c_int64, _P, _P, C.c_double, _P, _P]),
     "gem_format_fields": (C.c_int, [_P, C.c_int64, C.c_int64, _P, _P, _P]),
+    "gem_jpeg_header": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, C.c_int64]),
+    "gem_jpeg_bound": (C.c_int64, [C.c_int, C.c_int]),
+    "gem_jpeg_encode": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, _P, C.c_int64, _P, _P, _P]),
 }
 
 _lib = None

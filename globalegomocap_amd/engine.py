@@ -549,6 +549,62 @@ class WindowEngine:
                                                _ptr(ids), _ptr(response), _stream()), self.lib)
         return (out, ids, response) if want_ids else out
 
+    # ------------------------------------------------------------------ JPEG images of rendered frames
+    def jpeg_header(self, width, height, quality=90):
+        """The 629 bytes in front of an image's entropy data (gem_jpeg_header), as `bytes`.  Needs no GPU work."""
+        buf = (C.c_ubyte * 629)()
+        if self.lib.gem_jpeg_header(int(width), int(height), int(quality), buf, 629) != 629:
+            _capi.check(1, self.lib)
+        return bytes(buf)
+
+    def jpeg_bound(self, width, height):
+        """The most bytes one width x height image's JPEG file can take (gem_jpeg_bound)."""
+        n = self.lib.gem_jpeg_bound(int(width), int(height))
+        if n < 0:
+            _capi.check(1, self.lib)
+        return int(n)
+
+    def jpeg_encode_into(self, scan, width, height, quality, avi, out, offsets, coef=None):
+        """gem_jpeg_encode as it is: `scan` uint8 [n, stride] on the device with contiguous rows, `out` a contiguous uint8 device
+        tensor (its size is the capacity), `offsets` int64 [n + 1] on the device, `coef` None or int16 [n,3,Hp/8,Wp/8,64].
+        Asynchronous; nothing is read back."""
+        if not (torch.is_tensor(scan) and scan.is_cuda and scan.dtype == torch.uint8 and scan.dim() == 2 and (scan.shape[0] == 0 or scan.stride(1) == 1)):
+            raise TypeError("jpeg_encode: scan must be a uint8 device tensor [n, stride] with contiguous rows")
+        n = scan.shape[0]
+        if not (torch.is_tensor(out) and out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous()):
+            raise TypeError("jpeg_encode: out must be a contiguous uint8 device tensor")
+        if not (torch.is_tensor(offsets) and offsets.is_cuda and offsets.dtype == torch.int64 and offsets.is_contiguous() and offsets.numel() == n + 1):
+            raise TypeError("jpeg_encode: offsets must be a contiguous int64 device tensor [%d]" % (n + 1))
+        if scan.shape[1] < int(height) * (1 + 3 * int(width)):
+            raise ValueError("jpeg_encode: %d x %d pixels are %d scanline bytes, the rows of scan hold %d" %
+                             (width, height, int(height) * (1 + 3 * int(width)), scan.shape[1]))
+        if coef is not None:
+            shape = (n, 3, (int(height) + 7) // 8, (int(width) + 7) // 8, 64)
+            if not (torch.is_tensor(coef) and coef.is_cuda and coef.dtype == torch.int16 and coef.is_contiguous() and tuple(coef.shape) == shape):
+                raise TypeError("jpeg_encode: coef must be a contiguous int16 device tensor %s" % (shape,))
+        _capi.check(self.lib.gem_jpeg_encode(self._h, _ptr(scan), n, int(width), int(height), scan.stride(0) if n else scan.shape[1], int(quality),
+                                             1 if avi else 0, _ptr(out), out.numel(), _ptr(offsets), _ptr(coef), _stream()), self.lib)
+
+    def jpeg_encode(self, scan, width, height, quality=90, avi=False, coef=False, out=None):
+        """The images of `scan` -- uint8 [n, stride] on the device, every row the scanline stream `render_capsules` / `render_camera`
+        write -- as baseline JPEG (gem_jpeg_encode): (data, offsets[, coefficients]).  Image i is
+        data[offsets[i]:offsets[i+1]], a complete JPEG file, or with avi=True the `00dc` chunk of an AVI file; `data` is a uint8
+        device tensor of offsets[n] bytes and `offsets` a list of n + 1 integers.  coef=True adds the quantised coefficients, int16
+        [n,3,Hp/8,Wp/8,64] in zigzag order, on the device.  `out`: a contiguous uint8 device tensor to encode into when it is large
+        enough (default: n times a sixth of the scanline bytes plus the header).  One read-back (the offsets); when the images need more room
+        than there was, that much is allocated and the call made once more."""
+        n = scan.shape[0]
+        want = torch.empty(n, 3, (int(height) + 7) // 8, (int(width) + 7) // 8, 64, device=self.device, dtype=torch.int16) if coef else None
+        if out is None:
+            out = torch.empty(max(1, n * (1024 + int(height) * (1 + 3 * int(width)) // 6)), device=self.device, dtype=torch.uint8)
+        offsets = torch.empty(n + 1, device=self.device, dtype=torch.int64)
+        self.jpeg_encode_into(scan, width, height, quality, avi, out, offsets, want)
+        at = offsets.tolist()
+        if at[n] > out.numel():
+            out = torch.empty(at[n], device=self.device, dtype=torch.uint8)
+            self.jpeg_encode_into(scan, width, height, quality, avi, out, offsets, want)
+        return (out[:at[n]], at, want) if coef else (out[:at[n]], at)
+
     # ------------------------------------------------------------------ looking at a trained VAE (DESIGN.md section 6g)
     PATH_MODES = {"linear": 0, "spherical": 1}
     REPORT_KEYS = ("mu_error", "std_error", "kld", "mpjpe", "max_joint_error")

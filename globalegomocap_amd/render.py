@@ -15,6 +15,11 @@ sequences projected through the frame's camera by the reprojection term's own ar
 gem_project_sequence + gem_render_camera; `write_camera_frames` writes one `camera_%04d.png` per frame by the same route).
 
     python -m globalegomocap_amd.render out/<dataset>/<chunk>/result_pose.pkl --out DIR --camera <chunk directory> [--size N]
+
+Either set of frames can also become one clip that plays: `video=PATH` hands the same images to
+`video.write_video`, which encodes them on the device as Motion-JPEG.
+
+    python -m globalegomocap_amd.render result_pose.pkl --out DIR --video [--video_fps F] [--video_quality Q] [--no_frames]
 """
 import ctypes as C
 import os
@@ -302,13 +307,28 @@ def _write_scanlines(engine, draw, W, H, paths):
                         pass
 
 
-def write_frames(engine, sequences, out_dir, colours=None, align_to=None, size=None, view="side", overview=True, names=None):
+def _video_arguments(video, video_fps, video_quality, frames):
+    """What `write_frames` / `write_camera_frames` refuse before they draw anything."""
+    if video is None:
+        if not frames:
+            raise ValueError("frames=False leaves nothing to write: it needs video=PATH")
+        return
+    from .video import _check
+    _check(1, 1, video_fps, video_quality)
+
+
+def write_frames(engine, sequences, out_dir, colours=None, align_to=None, size=None, view="side", overview=True, names=None, video=None,
+                 video_fps=25, video_quality=90, frames=True):
     """`out_dir/frame_%04d.png` for every frame, all `sequences` (each [F,15,3]) overlaid in their `colours` (default: the palette's
     order estimated, optimised, ground truth), and -- overview=True -- `out_dir/overview_<name>.png` per sequence with all its
     frames in one scene (`names`, default: the palette's names).  align_to: None, one sequence [F,15,3] for all, or a list with one
     target or None per sequence; a sequence with a target is first moved by the one similarity transform that takes it onto the
     target (`errors.align_sequence`).  size = (width, height), default DEFAULT_SIZE; `view` as in `fit_view`, fitted once to everything that is drawn.
+    video=PATH additionally writes the per-frame images -- not the overviews -- as one Motion-JPEG clip to PATH at `video_fps` frames
+    per second and JPEG quality `video_quality` (`video.write_video`: encoded on the device); with
+    frames=False no PNG file is written, and `out_dir` is not touched.
     Runs on the current stream; every file is complete and closed on return; returns the number of files."""
+    _video_arguments(video, video_fps, video_quality, frames)
     seqs, crts = _prepare(engine, sequences, align_to)
     S, F = len(seqs), seqs[0].shape[0]
     default = list(PALETTE)
@@ -320,29 +340,38 @@ def write_frames(engine, sequences, out_dir, colours=None, align_to=None, size=N
         names = default[:S] if S <= len(default) else ["%d" % i for i in range(S)]
     if len(names) != S:
         raise ValueError("%d names for %d sequences" % (len(names), S))
-    os.makedirs(out_dir, exist_ok=True)
+    if frames:
+        os.makedirs(out_dir, exist_ok=True)
     if F == 0:
         return 0
     v = _view_of(seqs, crts, size, view)
     geom, rgb, first = _scene(engine, seqs, crts, colours, False)
+    if video is not None:
+        from .video import write_video
+        write_video(engine, lambda lo, n, out: engine.render_capsules(geom, rgb, first[lo:lo + n + 1], v, out=out), v.width, v.height, F,
+                    video, video_fps, video_quality)
+        if not frames:
+            return 1
     _write_images(engine, geom, rgb, first, v, [os.path.join(out_dir, "frame_%04d.png" % f) for f in range(F)])
     if not overview:
-        return F
+        return F + (video is not None)
     geom, rgb, first = _scene(engine, seqs, crts, colours, True)
     _write_images(engine, geom, rgb, first, v, [os.path.join(out_dir, "overview_%s.png" % n) for n in names])
-    return F + S
+    return F + S + (video is not None)
 
 
-def write_result_frames(engine, out_dir, estimated, optimized, gt=None, align=None, size=None, view="side"):
+def write_result_frames(engine, out_dir, estimated, optimized, gt=None, align=None, size=None, view="side", video=None, video_fps=25,
+                        video_quality=90, frames=True):
     """One result's frames under `out_dir`: the estimated, the optimised and, where there is one, the ground-truth sequence overlaid
     (red, blue, green), the first two aligned to the third (`align`, default: whenever there is one) as `meshes.write_result_meshes`
-    aligns the meshes."""
+    aligns the meshes.  video, video_fps, video_quality, frames: see `write_frames`."""
     align = gt is not None if align is None else align
     if align and gt is None:
         raise ValueError("aligned frames need a ground-truth sequence to align to")
     sequences = [estimated, optimized] + ([gt] if gt is not None else [])
     to = [gt if align else None] * 2 + ([None] if gt is not None else [])
-    return write_frames(engine, sequences, out_dir, align_to=to, size=size, view=view)
+    return write_frames(engine, sequences, out_dir, align_to=to, size=size, view=view, video=video, video_fps=video_fps,
+                        video_quality=video_quality, frames=frames)
 
 
 # ------------------------------------------------------------------------------------------------------------------ the camera's view
@@ -395,10 +424,11 @@ def camera_scanlines(engine, sequences, cams, heat, colours, size=None, joint_ra
 
 
 def write_camera_frames(engine, sequences, cams, heat, out_dir, colours=None, size=None, joint_radius=8.0, line_radius=3.0, heat_joints=None,
-                        align_to=None):
+                        align_to=None, video=None, video_fps=25, video_quality=90, frames=True):
     """`out_dir/camera_%04d.png` for every frame: `camera_scanlines` (colours default: the palette's order) through `write_frames`'
-    pinned buffers and writer threads.  Runs on the current stream; every file is complete and closed on return; returns the
-    number of files."""
+    pinned buffers and writer threads.  video, video_fps, video_quality, frames: as in `write_frames`, the same images as one clip.
+    Runs on the current stream; every file is complete and closed on return; returns the number of files."""
+    _video_arguments(video, video_fps, video_quality, frames)
     default = list(PALETTE)
     if colours is None:
         if len(sequences) > len(default):
@@ -406,22 +436,31 @@ def write_camera_frames(engine, sequences, cams, heat, out_dir, colours=None, si
         colours = [PALETTE[k] for k in default[:len(sequences)]]
     heat, uv, rgb = _camera_scene(engine, sequences, cams, heat, colours, align_to)
     view = camera_view(size, joint_radius, line_radius, heat_joints)
-    os.makedirs(out_dir, exist_ok=True)
+    if frames:
+        os.makedirs(out_dir, exist_ok=True)
     F = uv.shape[1]
 
     def draw(lo, n, out):
         engine.render_camera(None if heat is None else heat[lo:lo + n], uv[:, lo:lo + n].contiguous(), rgb, view, out=out)
+    if video is not None and F:
+        from .video import write_video
+        write_video(engine, draw, view.size, view.size, F, video, video_fps, video_quality)
+        if not frames:
+            return 1
     _write_scanlines(engine, draw, view.size, view.size, [os.path.join(out_dir, "camera_%04d.png" % f) for f in range(F)])
-    return F
+    return F + (video is not None and F > 0)
 
 
-def write_result_camera_frames(engine, out_dir, estimated, optimized, cams, heat, gt=None, size=None):
+def write_result_camera_frames(engine, out_dir, estimated, optimized, cams, heat, gt=None, size=None, video=None, video_fps=25,
+                               video_quality=90, frames=True):
     """One result as the camera saw it, `out_dir/camera_%04d.png`: the estimated (red), the optimised (blue) and, where there is one,
     the ground-truth sequence (green) over the frames' heat-maps.  The ground truth lives in the studio's frame, not in the
-    cameras': it is first moved by the one similarity that takes it onto the optimised sequence."""
+    cameras': it is first moved by the one similarity that takes it onto the optimised sequence.  video, video_fps, video_quality,
+    frames: see `write_frames`."""
     sequences = [estimated, optimized] + ([gt] if gt is not None else [])
     to = [None, None] + ([optimized] if gt is not None else [])
-    return write_camera_frames(engine, sequences, cams, heat, out_dir, align_to=to, size=size)
+    return write_camera_frames(engine, sequences, cams, heat, out_dir, align_to=to, size=size, video=video, video_fps=video_fps,
+                               video_quality=video_quality, frames=frames)
 
 
 def release():
@@ -465,7 +504,19 @@ def main(argv=None):
     p.add_argument("--camera", default=None, metavar="CHUNK_DIR",
                    help="draw the camera's view instead (camera_%%04d.png): the directory whose test_data.pkl holds the cameras and "
                         "heat-maps the poses belong to (merged frame f is the chunk's frame f); gt_pose is aligned onto optimized_pose")
+    p.add_argument("--video", action="store_true", help="also write the frames as one Motion-JPEG clip, DIR/frames.avi (with --camera: DIR/camera.avi)")
+    p.add_argument("--video_fps", default=25.0, type=float, metavar="F", help="frames per second of the clip (default 25)")
+    p.add_argument("--video_quality", default=90, type=int, metavar="Q", help="JPEG quality of the clip, 1 .. 100 (default 90)")
+    p.add_argument("--no_frames", action="store_true", help="with --video: the clip only, no PNG files")
     a = p.parse_args(argv)
+    if not a.video_fps > 0:
+        p.error("argument --video_fps: must be positive")
+    if not 1 <= a.video_quality <= 100:
+        p.error("argument --video_quality: a whole number 1 .. 100")
+    if a.no_frames and not a.video:
+        p.error("--no_frames needs --video")
+    clip = dict(video=os.path.join(a.out, "camera.avi" if a.camera is not None else "frames.avi") if a.video else None,
+                video_fps=a.video_fps, video_quality=a.video_quality, frames=not a.no_frames)
     if a.camera is None and isinstance(a.size, int):
         p.error("argument --size: a size is WIDTHxHEIGHT, for instance 640x480; got %r" % str(a.size))
     if a.camera is not None:
@@ -494,11 +545,12 @@ def main(argv=None):
         if c["n"] < F or len(c["cams"]) < F:
             p.error("--camera %s holds %d frames, the poses %d" % (a.camera, min(c["n"], len(c["cams"])), F))
         heat = np.asarray(c["heat_list"][:F], dtype=np.float32).reshape((F,) + tuple(c["heat_shape"]))
-        n = write_result_camera_frames(engine, a.out, est, opt, c["cams"][:F], heat, None if gt is None else np.asarray(gt), size=a.size)
+        n = write_result_camera_frames(engine, a.out, est, opt, c["cams"][:F], heat, None if gt is None else np.asarray(gt), size=a.size,
+                                       **clip)
     else:
         n = write_result_frames(engine, a.out, est, opt, None if gt is None else np.asarray(gt), align=a.align,
-                                size=DEFAULT_SIZE if a.size is None else a.size, view=a.view)
-    print("{} images written under {}".format(n, a.out))
+                                size=DEFAULT_SIZE if a.size is None else a.size, view=a.view, **clip)
+    print("{} {} written under {}".format(n, "files" if a.video else "images", a.out))
 
 
 if __name__ == "__main__":

@@ -240,6 +240,25 @@ def write_result_outputs(engine, data_id, sequences, mesh_root=None, render=None
         animation.write_result_bvh(engine, result_dir(bvh, data_id), est, opt, gt, fps=25 if bvh_fps is None else bvh_fps)
 
 
+def write_result_clips(engine, data_id, sequences, video=None, video_camera=None, cams=None, heat=None, first_frame=0, video_fps=None,
+                       video_quality=None):
+    """One chunk's clips from `sequences` as `write_result_outputs` takes them, each under `result_dir` of its own
+    root and only where that root is given:
+      video          the frames `render` draws -- the same view and overlay, without the overviews -- as one Motion-JPEG clip,
+                     <chunk>/frames.avi (`render.write_result_frames(video=..., frames=False)`);
+      video_camera   the images `render_camera` draws as <chunk>/camera.avi; `cams` / `heat` / `first_frame` as there.
+    Both play at `video_fps` frames per second (default 25) and are encoded on the device at JPEG quality `video_quality` (default
+    90).  No PNG file is written here: the clips do not need `render` / `render_camera`, and `write_result_outputs` is untouched by them."""
+    est, opt, gt = sequences
+    clip = dict(video_fps=25 if video_fps is None else video_fps, video_quality=90 if video_quality is None else video_quality, frames=False)
+    if video is not None:
+        rendering.write_result_frames(engine, None, est, opt, gt, video=os.path.join(result_dir(video, data_id), "frames.avi"), **clip)
+    if video_camera is not None:
+        frames = slice(first_frame, first_frame + len(est))
+        rendering.write_result_camera_frames(engine, None, est, opt, cams[frames], heat[frames], gt,
+                                             video=os.path.join(result_dir(video_camera, data_id), "camera.avi"), **clip)
+
+
 def result_pose_dict(est, opt, mid, gt, smooth):
     """What `result_pose.pkl` holds, in the reference's keys and containers (optimizer.py:469-483): merge_batches' lists of [15,3]
     frames; the optimised sequence an ndarray after the final smoothing (`smooth`); `gt_pose` only where there is a ground truth."""

@@ -20,7 +20,8 @@ chunk to `DIR/<chunk name>/result_pose.pkl` on either route; `save=True` / `--sa
 `mesh_root` (`meshes`); `render=DIR` / `--render DIR` writes every chunk's frames as PNG images under DIR
 (`render`); `render_camera=DIR` / `--render_camera DIR` writes every chunk as its camera saw it, the heat-maps
 under the reprojected skeletons; `bvh=DIR` / `--bvh DIR` writes every chunk's sequences as BVH animation files
-(`bvh`).
+(`bvh`); `video=DIR` / `--video DIR` and `video_camera=DIR` / `--video_camera DIR` write the frames of `render` and
+of `render_camera` as one Motion-JPEG clip per chunk, encoded on the device (`video`).
 """
 import ctypes as C
 import os
@@ -36,7 +37,7 @@ from .staging import (Laps, Scratch, cpus_near, drain, natural_key, reader_pool,
                       thread_state)
 from .optimizer import SequenceOptimizer, GLOBAL_VAE_PATH, LOCAL_VAE_PATH
 from .report import (QUALITY_LINES, QUALITY_KEYS, SUMMARY_LINES, batch_reports, chunk_reports, report_inputs, result_pose_dict,      # noqa: F401  (the three tables: part of this module's interface)
-                     sequence_result, write_result_outputs)
+                     sequence_result, write_result_clips, write_result_outputs)
 from .sequence import SEQ_LEN, OVERLAP, window_starts
 
 
@@ -313,6 +314,26 @@ def _settings(camera_model_path, vae_weight=0.0, gmm_weight=0.0, smoothness_weig
     return SimpleNamespace(**locals())
 
 
+CLIP_KEYS = ("video", "video_camera", "video_fps", "video_quality")
+
+
+def _clip_settings(video=None, video_camera=None, video_fps=None, video_quality=None):
+    """The clip arguments of `optimize_sequences` / `optimize_recordings` (by keyword only: they travel beside `_settings`, whose
+    positional order is closed), checked before anything runs."""
+    if video is not None or video_camera is not None:
+        from .video import _check
+        _check(1, 1, 25 if video_fps is None else video_fps, 90 if video_quality is None else video_quality)
+    return dict(video=video, video_camera=video_camera, video_fps=video_fps, video_quality=video_quality)
+
+
+def _all_settings(camera_model_path, args, kwargs):
+    """`_settings` of everything but the clip arguments, and those (`_clip_settings`) as further attributes."""
+    clip = _clip_settings(**{k: kwargs.pop(k) for k in CLIP_KEYS if k in kwargs})
+    cfg = _settings(camera_model_path, *args, **kwargs)
+    cfg.__dict__.update(clip)
+    return cfg
+
+
 class _Pipeline:
     """The private driver behind `optimize_sequences` and `optimize_recordings`: `groups[g]` are the chunk sources (_Source) of
     sequence g.  It holds one call's batches and what their stages share: the settings, the optimiser, the device's buffers
@@ -498,7 +519,7 @@ class _Pipeline:
                 reports = chunk_reports(e, b.chunks, mid_np, opt_global, cfg.seq_len, cfg.overlap, bool(cfg.final_smooth), cfg.device_metrics,
                                         frames)
             view_heat, view_cams = None, None
-            if cfg.render_camera is not None:
+            if cfg.render_camera is not None or cfg.video_camera is not None:
                 # the camera's view reads the batch's frame buffers too; its files are complete (the device has read the frames) before
                 # this returns, three batches before the slot's frame buffer is filled again
                 view_heat, view_cams = b.heat_d.contiguous(), b.prep["cams"]
@@ -510,6 +531,9 @@ class _Pipeline:
                     name = os.path.normpath(src.name)
                     write_result_outputs(e, name, r.sequences(), cfg.mesh_root if cfg.save else None, cfg.render, cfg.render_camera,
                                          view_cams, view_heat, int(b.frame_lo[ci]), bvh=cfg.bvh, bvh_fps=cfg.bvh_fps)
+                    if cfg.video is not None or cfg.video_camera is not None:
+                        write_result_clips(e, name, r.sequences(), cfg.video, cfg.video_camera, view_cams, view_heat, int(b.frame_lo[ci]),
+                                           cfg.video_fps, cfg.video_quality)
                     r.drop_views()          # (they alias this batch's slot, which batch k+3 fills again)
                     self.reports[src.group].append(r)
                     if cfg.save_pose is not None:
@@ -562,7 +586,7 @@ def optimize_sequences(data_dirs, camera_model_path, *args, **kwargs):
     Further arguments, positional or by keyword, in this order (defaults: `_settings`): vae_weight, gmm_weight, smoothness_weight,
     bone_length_weight, weight_3d, reproj_weight, final_smooth, merge, global_vae_path, local_vae_path, chunks_per_batch, optimizer,
     device_metrics, verbose, seq_len, overlap, timings, per_sequence, ground_truth, save_pose, save, mesh_root, render, render_camera,
-    bvh, bvh_fps.
+    bvh, bvh_fps; and by keyword only (`_clip_settings`): video, video_camera, video_fps, video_quality.
 
     ground_truth=False: the chunks carry no ground truth (`prepare` with a scale).  Their pickles are not asked for
     `gt_global_skeleton`, every chunk's report is the seven entries of QUALITY_KEYS (`WindowEngine.sequence_quality` on the estimated
@@ -584,8 +608,12 @@ def optimize_sequences(data_dirs, camera_model_path, *args, **kwargs):
     bvh=DIR: every chunk as animation, `DIR/<dataset>/<chunk>/{estimated,optimized,gt}.bvh` at `bvh_fps` frames per second (default
     25): a 19-node skeleton with the chunk's mean bone lengths and every frame keyed, the first two sequences aligned to the third
     (`bvh.write_result_bvh`, made on the device).  With ground_truth=False: two files, unaligned.  Results and reports do not
-    depend on it."""
-    cfg = _settings(camera_model_path, *args, **kwargs)
+    depend on it.
+    video=DIR: every chunk's frames -- the view and overlay of `render`, without the overviews -- as one Motion-JPEG clip,
+    `DIR/<dataset>/<chunk>/frames.avi`; video_camera=DIR: the images of `render_camera` as `.../camera.avi`.  Neither needs the PNG
+    option: without it no PNG file is written.  Both play at `video_fps` frames per second (default 25) and are encoded on the device
+    at JPEG quality `video_quality` (default 90; `report.write_result_clips`).  Results and reports do not depend on them."""
+    cfg = _all_settings(camera_model_path, args, kwargs)
     lap = Laps(cfg.timings, log=True)          # developer timing (tools/whole_sequence_timing.py): wall time of the main thread's phases
     groups = []
     for gi, d in enumerate(data_dirs):
@@ -607,7 +635,7 @@ def optimize_recordings(recordings, camera_model_path, *args, **kwargs):
     value and printed summary, one entry per `Recording`; no pickle is written or read.  The optimiser is handed the same
     float32 heat-maps, float64 skeletons and cameras that `Recording.write_chunks` + `optimize_sequences` would hand it, so
     the results are bitwise those."""
-    cfg = _settings(camera_model_path, *args, **kwargs)
+    cfg = _all_settings(camera_model_path, args, kwargs)
     lap = Laps(cfg.timings, log=True)
     titles = ["recording_%d" % gi for gi in range(len(recordings))]
     groups = []
@@ -627,12 +655,13 @@ def release_pools():
     """Give back what this module keeps between calls: the per-device frame buffers the readers fill, the pinned noise
     blocks and the mesh and frame writers' buffers, then (`staging.release`) the streams and the reader threads with their pinned staging buffers and device images.
     Not to be called while another call is in flight."""
-    from . import bvh, meshes, render
+    from . import bvh, meshes, render, video
     _heat_pool.clear()
     _noise_pool.clear()
     meshes.release()
     render.release()
     bvh.release()
+    video.release()
     staging.release()
     if torch.cuda.is_available():
         torch.cuda.empty_cache()
@@ -658,6 +687,10 @@ def _parser():
                    help="write every chunk as its camera saw it, DIR/<dataset>/<chunk>/camera_%%04d.png: heat-maps under the reprojected skeletons")
     p.add_argument("--bvh", default=None, metavar="DIR", help="write every chunk as animation, DIR/<dataset>/<chunk>/{estimated,optimized,gt}.bvh")
     p.add_argument("--bvh_fps", default=None, type=float, metavar="F", help="frames per second of the --bvh files (default 25)")
+    p.add_argument("--video", default=None, metavar="DIR", help="write every chunk's frames as one Motion-JPEG clip, DIR/<dataset>/<chunk>/frames.avi")
+    p.add_argument("--video_camera", default=None, metavar="DIR", help="write every chunk as its camera saw it as one clip, DIR/<dataset>/<chunk>/camera.avi")
+    p.add_argument("--video_fps", default=None, type=float, metavar="F", help="frames per second of the clips (default 25)")
+    p.add_argument("--video_quality", default=None, type=int, metavar="Q", help="JPEG quality of the clips, 1 .. 100 (default 90)")
     p.add_argument("--final_smooth", default=True, type=truthy)
     p.add_argument("--merge", default=True, type=truthy)
     p.add_argument("--chunks_per_batch", type=int, default=None, help="chunks optimised per device call (default: all)")
@@ -667,11 +700,16 @@ def _parser():
 
 
 def _cli(argv=None):
-    a = _parser().parse_args(argv)
+    p = _parser()
+    a = p.parse_args(argv)
+    if a.video_fps is not None and not a.video_fps > 0:
+        p.error("argument --video_fps: must be positive")
+    if a.video_quality is not None and not 1 <= a.video_quality <= 100:
+        p.error("argument --video_quality: a whole number 1 .. 100")
     optimize_directory(a.data_path, a.camera, a.vae, a.gmm, a.smooth, a.bone_length, a.weight_3d, a.reproj_weight,
                        final_smooth=a.final_smooth, merge=a.merge, chunks_per_batch=a.chunks_per_batch, ground_truth=a.ground_truth,
                        save_pose=a.save_pose, save=a.save, mesh_root=a.mesh_root, render=a.render, render_camera=a.render_camera, bvh=a.bvh,
-                       bvh_fps=a.bvh_fps)
+                       bvh_fps=a.bvh_fps, video=a.video, video_camera=a.video_camera, video_fps=a.video_fps, video_quality=a.video_quality)
 
 
 if __name__ == "__main__":

@@ -708,6 +708,28 @@ int gem_bvh_channels(const double* d_seq, int64_t n_frames, const double* d_crt,
  * back.  d_text must be 16-byte aligned: anything else is refused before the launch.  Works on the current device. */
 int gem_format_fields(const double* d_values, int64_t n_values, int64_t values_per_line, void* d_text, int64_t* d_bad, void* stream);
 
+/* ---- Rendered frames as baseline JPEG images and Motion-JPEG chunks: `video=PATH` / `--video DIR` ----
+ * The format is fixed: 8-bit YCbCr (JFIF, full range), 4:4:4, one restart segment per MCU row, the Annex K quantisation tables scaled
+ * by the IJG quality rule and the Annex K Huffman tables; integer arithmetic throughout, so the bytes are a function of the pixels
+ * and the quality alone (6j, "The format").
+ * gem_jpeg_header: the 629 bytes in front of the entropy data -- SOI, APP0 (JFIF 1.01), DQT 0, DQT 1, SOF0, DHT DC0 AC0 DC1 AC1, DRI,
+ * SOS -- into buf (cap >= 629); returns 629, or -1 with the reason in gem_last_error.  gem_jpeg_bound: the most bytes one image's
+ * file can take, 629 + ceil(H / 8) * (2 * ceil(3 * ceil(W / 8) * 1660 / 8) + 2); -1 for a size out of range.  Both need no GPU. */
+int gem_jpeg_header(int width, int height, int quality, void* buf, int64_t cap);
+int64_t gem_jpeg_bound(int width, int height);
+
+/* d_scan: n_images images as gem_render_capsules / gem_render_camera write them, `height` rows of 1 + 3 * width bytes each (byte 0 of
+ * a row, the PNG filter byte, is ignored), in_stride bytes apart.  Image i's bytes go to d_out[d_offsets[i] .. d_offsets[i+1]):
+ * with avi_chunks = 0 a complete JPEG file, with avi_chunks = 1 an AVI chunk -- '00dc', the file's length as uint32, the file, one
+ * zero byte behind an odd length -- so that the whole run can be appended to a 'movi' list verbatim.  d_offsets [n_images + 1] int64 is
+ * always complete; an image with d_offsets[i+1] > out_capacity is not written at all, and nothing at or behind d_offsets[n_images] or
+ * out_capacity is touched.  d_coef, unless NULL (16-byte aligned): int16 [n_images, 3, ceil(H/8), ceil(W/8), 64], the quantised
+ * coefficients of Y, Cb, Cr in zigzag order.  1 <= width <= 1024, 1 <= height <= 16384, 1 <= quality <= 100, 0 <= n_images <= 65535,
+ * in_stride >= height * (1 + 3 * width): anything else is refused before any launch.  Asynchronous on `stream` (it waits for the
+ * device only when the handle's scratch buffer has to grow); two calls give the same bytes. */
+int gem_jpeg_encode(gem_handle* h, const void* d_scan, int n_images, int width, int height, int64_t in_stride, int quality, int avi_chunks,
+                    void* d_out, int64_t out_capacity, int64_t* d_offsets, int16_t* d_coef, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
