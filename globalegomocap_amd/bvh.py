@@ -12,13 +12,12 @@ motion block's text, "%15.6f" per channel, correctly rounded (gem_format_fields)
 """
 import ctypes as C
 import os
-import pickle
 from collections import namedtuple
 
 import numpy as np
 
 from . import _capi
-from .meshes import _alignment, _sequence
+from .meshes import _alignment, _sequence, result_poses
 
 Layout = namedtuple("Layout", "nodes channels field_bytes frame_bytes")
 Tables = namedtuple("Tables", "parents joint_of_node rest_dirs")
@@ -27,12 +26,12 @@ NODE_NAMES = ("Hips", "Spine", "Neck", "Right_collar", "Right_shoulder", "Right_
               "Left_elbow", "Left_wrist", "Right_hip", "Right_knee", "Right_ankle", "Right_foot", "Left_hip", "Left_knee", "Left_ankle",
               "Left_foot")
 ROOT_CHANNELS = ("Xposition", "Yposition", "Zposition", "Zrotation", "Xrotation", "Yrotation")
+DEFAULT_FPS = 25                 # frames per second of a file wherever a caller gives none
 PINNED_BYTES = 16 << 20          # each of the two pinned buffers the text crosses PCIe through (17 476 frames), whatever the sequence's length
 FILE_NAMES = ("estimated.bvh", "optimized.bvh", "gt.bvh")
 
 _layout = None
 _tables = None
-_buffers = {}          # device -> [pinned, pinned, device buffer, pinned counters [2,2]]
 
 
 def layout():
@@ -136,7 +135,7 @@ def hierarchy_text(rest, unit_scale=100.0):
     return "\n".join(lines) + "\n"
 
 
-def write_bvh(engine, seq, path, fps=25, align_to=None, unit_scale=100.0):
+def write_bvh(engine, seq, path, fps=DEFAULT_FPS, align_to=None, unit_scale=100.0):
     """`seq` [F,15,3] (array or tensor, metres, F >= 1) as the BVH file `path`, one keyed frame per frame at `fps`; positions and
     offsets are metres times `unit_scale` (100: centimetres, what most importers assume).  align_to [F,15,3]: the sequence is first
     moved by the one similarity transform that takes it onto `align_to` (`errors.align_sequence`).  Rest lengths, channels and the
@@ -145,6 +144,7 @@ def write_bvh(engine, seq, path, fps=25, align_to=None, unit_scale=100.0):
     number or does not fit its field (a NaN joint, a position beyond +-9999999.999999 units) deletes the partial file and raises
     ValueError naming the frame.  Runs on the current stream; the file is complete and closed on return.  Returns F."""
     import torch
+    from .staging import STOP, reader_pool, stream_out
     seq_d = _sequence(engine, seq)
     F, lay = seq_d.shape[0], layout()
     if F < 1:
@@ -155,73 +155,38 @@ def write_bvh(engine, seq, path, fps=25, align_to=None, unit_scale=100.0):
     rest = rest_lengths(engine, seq_d, crt)
     chan = channels(engine, seq_d, crt, rest, unit_scale)
     per = max(1, PINNED_BYTES // lay.frame_bytes)
-    dev = engine.device
-    bufs = _buffers.get(dev)
-    if bufs is None or bufs[0].shape[0] != per:
-        bufs = _buffers[dev] = [torch.empty(per, lay.frame_bytes, dtype=torch.uint8).pin_memory() for _ in range(2)] + \
-            [torch.empty(per, lay.frame_bytes, dtype=torch.uint8, device=dev), torch.empty(2, 2, dtype=torch.int64).pin_memory()]
     header = hierarchy_text(rest.cpu().numpy(), unit_scale) + "MOTION\nFrames: %d\nFrame Time: %.6f\n" % (F, 1.0 / fps)
-    from .staging import reader_pool
     pool = reader_pool("bvh", 1)          # one writer: the slices are appended in order
+    counters = new_counter(engine.device).repeat((F + per - 1) // per, 1)          # one per slice: its first bad line counts from the slice's start
+    failed = []
+
+    def produce(k, out):
+        n = min(per, F - k * per)
+        format_fields(engine, chan[k * per:k * per + n], lay.channels, counters[k], out=out)
+        return n * lay.frame_bytes, counters[k]
+
+    def consume(k, data, side):
+        count, first = side.view(torch.int64).tolist()
+        if count:
+            failed.append(k * per + first)
+            return STOP
+        return [pool.submit(f.write, data.numpy())]
+
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-    f = open(path, "wb")
-    writing, arrived, failed = [None, None], None, None
-    try:
+    with open(path, "wb") as f:
         f.write(header.encode("ascii"))
-
-        def settle(slot):
-            if writing[slot] is not None:
-                writing[slot].result()          # (an OSError of the writer surfaces here)
-                writing[slot] = None
-
-        def hand_over(batch):
-            lo, n, slot, ev = batch
-            ev.synchronize()
-            count, first = bufs[3][slot].tolist()
-            if count:
-                return lo + first
-            writing[slot] = pool.submit(f.write, bufs[slot].numpy().reshape(-1)[:n * lay.frame_bytes])
-            return None
-
-        counters = new_counter(dev).repeat((F + per - 1) // per, 1)          # one per slice: its first bad line counts from the slice's start
-        for k, lo in enumerate(range(0, F, per)):
-            n, slot = min(per, F - lo), k % 2
-            settle(slot)
-            format_fields(engine, chan[lo:lo + n], lay.channels, counters[k], out=bufs[2].view(-1))
-            bufs[slot][:n].copy_(bufs[2][:n], non_blocking=True)
-            bufs[3][slot].copy_(counters[k], non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record(torch.cuda.current_stream())
-            if arrived is not None:
-                failed = hand_over(arrived)
-            arrived = (lo, n, slot, ev)
-            if failed is not None:
-                break
-        if failed is None:
-            failed = hand_over(arrived)
-            arrived = None
-        settle(0)
-        settle(1)
-    finally:
-        if arrived is not None:
-            arrived[3].synchronize()          # (nothing may still write the pinned buffers)
-        for w in writing:
-            if w is not None:
-                try:
-                    w.result()
-                except Exception:
-                    pass
-        f.close()
-    if failed is not None:
+        stream_out(engine.device, "bvh", per * lay.frame_bytes, len(counters), produce, consume, side_bytes=16)
+    if failed:
         os.remove(path)
         raise ValueError("%s: frame %d has a channel that is not a number of at most 7 digits before the point (a NaN joint, or a position "
-                         "beyond the field at unit_scale %g): no file written" % (path, failed, unit_scale))
+                         "beyond the field at unit_scale %g): no file written" % (path, failed[0], unit_scale))
     return F
 
 
 def release():
     """Give back the pinned and device buffers `write_bvh` keeps between calls."""
-    _buffers.clear()
+    from .staging import release_kept
+    release_kept("bvh")
 
 
 # ------------------------------------------------------------------------------------------------------------------ reading back
@@ -353,9 +318,9 @@ def skeleton_from_nodes(positions):
 
 
 # ------------------------------------------------------------------------------------------------------------------ a result's files
-def write_result_bvh(engine, out_dir, estimated, optimized, gt=None, fps=25, align=None, unit_scale=100.0):
+def write_result_bvh(engine, out_dir, estimated, optimized, gt=None, fps=DEFAULT_FPS, align=None, unit_scale=100.0):
     """`estimated.bvh`, `optimized.bvh` and, with a ground truth, `gt.bvh` under `out_dir` from the merged sequences, by the convention of
-    `report.write_result_outputs`: with a ground truth the first two are aligned to it (`align`, default: whenever there is one).
+    `report.Outputs`: with a ground truth the first two are aligned to it (`align`, default: whenever there is one).
     Returns the number of files."""
     align = gt is not None if align is None else align
     if align and gt is None:
@@ -371,12 +336,11 @@ def write_result_bvh(engine, out_dir, estimated, optimized, gt=None, fps=25, ali
 
 def main(argv=None):
     import argparse
-    from .camera import DEFAULT_CALIBRATION
     truthy = lambda x: str(x).lower() == "true"          # noqa: E731  (the reference's own flag parser)
     p = argparse.ArgumentParser(description="BVH animation files from a saved result_pose.pkl")
     p.add_argument("pose_pickle", help="result_pose.pkl as --save_pose writes it: estimated_pose, optimized_pose and, optionally, gt_pose")
     p.add_argument("--out", required=True, metavar="DIR")
-    p.add_argument("--fps", default=25.0, type=float, help="frames per second of the files (Frame Time = 1 / fps)")
+    p.add_argument("--fps", default=float(DEFAULT_FPS), type=float, help="frames per second of the files (Frame Time = 1 / fps)")
     p.add_argument("--align", default=False, type=truthy, help="true: align both sequences to gt_pose first")
     p.add_argument("--unit_scale", default=100.0, type=float, help="file units per metre (100: centimetres)")
     a = p.parse_args(argv)
@@ -384,21 +348,7 @@ def main(argv=None):
         p.error("--fps must be positive")
     if not a.unit_scale > 0:
         p.error("--unit_scale must be positive")
-    with open(a.pose_pickle, "rb") as f:
-        d = pickle.load(f)
-    for key in ("estimated_pose", "optimized_pose"):
-        if key not in d:
-            p.error("%s has no %s" % (a.pose_pickle, key))
-    gt = d.get("gt_pose")
-    if a.align and gt is None:
-        p.error("--align true needs a gt_pose in %s" % a.pose_pickle)
-    from .prepare import _lift_engine
-    import torch
-    if not torch.cuda.is_available():
-        raise _capi.GemError("no HIP device visible: the BVH files are made on the device")
-    n = write_result_bvh(_lift_engine(DEFAULT_CALIBRATION, torch.cuda.current_device()), a.out, np.asarray(d["estimated_pose"]),
-                         np.asarray(d["optimized_pose"]), None if gt is None else np.asarray(gt), fps=a.fps, align=a.align,
-                         unit_scale=a.unit_scale)
+    n = write_result_bvh(*result_poses(p, a, "the BVH files are made on the device"), fps=a.fps, align=a.align, unit_scale=a.unit_scale)
     print("{} BVH files written under {}".format(n, a.out))
 
 

@@ -28,7 +28,6 @@ PLAIN_DIRS = ("optimized_global", "input_global", "gt_global")
 
 _layout = None
 _constant = None
-_buffers = {}          # device -> [pinned, pinned, device buffer]
 
 
 def layout():
@@ -96,12 +95,10 @@ def _write_file(path, parts):
 
 def write_meshes(engine, seq, out_dir, align_to=None, pattern="out_%04d.ply"):
     """`out_dir/pattern % f` for every frame f of `seq` [F,15,3] (the reference's save_mesh), `align_to` as in `vertex_blocks`.
-    The vertex blocks are made on the device, at most PINNED_BYTES of them at a time, and cross PCIe through two alternating
-    pinned buffers: while one is being written to files by the writer threads (at most MAX_WRITERS, on the CPUs near the
-    device), the next batch arrives in the other.  Runs on the current stream.  Every file is complete and closed when this
+    The vertex blocks are made on the device, at most PINNED_BYTES of them at a time, and go through `staging.stream_out` to the
+    writer threads (at most MAX_WRITERS, on the CPUs near the device).  Runs on the current stream.  Every file is complete and closed when this
     returns; returns the number of files."""
-    import torch
-    from .staging import cpus_near, reader_pool
+    from .staging import cpus_near, reader_pool, stream_out
     seq_d = _sequence(engine, seq)
     crt = _alignment(engine, seq_d, align_to)
     os.makedirs(out_dir, exist_ok=True)
@@ -110,58 +107,25 @@ def write_meshes(engine, seq, out_dir, align_to=None, pattern="out_%04d.ply"):
         return 0
     header, faces = constant()
     per = max(1, PINNED_BYTES // lay.vertex_bytes)
-    dev = engine.device
-    bufs = _buffers.get(dev)
-    if bufs is None:
-        bufs = _buffers[dev] = [torch.empty(per, lay.vertex_bytes, dtype=torch.uint8).pin_memory() for _ in range(2)] + \
-            [torch.empty(per, lay.vertex_bytes, dtype=torch.uint8, device=dev)]
-    pool = reader_pool("mesh", min(MAX_WRITERS, os.cpu_count() or 1), cpus_near(dev))
-    writing, arrived = [[], []], None          # per pinned buffer: its files' futures; the batch whose copy has been enqueued
+    pool = reader_pool("mesh", min(MAX_WRITERS, os.cpu_count() or 1), cpus_near(engine.device))
 
-    def hand_over(batch):
-        lo, n, slot, ev = batch
-        ev.synchronize()
-        rows = bufs[slot].numpy()
-        writing[slot] = [pool.submit(_write_file, os.path.join(out_dir, pattern % (lo + i)), (header, rows[i], faces)) for i in range(n)]
+    def produce(k, out):
+        n = min(per, F - k * per)
+        engine.skeleton_mesh(seq_d[k * per:k * per + n], crt, out=out.view(per, lay.vertex_bytes)[:n])
+        return n * lay.vertex_bytes
 
-    def settle(futures):
-        for f in futures:
-            f.result()          # (an OSError of a writer surfaces here)
-        del futures[:]
+    def consume(k, data, side):
+        rows = data.numpy().reshape(-1, lay.vertex_bytes)
+        return (pool.submit(_write_file, os.path.join(out_dir, pattern % (k * per + i)), (header, rows[i], faces)) for i in range(len(rows)))
 
-    try:
-        for k, lo in enumerate(range(0, F, per)):
-            n, slot = min(per, F - lo), k % 2
-            settle(writing[slot])
-            engine.skeleton_mesh(seq_d[lo:lo + n], crt, out=bufs[2][:n])
-            bufs[slot][:n].copy_(bufs[2][:n], non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record(torch.cuda.current_stream())
-            if arrived is not None:
-                hand_over(arrived)
-            arrived = (lo, n, slot, ev)
-        hand_over(arrived)
-        arrived = None
-        settle(writing[0])
-        settle(writing[1])
-    finally:
-        if arrived is not None:
-            arrived[3].synchronize()
-        for futures in writing:          # (on the way out of an exception: nothing may still read the pinned buffers)
-            for f in futures:
-                f.cancel()
-            for f in futures:
-                if not f.cancelled():
-                    try:
-                        f.result()
-                    except Exception:
-                        pass
+    stream_out(engine.device, "meshes", per * lay.vertex_bytes, (F + per - 1) // per, produce, consume)
     return F
 
 
 def release():
     """Give back the pinned and device buffers `write_meshes` keeps between calls."""
-    _buffers.clear()
+    from .staging import release_kept
+    release_kept("meshes")
 
 
 _HEADER_RE = re.compile(rb"ply\nformat binary_little_endian 1\.0\ncomment [^\n]*\nelement vertex (\d+)\nproperty double x\nproperty double y\n"
@@ -208,15 +172,10 @@ def write_result_meshes(engine, out_dir, estimated, optimized, gt=None, align=No
     return n
 
 
-def main(argv=None):
-    import argparse
-    from .camera import DEFAULT_CALIBRATION
-    truthy = lambda x: str(x).lower() == "true"          # noqa: E731  (the reference's own flag parser)
-    p = argparse.ArgumentParser(description="Skeleton meshes (PLY, one per frame) from a saved result_pose.pkl")
-    p.add_argument("pose_pickle", help="result_pose.pkl as --save_pose writes it: estimated_pose, optimized_pose and, optionally, gt_pose")
-    p.add_argument("--out", required=True, metavar="DIR")
-    p.add_argument("--align", default=False, type=truthy, help="true: align both sequences to gt_pose first (the reference's --save)")
-    a = p.parse_args(argv)
+def result_poses(p, a, why_a_device):
+    """What the command lines of `meshes`, `render` and `bvh` do behind their parser `p`: `a.pose_pickle` loaded and checked (with
+    `a.align`: it has a gt_pose), a device found and an engine made -> (engine, a.out, estimated, optimised, ground truth or None),
+    the leading arguments of a `write_result_*`."""
     with open(a.pose_pickle, "rb") as f:
         d = pickle.load(f)
     for key in ("estimated_pose", "optimized_pose"):
@@ -225,12 +184,24 @@ def main(argv=None):
     gt = d.get("gt_pose")
     if a.align and gt is None:
         p.error("--align true needs a gt_pose in %s" % a.pose_pickle)
+    from .camera import DEFAULT_CALIBRATION
     from .prepare import _lift_engine
     import torch
     if not torch.cuda.is_available():
-        raise _capi.GemError("no HIP device visible: the meshes are built on the device")
-    n = write_result_meshes(_lift_engine(DEFAULT_CALIBRATION, torch.cuda.current_device()), a.out, np.asarray(d["estimated_pose"]),
-                            np.asarray(d["optimized_pose"]), None if gt is None else np.asarray(gt), align=a.align)
+        raise _capi.GemError("no HIP device visible: " + why_a_device)
+    return (_lift_engine(DEFAULT_CALIBRATION, torch.cuda.current_device()), a.out, np.asarray(d["estimated_pose"]),
+            np.asarray(d["optimized_pose"]), None if gt is None else np.asarray(gt))
+
+
+def main(argv=None):
+    import argparse
+    truthy = lambda x: str(x).lower() == "true"          # noqa: E731  (the reference's own flag parser)
+    p = argparse.ArgumentParser(description="Skeleton meshes (PLY, one per frame) from a saved result_pose.pkl")
+    p.add_argument("pose_pickle", help="result_pose.pkl as --save_pose writes it: estimated_pose, optimized_pose and, optionally, gt_pose")
+    p.add_argument("--out", required=True, metavar="DIR")
+    p.add_argument("--align", default=False, type=truthy, help="true: align both sequences to gt_pose first (the reference's --save)")
+    a = p.parse_args(argv)
+    n = write_result_meshes(*result_poses(p, a, "the meshes are built on the device"), align=a.align)
     print("{} meshes written under {}".format(n, a.out))
 
 

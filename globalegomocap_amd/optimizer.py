@@ -23,7 +23,7 @@ from . import _capi
 from .camera import FisheyeCamera
 from .engine import WindowEngine, energy_weights, stats_to_numpy, raise_if_degenerate, LOCAL_STAGE, GLOBAL_STAGE
 from .errors import calculate_errors
-from .report import result_dir, result_pose_dict, write_result_outputs
+from .report import Outputs, result_dir, result_pose_dict
 from .sequence import (SEQ_LEN, OVERLAP, window_starts, cut_windows, merge_batches, final_smooth,
                        relative_global_numpy, to_global_numpy)
 from .skeleton import KINEMATIC_PARENTS
@@ -246,11 +246,11 @@ def main(data_id, camera_model_path, vae_weight, gmm_weight, smoothness_weight, 
         os.makedirs(out_dir, exist_ok=True)
         with open(os.path.join(out_dir, "result_pose.pkl"), "wb") as f:
             pickle.dump(result_pose_dict(final_estimated_seq, final_optimized_seq, mid_estimated_seq, final_gt_seq, final_smooth is True), f)
-    if save or render is not None or render_camera is not None or bvh is not None:
+    outputs = Outputs(mesh_root if save else None, render, render_camera, bvh, bvh_fps)
+    if outputs:
         sequences = (np.asarray(final_estimated_seq), final_optimized_d if device_metrics else np.asarray(final_optimized_seq),
                      np.asarray(final_gt_seq))
-        write_result_outputs(opt.engine, data_id, sequences, mesh_root if save else None, render, render_camera, cams, heat, bvh=bvh,
-                             bvh_fps=bvh_fps)
+        outputs.write(opt.engine, data_id, sequences, cams, heat)
     if device_metrics:
         errors = opt.engine.calculate_errors(final_estimated_seq, mid_estimated_seq, final_optimized_d, final_gt_seq)
     else:

@@ -23,7 +23,6 @@ Either set of frames can also become one clip that plays:
 """
 import ctypes as C
 import os
-import pickle
 import struct
 import zlib
 from collections import namedtuple
@@ -31,7 +30,9 @@ from collections import namedtuple
 import numpy as np
 
 from . import _capi
+from .meshes import _alignment, _sequence, result_poses
 from .skeleton import N_JOINTS
+from .video import DEFAULT_FPS, DEFAULT_QUALITY
 
 Layout = namedtuple("Layout", "row_bytes image_bytes stride")
 PINNED_BYTES = 64 << 20          # each of the two pinned buffers the scanlines cross PCIe through (69 images of 640 x 480)
@@ -43,8 +44,6 @@ CAMERA_SIZE = 512                # pixels each way of a camera view wherever a c
 HEAT_COLOUR = (148, 103, 189)    # the background's colour where the heat-maps say 1
 MARGIN = 0.1                     # metres around the joints' bounding box
 PNG_SIGNATURE = b"\x89PNG\r\n\x1a\n"
-
-_buffers = {}          # device -> (stride, [pinned, pinned, device buffer])
 
 
 def layout(width, height):
@@ -104,15 +103,6 @@ def fit_view(sequences, width, height, view="side"):
     return v
 
 
-def _sequence(engine, seq):
-    import torch
-    t = seq if torch.is_tensor(seq) else torch.from_numpy(np.array(seq, dtype=np.float64))
-    t = t.to(device=engine.device, dtype=torch.float64).contiguous()
-    if t.dim() != 3 or tuple(t.shape[1:]) != (N_JOINTS, 3):
-        raise ValueError("a pose sequence must be [F,%d,3], got %s" % (N_JOINTS, tuple(t.shape)))
-    return t
-
-
 def _prepare(engine, sequences, align_to):
     """The sequences on the device and, per sequence, the similarity (`WindowEngine.sequence_align`, [13] on the device) onto its
     entry of `align_to`: None, one sequence for all, or a list with a sequence or None for each."""
@@ -124,16 +114,7 @@ def _prepare(engine, sequences, align_to):
     targets = list(align_to) if isinstance(align_to, (list, tuple)) else [align_to] * len(seqs)
     if len(targets) != len(seqs):
         raise ValueError("align_to lists %d targets for %d sequences" % (len(targets), len(seqs)))
-    crts = []
-    for s, to in zip(seqs, targets):
-        if to is None:
-            crts.append(None)
-            continue
-        to_d = _sequence(engine, to)
-        if to_d.shape != s.shape:
-            raise ValueError("align_to must have the sequence's shape %s, got %s" % (tuple(s.shape), tuple(to_d.shape)))
-        crts.append(engine.sequence_align(s, to_d))
-    return seqs, crts
+    return seqs, [_alignment(engine, s, to) for s, to in zip(seqs, targets)]
 
 
 def frames_view(engine, sequences, align_to=None, size=None, view="side"):
@@ -248,63 +229,26 @@ def _write_images(engine, geom, rgb, first, view, paths):
 
 def _write_scanlines(engine, draw, W, H, paths):
     """Image i -> paths[i], W x H pixels each; `draw(lo, n, out)` renders the images lo .. lo + n into the rows of `out`.  The
-    scanlines are made on the device, at most PINNED_BYTES of them at a time, and cross PCIe through two alternating pinned
-    buffers: while one is being deflated and written by the writer threads, the next batch arrives in the other
-    (`meshes.write_meshes`' route).  Every file is complete and closed when this returns."""
-    import torch
-    from .staging import cpus_near, reader_pool
+    scanlines are made on the device, at most PINNED_BYTES of them at a time, and go through `staging.stream_out` to the meshes'
+    writer threads, which deflate and write them.  Every file is complete and closed when this returns."""
+    from .staging import cpus_near, reader_pool, stream_out
     n_images = len(paths)
     if n_images == 0:
         return
     lay = layout(W, H)
     per = max(1, PINNED_BYTES // lay.stride)
-    dev = engine.device
-    kept = _buffers.get(dev)
-    if kept is None or kept[0] != (lay.stride, per):
-        kept = _buffers[dev] = ((lay.stride, per), [torch.empty(per, lay.stride, dtype=torch.uint8).pin_memory() for _ in range(2)] +
-                                [torch.empty(per, lay.stride, dtype=torch.uint8, device=dev)])
-    bufs = kept[1]
-    pool = reader_pool("mesh", min(MAX_WRITERS, os.cpu_count() or 1), cpus_near(dev))          # (the meshes' writer threads)
-    writing, arrived = [[], []], None          # per pinned buffer: its files' futures; the batch whose copy has been enqueued
+    pool = reader_pool("mesh", min(MAX_WRITERS, os.cpu_count() or 1), cpus_near(engine.device))          # (the meshes' writer threads)
 
-    def hand_over(batch):
-        lo, n, slot, ev = batch
-        ev.synchronize()
-        rows = bufs[slot].numpy()
-        writing[slot] = [pool.submit(write_png, paths[lo + i], rows[i, :lay.image_bytes], W, H) for i in range(n)]
+    def produce(k, out):
+        n = min(per, n_images - k * per)
+        draw(k * per, n, out.view(per, lay.stride)[:n])
+        return n * lay.stride
 
-    def settle(futures):
-        for f in futures:
-            f.result()          # (an OSError of a writer surfaces here)
-        del futures[:]
+    def consume(k, data, side):
+        rows = data.numpy().reshape(-1, lay.stride)
+        return (pool.submit(write_png, paths[k * per + i], rows[i, :lay.image_bytes], W, H) for i in range(len(rows)))
 
-    try:
-        for k, lo in enumerate(range(0, n_images, per)):
-            n, slot = min(per, n_images - lo), k % 2
-            settle(writing[slot])
-            draw(lo, n, bufs[2][:n])
-            bufs[slot][:n].copy_(bufs[2][:n], non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record(torch.cuda.current_stream())
-            if arrived is not None:
-                hand_over(arrived)
-            arrived = (lo, n, slot, ev)
-        hand_over(arrived)
-        arrived = None
-        settle(writing[0])
-        settle(writing[1])
-    finally:
-        if arrived is not None:
-            arrived[3].synchronize()
-        for futures in writing:          # (on the way out of an exception: nothing may still read the pinned buffers)
-            for f in futures:
-                f.cancel()
-            for f in futures:
-                if not f.cancelled():
-                    try:
-                        f.result()
-                    except Exception:
-                        pass
+    stream_out(engine.device, "render", per * lay.stride, (n_images + per - 1) // per, produce, consume)
 
 
 def _video_arguments(video, video_fps, video_quality, frames):
@@ -313,12 +257,12 @@ def _video_arguments(video, video_fps, video_quality, frames):
         if not frames:
             raise ValueError("frames=False leaves nothing to write: it needs video=PATH")
         return
-    from .video import _check
-    _check(1, 1, video_fps, video_quality)
+    from .video import check_options
+    check_options(video_fps, video_quality)
 
 
 def write_frames(engine, sequences, out_dir, colours=None, align_to=None, size=None, view="side", overview=True, names=None, video=None,
-                 video_fps=25, video_quality=90, frames=True):
+                 video_fps=DEFAULT_FPS, video_quality=DEFAULT_QUALITY, frames=True):
     """`out_dir/frame_%04d.png` for every frame, all `sequences` (each [F,15,3]) overlaid in their `colours` (default: the palette's
     order estimated, optimised, ground truth), and -- overview=True -- `out_dir/overview_<name>.png` per sequence with all its
     frames in one scene (`names`, default: the palette's names).  align_to: None, one sequence [F,15,3] for all, or a list with one
@@ -360,8 +304,8 @@ def write_frames(engine, sequences, out_dir, colours=None, align_to=None, size=N
     return F + S + (video is not None)
 
 
-def write_result_frames(engine, out_dir, estimated, optimized, gt=None, align=None, size=None, view="side", video=None, video_fps=25,
-                        video_quality=90, frames=True):
+def write_result_frames(engine, out_dir, estimated, optimized, gt=None, align=None, size=None, view="side", video=None, video_fps=DEFAULT_FPS,
+                        video_quality=DEFAULT_QUALITY, frames=True):
     """One result's frames under `out_dir`: the estimated, the optimised and, where there is one, the ground-truth sequence overlaid
     (red, blue, green), the first two aligned to the third (`align`, default: whenever there is one) as `meshes.write_result_meshes`
     aligns the meshes.  video, video_fps, video_quality, frames: see `write_frames`."""
@@ -424,7 +368,7 @@ def camera_scanlines(engine, sequences, cams, heat, colours, size=None, joint_ra
 
 
 def write_camera_frames(engine, sequences, cams, heat, out_dir, colours=None, size=None, joint_radius=8.0, line_radius=3.0, heat_joints=None,
-                        align_to=None, video=None, video_fps=25, video_quality=90, frames=True):
+                        align_to=None, video=None, video_fps=DEFAULT_FPS, video_quality=DEFAULT_QUALITY, frames=True):
     """`out_dir/camera_%04d.png` for every frame: `camera_scanlines` (colours default: the palette's order) through `write_frames`'
     pinned buffers and writer threads.  video, video_fps, video_quality, frames: as in `write_frames`, the same images as one clip.
     Runs on the current stream; every file is complete and closed on return; returns the number of files."""
@@ -451,8 +395,8 @@ def write_camera_frames(engine, sequences, cams, heat, out_dir, colours=None, si
     return F + (video is not None and F > 0)
 
 
-def write_result_camera_frames(engine, out_dir, estimated, optimized, cams, heat, gt=None, size=None, video=None, video_fps=25,
-                               video_quality=90, frames=True):
+def write_result_camera_frames(engine, out_dir, estimated, optimized, cams, heat, gt=None, size=None, video=None, video_fps=DEFAULT_FPS,
+                               video_quality=DEFAULT_QUALITY, frames=True):
     """One result as the camera saw it, `out_dir/camera_%04d.png`: the estimated (red), the optimised (blue) and, where there is one,
     the ground-truth sequence (green) over the frames' heat-maps.  The ground truth lives in the studio's frame, not in the
     cameras': it is first moved by the one similarity that takes it onto the optimised sequence.  video, video_fps, video_quality,
@@ -465,7 +409,8 @@ def write_result_camera_frames(engine, out_dir, estimated, optimized, cams, heat
 
 def release():
     """Give back the pinned and device buffers `write_frames` keeps between calls."""
-    _buffers.clear()
+    from .staging import release_kept
+    release_kept("render")
 
 
 def _size(text):
@@ -493,7 +438,6 @@ def _size_or_side(text):
 
 def main(argv=None):
     import argparse
-    from .camera import DEFAULT_CALIBRATION
     truthy = lambda x: str(x).lower() == "true"          # noqa: E731  (the reference's own flag parser)
     p = argparse.ArgumentParser(description="Skeleton frames (PNG, one per frame, and one overview per sequence) from a saved result_pose.pkl")
     p.add_argument("pose_pickle", help="result_pose.pkl as --save_pose writes it: estimated_pose, optimized_pose and, optionally, gt_pose")
@@ -505,8 +449,8 @@ def main(argv=None):
                    help="draw the camera's view instead (camera_%%04d.png): the directory whose test_data.pkl holds the cameras and "
                         "heat-maps the poses belong to (merged frame f is the chunk's frame f); gt_pose is aligned onto optimized_pose")
     p.add_argument("--video", action="store_true", help="also write the frames as one Motion-JPEG clip, DIR/frames.avi (with --camera: DIR/camera.avi)")
-    p.add_argument("--video_fps", default=25.0, type=float, metavar="F", help="frames per second of the clip (default 25)")
-    p.add_argument("--video_quality", default=90, type=int, metavar="Q", help="JPEG quality of the clip, 1 .. 100 (default 90)")
+    p.add_argument("--video_fps", default=float(DEFAULT_FPS), type=float, metavar="F", help="frames per second of the clip (default 25)")
+    p.add_argument("--video_quality", default=DEFAULT_QUALITY, type=int, metavar="Q", help="JPEG quality of the clip, 1 .. 100 (default 90)")
     p.add_argument("--no_frames", action="store_true", help="with --video: the clip only, no PNG files")
     a = p.parse_args(argv)
     if not a.video_fps > 0:
@@ -524,20 +468,7 @@ def main(argv=None):
             p.error("argument --size: with --camera a size is one number of pixels 1 .. 1024")
         if not os.path.isfile(os.path.join(a.camera, "test_data.pkl")):
             p.error("--camera %s: no test_data.pkl in that directory" % a.camera)
-    with open(a.pose_pickle, "rb") as f:
-        d = pickle.load(f)
-    for key in ("estimated_pose", "optimized_pose"):
-        if key not in d:
-            p.error("%s has no %s" % (a.pose_pickle, key))
-    gt = d.get("gt_pose")
-    if a.align and gt is None:
-        p.error("--align true needs a gt_pose in %s" % a.pose_pickle)
-    from .prepare import _lift_engine
-    import torch
-    if not torch.cuda.is_available():
-        raise _capi.GemError("no HIP device visible: the frames are rendered on the device")
-    engine = _lift_engine(DEFAULT_CALIBRATION, torch.cuda.current_device())
-    est, opt = np.asarray(d["estimated_pose"]), np.asarray(d["optimized_pose"])
+    engine, out, est, opt, gt = result_poses(p, a, "the frames are rendered on the device")
     if a.camera is not None:
         from .whole_sequence import parse_chunk
         c = parse_chunk(a.camera, native=False, ground_truth=False)
@@ -545,11 +476,9 @@ def main(argv=None):
         if c["n"] < F or len(c["cams"]) < F:
             p.error("--camera %s holds %d frames, the poses %d" % (a.camera, min(c["n"], len(c["cams"])), F))
         heat = np.asarray(c["heat_list"][:F], dtype=np.float32).reshape((F,) + tuple(c["heat_shape"]))
-        n = write_result_camera_frames(engine, a.out, est, opt, c["cams"][:F], heat, None if gt is None else np.asarray(gt), size=a.size,
-                                       **clip)
+        n = write_result_camera_frames(engine, out, est, opt, c["cams"][:F], heat, gt, size=a.size, **clip)
     else:
-        n = write_result_frames(engine, a.out, est, opt, None if gt is None else np.asarray(gt), align=a.align,
-                                size=DEFAULT_SIZE if a.size is None else a.size, view=a.view, **clip)
+        n = write_result_frames(engine, out, est, opt, gt, align=a.align, size=DEFAULT_SIZE if a.size is None else a.size, view=a.view, **clip)
     print("{} {} written under {}".format(n, "files" if a.video else "images", a.out))
 
 

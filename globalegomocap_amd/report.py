@@ -1,6 +1,6 @@
 """The report half of a run: what one chunk's report is (`ChunkReport`), how a batch's reports are computed on the device
 (`batch_reports`, or chunk by chunk: `chunk_reports`), how a sequence's return value and printed summary follow from them
-(`sequence_result`), and the files a chunk's result may be written to (`write_result_outputs`, `result_pose_dict`).  Shared by the
+(`sequence_result`), and the files a chunk's result may be written to (`Outputs`, `result_pose_dict`).  Shared by the
 batch pipeline (`whole_sequence`) and the one-chunk `optimizer.main`; it imports neither."""
 import os
 from collections import OrderedDict
@@ -9,7 +9,7 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
-from . import meshes, render as rendering          # (`render` is also an argument's name here)
+from . import bvh as animation, meshes, render as rendering, video as clips          # (`bvh`, `render` and `video` are also fields' names here)
 from .errors import calculate_errors
 from .sequence import cut_windows, merge_batches, merge_chunks, final_smooth, relative_global_numpy, to_global_numpy
 
@@ -215,48 +215,69 @@ def result_dir(root, data_id):
     return os.path.join(root, os.path.split(dataset_dir)[1], seq_name)
 
 
-def write_result_outputs(engine, data_id, sequences, mesh_root=None, render=None, render_camera=None, cams=None, heat=None, first_frame=0,
-                         bvh=None, bvh_fps=None):
-    """One chunk's output files from `sequences` = (estimated, optimised, ground truth or None), host arrays or device tensors, each
-    under `result_dir` of its own root and only where that root is given:
+@dataclass(frozen=True)
+class Outputs:
+    """Which files a chunk's result is written to, and how: a root directory per kind (None: not asked for), each chunk's files
+    under `result_dir` of that root.
       mesh_root      the skeleton meshes, <chunk>/{optimized,input,gt}_global_aligned/out_%04d.ply (`meshes.write_result_meshes`);
       render         the frames, <chunk>/frame_%04d.png and overview_*.png (`render.write_result_frames`);
-      render_camera  the chunk as its camera saw it, <chunk>/camera_%04d.png (`render.write_result_camera_frames`): `cams` / `heat`
-                     hold the chunk's frames from `first_frame` on; merged frame f is the chunk's frame f;
+      render_camera  the chunk as its camera saw it, <chunk>/camera_%04d.png (`render.write_result_camera_frames`);
       bvh            the sequences as animation, <chunk>/{estimated,optimized,gt}.bvh at `bvh_fps` frames per second (default 25;
-                     `bvh.write_result_bvh`).
-    With a ground truth the estimated and the optimised sequence are aligned to it and all three are written, as in the reference;
-    without, nothing is aligned and there is no third sequence."""
-    est, opt, gt = sequences
-    if mesh_root is not None:
-        meshes.write_result_meshes(engine, result_dir(mesh_root, data_id), est, opt, gt)
-    if render is not None:
-        rendering.write_result_frames(engine, result_dir(render, data_id), est, opt, gt)
-    if render_camera is not None:
-        frames = slice(first_frame, first_frame + len(est))
-        rendering.write_result_camera_frames(engine, result_dir(render_camera, data_id), est, opt, cams[frames], heat[frames], gt)
-    if bvh is not None:
-        from . import bvh as animation          # (`bvh` is an argument's name here)
-        animation.write_result_bvh(engine, result_dir(bvh, data_id), est, opt, gt, fps=25 if bvh_fps is None else bvh_fps)
-
-
-def write_result_clips(engine, data_id, sequences, video=None, video_camera=None, cams=None, heat=None, first_frame=0, video_fps=None,
-                       video_quality=None):
-    """One chunk's clips from `sequences` as `write_result_outputs` takes them, each under `result_dir` of its own
-    root and only where that root is given:
+                     `bvh.write_result_bvh`);
       video          the frames `render` draws -- the same view and overlay, without the overviews -- as one Motion-JPEG clip,
-                     <chunk>/frames.avi (`render.write_result_frames(video=..., frames=False)`);
-      video_camera   the images `render_camera` draws as <chunk>/camera.avi; `cams` / `heat` / `first_frame` as there.
-    Both play at `video_fps` frames per second (default 25) and are encoded on the device at JPEG quality `video_quality` (default
-    90).  No PNG file is written here: the clips do not need `render` / `render_camera`, and `write_result_outputs` is untouched by them."""
-    est, opt, gt = sequences
-    clip = dict(video_fps=25 if video_fps is None else video_fps, video_quality=90 if video_quality is None else video_quality, frames=False)
-    if video is not None:
-        rendering.write_result_frames(engine, None, est, opt, gt, video=os.path.join(result_dir(video, data_id), "frames.avi"), **clip)
-    if video_camera is not None:
+                     <chunk>/frames.avi (DESIGN.md section 6j); no PNG file is written for it, and it does not need `render`;
+      video_camera   the images `render_camera` draws as <chunk>/camera.avi, likewise.
+    Both clips play at `video_fps` frames per second (default 25) and are encoded at JPEG quality `video_quality` (default 90)."""
+    mesh_root: object = None
+    render: object = None
+    render_camera: object = None
+    bvh: object = None
+    bvh_fps: object = None
+    video: object = None
+    video_camera: object = None
+    video_fps: object = None
+    video_quality: object = None
+
+    def __bool__(self):
+        return any(root is not None for root in (self.mesh_root, self.render, self.render_camera, self.bvh, self.video, self.video_camera))
+
+    @property
+    def needs_frames(self):
+        """Whether `write` reads the chunk's cameras and heat-maps."""
+        return self.render_camera is not None or self.video_camera is not None
+
+    def _rates(self):
+        """(bvh_fps, video_fps, video_quality) with the defaults where None was given."""
+        return (animation.DEFAULT_FPS if self.bvh_fps is None else self.bvh_fps, clips.DEFAULT_FPS if self.video_fps is None else self.video_fps,
+                clips.DEFAULT_QUALITY if self.video_quality is None else self.video_quality)
+
+    def check(self):
+        """ValueError for clip options no clip can be written with, before anything runs."""
+        if self.video is not None or self.video_camera is not None:
+            clips.check_options(*self._rates()[1:])
+
+    def write(self, engine, data_id, sequences, cams=None, heat=None, first_frame=0):
+        """One chunk's output files from `sequences` = (estimated, optimised, ground truth or None), host arrays or device tensors.
+        `cams` / `heat` (`needs_frames`) hold the chunk's frames from `first_frame` on; merged frame f is the chunk's frame f.  With
+        a ground truth the estimated and the optimised sequence are aligned to it and all three are written, as in the reference;
+        without, nothing is aligned and there is no third sequence."""
+        est, opt, gt = sequences
+        bvh_fps, video_fps, video_quality = self._rates()
+        clip = dict(video_fps=video_fps, video_quality=video_quality, frames=False)
         frames = slice(first_frame, first_frame + len(est))
-        rendering.write_result_camera_frames(engine, None, est, opt, cams[frames], heat[frames], gt,
-                                             video=os.path.join(result_dir(video_camera, data_id), "camera.avi"), **clip)
+        if self.mesh_root is not None:
+            meshes.write_result_meshes(engine, result_dir(self.mesh_root, data_id), est, opt, gt)
+        if self.render is not None:
+            rendering.write_result_frames(engine, result_dir(self.render, data_id), est, opt, gt)
+        if self.render_camera is not None:
+            rendering.write_result_camera_frames(engine, result_dir(self.render_camera, data_id), est, opt, cams[frames], heat[frames], gt)
+        if self.bvh is not None:
+            animation.write_result_bvh(engine, result_dir(self.bvh, data_id), est, opt, gt, fps=bvh_fps)
+        if self.video is not None:
+            rendering.write_result_frames(engine, None, est, opt, gt, video=os.path.join(result_dir(self.video, data_id), "frames.avi"), **clip)
+        if self.video_camera is not None:
+            rendering.write_result_camera_frames(engine, None, est, opt, cams[frames], heat[frames], gt,
+                                                 video=os.path.join(result_dir(self.video_camera, data_id), "camera.avi"), **clip)
 
 
 def result_pose_dict(est, opt, mid, gt, smooth):

@@ -1,12 +1,14 @@
-"""How bytes get from the host to the device: reader threads next to the device, two copy streams, pinned staging buffers.
+"""How bytes get to the device and back out to files: reader threads next to the device, two copy streams, pinned staging
+buffers, and the one two-slot loop device buffer -> pinned memory -> writer threads -> files.
 
-Nothing here knows about chunks, windows or MAT files.  `whole_sequence` (chunk pickles) and `prepare` (the pose network's
-.mat files) are built on it:
+Nothing here knows about chunks, windows, MAT files or file formats.  `whole_sequence` (chunk pickles) and `prepare` (the pose
+network's .mat files) are built on the inbound half, the writers (`meshes`, `render`, `bvh`, `video`) on the outbound half:
 
   * `reader_pool`: the process's named pools of reader threads, optionally confined to the CPUs `cpus_near` the device;
   * `copy_stream` / `report_stream`: the few streams the copies and the read-backs run on;
   * `thread_state` / `staging_buffer`: a reader thread's two alternating pinned buffers and the events that guard them;
   * `Scratch`: a pinned block from which small arrays go up asynchronously;
+  * `stream_out` / `kept_bytes` / `release_kept`: the outbound loop and the buffers it keeps between calls;
   * `padded`, `side_by_side`, `natural_key`, `Laps`, `drain`: layout, ordering, timing and clean-up helpers;
   * `release`: gives back what the module keeps between calls.
 """
@@ -26,6 +28,8 @@ _pools = {}
 _copy_streams = {}
 _report_streams = {}
 _copy_lock = threading.Lock()
+_kept = {}                             # (device, key, part) -> a uint8 buffer kept between calls (`kept_bytes`)
+STOP = "stop"                          # what a `stream_out` consumer returns to end the loop early
 _reader_local = threading.local()      # per reader thread: two pinned staging buffers, (whole_sequence.load_chunk only) a device image of the file
 
 
@@ -188,9 +192,116 @@ class Scratch:
         return view.to(self.device, non_blocking=True)
 
 
+# ------------------------------------------------------------------------------------------------------------------ device -> files
+def kept_bytes(device, key, part, nbytes, host=False, grow_only=False):
+    """The uint8 buffer of exactly `nbytes` kept between calls under (device, key, part): on the device, or (host=True) in host
+    memory, pinned unless the device is the CPU.  Re-made whenever `nbytes` differs from what is kept -- with grow_only, only when
+    it is more, and the buffer may then be larger than `nbytes`."""
+    device = torch.device(device)
+    buf = _kept.get((device, key, part))
+    if buf is None or (buf.numel() < nbytes if grow_only else buf.numel() != nbytes):
+        _kept.pop((device, key, part), None)          # (the old one goes before the new one is made)
+        buf = torch.empty(nbytes, dtype=torch.uint8, device="cpu" if host else device)
+        if host and device.type != "cpu":
+            buf = buf.pin_memory()
+        _kept[(device, key, part)] = buf
+    return buf
+
+
+def release_kept(key):
+    """Give back every buffer kept under `key` (on all devices)."""
+    for k in [k for k in _kept if k[1] == key]:
+        del _kept[k]
+
+
+def stream_out(device, key, nbytes, batches, produce, consume, side_bytes=0, waited=None):
+    """`batches` batches of bytes made on the device, each at most `nbytes`, through two alternating pinned buffers to the caller's
+    writer threads: while batch k is being written to its files, batch k+1 is made and crosses PCIe into the other buffer.
+
+    `produce(k, device_buffer)` enqueues batch k's kernels on the current stream, writing into `device_buffer` (uint8 [nbytes]; the
+    caller takes its 2-D views), and returns how many of its bytes are valid -- or (valid, side): `side` a small contiguous device
+    tensor of `side_bytes` bytes that travels beside the batch.  `valid` may instead be a uint8 device tensor of the caller's own
+    (a batch that outgrew `nbytes`): that one comes to the host with a blocking copy and is handed over in its turn, without overlap.
+    `consume(k, host_bytes, side)` is called on this thread once batch k has arrived and batch k+1 has been enqueued: `host_bytes`
+    is the uint8 host tensor of the valid bytes, `side` the uint8 host tensor [side_bytes] (None without; good until `consume`
+    returns).  It submits the batch's file work to a pool of the caller's and returns the futures -- best as a generator: the loop
+    takes them over one by one, so that those already submitted are looked after even if a later `submit` raises -- or STOP:
+    nothing more is enqueued, the batch already under way is dropped, and the loop settles what it has.
+
+    Batch k uses buffer k % 2; before `produce` may touch it, every future of the batch that last used it has been awaited (a
+    writer's exception surfaces there), and both buffers are settled before this returns: every file is complete.  On any
+    exception the last copy is waited for, futures that have not started are cancelled, the others awaited with their errors
+    swallowed, and the exception goes on: nothing reads or writes the buffers once this has returned.  The buffers are kept
+    between calls per (device, key) (`kept_bytes`, `release_kept`).  Everything runs on the current stream.  A `device` of type
+    cpu takes ordinary host memory, synchronous copies and no event.  `waited(name, seconds)`: told the time spent waiting for a
+    batch to arrive ("copy") and for a buffer's writers ("file")."""
+    if batches < 1:
+        return
+    device = torch.device(device)
+    on_gpu = device.type != "cpu"
+    host = [kept_bytes(device, key, "host%d" % i, nbytes, host=True) for i in range(2)]
+    sides = [kept_bytes(device, key, "side%d" % i, side_bytes, host=True) for i in range(2)] if side_bytes else None
+    dev = kept_bytes(device, key, "device", nbytes)
+    writing, arrived, last = [[], []], None, None          # per buffer: its batch's futures; the batch under way; the last copy's event
+
+    def wait(name, fn):
+        t0 = time.perf_counter()
+        try:
+            fn()
+        finally:
+            if waited is not None:
+                waited(name, time.perf_counter() - t0)
+
+    def settle(futures):
+        for f in futures:
+            wait("file", f.result)
+        del futures[:]
+
+    def hand_over(batch):
+        k, ev, data, side = batch
+        if ev is not None:
+            wait("copy", ev.synchronize)
+        out = consume(k, data, side)
+        if out != STOP:
+            for f in out:
+                writing[k % 2].append(f)
+        return out
+
+    try:
+        for k in range(batches):
+            settle(writing[k % 2])
+            out = produce(k, dev)
+            valid, side = out if isinstance(out, tuple) else (out, None)
+            if torch.is_tensor(valid):
+                data = valid.cpu()
+            else:
+                data = host[k % 2][:valid]
+                data.copy_(dev[:valid], non_blocking=True)
+            if side is not None:
+                sides[k % 2].copy_(side.view(torch.uint8).view(-1), non_blocking=True)
+                side = sides[k % 2]
+            if on_gpu:
+                last = torch.cuda.Event()
+                last.record(torch.cuda.current_stream())
+            batch, arrived = arrived, (k, last, data, side)
+            if batch is not None and hand_over(batch) == STOP:
+                arrived = None
+                break
+        if arrived is not None:
+            hand_over(arrived)
+        settle(writing[0])
+        settle(writing[1])
+    finally:
+        if last is not None:
+            last.synchronize()          # (the stream's last copy: with it every earlier one has left the buffers alone)
+        drain(writing[0])
+        drain(writing[1])
+
+
 def release():
-    """Give back what this module keeps between calls: the copy and report streams and the reader threads (with their pinned
-    staging buffers and device images).  Not to be called while a call that uses them is in flight."""
+    """Give back what this module keeps between calls: the copy and report streams, the outbound buffers and the reader threads
+    (with their pinned staging buffers and device images).  Not to be called while a call that uses them is in flight."""
+    _kept.clear()
     _copy_streams.clear()
     _report_streams.clear()
     pools = list(_pools.values())

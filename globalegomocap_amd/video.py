@@ -2,7 +2,7 @@
 
 `write_video` takes the images the renderers draw (`render._write_scanlines`' `draw(lo, n, out)` contract), turns every batch into
 baseline JPEG images on the device (`WindowEngine.jpeg_encode_into`: gem_jpeg_encode, already framed as the file's `00dc` chunks) and
-moves only those bytes -- a few tens of KB per frame instead of the scanlines -- through two alternating pinned buffers to one writer
+moves only those bytes -- a few tens of KB per frame instead of the scanlines -- through `staging.stream_out` to one writer
 thread, which appends them to the file and keeps the index.  The container is RIFF AVI 1.0 (no OpenDML: a file ends below 2 GiB),
 one video stream `MJPG`, an `idx1` index; `read_avi` reads such a file back, strictly.  No player exists where this was written: the
 container is checked against its specification and by reading it back (6j, "Container").
@@ -12,11 +12,10 @@ import struct
 
 PINNED_BYTES = 32 << 20          # each of the two pinned buffers the chunks cross PCIe through, and the device buffer they are made in
 SCAN_BYTES = 64 << 20            # the device buffer the scanlines are drawn into (`render.PINNED_BYTES`: the same batches)
+DEFAULT_FPS, DEFAULT_QUALITY = 25, 90          # of a clip wherever a caller gives none (`report.Outputs` resolves None to them)
 MAX_FILE = (1 << 31) - 1
 HEADER_BYTES = 224               # everything in front of the first chunk; the 'movi' fourcc is at 220
 AVIF_HASINDEX, AVIIF_KEYFRAME = 0x10, 0x10
-
-_buffers = {}          # device -> [pinned, pinned, device chunks, device scanlines or None]
 
 
 def _check(width, height, fps, quality):
@@ -26,6 +25,11 @@ def _check(width, height, fps, quality):
         raise ValueError("video_fps must be positive, got %r" % (fps,))
     if not (int(quality) == quality and 1 <= quality <= 100):
         raise ValueError("video_quality is a whole number 1 .. 100, got %r" % (quality,))
+
+
+def check_options(fps, quality):
+    """ValueError for a frame rate or a JPEG quality no clip can be written with."""
+    _check(1, 1, fps, quality)
 
 
 def _header(width, height, fps, frames, largest, movi_bytes):
@@ -48,7 +52,7 @@ class AviWriter:
     and sizes into the header.  A run that would take the file past 2^31 - 1 bytes closes it as a valid file of the frames written
     so far and raises OverflowError."""
 
-    def __init__(self, path, width, height, fps=25, quality=90):
+    def __init__(self, path, width, height, fps=DEFAULT_FPS, quality=DEFAULT_QUALITY):
         _check(width, height, fps, quality)
         self.path, self.width, self.height, self.fps = path, int(width), int(height), float(fps)
         os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
@@ -101,7 +105,7 @@ class AviWriter:
             f.close()
 
 
-def write_avi(path, frames, width, height, fps=25):
+def write_avi(path, frames, width, height, fps=DEFAULT_FPS):
     """JPEG files (a list of bytes) -> one AVI file; host only.  Returns the number of frames."""
     w = AviWriter(path, width, height, fps)
     try:
@@ -177,31 +181,18 @@ def read_avi(path):
     return fps, width, height, frames
 
 
-def _device_buffers(engine, scan_stride, per):
-    import torch
-    dev = engine.device
-    kept = _buffers.get(dev)
-    if kept is None:
-        kept = _buffers[dev] = [torch.empty(PINNED_BYTES, dtype=torch.uint8).pin_memory() for _ in range(2)] + \
-            [torch.empty(PINNED_BYTES, dtype=torch.uint8, device=dev), None]
-    if kept[3] is None or kept[3].numel() < per * scan_stride:
-        kept[3] = None
-        kept[3] = torch.empty(per * scan_stride, dtype=torch.uint8, device=dev)
-    return kept[:3] + [kept[3][:per * scan_stride].view(per, scan_stride)]
-
-
-def write_video(engine, draw, W, H, n_frames, path, fps=25, quality=90, timings=None):
+def write_video(engine, draw, W, H, n_frames, path, fps=DEFAULT_FPS, quality=DEFAULT_QUALITY, timings=None):
     """`n_frames` images of W x H pixels as one Motion-JPEG clip `path`; `draw(lo, n, out)` renders the images lo .. lo + n into the
     rows of `out`, a uint8 device tensor [n, stride] (`render._write_scanlines`' contract).  Batches as there: the scanlines are
     drawn into a device buffer, encoded on the device as the file's chunks (`WindowEngine.jpeg_encode_into`), the chunk offsets read
-    back, and only offsets[n] bytes cross PCIe, through two alternating pinned buffers; one writer thread appends them and keeps the
-    index (`AviWriter`).  A batch whose chunks outgrow the pinned buffer -- noise at quality 100 -- is encoded again into a buffer of
-    its own and written without the overlap.  Runs on the current stream; the file is complete and closed on return; returns
+    back, and only offsets[n] bytes cross PCIe (`staging.stream_out`); one writer thread appends them and keeps the index
+    (`AviWriter`).  A batch whose chunks outgrow the loop's buffer -- noise at quality 100 -- is encoded again into a buffer of its own
+    and written without the overlap.  Runs on the current stream; the file is complete and closed on return; returns
     n_frames.  timings: a dict that receives the seconds spent waiting in the phases render, encode, copy and file."""
     import time
     import torch
     from . import render
-    from .staging import reader_pool
+    from .staging import kept_bytes, reader_pool, stream_out
     _check(W, H, fps, quality)
     n_frames = int(n_frames)
     if n_frames < 0:
@@ -210,8 +201,8 @@ def write_video(engine, draw, W, H, n_frames, path, fps=25, quality=90, timings=
     per = max(1, min(SCAN_BYTES // lay.stride, n_frames))
     writer = AviWriter(path, W, H, fps, quality)
     pool = reader_pool("video", 1)          # one writer: the runs are appended in order
-    writing, arrived = [None, None], None
     laps = {"render": 0.0, "encode": 0.0, "copy": 0.0, "file": 0.0}
+    offsets_of = {}          # batch -> its chunks' offsets, from `produce` to `consume`
 
     def lap(name, t0, sync=False):
         if timings is not None and sync:
@@ -219,61 +210,33 @@ def write_video(engine, draw, W, H, n_frames, path, fps=25, quality=90, timings=
         laps[name] += time.perf_counter() - t0
         return time.perf_counter()
 
-    def settle(slot):
-        if writing[slot] is not None:
-            t0 = time.perf_counter()
-            try:
-                writing[slot].result()          # (an OSError or OverflowError of the writer surfaces here)
-            finally:
-                writing[slot] = None
-            lap("file", t0)
+    def waited(name, seconds):
+        laps[name] += seconds
 
-    def hand_over(batch):
-        slot, ev, at, data = batch
+    def produce(k, out):
+        n = min(per, n_frames - k * per)
+        scan = scanlines[:n]
         t0 = time.perf_counter()
-        ev.synchronize()
-        lap("copy", t0)
-        writing[slot] = pool.submit(writer.append, data, at)
+        draw(k * per, n, scan)
+        t0 = lap("render", t0, True)
+        offsets = torch.empty(n + 1, dtype=torch.int64, device=engine.device)
+        engine.jpeg_encode_into(scan, W, H, quality, True, out, offsets)
+        at = offsets_of[k] = offsets.tolist()          # the one read-back of the batch
+        lap("encode", t0)
+        if at[n] <= out.numel():
+            return at[n]
+        big = torch.empty(at[n], dtype=torch.uint8, device=engine.device)
+        engine.jpeg_encode_into(scan, W, H, quality, True, big, offsets)
+        return big
+
+    def consume(k, data, side):
+        return [pool.submit(writer.append, data.numpy(), offsets_of.pop(k))]
 
     try:
-        if n_frames:
-            bufs = _device_buffers(engine, lay.stride, per)
-        for k, lo in enumerate(range(0, n_frames, per)):
-            n, slot = min(per, n_frames - lo), k % 2
-            settle(slot)
-            t0 = time.perf_counter()
-            draw(lo, n, bufs[3][:n])
-            t0 = lap("render", t0, True)
-            offsets = torch.empty(n + 1, dtype=torch.int64, device=engine.device)
-            engine.jpeg_encode_into(bufs[3][:n], W, H, quality, True, bufs[2], offsets)
-            at = offsets.tolist()          # the one read-back of the batch
-            t0 = lap("encode", t0)
-            if at[n] <= PINNED_BYTES:
-                bufs[slot][:at[n]].copy_(bufs[2][:at[n]], non_blocking=True)
-                data = bufs[slot].numpy()
-            else:
-                big = torch.empty(at[n], dtype=torch.uint8, device=engine.device)
-                engine.jpeg_encode_into(bufs[3][:n], W, H, quality, True, big, offsets)
-                data = big.cpu().numpy()
-            ev = torch.cuda.Event()
-            ev.record(torch.cuda.current_stream())
-            if arrived is not None:
-                hand_over(arrived)
-            arrived = (slot, ev, at, data)
-        if arrived is not None:
-            hand_over(arrived)
-            arrived = None
-        settle(0)
-        settle(1)
+        if n_frames:          # the device buffer the scanlines are drawn into
+            scanlines = kept_bytes(engine.device, "video", "scanlines", per * lay.stride, grow_only=True)[:per * lay.stride].view(per, lay.stride)
+        stream_out(engine.device, "video", PINNED_BYTES, (n_frames + per - 1) // per, produce, consume, waited=waited)
     finally:
-        if arrived is not None:
-            arrived[1].synchronize()          # (nothing may still write the pinned buffers)
-        for w in writing:
-            if w is not None:
-                try:
-                    w.result()
-                except Exception:
-                    pass
         t0 = time.perf_counter()
         writer.close()
         lap("file", t0)
@@ -284,4 +247,5 @@ def write_video(engine, draw, W, H, n_frames, path, fps=25, quality=90, timings=
 
 def release():
     """Give back the pinned and device buffers `write_video` keeps between calls."""
-    _buffers.clear()
+    from .staging import release_kept
+    release_kept("video")

@@ -36,8 +36,8 @@ from . import _capi, staging
 from .staging import (Laps, Scratch, cpus_near, drain, natural_key, reader_pool, report_stream, side_by_side, staging_buffer,      # noqa: F401  (cpus_near, natural_key: part of this module's interface)
                       thread_state)
 from .optimizer import SequenceOptimizer, GLOBAL_VAE_PATH, LOCAL_VAE_PATH
-from .report import (QUALITY_LINES, QUALITY_KEYS, SUMMARY_LINES, batch_reports, chunk_reports, report_inputs, result_pose_dict,      # noqa: F401  (the three tables: part of this module's interface)
-                     sequence_result, write_result_clips, write_result_outputs)
+from .report import (QUALITY_LINES, QUALITY_KEYS, SUMMARY_LINES, Outputs, batch_reports, chunk_reports, report_inputs, result_pose_dict,      # noqa: F401  (the three tables: part of this module's interface)
+                     sequence_result)
 from .sequence import SEQ_LEN, OVERLAP, window_starts
 
 
@@ -306,32 +306,15 @@ def _settings(camera_model_path, vae_weight=0.0, gmm_weight=0.0, smoothness_weig
               reproj_weight=0.01, final_smooth=True, merge=True, global_vae_path=GLOBAL_VAE_PATH, local_vae_path=LOCAL_VAE_PATH,
               chunks_per_batch=None, optimizer=None, device_metrics=True, verbose=True, seq_len=SEQ_LEN, overlap=OVERLAP, timings=None,
               per_sequence=False, ground_truth=True, save_pose=None, save=False, mesh_root="out", render=None, render_camera=None, bvh=None,
-              bvh_fps=None):
-    """The arguments of `optimize_sequences` / `optimize_recordings` behind the sequences themselves, as one object.
+              bvh_fps=None, *, video=None, video_camera=None, video_fps=None, video_quality=None):
+    """The arguments of `optimize_sequences` / `optimize_recordings` behind the sequences themselves, as one object; `outputs`: the
+    files asked for (`report.Outputs`, checked here).  The clip arguments go by keyword only.
     (`gmm_weight` and `merge` are accepted and unused, as in the reference: SURVEY D4.)"""
+    outputs = Outputs(mesh_root if save else None, render, render_camera, bvh, bvh_fps, video, video_camera, video_fps, video_quality)
+    outputs.check()
     if not ground_truth and not device_metrics:
         raise ValueError("ground_truth=False: the report without ground truth is computed on the device only (device_metrics=True)")
     return SimpleNamespace(**locals())
-
-
-CLIP_KEYS = ("video", "video_camera", "video_fps", "video_quality")
-
-
-def _clip_settings(video=None, video_camera=None, video_fps=None, video_quality=None):
-    """The clip arguments of `optimize_sequences` / `optimize_recordings` (by keyword only: they travel beside `_settings`, whose
-    positional order is closed), checked before anything runs."""
-    if video is not None or video_camera is not None:
-        from .video import _check
-        _check(1, 1, 25 if video_fps is None else video_fps, 90 if video_quality is None else video_quality)
-    return dict(video=video, video_camera=video_camera, video_fps=video_fps, video_quality=video_quality)
-
-
-def _all_settings(camera_model_path, args, kwargs):
-    """`_settings` of everything but the clip arguments, and those (`_clip_settings`) as further attributes."""
-    clip = _clip_settings(**{k: kwargs.pop(k) for k in CLIP_KEYS if k in kwargs})
-    cfg = _settings(camera_model_path, *args, **kwargs)
-    cfg.__dict__.update(clip)
-    return cfg
 
 
 class _Pipeline:
@@ -519,7 +502,7 @@ class _Pipeline:
                 reports = chunk_reports(e, b.chunks, mid_np, opt_global, cfg.seq_len, cfg.overlap, bool(cfg.final_smooth), cfg.device_metrics,
                                         frames)
             view_heat, view_cams = None, None
-            if cfg.render_camera is not None or cfg.video_camera is not None:
+            if cfg.outputs.needs_frames:
                 # the camera's view reads the batch's frame buffers too; its files are complete (the device has read the frames) before
                 # this returns, three batches before the slot's frame buffer is filled again
                 view_heat, view_cams = b.heat_d.contiguous(), b.prep["cams"]
@@ -529,11 +512,7 @@ class _Pipeline:
             for ci, (src, r) in enumerate(zip(b.sources, reports)):
                 if r is not None:
                     name = os.path.normpath(src.name)
-                    write_result_outputs(e, name, r.sequences(), cfg.mesh_root if cfg.save else None, cfg.render, cfg.render_camera,
-                                         view_cams, view_heat, int(b.frame_lo[ci]), bvh=cfg.bvh, bvh_fps=cfg.bvh_fps)
-                    if cfg.video is not None or cfg.video_camera is not None:
-                        write_result_clips(e, name, r.sequences(), cfg.video, cfg.video_camera, view_cams, view_heat, int(b.frame_lo[ci]),
-                                           cfg.video_fps, cfg.video_quality)
+                    cfg.outputs.write(e, name, r.sequences(), view_cams, view_heat, int(b.frame_lo[ci]))
                     r.drop_views()          # (they alias this batch's slot, which batch k+3 fills again)
                     self.reports[src.group].append(r)
                     if cfg.save_pose is not None:
@@ -586,7 +565,7 @@ def optimize_sequences(data_dirs, camera_model_path, *args, **kwargs):
     Further arguments, positional or by keyword, in this order (defaults: `_settings`): vae_weight, gmm_weight, smoothness_weight,
     bone_length_weight, weight_3d, reproj_weight, final_smooth, merge, global_vae_path, local_vae_path, chunks_per_batch, optimizer,
     device_metrics, verbose, seq_len, overlap, timings, per_sequence, ground_truth, save_pose, save, mesh_root, render, render_camera,
-    bvh, bvh_fps; and by keyword only (`_clip_settings`): video, video_camera, video_fps, video_quality.
+    bvh, bvh_fps; and by keyword only: video, video_camera, video_fps, video_quality.
 
     ground_truth=False: the chunks carry no ground truth (`prepare` with a scale).  Their pickles are not asked for
     `gt_global_skeleton`, every chunk's report is the seven entries of QUALITY_KEYS (`WindowEngine.sequence_quality` on the estimated
@@ -612,8 +591,8 @@ def optimize_sequences(data_dirs, camera_model_path, *args, **kwargs):
     video=DIR: every chunk's frames -- the view and overlay of `render`, without the overviews -- as one Motion-JPEG clip,
     `DIR/<dataset>/<chunk>/frames.avi`; video_camera=DIR: the images of `render_camera` as `.../camera.avi`.  Neither needs the PNG
     option: without it no PNG file is written.  Both play at `video_fps` frames per second (default 25) and are encoded on the device
-    at JPEG quality `video_quality` (default 90; `report.write_result_clips`).  Results and reports do not depend on them."""
-    cfg = _all_settings(camera_model_path, args, kwargs)
+    at JPEG quality `video_quality` (default 90; `report.Outputs`).  Results and reports do not depend on them."""
+    cfg = _settings(camera_model_path, *args, **kwargs)
     lap = Laps(cfg.timings, log=True)          # developer timing (tools/whole_sequence_timing.py): wall time of the main thread's phases
     groups = []
     for gi, d in enumerate(data_dirs):
@@ -635,7 +614,7 @@ def optimize_recordings(recordings, camera_model_path, *args, **kwargs):
     value and printed summary, one entry per `Recording`; no pickle is written or read.  The optimiser is handed the same
     float32 heat-maps, float64 skeletons and cameras that `Recording.write_chunks` + `optimize_sequences` would hand it, so
     the results are bitwise those."""
-    cfg = _all_settings(camera_model_path, args, kwargs)
+    cfg = _settings(camera_model_path, *args, **kwargs)
     lap = Laps(cfg.timings, log=True)
     titles = ["recording_%d" % gi for gi in range(len(recordings))]
     groups = []

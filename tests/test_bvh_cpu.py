@@ -173,21 +173,26 @@ def test_the_argument_is_wired_and_none_writes_nothing(B, tmp_path, monkeypatch)
     cfg = ws._settings("cam.json", bvh="somewhere", bvh_fps=30.0)
     assert cfg.bvh == "somewhere" and cfg.bvh_fps == 30.0
     assert ws._settings("cam.json").bvh is None and ws._settings("cam.json").bvh_fps is None
-    for fn in (ws._settings, optimizer.main, report.write_result_outputs):
-        par = list(inspect.signature(fn).parameters.values())
+    for fn in (ws._settings, optimizer.main):
+        par = [p for p in inspect.signature(fn).parameters.values() if p.kind is p.POSITIONAL_OR_KEYWORD]
         assert [p.name for p in par[-2:]] == ["bvh", "bvh_fps"] and par[-2].default is None and par[-1].default is None, fn
+    # the positional order of `_settings` is closed: what comes later goes by keyword only
+    assert [p.name for p in inspect.signature(ws._settings).parameters.values() if p.kind is p.POSITIONAL_OR_KEYWORD] == [
+        "camera_model_path", "vae_weight", "gmm_weight", "smoothness_weight", "bone_length_weight", "weight_3d", "reproj_weight", "final_smooth",
+        "merge", "global_vae_path", "local_vae_path", "chunks_per_batch", "optimizer", "device_metrics", "verbose", "seq_len", "overlap",
+        "timings", "per_sequence", "ground_truth", "save_pose", "save", "mesh_root", "render", "render_camera", "bvh", "bvh_fps"]
     a = ws._parser().parse_args(["--data_path", "d", "--bvh", "B", "--bvh_fps", "50"])
     assert a.bvh == "B" and a.bvh_fps == 50.0
     a = ws._parser().parse_args(["--data_path", "d"])
     assert a.bvh is None and a.bvh_fps is None
     monkeypatch.chdir(tmp_path)
     seqs = (np.zeros((3, 15, 3)), np.zeros((3, 15, 3)), None)
-    report.write_result_outputs(None, "studio/chunk_0", seqs)
-    report.write_result_outputs(None, "studio/chunk_0", seqs, bvh=None, bvh_fps=30)
+    report.Outputs().write(None, "studio/chunk_0", seqs)
+    report.Outputs(bvh=None, bvh_fps=30).write(None, "studio/chunk_0", seqs)
     assert os.listdir(str(tmp_path)) == []
     calls = []
     monkeypatch.setattr(B, "write_result_bvh", lambda *a, **k: calls.append((a, k)))
-    report.write_result_outputs("engine", "data/studio/chunk_0", seqs, bvh="root")
-    report.write_result_outputs("engine", "data/studio/chunk_0", seqs, bvh="root", bvh_fps=50)
+    report.Outputs(bvh="root").write("engine", "data/studio/chunk_0", seqs)
+    report.Outputs(bvh="root", bvh_fps=50).write("engine", "data/studio/chunk_0", seqs)
     assert [c[0][:2] for c in calls] == [("engine", os.path.join("root", "studio", "chunk_0"))] * 2
     assert [c[1]["fps"] for c in calls] == [25, 50] and calls[0][0][2] is seqs[0] and calls[0][0][4] is None

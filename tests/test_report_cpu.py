@@ -118,14 +118,14 @@ def test_write_result_outputs_calls_the_writers_asked_for(monkeypatch):
     monkeypatch.setattr(render, "write_result_camera_frames", lambda *a: calls.append(("camera",) + a))
     r = _with_gt(7, 3)
     cams, heat = np.arange(10), np.arange(10) * 2
-    R.write_result_outputs("engine", "d/studio/chunk_2", r.sequences())
+    R.Outputs().write("engine", "d/studio/chunk_2", r.sequences())
     assert calls == []
-    R.write_result_outputs("engine", "d/studio/chunk_2", r.sequences(), mesh_root="m")
+    R.Outputs(mesh_root="m").write("engine", "d/studio/chunk_2", r.sequences())
     assert [c[:3] for c in calls] == [("meshes", "engine", "m/studio/chunk_2")] and all(x is y for x, y in zip(calls[0][3:], (r.est, r.opt, r.gt)))
     del calls[:]
     # the device views where the report left them, every writer, the camera's frames from the chunk's first frame on
     r.views = ("est_d", "opt_d", "gt_d")
-    R.write_result_outputs("engine", "d/studio/chunk_2", r.sequences(), "m", "f", "c", cams, heat, 4)
+    R.Outputs("m", "f", "c").write("engine", "d/studio/chunk_2", r.sequences(), cams, heat, 4)
     assert [c[:6] for c in calls[:2]] == [("meshes", "engine", "m/studio/chunk_2", "est_d", "opt_d", "gt_d"),
                                           ("frames", "engine", "f/studio/chunk_2", "est_d", "opt_d", "gt_d")] and len(calls) == 3
     name, engine, folder, est, opt, c, h, gt = calls[2]
@@ -134,7 +134,7 @@ def test_write_result_outputs_calls_the_writers_asked_for(monkeypatch):
     del calls[:]
     # without ground truth and without views: the host arrays, None for the third
     q = _without_gt(9, 3)
-    R.write_result_outputs("engine", "chunk_0", q.sequences(), render="f", render_camera="c", cams=cams, heat=heat)
+    R.Outputs(render="f", render_camera="c").write("engine", "chunk_0", q.sequences(), cams=cams, heat=heat)
     assert [c[0] for c in calls] == ["frames", "camera"] and calls[0][2] == "f/chunk_0" and calls[1][2] == "c/chunk_0"
     assert calls[0][3] is q.est and calls[0][4] is q.opt and calls[0][5] is None and calls[1][7] is None
     assert calls[1][5].tolist() == [0, 1, 2] and calls[1][6].tolist() == [0, 2, 4]

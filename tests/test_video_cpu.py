@@ -258,9 +258,9 @@ def test_argument_errors(V, tmp_path, capsys):
     with pytest.raises(ValueError, match="frames=False"):
         R.write_camera_frames(None, seqs, None, None, out, frames=False)
     with pytest.raises(ValueError, match="video_quality"):
-        ws._all_settings("cam.json", (), dict(video="d", video_quality=0))
+        ws._settings("cam.json", video="d", video_quality=0)
     with pytest.raises(ValueError, match="video_fps"):
-        ws._all_settings("cam.json", (), dict(video_camera="d", video_fps=0.0))
+        ws._settings("cam.json", video_camera="d", video_fps=0.0)
     with pytest.raises(ValueError, match="video_fps"):
         V.AviWriter(clip, 20, 12, fps=0)
     for argv, word in ((["--data_path", "d", "--video", "v", "--video_quality", "0"], "--video_quality"),
@@ -279,26 +279,28 @@ def test_argument_errors(V, tmp_path, capsys):
 
 def test_the_arguments_are_wired_and_none_writes_nothing(V, tmp_path, monkeypatch):
     from globalegomocap_amd import render as R, report, whole_sequence as ws
-    cfg = ws._all_settings("cam.json", (), dict(video="a", video_camera="b", video_fps=30.0, video_quality=75, bvh="c"))
+    cfg = ws._settings("cam.json", video="a", video_camera="b", video_fps=30.0, video_quality=75, bvh="c")
     assert (cfg.video, cfg.video_camera, cfg.video_fps, cfg.video_quality, cfg.bvh) == ("a", "b", 30.0, 75, "c")
-    cfg = ws._all_settings("cam.json", (0.5,), {})
+    cfg = ws._settings("cam.json", 0.5)
     assert (cfg.video, cfg.video_camera, cfg.video_fps, cfg.video_quality, cfg.vae_weight) == (None, None, None, None, 0.5)
+    with pytest.raises(TypeError):          # the clip options go by keyword only: there is no 28th positional argument
+        ws._settings("cam.json", *([None] * 27))
     a = ws._parser().parse_args(["--data_path", "d", "--video", "V", "--video_camera", "C", "--video_fps", "50", "--video_quality", "80"])
     assert (a.video, a.video_camera, a.video_fps, a.video_quality) == ("V", "C", 50.0, 80)
     a = ws._parser().parse_args(["--data_path", "d"])
     assert (a.video, a.video_camera, a.video_fps, a.video_quality) == (None, None, None, None)
     monkeypatch.chdir(tmp_path)
     seqs = (np.zeros((3, 15, 3)), np.zeros((3, 15, 3)), None)
-    report.write_result_clips(None, "studio/chunk_0", seqs)
-    report.write_result_clips(None, "studio/chunk_0", seqs, video_fps=30, video_quality=50)
+    report.Outputs().write(None, "studio/chunk_0", seqs)
+    report.Outputs(video_fps=30, video_quality=50).write(None, "studio/chunk_0", seqs)
     assert os.listdir(str(tmp_path)) == []
     calls = []
     monkeypatch.setattr(R, "write_result_frames", lambda *a, **k: calls.append(("frames", a, k)))
     monkeypatch.setattr(R, "write_result_camera_frames", lambda *a, **k: calls.append(("camera", a, k)))
     cams, heat = np.zeros((5, 4, 4)), np.zeros((5, 2, 2, 15))
-    report.write_result_clips("engine", "data/studio/chunk_0", seqs, video="root")
-    report.write_result_clips("engine", "data/studio/chunk_0", seqs, video="root", video_camera="cam", cams=cams, heat=heat, first_frame=1,
-                              video_fps=50, video_quality=70)
+    report.Outputs(video="root").write("engine", "data/studio/chunk_0", seqs)
+    report.Outputs(video="root", video_camera="cam", video_fps=50, video_quality=70).write("engine", "data/studio/chunk_0", seqs, cams=cams,
+                                                                                          heat=heat, first_frame=1)
     assert [c[0] for c in calls] == ["frames", "frames", "camera"]
     assert calls[0][2] == dict(video=os.path.join("root", "studio", "chunk_0", "frames.avi"), video_fps=25, video_quality=90, frames=False)
     assert calls[2][2] == dict(video=os.path.join("cam", "studio", "chunk_0", "camera.avi"), video_fps=50, video_quality=70, frames=False)
