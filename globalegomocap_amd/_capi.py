@@ -173,6 +173,9 @@ SIGNATURES = {
     "gem_jpeg_header": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, C.c_int64]),
     "gem_jpeg_bound": (C.c_int64, [C.c_int, C.c_int]),
     "gem_jpeg_encode": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, _P, C.c_int64, _P, _P, _P]),
+    "gem_keypoint_heatmaps": (C.c_int, [_P, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_double, _P, _P]),
+    "gem_lift_keypoints": (C.c_int, [_P, _P, _P, C.c_int64, C.POINTER(C.c_double), C.c_int, _P, _P, _P, _P, _P]),
+    "gem_fill_missing": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P]),
 }
 
 _lib = None

@@ -753,6 +753,61 @@ class WindowEngine:
                                                len(poly), upscale, pad_x, pad_y, _ptr(o64), _ptr(o32), _stream()), self.lib)
         return o64, o32
 
+    # ------------------------------------------------------------------ 2-D joint detections (DESIGN.md section 6k)
+    def _keypoints(self, what, kp):
+        """[F,15,2|3] detections (u, v[, confidence]) -> a contiguous [F,15,3] f64 device tensor; without a third column every
+        confidence is 1."""
+        t = self._f64(kp)
+        if t.dim() != 3 or t.shape[1] != N_JOINTS or t.shape[2] not in (2, 3):
+            raise ValueError("%s wants detections [F,%d,2] or [F,%d,3], got %s" % (what, N_JOINTS, N_JOINTS, tuple(t.shape)))
+        if t.shape[2] == 2:
+            t = torch.cat([t, torch.ones_like(t[..., :1])], dim=2).contiguous()
+        return t
+
+    def keypoint_heatmaps(self, kp, sigma=1.5, out=None):
+        """kp [F,15,2|3] (u, v in pixels of the fisheye image[, confidence]) -> heat [F,H,W,15] f32 at the engine's `heat_size`: unit-peak
+        Gaussians times the clamped confidence, centred where the reprojection term samples (u, v); a blank map for an unusable
+        detection (gem_keypoint_heatmaps).  `out`: a contiguous float32 device tensor of that shape to write into.  No synchronisation."""
+        t = self._keypoints("keypoint_heatmaps", kp)
+        sigma = float(sigma)
+        if not (np.isfinite(sigma) and sigma > 0):
+            raise ValueError("keypoint_heatmaps: sigma must be a positive number, got %r" % sigma)
+        F, (H, W) = t.shape[0], self.heat_size
+        if out is None:
+            out = torch.empty(F, H, W, N_JOINTS, device=self.device, dtype=torch.float32)
+        self._live_check("keypoint_heatmaps", (out, torch.float32, (F, H, W, N_JOINTS)))
+        _capi.check(self.lib.gem_keypoint_heatmaps(_ptr(t), F, N_JOINTS, H, W, sigma, _ptr(out), _stream()), self.lib)
+        return out
+
+    def lift_keypoints(self, kp, depth, prev=None, want_f64=True):
+        """kp [F,15,2|3] + depth [F,15] -> (o64 [F,15,3] f64 or None, o32 [F,15,3] f32, valid [F,15] u8): camera2world at the sub-pixel
+        detection (gem_lift_keypoints).  prev None: an unusable joint is zeros (`fill_missing` replaces it).  prev [15,3] f64, a
+        contiguous device tensor: frames in order, an unusable joint takes prev's value, every usable one updates it, in place."""
+        t = self._keypoints("lift_keypoints", kp)
+        F = t.shape[0]
+        dep = self._f64(depth)
+        if dep.numel() != F * N_JOINTS:
+            raise ValueError("lift_keypoints wants depth [F,%d] for these %d frames, got %s" % (N_JOINTS, F, tuple(dep.shape)))
+        self._live_check("lift_keypoints", (prev, torch.float64, (N_JOINTS, 3)))
+        poly = np.ascontiguousarray(self.camera.poly_c2w, dtype=np.float64)
+        o64 = torch.empty(F, N_JOINTS, 3, device=self.device, dtype=torch.float64) if want_f64 else None
+        o32 = torch.empty(F, N_JOINTS, 3, device=self.device, dtype=torch.float32)
+        valid = torch.empty(F, N_JOINTS, device=self.device, dtype=torch.uint8)
+        _capi.check(self.lib.gem_lift_keypoints(self._h, _ptr(t), _ptr(dep), F, poly.ctypes.data_as(C.POINTER(C.c_double)), len(poly),
+                                                _ptr(prev), _ptr(o64), _ptr(o32), _ptr(valid), _stream()), self.lib)
+        return o64, o32, valid
+
+    def fill_missing(self, seq, valid, n_chunks):
+        """In place on seq [n_chunks*F,15,3] f64 with valid [n_chunks*F,15] u8 (contiguous device tensors): per chunk and joint, frames
+        with valid 0 become the linear interpolation in time between their valid neighbours, the nearest valid value at the chunk's
+        ends (gem_fill_missing).  A joint with no valid frame in a chunk stays as it is.  -> seq.  No synchronisation."""
+        total = int(seq.shape[0]) if torch.is_tensor(seq) and seq.dim() == 3 else -1
+        if n_chunks < 1 or total < 0 or total % n_chunks:
+            raise ValueError("fill_missing: a sequence [n,%d,3] of %d equal chunks is wanted" % (N_JOINTS, n_chunks))
+        self._live_check("fill_missing", (seq, torch.float64, (total, N_JOINTS, 3)), (valid, torch.uint8, (total, N_JOINTS)))
+        _capi.check(self.lib.gem_fill_missing(_ptr(seq), _ptr(valid), int(n_chunks), total // n_chunks, N_JOINTS, _stream()), self.lib)
+        return seq
+
     # ------------------------------------------------------------------ profiling hook (bench.py)
     def profile_enable(self, on):
         _capi.check(self.lib.gem_profile_enable(self._h, 1 if on else 0), self.lib)

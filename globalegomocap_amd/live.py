@@ -61,12 +61,14 @@ def _pieces(n_pushed, k):
     return out
 
 
-def check_push(n_pushed_times, heat, depth, est_local, rows, cams, times, heat_size=(64, 64)):
-    """The host-side checks of `LiveOptimizer.push`, before anything is enqueued: exactly one of depth / est_local and of rows /
-    cams + times, shapes that agree on k >= 1 frames, timestamps that increase strictly (also past `n_pushed_times`, the last
-    timestamp of the pushes before; None on the first).  -> (k, timestamps as a float64 array, the five other arguments as arrays or tensors).  ValueError otherwise."""
-    if heat is None:
+def check_push(n_pushed_times, heat, depth, est_local, rows, cams, times, heat_size=(64, 64), keypoints=None):
+    """The host-side checks of `LiveOptimizer.push`, before anything is enqueued: exactly one of heat / keypoints, of depth / est_local
+    and of rows / cams + times, shapes that agree on k >= 1 frames, timestamps that increase strictly (also past `n_pushed_times`, the
+    last timestamp of the pushes before; None on the first).  -> (k, timestamps as a float64 array, the five other arguments as arrays or tensors).  ValueError otherwise."""
+    if heat is None and keypoints is None:
         raise ValueError("push: heat= is needed")
+    if heat is not None and keypoints is not None:
+        raise ValueError("push: give exactly one of heat= (the pose network's maps) and keypoints= (2-D detections, splatted here)")
     heat, depth, est_local, rows, cams, times = (x if x is None or torch.is_tensor(x) else np.asarray(x) for x in (heat, depth, est_local, rows, cams, times))
     if (depth is None) == (est_local is None):
         raise ValueError("push: give exactly one of depth= (lifted here) and est_local= (already lifted)")
@@ -74,10 +76,16 @@ def check_push(n_pushed_times, heat, depth, est_local, rows, cams, times, heat_s
         raise ValueError("push: give exactly one of rows= (trajectory rows) and cams= with times=")
     if (cams is None) != (times is None):
         raise ValueError("push: cams= and times= come together (rows= carry their own timestamps)")
-    k = int(heat.shape[0]) if len(heat.shape) == 4 else -1
-    want = (k,) + tuple(heat_size) + (N_JOINTS,)
-    if k < 1 or tuple(heat.shape) != want:
-        raise ValueError("push: heat must be [k,%d,%d,%d] with k >= 1, got %s" % (tuple(heat_size) + (N_JOINTS, tuple(heat.shape))))
+    if keypoints is not None:
+        shape = tuple(keypoints.shape) if torch.is_tensor(keypoints) else np.shape(keypoints)
+        k = int(shape[0]) if len(shape) == 3 else -1
+        if k < 1 or shape[1] != N_JOINTS or shape[2] not in (2, 3):
+            raise ValueError("push: keypoints must be [k,%d,2] or [k,%d,3] (u, v[, confidence]) with k >= 1, got %s" % (N_JOINTS, N_JOINTS, shape))
+    else:
+        k = int(heat.shape[0]) if len(heat.shape) == 4 else -1
+        want = (k,) + tuple(heat_size) + (N_JOINTS,)
+        if k < 1 or tuple(heat.shape) != want:
+            raise ValueError("push: heat must be [k,%d,%d,%d] with k >= 1, got %s" % (tuple(heat_size) + (N_JOINTS, tuple(heat.shape))))
     for name, x, shape in (("depth", depth, (k, N_JOINTS)), ("est_local", est_local, (k, N_JOINTS, 3)), ("rows", rows, (k, 8)),
                            ("cams", cams, (k, 4, 4)), ("times", times, (k,))):
         if x is not None and tuple(x.shape) != shape:
@@ -102,10 +110,11 @@ class LiveOptimizer:
     eps: None -- torch.randn(2, D) per window (local stage, then global) from a generator seeded by `seed` -- or callable(w) -> [2,D].
     graphs: replay one captured `optimize_windows` call for every window (the window's inputs lie in buffers of fixed address).
     scale: the SLAM scale applied to the translations of `rows=`.
+    sigma: the width, in heat-map pixels, of the Gaussians that `push(keypoints=)` splats.
     """
 
     def __init__(self, camera_model_path, global_vae=GLOBAL_VAE_PATH, local_vae=LOCAL_VAE_PATH, *, scale=1.0, weights=None, bone="running",
-                 one_euro=None, eps=None, seed=0, graphs=True, lr=2, max_iter=25, heat_size=(64, 64)):
+                 one_euro=None, eps=None, seed=0, graphs=True, lr=2, max_iter=25, heat_size=(64, 64), sigma=1.5):
         sd_g, sd_l = _as_state_dict(global_vae), _as_state_dict(local_vae)
         shape = infer_shape(sd_l, seq_len=SEQ_LEN)
         if infer_shape(sd_g, seq_len=SEQ_LEN) != shape:
@@ -116,7 +125,9 @@ class LiveOptimizer:
                 one_euro += (1.0,)
             if len(one_euro) != 3 or not all(np.isfinite(v) and v >= 0 for v in one_euro) or one_euro[0] <= 0 or one_euro[2] <= 0:
                 raise ValueError("one_euro is (min_cutoff > 0, beta >= 0, d_cutoff > 0), got %r" % (one_euro,))
-        self.one_euro, self.scale = one_euro, float(scale)
+        self.one_euro, self.scale, self.sigma = one_euro, float(scale), float(sigma)
+        if not (np.isfinite(self.sigma) and self.sigma > 0):
+            raise ValueError("sigma must be a positive number, got %r" % (sigma,))
         self.engine = e = WindowEngine(shape, FisheyeCamera.from_json(camera_model_path), max_windows=1, heat_size=heat_size)
         e.load_vae(LOCAL_STAGE, sd_l)
         e.load_vae(GLOBAL_STAGE, sd_g)
@@ -141,6 +152,7 @@ class LiveOptimizer:
         self._mean_bone = torch.zeros(1, N_JOINTS, device=dev, dtype=torch.float32)
         self._eps_l, self._eps_g = (torch.zeros(1, e.D, device=dev, dtype=torch.float32) for _ in range(2))
         self._out = torch.zeros(2, STRIDE, N_JOINTS, 3, device=dev, dtype=torch.float64)
+        self._kp_prev = torch.zeros(N_JOINTS, 3, device=dev, dtype=torch.float64)          # push(keypoints=, depth=): the last usable lift of every joint
         self.n_pushed = self.n_windows = self.n_emitted = 0
         self._last_time, self._row0, self._flushed = None, None, False
         self.window_log, self._optimized, self._estimated = [], [], []
@@ -152,7 +164,7 @@ class LiveOptimizer:
             torch.cuda.synchronize(self.engine.device)
             self.engine.close()
         self.engine = self._bufs = self._win_pose = self._win_cams = self._win_heat = self._out = None
-        self._mean_bone = self._eps_l = self._eps_g = self._frame0 = self._bone_fixed = None
+        self._mean_bone = self._eps_l = self._eps_g = self._frame0 = self._bone_fixed = self._kp_prev = None
 
     def __enter__(self):
         return self
@@ -197,8 +209,11 @@ class LiveOptimizer:
         both = np.concatenate([self._row0, rows])
         return slam.scaled_trajectory(both[:, 1:4], both[:, 4:8], self.scale)[1:]
 
-    def push(self, *, heat=None, depth=None, est_local=None, rows=None, cams=None, times=None):
-        """k >= 1 new frames: heat [k,H,W,15]; either depth [k,15] (lifted with `WindowEngine.lift_skeleton`) or est_local [k,15,3]
+    def push(self, *, heat=None, depth=None, est_local=None, rows=None, cams=None, times=None, keypoints=None):
+        """k >= 1 new frames: heat [k,H,W,15], or in its place keypoints [k,15,2|3] -- 2-D detections (u, v[, confidence]) in pixels of the
+        fisheye image, splatted into the maps on the device (`WindowEngine.keypoint_heatmaps`; with depth= they are lifted at the
+        detection itself, `lift_keypoints`, a joint without a usable detection holding its last usable lift: the session's first frame
+        must have every joint); either depth [k,15] (lifted with `WindowEngine.lift_skeleton`) or est_local [k,15,3]
         (already lifted); either rows [k,8] trajectory rows `time tx ty tz qx qy qz qw` (made cameras by `slam`'s functions, relative
         to the session's first frame, translations times `scale`) or cams [k,4,4] with times [k].  Host or device arrays.  Every window
         these frames complete is optimised at once; the call blocks until they are done, reads their statistics and raises the
@@ -208,9 +223,20 @@ class LiveOptimizer:
         e = self._engine()
         if self._flushed:
             raise _capi.GemError("this live session has been flushed: its held frames are out, a new stream needs a new session")
-        k, t, (heat, depth, est_local, rows, cams) = check_push(self._last_time, heat, depth, est_local, rows, cams, times, e.heat_size)
-        heat_d = self._device(heat, torch.float32)
-        pose_d = self._device(est_local, torch.float32) if est_local is not None else e.lift_skeleton(heat_d, depth, want_f64=False)[1]
+        k, t, (heat, depth, est_local, rows, cams) = check_push(self._last_time, heat, depth, est_local, rows, cams, times, e.heat_size, keypoints)
+        if keypoints is not None:
+            if depth is not None and self.n_pushed == 0:
+                from .detections import usable
+                kp0 = np.asarray(keypoints[0].detach().cpu().numpy() if torch.is_tensor(keypoints) else np.asarray(keypoints)[0], dtype=np.float64)
+                lost = np.nonzero(~(usable(kp0) if kp0.shape[1] == 3 else np.isfinite(kp0).all(axis=1)))[0]
+                if len(lost):
+                    raise ValueError("push: joints %s of the session's first frame have no usable detection: nothing to hold" % lost.tolist())
+            kp_d = e._keypoints("push", keypoints)
+            heat_d = e.keypoint_heatmaps(kp_d, self.sigma)
+            pose_d = self._device(est_local, torch.float32) if est_local is not None else e.lift_keypoints(kp_d, depth, prev=self._kp_prev, want_f64=False)[1]
+        else:
+            heat_d = self._device(heat, torch.float32)
+            pose_d = self._device(est_local, torch.float32) if est_local is not None else e.lift_skeleton(heat_d, depth, want_f64=False)[1]
         cams_d = self._device(self._cameras(rows) if rows is not None else cams, torch.float64)
         times_d = self._device(t, torch.float64)
         self._last_time = float(t[-1])
@@ -277,11 +303,13 @@ def step_summary(window_log):
 
 
 def replay(slam_result_path, heatmap_dir, depth_dir, start_frame, end_frame, camera_model_path, fps=25, pace="max", save_pose=None,
-           verbose=True, **session):
+           verbose=True, keypoints=None, first_id=0, **session):
     """A prepared recording pushed through a `LiveOptimizer` one frame at a time: the frames [start_frame, end_frame) of the listings
     come to the device with `prepare`'s reader, the trajectory's rows of those frame ids are the cameras.  pace "realtime" sleeps to
     the timestamps, "max" does not.  `session`: the keyword arguments of `LiveOptimizer`.  -> (result dict with "dropped", the
-    session's window_log).  A replay of a recording: a rig calls `push` itself."""
+    session's window_log).  A replay of a recording: a rig calls `push` itself.  `keypoints` (with `heatmap_dir` None): a detections
+    file (`detections.read_detections`; `first_id`: the frame id of its first row) pushed with `keypoints=` instead of heat-maps, the
+    depths from the file or from `depth_dir`."""
     from . import prepare, slam
     if pace not in ("max", "realtime"):
         raise ValueError('pace is "max" or "realtime"')
@@ -290,12 +318,24 @@ def replay(slam_result_path, heatmap_dir, depth_dir, start_frame, end_frame, cam
     prepare.check_trajectory(rows, start_frame, end_frame, fps)
     ids = slam.frame_ids(rows, fps)
     rows = rows[(ids >= start_frame) & (ids < end_frame)]
-    heat_paths, depth_paths = prepare.list_frames(heatmap_dir, start_frame, end_frame), prepare.list_frames(depth_dir, start_frame, end_frame)
-    if len(heat_paths) != end_frame - start_frame or len(depth_paths) != end_frame - start_frame:
-        raise ValueError("frames [%d, %d) of the listings are asked for, but there are %d heat-map and %d depth files"
-                         % (start_frame, end_frame, len(heat_paths), len(depth_paths)))
-    heat, depth, _ = prepare.frames_to_device(heat_paths, depth_paths)
-    live = LiveOptimizer(camera_model_path, heat_size=tuple(heat.shape[1:3]), **session)
+    if (keypoints is None) == (heatmap_dir is None):
+        raise ValueError("replay: give exactly one of the heat-map directory and keypoints=")
+    if keypoints is not None:
+        from . import detections
+        det = detections.read_detections(keypoints, first_id)
+        pick = detections.span_rows(det["frame_ids"], [(start_frame, end_frame)])[0]
+        if det["depth"] is None and depth_dir is None:
+            raise ValueError("replay: the joints' depths are needed: `depth` in the detections file, or the depth directory")
+        kp = det["keypoints"][pick]
+        depth = det["depth"][pick] if det["depth"] is not None else detections.depths_from_mat_dir(depth_dir, det["frame_ids"][pick])
+        heat, live = None, LiveOptimizer(camera_model_path, **session)
+    else:
+        heat_paths, depth_paths = prepare.list_frames(heatmap_dir, start_frame, end_frame), prepare.list_frames(depth_dir, start_frame, end_frame)
+        if len(heat_paths) != end_frame - start_frame or len(depth_paths) != end_frame - start_frame:
+            raise ValueError("frames [%d, %d) of the listings are asked for, but there are %d heat-map and %d depth files"
+                             % (start_frame, end_frame, len(heat_paths), len(depth_paths)))
+        heat, depth, _ = prepare.frames_to_device(heat_paths, depth_paths)
+        live = LiveOptimizer(camera_model_path, heat_size=tuple(heat.shape[1:3]), **session)
     try:
         wall0 = time.perf_counter()
         for i in range(len(rows)):
@@ -303,7 +343,10 @@ def replay(slam_result_path, heatmap_dir, depth_dir, start_frame, end_frame, cam
                 wait = (rows[i, 0] - rows[0, 0]) - (time.perf_counter() - wall0)
                 if wait > 0:
                     time.sleep(wait)
-            live.push(heat=heat[i:i + 1], depth=depth[i:i + 1], rows=rows[i:i + 1])
+            if heat is None:
+                live.push(keypoints=kp[i:i + 1], depth=depth[i:i + 1], rows=rows[i:i + 1])
+            else:
+                live.push(heat=heat[i:i + 1], depth=depth[i:i + 1], rows=rows[i:i + 1])
         tail = live.flush()
         res = dict(live.result(), dropped=tail["dropped"])
         if save_pose is not None:
@@ -338,8 +381,13 @@ def _parser():
     p = argparse.ArgumentParser(description="Replay a prepared recording through live mode, one frame at a time. This replays a "
                                             "recording; a head-mounted rig calls LiveOptimizer.push itself.")
     p.add_argument("--slam", required=True, metavar="TRAJ", help="the trajectory: lines `time tx ty tz qx qy qz qw`")
-    p.add_argument("--heatmaps", required=True, metavar="DIR")
-    p.add_argument("--depths", required=True, metavar="DIR")
+    src = p.add_mutually_exclusive_group(required=True)
+    src.add_argument("--heatmaps", default=None, metavar="DIR")
+    src.add_argument("--keypoints", default=None, metavar="FILE", help="2-D detections in place of heat-maps: .npy [N,15,2|3] or .npz with "
+                                                                       "keypoints[, depth, frame_ids]; u, v in pixels of the fisheye image")
+    p.add_argument("--depths", default=None, metavar="DIR", help="needed with --heatmaps, and with --keypoints unless the file carries `depth`")
+    p.add_argument("--first_id", type=int, default=0, help="frame id of the first row of --keypoints (without frame_ids)")
+    p.add_argument("--sigma", type=float, default=1.5, help="the width of the Gaussians splatted from --keypoints, in heat-map pixels")
     p.add_argument("--scale", type=float, default=1.0, help="the SLAM scale applied to the trajectory's translations")
     p.add_argument("--start", type=int, required=True, metavar="A")
     p.add_argument("--end", type=int, required=True, metavar="B")
@@ -361,11 +409,15 @@ def _parser():
 
 
 def _cli(argv=None):
-    a = _parser().parse_args(argv)
+    p = _parser()
+    a = p.parse_args(argv)
+    if a.heatmaps is not None and a.depths is None:
+        p.error("--heatmaps needs --depths")
     weights = dict(vae_weight=a.vae, smoothness_weight=a.smooth, bone_length_weight=a.bone_length, weight_3d=a.weight_3d,
                    reproj_weight=a.reproj_weight)
     replay(a.slam, a.heatmaps, a.depths, a.start, a.end, a.camera, fps=a.fps, pace=a.pace, save_pose=a.save_pose, global_vae=a.global_vae,
-           local_vae=a.local_vae, scale=a.scale, weights=weights, bone=a.bone, one_euro=a.one_euro, seed=a.seed)
+           local_vae=a.local_vae, scale=a.scale, weights=weights, bone=a.bone, one_euro=a.one_euro, seed=a.seed, keypoints=a.keypoints,
+           first_id=a.first_id, sigma=a.sigma)
 
 
 if __name__ == "__main__":

@@ -730,6 +730,35 @@ int64_t gem_jpeg_bound(int width, int height);
 int gem_jpeg_encode(gem_handle* h, const void* d_scan, int n_images, int width, int height, int64_t in_stride, int quality, int avi_chunks,
                     void* d_out, int64_t out_capacity, int64_t* d_offsets, int16_t* d_coef, void* stream);
 
+/* ---- Recordings given as 2-D joint detections ----
+ * A detection is (u, v, confidence): u, v in pixels of the fisheye image (the 1280 x 1024 image the calibration describes).  It is
+ * USABLE when confidence > 0 (NaN is not) and u and v are finite.
+ *
+ * gem_keypoint_heatmaps: d_kp [n_frames,n_joints,3] f64 -> d_heat [n_frames,heat_h,heat_w,n_joints] f32, the layout every consumer
+ * takes.  Joint j of frame f becomes a * exp(-((x - ix)^2 + (y - iy)^2) / (2 sigma^2)) with a = min(max(confidence, 0), 1) and
+ * (ix, iy) = ((u - 128) (heat_w - 1) / 1024, v (heat_h - 1) / 1024): the heat-map coordinate at which the reprojection term samples
+ * image point (u, v) (optimizer.py:143-147), so that the energy's maximum sits on the detection.  An unusable joint gets an all-zero
+ * map.  The value is the float64 expression rounded to float32.  2 <= n_joints <= 16, heat_w >= 2, n_joints (heat_h + heat_w) <= 8192;
+ * d_heat needs no more than a float's alignment (16-byte stores wherever the frame's run allows).  Works on the current device. */
+int gem_keypoint_heatmaps(const double* d_kp, int64_t n_frames, int n_joints, int heat_h, int heat_w, double sigma, float* d_heat,
+                          void* stream);
+
+/* FishEyeCameraCalibrated.camera2world (utils/fisheye/FishEyeCalibrated.py:18-33) at the detection itself, in float64, with the
+ * handle's image centre and h_poly_c2w (polynomialC2W, ascending powers): the un-projection of gem_lift_skeleton without its argmax
+ * and its 16-pixel grid -- for the same image point the same bits.  d_kp [n_frames,J,3] f64, d_depth [n_frames,J] f64; outputs (each
+ * may be NULL, not all) d_out64 / d_out32 [n_frames,J,3] and d_valid [n_frames,J] u8: 1 where the detection was usable.
+ * d_prev NULL: frames are independent, an unusable joint is written as zeros (gem_fill_missing replaces it).
+ * d_prev [J,3] f64: the frames are taken in order; an unusable joint takes d_prev's value, every usable one updates it, and d_prev
+ * holds the last values afterwards -- the causal "hold the last one" of a stream, carried from call to call. */
+int gem_lift_keypoints(gem_handle* h, const double* d_kp, const double* d_depth, int64_t n_frames, const double* h_poly_c2w, int n_poly,
+                       double* d_prev, double* d_out64, float* d_out32, unsigned char* d_valid, void* stream);
+
+/* In place on d_seq [n_chunks * frames_per_chunk, n_joints, 3] f64 with d_valid [n_chunks * frames_per_chunk, n_joints] u8: per chunk
+ * and joint, a frame with valid = 0 between valid frames lo < f < hi becomes seq[lo] + (seq[hi] - seq[lo]) (f - lo) / (hi - lo); in
+ * front of the chunk's first valid frame it takes that frame's value, behind the last valid frame that one's.  A joint with no valid
+ * frame in a chunk is left untouched (the caller refuses such a recording).  Works on the current device. */
+int gem_fill_missing(double* d_seq, const unsigned char* d_valid, int n_chunks, int frames_per_chunk, int n_joints, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
