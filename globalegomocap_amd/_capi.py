@@ -80,6 +80,15 @@ MAT_HEAT_F64, MAT_DEPTH_F32 = 1, 2
 MI_SINGLE, MI_DOUBLE = 7, 9
 
 
+class GemScaleReport(C.Structure):
+    _fields_ = [(k, C.c_double) for k in ("scale", "s0", "s_ref", "g0", "pairs", "inliers", "informative", "residual_rms", "path_length",
+                                          "stance_right", "stance_left", "status", "lag", "tau", "min_pairs", "n_chunks")]
+
+
+SCALE_CANDIDATES, SCALE_TILE, SCALE_REPORT_DOUBLES = 513, 256, 16
+SCALE_NO_PAIRS, SCALE_TOO_FEW, SCALE_BAD_SCALE = 2, 3, 4
+
+
 class GemWindowStats(C.Structure):
     _fields_ = [("n_iter", C.c_int32), ("func_evals", C.c_int32), ("final_loss", C.c_float), ("status", C.c_int32)]
 
@@ -176,6 +185,9 @@ SIGNATURES = {
     "gem_keypoint_heatmaps": (C.c_int, [_P, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_double, _P, _P]),
     "gem_lift_keypoints": (C.c_int, [_P, _P, _P, C.c_int64, C.POINTER(C.c_double), C.c_int, _P, _P, _P, _P, _P]),
     "gem_fill_missing": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P]),
+    "gem_slam_scale_work": (C.c_int64, [C.c_int64, C.c_int, C.c_int]),
+    "gem_slam_scale": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(C.c_int), _P, _P, _P, C.c_int64, C.c_int, C.c_double, C.c_int, _P,
+                                 C.c_int64, _P, _P, _P, _P]),
 }
 
 _lib = None

@@ -11,7 +11,7 @@ u, v are pixels of the fisheye image the calibration describes (1280 x 1024).  A
 and u, v are finite; a joint that is unusable in a frame gets a blank heat-map there and the pose interpolated in time from its
 usable neighbours inside the chunk.  A joint with no usable detection in a whole chunk is a ValueError.
 
-    python -m globalegomocap_amd.detections --slam traj.txt --keypoints det.npz --scale 1.0 --start 0 --end 2001 --fps 25 \\
+    python -m globalegomocap_amd.detections --slam traj.txt --keypoints det.npz --scale 1.0|auto --start 0 --end 2001 --fps 25 \\
         [--depths DIR | --depth FILE.npy] [--sigma 1.5] [--first_id 0] [--test_size 100] [--out DIR] [--optimize] [--camera JSON]
 """
 import os
@@ -120,12 +120,13 @@ def depths_from_mat_dir(directory, frame_ids):
 
 # ------------------------------------------------------------------------------------------------------------------ the device path
 def recording_from_detections(slam_result_path, detections, gt_path=None, scale=None, spans=(), fps=25, depth=None, sigma=1.5, first_id=0,
-                              camera_model_path=None, device=None, gt_start_frame=None):
+                              camera_model_path=None, device=None, gt_start_frame=None, lag=None, tau=0.10, min_pairs=50):
     """Every (start_frame, end_frame) of `spans` as one chunk of a `prepare.Recording`, from 2-D detections: `detections` is a file
     (`read_detections`), an array [N,15,2|3] or `as_detections`' dict; `depth` [N,15] unless the file carries it.  Exactly one of
     `gt_path` (the ground truth fixes the SLAM scale per chunk, as `prepare` does; entry i - gt_start_frame of the pickle is frame id
-    i, gt_start_frame defaulting to the first span's start) and `scale`.  One upload, then on the device: lift -> fill -> heat-maps
-    -> cameras -> gem_prepare_global."""
+    i, gt_start_frame defaulting to the first span's start) and `scale`: a number, or "auto" to estimate it from the foot contacts of
+    the filled poses (`prepare.auto_scale` with `lag`, `tau`, `min_pairs`).  One upload, then on the device:
+    lift -> fill -> heat-maps -> cameras -> gem_prepare_global."""
     from . import prepare, slam
     scale = prepare.gt_or_scale(gt_path, scale)
     import torch
@@ -171,13 +172,16 @@ def recording_from_detections(slam_result_path, detections, gt_path=None, scale=
         else:
             for lo, hi in bounds:
                 engine.fill_missing(est_local[lo:hi], valid[lo:hi], 1)
+        if scale is not None:          # (a recording that does not fix the scale is refused before the heat-maps are made)
+            scale_given = scale
+            scale, scale_report = prepare.auto_scale(est_local, text, spans, fps, scale, lag, tau, min_pairs)
         heat = engine.keypoint_heatmaps(kp_d, sigma)
         if scale is not None:
             cams, origins = prepare.scaled_cameras(text, spans, fps, scale)
             cams_d = torch.from_numpy(np.concatenate(cams)).to(device)
             est_global, _ = prepare.prepare_global(est_local, cams_d, None)
             return prepare.Recording([prepare.RecordingChunk(a, b, heat[lo:hi], est_local[lo:hi], est_global[lo:hi], cams_d[lo:hi], None)
-                                      for (a, b), (lo, hi) in zip(spans, bounds)], origins)
+                                      for (a, b), (lo, hi) in zip(spans, bounds)], origins, scale if scale_given == "auto" else None, scale_report)
         heads = est_local[:, 0].cpu().numpy()
         gt_all = np.concatenate([np.asarray(g, dtype=np.float64) for g in gts])
         cams = np.concatenate([slam.camera_pose_list_from_heads(text, heads[lo:hi], gt_all[lo:hi, 0], a, b, fps)[0]
@@ -193,13 +197,15 @@ def recording_from_detections(slam_result_path, detections, gt_path=None, scale=
 def _parser():
     import argparse
     from .camera import DEFAULT_CALIBRATION
+    from .slam_scale import scale_arg
     p = argparse.ArgumentParser(description="recording (2-D joint detections) -> chunks for the optimiser")
     p.add_argument("--slam", required=True, help="SLAM trajectory: lines `time tx ty tz qx qy qz qw`")
     p.add_argument("--keypoints", required=True, metavar="FILE", help=".npy [N,15,2|3] or .npz with keypoints[, depth, frame_ids]: u, v in "
                                                                        "pixels of the fisheye image[, confidence]")
     how = p.add_mutually_exclusive_group(required=True)
     how.add_argument("--gt", default=None, help="ground-truth pickle (it fixes the SLAM scale)")
-    how.add_argument("--scale", type=float, default=None, help="the SLAM scale of a recording without ground truth (a metric SLAM: 1)")
+    how.add_argument("--scale", type=scale_arg, default=None, help="the SLAM scale of a recording without ground truth (a metric SLAM: 1), "
+                                                                  "or `auto`: estimate it from the foot contacts")
     dep = p.add_mutually_exclusive_group()
     dep.add_argument("--depths", default=None, metavar="DIR", help="directory of per-frame depth .mat files")
     dep.add_argument("--depth", default=None, metavar="FILE.npy", help="the joints' depths [N,15], row for row with the detections")
@@ -229,6 +235,8 @@ def _cli(argv=None):
         det["depth"] = depths_from_mat_dir(a.depths, det["frame_ids"])
     rec = recording_from_detections(a.slam, det, a.gt, a.scale, prepare.chunk_spans(a.start, a.end, a.test_size), a.fps, sigma=a.sigma,
                                     camera_model_path=a.camera, gt_start_frame=a.mat_start)
+    if rec.scale_report is not None:
+        print(rec.scale_report.line())
     for c in rec.chunks:
         print("running test sequence from {} to {}".format(c.start_frame, c.end_frame))
         if c.initial_mpjpe is not None:

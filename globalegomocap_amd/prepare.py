@@ -28,8 +28,9 @@ listing with fewer files than the range asks for.
     python -m globalegomocap_amd.prepare --slam traj.txt --heatmaps DIR --depths DIR --gt gt.pkl --start 551 --end 3300 \\
         --fps 25 --out DIR [--optimize]
 
-A recording without ground truth gives the SLAM scale instead -- 1 for a metric SLAM, else what the user
-calibrated: `--scale S` in place of `--gt`, `scale=` in place of `gt_path=`.  The cameras of a chunk are then the reference's
+A recording without ground truth gives the SLAM scale instead -- 1 for a metric SLAM, a number the user
+knows, or `auto` for a monocular SLAM, whose scale is then estimated from the recording's own foot contacts before the cameras are
+made (`slam_scale`): `--scale S|auto` in place of `--gt`, `scale=` in place of `gt_path=`.  The cameras of a chunk are then the reference's
 `SLAMReader.read_trajectory(path, start, end, scale)` (`slam.scaled_trajectory`), the chunks carry no ground truth, their pickles
 no `gt_global_skeleton`, and since one scale holds for the whole recording its chunks share a world: `Recording.origins`,
 `to_recording_frame`.
@@ -98,12 +99,15 @@ def check_trajectory(text, start_frame, end_frame, fps):
 
 
 def gt_or_scale(gt_path, scale):
-    """Exactly one of the ground-truth pickle and the SLAM scale must be given: ValueError otherwise.  -> the scale as a float, or
+    """Exactly one of the ground-truth pickle and the SLAM scale must be given: ValueError otherwise.  -> the scale as a float, the
+    word "auto" as it is (the scale is then estimated from the recording's foot contacts: `slam_scale`), or
     None on the ground-truth route."""
     if (gt_path is None) == (scale is None):
         raise ValueError("give exactly one of gt_path (the ground truth fixes the SLAM scale) and scale (a recording without ground truth)")
     if scale is None:
         return None
+    if isinstance(scale, str) and scale == "auto":
+        return "auto"
     scale = float(scale)
     if not (np.isfinite(scale) and scale > 0):
         raise ValueError("the SLAM scale must be a positive number, got %r" % scale)
@@ -218,11 +222,13 @@ class RecordingChunk:
 class Recording:
     """The chunks of one recording, device-resident.  `heat`, `est_local`, `est_global`, `cams`, `gt`: one tensor per chunk.
     `origins` [n_chunks,4,4] float64 (numpy) for a recording without ground truth, whose chunks share a world (`scaled_cameras`,
-    `to_recording_frame`); None for a recording with ground truth."""
+    `to_recording_frame`); None for a recording with ground truth.  `scale` and `scale_report` (`slam_scale.ScaleEstimate`): the SLAM
+    scale a recording prepared with scale="auto" was given and how it was found; None on the other routes."""
 
-    def __init__(self, chunks, origins=None):
+    def __init__(self, chunks, origins=None, scale=None, scale_report=None):
         self.chunks = list(chunks)
         self.origins = origins
+        self.scale, self.scale_report = scale, scale_report
 
     def __len__(self):
         return len(self.chunks)
@@ -511,12 +517,23 @@ def prepare_global(est_local, cams, gt):
     return out, err
 
 
+def auto_scale(est_local, rows, spans, fps, scale, lag=None, tau=0.10, min_pairs=50):
+    """`scale` as a number -> (scale, None).  "auto" -> (the estimate, its `slam_scale.ScaleEstimate`): `gem_slam_scale` on the lifted
+    poses where they lie, one small record back; ValueError when the recording does not fix the scale."""
+    if not (isinstance(scale, str) and scale == "auto"):
+        return scale, None
+    from .slam_scale import estimate_scale
+    report = estimate_scale(est_local, rows, spans, fps, lag=lag, tau=tau, min_pairs=min_pairs)
+    return float(report.scale), report
+
+
 def prepare_spans(slam_result_path, heatmap_dir, depth_dir, gt_path, spans, fps, mat_start_frame, camera_model_path=None, device=None,
-                  timings=None, scale=None):
+                  timings=None, scale=None, lag=None, tau=0.10, min_pairs=50):
     """Every (start_frame, end_frame) of `spans` as one chunk, each prepared on its own as `main` does, all of them through the
     device together: stage -> gem_mat_frames -> lift -> head joints to the host -> per-chunk scale and cameras -> cameras up ->
     gem_prepare_global.  -> Recording.  `gt_path` None and `scale` given: a recording without ground truth -- the cameras come from
-    `scaled_cameras`, nothing goes to the host in between, `mat_start_frame` is not used."""
+    `scaled_cameras`, nothing goes to the host in between, `mat_start_frame` is not used.  scale="auto": the scale is estimated from the
+    lifted poses first (`auto_scale` with `lag`, `tau`, `min_pairs`; one small record comes back), then the same path runs with it."""
     scale = gt_or_scale(gt_path, scale)
     import torch
     from . import slam
@@ -550,6 +567,10 @@ def prepare_spans(slam_result_path, heatmap_dir, depth_dir, gt_path, spans, fps,
             raise ValueError("heat-maps of %d x %d: the lifting kernel is built for %d x %d" % (tuple(heat.shape[1:3]) + tuple(engine.heat_size)))
         est_local, _ = engine.lift_skeleton(heat, depth)
         if scale is not None:
+            scale_given = scale
+            scale, scale_report = auto_scale(est_local, text, spans, fps, scale, lag, tau, min_pairs)
+            if scale_report is not None:
+                lap("lift + SLAM scale estimate (gem_slam_scale, report back)")
             cams, origins = scaled_cameras(text, spans, fps, scale)
             lap("lift enqueued + cameras at the given scale (host)")
             cams_d = torch.from_numpy(np.concatenate(cams)).to(device)
@@ -557,7 +578,7 @@ def prepare_spans(slam_result_path, heatmap_dir, depth_dir, gt_path, spans, fps,
             lap("cameras up + gem_prepare_global")
             return Recording([RecordingChunk(a, b, heat[lo:hi], est_local[lo:hi], est_global[lo:hi], cams_d[lo:hi], None,
                                              heat_files=heat_files[lo:hi] if any(k is not None for k in heat_files[lo:hi]) else None)
-                              for (a, b), (lo, hi) in zip(spans, bounds)], origins)
+                              for (a, b), (lo, hi) in zip(spans, bounds)], origins, scale if scale_given == "auto" else None, scale_report)
         heads = est_local[:, 0].cpu().numpy()
         lap("lift + head joints to the host")
         gt_all = np.concatenate([np.asarray(g, dtype=np.float64) for g in gts])
@@ -578,13 +599,17 @@ def prepare_spans(slam_result_path, heatmap_dir, depth_dir, gt_path, spans, fps,
 
 
 def main(slam_result_path, heatmap_dir, depth_dir, gt_path, start_frame, end_frame, out_dir, fps, mat_start_frame=None,
-         camera_model_path=None, scale=None):
+         camera_model_path=None, scale=None, lag=None, tau=0.10, min_pairs=50):
     """The reference's `main` (:126-165): one chunk [start_frame, end_frame) -> `<out_dir>/test_data.pkl`, and the line
     `The initial mpjpe is: ...`.  Returns the one-chunk Recording (the reference returns nothing).  Without ground truth (`gt_path`
-    None, `scale` given) the pickle has four keys and there is no such line."""
+    None, `scale` given) the pickle has four keys and there is no such line; with scale="auto" one line tells the estimate and its
+    counts, and a recording that does not fix the scale is a ValueError before anything is written."""
     gt_or_scale(gt_path, scale)
     rec = prepare_spans(slam_result_path, heatmap_dir, depth_dir, gt_path, [(start_frame, end_frame)], fps,
-                        start_frame if mat_start_frame is None else mat_start_frame, camera_model_path, scale=scale)
+                        start_frame if mat_start_frame is None else mat_start_frame, camera_model_path, scale=scale, lag=lag, tau=tau,
+                        min_pairs=min_pairs)
+    if rec.scale_report is not None:
+        print(rec.scale_report.line())
     rec.write_chunk(0, out_dir)
     if scale is None:
         print("The initial mpjpe is: {}".format(rec.chunks[0].initial_mpjpe))
@@ -592,16 +617,19 @@ def main(slam_result_path, heatmap_dir, depth_dir, gt_path, start_frame, end_fra
 
 
 def prepare_sequence(slam_result_path, heatmap_dir, depth_dir, gt_path, total_start_frame, total_end_frame, fps=25, mat_start_frame=None,
-                     test_size=100, out_root=None, camera_model_path=None, verbose=True, scale=None):
+                     test_size=100, out_root=None, camera_model_path=None, verbose=True, scale=None, lag=None, tau=0.10, min_pairs=50):
     """The reference's chunk loop (:176-190): chunks of `test_size` frames from `total_start_frame` (see `chunk_spans` for the
     chunk it drops), `mat_start_frame` defaulting to `total_start_frame` as there.  All chunks go through the device together,
     each prepared on its own.  Returns the Recording; with `out_root`, `data_start_{a}_end_{b}/test_data.pkl` are written too.
     Exactly one of `gt_path` and `scale` is given (else ValueError, before anything else happens): with `scale` the recording has no
-    ground truth (`prepare_spans`)."""
+    ground truth (`prepare_spans`); scale="auto" estimates it from the foot contacts (`lag`, `tau`, `min_pairs`: `slam_scale`)."""
     gt_or_scale(gt_path, scale)
     spans = chunk_spans(total_start_frame, total_end_frame, test_size)
     rec = prepare_spans(slam_result_path, heatmap_dir, depth_dir, gt_path, spans, fps,
-                        total_start_frame if mat_start_frame is None else mat_start_frame, camera_model_path, scale=scale)
+                        total_start_frame if mat_start_frame is None else mat_start_frame, camera_model_path, scale=scale, lag=lag, tau=tau,
+                        min_pairs=min_pairs)
+    if verbose and rec.scale_report is not None:
+        print(rec.scale_report.line())
     for c in rec.chunks:
         if verbose:
             print("running test sequence from {} to {}".format(c.start_frame, c.end_frame))
@@ -615,13 +643,15 @@ def prepare_sequence(slam_result_path, heatmap_dir, depth_dir, gt_path, total_st
 def _parser():
     import argparse
     from .camera import DEFAULT_CALIBRATION
+    from .slam_scale import scale_arg
     p = argparse.ArgumentParser(description="recording (.mat files of the pose network) -> chunks for the optimiser")
     p.add_argument("--slam", required=True, help="SLAM trajectory: lines `time tx ty tz qx qy qz qw`")
     p.add_argument("--heatmaps", required=True, help="directory of per-frame heatmap .mat files")
     p.add_argument("--depths", required=True, help="directory of per-frame depth .mat files")
     how = p.add_mutually_exclusive_group(required=True)
     how.add_argument("--gt", default=None, help="ground-truth pickle (it fixes the SLAM scale)")
-    how.add_argument("--scale", type=float, default=None, help="the SLAM scale of a recording without ground truth (a metric SLAM: 1)")
+    how.add_argument("--scale", type=scale_arg, default=None, help="the SLAM scale of a recording without ground truth (a metric SLAM: 1), "
+                                                                  "or `auto`: estimate it from the foot contacts")
     p.add_argument("--start", required=True, type=int)
     p.add_argument("--end", required=True, type=int)
     p.add_argument("--fps", type=float, default=25)

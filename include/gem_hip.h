@@ -759,6 +759,50 @@ int gem_lift_keypoints(gem_handle* h, const double* d_kp, const double* d_depth,
  * frame in a chunk is left untouched (the caller refuses such a recording).  Works on the current device. */
 int gem_fill_missing(double* d_seq, const unsigned char* d_valid, int n_chunks, int frames_per_chunk, int n_joints, void* stream);
 
+/* ---- The SLAM scale of a recording without ground truth, from foot contacts: `--scale auto` ----
+ * A monocular SLAM gives the camera's rotation R_t and its translation c_t up to one factor s; the lifted poses x_t are metric.  A
+ * foot that stands does not move in the world, so R_t x_t,foot + s c_t is constant over a stance phase.  With q[t,side] =
+ * R_t (x[t,ankle] + x[t,foot]) / 2, a[p,side] = q[t+lag,side] - q[t,side] and b[p] = c[t+lag] - c[t] for every t with
+ * ids[t+lag] - ids[t] = lag: s_ref = sqrt(sum |a|^2 / (2 sum |b|^2)); the cost C(s) = sum_p min(min_side |a + s b|^2, tau^2) at the
+ * 513 candidates s_ref 2^(g/32), g = -256 .. 256; s0 the candidate of the smallest cost (the smallest g of equal ones); four rounds
+ * of: every pair takes the side of the smaller residual (a tie: the right foot), is an inlier when that residual is < tau^2, and
+ * s <- -sum_inl <a,b> / sum_inl <b,b>.  Everything is float64 without fused multiply-adds and every sum has a fixed order: two calls
+ * give the same bits.
+ *
+ * The report: a gem_scale_report and behind it [n_chunks][3] doubles -- numerator, denominator and scale of the inlier pairs whose
+ * first frame lies in the chunk.  `informative`: inliers with s |b| > tau (the camera moved further than a swinging foot is allowed
+ * to); stance_right / stance_left: the inliers' shares of the two sides.  status is 0 or why no scale can be given. */
+#define GEM_SCALE_CANDIDATES 513
+#define GEM_SCALE_TILE 256          /* pairs per workgroup of the cost kernel */
+#define GEM_SCALE_REPORT_DOUBLES 16
+#define GEM_SCALE_NO_PAIRS 2        /* no two frames lag apart, or the camera never moved (sum |b|^2 = 0) */
+#define GEM_SCALE_TOO_FEW 3         /* fewer than min_pairs informative pairs: the wearer did not walk enough */
+#define GEM_SCALE_BAD_SCALE 4       /* the fitted scale is not a finite positive number */
+typedef struct gem_scale_report {
+    double scale, s0, s_ref, g0;                    /* g0: index 0 .. 512 of s0 among the candidates */
+    double pairs, inliers, informative;             /* counts */
+    double residual_rms, path_length;               /* metres: RMS of the inliers' residuals; scale * sum |b| / lag */
+    double stance_right, stance_left;
+    double status;                                  /* 0, GEM_SCALE_NO_PAIRS, GEM_SCALE_TOO_FEW or GEM_SCALE_BAD_SCALE */
+    double lag, tau, min_pairs, n_chunks;           /* the call's parameters */
+} gem_scale_report;
+
+/* Bytes of d_work a call with these sizes needs; -1 with the reason in gem_last_error for sizes out of range.  Needs no GPU. */
+int64_t gem_slam_scale_work(int64_t n_frames, int lag, int n_chunks);
+
+/* h_chunks (host) and d_chunks (the same numbers on the device): [n_chunks] device addresses of the chunks' poses, each its own
+ * [n,n_joints,3] f64 allocation, then [n_chunks + 1] first rows, rising from 0 to n_frames (a chunk may be empty; the chunks are
+ * also the partition of the per-chunk sums).  h_feet [4]: right ankle, right foot, left ankle, left foot.  d_rot [n_frames,3,3],
+ * d_trans [n_frames,3]: the unscaled SLAM poses relative to the first frame; d_ids [n_frames] int64 frame ids.  d_work: scratch;
+ * d_report [16 + 3 n_chunks]; d_costs [513] or NULL: the candidates' costs.  Arguments are checked before any launch; n_frames <= lag
+ * returns GEM_SCALE_NO_PAIRS and launches nothing.  h_report NULL: everything is enqueued on `stream`, the return value says only
+ * whether that worked and the verdict is the report's status.  h_report [16 + 3 n_chunks] (host): the report is copied there, the
+ * stream is waited for, and a status other than 0 is the return value, its text with the counts in gem_last_error.  Inputs must be
+ * finite.  Works on the current device. */
+int gem_slam_scale(const int64_t* h_chunks, const int64_t* d_chunks, int n_chunks, int n_joints, const int* h_feet, const double* d_rot,
+                   const double* d_trans, const int64_t* d_ids, int64_t n_frames, int lag, double tau, int min_pairs, void* d_work,
+                   int64_t work_bytes, double* d_report, double* d_costs, double* h_report, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
