@@ -425,6 +425,7 @@ struct TailLayerDev { const float* w4; const float* bias; int K, N; };
 struct TailArgs {
     int n, B, G, forward_only, escr, mask_first;
     int waves, rows;         // kernel shape (8 wavefronts, one workgroup per CU | 4, three per CU) and rows per LDS buffer (16 | G*T): plan_tail
+    int maxnt;               // 16-column tiles per wave the kernel is compiled for (2: no layer wider than 256 | 4): plan_tail
     SlabSrc in_slab;         // a_in still lies in split-K slabs (+ in_bias, LeakyReLU to apply) when in_slab.base != nullptr
     const float* in_bias;    // bias of row r, column c: in_bias[(r % T) * in_bias_ld + c]
     int in_bias_ld;          // 0: one bias per channel (a conv produced a_in); K0: per (frame, channel) (the composed front layer)

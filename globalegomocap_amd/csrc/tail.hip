@@ -14,7 +14,7 @@
 //
 // A operands come from LDS (rows are (window, frame); the k=3 conv reads rows t-1, t, t+1 of the same
 // window; rows outside it read a zero line).  B operands (weights) are read straight from L2 into registers, one
-// k-block ahead; the tail weights are stored [tap][K/4][N][4] so that 16 lanes read 256 contiguous bytes.  Every
+// k-block ahead inside a layer, the first block of the NEXT layer a layer ahead (TailSched below); the tail weights are stored [tap][K/4][N][4] so that 16 lanes read 256 contiguous bytes.  Every
 // workgroup streams the same weights (1.3 MB per launch): with 30 workgroups per XCD the two 256<->128 layers run
 // at about half the MFMA rate, bound by L2 -> CU bandwidth; the 64-wide layers are latency chains of ~2 us.
 // Output tiles are 16x16 (v_mfma_f32_16x16x4_f32), wave w owns columns 16w..16w+15 (+128 per extra tile) with the
@@ -40,10 +40,11 @@ __device__ __forceinline__ float bf16_round(float x) {
 // 8 waves per workgroup = 2 per SIMD: the per-block latency chain (L2 weight fragment -> LDS fragment -> 16 MFMAs)
 // of one wave overlaps the other's, and K is cut twice as fine (each wave walks half as many blocks).  That is the shape for
 // batches of at most one workgroup per CU (the 240-window workload): the window's chain is as short as it gets.
-// With MORE workgroups than CUs the 8-wave kernel (243 VGPRs, 2 waves per SIMD, 70 KB of LDS) runs them one after the other on a
+// With MORE workgroups than CUs the 8-wave kernel (148 VGPRs when no layer is wider than 256 columns, 204-225 otherwise; 2 waves per
+// SIMD by its launch bounds, 70 KB of LDS) runs them one after the other on a
 // CU, each paying its staging / barrier / energy latencies with the MFMA pipes idle.  The 4-wave shape (W = 4: one wave per SIMD,
 // each wave owns twice the columns, so one LDS A fragment feeds twice the MFMAs; LDS buffers of the window's T rows instead of 16:
-// 48 KB; 167 VGPRs) lets THREE workgroups share a CU: one window's latencies hide behind the others' matrix work.  Same K walk
+// 48 KB; 141-161 VGPRs of the 168 allowed) lets THREE workgroups share a CU: one window's latencies hide behind the others' matrix work.  Same K walk
 // per output element, so the layers' results are bitwise those of the 8-wave shape; the energies' fp64 partial sums are
 // combined over 4 instead of 8 wavefronts (last-bit differences in f only).
 constexpr int TAIL_WAVES = 8;
@@ -57,30 +58,93 @@ constexpr int TAIL_WAVES_SHARED = 4;       // the three-workgroups-per-CU shape
 // the k-pairing is a permutation inside the group, which a sum over k does not care about.
 constexpr int TAIL_ROWS = 16;          // rows of (window, frame) per workgroup = one MFMA tile
 
-// B fragments of the first block of the first tile a wave owns in layer L: issued before the barrier that ends
-// the previous layer, so that their L2 latency overlaps the epilogue / barrier / energy phase.
-template <int W>
-__device__ __forceinline__ void tail_prefetch_first(const TailLayerDev L, f32x4 (&dst)[4]) {
+// How far ahead of the MFMAs a wave requests its weight fragments (compile time):
+//   P = (tap, k-block) pairs of the NEXT layer a wave requests for every tile it owns there, so that their L2 latency overlaps the
+//       epilogue / barrier / energy phase.  With P = 3 a one-tile layer of K = 64 (three blocks) finds ALL its weights in registers and
+//       issues no weight load of its own; a longer layer, and the further tiles of a wave, take min(P, D - 1) blocks from the
+//       prefetch (what the ring has room for ahead of the first block).
+//   D = depth of the B-fragment register ring inside a layer: block blk + D - 1 is requested when block blk starts.
+//   EARLY = the next layer's prefetch is issued BEFORE this layer's K walk (a whole layer of lead) instead of behind it.
+// Compiled for at most two tiles per wave (MAXNT <= 2: no layer wider than 256 columns, the shipped tail) the 8-wave kernel needs about
+// 150 VGPRs of its 256 at P = 1, D = 2, so these are free choices there; measured (profiles/tail_prefetch.txt, 240 workgroups):
+// with the weights warm in L2 neither P = 3 nor D = 3, 4 shortens a layer -- the 64-wide layers (1.8 us each) do not wait for their
+// second and third block, they wait for the first one -- and P = 3 with EARLY or D >= 3 spills.  What pays is EARLY at P = 1, D = 2
+// (launch 42.1 -> 40.5 us): that is the setting.  The 4-tile instantiation (layers of 512 columns: 128 VGPRs of B fragments at D = 2
+// alone) and the 4-wave shape (168 VGPRs for three workgroups per CU) keep P = 1, D = 2, first tile only, issued behind the K walk.
+#ifndef TAIL_PREFETCH_BLOCKS
+#define TAIL_PREFETCH_BLOCKS 1
+#endif
+#ifndef TAIL_RING_DEPTH
+#define TAIL_RING_DEPTH 2
+#endif
+#ifndef TAIL_PREFETCH_EARLY
+#define TAIL_PREFETCH_EARLY 1
+#endif
+template <int W, int MAXNT>
+struct TailSched {
+    static constexpr bool DEEP = W == TAIL_WAVES && MAXNT <= 2;
+    static constexpr int P = DEEP ? TAIL_PREFETCH_BLOCKS : 1;
+    static constexpr int D = DEEP ? TAIL_RING_DEPTH : 2;
+    static constexpr int NTP = DEEP ? MAXNT : 1;             // tiles per wave the prefetch covers
+    static constexpr int PW = P < D - 1 ? P : D - 1;         // prefetched blocks of a layer longer than P (the ring has D - 1 slots ahead)
+    static constexpr bool EARLY = DEEP && TAIL_PREFETCH_EARLY;   // the next layer's prefetch goes out BEFORE this layer's K walk, not behind it
+    static_assert(P >= 1 && D >= 2 && D <= 4, "ring of two to four register sets");
+};
+// what a layer finds fetched by its predecessor: B fragments [block][16-deep group] of the wave's first tile, [tile - 1][block][group]
+// of its further tiles, and the bias values of its columns
+template <int W, int MAXNT>
+struct TailPre {
+    f32x4 b[TailSched<W, MAXNT>::P][4];
+    f32x4 bx[TailSched<W, MAXNT>::NTP > 1 ? TailSched<W, MAXNT>::NTP - 1 : 1][TailSched<W, MAXNT>::PW][4];
+    float bias[TailSched<W, MAXNT>::NTP];
+};
+
+// Issued by the previous layer (TailSched::EARLY: before its K walk, else before its closing barrier).  Nothing is requested past the
+// layer's weights: the blocks, and the tiles the wave does not own in L, are skipped by wave-uniform branches.
+template <int W, int MAXNT>
+__device__ __forceinline__ void tail_prefetch(const TailLayerDev L, TailPre<W, MAXNT>& dst) {
+    using S = TailSched<W, MAXNT>;
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int c = lane & 15, q = lane >> 4;
     const int n0 = wave * 16;
     if (n0 >= L.N) return;                                                                   // this wave idles in layer L
-    const f32x4* p = reinterpret_cast<const f32x4*>(L.w4) + (size_t)q * L.N + n0 + c;       // tap 0, k0 = 0
+    const int nblk = 3 * (L.K / 64);
+    const int nb = nblk <= S::P ? nblk : S::PW;
+    // (wave-uniform base + one 32-bit lane offset: every request of the wave is addressed from a single VGPR)
+    const char* p = reinterpret_cast<const char*>(reinterpret_cast<const f32x4*>(L.w4) + n0);   // tap 0, k0 = 0
+    const unsigned vo = (unsigned)(q * L.N + c) * 16u;
 #pragma unroll
-    for (int g = 0; g < 4; ++g) dst[g] = p[(size_t)(4 * g) * L.N];
+    for (int i = 0; i < S::NTP; ++i) {
+        if (n0 + 16 * W * i < L.N) {
+#pragma unroll
+            for (int s = 0; s < (i == 0 ? S::P : S::PW); ++s) {
+                if (s < nb) {
+#pragma unroll
+                    for (int g = 0; g < 4; ++g) {
+                        const f32x4 v = *reinterpret_cast<const f32x4*>(p + (((size_t)16 * s + 4 * g) * L.N + 16 * W * i) * 16 + vo);
+                        if (i == 0) dst.b[s][g] = v;
+                        else dst.bx[i > 0 ? i - 1 : 0][s][g] = v;
+                    }
+                }
+            }
+            if constexpr (S::DEEP) dst.bias[i] = L.bias ? L.bias[n0 + 16 * W * i + c] : 0.f;
+        }
+    }
 }
 
-// bpre: in = fragments from tail_prefetch_first(L); out = the same for `next` (if any), issued before the epilogue.
+// pre: in = what tail_prefetch(L) fetched; out = the same for `next` (if any).
 // epi(acc, tile_row0, col, bias_value) receives the 4 rows tile_row0 + 4*(lane>>4) + {0..3} of column `col`.
 // NT = tiles per wave (N / 128, at least 1): the NT tiles of a wave share the 16 rows, so they walk K together:
 // one A fragment feeds NT independent accumulators.
 // c0 / use_pre: a layer done as several passes over column ranges (4-wave shape, N = 256: two passes of two tiles per wave, so
 // that the operand double buffers stay within the register budget of three waves per SIMD) starts pass p at column c0 = p * NT * TS;
-// only the first pass finds its first B fragment in bpre, only the last one (has_next) fetches the next layer's.
-template <int W, int NT, typename Epi>
+// only the first pass finds its first B fragment in pre, only the last one (has_next) fetches the next layer's.
+template <int W, int MAXNT, int NT, typename Epi>
 __device__ __forceinline__ void tail_gemm_nt(const float* in, int ld_in, const float* zero_line, const TailLayerDev L,
-                                             const TailLayerDev next, bool has_next, int T, int R, f32x4 (&bpre)[4], Epi epi,
+                                             const TailLayerDev next, bool has_next, int T, int R, TailPre<W, MAXNT>& pre, Epi epi,
                                              int c0 = 0, bool use_pre = true) {
+    using S = TailSched<W, MAXNT>;
+    constexpr int P = S::P, D = S::D, NTP = S::NTP, PW = S::PW;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int fr = lane & 15, fq = lane >> 4;
     const int kb = L.K / 64, nblk = 3 * kb;                   // (tap, 64-wide k block) pairs
@@ -88,7 +152,7 @@ __device__ __forceinline__ void tail_gemm_nt(const float* in, int ld_in, const f
     constexpr int TS = 16 * W;                                // column stride between the tiles of a wave
     const int n0 = wave * 16 + c0;                            // tile i of this wave: columns n0 + TS*i
     if (n0 >= L.N) {                                          // 64-wide layer, 8 waves: waves 4-7 only fetch ahead
-        if (has_next) tail_prefetch_first<W>(next, bpre);
+        if (has_next) tail_prefetch<W, MAXNT>(next, pre);
         return;
     }
     const int row = fr;
@@ -98,24 +162,28 @@ __device__ __forceinline__ void tail_gemm_nt(const float* in, int ld_in, const f
     f32x4 acc[NT];
 #pragma unroll
     for (int i = 0; i < NT; ++i) {
-        bv[i] = L.bias ? L.bias[n0 + TS * i + fr] : 0.f;      // issued now, consumed in the epilogue
+        if (S::DEEP && i < NTP && use_pre) bv[i] = pre.bias[i];   // (nothing in flight in front of the first block's fragments)
+        else bv[i] = L.bias ? L.bias[n0 + TS * i + fr] : 0.f; // issued now, consumed in the epilogue
         acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
     // B: with the [tap][K/4][N][4] layout the (tap, k-block) pairs are consecutive: block blk starts 16*N float4 after
     // block blk-1, whatever the tap.  A: rows outside the window (the conv's zero padding) and rows past R read a
     // zero line of LDS instead -- selecting the ADDRESS keeps the ds_reads in flight behind the MFMAs, a select on
     // the loaded DATA would make the wave wait for them on the spot.
-    const f32x4* pB = W4 + (size_t)fq * L.N + n0 + fr;
+    // (addressed as wave-uniform base + one 32-bit lane offset, so that the requests of a block cost a single VGPR of addresses)
+    const char* pB = reinterpret_cast<const char*>(W4 + n0);
+    const unsigned vB = (unsigned)(fq * L.N + fr) * 16u;
     const int strideB = 16 * L.N;
     const int a_own = row * ld_in + 4 * fq;                   // this lane's row, tap 1
     const int a_zero = (int)(zero_line - in) + 4 * fq;
     const bool ok_m = row_ok && t_row >= 1, ok_p = row_ok && t_row + 1 < T;
-#define TAIL_LOAD_B(blk_, dst_)                                                                        \
+#define TAIL_LOAD_B1(blk_, dst_, i_)                                                                   \
     {                                                                                                  \
-        const f32x4* p_ = pB + (size_t)(blk_) * strideB;                                               \
-        _Pragma("unroll") for (int i = 0; i < NT; ++i)                                                 \
-            _Pragma("unroll") for (int g = 0; g < 4; ++g) dst_[i][g] = p_[(size_t)(4 * g) * L.N + TS * i]; \
+        const char* p_ = pB + ((size_t)(blk_) * strideB + TS * (i_)) * 16;                             \
+        _Pragma("unroll") for (int g = 0; g < 4; ++g) dst_[i_][g] = *reinterpret_cast<const f32x4*>(p_ + (size_t)(64 * g) * L.N + vB); \
     }
+#define TAIL_LOAD_B(blk_, dst_)                                                                        \
+    { _Pragma("unroll") for (int i = 0; i < NT; ++i) TAIL_LOAD_B1(blk_, dst_, i); }
 #define TAIL_LOAD_A(blk_, dst_)                                                                        \
     {                                                                                                  \
         const int tap_ = ((blk_) >= kb) + ((blk_) >= 2 * kb), k0_ = ((blk_) - tap_ * kb) * 64;         \
@@ -132,72 +200,128 @@ __device__ __forceinline__ void tail_gemm_nt(const float* in, int ld_in, const f
             _Pragma("unroll") for (int i = 0; i < NT; ++i) acc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(a_[g].w, b_[i][g].w, acc[i], 0, 0, 0); \
         }                                                                                              \
     }
-    // two register sets for both operands, loads issued one block (16*NT MFMAs) ahead of their use
-    f32x4 b0[NT][4], b1[NT][4], a0[4], a1[4];
-    TAIL_LOAD_B(0, b0);
-    if (use_pre) {
-#pragma unroll
-        for (int g = 0; g < 4; ++g) b0[0][g] = bpre[g];       // tile 0 / block 0 was prefetched by the previous layer
-    }
-    TAIL_LOAD_A(0, a0);
-    // Branch-free pair loop (a conditional prefetch makes hipcc fall back to vmcnt(0) at the join); a sched_barrier between the
-    // halves (otherwise both prefetches are hoisted to the loop top and waited for together), and inside a half the loads of the
-    // next block are dealt out between the MFMAs of the current one (sched_group_barrier): a wave issues them in the shadow of its
-    // own matrix instructions instead of in front of them -- with one wave per SIMD and workgroup (the 4-wave shape) nothing else
-    // would feed the pipe meanwhile (1536 windows fp32: 49.4 k against 48.0 k windows/s; no difference for the 8-wave shape).
-    const int npairs = nblk / 2;
-    // one block = 16 NT MFMAs, 4 NT global loads (B of the next block), 4 LDS reads (A of the next block)
-#define TAIL_INTERLEAVE()                                                                                          \
+    // One block = 16 NT MFMAs, 4 LDS reads (A of the next block) and, while the layer still has weights to request, 4 NT global
+    // loads (B of block blk + D - 1).  The loads are dealt out between the MFMAs of the block (sched_group_barrier): a wave
+    // issues them in the shadow of its own matrix instructions instead of in front of them -- with one wave per SIMD and workgroup
+    // (the 4-wave shape) nothing else would feed the pipe meanwhile (1536 windows fp32: 49.4 k against 48.0 k windows/s; no
+    // difference for the 8-wave shape).  A sched_barrier closes every block (otherwise the loads of several blocks are hoisted
+    // together and waited for together).
+#define TAIL_INTERLEAVE(LB_)                                                                                       \
     {                                                                                                              \
-        _Pragma("unroll") for (int i_ = 0; i_ < 4 * NT; ++i_) { __builtin_amdgcn_sched_group_barrier(0x008, 2, 0); __builtin_amdgcn_sched_group_barrier(0x020, 1, 0); } \
+        if (LB_) { _Pragma("unroll") for (int i_ = 0; i_ < 4 * NT; ++i_) { __builtin_amdgcn_sched_group_barrier(0x008, 2, 0); __builtin_amdgcn_sched_group_barrier(0x020, 1, 0); } } \
+        else __builtin_amdgcn_sched_group_barrier(0x008, 8 * NT, 0);                                               \
         _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_) { __builtin_amdgcn_sched_group_barrier(0x008, 2 * NT, 0); __builtin_amdgcn_sched_group_barrier(0x100, 1, 0); } \
     }
-    for (int p = 0; p < npairs; ++p) {
-        const int blk = 2 * p;
-        TAIL_LOAD_B(blk + 1, b1);
-        TAIL_LOAD_A(blk + 1, a1);
-        TAIL_COMPUTE(a0, b0);
-        TAIL_INTERLEAVE();
-        __builtin_amdgcn_sched_barrier(0);
-        const int nxt = min(blk + 2, nblk - 1);            // last pair: harmless re-load of the final block
-        TAIL_LOAD_B(nxt, b0);
-        TAIL_LOAD_A(nxt, a0);
-        TAIL_COMPUTE(a1, b1);
-        TAIL_INTERLEAVE();
-        __builtin_amdgcn_sched_barrier(0);
+    // block blk_ from register set s_ (A: set s_ of its own ring, always one block ahead; the last block re-reads its own rows)
+#define TAIL_STEP(blk_, s_, LB_, bcur_)                                                                \
+    {                                                                                                  \
+        if (LB_) TAIL_LOAD_B((blk_) + D - 1, b[((s_) + D - 1) % D]);                                   \
+        TAIL_LOAD_A(min((blk_) + 1, nblk - 1), a[((s_) + 1) % D]);                                     \
+        TAIL_COMPUTE(a[(s_) % D], bcur_);                                                              \
+        TAIL_INTERLEAVE(LB_);                                                                          \
+        __builtin_amdgcn_sched_barrier(0);                                                             \
     }
+    f32x4 a[D][4], b[D][NT][4];
+    TailPre<W, MAXNT> pre_next;
+    bool whole = false;                                       // the whole layer was prefetched
+    if constexpr (P >= 3 && NT == 1) whole = use_pre && nblk <= P;
+    if constexpr (S::EARLY) {
+        // What the previous layer requested for this one has been in flight for a whole layer: wait for it here and pin it (the empty
+        // asm makes the values "arrived" for the compiler), so that no later use of it waits for the requests issued from now on.
+        if (use_pre) {
+#pragma unroll
+            for (int s = 0; s < P; ++s) {
+                if (s < PW || whole) {
+#pragma unroll
+                    for (int g = 0; g < 4; ++g) asm volatile("" : "+v"(pre.b[s][g]));
+                }
+            }
+#pragma unroll
+            for (int i = 1; i < (NT < NTP ? NT : NTP); ++i)
+#pragma unroll
+                for (int s = 0; s < PW; ++s)
+#pragma unroll
+                    for (int g = 0; g < 4; ++g) asm volatile("" : "+v"(pre.bx[i - 1][s][g]));
+        }
+        if (has_next) tail_prefetch<W, MAXNT>(next, pre_next);
+    }
+    TAIL_LOAD_A(0, a[0]);
+    if (whole) {
+        if constexpr (P >= 3 && NT == 1) {
+            static_assert(P == 3, "a layer has at least three blocks: K = 64, three taps");
+#pragma unroll
+            for (int t = 0; t < P; ++t) TAIL_STEP(t, t, false, (&pre.b[t]));
+        }
+    } else {
+        // Ring of D register sets for B: sets 0 .. D-2 hold blocks 0 .. D-2 (prefetched by the previous layer, or requested here).
+        // Branch-free groups of D blocks while there is a block D - 1 ahead to request (a conditional request makes hipcc fall
+        // back to vmcnt(0) at the join), then the r = (nblk - D + 1) mod D left-over requesting blocks and the D - 1 blocks that
+        // only compute: nothing is requested past the layer's weights.
+#pragma unroll
+        for (int s = 0; s < D - 1; ++s)
+#pragma unroll
+            for (int i = 0; i < NT; ++i) {
+                if (s < PW && i < NTP && use_pre) {
+#pragma unroll
+                    for (int g = 0; g < 4; ++g) b[s][i][g] = i == 0 ? pre.b[s][g] : pre.bx[i > 0 ? i - 1 : 0][s < PW ? s : 0][g];
+                } else TAIL_LOAD_B1(s, b[s], i);
+            }
+        const int nl = nblk - (D - 1), ngrp = nl / D, r = nl - ngrp * D;
+        for (int grp = 0; grp < ngrp; ++grp) {
+#pragma unroll
+            for (int j = 0; j < D; ++j) TAIL_STEP(grp * D + j, j, true, b[j]);
+        }
+        const int blk0 = ngrp * D;
+#pragma unroll
+        for (int rr = 0; rr < D; ++rr) {
+            if (r != rr) continue;
+#pragma unroll
+            for (int t = 0; t < rr + D - 1; ++t) TAIL_STEP(blk0 + t, t, t < rr, b[t % D]);
+        }
+    }
+    if constexpr (S::EARLY) pre = pre_next;
+    else if (has_next) tail_prefetch<W, MAXNT>(next, pre);
+#undef TAIL_STEP
 #undef TAIL_INTERLEAVE
-    if (nblk & 1) TAIL_COMPUTE(a0, b0);
-    if (has_next) tail_prefetch_first<W>(next, bpre);
 #undef TAIL_LOAD_A
 #undef TAIL_LOAD_B
+#undef TAIL_LOAD_B1
 #undef TAIL_COMPUTE
 #pragma unroll
     for (int i = 0; i < NT; ++i) epi(acc[i], 4 * fq, n0 + TS * i + fr, bv[i]);
 }
 
-template <int W, typename Epi>
+// MAXNT = compile-time bound on the tiles per wave (plan_tail: from the widest layer of the chain): only NT <= MAXNT is instantiated,
+// so a chain without 512-column layers is not compiled for the registers of the 4-tile walk.
+template <int W, int MAXNT, typename Epi>
 __device__ __forceinline__ void tail_gemm(const float* in, int ld_in, const float* zero_line, const TailLayerDev L,
-                                          const TailLayerDev next, bool has_next, int T, int R, f32x4 (&bpre)[4], Epi epi) {
+                                          const TailLayerDev next, bool has_next, int T, int R, TailPre<W, MAXNT>& pre, Epi epi) {
     // N is 64, 128, 256 or 512 (plan_tail): N / (16 W) tiles per wave, at least one (W = 4: N <= 256, tail_can_share_cu checks)
     if constexpr (W == TAIL_WAVES_SHARED) {
         if (L.N > 32 * W) {
-            tail_gemm_nt<W, 2>(in, ld_in, zero_line, L, next, false, T, R, bpre, epi);
-            tail_gemm_nt<W, 2>(in, ld_in, zero_line, L, next, has_next, T, R, bpre, epi, 32 * W, false);
-        } else if (L.N > 16 * W) tail_gemm_nt<W, 2>(in, ld_in, zero_line, L, next, has_next, T, R, bpre, epi);
-        else tail_gemm_nt<W, 1>(in, ld_in, zero_line, L, next, has_next, T, R, bpre, epi);
+            tail_gemm_nt<W, MAXNT, 2>(in, ld_in, zero_line, L, next, false, T, R, pre, epi);
+            tail_gemm_nt<W, MAXNT, 2>(in, ld_in, zero_line, L, next, has_next, T, R, pre, epi, 32 * W, false);
+        } else if (L.N > 16 * W) tail_gemm_nt<W, MAXNT, 2>(in, ld_in, zero_line, L, next, has_next, T, R, pre, epi);
+        else tail_gemm_nt<W, MAXNT, 1>(in, ld_in, zero_line, L, next, has_next, T, R, pre, epi);
     } else {
-        if (L.N > 32 * W) tail_gemm_nt<W, 4>(in, ld_in, zero_line, L, next, has_next, T, R, bpre, epi);
-        else if (L.N > 16 * W) tail_gemm_nt<W, 2>(in, ld_in, zero_line, L, next, has_next, T, R, bpre, epi);
-        else tail_gemm_nt<W, 1>(in, ld_in, zero_line, L, next, has_next, T, R, bpre, epi);
+        if constexpr (MAXNT >= 4) {
+            if (L.N > 32 * W) { tail_gemm_nt<W, MAXNT, 4>(in, ld_in, zero_line, L, next, has_next, T, R, pre, epi); return; }
+        }
+        if (L.N > 16 * W) tail_gemm_nt<W, MAXNT, 2>(in, ld_in, zero_line, L, next, has_next, T, R, pre, epi);
+        else tail_gemm_nt<W, MAXNT, 1>(in, ld_in, zero_line, L, next, has_next, T, R, pre, epi);
     }
 }
 
 // NL = number of fused layers (compile time: the two layer loops unroll, so every layer's descriptor sits at a fixed
 // kernel-argument offset instead of being fetched by index behind each barrier)
-// W = wavefronts per workgroup: 8 (one workgroup per CU) or 4 (two per CU, G == 1 and N <= 256 only); launch_tail chooses
+// W = wavefronts per workgroup: 8 (one workgroup per CU) or 4 (three per CU, G == 1 and N <= 256 only); launch_tail chooses
+// MAXNT = most 16-column tiles a wave owns in any layer of the chain (TailArgs::maxnt, see tail_gemm).  It is the parameter of the
+// enclosing class, so that a kernel reads gem::TailTiles<2>::decoder_tail_kernel<5, 8> in profiles: the shape <NL, W> stays where
+// tools and tests that select kernels by name look for it.
+template <int MAXNT>
+struct TailTiles {
 template <int NL, int W>
-__global__ __launch_bounds__(64 * W, W == TAIL_WAVES_SHARED ? 3 : 2) void decoder_tail_kernel(TailArgs a) {
+static __global__ __launch_bounds__(64 * W, W == TAIL_WAVES_SHARED ? 3 : 2) void decoder_tail_kernel(TailArgs a) {
     constexpr int THREADS = 64 * W;
     constexpr bool TIGHT = W == TAIL_WAVES_SHARED;           // the LDS carve holds a.rows = G*T rows per buffer instead of 16
     constexpr int STAGE_U = 2048 / THREADS;                  // float4 per thread that cover 16 rows of K0 <= 512
@@ -290,8 +414,8 @@ __global__ __launch_bounds__(64 * W, W == TAIL_WAVES_SHARED ? 3 : 2) void decode
     TAIL_PROBE();
 
     // ---- forward layers
-    f32x4 bpre[4];
-    tail_prefetch_first<W>(a.fwd[0], bpre);
+    TailPre<W, MAXNT> bpre;
+    tail_prefetch<W, MAXNT>(a.fwd[0], bpre);
 #pragma unroll
     for (int i = 0; i < NL; ++i) {
         const bool last = (i + 1 == NL);
@@ -300,7 +424,7 @@ __global__ __launch_bounds__(64 * W, W == TAIL_WAVES_SHARED ? 3 : 2) void decode
         float* Xp = last ? a.Xp : nullptr;
         // (by value: taking the address of a kernel-argument member would put the whole struct in scratch)
         const TailLayerDev nxt = !last ? a.fwd[i + 1 < NL ? i + 1 : i] : a.bwd[NL - 1];
-        tail_gemm<W>(lds + a.off_act[i], a.ld_act[i], lds + a.off_zero, a.fwd[i], nxt, !last || !a.forward_only, T, R, bpre,
+        tail_gemm<W, MAXNT>(lds + a.off_act[i], a.ld_act[i], lds + a.off_zero, a.fwd[i], nxt, !last || !a.forward_only, T, R, bpre,
                   [&](const f32x4& acc, int r0, int col, float bv) {
 #pragma unroll
                       for (int e = 0; e < 4; ++e) {
@@ -364,7 +488,7 @@ __global__ __launch_bounds__(64 * W, W == TAIL_WAVES_SHARED ? 3 : 2) void decode
         float* gout = a.g_out;
         uint16_t* gout_b = a.g_out_b;
         const int K0 = a.fwd[0].K;
-        tail_gemm<W>(g_cur, a.ld_g, lds + a.off_zero, a.bwd[i], a.bwd[i > 0 ? i - 1 : 0], i > 0, T, R, bpre,
+        tail_gemm<W, MAXNT>(g_cur, a.ld_g, lds + a.off_zero, a.bwd[i], a.bwd[i > 0 ? i - 1 : 0], i > 0, T, R, bpre,
                   [&](const f32x4& acc, int r0, int col, float) {
 #pragma unroll
                       for (int e = 0; e < 4; ++e) {
@@ -384,6 +508,7 @@ __global__ __launch_bounds__(64 * W, W == TAIL_WAVES_SHARED ? 3 : 2) void decode
     }
 #undef TAIL_PROBE
 }
+};
 
 // LDS plan for a fused chain starting at decoder conv `start` (input = output of conv start-1, or of
 // decoder_input when start == 0).  Returns the byte size, or 0 when the chain is not fusable.
@@ -404,6 +529,11 @@ size_t plan_tail(const std::vector<Layer>& dec, int start, int T, int J, TailArg
     // >= R come from the zero line) and the epilogues do not write them
     a.waves = shared ? TAIL_WAVES_SHARED : TAIL_WAVES;
     a.rows = shared ? a.G * T : TAIL_ROWS;
+    // tiles per wave the kernel is compiled for: the widest output of a forward layer (N) or of its adjoint (K).  8 waves: 128 columns
+    // per tile index, so two tiles reach 256 columns; the 4-wave shape walks its (at most 256) columns in passes of two tiles.
+    int widest = 0;
+    for (int i = start; i < (int)dec.size(); ++i) widest = std::max(widest, std::max(dec[i].K, dec[i].N));
+    a.maxnt = !shared && widest > 32 * TAIL_WAVES ? 4 : 2;
     const int rows = a.rows;
     int off = 0, maxg = 0;
     for (int i = 0; i <= n; ++i) {
@@ -428,21 +558,21 @@ size_t plan_tail(const std::vector<Layer>& dec, int start, int T, int J, TailArg
     return (size_t)off * sizeof(float);
 }
 
-template <int NL, int W>
+template <int NL, int W, int MAXNT>
 static void launch_tail_as(gem_handle* h, const TailArgs& a, int wgs, size_t lds_bytes, hipStream_t s) {
-    note_kernel(h, reinterpret_cast<const void*>(decoder_tail_kernel<NL, W>));
-    hipLaunchKernelGGL((decoder_tail_kernel<NL, W>), dim3(wgs), dim3(64 * W), lds_bytes, s, a);
+    note_kernel(h, reinterpret_cast<const void*>(&TailTiles<MAXNT>::template decoder_tail_kernel<NL, W>));
+    hipLaunchKernelGGL((TailTiles<MAXNT>::template decoder_tail_kernel<NL, W>), dim3(wgs), dim3(64 * W), lds_bytes, s, a);
 }
 
-template <int W>
+template <int W, int MAXNT>
 static int launch_tail_w(gem_handle* h, const TailArgs& a, int wgs, size_t lds_bytes, hipStream_t s) {
     switch (a.n) {
-        case 1: launch_tail_as<1, W>(h, a, wgs, lds_bytes, s); break;
-        case 2: launch_tail_as<2, W>(h, a, wgs, lds_bytes, s); break;
-        case 3: launch_tail_as<3, W>(h, a, wgs, lds_bytes, s); break;
-        case 4: launch_tail_as<4, W>(h, a, wgs, lds_bytes, s); break;
-        case 5: launch_tail_as<5, W>(h, a, wgs, lds_bytes, s); break;
-        case 6: launch_tail_as<6, W>(h, a, wgs, lds_bytes, s); break;
+        case 1: launch_tail_as<1, W, MAXNT>(h, a, wgs, lds_bytes, s); break;
+        case 2: launch_tail_as<2, W, MAXNT>(h, a, wgs, lds_bytes, s); break;
+        case 3: launch_tail_as<3, W, MAXNT>(h, a, wgs, lds_bytes, s); break;
+        case 4: launch_tail_as<4, W, MAXNT>(h, a, wgs, lds_bytes, s); break;
+        case 5: launch_tail_as<5, W, MAXNT>(h, a, wgs, lds_bytes, s); break;
+        case 6: launch_tail_as<6, W, MAXNT>(h, a, wgs, lds_bytes, s); break;
         default: set_error("launch_tail: unsupported number of fused layers"); return 1;
     }
     return 0;
@@ -482,12 +612,15 @@ int tail_cap_workgroups(const gem_handle* h, const std::vector<Layer>& dec, int 
 int launch_tail(gem_handle* h, const TailArgs& a, size_t lds_bytes, hipStream_t s, const RoundSet* rs) {
     static PerDeviceOnce attr_once;
     if (attr_once.need(h->cfg.device)) {
-        const void* ks[] = {reinterpret_cast<const void*>(decoder_tail_kernel<1, 8>), reinterpret_cast<const void*>(decoder_tail_kernel<2, 8>),
-                            reinterpret_cast<const void*>(decoder_tail_kernel<3, 8>), reinterpret_cast<const void*>(decoder_tail_kernel<4, 8>),
-                            reinterpret_cast<const void*>(decoder_tail_kernel<5, 8>), reinterpret_cast<const void*>(decoder_tail_kernel<6, 8>),
-                            reinterpret_cast<const void*>(decoder_tail_kernel<1, 4>), reinterpret_cast<const void*>(decoder_tail_kernel<2, 4>),
-                            reinterpret_cast<const void*>(decoder_tail_kernel<3, 4>), reinterpret_cast<const void*>(decoder_tail_kernel<4, 4>),
-                            reinterpret_cast<const void*>(decoder_tail_kernel<5, 4>), reinterpret_cast<const void*>(decoder_tail_kernel<6, 4>)};
+        const void* ks[] = {reinterpret_cast<const void*>(&TailTiles<2>::decoder_tail_kernel<1, 8>), reinterpret_cast<const void*>(&TailTiles<2>::decoder_tail_kernel<2, 8>),
+                            reinterpret_cast<const void*>(&TailTiles<2>::decoder_tail_kernel<3, 8>), reinterpret_cast<const void*>(&TailTiles<2>::decoder_tail_kernel<4, 8>),
+                            reinterpret_cast<const void*>(&TailTiles<2>::decoder_tail_kernel<5, 8>), reinterpret_cast<const void*>(&TailTiles<2>::decoder_tail_kernel<6, 8>),
+                            reinterpret_cast<const void*>(&TailTiles<4>::decoder_tail_kernel<1, 8>), reinterpret_cast<const void*>(&TailTiles<4>::decoder_tail_kernel<2, 8>),
+                            reinterpret_cast<const void*>(&TailTiles<4>::decoder_tail_kernel<3, 8>), reinterpret_cast<const void*>(&TailTiles<4>::decoder_tail_kernel<4, 8>),
+                            reinterpret_cast<const void*>(&TailTiles<4>::decoder_tail_kernel<5, 8>), reinterpret_cast<const void*>(&TailTiles<4>::decoder_tail_kernel<6, 8>),
+                            reinterpret_cast<const void*>(&TailTiles<2>::decoder_tail_kernel<1, 4>), reinterpret_cast<const void*>(&TailTiles<2>::decoder_tail_kernel<2, 4>),
+                            reinterpret_cast<const void*>(&TailTiles<2>::decoder_tail_kernel<3, 4>), reinterpret_cast<const void*>(&TailTiles<2>::decoder_tail_kernel<4, 4>),
+                            reinterpret_cast<const void*>(&TailTiles<2>::decoder_tail_kernel<5, 4>), reinterpret_cast<const void*>(&TailTiles<2>::decoder_tail_kernel<6, 4>)};
         for (const void* k : ks) GEM_HIP(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     }
     Profile::Rec rec;
@@ -504,9 +637,15 @@ int launch_tail(gem_handle* h, const TailArgs& a, size_t lds_bytes, hipStream_t 
         GEM_HIP(hipEventRecord(rec.a, s));
     }
     const int wgs = (a.B + a.G - 1) / a.G;
-    if (a.waves != TAIL_WAVES && a.waves != TAIL_WAVES_SHARED) { set_error("launch_tail: the arguments do not come from plan_tail"); return 1; }
-    if (a.waves == TAIL_WAVES_SHARED ? launch_tail_w<TAIL_WAVES_SHARED>(h, a, wgs, lds_bytes, s) : launch_tail_w<TAIL_WAVES>(h, a, wgs, lds_bytes, s))
-        return 1;
+    // the shape and the tile bound are plan_tail's; a layer wider than the instantiation walks would lose columns
+    bool planned = (a.waves == TAIL_WAVES && (a.maxnt == 2 || a.maxnt == 4)) || (a.waves == TAIL_WAVES_SHARED && a.maxnt == 2);
+    for (int i = 0; planned && i < a.n && i < TAIL_MAX_LAYERS; ++i)
+        planned = std::max(a.fwd[i].N, a.bwd[i].N) <= (a.waves == TAIL_WAVES ? 16 * TAIL_WAVES * a.maxnt : 64 * TAIL_WAVES_SHARED);
+    if (!planned) { set_error("launch_tail: the arguments do not come from plan_tail"); return 1; }
+    const int err = a.waves == TAIL_WAVES_SHARED ? launch_tail_w<TAIL_WAVES_SHARED, 2>(h, a, wgs, lds_bytes, s)
+                    : a.maxnt == 4           ? launch_tail_w<TAIL_WAVES, 4>(h, a, wgs, lds_bytes, s)
+                                             : launch_tail_w<TAIL_WAVES, 2>(h, a, wgs, lds_bytes, s);
+    if (err) return 1;
     GEM_HIP(hipGetLastError());
     if (prof) { GEM_HIP(hipEventRecord(rec.b, s)); h->prof.recs.push_back(rec); }
     commit_kernel_names(h, prof ? 1 : -1);

@@ -1,5 +1,8 @@
 // Stand-alone timing harness for csrc/tail.hip (developer tool).
 //   hipcc -w --offload-arch=gfx950 -O3 -std=c++17 -o tools/tail_bench tools/tail_bench.hip && ./tools/tail_bench 240
+// The weight-stream schedule of the 8-wave kernel is a compile-time choice: add -DTAIL_PREFETCH_BLOCKS=P -DTAIL_RING_DEPTH=D to compare
+// settings (profiles/tail_prefetch.txt).  Every table is printed twice: launches back to back (weights warm in L2) and each launch
+// behind a 512 MB memset (L2 and the memory-side cache cold).
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
@@ -68,19 +71,29 @@ int main(int argc, char** argv) {
         printf("B=%d first %d forward layers only: %.1f us\n", B, nn, ms * 1e3 / iters);
     }
     a.n = nfull;
-    {   // phase timestamps of workgroup 0 (staging issued, staged, 5 forward layers, energy, 5 backward layers)
+    const size_t flush_bytes = (size_t)512 << 20;
+    void* flush; hipMalloc(&flush, flush_bytes);
+    for (int cold = 0; cold <= 1; ++cold) {   // phase timestamps of workgroup 0 (staging issued, staged, 5 forward layers, energy, 5 backward layers)
         long long* d_ts; hipMalloc(&d_ts, 64 * 8); hipMemset(d_ts, 0, 64 * 8);
         a.forward_only = 0; a.dbg_ts = d_ts;
-        for (int i = 0; i < 20; ++i) launch_tail(&h, a, lds, s);
+        for (int i = 0; i < 20; ++i) {
+            if (cold) hipMemsetAsync(flush, i, flush_bytes, s);
+            launch_tail(&h, a, lds, s);
+        }
         hipStreamSynchronize(s);
         long long ts[64]; hipMemcpy(ts, d_ts, sizeof(ts), hipMemcpyDeviceToHost);
         a.dbg_ts = nullptr;
+        printf("phases of workgroup 0, %s L2:\n", cold ? "cold" : "warm");
         const char* names[13] = {"loads issued", "staged", "fwd 256->128", "fwd 128->64", "fwd 64->64", "fwd 64->64", "fwd 64->45",
                                  "energy", "bwd 45->64", "bwd 64->64", "bwd 64->64", "bwd 64->128", "bwd 128->256"};
         for (int i = 1; i < 13; ++i)
             printf("  %-14s %7.2f us  (%6lld shader clocks, %.2f GHz)\n", names[i], (ts[2 * i + 1] - ts[2 * i - 1]) * 0.01,
                    ts[2 * i] - ts[2 * i - 2], (ts[2 * i] - ts[2 * i - 2]) / ((ts[2 * i + 1] - ts[2 * i - 1]) * 10.0 + 1e-9));
-        printf("  total inside the kernel %.2f us\n", (ts[25] - ts[1]) * 0.01);
+        auto span = [&](int i) { return (ts[2 * i + 1] - ts[2 * i - 1]) * 0.01; };
+        printf("  summary %s: wide layers (256<->128) %.2f us, the eight narrow layers %.2f us, energy %.2f us, total inside the kernel %.2f us\n",
+               cold ? "cold" : "warm", span(2) + span(12), span(3) + span(4) + span(5) + span(6) + span(8) + span(9) + span(10) + span(11),
+               span(7), (ts[25] - ts[1]) * 0.01);
+        hipFree(d_ts);
     }
     for (int fo = 1; fo >= 0; --fo) {
         a.forward_only = fo;
@@ -90,6 +103,19 @@ int main(int argc, char** argv) {
         hipEventRecord(e1, s); hipEventSynchronize(e1);
         float ms; hipEventElapsedTime(&ms, e0, e1);
         printf("B=%d forward_only=%d: %.1f us\n", B, fo, ms * 1e3 / iters);
+    }
+    {   // whole launch with cold caches: each launch timed on its own behind the memset
+        a.forward_only = 0;
+        float sum = 0.f;
+        for (int i = 0; i < 10; ++i) {
+            hipMemsetAsync(flush, i, flush_bytes, s);
+            hipEventRecord(e0, s);
+            launch_tail(&h, a, lds, s);
+            hipEventRecord(e1, s); hipEventSynchronize(e1);
+            float ms; hipEventElapsedTime(&ms, e0, e1);
+            sum += ms;
+        }
+        printf("B=%d forward_only=0, cold L2: %.1f us\n", B, sum * 1e3 / 10);
     }
     return 0;
 }
