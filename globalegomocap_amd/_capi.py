@@ -89,6 +89,18 @@ SCALE_CANDIDATES, SCALE_TILE, SCALE_REPORT_DOUBLES = 513, 256, 16
 SCALE_NO_PAIRS, SCALE_TOO_FEW, SCALE_BAD_SCALE = 2, 3, 4
 
 
+class GemGroundRecord(C.Structure):
+    _fields_ = [("status", C.c_double), ("source", C.c_double), ("n", C.c_double * 3), ("d", C.c_double), ("u0", C.c_double * 3),
+                ("tilt_cos", C.c_double)] + \
+               [(k, C.c_double) for k in ("points", "inliers", "rms", "spread", "extent", "contact_right", "contact_left", "skate", "penetration",
+                                          "lift_max", "skate_pairs", "frames", "lag")] + [("crt", C.c_double * 13), ("reserved", C.c_double * 12)]
+
+
+GROUND_RECORD_DOUBLES, GROUND_LDS_FRAMES = 48, 1024
+GROUND_NO_BODY, GROUND_BAD_SEQUENCE = 2, 3
+GROUND_SOURCES = ("plane", "body_normal", "body")
+
+
 class GemWindowStats(C.Structure):
     _fields_ = [("n_iter", C.c_int32), ("func_evals", C.c_int32), ("final_loss", C.c_float), ("status", C.c_int32)]
 
@@ -188,6 +200,9 @@ SIGNATURES = {
     "gem_slam_scale_work": (C.c_int64, [C.c_int64, C.c_int, C.c_int]),
     "gem_slam_scale": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(C.c_int), _P, _P, _P, C.c_int64, C.c_int, C.c_double, C.c_int, _P,
                                  C.c_int64, _P, _P, _P, _P]),
+    "gem_ground_plane_work": (C.c_int64, [_P, C.c_int, _P]),
+    "gem_ground_plane": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, C.c_double, _P, C.c_int64, _P, _P]),
+    "gem_similarity_compose": (C.c_int, [_P, _P, _P, C.c_int64, _P]),
 }
 
 _lib = None

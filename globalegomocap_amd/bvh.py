@@ -17,7 +17,7 @@ from collections import namedtuple
 import numpy as np
 
 from . import _capi
-from .meshes import _alignment, _sequence, result_poses
+from .meshes import _alignment, _sequence, _upright, result_poses
 
 Layout = namedtuple("Layout", "nodes channels field_bytes frame_bytes")
 Tables = namedtuple("Tables", "parents joint_of_node rest_dirs")
@@ -135,10 +135,11 @@ def hierarchy_text(rest, unit_scale=100.0):
     return "\n".join(lines) + "\n"
 
 
-def write_bvh(engine, seq, path, fps=DEFAULT_FPS, align_to=None, unit_scale=100.0):
+def write_bvh(engine, seq, path, fps=DEFAULT_FPS, align_to=None, unit_scale=100.0, move=None):
     """`seq` [F,15,3] (array or tensor, metres, F >= 1) as the BVH file `path`, one keyed frame per frame at `fps`; positions and
     offsets are metres times `unit_scale` (100: centimetres, what most importers assume).  align_to [F,15,3]: the sequence is first
-    moved by the one similarity transform that takes it onto `align_to` (`errors.align_sequence`).  Rest lengths, channels and the
+    moved by the one similarity transform that takes it onto `align_to` (`errors.align_sequence`).  move: a [13] device tensor
+    (c, R, t), for instance `GroundEstimate.crt`, applied behind the alignment.  Rest lengths, channels and the
     motion block's text are made on the device; the text crosses PCIe in slices of at most PINNED_BYTES through two alternating
     pinned buffers and is appended in order while the next slice is formatted and copied.  A frame with a channel that is no
     number or does not fit its field (a NaN joint, a position beyond +-9999999.999999 units) deletes the partial file and raises
@@ -151,7 +152,7 @@ def write_bvh(engine, seq, path, fps=DEFAULT_FPS, align_to=None, unit_scale=100.
         raise ValueError("a BVH file needs at least one frame")
     if not fps > 0:
         raise ValueError("fps must be positive, got %r" % (fps,))
-    crt = _alignment(engine, seq_d, align_to)
+    crt = _alignment(engine, seq_d, align_to, move)
     rest = rest_lengths(engine, seq_d, crt)
     chan = channels(engine, seq_d, crt, rest, unit_scale)
     per = max(1, PINNED_BYTES // lay.frame_bytes)
@@ -318,19 +319,22 @@ def skeleton_from_nodes(positions):
 
 
 # ------------------------------------------------------------------------------------------------------------------ a result's files
-def write_result_bvh(engine, out_dir, estimated, optimized, gt=None, fps=DEFAULT_FPS, align=None, unit_scale=100.0):
+def write_result_bvh(engine, out_dir, estimated, optimized, gt=None, fps=DEFAULT_FPS, align=None, unit_scale=100.0, upright=None):
     """`estimated.bvh`, `optimized.bvh` and, with a ground truth, `gt.bvh` under `out_dir` from the merged sequences, by the convention of
-    `report.Outputs`: with a ground truth the first two are aligned to it (`align`, default: whenever there is one).
-    Returns the number of files."""
+    `report.Outputs`: with a ground truth the first two are aligned to it (`align`, default: whenever there is one).  upright: True or
+    a `ground.GroundEstimate`: the files stand in the upright frame of the ground estimated from the foot contacts -- Y up, the floor at
+    0, the wearer at the origin facing +Z in the first frame (`meshes._upright`).  Returns the number of files."""
     align = gt is not None if align is None else align
     if align and gt is None:
         raise ValueError("aligned BVH files need a ground-truth sequence to align to")
     to = gt if align else None
+    move, move_gt = _upright(engine, upright, align, optimized, gt)
+    extra, extra_gt = ({} if move is None else {"move": move}), ({} if move_gt is None else {"move": move_gt})
     os.makedirs(out_dir, exist_ok=True)
-    write_bvh(engine, estimated, os.path.join(out_dir, FILE_NAMES[0]), fps=fps, align_to=to, unit_scale=unit_scale)
-    write_bvh(engine, optimized, os.path.join(out_dir, FILE_NAMES[1]), fps=fps, align_to=to, unit_scale=unit_scale)
+    write_bvh(engine, estimated, os.path.join(out_dir, FILE_NAMES[0]), fps=fps, align_to=to, unit_scale=unit_scale, **extra)
+    write_bvh(engine, optimized, os.path.join(out_dir, FILE_NAMES[1]), fps=fps, align_to=to, unit_scale=unit_scale, **extra)
     if gt is not None:
-        write_bvh(engine, gt, os.path.join(out_dir, FILE_NAMES[2]), fps=fps, unit_scale=unit_scale)
+        write_bvh(engine, gt, os.path.join(out_dir, FILE_NAMES[2]), fps=fps, unit_scale=unit_scale, **extra_gt)
     return 2 if gt is None else 3
 
 
@@ -343,12 +347,14 @@ def main(argv=None):
     p.add_argument("--fps", default=float(DEFAULT_FPS), type=float, help="frames per second of the files (Frame Time = 1 / fps)")
     p.add_argument("--align", default=False, type=truthy, help="true: align both sequences to gt_pose first")
     p.add_argument("--unit_scale", default=100.0, type=float, help="file units per metre (100: centimetres)")
+    p.add_argument("--upright", action="store_true", help="stand the files upright on the ground estimated from the foot contacts: Y up, the floor at 0")
     a = p.parse_args(argv)
     if not a.fps > 0:
         p.error("--fps must be positive")
     if not a.unit_scale > 0:
         p.error("--unit_scale must be positive")
-    n = write_result_bvh(*result_poses(p, a, "the BVH files are made on the device"), fps=a.fps, align=a.align, unit_scale=a.unit_scale)
+    n = write_result_bvh(*result_poses(p, a, "the BVH files are made on the device"), fps=a.fps, align=a.align, unit_scale=a.unit_scale,
+                         upright=a.upright or None)
     print("{} BVH files written under {}".format(n, a.out))
 
 

@@ -61,21 +61,44 @@ def _sequence(engine, seq):
     return t
 
 
-def _alignment(engine, seq_d, align_to):
-    if align_to is None:
-        return None
-    to_d = _sequence(engine, align_to)
-    if to_d.shape != seq_d.shape:
-        raise ValueError("align_to must have the sequence's shape %s, got %s" % (tuple(seq_d.shape), tuple(to_d.shape)))
-    return engine.sequence_align(seq_d, to_d)
+def _alignment(engine, seq_d, align_to, move=None):
+    """The (c, R, t) [13] on the device that the kernels apply to the joints, or None: the similarity onto `align_to`, then `move`
+    (composed on the device, `ground.compose`)."""
+    crt = None
+    if align_to is not None:
+        to_d = _sequence(engine, align_to)
+        if to_d.shape != seq_d.shape:
+            raise ValueError("align_to must have the sequence's shape %s, got %s" % (tuple(seq_d.shape), tuple(to_d.shape)))
+        crt = engine.sequence_align(seq_d, to_d)
+    if move is None:
+        return crt
+    import torch
+    from .ground import compose
+    if not (torch.is_tensor(move) and move.is_cuda and move.dtype == torch.float64 and move.is_contiguous() and tuple(move.shape) == (13,)):
+        raise TypeError("move must be a contiguous float64 device tensor of 13 values (c, R, t)")
+    return move if crt is None else compose(engine, crt, move)
 
 
-def vertex_blocks(engine, seq, align_to=None):
+def _upright(engine, upright, aligned, optimized, gt):
+    """The `move` of a `write_result_*` for its `upright` argument -> (for the estimated and the optimised sequence, for the ground
+    truth).  True: ONE estimate for all sequences written -- of the ground truth where the other two are aligned to it, else of the
+    optimised sequence; a ground truth the others are not aligned to lives in a frame of its own and is stood upright by its own."""
+    if upright is None or upright is False:
+        return None, None
+    from .ground import resolve
+    g = resolve(engine, upright, gt if aligned else optimized)
+    if gt is None or aligned or upright is not True:
+        return g.crt, g.crt
+    return g.crt, resolve(engine, True, gt).crt
+
+
+def vertex_blocks(engine, seq, align_to=None, move=None):
     """The vertex blocks of the meshes of `seq` [F,15,3] (array or tensor) as the files hold them: a uint8 device tensor
     [F, vertex_bytes].  align_to [F,15,3]: the sequence is first moved by the one similarity transform that takes it onto
-    `align_to` (`errors.align_sequence`, the reference's global_align_skeleton_seq).  Nothing synchronises."""
+    `align_to` (`errors.align_sequence`, the reference's global_align_skeleton_seq).  move: a [13] device tensor (c, R, t), for
+    instance `GroundEstimate.crt`, applied behind the alignment.  Nothing synchronises."""
     seq_d = _sequence(engine, seq)
-    return engine.skeleton_mesh(seq_d, _alignment(engine, seq_d, align_to))
+    return engine.skeleton_mesh(seq_d, _alignment(engine, seq_d, align_to, move))
 
 
 def _write_file(path, parts):
@@ -93,14 +116,14 @@ def _write_file(path, parts):
         os.close(fd)
 
 
-def write_meshes(engine, seq, out_dir, align_to=None, pattern="out_%04d.ply"):
-    """`out_dir/pattern % f` for every frame f of `seq` [F,15,3] (the reference's save_mesh), `align_to` as in `vertex_blocks`.
+def write_meshes(engine, seq, out_dir, align_to=None, pattern="out_%04d.ply", move=None):
+    """`out_dir/pattern % f` for every frame f of `seq` [F,15,3] (the reference's save_mesh), `align_to` and `move` as in `vertex_blocks`.
     The vertex blocks are made on the device, at most PINNED_BYTES of them at a time, and go through `staging.stream_out` to the
     writer threads (at most MAX_WRITERS, on the CPUs near the device).  Runs on the current stream.  Every file is complete and closed when this
     returns; returns the number of files."""
     from .staging import cpus_near, reader_pool, stream_out
     seq_d = _sequence(engine, seq)
-    crt = _alignment(engine, seq_d, align_to)
+    crt = _alignment(engine, seq_d, align_to, move)
     os.makedirs(out_dir, exist_ok=True)
     F, lay = seq_d.shape[0], layout()
     if F == 0:
@@ -156,19 +179,22 @@ def read_ply(path):
     return vert["p"].copy(), vert["c"].copy(), face["i"].astype(np.uint32)
 
 
-def write_result_meshes(engine, out_dir, estimated, optimized, gt=None, align=None):
+def write_result_meshes(engine, out_dir, estimated, optimized, gt=None, align=None, upright=None):
     """The reference's three folders under `out_dir` (optimizer.py:486-504) from the merged sequences: the optimised and the
     estimated one aligned to the ground truth (`align`, default: whenever there is one), and the ground truth itself.  Without
-    alignment the folders are called optimized_global / input_global (/ gt_global)."""
+    alignment the folders are called optimized_global / input_global (/ gt_global).  upright: True or a `ground.GroundEstimate`: all
+    meshes stand in the upright frame of the ground estimated from the foot contacts (`_upright`)."""
     align = gt is not None if align is None else align
     if align and gt is None:
         raise ValueError("aligned meshes need a ground-truth sequence to align to")
     names = ALIGNED_DIRS if align else PLAIN_DIRS
     to = gt if align else None
-    n = write_meshes(engine, optimized, os.path.join(out_dir, names[0]), align_to=to)
-    n += write_meshes(engine, estimated, os.path.join(out_dir, names[1]), align_to=to)
+    move, move_gt = _upright(engine, upright, align, optimized, gt)
+    extra, extra_gt = ({} if move is None else {"move": move}), ({} if move_gt is None else {"move": move_gt})
+    n = write_meshes(engine, optimized, os.path.join(out_dir, names[0]), align_to=to, **extra)
+    n += write_meshes(engine, estimated, os.path.join(out_dir, names[1]), align_to=to, **extra)
     if gt is not None:
-        n += write_meshes(engine, gt, os.path.join(out_dir, names[2]))
+        n += write_meshes(engine, gt, os.path.join(out_dir, names[2]), **extra_gt)
     return n
 
 
@@ -200,8 +226,9 @@ def main(argv=None):
     p.add_argument("pose_pickle", help="result_pose.pkl as --save_pose writes it: estimated_pose, optimized_pose and, optionally, gt_pose")
     p.add_argument("--out", required=True, metavar="DIR")
     p.add_argument("--align", default=False, type=truthy, help="true: align both sequences to gt_pose first (the reference's --save)")
+    p.add_argument("--upright", action="store_true", help="stand the meshes upright on the ground estimated from the foot contacts")
     a = p.parse_args(argv)
-    n = write_result_meshes(*result_poses(p, a, "the meshes are built on the device"), align=a.align)
+    n = write_result_meshes(*result_poses(p, a, "the meshes are built on the device"), align=a.align, upright=a.upright or None)
     print("{} meshes written under {}".format(n, a.out))
 
 

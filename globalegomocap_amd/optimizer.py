@@ -190,7 +190,7 @@ class SequenceOptimizer:
 def main(data_id, camera_model_path, vae_weight, gmm_weight, smoothness_weight, bone_length_weight, weight_3d,
          reproj_weight, visualization=False, final_smooth=False, merge=True, save=False, save_pose=False,
          global_vae_path=GLOBAL_VAE_PATH, local_vae_path=LOCAL_VAE_PATH, eps=None, optimizer=None, return_stats=False,
-         device_metrics=False, mesh_root="out", render=None, render_camera=None, bvh=None, bvh_fps=None):
+         device_metrics=False, mesh_root="out", render=None, render_camera=None, bvh=None, bvh_fps=None, *, upright=False, foot_height=None):
     """pickle in, poses out -- the reference's `main` (optimizer.py:311-507) for one chunk directory.
 
     Returns (errors OrderedDict[18], final_estimated_seq, mid_local_pose_seq, final_optimized_seq, final_gt_seq): lists of [15,3]
@@ -205,6 +205,9 @@ def main(data_id, camera_model_path, vae_weight, gmm_weight, smoothness_weight, 
     three sequences, the ground truth moved onto the optimised one (`render.write_result_camera_frames`).
     bvh=DIR writes the three sequences as animation, DIR/<dataset>/<chunk>/{estimated,optimized,gt}.bvh at `bvh_fps` frames per second
     (default 25), the first two aligned to the ground truth (`bvh.write_result_bvh`).
+    upright=True (keyword only, with foot_height): the meshes, frames and BVH files stand upright on the ground estimated from the
+    chunk's foot contacts (`ground.estimate_ground`); the errors then have the entry `ground`
+    (`GroundEstimate.as_dict`) and its line is printed.
     """
     if visualization:
         raise NotImplementedError("visualization opens open3d's viewer (optimizer.py:452-467), which this package does not have: "
@@ -246,15 +249,20 @@ def main(data_id, camera_model_path, vae_weight, gmm_weight, smoothness_weight, 
         os.makedirs(out_dir, exist_ok=True)
         with open(os.path.join(out_dir, "result_pose.pkl"), "wb") as f:
             pickle.dump(result_pose_dict(final_estimated_seq, final_optimized_seq, mid_estimated_seq, final_gt_seq, final_smooth is True), f)
-    outputs = Outputs(mesh_root if save else None, render, render_camera, bvh, bvh_fps)
+    outputs = Outputs(mesh_root if save else None, render, render_camera, bvh, bvh_fps, upright=upright if upright else None,
+                      upright_foot_height=foot_height if upright else None)
+    found = None
     if outputs:
         sequences = (np.asarray(final_estimated_seq), final_optimized_d if device_metrics else np.asarray(final_optimized_seq),
                      np.asarray(final_gt_seq))
-        outputs.write(opt.engine, data_id, sequences, cams, heat)
+        found = outputs.write(opt.engine, data_id, sequences, cams, heat)
     if device_metrics:
         errors = opt.engine.calculate_errors(final_estimated_seq, mid_estimated_seq, final_optimized_d, final_gt_seq)
     else:
         errors = calculate_errors(final_estimated_seq, mid_estimated_seq, final_optimized_seq, final_gt_seq)
+    if found is not None:
+        errors["ground"] = found.as_dict()
+        print("{}: {}".format(data_id, found.line()))
     # The reference's merge_batches returns a LIST of [15,3] frames (optimizer.py:425-437); only the final Gaussian smoothing
     # (optimizer.py:448-450: gaussian_filter1d) turns final_optimized_seq into an ndarray -- same container types here.
     opt_out = final_optimized_seq if final_smooth is True else list(np.asarray(final_optimized_seq))

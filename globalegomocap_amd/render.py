@@ -103,9 +103,10 @@ def fit_view(sequences, width, height, view="side"):
     return v
 
 
-def _prepare(engine, sequences, align_to):
+def _prepare(engine, sequences, align_to, move=None):
     """The sequences on the device and, per sequence, the similarity (`WindowEngine.sequence_align`, [13] on the device) onto its
-    entry of `align_to`: None, one sequence for all, or a list with a sequence or None for each."""
+    entry of `align_to`: None, one sequence for all, or a list with a sequence or None for each.  move: None, one [13] device tensor
+    for all or a list with one or None for each, applied behind the alignment."""
     seqs = [_sequence(engine, s) for s in sequences]
     if not seqs:
         raise ValueError("no sequence to draw")
@@ -114,7 +115,12 @@ def _prepare(engine, sequences, align_to):
     targets = list(align_to) if isinstance(align_to, (list, tuple)) else [align_to] * len(seqs)
     if len(targets) != len(seqs):
         raise ValueError("align_to lists %d targets for %d sequences" % (len(targets), len(seqs)))
-    return seqs, [_alignment(engine, s, to) for s, to in zip(seqs, targets)]
+    if move is None:
+        return seqs, [_alignment(engine, s, to) for s, to in zip(seqs, targets)]
+    moves = list(move) if isinstance(move, (list, tuple)) else [move] * len(seqs)
+    if len(moves) != len(seqs):
+        raise ValueError("move lists %d transforms for %d sequences" % (len(moves), len(seqs)))
+    return seqs, [_alignment(engine, s, to, m) for s, to, m in zip(seqs, targets, moves)]
 
 
 def frames_view(engine, sequences, align_to=None, size=None, view="side"):
@@ -262,7 +268,7 @@ def _video_arguments(video, video_fps, video_quality, frames):
 
 
 def write_frames(engine, sequences, out_dir, colours=None, align_to=None, size=None, view="side", overview=True, names=None, video=None,
-                 video_fps=DEFAULT_FPS, video_quality=DEFAULT_QUALITY, frames=True):
+                 video_fps=DEFAULT_FPS, video_quality=DEFAULT_QUALITY, frames=True, move=None):
     """`out_dir/frame_%04d.png` for every frame, all `sequences` (each [F,15,3]) overlaid in their `colours` (default: the palette's
     order estimated, optimised, ground truth), and -- overview=True -- `out_dir/overview_<name>.png` per sequence with all its
     frames in one scene (`names`, default: the palette's names).  align_to: None, one sequence [F,15,3] for all, or a list with one
@@ -270,10 +276,11 @@ def write_frames(engine, sequences, out_dir, colours=None, align_to=None, size=N
     target (`errors.align_sequence`).  size = (width, height), default DEFAULT_SIZE; `view` as in `fit_view`, fitted once to everything that is drawn.
     video=PATH additionally writes the per-frame images -- not the overviews -- as one Motion-JPEG clip to PATH at `video_fps` frames
     per second and JPEG quality `video_quality` (`video.write_video`: encoded on the device); with
-    frames=False no PNG file is written, and `out_dir` is not touched.
+    frames=False no PNG file is written, and `out_dir` is not touched.  move: a [13] device tensor (c, R, t), for instance
+    `GroundEstimate.crt`, or a list with one or None per sequence, applied behind the alignment.
     Runs on the current stream; every file is complete and closed on return; returns the number of files."""
     _video_arguments(video, video_fps, video_quality, frames)
-    seqs, crts = _prepare(engine, sequences, align_to)
+    seqs, crts = _prepare(engine, sequences, align_to, move)
     S, F = len(seqs), seqs[0].shape[0]
     default = list(PALETTE)
     if colours is None:
@@ -305,17 +312,21 @@ def write_frames(engine, sequences, out_dir, colours=None, align_to=None, size=N
 
 
 def write_result_frames(engine, out_dir, estimated, optimized, gt=None, align=None, size=None, view="side", video=None, video_fps=DEFAULT_FPS,
-                        video_quality=DEFAULT_QUALITY, frames=True):
+                        video_quality=DEFAULT_QUALITY, frames=True, upright=None):
     """One result's frames under `out_dir`: the estimated, the optimised and, where there is one, the ground-truth sequence overlaid
     (red, blue, green), the first two aligned to the third (`align`, default: whenever there is one) as `meshes.write_result_meshes`
-    aligns the meshes.  video, video_fps, video_quality, frames: see `write_frames`."""
+    aligns the meshes.  video, video_fps, video_quality, frames: see `write_frames`.  upright: True or a `ground.GroundEstimate`: the
+    sequences are drawn in the upright frame of the ground estimated from the foot contacts (`meshes._upright`)."""
     align = gt is not None if align is None else align
     if align and gt is None:
         raise ValueError("aligned frames need a ground-truth sequence to align to")
     sequences = [estimated, optimized] + ([gt] if gt is not None else [])
     to = [gt if align else None] * 2 + ([None] if gt is not None else [])
+    from .meshes import _upright
+    move, move_gt = _upright(engine, upright, align, optimized, gt)
+    extra = {} if move is None else {"move": [move, move] + ([move_gt] if gt is not None else [])}
     return write_frames(engine, sequences, out_dir, align_to=to, size=size, view=view, video=video, video_fps=video_fps,
-                        video_quality=video_quality, frames=frames)
+                        video_quality=video_quality, frames=frames, **extra)
 
 
 # ------------------------------------------------------------------------------------------------------------------ the camera's view
@@ -452,6 +463,7 @@ def main(argv=None):
     p.add_argument("--video_fps", default=float(DEFAULT_FPS), type=float, metavar="F", help="frames per second of the clip (default 25)")
     p.add_argument("--video_quality", default=DEFAULT_QUALITY, type=int, metavar="Q", help="JPEG quality of the clip, 1 .. 100 (default 90)")
     p.add_argument("--no_frames", action="store_true", help="with --video: the clip only, no PNG files")
+    p.add_argument("--upright", action="store_true", help="draw the sequences upright on the ground estimated from the foot contacts (not with --camera)")
     a = p.parse_args(argv)
     if not a.video_fps > 0:
         p.error("argument --video_fps: must be positive")
@@ -463,6 +475,8 @@ def main(argv=None):
                 video_fps=a.video_fps, video_quality=a.video_quality, frames=not a.no_frames)
     if a.camera is None and isinstance(a.size, int):
         p.error("argument --size: a size is WIDTHxHEIGHT, for instance 640x480; got %r" % str(a.size))
+    if a.camera is not None and a.upright:
+        p.error("--upright: the camera's view is the camera's own image and is not stood upright")
     if a.camera is not None:
         if isinstance(a.size, tuple) or (a.size is not None and a.size > 1024):
             p.error("argument --size: with --camera a size is one number of pixels 1 .. 1024")
@@ -478,7 +492,8 @@ def main(argv=None):
         heat = np.asarray(c["heat_list"][:F], dtype=np.float32).reshape((F,) + tuple(c["heat_shape"]))
         n = write_result_camera_frames(engine, out, est, opt, c["cams"][:F], heat, gt, size=a.size, **clip)
     else:
-        n = write_result_frames(engine, out, est, opt, gt, align=a.align, size=DEFAULT_SIZE if a.size is None else a.size, view=a.view, **clip)
+        n = write_result_frames(engine, out, est, opt, gt, align=a.align, size=DEFAULT_SIZE if a.size is None else a.size, view=a.view,
+                                upright=a.upright or None, **clip)
     print("{} {} written under {}".format(n, "files" if a.video else "images", a.out))
 
 

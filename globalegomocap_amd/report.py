@@ -185,12 +185,13 @@ def sequence_result(reports, title, verbose):
     results, raw = [r.result for r in reports], [r.raw for r in reports]
     ground_truth = not reports or reports[0].gt is not None
     summary = OrderedDict()
+    keys = [k for k in results[0] if k != "ground"] if reports else []          # (`ground`: a chunk's ground record, with --upright; no number to average)
     if reports and all(x is not None for x in raw):          # (every chunk of the sequence came as a row of the device report: one mean)
         mean = np.mean(np.stack(raw), axis=0)
-        for i, k in enumerate(results[0]):
+        for i, k in enumerate(keys):
             summary[k] = mean[17:].copy() if k == "joints_error" else float(mean[i])
     elif reports:
-        for k in results[0]:
+        for k in keys:
             summary[k] = (np.mean([r[k] for r in results], axis=0) if k == "joints_error"
                           else float(np.average([r[k] for r in results])))
     if verbose and reports:
@@ -227,7 +228,13 @@ class Outputs:
       video          the frames `render` draws -- the same view and overlay, without the overviews -- as one Motion-JPEG clip,
                      <chunk>/frames.avi (DESIGN.md section 6j); no PNG file is written for it, and it does not need `render`;
       video_camera   the images `render_camera` draws as <chunk>/camera.avi, likewise.
-    Both clips play at `video_fps` frames per second (default 25) and are encoded at JPEG quality `video_quality` (default 90)."""
+    Both clips play at `video_fps` frames per second (default 25) and are encoded at JPEG quality `video_quality` (default 90).
+      upright        True, or a `ground.GroundEstimate`: the meshes, frames, clip and BVH files of a chunk stand in ONE upright frame -- Y up,
+                     the floor at 0, the wearer at the origin facing +Z in the first frame -- of the ground estimated once per chunk from
+                     its foot contacts: from the ground truth where there is one (the other sequences are
+                     aligned to it), else from the optimised sequence; `upright_foot_height`: metres a standing foot point lies above
+                     the floor (default 0), `upright_lag`: frames between the two frames of a still pair (default 0.2 s at `bvh_fps`).
+                     The camera's views are the camera's own images and take no part."""
     mesh_root: object = None
     render: object = None
     render_camera: object = None
@@ -237,6 +244,9 @@ class Outputs:
     video_camera: object = None
     video_fps: object = None
     video_quality: object = None
+    upright: object = None
+    upright_foot_height: object = None
+    upright_lag: object = None
 
     def __bool__(self):
         return any(root is not None for root in (self.mesh_root, self.render, self.render_camera, self.bvh, self.video, self.video_camera))
@@ -260,24 +270,33 @@ class Outputs:
         """One chunk's output files from `sequences` = (estimated, optimised, ground truth or None), host arrays or device tensors.
         `cams` / `heat` (`needs_frames`) hold the chunk's frames from `first_frame` on; merged frame f is the chunk's frame f.  With
         a ground truth the estimated and the optimised sequence are aligned to it and all three are written, as in the reference;
-        without, nothing is aligned and there is no third sequence."""
+        without, nothing is aligned and there is no third sequence.  -> the chunk's `ground.GroundEstimate` with `upright`, else None."""
         est, opt, gt = sequences
         bvh_fps, video_fps, video_quality = self._rates()
         clip = dict(video_fps=video_fps, video_quality=video_quality, frames=False)
         frames = slice(first_frame, first_frame + len(est))
+        found, extra = None, {}
+        if self.upright is not None and self.upright is not False and any(r is not None for r in (self.mesh_root, self.render, self.bvh, self.video)):
+            from . import ground
+            options = {} if self.upright is not True else dict(fps=bvh_fps, lag=self.upright_lag,
+                                                                foot_height=0.0 if self.upright_foot_height is None else self.upright_foot_height)
+            found = ground.resolve(engine, self.upright, gt if gt is not None else opt, **options)
+            extra = {"upright": found}          # (ONE estimate per chunk: its files share one frame)
         if self.mesh_root is not None:
-            meshes.write_result_meshes(engine, result_dir(self.mesh_root, data_id), est, opt, gt)
+            meshes.write_result_meshes(engine, result_dir(self.mesh_root, data_id), est, opt, gt, **extra)
         if self.render is not None:
-            rendering.write_result_frames(engine, result_dir(self.render, data_id), est, opt, gt)
+            rendering.write_result_frames(engine, result_dir(self.render, data_id), est, opt, gt, **extra)
         if self.render_camera is not None:
             rendering.write_result_camera_frames(engine, result_dir(self.render_camera, data_id), est, opt, cams[frames], heat[frames], gt)
         if self.bvh is not None:
-            animation.write_result_bvh(engine, result_dir(self.bvh, data_id), est, opt, gt, fps=bvh_fps)
+            animation.write_result_bvh(engine, result_dir(self.bvh, data_id), est, opt, gt, fps=bvh_fps, **extra)
         if self.video is not None:
-            rendering.write_result_frames(engine, None, est, opt, gt, video=os.path.join(result_dir(self.video, data_id), "frames.avi"), **clip)
+            rendering.write_result_frames(engine, None, est, opt, gt, video=os.path.join(result_dir(self.video, data_id), "frames.avi"), **clip,
+                                          **extra)
         if self.video_camera is not None:
             rendering.write_result_camera_frames(engine, None, est, opt, cams[frames], heat[frames], gt,
                                                  video=os.path.join(result_dir(self.video_camera, data_id), "camera.avi"), **clip)
+        return found
 
 
 def result_pose_dict(est, opt, mid, gt, smooth):

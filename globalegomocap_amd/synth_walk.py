@@ -59,6 +59,7 @@ def walk(n_frames, scale=1.0, fps=25.0, stance=14, step=10, speed=1.2, stand=(),
       depth [n,15]    |local|, the joints' distances from the camera
       rows [n,8]      the SLAM trajectory `time tx ty tz qx qy qz qw` (time = frame id / fps), frame_ids [n]
       standing [n,2]  whether the foot stands (is stationary) in that frame
+      world [n,15,3]  the joints in the world, without noise: a standing foot's joints hold the same doubles frame after frame
     step: a foot lands every `step` frames, the right one at the even multiples; stance: it then stands for frames
     [m step, m step + stance], both ends included (step <= stance < 2 step: both feet stand for stance - step frames in between),
     so that of any two frames no more than stance - step + 1 apart one foot stands in both; speed: metres per second, a number or one
@@ -130,7 +131,7 @@ def walk(n_frames, scale=1.0, fps=25.0, stance=14, step=10, speed=1.2, stand=(),
     ids = np.arange(n, dtype=np.int64) + int(first_id)
     rows = np.concatenate([(ids / fps)[:, None], head[cut] @ Q.T / scale + np.asarray(world_offset, dtype=np.float64), _quat_xyzw(Q @ R[cut])], 1)
     return {"feet": feet[cut], "head": head[cut], "cams": cams, "local": local, "depth": np.sqrt((local * local).sum(-1)), "rows": rows,
-            "frame_ids": ids, "standing": standing[cut], "scale": float(scale), "fps": float(fps), "stance": S, "step": P}
+            "frame_ids": ids, "standing": standing[cut], "world": world[cut], "scale": float(scale), "fps": float(fps), "stance": S, "step": P}
 
 
 def slam_inputs(w, lo=0, hi=None):

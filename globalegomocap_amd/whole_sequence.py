@@ -306,11 +306,14 @@ def _settings(camera_model_path, vae_weight=0.0, gmm_weight=0.0, smoothness_weig
               reproj_weight=0.01, final_smooth=True, merge=True, global_vae_path=GLOBAL_VAE_PATH, local_vae_path=LOCAL_VAE_PATH,
               chunks_per_batch=None, optimizer=None, device_metrics=True, verbose=True, seq_len=SEQ_LEN, overlap=OVERLAP, timings=None,
               per_sequence=False, ground_truth=True, save_pose=None, save=False, mesh_root="out", render=None, render_camera=None, bvh=None,
-              bvh_fps=None, *, video=None, video_camera=None, video_fps=None, video_quality=None):
+              bvh_fps=None, *, video=None, video_camera=None, video_fps=None, video_quality=None, upright=False, foot_height=None):
     """The arguments of `optimize_sequences` / `optimize_recordings` behind the sequences themselves, as one object; `outputs`: the
-    files asked for (`report.Outputs`, checked here).  The clip arguments go by keyword only.
+    files asked for (`report.Outputs`, checked here).  The clip arguments and `upright` / `foot_height` go by keyword only.
     (`gmm_weight` and `merge` are accepted and unused, as in the reference: SURVEY D4.)"""
-    outputs = Outputs(mesh_root if save else None, render, render_camera, bvh, bvh_fps, video, video_camera, video_fps, video_quality)
+    if foot_height is not None and not np.isfinite(foot_height):
+        raise ValueError("foot_height must be a finite number of metres, got %r" % (foot_height,))
+    outputs = Outputs(mesh_root if save else None, render, render_camera, bvh, bvh_fps, video, video_camera, video_fps, video_quality,
+                      upright if upright else None, foot_height if upright else None)
     outputs.check()
     if not ground_truth and not device_metrics:
         raise ValueError("ground_truth=False: the report without ground truth is computed on the device only (device_metrics=True)")
@@ -512,7 +515,11 @@ class _Pipeline:
             for ci, (src, r) in enumerate(zip(b.sources, reports)):
                 if r is not None:
                     name = os.path.normpath(src.name)
-                    cfg.outputs.write(e, name, r.sequences(), view_cams, view_heat, int(b.frame_lo[ci]))
+                    found = cfg.outputs.write(e, name, r.sequences(), view_cams, view_heat, int(b.frame_lo[ci]))
+                    if found is not None:          # (--upright: the chunk's ground record, beside its errors)
+                        r.result["ground"] = found.as_dict()
+                        if cfg.verbose:
+                            print("{}: {}".format(src.name, found.line()))
                     r.drop_views()          # (they alias this batch's slot, which batch k+3 fills again)
                     self.reports[src.group].append(r)
                     if cfg.save_pose is not None:
@@ -565,7 +572,7 @@ def optimize_sequences(data_dirs, camera_model_path, *args, **kwargs):
     Further arguments, positional or by keyword, in this order (defaults: `_settings`): vae_weight, gmm_weight, smoothness_weight,
     bone_length_weight, weight_3d, reproj_weight, final_smooth, merge, global_vae_path, local_vae_path, chunks_per_batch, optimizer,
     device_metrics, verbose, seq_len, overlap, timings, per_sequence, ground_truth, save_pose, save, mesh_root, render, render_camera,
-    bvh, bvh_fps; and by keyword only: video, video_camera, video_fps, video_quality.
+    bvh, bvh_fps; and by keyword only: video, video_camera, video_fps, video_quality, upright, foot_height.
 
     ground_truth=False: the chunks carry no ground truth (`prepare` with a scale).  Their pickles are not asked for
     `gt_global_skeleton`, every chunk's report is the seven entries of QUALITY_KEYS (`WindowEngine.sequence_quality` on the estimated
@@ -591,7 +598,11 @@ def optimize_sequences(data_dirs, camera_model_path, *args, **kwargs):
     video=DIR: every chunk's frames -- the view and overlay of `render`, without the overviews -- as one Motion-JPEG clip,
     `DIR/<dataset>/<chunk>/frames.avi`; video_camera=DIR: the images of `render_camera` as `.../camera.avi`.  Neither needs the PNG
     option: without it no PNG file is written.  Both play at `video_fps` frames per second (default 25) and are encoded on the device
-    at JPEG quality `video_quality` (default 90; `report.Outputs`).  Results and reports do not depend on them."""
+    at JPEG quality `video_quality` (default 90; `report.Outputs`).  Results and reports do not depend on them.
+    upright=True: the meshes, frames, clip and BVH files of every chunk stand upright on the ground estimated from the chunk's foot
+    contacts -- Y up, the floor at 0, the wearer at the origin facing +Z in the first frame -- (`ground.estimate_ground`, DESIGN.md
+    section 6m; foot_height: metres a standing foot point lies above the floor, default 0).  Every chunk's report dict then has the
+    entry `ground` (`GroundEstimate.as_dict`), and one line per chunk is printed; the summary does not change."""
     cfg = _settings(camera_model_path, *args, **kwargs)
     lap = Laps(cfg.timings, log=True)          # developer timing (tools/whole_sequence_timing.py): wall time of the main thread's phases
     groups = []
@@ -670,6 +681,9 @@ def _parser():
     p.add_argument("--video_camera", default=None, metavar="DIR", help="write every chunk as its camera saw it as one clip, DIR/<dataset>/<chunk>/camera.avi")
     p.add_argument("--video_fps", default=None, type=float, metavar="F", help="frames per second of the clips (default 25)")
     p.add_argument("--video_quality", default=None, type=int, metavar="Q", help="JPEG quality of the clips, 1 .. 100 (default 90)")
+    p.add_argument("--upright", default=False, type=truthy,
+                   help="true: the meshes, frames, clip and BVH files stand upright on the ground estimated from every chunk's foot contacts")
+    p.add_argument("--foot_height", default=None, type=float, metavar="M", help="with --upright true: metres a standing foot point lies above the floor (default 0)")
     p.add_argument("--final_smooth", default=True, type=truthy)
     p.add_argument("--merge", default=True, type=truthy)
     p.add_argument("--chunks_per_batch", type=int, default=None, help="chunks optimised per device call (default: all)")
@@ -688,7 +702,8 @@ def _cli(argv=None):
     optimize_directory(a.data_path, a.camera, a.vae, a.gmm, a.smooth, a.bone_length, a.weight_3d, a.reproj_weight,
                        final_smooth=a.final_smooth, merge=a.merge, chunks_per_batch=a.chunks_per_batch, ground_truth=a.ground_truth,
                        save_pose=a.save_pose, save=a.save, mesh_root=a.mesh_root, render=a.render, render_camera=a.render_camera, bvh=a.bvh,
-                       bvh_fps=a.bvh_fps, video=a.video, video_camera=a.video_camera, video_fps=a.video_fps, video_quality=a.video_quality)
+                       bvh_fps=a.bvh_fps, video=a.video, video_camera=a.video_camera, video_fps=a.video_fps, video_quality=a.video_quality,
+                       **(dict(upright=True, foot_height=a.foot_height) if a.upright else {}))
 
 
 if __name__ == "__main__":

@@ -803,6 +803,58 @@ int gem_slam_scale(const int64_t* h_chunks, const int64_t* d_chunks, int n_chunk
                    const double* d_trans, const int64_t* d_ids, int64_t n_frames, int lag, double tau, int min_pairs, void* d_work,
                    int64_t work_bytes, double* d_report, double* d_costs, double* h_report, void* stream);
 
+/* ---- The ground plane of a pose sequence from its foot contacts, and the upright frame: `--upright` ----
+ * A foot that stands does not move, and the places where the feet stand lie on the floor.  With q[f,side] = (x[f,ankle] + x[f,foot]) / 2
+ * (right: joints 9 and 10, left: 13 and 14), foot point (f, side) is a candidate when f + lag < n_frames and
+ * |q[f+lag,side] - q[f,side]| < tau_v.  Body up u0 = normalise(sum_f (x[f,0] - (q[f,0] + q[f,1]) / 2)).  The plane n . p = d: centroid
+ * and scatter of the candidates, n the singular vector of the scatter's smallest singular value with n . u0 >= 0, d = n . centroid;
+ * four rounds of refit on the candidates with |n . p - d| < tau_h; a round with fewer than min_points of them ends the fit.
+ * source PLANE: every round had min_points inliers and sqrt(middle eigenvalue of the last scatter) >= min_spread.  BODY_NORMAL: the
+ * candidates span no plane: n = u0, d the candidates' height along u0, from their lower median by four rounds of refit within tau_h.
+ * BODY: fewer than min_points candidates: n = u0, d the lowest foot point's height.  The foot figures at the final (n, d), over all
+ * frames: h = n . q - d; a foot point is in contact when it is a candidate and |h| < tau_h; skate: the mean displacement, without its
+ * part along n, between frames f and f + 1 of a foot in contact in both (metres per frame, 0 without such a pair); penetration =
+ * max(0, -min h); lift_max = max h.  The upright transform crt = (c = 1, R row-major, t), p -> c * (p . R) + t for row vectors as
+ * gem_sequence_align writes it: the columns of R are X (left hip - right hip of frame 0, made level; the most nearly level world
+ * axis if that is shorter than 1e-6), Y = n and Z = X x Y ("forward"), det R = +1; t puts frame 0's hip midpoint on x = z = 0 and
+ * the plane n . p = d - foot_height on y = 0.  Everything is float64, every sum has a fixed order, there are no floating-point
+ * atomics: two calls give the same bytes. */
+#define GEM_GROUND_RECORD_DOUBLES 48
+#define GEM_GROUND_LDS_FRAMES 1024        /* a longer sequence keeps its foot points in d_work */
+#define GEM_GROUND_NO_BODY 2              /* |sum_f (neck - feet)| < 1e-6 n_frames, or a joint that is no number */
+#define GEM_GROUND_BAD_SEQUENCE 3         /* the table's row: no or a misaligned address, frames outside 1 .. 2^24 */
+#define GEM_GROUND_SOURCE_PLANE 0
+#define GEM_GROUND_SOURCE_BODY_NORMAL 1
+#define GEM_GROUND_SOURCE_BODY 2
+typedef struct gem_ground_record {
+    double status, source;                          /* 0 or GEM_GROUND_NO_BODY / GEM_GROUND_BAD_SEQUENCE; GEM_GROUND_SOURCE_* */
+    double n[3], d, u0[3], tilt_cos;                /* the plane, body up, n . u0 */
+    double points, inliers, rms, spread, extent;    /* candidates; inliers and their residual RMS at the final plane; sqrt of the last scatter's middle and largest eigenvalue */
+    double contact_right, contact_left;             /* frames in contact */
+    double skate, penetration, lift_max, skate_pairs;
+    double frames, lag;
+    double crt[13];
+    double reserved[12];
+} gem_ground_record;
+
+/* h_frames [n_sequences] -> h_offsets [n_sequences] (or NULL): where in d_work, in doubles, a sequence of more than
+ * GEM_GROUND_LDS_FRAMES frames keeps its foot points, -1 for the others.  Returns the bytes of d_work a call needs (0: none), -1 with the
+ * reason in gem_last_error for a bad argument.  Needs no GPU. */
+int64_t gem_ground_plane_work(const int64_t* h_frames, int n_sequences, int64_t* h_offsets);
+
+/* h_table (host) and d_table (the same numbers on the device), [4 n_sequences] int64: the device addresses of the sequences, each a
+ * [frames,15,3] float64 array of its own; their frame counts; per sequence the device address of a (c, R, t) [13] that is applied to
+ * the joints first, or 0; the work offsets of gem_ground_plane_work.  d_records [n_sequences] gem_ground_record.  The call's own
+ * arguments are checked before the launch -- an empty table is an error, no grid of zero workgroups is launched --; a row of the
+ * table that cannot be used sets its own record's status and leaves the other rows alone.  One launch on `stream`, no
+ * synchronisation.  Works on the current device. */
+int gem_ground_plane(const int64_t* h_table, const int64_t* d_table, int n_sequences, int lag, double tau_v, double tau_h, double min_spread,
+                     int min_points, double foot_height, double* d_work, int64_t work_bytes, double* d_records, void* stream);
+
+/* n records (c, R, t) [13] each: d_out = a, then b, that is c = c_a c_b, R = R_a R_b, t = c_b (t_a . R_b) + t_b.  d_out may be d_a or
+ * d_b. */
+int gem_similarity_compose(const double* d_a, const double* d_b, double* d_out, int64_t n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
