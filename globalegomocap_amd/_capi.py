@@ -101,6 +101,16 @@ GROUND_NO_BODY, GROUND_BAD_SEQUENCE = 2, 3
 GROUND_SOURCES = ("plane", "body_normal", "body")
 
 
+class GemFootLockRecord(C.Structure):
+    _fields_ = [(k, C.c_double) for k in ("status", "runs_right", "runs_left", "pinned_right", "pinned_left", "changed", "lengthened", "unreachable",
+                                          "delta_max", "delta_mean", "knee_max", "stretch_max", "slide_before", "slide_after", "slide_pairs",
+                                          "frames")] + [("reserved", C.c_double * 8)]
+
+
+FOOT_LOCK_RECORD_DOUBLES = 24
+FOOT_LOCK_NO_CONTACT, FOOT_LOCK_BAD_GROUND, FOOT_LOCK_BAD_SEQUENCE = 2, 3, 4
+
+
 class GemWindowStats(C.Structure):
     _fields_ = [("n_iter", C.c_int32), ("func_evals", C.c_int32), ("final_loss", C.c_float), ("status", C.c_int32)]
 
@@ -203,6 +213,8 @@ SIGNATURES = {
     "gem_ground_plane_work": (C.c_int64, [_P, C.c_int, _P]),
     "gem_ground_plane": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, C.c_double, _P, C.c_int64, _P, _P]),
     "gem_similarity_compose": (C.c_int, [_P, _P, _P, C.c_int64, _P]),
+    "gem_foot_lock_work": (C.c_int64, [_P, C.c_int, _P]),
+    "gem_foot_lock": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, C.c_double, _P, C.c_int64, _P, _P]),
 }
 
 _lib = None

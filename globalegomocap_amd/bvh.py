@@ -348,6 +348,7 @@ def main(argv=None):
     p.add_argument("--align", default=False, type=truthy, help="true: align both sequences to gt_pose first")
     p.add_argument("--unit_scale", default=100.0, type=float, help="file units per metre (100: centimetres)")
     p.add_argument("--upright", action="store_true", help="stand the files upright on the ground estimated from the foot contacts: Y up, the floor at 0")
+    p.add_argument("--foot_lock", action="store_true", help="pin the standing feet of the optimised sequence and re-solve its legs first")
     a = p.parse_args(argv)
     if not a.fps > 0:
         p.error("--fps must be positive")

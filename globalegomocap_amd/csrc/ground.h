@@ -55,6 +55,11 @@ __device__ __forceinline__ bool gr_candidate(const double* q, int i, int F, int 
     return sqrt(d0 * d0 + d1 * d1 + d2 * d2) < tau_v;
 }
 
+// whether foot point i = 2 f + side is in contact: a candidate within tau_h of the plane (n, d)
+__device__ __forceinline__ bool gr_contact(const double* q, int i, int F, int lag, double tau_v, double tau_h, const double* n, double d) {
+    return gr_candidate(q, i, F, lag, tau_v) && fabs(gr_dot(q + (size_t)i * 3, n) - d) < tau_h;
+}
+
 // the workgroup's largest value, in every thread (NaN wins); two barriers
 __device__ inline double gr_block_max(double v, double* mx) {
     const double w = wave_max_dpp(v);
@@ -237,9 +242,9 @@ __global__ __launch_bounds__(ERR_ST) void ground_plane_kernel(GroundArgs a) {
         const double* p = q + (size_t)i * 3;
         const double h = gr_dot(p, n) - d;
         hmin = h < hmin ? h : hmin; hmax = h > hmax ? h : hmax;
-        if (!(gr_candidate(q, i, F, a.lag, a.tau_v) && fabs(h) < a.tau_h)) continue;
+        if (!gr_contact(q, i, F, a.lag, a.tau_v, a.tau_h, n, d)) continue;
         fig[i & 1] += 1.0;
-        if ((i >> 1) + 1 < F && gr_candidate(q, i + 2, F, a.lag, a.tau_v) && fabs(gr_dot(p + 6, n) - d) < a.tau_h) {
+        if ((i >> 1) + 1 < F && gr_contact(q, i + 2, F, a.lag, a.tau_v, a.tau_h, n, d)) {
 #pragma clang fp contract(off)
             double v[3] = {p[6] - p[0], p[7] - p[1], p[8] - p[2]};
             const double along = gr_dot(v, n);

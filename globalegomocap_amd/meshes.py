@@ -201,7 +201,8 @@ def write_result_meshes(engine, out_dir, estimated, optimized, gt=None, align=No
 def result_poses(p, a, why_a_device):
     """What the command lines of `meshes`, `render` and `bvh` do behind their parser `p`: `a.pose_pickle` loaded and checked (with
     `a.align`: it has a gt_pose), a device found and an engine made -> (engine, a.out, estimated, optimised, ground truth or None),
-    the leading arguments of a `write_result_*`."""
+    the leading arguments of a `write_result_*`.  With `a.foot_lock` the optimised sequence is its foot-locked version
+    (`foot_lock.lock_feet` at its defaults; the estimate's frame rate is `a.fps` where the parser has one)."""
     with open(a.pose_pickle, "rb") as f:
         d = pickle.load(f)
     for key in ("estimated_pose", "optimized_pose"):
@@ -215,8 +216,13 @@ def result_poses(p, a, why_a_device):
     import torch
     if not torch.cuda.is_available():
         raise _capi.GemError("no HIP device visible: " + why_a_device)
-    return (_lift_engine(DEFAULT_CALIBRATION, torch.cuda.current_device()), a.out, np.asarray(d["estimated_pose"]),
-            np.asarray(d["optimized_pose"]), None if gt is None else np.asarray(gt))
+    engine, optimized = _lift_engine(DEFAULT_CALIBRATION, torch.cuda.current_device()), np.asarray(d["optimized_pose"])
+    if getattr(a, "foot_lock", False):
+        from . import foot_lock
+        lock = foot_lock.lock_feet(engine, optimized, **({"fps": a.fps} if getattr(a, "fps", None) else {}))
+        print(lock.line())
+        optimized = lock.sequence
+    return engine, a.out, np.asarray(d["estimated_pose"]), optimized, None if gt is None else np.asarray(gt)
 
 
 def main(argv=None):
@@ -227,6 +233,7 @@ def main(argv=None):
     p.add_argument("--out", required=True, metavar="DIR")
     p.add_argument("--align", default=False, type=truthy, help="true: align both sequences to gt_pose first (the reference's --save)")
     p.add_argument("--upright", action="store_true", help="stand the meshes upright on the ground estimated from the foot contacts")
+    p.add_argument("--foot_lock", action="store_true", help="pin the standing feet of the optimised sequence and re-solve its legs first")
     a = p.parse_args(argv)
     n = write_result_meshes(*result_poses(p, a, "the meshes are built on the device"), align=a.align, upright=a.upright or None)
     print("{} meshes written under {}".format(n, a.out))

@@ -190,7 +190,8 @@ class SequenceOptimizer:
 def main(data_id, camera_model_path, vae_weight, gmm_weight, smoothness_weight, bone_length_weight, weight_3d,
          reproj_weight, visualization=False, final_smooth=False, merge=True, save=False, save_pose=False,
          global_vae_path=GLOBAL_VAE_PATH, local_vae_path=LOCAL_VAE_PATH, eps=None, optimizer=None, return_stats=False,
-         device_metrics=False, mesh_root="out", render=None, render_camera=None, bvh=None, bvh_fps=None, *, upright=False, foot_height=None):
+         device_metrics=False, mesh_root="out", render=None, render_camera=None, bvh=None, bvh_fps=None, *, upright=False, foot_height=None,
+         foot_lock=False, foot_lock_stretch=None, foot_lock_blend=None):
     """pickle in, poses out -- the reference's `main` (optimizer.py:311-507) for one chunk directory.
 
     Returns (errors OrderedDict[18], final_estimated_seq, mid_local_pose_seq, final_optimized_seq, final_gt_seq): lists of [15,3]
@@ -208,6 +209,10 @@ def main(data_id, camera_model_path, vae_weight, gmm_weight, smoothness_weight, 
     upright=True (keyword only, with foot_height): the meshes, frames and BVH files stand upright on the ground estimated from the
     chunk's foot contacts (`ground.estimate_ground`); the errors then have the entry `ground`
     (`GroundEstimate.as_dict`) and its line is printed.
+    foot_lock=True (keyword only, with foot_lock_stretch and foot_lock_blend): the meshes, frames and BVH files show the optimised
+    sequence with its standing feet pinned to the floor and the legs re-solved (`foot_lock.lock_feet`); the
+    errors then have the entry `foot_lock` (`FootLock.as_dict`), its line is printed, and with save_pose result_pose.pkl holds
+    `foot_locked_pose`.  The returned poses and the 18 errors are those of the optimiser's own sequence.
     """
     if visualization:
         raise NotImplementedError("visualization opens open3d's viewer (optimizer.py:452-467), which this package does not have: "
@@ -243,23 +248,29 @@ def main(data_id, camera_model_path, vae_weight, gmm_weight, smoothness_weight, 
     if final_smooth is True and not device_metrics:
         from .sequence import final_smooth as _smooth
         final_optimized_seq = _smooth(final_optimized_seq)
+    outputs = Outputs(mesh_root if save else None, render, render_camera, bvh, bvh_fps, upright=upright if upright else None,
+                      upright_foot_height=foot_height if upright else None,
+                      **(dict(foot_lock=True, foot_lock_stretch=foot_lock_stretch, foot_lock_blend=foot_lock_blend) if foot_lock else {}))
+    lock = outputs.lock(opt.engine, final_optimized_d if device_metrics else np.asarray(final_optimized_seq))          # (None without foot_lock)
     if save_pose:
         # optimizer.py:469-483: out/<dataset>/<sequence>/result_pose.pkl under the working directory
         out_dir = result_dir("out", data_id)
         os.makedirs(out_dir, exist_ok=True)
         with open(os.path.join(out_dir, "result_pose.pkl"), "wb") as f:
-            pickle.dump(result_pose_dict(final_estimated_seq, final_optimized_seq, mid_estimated_seq, final_gt_seq, final_smooth is True), f)
-    outputs = Outputs(mesh_root if save else None, render, render_camera, bvh, bvh_fps, upright=upright if upright else None,
-                      upright_foot_height=foot_height if upright else None)
+            pickle.dump(result_pose_dict(final_estimated_seq, final_optimized_seq, mid_estimated_seq, final_gt_seq, final_smooth is True,
+                                         **({} if lock is None else {"locked": lock.sequence.cpu().numpy()})), f)
     found = None
     if outputs:
         sequences = (np.asarray(final_estimated_seq), final_optimized_d if device_metrics else np.asarray(final_optimized_seq),
                      np.asarray(final_gt_seq))
-        found = outputs.write(opt.engine, data_id, sequences, cams, heat)
+        found = outputs.write(opt.engine, data_id, sequences, cams, heat, **({} if lock is None else {"locked": lock}))
     if device_metrics:
         errors = opt.engine.calculate_errors(final_estimated_seq, mid_estimated_seq, final_optimized_d, final_gt_seq)
     else:
         errors = calculate_errors(final_estimated_seq, mid_estimated_seq, final_optimized_seq, final_gt_seq)
+    if lock is not None:
+        errors["foot_lock"] = lock.as_dict()
+        print("{}: {}".format(data_id, lock.line()))
     if found is not None:
         errors["ground"] = found.as_dict()
         print("{}: {}".format(data_id, found.line()))

@@ -464,6 +464,7 @@ def main(argv=None):
     p.add_argument("--video_quality", default=DEFAULT_QUALITY, type=int, metavar="Q", help="JPEG quality of the clip, 1 .. 100 (default 90)")
     p.add_argument("--no_frames", action="store_true", help="with --video: the clip only, no PNG files")
     p.add_argument("--upright", action="store_true", help="draw the sequences upright on the ground estimated from the foot contacts (not with --camera)")
+    p.add_argument("--foot_lock", action="store_true", help="pin the standing feet of the optimised sequence and re-solve its legs first (not with --camera)")
     a = p.parse_args(argv)
     if not a.video_fps > 0:
         p.error("argument --video_fps: must be positive")
@@ -477,6 +478,8 @@ def main(argv=None):
         p.error("argument --size: a size is WIDTHxHEIGHT, for instance 640x480; got %r" % str(a.size))
     if a.camera is not None and a.upright:
         p.error("--upright: the camera's view is the camera's own image and is not stood upright")
+    if a.camera is not None and a.foot_lock:
+        p.error("--foot_lock: the camera's view shows the optimiser's own result")
     if a.camera is not None:
         if isinstance(a.size, tuple) or (a.size is not None and a.size > 1024):
             p.error("argument --size: with --camera a size is one number of pixels 1 .. 1024")

@@ -185,7 +185,8 @@ def sequence_result(reports, title, verbose):
     results, raw = [r.result for r in reports], [r.raw for r in reports]
     ground_truth = not reports or reports[0].gt is not None
     summary = OrderedDict()
-    keys = [k for k in results[0] if k != "ground"] if reports else []          # (`ground`: a chunk's ground record, with --upright; no number to average)
+    # (`ground`, `foot_lock`: a chunk's ground record with --upright and its foot-lock record with --foot_lock; no numbers to average)
+    keys = [k for k in results[0] if k not in ("ground", "foot_lock")] if reports else []
     if reports and all(x is not None for x in raw):          # (every chunk of the sequence came as a row of the device report: one mean)
         mean = np.mean(np.stack(raw), axis=0)
         for i, k in enumerate(keys):
@@ -234,7 +235,13 @@ class Outputs:
                      its foot contacts: from the ground truth where there is one (the other sequences are
                      aligned to it), else from the optimised sequence; `upright_foot_height`: metres a standing foot point lies above
                      the floor (default 0), `upright_lag`: frames between the two frames of a still pair (default 0.2 s at `bvh_fps`).
-                     The camera's views are the camera's own images and take no part."""
+                     The camera's views are the camera's own images and take no part.
+      foot_lock      True: the optimised sequence is replaced by its foot-locked version (`foot_lock.lock_feet`, DESIGN.md section 6n:
+                     standing feet pinned to the floor, the legs by two-bone inverse kinematics) for the meshes, frames, clip and BVH
+                     files; the estimated sequence stays as it is, the "before".  `foot_lock_stretch`: how much longer a straight leg may
+                     become to hold its pin (default 0.05); `foot_lock_blend`: frames over which a correction is eased in and out (default
+                     0.12 s at `bvh_fps`); the contact rule's lag is `upright_lag`.  Ground truth, alignment and `upright` work as before,
+                     on the locked sequence."""
     mesh_root: object = None
     render: object = None
     render_camera: object = None
@@ -244,6 +251,9 @@ class Outputs:
     video_camera: object = None
     video_fps: object = None
     video_quality: object = None
+    foot_lock: object = None
+    foot_lock_stretch: object = None
+    foot_lock_blend: object = None
     upright: object = None
     upright_foot_height: object = None
     upright_lag: object = None
@@ -266,13 +276,26 @@ class Outputs:
         if self.video is not None or self.video_camera is not None:
             clips.check_options(*self._rates()[1:])
 
-    def write(self, engine, data_id, sequences, cams=None, heat=None, first_frame=0):
+    def lock(self, engine, optimized):
+        """The chunk's `foot_lock.FootLock` of its optimised sequence with this record's options, or None without `foot_lock`."""
+        if not self.foot_lock:
+            return None
+        from . import foot_lock
+        return foot_lock.lock_feet(engine, optimized, fps=self._rates()[0], lag=self.upright_lag, blend=self.foot_lock_blend,
+                                   stretch=foot_lock.STRETCH if self.foot_lock_stretch is None else self.foot_lock_stretch)
+
+    def write(self, engine, data_id, sequences, cams=None, heat=None, first_frame=0, locked=None):
         """One chunk's output files from `sequences` = (estimated, optimised, ground truth or None), host arrays or device tensors.
         `cams` / `heat` (`needs_frames`) hold the chunk's frames from `first_frame` on; merged frame f is the chunk's frame f.  With
         a ground truth the estimated and the optimised sequence are aligned to it and all three are written, as in the reference;
-        without, nothing is aligned and there is no third sequence.  -> the chunk's `ground.GroundEstimate` with `upright`, else None."""
+        without, nothing is aligned and there is no third sequence.  With `foot_lock` the optimised sequence is replaced by its locked
+        version for every file but the camera's views (`locked`: the chunk's FootLock where the caller has made it with `lock`, else
+        it is made here, once).  -> the chunk's `ground.GroundEstimate` with `upright`, else None."""
         est, opt, gt = sequences
         bvh_fps, video_fps, video_quality = self._rates()
+        shown = opt          # (the camera's views show the optimiser's own result)
+        if self.foot_lock and any(r is not None for r in (self.mesh_root, self.render, self.bvh, self.video)):
+            opt = (self.lock(engine, opt) if locked is None else locked).sequence
         clip = dict(video_fps=video_fps, video_quality=video_quality, frames=False)
         frames = slice(first_frame, first_frame + len(est))
         found, extra = None, {}
@@ -287,22 +310,25 @@ class Outputs:
         if self.render is not None:
             rendering.write_result_frames(engine, result_dir(self.render, data_id), est, opt, gt, **extra)
         if self.render_camera is not None:
-            rendering.write_result_camera_frames(engine, result_dir(self.render_camera, data_id), est, opt, cams[frames], heat[frames], gt)
+            rendering.write_result_camera_frames(engine, result_dir(self.render_camera, data_id), est, shown, cams[frames], heat[frames], gt)
         if self.bvh is not None:
             animation.write_result_bvh(engine, result_dir(self.bvh, data_id), est, opt, gt, fps=bvh_fps, **extra)
         if self.video is not None:
             rendering.write_result_frames(engine, None, est, opt, gt, video=os.path.join(result_dir(self.video, data_id), "frames.avi"), **clip,
                                           **extra)
         if self.video_camera is not None:
-            rendering.write_result_camera_frames(engine, None, est, opt, cams[frames], heat[frames], gt,
+            rendering.write_result_camera_frames(engine, None, est, shown, cams[frames], heat[frames], gt,
                                                  video=os.path.join(result_dir(self.video_camera, data_id), "camera.avi"), **clip)
         return found
 
 
-def result_pose_dict(est, opt, mid, gt, smooth):
+def result_pose_dict(est, opt, mid, gt, smooth, locked=None):
     """What `result_pose.pkl` holds, in the reference's keys and containers (optimizer.py:469-483): merge_batches' lists of [15,3]
-    frames; the optimised sequence an ndarray after the final smoothing (`smooth`); `gt_pose` only where there is a ground truth."""
+    frames; the optimised sequence an ndarray after the final smoothing (`smooth`); `gt_pose` only where there is a ground truth;
+    `foot_locked_pose`, in the container of `optimized_pose`, only with `locked` (--foot_lock)."""
     d = {"estimated_pose": list(est), "optimized_pose": np.asarray(opt) if smooth else list(np.asarray(opt)), "mid_optimized_pose": list(mid)}
     if gt is not None:
         d["gt_pose"] = list(gt)
+    if locked is not None:
+        d["foot_locked_pose"] = np.asarray(locked) if smooth else list(np.asarray(locked))
     return d

@@ -252,11 +252,12 @@ def _resident_chunk(c, ground_truth=True):
     return p
 
 
-def _save_pose(out_dir, report, smooth):
-    """`<out_dir>/result_pose.pkl` of one chunk (`report.result_pose_dict`)."""
+def _save_pose(out_dir, report, smooth, locked=None):
+    """`<out_dir>/result_pose.pkl` of one chunk (`report.result_pose_dict`); locked: the chunk's foot-locked sequence, with --foot_lock."""
     os.makedirs(out_dir, exist_ok=True)
+    extra = {} if locked is None else {"locked": locked}
     with open(os.path.join(out_dir, "result_pose.pkl"), "wb") as f:
-        pickle.dump(result_pose_dict(report.est, report.opt, report.mid, report.gt, smooth), f)
+        pickle.dump(result_pose_dict(report.est, report.opt, report.mid, report.gt, smooth, **extra), f)
 
 
 # ------------------------------------------------------------------------------------------------------------------ the batch pipeline
@@ -306,14 +307,21 @@ def _settings(camera_model_path, vae_weight=0.0, gmm_weight=0.0, smoothness_weig
               reproj_weight=0.01, final_smooth=True, merge=True, global_vae_path=GLOBAL_VAE_PATH, local_vae_path=LOCAL_VAE_PATH,
               chunks_per_batch=None, optimizer=None, device_metrics=True, verbose=True, seq_len=SEQ_LEN, overlap=OVERLAP, timings=None,
               per_sequence=False, ground_truth=True, save_pose=None, save=False, mesh_root="out", render=None, render_camera=None, bvh=None,
-              bvh_fps=None, *, video=None, video_camera=None, video_fps=None, video_quality=None, upright=False, foot_height=None):
+              bvh_fps=None, *, video=None, video_camera=None, video_fps=None, video_quality=None, upright=False, foot_height=None,
+              foot_lock=False, foot_lock_stretch=None, foot_lock_blend=None):
     """The arguments of `optimize_sequences` / `optimize_recordings` behind the sequences themselves, as one object; `outputs`: the
-    files asked for (`report.Outputs`, checked here).  The clip arguments and `upright` / `foot_height` go by keyword only.
+    files asked for (`report.Outputs`, checked here).  The clip arguments, `upright` / `foot_height` and `foot_lock` with its two
+    options go by keyword only.
     (`gmm_weight` and `merge` are accepted and unused, as in the reference: SURVEY D4.)"""
     if foot_height is not None and not np.isfinite(foot_height):
         raise ValueError("foot_height must be a finite number of metres, got %r" % (foot_height,))
+    if foot_lock_stretch is not None and not (np.isfinite(foot_lock_stretch) and foot_lock_stretch >= 0):
+        raise ValueError("foot_lock_stretch must be a finite number that is not negative, got %r" % (foot_lock_stretch,))
+    if foot_lock_blend is not None and not foot_lock_blend >= 1:
+        raise ValueError("foot_lock_blend must be at least one frame, got %r" % (foot_lock_blend,))
     outputs = Outputs(mesh_root if save else None, render, render_camera, bvh, bvh_fps, video, video_camera, video_fps, video_quality,
-                      upright if upright else None, foot_height if upright else None)
+                      upright=upright if upright else None, upright_foot_height=foot_height if upright else None,
+                      **(dict(foot_lock=True, foot_lock_stretch=foot_lock_stretch, foot_lock_blend=foot_lock_blend) if foot_lock else {}))
     outputs.check()
     if not ground_truth and not device_metrics:
         raise ValueError("ground_truth=False: the report without ground truth is computed on the device only (device_metrics=True)")
@@ -515,7 +523,12 @@ class _Pipeline:
             for ci, (src, r) in enumerate(zip(b.sources, reports)):
                 if r is not None:
                     name = os.path.normpath(src.name)
-                    found = cfg.outputs.write(e, name, r.sequences(), view_cams, view_heat, int(b.frame_lo[ci]))
+                    lock = cfg.outputs.lock(e, r.sequences()[1])          # (--foot_lock: None without it)
+                    found = cfg.outputs.write(e, name, r.sequences(), view_cams, view_heat, int(b.frame_lo[ci]), **({} if lock is None else {"locked": lock}))
+                    if lock is not None:          # (the chunk's foot-lock record, beside its errors)
+                        r.result["foot_lock"] = lock.as_dict()
+                        if cfg.verbose:
+                            print("{}: {}".format(src.name, lock.line()))
                     if found is not None:          # (--upright: the chunk's ground record, beside its errors)
                         r.result["ground"] = found.as_dict()
                         if cfg.verbose:
@@ -523,7 +536,8 @@ class _Pipeline:
                     r.drop_views()          # (they alias this batch's slot, which batch k+3 fills again)
                     self.reports[src.group].append(r)
                     if cfg.save_pose is not None:
-                        _save_pose(os.path.join(cfg.save_pose, os.path.basename(name)), r, bool(cfg.final_smooth))
+                        _save_pose(os.path.join(cfg.save_pose, os.path.basename(name)), r, bool(cfg.final_smooth),
+                                   **({} if lock is None else {"locked": lock.sequence.cpu().numpy()}))
                     if cfg.ground_truth and cfg.verbose and \
                             r.result["bone_length_aligned_optimized_mpjpe"] > r.result["bone_length_aligned_mid_optimized_mpjpe"]:
                         print(r.result)
@@ -572,7 +586,8 @@ def optimize_sequences(data_dirs, camera_model_path, *args, **kwargs):
     Further arguments, positional or by keyword, in this order (defaults: `_settings`): vae_weight, gmm_weight, smoothness_weight,
     bone_length_weight, weight_3d, reproj_weight, final_smooth, merge, global_vae_path, local_vae_path, chunks_per_batch, optimizer,
     device_metrics, verbose, seq_len, overlap, timings, per_sequence, ground_truth, save_pose, save, mesh_root, render, render_camera,
-    bvh, bvh_fps; and by keyword only: video, video_camera, video_fps, video_quality, upright, foot_height.
+    bvh, bvh_fps; and by keyword only: video, video_camera, video_fps, video_quality, upright, foot_height, foot_lock,
+    foot_lock_stretch, foot_lock_blend.
 
     ground_truth=False: the chunks carry no ground truth (`prepare` with a scale).  Their pickles are not asked for
     `gt_global_skeleton`, every chunk's report is the seven entries of QUALITY_KEYS (`WindowEngine.sequence_quality` on the estimated
@@ -602,7 +617,13 @@ def optimize_sequences(data_dirs, camera_model_path, *args, **kwargs):
     upright=True: the meshes, frames, clip and BVH files of every chunk stand upright on the ground estimated from the chunk's foot
     contacts -- Y up, the floor at 0, the wearer at the origin facing +Z in the first frame -- (`ground.estimate_ground`, DESIGN.md
     section 6m; foot_height: metres a standing foot point lies above the floor, default 0).  Every chunk's report dict then has the
-    entry `ground` (`GroundEstimate.as_dict`), and one line per chunk is printed; the summary does not change."""
+    entry `ground` (`GroundEstimate.as_dict`), and one line per chunk is printed; the summary does not change.
+    foot_lock=True: the meshes, frames, clip and BVH files show the optimised sequence with its standing feet pinned to the floor and
+    the legs re-solved by two-bone inverse kinematics (`foot_lock.lock_feet`; foot_lock_stretch: how much longer
+    a straight leg may become to hold its pin, default 0.05; foot_lock_blend: frames over which a correction is eased in and out,
+    default 0.12 s at `bvh_fps`); the estimated sequence stays as it is.  Every chunk's report dict then has the entry `foot_lock`
+    (`FootLock.as_dict`), one line per chunk is printed, and result_pose.pkl holds `foot_locked_pose`.  The returned poses, the
+    errors and the report are those of the optimiser's own sequence."""
     cfg = _settings(camera_model_path, *args, **kwargs)
     lap = Laps(cfg.timings, log=True)          # developer timing (tools/whole_sequence_timing.py): wall time of the main thread's phases
     groups = []
@@ -684,6 +705,12 @@ def _parser():
     p.add_argument("--upright", default=False, type=truthy,
                    help="true: the meshes, frames, clip and BVH files stand upright on the ground estimated from every chunk's foot contacts")
     p.add_argument("--foot_height", default=None, type=float, metavar="M", help="with --upright true: metres a standing foot point lies above the floor (default 0)")
+    p.add_argument("--foot_lock", default=False, type=truthy,
+                   help="true: the meshes, frames, clip and BVH files show the optimised sequence with its standing feet pinned and the legs re-solved")
+    p.add_argument("--foot_lock_stretch", default=None, type=float, metavar="S",
+                   help="with --foot_lock true: how much longer a straight leg may become to hold its pin (default 0.05)")
+    p.add_argument("--foot_lock_blend", default=None, type=int, metavar="FRAMES",
+                   help="with --foot_lock true: frames over which a correction is eased in and out (default: 0.12 s)")
     p.add_argument("--final_smooth", default=True, type=truthy)
     p.add_argument("--merge", default=True, type=truthy)
     p.add_argument("--chunks_per_batch", type=int, default=None, help="chunks optimised per device call (default: all)")
@@ -703,7 +730,8 @@ def _cli(argv=None):
                        final_smooth=a.final_smooth, merge=a.merge, chunks_per_batch=a.chunks_per_batch, ground_truth=a.ground_truth,
                        save_pose=a.save_pose, save=a.save, mesh_root=a.mesh_root, render=a.render, render_camera=a.render_camera, bvh=a.bvh,
                        bvh_fps=a.bvh_fps, video=a.video, video_camera=a.video_camera, video_fps=a.video_fps, video_quality=a.video_quality,
-                       **(dict(upright=True, foot_height=a.foot_height) if a.upright else {}))
+                       **(dict(upright=True, foot_height=a.foot_height) if a.upright else {}),
+                       **(dict(foot_lock=True, foot_lock_stretch=a.foot_lock_stretch, foot_lock_blend=a.foot_lock_blend) if a.foot_lock else {}))
 
 
 if __name__ == "__main__":

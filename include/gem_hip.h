@@ -855,6 +855,55 @@ int gem_ground_plane(const int64_t* h_table, const int64_t* d_table, int n_seque
  * d_b. */
 int gem_similarity_compose(const double* d_a, const double* d_b, double* d_out, int64_t n, void* stream);
 
+/* ---- Foot-skate clean-up: standing feet pinned to the floor, legs by two-bone inverse kinematics: `--foot_lock` ----
+ * With the foot points q and the contact rule of gem_ground_plane (a candidate within tau_h of the plane n . p = d, both read from the
+ * sequence's gem_ground_record on the device): a RUN is a maximal stretch of at least min_run consecutive contact frames of one foot.
+ * Its anchor a = q[s] + mean_f (q[f] - q[s]) over its frames s .. e, and with `snap` a -= (n . a - d) n unless |n . a - d| < 1e-12.
+ * The correction of a foot point: a - q[f] inside a run; outside, with k(u) = 1 - u^2 (3 - 2 u) for u < 1 and 0 beyond,
+ * (a1 - q[e]) k((f - e) / B) + (a2 - q[s]) k((s - f) / B) for the run before (last frame e, anchor a1) and the run after (first frame
+ * s, anchor a2), either of which may be absent; B = min(blend, (s - e) / 2) between two runs, blend at the sequence's ends.  A leg
+ * whose correction is not zero is re-solved from its unmoved hip h: l1 = |knee - h|, l2 = |ankle - knee|, target a' = ankle +
+ * correction, D = |a' - h|, u = (a' - h) / D.  |l1 - l2| < D < l1 + l2: c = (l1^2 - l2^2 + D^2) / (2 D), knee' = h + c u +
+ * sqrt(max(l1^2 - c^2, 0)) b and ankle' = a', b the unit part of knee - h across u (shorter than 1e-9: that of foot - ankle; that
+ * too: of the world axis most nearly across u).  D >= l1 + l2: the leg straight and lengthened by g = min(D / (l1 + l2), 1 + stretch),
+ * knee' = h + g l1 u, ankle' = h + g (l1 + l2) u; the pin is missed where D / (l1 + l2) > 1 + stretch (`unreachable`).
+ * D <= |l1 - l2|: folded on the axis, knee' = h +- l1 u, ankle' = h + |l1 - l2| u (`unreachable`).  foot' = foot + (ankle' - ankle).
+ * Only joints 8, 9, 10, 12, 13, 14 change; every other joint, and every leg whose correction is exactly zero, is copied bit for bit.
+ * Everything is float64, every sum has a fixed order, there are no floating-point atomics: two calls give the same bytes. */
+#define GEM_FOOT_LOCK_RECORD_DOUBLES 24
+#define GEM_FOOT_LOCK_NO_CONTACT 2        /* no run in the sequence: it is copied bit for bit (a result, not an error) */
+#define GEM_FOOT_LOCK_BAD_GROUND 3        /* the sequence's ground record has a status other than 0: copied */
+#define GEM_FOOT_LOCK_BAD_SEQUENCE 4      /* the table's row: no or a misaligned address, in place, frames outside 1 .. 2^24: nothing is written */
+typedef struct gem_foot_lock_record {
+    double status;                                  /* 0 or GEM_FOOT_LOCK_* */
+    double runs_right, runs_left;                   /* runs per foot */
+    double pinned_right, pinned_left;               /* frames inside a run */
+    double changed;                                 /* frames with a leg that moved */
+    double lengthened, unreachable;                 /* legs (frame and side) made straight and longer; legs whose target was missed */
+    double delta_max, delta_mean;                   /* the correction's length over the pinned foot points, metres */
+    double knee_max;                                /* the largest displacement of a knee */
+    double stretch_max;                             /* the largest g (1: no leg was lengthened) */
+    double slide_before, slide_after;               /* mean in-plane movement per frame of a foot point over the consecutive frame pairs of one run */
+    double slide_pairs, frames;
+    double reserved[8];
+} gem_foot_lock_record;
+
+/* h_frames [n_sequences] -> h_offsets [n_sequences] (or NULL): where in d_work, in doubles, a sequence keeps its run table (and, beyond
+ * GEM_GROUND_LDS_FRAMES frames, its foot points), -1 for a frame count outside 1 .. 2^24.  Returns the bytes of d_work a call needs, -1
+ * with the reason in gem_last_error for a bad argument.  Needs no GPU. */
+int64_t gem_foot_lock_work(const int64_t* h_frames, int n_sequences, int64_t* h_offsets);
+
+/* h_table (host) and d_table (the same numbers on the device), [4 n_sequences] int64: the device addresses of the sequences, each a
+ * [frames,15,3] float64 array; their frame counts; the device addresses of the outputs, arrays of the same size that do not overlap
+ * their inputs; the work offsets of gem_foot_lock_work.  d_ground_records [n_sequences] gem_ground_record, as gem_ground_plane wrote
+ * them for the same sequences with the same lag, tau_v and tau_h (no read-back in between).  d_records [n_sequences]
+ * gem_foot_lock_record.  blend: frames over which a correction is eased in and out.  The call's own arguments are checked before the
+ * launch, the argument at fault named in gem_last_error; a row that cannot be used sets its own record's status and leaves the other
+ * rows alone.  One launch on `stream`, no synchronisation.  Works on the current device. */
+int gem_foot_lock(const int64_t* h_table, const int64_t* d_table, int n_sequences, const double* d_ground_records, int lag, double tau_v,
+                  double tau_h, int min_run, int blend, int snap, double stretch, double* d_work, int64_t work_bytes, double* d_records,
+                  void* stream);
+
 #ifdef __cplusplus
 }
 #endif
