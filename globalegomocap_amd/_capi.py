@@ -111,6 +111,15 @@ FOOT_LOCK_RECORD_DOUBLES = 24
 FOOT_LOCK_NO_CONTACT, FOOT_LOCK_BAD_GROUND, FOOT_LOCK_BAD_SEQUENCE = 2, 3, 4
 
 
+class GemBridgeRecord(C.Structure):
+    _fields_ = [(k, C.c_double) for k in ("status", "frames", "lost", "gaps", "systems", "longest_gap", "offset_max", "angle_max",
+                                          "translation_max")] + [("reserved", C.c_double * 7)]
+
+
+BRIDGE_RECORD_DOUBLES, BRIDGE_MAX_GAP, BRIDGE_MAX_SPAN = 16, 64, 127
+BRIDGE_NOT_SOLVED = 2
+
+
 class GemWindowStats(C.Structure):
     _fields_ = [("n_iter", C.c_int32), ("func_evals", C.c_int32), ("final_loss", C.c_float), ("status", C.c_int32)]
 
@@ -215,6 +224,8 @@ SIGNATURES = {
     "gem_similarity_compose": (C.c_int, [_P, _P, _P, C.c_int64, _P]),
     "gem_foot_lock_work": (C.c_int64, [_P, C.c_int, _P]),
     "gem_foot_lock": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, C.c_double, _P, C.c_int64, _P, _P]),
+    "gem_slam_bridge_work": (C.c_int64, [C.c_int64]),
+    "gem_slam_bridge": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, _P, _P, C.c_int, C.c_int64, _P, _P, _P, _P, _P, C.c_int64, _P, _P]),
 }
 
 _lib = None

@@ -343,3 +343,5 @@ int gem_profile_read(gem_handle* h, int family, double* total_ms, int64_t* n_lau
 }
 
 }  // extern "C"
+
+#include "slam_bridge.h"          // gem_slam_bridge_work, gem_slam_bridge

@@ -120,15 +120,17 @@ def depths_from_mat_dir(directory, frame_ids):
 
 # ------------------------------------------------------------------------------------------------------------------ the device path
 def recording_from_detections(slam_result_path, detections, gt_path=None, scale=None, spans=(), fps=25, depth=None, sigma=1.5, first_id=0,
-                              camera_model_path=None, device=None, gt_start_frame=None, lag=None, tau=0.10, min_pairs=50):
+                              camera_model_path=None, device=None, gt_start_frame=None, lag=None, tau=0.10, min_pairs=50, bridge=None):
     """Every (start_frame, end_frame) of `spans` as one chunk of a `prepare.Recording`, from 2-D detections: `detections` is a file
     (`read_detections`), an array [N,15,2|3] or `as_detections`' dict; `depth` [N,15] unless the file carries it.  Exactly one of
     `gt_path` (the ground truth fixes the SLAM scale per chunk, as `prepare` does; entry i - gt_start_frame of the pickle is frame id
     i, gt_start_frame defaulting to the first span's start) and `scale`: a number, or "auto" to estimate it from the foot contacts of
     the filled poses (`prepare.auto_scale` with `lag`, `tau`, `min_pairs`).  One upload, then on the device:
-    lift -> fill -> heat-maps -> cameras -> gem_prepare_global."""
-    from . import prepare, slam
+    lift -> fill -> heat-maps -> cameras -> gem_prepare_global.  `bridge`: None, or the seconds of lost SLAM tracking whose cameras are
+    invented (`slam_bridge`), without ground truth only."""
+    from . import prepare, slam, slam_bridge
     scale = prepare.gt_or_scale(gt_path, scale)
+    bridge = slam_bridge.bridge_arg(bridge, gt_path)
     import torch
     from .camera import DEFAULT_CALIBRATION
     if isinstance(detections, (str, os.PathLike)):
@@ -145,8 +147,11 @@ def recording_from_detections(slam_result_path, detections, gt_path=None, scale=
     device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     with open(slam_result_path) as f:
         text = slam.trajectory_rows(f.read())
+    if bridge is not None and spans:
+        slam_bridge.find_gaps(slam.frame_ids(text, fps), *slam_bridge.contiguous_span(spans), slam_bridge.max_gap_frames(bridge, fps))
     for a, b in spans:
-        prepare.check_trajectory(text, a, b, fps)
+        if bridge is None:
+            prepare.check_trajectory(text, a, b, fps)
     rows = span_rows(det["frame_ids"], spans)
     if not spans:
         return prepare.Recording([], None if scale is None else np.empty((0, 4, 4)))
@@ -174,14 +179,23 @@ def recording_from_detections(slam_result_path, detections, gt_path=None, scale=
                 engine.fill_missing(est_local[lo:hi], valid[lo:hi], 1)
         if scale is not None:          # (a recording that does not fix the scale is refused before the heat-maps are made)
             scale_given = scale
-            scale, scale_report = prepare.auto_scale(est_local, text, spans, fps, scale, lag, tau, min_pairs)
+            bridge_report = None
+            if bridge is not None:
+                scale, scale_report, cams, origins, bridge_report = slam_bridge.recording_cameras(engine, est_local, text, spans, fps, scale, bridge,
+                                                                                                  lag, tau, min_pairs)
+            else:
+                scale, scale_report = prepare.auto_scale(est_local, text, spans, fps, scale, lag, tau, min_pairs)
         heat = engine.keypoint_heatmaps(kp_d, sigma)
         if scale is not None:
-            cams, origins = prepare.scaled_cameras(text, spans, fps, scale)
-            cams_d = torch.from_numpy(np.concatenate(cams)).to(device)
+            if bridge is not None:
+                cams_d = torch.cat(cams)
+            else:
+                cams, origins = prepare.scaled_cameras(text, spans, fps, scale)
+                cams_d = torch.from_numpy(np.concatenate(cams)).to(device)
             est_global, _ = prepare.prepare_global(est_local, cams_d, None)
             return prepare.Recording([prepare.RecordingChunk(a, b, heat[lo:hi], est_local[lo:hi], est_global[lo:hi], cams_d[lo:hi], None)
-                                      for (a, b), (lo, hi) in zip(spans, bounds)], origins, scale if scale_given == "auto" else None, scale_report)
+                                      for (a, b), (lo, hi) in zip(spans, bounds)], origins, scale if scale_given == "auto" else None, scale_report,
+                                     bridge_report)
         heads = est_local[:, 0].cpu().numpy()
         gt_all = np.concatenate([np.asarray(g, dtype=np.float64) for g in gts])
         cams = np.concatenate([slam.camera_pose_list_from_heads(text, heads[lo:hi], gt_all[lo:hi, 0], a, b, fps)[0]
@@ -209,6 +223,8 @@ def _parser():
     dep = p.add_mutually_exclusive_group()
     dep.add_argument("--depths", default=None, metavar="DIR", help="directory of per-frame depth .mat files")
     dep.add_argument("--depth", default=None, metavar="FILE.npy", help="the joints' depths [N,15], row for row with the detections")
+    p.add_argument("--bridge", nargs="?", type=float, const=1.0, default=None, metavar="SECONDS",
+                   help="with --scale: invent the cameras of stretches of lost SLAM tracking up to this long (default 1 s)")
     p.add_argument("--start", required=True, type=int)
     p.add_argument("--end", required=True, type=int)
     p.add_argument("--fps", type=float, default=25)
@@ -228,15 +244,19 @@ def _cli(argv=None):
     a = p.parse_args(argv)
     if a.out is None and not a.optimize:
         p.error("nothing to do: give --out, --optimize or both")
+    if a.bridge is not None and a.gt is not None:
+        p.error("--bridge needs --scale: with --gt every chunk has its own scale and there is no common world to bridge in")
     det = read_detections(a.keypoints, a.first_id)
     if a.depth is not None:
         det["depth"] = _depth_array(np.load(a.depth, allow_pickle=False), len(det["keypoints"]), a.depth)
     elif a.depths is not None:
         det["depth"] = depths_from_mat_dir(a.depths, det["frame_ids"])
     rec = recording_from_detections(a.slam, det, a.gt, a.scale, prepare.chunk_spans(a.start, a.end, a.test_size), a.fps, sigma=a.sigma,
-                                    camera_model_path=a.camera, gt_start_frame=a.mat_start)
+                                    camera_model_path=a.camera, gt_start_frame=a.mat_start, bridge=a.bridge)
     if rec.scale_report is not None:
         print(rec.scale_report.line())
+    if rec.bridge_report is not None:
+        print(rec.bridge_report.line())
     for c in rec.chunks:
         print("running test sequence from {} to {}".format(c.start_frame, c.end_frame))
         if c.initial_mpjpe is not None:

@@ -37,6 +37,10 @@ no `gt_global_skeleton`, and since one scale holds for the whole recording its c
 
     python -m globalegomocap_amd.prepare --slam traj.txt --heatmaps DIR --depths DIR --scale 1.0 --start 551 --end 3300 \\
         --fps 25 --out DIR [--optimize]
+
+A trajectory that lacks lines because SLAM lost tracking is still refused -- unless `--bridge [SECONDS]` (`bridge=`) is given on this
+route: the missing cameras are then invented kinematically, marked in `Recording.bridged` and accounted for in
+`Recording.bridge_report` (`slam_bridge`).
 """
 import ctypes as C
 import io
@@ -223,12 +227,22 @@ class Recording:
     """The chunks of one recording, device-resident.  `heat`, `est_local`, `est_global`, `cams`, `gt`: one tensor per chunk.
     `origins` [n_chunks,4,4] float64 (numpy) for a recording without ground truth, whose chunks share a world (`scaled_cameras`,
     `to_recording_frame`); None for a recording with ground truth.  `scale` and `scale_report` (`slam_scale.ScaleEstimate`): the SLAM
-    scale a recording prepared with scale="auto" was given and how it was found; None on the other routes."""
+    scale a recording prepared with scale="auto" was given and how it was found; None on the other routes.  `bridge_report`
+    (`slam_bridge.BridgeReport`) and `bridged` (one bool array per chunk: the frames whose camera was invented) for a recording prepared
+    with `bridge=`; None without."""
 
-    def __init__(self, chunks, origins=None, scale=None, scale_report=None):
+    def __init__(self, chunks, origins=None, scale=None, scale_report=None, bridge_report=None):
         self.chunks = list(chunks)
         self.origins = origins
         self.scale, self.scale_report = scale, scale_report
+        self.bridge_report = bridge_report
+
+    @property
+    def bridged(self):
+        if self.bridge_report is None:
+            return None
+        cuts = np.concatenate([[0], np.cumsum([c.n for c in self.chunks])])
+        return [self.bridge_report.bridged[lo:hi] for lo, hi in zip(cuts[:-1], cuts[1:])]
 
     def __len__(self):
         return len(self.chunks)
@@ -528,13 +542,17 @@ def auto_scale(est_local, rows, spans, fps, scale, lag=None, tau=0.10, min_pairs
 
 
 def prepare_spans(slam_result_path, heatmap_dir, depth_dir, gt_path, spans, fps, mat_start_frame, camera_model_path=None, device=None,
-                  timings=None, scale=None, lag=None, tau=0.10, min_pairs=50):
+                  timings=None, scale=None, lag=None, tau=0.10, min_pairs=50, bridge=None):
     """Every (start_frame, end_frame) of `spans` as one chunk, each prepared on its own as `main` does, all of them through the
     device together: stage -> gem_mat_frames -> lift -> head joints to the host -> per-chunk scale and cameras -> cameras up ->
     gem_prepare_global.  -> Recording.  `gt_path` None and `scale` given: a recording without ground truth -- the cameras come from
     `scaled_cameras`, nothing goes to the host in between, `mat_start_frame` is not used.  scale="auto": the scale is estimated from the
-    lifted poses first (`auto_scale` with `lag`, `tau`, `min_pairs`; one small record comes back), then the same path runs with it."""
+    lifted poses first (`auto_scale` with `lag`, `tau`, `min_pairs`; one small record comes back), then the same path runs with it.
+    `bridge`: None, or the longest stretch of lost SLAM tracking, in seconds, whose cameras are invented (True: 1 s; `slam_bridge`,
+    DESIGN.md section 6o) -- only without ground truth, and the chunks must follow one another."""
     scale = gt_or_scale(gt_path, scale)
+    from . import slam_bridge
+    bridge = slam_bridge.bridge_arg(bridge, gt_path)
     import torch
     from . import slam
     from .camera import DEFAULT_CALIBRATION
@@ -546,8 +564,11 @@ def prepare_spans(slam_result_path, heatmap_dir, depth_dir, gt_path, spans, fps,
     heat_names = sorted(os.listdir(heatmap_dir), key=natural_key)
     depth_names = sorted(os.listdir(depth_dir), key=natural_key)
     heat_paths, depth_paths, gts, bounds = [], [], [], []
+    if bridge is not None and spans:
+        slam_bridge.find_gaps(slam.frame_ids(text, fps), *slam_bridge.contiguous_span(spans), slam_bridge.max_gap_frames(bridge, fps))
     for a, b in spans:
-        check_trajectory(text, a, b, fps)
+        if bridge is None:
+            check_trajectory(text, a, b, fps)
         hp, dp = heat_names[a:b], depth_names[a:b]
         if len(hp) != b - a or len(dp) != b - a:
             raise ValueError("frames [%d, %d) of the listings are asked for, but %s holds %d files and %s holds %d" %
@@ -568,17 +589,25 @@ def prepare_spans(slam_result_path, heatmap_dir, depth_dir, gt_path, spans, fps,
         est_local, _ = engine.lift_skeleton(heat, depth)
         if scale is not None:
             scale_given = scale
-            scale, scale_report = auto_scale(est_local, text, spans, fps, scale, lag, tau, min_pairs)
-            if scale_report is not None:
-                lap("lift + SLAM scale estimate (gem_slam_scale, report back)")
-            cams, origins = scaled_cameras(text, spans, fps, scale)
-            lap("lift enqueued + cameras at the given scale (host)")
-            cams_d = torch.from_numpy(np.concatenate(cams)).to(device)
+            bridge_report = None
+            if bridge is not None:
+                scale, scale_report, cams, origins, bridge_report = slam_bridge.recording_cameras(engine, est_local, text, spans, fps, scale, bridge,
+                                                                                                  lag, tau, min_pairs)
+                lap("lift enqueued + bridged cameras (gem_slam_bridge, report back)")
+                cams_d = torch.cat(cams)
+            else:
+                scale, scale_report = auto_scale(est_local, text, spans, fps, scale, lag, tau, min_pairs)
+                if scale_report is not None:
+                    lap("lift + SLAM scale estimate (gem_slam_scale, report back)")
+                cams, origins = scaled_cameras(text, spans, fps, scale)
+                lap("lift enqueued + cameras at the given scale (host)")
+                cams_d = torch.from_numpy(np.concatenate(cams)).to(device)
             est_global, _ = prepare_global(est_local, cams_d, None)
             lap("cameras up + gem_prepare_global")
             return Recording([RecordingChunk(a, b, heat[lo:hi], est_local[lo:hi], est_global[lo:hi], cams_d[lo:hi], None,
                                              heat_files=heat_files[lo:hi] if any(k is not None for k in heat_files[lo:hi]) else None)
-                              for (a, b), (lo, hi) in zip(spans, bounds)], origins, scale if scale_given == "auto" else None, scale_report)
+                              for (a, b), (lo, hi) in zip(spans, bounds)], origins, scale if scale_given == "auto" else None, scale_report,
+                             bridge_report)
         heads = est_local[:, 0].cpu().numpy()
         lap("lift + head joints to the host")
         gt_all = np.concatenate([np.asarray(g, dtype=np.float64) for g in gts])
@@ -599,7 +628,7 @@ def prepare_spans(slam_result_path, heatmap_dir, depth_dir, gt_path, spans, fps,
 
 
 def main(slam_result_path, heatmap_dir, depth_dir, gt_path, start_frame, end_frame, out_dir, fps, mat_start_frame=None,
-         camera_model_path=None, scale=None, lag=None, tau=0.10, min_pairs=50):
+         camera_model_path=None, scale=None, lag=None, tau=0.10, min_pairs=50, bridge=None):
     """The reference's `main` (:126-165): one chunk [start_frame, end_frame) -> `<out_dir>/test_data.pkl`, and the line
     `The initial mpjpe is: ...`.  Returns the one-chunk Recording (the reference returns nothing).  Without ground truth (`gt_path`
     None, `scale` given) the pickle has four keys and there is no such line; with scale="auto" one line tells the estimate and its
@@ -607,9 +636,11 @@ def main(slam_result_path, heatmap_dir, depth_dir, gt_path, start_frame, end_fra
     gt_or_scale(gt_path, scale)
     rec = prepare_spans(slam_result_path, heatmap_dir, depth_dir, gt_path, [(start_frame, end_frame)], fps,
                         start_frame if mat_start_frame is None else mat_start_frame, camera_model_path, scale=scale, lag=lag, tau=tau,
-                        min_pairs=min_pairs)
+                        min_pairs=min_pairs, bridge=bridge)
     if rec.scale_report is not None:
         print(rec.scale_report.line())
+    if rec.bridge_report is not None:
+        print(rec.bridge_report.line())
     rec.write_chunk(0, out_dir)
     if scale is None:
         print("The initial mpjpe is: {}".format(rec.chunks[0].initial_mpjpe))
@@ -617,19 +648,23 @@ def main(slam_result_path, heatmap_dir, depth_dir, gt_path, start_frame, end_fra
 
 
 def prepare_sequence(slam_result_path, heatmap_dir, depth_dir, gt_path, total_start_frame, total_end_frame, fps=25, mat_start_frame=None,
-                     test_size=100, out_root=None, camera_model_path=None, verbose=True, scale=None, lag=None, tau=0.10, min_pairs=50):
+                     test_size=100, out_root=None, camera_model_path=None, verbose=True, scale=None, lag=None, tau=0.10, min_pairs=50,
+                     bridge=None):
     """The reference's chunk loop (:176-190): chunks of `test_size` frames from `total_start_frame` (see `chunk_spans` for the
     chunk it drops), `mat_start_frame` defaulting to `total_start_frame` as there.  All chunks go through the device together,
     each prepared on its own.  Returns the Recording; with `out_root`, `data_start_{a}_end_{b}/test_data.pkl` are written too.
     Exactly one of `gt_path` and `scale` is given (else ValueError, before anything else happens): with `scale` the recording has no
-    ground truth (`prepare_spans`); scale="auto" estimates it from the foot contacts (`lag`, `tau`, `min_pairs`: `slam_scale`)."""
+    ground truth (`prepare_spans`); scale="auto" estimates it from the foot contacts (`lag`, `tau`, `min_pairs`: `slam_scale`).  `bridge`:
+    seconds of lost SLAM tracking to bridge (`slam_bridge`), without ground truth only."""
     gt_or_scale(gt_path, scale)
     spans = chunk_spans(total_start_frame, total_end_frame, test_size)
     rec = prepare_spans(slam_result_path, heatmap_dir, depth_dir, gt_path, spans, fps,
                         total_start_frame if mat_start_frame is None else mat_start_frame, camera_model_path, scale=scale, lag=lag, tau=tau,
-                        min_pairs=min_pairs)
+                        min_pairs=min_pairs, bridge=bridge)
     if verbose and rec.scale_report is not None:
         print(rec.scale_report.line())
+    if verbose and rec.bridge_report is not None:
+        print(rec.bridge_report.line())
     for c in rec.chunks:
         if verbose:
             print("running test sequence from {} to {}".format(c.start_frame, c.end_frame))
@@ -652,6 +687,8 @@ def _parser():
     how.add_argument("--gt", default=None, help="ground-truth pickle (it fixes the SLAM scale)")
     how.add_argument("--scale", type=scale_arg, default=None, help="the SLAM scale of a recording without ground truth (a metric SLAM: 1), "
                                                                   "or `auto`: estimate it from the foot contacts")
+    p.add_argument("--bridge", nargs="?", type=float, const=1.0, default=None, metavar="SECONDS",
+                   help="with --scale: invent the cameras of stretches of lost SLAM tracking up to this long (default 1 s)")
     p.add_argument("--start", required=True, type=int)
     p.add_argument("--end", required=True, type=int)
     p.add_argument("--fps", type=float, default=25)
@@ -668,8 +705,10 @@ def _cli(argv=None):
     a = p.parse_args(argv)
     if a.out is None and not a.optimize:
         p.error("nothing to do: give --out, --optimize or both")
+    if a.bridge is not None and a.gt is not None:
+        p.error("--bridge needs --scale: with --gt every chunk has its own scale and there is no common world to bridge in")
     rec = prepare_sequence(a.slam, a.heatmaps, a.depths, a.gt, a.start, a.end, a.fps, a.mat_start, a.test_size, a.out, a.camera,
-                           scale=a.scale)
+                           scale=a.scale, bridge=a.bridge)
     if a.optimize:
         from .whole_sequence import optimize_recording
         if a.scale is None:

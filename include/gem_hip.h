@@ -904,6 +904,48 @@ int gem_foot_lock(const int64_t* h_table, const int64_t* d_table, int n_sequence
                   double tau_h, int min_run, int blend, int snap, double stretch, double* d_work, int64_t work_bytes, double* d_records,
                   void* stream);
 
+/* ---- Bridging the frames on which SLAM lost tracking: `--bridge` ----
+ * The n frames of a recording's span carry metric poses relative to the first frame (t xyz, q xyzw); a frame whose byte in `tracked`
+ * is 0 has none.  A GAP is a maximal run of lost frames with tracked neighbours e and s.  Rotation of a lost frame t: slerp between
+ * the unit quaternions of e and s (the second negated where their dot product is negative) at u = (t - e) / (s - e), the normalised
+ * linear blend where the angle between them is below 1e-8; every matrix is made from the normalised quaternion.  Translation: the
+ * unknown c_t minimise the sum of |c_{t-1} - 2 c_t + c_{t+1}|^2 over every t in [e, s] whose three frames lie in the span and hold a
+ * lost frame; gaps with fewer than two tracked frames between them couple and form ONE system, given as (first lost frame, frames up
+ * to and including its last lost frame).  A system's normal equations (symmetric positive definite, pentadiagonal, one matrix for the
+ * three axes, at most GEM_BRIDGE_MAX_GAP unknowns) are solved by Cholesky in a fixed order, for the offset from the straight line
+ * between the system's tracked neighbours.  Then G[f] is frame f's 4x4 matrix, cams[f] = inv(G[a]) G[f] with a the first frame of f's
+ * chunk and the rigid inverse (R^T, -R^T c), origins[k] = G[a_k], bridged[f] = 1 for a lost frame.  Everything is float64, there
+ * are no floating-point atomics: two calls give the same bytes.  tests/bridge_twin.py is the specification. */
+#define GEM_BRIDGE_MAX_GAP 64             /* lost frames of one gap, and unknowns of one system */
+#define GEM_BRIDGE_MAX_SPAN 127           /* frames of one system: 64 lost ones with single tracked frames between them */
+#define GEM_BRIDGE_RECORD_DOUBLES 16
+#define GEM_BRIDGE_NOT_SOLVED 2           /* a pivot of a system was not positive (poses that are not finite): status of the record */
+typedef struct gem_bridge_record {
+    double status;                                  /* 0 or GEM_BRIDGE_NOT_SOLVED */
+    double frames, lost, gaps, systems;
+    double longest_gap;                             /* lost frames */
+    double offset_max;                              /* largest |c_t - straight line between the gap's neighbours|, metres */
+    double angle_max;                               /* largest rotation bridged across one gap, radians */
+    double translation_max;                         /* largest |c_s - c_e| bridged across one gap, metres */
+    double reserved[7];
+} gem_bridge_record;
+
+/* The bytes of d_work a call on n frames needs; -1 with the reason in gem_last_error unless n lies in 1 .. 2^20.  Needs no GPU. */
+int64_t gem_slam_bridge_work(int64_t n);
+
+/* d_poses [n,7] float64; h_tracked / d_tracked [n] bytes (the same on the host and on the device, like the tables that follow);
+ * h_systems / d_systems [n_systems,2] int32 (may be NULL for none); h_chunk_starts / d_chunk_starts [n_chunks] int32, ascending from
+ * 0.  Outputs: d_G [n,4,4], d_cams [n,4,4], d_origins [n_chunks,4,4] float64, d_bridged [n] bytes, d_record one gem_bridge_record.
+ * The host tables are checked before the launch and the argument at fault named in gem_last_error: null pointers, n outside
+ * 1 .. 2^20, alignment, a first or last frame that is not tracked, chunk starts out of order, and a system table that is not the
+ * one of the mask (a system out of place, longer than GEM_BRIDGE_MAX_SPAN frames or with more than GEM_BRIDGE_MAX_GAP unknowns, a
+ * lost frame outside every system).  Two launches on `stream` (one workgroup of 256 per system, then the per-chunk rebase), no
+ * synchronisation.  Works on the current device. */
+int gem_slam_bridge(const double* d_poses, const unsigned char* h_tracked, const unsigned char* d_tracked, const int32_t* h_systems,
+                    const int32_t* d_systems, int n_systems, const int32_t* h_chunk_starts, const int32_t* d_chunk_starts, int n_chunks,
+                    int64_t n, double* d_G, double* d_cams, double* d_origins, unsigned char* d_bridged, double* d_work, int64_t work_bytes,
+                    double* d_record, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
