@@ -118,6 +118,16 @@ def depths_from_mat_dir(directory, frame_ids):
     return np.stack([np.asarray(read_mat_array(os.path.join(directory, names[int(i)]), DEPTH_NAME)[0], dtype=np.float64)[0] for i in frame_ids])
 
 
+def detections_from_args(a):
+    """The detections dict of a command line's parsed `--keypoints`, `--first_id` and `--depth` or `--depths`."""
+    det = read_detections(a.keypoints, a.first_id)
+    if a.depth is not None:
+        det["depth"] = _depth_array(np.load(a.depth, allow_pickle=False), len(det["keypoints"]), a.depth)
+    elif a.depths is not None:
+        det["depth"] = depths_from_mat_dir(a.depths, det["frame_ids"])
+    return det
+
+
 # ------------------------------------------------------------------------------------------------------------------ the device path
 def recording_from_detections(slam_result_path, detections, gt_path=None, scale=None, spans=(), fps=25, depth=None, sigma=1.5, first_id=0,
                               camera_model_path=None, device=None, gt_start_frame=None, lag=None, tau=0.10, min_pairs=50, bridge=None):
@@ -126,11 +136,11 @@ def recording_from_detections(slam_result_path, detections, gt_path=None, scale=
     `gt_path` (the ground truth fixes the SLAM scale per chunk, as `prepare` does; entry i - gt_start_frame of the pickle is frame id
     i, gt_start_frame defaulting to the first span's start) and `scale`: a number, or "auto" to estimate it from the foot contacts of
     the filled poses (`prepare.auto_scale` with `lag`, `tau`, `min_pairs`).  One upload, then on the device:
-    lift -> fill -> heat-maps -> cameras -> gem_prepare_global.  `bridge`: None, or the seconds of lost SLAM tracking whose cameras are
-    invented (`slam_bridge`), without ground truth only."""
-    from . import prepare, slam, slam_bridge
-    scale = prepare.gt_or_scale(gt_path, scale)
-    bridge = slam_bridge.bridge_arg(bridge, gt_path)
+    lift -> fill -> heat-maps -> cameras -> gem_prepare_global; from the filled poses on this is `prepare.RecordingStage`.  `bridge`:
+    None, or the seconds of lost SLAM tracking whose cameras are invented (`slam_bridge`), without ground truth
+    only."""
+    from . import prepare
+    stage = prepare.RecordingStage(gt_path, scale, bridge, spans, fps, lag, tau, min_pairs)
     import torch
     from .camera import DEFAULT_CALIBRATION
     if isinstance(detections, (str, os.PathLike)):
@@ -143,28 +153,22 @@ def recording_from_detections(slam_result_path, detections, gt_path=None, scale=
         det["depth"] = _depth_array(depth, len(det["keypoints"]), "recording_from_detections")
     if det["depth"] is None:
         raise ValueError("recording_from_detections: the joints' depths are needed (depth=, or `depth` in the .npz)")
-    spans = [(int(a), int(b)) for a, b in spans]
+    spans = stage.spans
     device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-    with open(slam_result_path) as f:
-        text = slam.trajectory_rows(f.read())
-    if bridge is not None and spans:
-        slam_bridge.find_gaps(slam.frame_ids(text, fps), *slam_bridge.contiguous_span(spans), slam_bridge.max_gap_frames(bridge, fps))
-    for a, b in spans:
-        if bridge is None:
-            prepare.check_trajectory(text, a, b, fps)
+    stage.read_trajectory(slam_result_path)
+    stage.check_trajectory()
     rows = span_rows(det["frame_ids"], spans)
     if not spans:
-        return prepare.Recording([], None if scale is None else np.empty((0, 4, 4)))
+        return stage.empty()
     bounds = np.concatenate([[0], np.cumsum([len(r) for r in rows])])
-    bounds = [(int(lo), int(hi)) for lo, hi in zip(bounds[:-1], bounds[1:])]
+    stage.bounds = bounds = [(int(lo), int(hi)) for lo, hi in zip(bounds[:-1], bounds[1:])]
     pick = np.concatenate(rows)
     kp = det["keypoints"][pick]
     check_chunks_have_every_joint(kp, bounds, spans)
-    gts = None
-    if scale is None:
-        pose_gt = prepare.read_gt(gt_path)
+    pose_gt = stage.read_gt()
+    if pose_gt is not None:
         g0 = spans[0][0] if gt_start_frame is None else int(gt_start_frame)
-        gts = [prepare.gt_clip(pose_gt, a, b, g0) for a, b in spans]
+        stage.gts = [prepare.gt_clip(pose_gt, a, b, g0) for a, b in spans]
     packed = np.concatenate([kp, det["depth"][pick][..., None]], axis=2)          # [n,15,4]: ONE copy carries detections and depths
     with torch.cuda.device(device):
         engine = prepare._lift_engine(camera_model_path or DEFAULT_CALIBRATION, device.index)
@@ -177,90 +181,32 @@ def recording_from_detections(slam_result_path, detections, gt_path=None, scale=
         else:
             for lo, hi in bounds:
                 engine.fill_missing(est_local[lo:hi], valid[lo:hi], 1)
-        if scale is not None:          # (a recording that does not fix the scale is refused before the heat-maps are made)
-            scale_given = scale
-            bridge_report = None
-            if bridge is not None:
-                scale, scale_report, cams, origins, bridge_report = slam_bridge.recording_cameras(engine, est_local, text, spans, fps, scale, bridge,
-                                                                                                  lag, tau, min_pairs)
-            else:
-                scale, scale_report = prepare.auto_scale(est_local, text, spans, fps, scale, lag, tau, min_pairs)
-        heat = engine.keypoint_heatmaps(kp_d, sigma)
-        if scale is not None:
-            if bridge is not None:
-                cams_d = torch.cat(cams)
-            else:
-                cams, origins = prepare.scaled_cameras(text, spans, fps, scale)
-                cams_d = torch.from_numpy(np.concatenate(cams)).to(device)
-            est_global, _ = prepare.prepare_global(est_local, cams_d, None)
-            return prepare.Recording([prepare.RecordingChunk(a, b, heat[lo:hi], est_local[lo:hi], est_global[lo:hi], cams_d[lo:hi], None)
-                                      for (a, b), (lo, hi) in zip(spans, bounds)], origins, scale if scale_given == "auto" else None, scale_report,
-                                     bridge_report)
-        heads = est_local[:, 0].cpu().numpy()
-        gt_all = np.concatenate([np.asarray(g, dtype=np.float64) for g in gts])
-        cams = np.concatenate([slam.camera_pose_list_from_heads(text, heads[lo:hi], gt_all[lo:hi, 0], a, b, fps)[0]
-                               for (a, b), (lo, hi) in zip(spans, bounds)])
-        cams_d, gt_d = torch.from_numpy(cams).to(device), torch.from_numpy(gt_all).to(device)
-        est_global, err = prepare.prepare_global(est_local, cams_d, gt_d)
-        err = err.cpu().numpy()
-    return prepare.Recording([prepare.RecordingChunk(a, b, heat[lo:hi], est_local[lo:hi], est_global[lo:hi], cams_d[lo:hi], gt_d[lo:hi], gt_list=g,
-                                                     initial_mpjpe=float(np.mean(err[lo:hi])))
-                              for (a, b), (lo, hi), g in zip(spans, bounds, gts)])
+        stage.fix_scale(engine, est_local)          # (a recording that does not fix the scale is refused before the heat-maps are made)
+        heat = engine.keypoint_heatmaps(kp_d, sigma)          # (enqueued ahead of the host's camera work and its blocking upload)
+        return stage.recording(est_local, heat)
 
 
 def _parser():
     import argparse
-    from .camera import DEFAULT_CALIBRATION
-    from .slam_scale import scale_arg
+    from . import prepare
     p = argparse.ArgumentParser(description="recording (2-D joint detections) -> chunks for the optimiser")
-    p.add_argument("--slam", required=True, help="SLAM trajectory: lines `time tx ty tz qx qy qz qw`")
     p.add_argument("--keypoints", required=True, metavar="FILE", help=".npy [N,15,2|3] or .npz with keypoints[, depth, frame_ids]: u, v in "
                                                                        "pixels of the fisheye image[, confidence]")
-    how = p.add_mutually_exclusive_group(required=True)
-    how.add_argument("--gt", default=None, help="ground-truth pickle (it fixes the SLAM scale)")
-    how.add_argument("--scale", type=scale_arg, default=None, help="the SLAM scale of a recording without ground truth (a metric SLAM: 1), "
-                                                                  "or `auto`: estimate it from the foot contacts")
     dep = p.add_mutually_exclusive_group()
     dep.add_argument("--depths", default=None, metavar="DIR", help="directory of per-frame depth .mat files")
     dep.add_argument("--depth", default=None, metavar="FILE.npy", help="the joints' depths [N,15], row for row with the detections")
-    p.add_argument("--bridge", nargs="?", type=float, const=1.0, default=None, metavar="SECONDS",
-                   help="with --scale: invent the cameras of stretches of lost SLAM tracking up to this long (default 1 s)")
-    p.add_argument("--start", required=True, type=int)
-    p.add_argument("--end", required=True, type=int)
-    p.add_argument("--fps", type=float, default=25)
     p.add_argument("--sigma", type=float, default=1.5, help="the splatted Gaussians' width in heat-map pixels")
     p.add_argument("--first_id", type=int, default=0, help="frame id of the detections' first row (without frame_ids)")
-    p.add_argument("--mat_start", type=int, default=None, help="frame id of the GT pickle's first entry (default: --start)")
-    p.add_argument("--test_size", type=int, default=100)
-    p.add_argument("--out", default=None, help="directory for data_start_{a}_end_{b}/test_data.pkl")
-    p.add_argument("--camera", default=DEFAULT_CALIBRATION)
-    p.add_argument("--optimize", action="store_true", help="optimise the recording right away (no pickle in between)")
+    prepare.add_recording_options(p)
     return p
 
 
 def _cli(argv=None):
     from . import prepare
-    p = _parser()
-    a = p.parse_args(argv)
-    if a.out is None and not a.optimize:
-        p.error("nothing to do: give --out, --optimize or both")
-    if a.bridge is not None and a.gt is not None:
-        p.error("--bridge needs --scale: with --gt every chunk has its own scale and there is no common world to bridge in")
-    det = read_detections(a.keypoints, a.first_id)
-    if a.depth is not None:
-        det["depth"] = _depth_array(np.load(a.depth, allow_pickle=False), len(det["keypoints"]), a.depth)
-    elif a.depths is not None:
-        det["depth"] = depths_from_mat_dir(a.depths, det["frame_ids"])
-    rec = recording_from_detections(a.slam, det, a.gt, a.scale, prepare.chunk_spans(a.start, a.end, a.test_size), a.fps, sigma=a.sigma,
-                                    camera_model_path=a.camera, gt_start_frame=a.mat_start, bridge=a.bridge)
-    if rec.scale_report is not None:
-        print(rec.scale_report.line())
-    if rec.bridge_report is not None:
-        print(rec.bridge_report.line())
-    for c in rec.chunks:
-        print("running test sequence from {} to {}".format(c.start_frame, c.end_frame))
-        if c.initial_mpjpe is not None:
-            print("The initial mpjpe is: {}".format(c.initial_mpjpe))
+    a = prepare.parse_recording_options(_parser(), argv)
+    rec = recording_from_detections(a.slam, detections_from_args(a), a.gt, a.scale, prepare.chunk_spans(a.start, a.end, a.test_size), a.fps,
+                                    sigma=a.sigma, camera_model_path=a.camera, gt_start_frame=a.mat_start, bridge=a.bridge)
+    prepare.print_report(rec)
     if a.out is not None:
         rec.write_chunks(a.out)
     if a.optimize:

@@ -531,14 +531,119 @@ def prepare_global(est_local, cams, gt):
     return out, err
 
 
-def auto_scale(est_local, rows, spans, fps, scale, lag=None, tau=0.10, min_pairs=50):
+def auto_scale(est_local, rows, spans, fps, scale, lag=None, tau=0.10, min_pairs=50, tracked=False):
     """`scale` as a number -> (scale, None).  "auto" -> (the estimate, its `slam_scale.ScaleEstimate`): `gem_slam_scale` on the lifted
-    poses where they lie, one small record back; ValueError when the recording does not fix the scale."""
+    poses where they lie (`tracked`: on the tracked frames of a trajectory that lacks lines), one small record back; ValueError when
+    the recording does not fix the scale."""
     if not (isinstance(scale, str) and scale == "auto"):
         return scale, None
     from .slam_scale import estimate_scale
-    report = estimate_scale(est_local, rows, spans, fps, lag=lag, tau=tau, min_pairs=min_pairs)
+    report = estimate_scale(est_local, rows, spans, fps, lag=lag, tau=tau, min_pairs=min_pairs, tracked=tracked)
     return float(report.scale), report
+
+
+class RecordingStage:
+    """What every route into a `Recording` does once it has the lifted poses `est_local`: fix the SLAM scale, build the cameras, apply
+    them (`gem_prepare_global`) and cut the chunks.  One per call.  The route makes it first (the argument checks), reads and checks
+    the trajectory through it, sets `bounds` [(first row, row behind the last)] and `gts` (per chunk the ground-truth arrays; unused
+    without ground truth) for its chunks, and then calls `fix_scale` and `recording` -- two steps, because a route may enqueue device
+    work between them that the host's camera work then overlaps (the detection route's heat-maps)."""
+
+    def __init__(self, gt_path, scale, bridge, spans, fps, lag=None, tau=0.10, min_pairs=50):
+        from .slam_bridge import bridge_arg
+        self.gt_path, self.scale = gt_path, gt_or_scale(gt_path, scale)
+        self.bridge = bridge_arg(bridge, gt_path)
+        self.spans, self.fps = [(int(a), int(b)) for a, b in spans], fps
+        self.lag, self.tau, self.min_pairs = lag, tau, min_pairs
+        self.rows = self.systems = self.bounds = self.gts = None
+        self.cams = self.origins = self.scale_report = self.bridge_report = None
+
+    def read_trajectory(self, slam_result_path):
+        from . import slam
+        with open(slam_result_path) as f:
+            self.rows = slam.trajectory_rows(f.read())          # (parsed once for all chunks)
+
+    def read_gt(self):
+        """The ground-truth pickle's poses; None for a recording without ground truth."""
+        return read_gt(self.gt_path) if self.scale is None else None
+
+    def check_trajectory(self):
+        """Every span's frame ids have their trajectory line (`check_trajectory`) -- or, with `bridge`, the lost ones can be bridged
+        (`slam_bridge.find_gaps`, whose systems are kept for `fix_scale`).  ValueError otherwise."""
+        from . import slam, slam_bridge
+        if self.bridge is None:
+            for a, b in self.spans:
+                check_trajectory(self.rows, a, b, self.fps)
+        elif self.spans:
+            self.systems = slam_bridge.find_gaps(slam.frame_ids(self.rows, self.fps), *slam_bridge.contiguous_span(self.spans),
+                                                 slam_bridge.max_gap_frames(self.bridge, self.fps))
+
+    def empty(self):
+        """The recording of no spans."""
+        return Recording([], None if self.scale is None else np.empty((0, 4, 4)))
+
+    def fix_scale(self, engine, est_local, lap=Laps(None)):
+        """Everything that can still refuse the recording, and everything that needs a read-back before the cameras exist: "auto"
+        becomes a number and a `slam_scale.ScaleEstimate` (with `bridge` from the tracked frames only; ValueError when the recording
+        does not fix the scale), and with `bridge` the bridged cameras, the origins and the `slam_bridge.BridgeReport` are made; the
+        cameras stay on the device.  Nothing to do with ground truth."""
+        if self.scale is None:
+            return
+        self.scale, self.scale_report = auto_scale(est_local, self.rows, self.spans, self.fps, self.scale, self.lag, self.tau, self.min_pairs,
+                                                   tracked=self.bridge is not None)
+        if self.bridge is not None:
+            from .slam_bridge import bridge_cameras
+            self.cams, self.origins, self.bridge_report = bridge_cameras(engine, self.rows, self.spans, self.fps, self.scale, self.bridge,
+                                                                         systems=self.systems)
+            lap("lift enqueued + bridged cameras (gem_slam_bridge, report back)")
+        elif self.scale_report is not None:
+            lap("lift + SLAM scale estimate (gem_slam_scale, report back)")
+
+    def recording(self, est_local, heat, heat_files=None, lap=Laps(None)):
+        """The cameras -- per-chunk Umeyama against the ground truth's head track on the host, `scaled_cameras`, or `fix_scale`'s
+        bridged ones -- go up, `gem_prepare_global` applies them, and the chunks are cut.  -> Recording."""
+        import torch
+        from . import slam
+        spans, bounds, gt_all = self.spans, self.bounds, None
+        if self.scale is None:
+            heads = est_local[:, 0].cpu().numpy()
+            lap("lift + head joints to the host")
+            gt_all = np.concatenate([np.asarray(g, dtype=np.float64) for g in self.gts])
+            cams = np.concatenate([slam.camera_pose_list_from_heads(self.rows, heads[lo:hi], gt_all[lo:hi, 0], a, b, self.fps)[0]
+                                   for (a, b), (lo, hi) in zip(spans, bounds)])
+            lap("per-chunk scale and cameras (host)")
+        elif self.bridge is None:
+            cams, self.origins = scaled_cameras(self.rows, spans, self.fps, self.scale)
+            cams = np.concatenate(cams)
+            lap("lift enqueued + cameras at the given scale (host)")
+        cams_d = torch.cat(self.cams) if self.bridge is not None else torch.from_numpy(cams).to(est_local.device)
+        gt_d = None if gt_all is None else torch.from_numpy(gt_all).to(est_local.device)
+        est_global, err = prepare_global(est_local, cams_d, gt_d)
+        if err is not None:
+            err = err.cpu().numpy()
+        lap("cameras up + gem_prepare_global" if err is None else "cameras up + gem_prepare_global + errors back")
+        chunks = []
+        for k, ((a, b), (lo, hi)) in enumerate(zip(spans, bounds)):
+            kept = None if heat_files is None else heat_files[lo:hi]
+            chunks.append(RecordingChunk(a, b, heat[lo:hi], est_local[lo:hi], est_global[lo:hi], cams_d[lo:hi], None if gt_d is None else gt_d[lo:hi],
+                                         gt_list=None if gt_d is None else self.gts[k],
+                                         heat_files=kept if kept is not None and any(x is not None for x in kept) else None,
+                                         initial_mpjpe=None if err is None else float(np.mean(err[lo:hi]))))
+        return Recording(chunks, self.origins, self.scale if self.scale_report is not None else None, self.scale_report, self.bridge_report)
+
+
+def print_report(rec, sequence=True):
+    """What a preparation tells about its recording: the scale estimate's line, the bridge's line, and per chunk the reference's
+    `running test sequence from a to b` (its chunk loop's; not with `sequence` False) and `The initial mpjpe is: ...` (with ground
+    truth)."""
+    for report in (rec.scale_report, rec.bridge_report):
+        if report is not None:
+            print(report.line())
+    for c in rec.chunks:
+        if sequence:
+            print("running test sequence from {} to {}".format(c.start_frame, c.end_frame))
+        if c.initial_mpjpe is not None:
+            print("The initial mpjpe is: {}".format(c.initial_mpjpe))
 
 
 def prepare_spans(slam_result_path, heatmap_dir, depth_dir, gt_path, spans, fps, mat_start_frame, camera_model_path=None, device=None,
@@ -549,36 +654,30 @@ def prepare_spans(slam_result_path, heatmap_dir, depth_dir, gt_path, spans, fps,
     `scaled_cameras`, nothing goes to the host in between, `mat_start_frame` is not used.  scale="auto": the scale is estimated from the
     lifted poses first (`auto_scale` with `lag`, `tau`, `min_pairs`; one small record comes back), then the same path runs with it.
     `bridge`: None, or the longest stretch of lost SLAM tracking, in seconds, whose cameras are invented (True: 1 s; `slam_bridge`,
-    DESIGN.md section 6o) -- only without ground truth, and the chunks must follow one another."""
-    scale = gt_or_scale(gt_path, scale)
-    from . import slam_bridge
-    bridge = slam_bridge.bridge_arg(bridge, gt_path)
+    DESIGN.md section 6o) -- only without ground truth, and the chunks must follow one another.  From the lifted poses on this is
+    `RecordingStage`."""
+    stage = RecordingStage(gt_path, scale, bridge, spans, fps, lag, tau, min_pairs)
     import torch
-    from . import slam
     from .camera import DEFAULT_CALIBRATION
     lap = Laps(timings)          # developer timing (tools/prepare_bench.py)
     device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-    with open(slam_result_path) as f:
-        text = slam.trajectory_rows(f.read())          # (parsed once for all chunks)
-    pose_gt = read_gt(gt_path) if scale is None else None
+    stage.read_trajectory(slam_result_path)
+    pose_gt = stage.read_gt()
     heat_names = sorted(os.listdir(heatmap_dir), key=natural_key)
     depth_names = sorted(os.listdir(depth_dir), key=natural_key)
-    heat_paths, depth_paths, gts, bounds = [], [], [], []
-    if bridge is not None and spans:
-        slam_bridge.find_gaps(slam.frame_ids(text, fps), *slam_bridge.contiguous_span(spans), slam_bridge.max_gap_frames(bridge, fps))
+    heat_paths, depth_paths, stage.gts, stage.bounds = [], [], [], []
+    stage.check_trajectory()
     for a, b in spans:
-        if bridge is None:
-            check_trajectory(text, a, b, fps)
         hp, dp = heat_names[a:b], depth_names[a:b]
         if len(hp) != b - a or len(dp) != b - a:
             raise ValueError("frames [%d, %d) of the listings are asked for, but %s holds %d files and %s holds %d" %
                              (a, b, heatmap_dir, len(heat_names), depth_dir, len(depth_names)))
-        bounds.append((len(heat_paths), len(heat_paths) + b - a))
+        stage.bounds.append((len(heat_paths), len(heat_paths) + b - a))
         heat_paths += [os.path.join(heatmap_dir, x) for x in hp]
         depth_paths += [os.path.join(depth_dir, x) for x in dp]
-        gts.append(gt_clip(pose_gt, a, b, mat_start_frame) if scale is None else None)
+        stage.gts.append(gt_clip(pose_gt, a, b, mat_start_frame) if pose_gt is not None else None)
     if not spans:
-        return Recording([], None if scale is None else np.empty((0, 4, 4)))
+        return stage.empty()
     lap("listings, ground truth, trajectory")
     with torch.cuda.device(device):
         heat, depth, heat_files = frames_to_device(heat_paths, depth_paths, device, timings=timings)
@@ -587,44 +686,8 @@ def prepare_spans(slam_result_path, heatmap_dir, depth_dir, gt_path, spans, fps,
         if tuple(heat.shape[1:3]) != tuple(engine.heat_size):
             raise ValueError("heat-maps of %d x %d: the lifting kernel is built for %d x %d" % (tuple(heat.shape[1:3]) + tuple(engine.heat_size)))
         est_local, _ = engine.lift_skeleton(heat, depth)
-        if scale is not None:
-            scale_given = scale
-            bridge_report = None
-            if bridge is not None:
-                scale, scale_report, cams, origins, bridge_report = slam_bridge.recording_cameras(engine, est_local, text, spans, fps, scale, bridge,
-                                                                                                  lag, tau, min_pairs)
-                lap("lift enqueued + bridged cameras (gem_slam_bridge, report back)")
-                cams_d = torch.cat(cams)
-            else:
-                scale, scale_report = auto_scale(est_local, text, spans, fps, scale, lag, tau, min_pairs)
-                if scale_report is not None:
-                    lap("lift + SLAM scale estimate (gem_slam_scale, report back)")
-                cams, origins = scaled_cameras(text, spans, fps, scale)
-                lap("lift enqueued + cameras at the given scale (host)")
-                cams_d = torch.from_numpy(np.concatenate(cams)).to(device)
-            est_global, _ = prepare_global(est_local, cams_d, None)
-            lap("cameras up + gem_prepare_global")
-            return Recording([RecordingChunk(a, b, heat[lo:hi], est_local[lo:hi], est_global[lo:hi], cams_d[lo:hi], None,
-                                             heat_files=heat_files[lo:hi] if any(k is not None for k in heat_files[lo:hi]) else None)
-                              for (a, b), (lo, hi) in zip(spans, bounds)], origins, scale if scale_given == "auto" else None, scale_report,
-                             bridge_report)
-        heads = est_local[:, 0].cpu().numpy()
-        lap("lift + head joints to the host")
-        gt_all = np.concatenate([np.asarray(g, dtype=np.float64) for g in gts])
-        cams = np.concatenate([slam.camera_pose_list_from_heads(text, heads[lo:hi], gt_all[lo:hi, 0], a, b, fps)[0]
-                               for (a, b), (lo, hi) in zip(spans, bounds)])
-        lap("per-chunk scale and cameras (host)")
-        cams_d, gt_d = torch.from_numpy(cams).to(device), torch.from_numpy(gt_all).to(device)
-        est_global, err = prepare_global(est_local, cams_d, gt_d)
-        err = err.cpu().numpy()
-        lap("cameras up + gem_prepare_global + errors back")
-    chunks = []
-    for (a, b), (lo, hi), g in zip(spans, bounds, gts):
-        kept = heat_files[lo:hi]
-        chunks.append(RecordingChunk(a, b, heat[lo:hi], est_local[lo:hi], est_global[lo:hi], cams_d[lo:hi], gt_d[lo:hi], gt_list=g,
-                                     heat_files=kept if any(k is not None for k in kept) else None,
-                                     initial_mpjpe=float(np.mean(err[lo:hi]))))
-    return Recording(chunks)
+        stage.fix_scale(engine, est_local, lap)
+        return stage.recording(est_local, heat, heat_files, lap)
 
 
 def main(slam_result_path, heatmap_dir, depth_dir, gt_path, start_frame, end_frame, out_dir, fps, mat_start_frame=None,
@@ -633,17 +696,11 @@ def main(slam_result_path, heatmap_dir, depth_dir, gt_path, start_frame, end_fra
     `The initial mpjpe is: ...`.  Returns the one-chunk Recording (the reference returns nothing).  Without ground truth (`gt_path`
     None, `scale` given) the pickle has four keys and there is no such line; with scale="auto" one line tells the estimate and its
     counts, and a recording that does not fix the scale is a ValueError before anything is written."""
-    gt_or_scale(gt_path, scale)
     rec = prepare_spans(slam_result_path, heatmap_dir, depth_dir, gt_path, [(start_frame, end_frame)], fps,
                         start_frame if mat_start_frame is None else mat_start_frame, camera_model_path, scale=scale, lag=lag, tau=tau,
                         min_pairs=min_pairs, bridge=bridge)
-    if rec.scale_report is not None:
-        print(rec.scale_report.line())
-    if rec.bridge_report is not None:
-        print(rec.bridge_report.line())
+    print_report(rec, sequence=False)
     rec.write_chunk(0, out_dir)
-    if scale is None:
-        print("The initial mpjpe is: {}".format(rec.chunks[0].initial_mpjpe))
     return rec
 
 
@@ -661,28 +718,19 @@ def prepare_sequence(slam_result_path, heatmap_dir, depth_dir, gt_path, total_st
     rec = prepare_spans(slam_result_path, heatmap_dir, depth_dir, gt_path, spans, fps,
                         total_start_frame if mat_start_frame is None else mat_start_frame, camera_model_path, scale=scale, lag=lag, tau=tau,
                         min_pairs=min_pairs, bridge=bridge)
-    if verbose and rec.scale_report is not None:
-        print(rec.scale_report.line())
-    if verbose and rec.bridge_report is not None:
-        print(rec.bridge_report.line())
-    for c in rec.chunks:
-        if verbose:
-            print("running test sequence from {} to {}".format(c.start_frame, c.end_frame))
-            if c.initial_mpjpe is not None:
-                print("The initial mpjpe is: {}".format(c.initial_mpjpe))
+    if verbose:
+        print_report(rec)
     if out_root is not None:
         rec.write_chunks(out_root)
     return rec
 
 
-def _parser():
-    import argparse
+def add_recording_options(p):
+    """The options every preparation command line has (`prepare`, `detections`): the trajectory, what fixes the SLAM scale, the
+    frames, the chunks and what to do with them."""
     from .camera import DEFAULT_CALIBRATION
     from .slam_scale import scale_arg
-    p = argparse.ArgumentParser(description="recording (.mat files of the pose network) -> chunks for the optimiser")
     p.add_argument("--slam", required=True, help="SLAM trajectory: lines `time tx ty tz qx qy qz qw`")
-    p.add_argument("--heatmaps", required=True, help="directory of per-frame heatmap .mat files")
-    p.add_argument("--depths", required=True, help="directory of per-frame depth .mat files")
     how = p.add_mutually_exclusive_group(required=True)
     how.add_argument("--gt", default=None, help="ground-truth pickle (it fixes the SLAM scale)")
     how.add_argument("--scale", type=scale_arg, default=None, help="the SLAM scale of a recording without ground truth (a metric SLAM: 1), "
@@ -697,24 +745,34 @@ def _parser():
     p.add_argument("--out", default=None, help="directory for data_start_{a}_end_{b}/test_data.pkl")
     p.add_argument("--camera", default=DEFAULT_CALIBRATION)
     p.add_argument("--optimize", action="store_true", help="optimise the recording right away (no pickle in between)")
-    return p
 
 
-def _cli(argv=None):
-    p = _parser()
+def parse_recording_options(p, argv=None):
+    """`p.parse_args(argv)` and the checks that go with `add_recording_options`."""
     a = p.parse_args(argv)
     if a.out is None and not a.optimize:
         p.error("nothing to do: give --out, --optimize or both")
     if a.bridge is not None and a.gt is not None:
         p.error("--bridge needs --scale: with --gt every chunk has its own scale and there is no common world to bridge in")
+    return a
+
+
+def _parser():
+    import argparse
+    p = argparse.ArgumentParser(description="recording (.mat files of the pose network) -> chunks for the optimiser")
+    p.add_argument("--heatmaps", required=True, help="directory of per-frame heatmap .mat files")
+    p.add_argument("--depths", required=True, help="directory of per-frame depth .mat files")
+    add_recording_options(p)
+    return p
+
+
+def _cli(argv=None):
+    a = parse_recording_options(_parser(), argv)
     rec = prepare_sequence(a.slam, a.heatmaps, a.depths, a.gt, a.start, a.end, a.fps, a.mat_start, a.test_size, a.out, a.camera,
                            scale=a.scale, bridge=a.bridge)
     if a.optimize:
         from .whole_sequence import optimize_recording
-        if a.scale is None:
-            optimize_recording(rec, a.camera)
-        else:
-            optimize_recording(rec, a.camera, ground_truth=False)
+        optimize_recording(rec, a.camera, ground_truth=a.scale is None)
 
 
 if __name__ == "__main__":

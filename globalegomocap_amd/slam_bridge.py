@@ -22,12 +22,17 @@ MAX_GAP = _capi.BRIDGE_MAX_GAP
 DEFAULT_MAX_GAP_SECONDS = 1.0
 
 
+def gap_seconds(value):
+    """The longest gap to bridge as a float; ValueError unless it is a positive finite number."""
+    seconds = float(value)
+    if not (math.isfinite(seconds) and seconds > 0):
+        raise ValueError("bridge: the longest gap to bridge must be a positive number of seconds, got %r" % (value,))
+    return seconds
+
+
 def max_gap_frames(seconds, fps):
     """floor(seconds * fps + 0.5); ValueError unless seconds is a positive finite number."""
-    seconds = float(seconds)
-    if not (math.isfinite(seconds) and seconds > 0):
-        raise ValueError("bridge: the longest gap to bridge must be a positive number of seconds, got %r" % seconds)
-    return int(math.floor(seconds * float(fps) + 0.5))
+    return int(math.floor(gap_seconds(float(seconds)) * float(fps) + 0.5))
 
 
 def bridge_arg(bridge, gt_path=None):
@@ -38,10 +43,7 @@ def bridge_arg(bridge, gt_path=None):
     if gt_path is not None:
         raise ValueError("bridge applies to a recording without ground truth (scale=): with gt_path every chunk has its own Umeyama scale "
                          "and there is no common world to bridge in")
-    seconds = DEFAULT_MAX_GAP_SECONDS if bridge is True else float(bridge)
-    if not (math.isfinite(seconds) and seconds > 0):
-        raise ValueError("bridge: the longest gap to bridge must be a positive number of seconds, got %r" % bridge)
-    return seconds
+    return DEFAULT_MAX_GAP_SECONDS if bridge is True else gap_seconds(bridge)
 
 
 def tracked_mask(frame_ids, start_frame, end_frame):
@@ -216,14 +218,16 @@ def contiguous_span(spans):
     return spans[0][0], spans[-1][1]
 
 
-def bridge_cameras(engine, rows, spans, fps, scale, max_gap=DEFAULT_MAX_GAP_SECONDS, stream=None):
+def bridge_cameras(engine, rows, spans, fps, scale, max_gap=DEFAULT_MAX_GAP_SECONDS, stream=None, systems=None):
     """The cameras of a recording without ground truth whose trajectory (`slam.trajectory_rows`) lacks lines: the span from the first
-    chunk's start to the last chunk's end is bridged as a whole (`find_gaps`, `gem_slam_bridge`) and cut into the chunks of `spans`
-    on the device.  -> ([cams [n_k,4,4] per chunk: device tensors, views of one block], origins [n_chunks,4,4] numpy, BridgeReport).
+    chunk's start to the last chunk's end is bridged as a whole (`find_gaps`, or its result for this span as `systems`;
+    `gem_slam_bridge`) and cut into the chunks of `spans` on the device.
+    -> ([cams [n_k,4,4] per chunk: device tensors, views of one block], origins [n_chunks,4,4] numpy, BridgeReport).
     With no lost frame the cameras are those of `prepare.scaled_cameras`, to rounding.  `engine`: anything with a `.device`."""
     from . import slam
     A, B = contiguous_span(spans)
-    systems = find_gaps(slam.frame_ids(rows, fps), A, B, max_gap_frames(max_gap, fps))
+    if systems is None:
+        systems = find_gaps(slam.frame_ids(rows, fps), A, B, max_gap_frames(max_gap, fps))
     poses, mask = relative_rows(rows, A, B, fps, scale)
     device = getattr(engine, "device", engine)
     starts = [a - A for a, _ in spans]
@@ -232,43 +236,6 @@ def bridge_cameras(engine, rows, spans, fps, scale, max_gap=DEFAULT_MAX_GAP_SECO
     if report.status != 0:
         raise ValueError("the bridge's equations could not be solved: the tracked poses around a gap are not finite")
     return [cams[a - A:b - A] for a, b in spans], origins.cpu().numpy(), report
-
-
-def estimate_scale_tracked(est_local, rows, spans, fps, lag=None, tau=0.10, min_pairs=50):
-    """`slam_scale.estimate_scale` on the tracked frames of a recording with lost frames: only the tracked rows and their poses are
-    passed, and the estimator pairs rows where their frame ids lie `lag` apart, so no pair reaches across a gap.  `est_local`: ONE
-    device tensor holding the spans' poses in order.  -> ScaleEstimate."""
-    import torch
-    from . import slam, slam_scale
-    A, B = contiguous_span(spans)
-    picked, ids = tracked_rows(rows, A, B, fps)
-    mask = tracked_mask(ids, A, B)
-    rt, rq = slam.relative_poses(picked[:, 1:4], picked[:, 4:8])
-    R = slam.pose_matrix(rt, rq)[:, :3, :3]
-    keep = torch.from_numpy(np.flatnonzero(mask)).to(est_local.device)
-    kept = est_local.index_select(0, keep).contiguous()
-    cuts = np.concatenate([[0], np.cumsum([int(mask[a - A:b - A].sum()) for a, b in spans])])
-    lag = slam_scale.default_lag(fps) if lag is None else int(lag)
-    rc, report, costs, msg = slam_scale.scale_call([kept[lo:hi] for lo, hi in zip(cuts[:-1], cuts[1:])], R, rt, ids, lag, tau, min_pairs)
-    if rc in (_capi.SCALE_NO_PAIRS, _capi.SCALE_TOO_FEW, _capi.SCALE_BAD_SCALE):
-        raise ValueError(msg.replace("gem_slam_scale: ", "the SLAM scale cannot be estimated: "))
-    if rc:
-        raise _capi.GemError(msg or "gem_slam_scale failed")
-    return slam_scale.ScaleEstimate(report, costs)
-
-
-def recording_cameras(engine, est_local, rows, spans, fps, scale, bridge, lag=None, tau=0.10, min_pairs=50):
-    """What `prepare` and `detections` do with `bridge=` seconds on the route without ground truth: the scale (estimated on the tracked
-    frames for "auto") and the bridged cameras.  -> (scale, ScaleEstimate or None, cams per chunk, origins, BridgeReport)."""
-    A, B = contiguous_span(spans)
-    from . import slam
-    find_gaps(slam.frame_ids(rows, fps), A, B, max_gap_frames(bridge, fps))          # (refusals come before any estimate)
-    scale_report = None
-    if isinstance(scale, str) and scale == "auto":
-        scale_report = estimate_scale_tracked(est_local, rows, spans, fps, lag, tau, min_pairs)
-        scale = float(scale_report.scale)
-    cams, origins, report = bridge_cameras(engine, rows, spans, fps, scale, bridge)
-    return scale, scale_report, cams, origins, report
 
 
 # ------------------------------------------------------------------------------------------------------------------ command line

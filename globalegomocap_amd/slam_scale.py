@@ -18,14 +18,10 @@ import os
 import numpy as np
 
 from . import _capi
+from .ground import default_lag
 from .skeleton import JOINT_NAMES
 
 FEET = tuple(JOINT_NAMES.index(k) for k in ("Right_ankle", "Right_foot", "Left_ankle", "Left_foot"))
-
-
-def default_lag(fps):
-    """0.2 s in frames, at least one."""
-    return max(1, int(round(0.2 * fps)))
 
 
 class ScaleEstimate:
@@ -132,24 +128,47 @@ def scale_call(chunks, R, c, ids, lag, tau=0.10, min_pairs=50, feet=None, stream
     return rc, (host if read_back else report), costs, msg
 
 
-def estimate_scale(est_local, rows_or_text, spans, fps, *, lag=None, tau=0.10, min_pairs=50, feet=None, stream=None):
+def tracked_poses(est_local, rows, spans, fps):
+    """The estimator's inputs for a recording with lost frames: the tracked frames of the spans (which follow one another) alone.
+    `est_local`: ONE device tensor holding the spans' poses in order; `rows`: `slam.trajectory_rows`.
+    -> ([the tracked frames' poses per span], R, c, ids) as `selected_poses` gives them for a whole trajectory."""
+    import torch
+    from . import slam
+    from .slam_bridge import contiguous_span, tracked_mask, tracked_rows
+    A, B = contiguous_span(spans)
+    picked, ids = tracked_rows(rows, A, B, fps)
+    mask = tracked_mask(ids, A, B)
+    rt, rq = slam.relative_poses(picked[:, 1:4], picked[:, 4:8])
+    R = slam.pose_matrix(rt, rq)[:, :3, :3]
+    keep = torch.from_numpy(np.flatnonzero(mask)).to(est_local.device)
+    kept = est_local.index_select(0, keep).contiguous()
+    cuts = np.concatenate([[0], np.cumsum([int(mask[a - A:b - A].sum()) for a, b in spans])])
+    return [kept[lo:hi] for lo, hi in zip(cuts[:-1], cuts[1:])], R, rt, ids
+
+
+def estimate_scale(est_local, rows_or_text, spans, fps, *, lag=None, tau=0.10, min_pairs=50, feet=None, stream=None, tracked=False):
     """The SLAM scale of the recording whose lifted poses are `est_local` -- one device tensor [n,15,3] float64 per span of `spans`
     [(start_frame, end_frame)], or ONE tensor holding them all in order -- and whose trajectory is `rows_or_text`
     (`slam.trajectory_rows`, or the file's text).  On the detection route these are the poses after `gem_fill_missing`.
+    `tracked`: the trajectory lacks lines (`slam_bridge`); only the tracked rows and their poses are passed (`tracked_poses`), and
+    since the estimator pairs rows where their frame ids lie `lag` apart, no pair reaches across a gap.
     -> ScaleEstimate; ValueError naming the counts when the recording does not fix the scale."""
     import torch
     spans = [(int(a), int(b)) for a, b in spans]
-    if torch.is_tensor(est_local):
-        cuts = np.concatenate([[0], np.cumsum([b - a for a, b in spans])])
-        if int(cuts[-1]) != len(est_local):
-            raise ValueError("estimate_scale: %d frames of poses for spans of %d frames" % (len(est_local), int(cuts[-1])))
-        est_local = [est_local[lo:hi] for lo, hi in zip(cuts[:-1], cuts[1:])]
-    est_local = list(est_local)
-    if len(est_local) != len(spans) or any(len(x) != b - a for x, (a, b) in zip(est_local, spans)):
-        raise ValueError("estimate_scale: one tensor of end - start frames per span is needed")
-    if not spans:
-        raise ValueError("estimate_scale: no frames, so no pairs (0 pairs, 0 inliers, 0 informative)")
-    R, c, ids = selected_poses(rows_or_text, spans, fps)
+    if tracked:
+        est_local, R, c, ids = tracked_poses(est_local, rows_or_text, spans, fps)
+    else:
+        if torch.is_tensor(est_local):
+            cuts = np.concatenate([[0], np.cumsum([b - a for a, b in spans])])
+            if int(cuts[-1]) != len(est_local):
+                raise ValueError("estimate_scale: %d frames of poses for spans of %d frames" % (len(est_local), int(cuts[-1])))
+            est_local = [est_local[lo:hi] for lo, hi in zip(cuts[:-1], cuts[1:])]
+        est_local = list(est_local)
+        if len(est_local) != len(spans) or any(len(x) != b - a for x, (a, b) in zip(est_local, spans)):
+            raise ValueError("estimate_scale: one tensor of end - start frames per span is needed")
+        if not spans:
+            raise ValueError("estimate_scale: no frames, so no pairs (0 pairs, 0 inliers, 0 informative)")
+        R, c, ids = selected_poses(rows_or_text, spans, fps)
     lag = default_lag(fps) if lag is None else int(lag)
     rc, report, costs, msg = scale_call(est_local, R, c, ids, lag, tau, min_pairs, feet, stream)
     if rc in (_capi.SCALE_NO_PAIRS, _capi.SCALE_TOO_FEW, _capi.SCALE_BAD_SCALE):
@@ -232,12 +251,8 @@ def _cli(argv=None):
     if a.heatmaps is not None:
         rec = prepare.prepare_spans(a.slam, a.heatmaps, a.depths, None, spans, a.fps, a.start, a.camera, scale="auto", **options)
     else:
-        det = detections.read_detections(a.keypoints, a.first_id)
-        if a.depth is not None:
-            det["depth"] = detections._depth_array(np.load(a.depth, allow_pickle=False), len(det["keypoints"]), a.depth)
-        elif a.depths is not None:
-            det["depth"] = detections.depths_from_mat_dir(a.depths, det["frame_ids"])
-        rec = detections.recording_from_detections(a.slam, det, None, "auto", spans, a.fps, camera_model_path=a.camera, **options)
+        rec = detections.recording_from_detections(a.slam, detections.detections_from_args(a), None, "auto", spans, a.fps,
+                                                   camera_model_path=a.camera, **options)
     est = rec.scale_report
     print(est.line())
     out = est.as_dict()

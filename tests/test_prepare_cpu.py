@@ -401,3 +401,76 @@ def test_scale_from_head_joints_is_the_scale_from_whole_skeletons(golden):
         m1, R1, t1 = slam.camera_pose_list_from_heads(text, loc[:, 0], gt[:, 0], a, b, fps)
         assert np.array_equal(m0, m1) and np.array_equal(R0, R1) and np.array_equal(t0, t1)
         np.testing.assert_allclose(m1, g["camera_pose_list_" + tag], rtol=0, atol=1e-12)
+
+
+# ------------------------------------------------------------------------------------------------ the two preparation command lines
+SHARED_OPTIONS = ("slam", "gt", "scale", "bridge", "start", "end", "fps", "mat_start", "test_size", "out", "camera", "optimize")
+OWN_ARGUMENTS = {"prepare": ["--heatmaps", "h", "--depths", "d"], "detections": ["--keypoints", "k"]}
+
+
+def test_the_preparation_parsers_share_their_options():
+    from globalegomocap_amd import detections, prepare
+    from globalegomocap_amd.camera import DEFAULT_CALIBRATION
+    parsers = {"prepare": prepare._parser(), "detections": detections._parser()}
+    actions = {m: {a.dest: a for a in p._actions} for m, p in parsers.items()}
+    for dest in SHARED_OPTIONS:
+        a, b = actions["prepare"][dest], actions["detections"][dest]
+        assert (a.option_strings, a.default, a.help, a.required, a.nargs, a.const, a.metavar) == \
+            (b.option_strings, b.default, b.help, b.required, b.nargs, b.const, b.metavar), dest
+    a = actions["prepare"]
+    assert (a["fps"].default, a["test_size"].default, a["camera"].default, a["bridge"].const) == (25, 100, DEFAULT_CALIBRATION, 1.0)
+    assert all(a[d].default is None for d in ("gt", "scale", "bridge", "mat_start", "out")) and a["optimize"].default is False
+    full = ["--slam", "t", "--scale", "auto", "--bridge", "0.4", "--start", "3", "--end", "90", "--fps", "30", "--mat_start", "2", "--test_size", "20",
+            "--out", "o", "--camera", "c.json", "--optimize"]
+    parsed = {m: vars(p.parse_args(OWN_ARGUMENTS[m] + full)) for m, p in parsers.items()}
+    want = dict(slam="t", gt=None, scale="auto", bridge=0.4, start=3, end=90, fps=30.0, mat_start=2, test_size=20, out="o", camera="c.json",
+                optimize=True)
+    for m in parsers:
+        assert {d: parsed[m][d] for d in SHARED_OPTIONS} == want, m
+
+
+@pytest.mark.parametrize("module", ["prepare", "detections"])
+def test_the_preparation_command_lines_refuse_what_they_refused(module, capsys):
+    """Before any file is opened."""
+    import importlib
+    m = importlib.import_module("globalegomocap_amd." + module)
+    base = OWN_ARGUMENTS[module] + ["--slam", "t", "--start", "0", "--end", "9"]
+    for argv, message in ((base + ["--gt", "g", "--bridge", "--out", "o"],
+                           "error: --bridge needs --scale: with --gt every chunk has its own scale and there is no common world to bridge in"),
+                          (base + ["--scale", "1"], "error: nothing to do: give --out, --optimize or both"),
+                          (base + ["--gt", "g", "--scale", "1", "--out", "o"], "error: argument --scale: not allowed with argument --gt"),
+                          (base + ["--out", "o"], "error: one of the arguments --gt --scale is required")):
+        with pytest.raises(SystemExit) as e:
+            m._cli(argv)
+        assert e.value.code == 2 and capsys.readouterr().err.rstrip().endswith(message), argv
+
+
+def _stub_recording(P, mpjpe=(None, None), reports=False):
+    """Two chunks of host-only stubs: nothing of them is on a device, and nothing but their frame range and error is printed."""
+    from globalegomocap_amd import _capi, slam_bridge, slam_scale
+    chunks = [P.RecordingChunk(a, a + 26, None, np.zeros((26, 15, 3)), None, None, None, initial_mpjpe=e) for a, e in zip((0, 26), mpjpe)]
+    if not reports:
+        return P.Recording(chunks)
+    scale = slam_scale.ScaleEstimate(np.arange(_capi.SCALE_REPORT_DOUBLES + 3 * 2, dtype=np.float64))
+    bridge = slam_bridge.BridgeReport(np.zeros(_capi.BRIDGE_RECORD_DOUBLES), np.zeros(52, dtype=bool), [], 25, 1.0)
+    return P.Recording(chunks, np.zeros((2, 4, 4)), scale.scale, scale, bridge)
+
+
+def test_the_report_printer(capsys):
+    from globalegomocap_amd import prepare as P
+    running = ["running test sequence from 0 to 26", "running test sequence from 26 to 52"]
+
+    def lines(rec, **kw):
+        capsys.readouterr()
+        P.print_report(rec, **kw)
+        return capsys.readouterr().out.splitlines()
+    rec = _stub_recording(P, reports=True)
+    reports = [rec.scale_report.line(), rec.bridge_report.line()]
+    assert reports[0].startswith("SLAM scale estimate: ") and reports[1].startswith("SLAM bridge: 0 of 0 frames invented in 0 gaps")
+    assert lines(rec) == reports + running          # (`prepare_sequence`, `detections`)
+    assert lines(rec, sequence=False) == reports          # (`main`)
+    rec = _stub_recording(P)
+    assert lines(rec) == running and lines(rec, sequence=False) == []
+    rec = _stub_recording(P, mpjpe=(0.0625, 0.125))
+    assert lines(rec) == [running[0], "The initial mpjpe is: 0.0625", running[1], "The initial mpjpe is: 0.125"]
+    assert lines(rec, sequence=False) == ["The initial mpjpe is: 0.0625", "The initial mpjpe is: 0.125"]

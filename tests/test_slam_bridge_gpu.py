@@ -251,3 +251,55 @@ def test_auto_scale_pairs_only_tracked_frames(env, tmp_path, capsys):
     cams = np.concatenate([np.einsum("ij,njk->nik", o, c.cpu().numpy()) for o, c in zip(rec.origins, rec.cams)])
     pos, rot = T.errors(cams, T.relative_truth(w), np.flatnonzero(~keep))
     assert pos.max() <= 0.08 and rot.max() <= 12.0
+
+
+def test_bridge_and_auto_scale_on_the_mat_route(env, tmp_path, capsys):
+    """`prepare` with scale="auto" and `bridge=` together: three 26-frame chunks of the pose network's files that carry a walker (the
+    recording of tests/test_slam_scale_gpu.py's prepare test), the trajectory without the lines of frame ids 30 .. 34, inside the second
+    chunk.  The estimate is made on the tracked frames alone and is the twin's on the lifted poses (whose discrete decisions must be
+    MARGIN from flipping: with this hole the smallest margin, the cost gap, is 1.1e-2), no pair reaches across the gap, exactly the five
+    frames are marked, and the recording is bit for bit the one the number gives."""
+    import torch
+    import slam_scale_twin as ST
+    from test_slam_scale_cpu import LAG
+    from test_slam_scale_gpu import MARGIN, RTOL
+    from globalegomocap_amd import prepare as P, slam, slam_scale as S, synth, synth_recording as R, synth_walk as W
+    from globalegomocap_amd.camera import FisheyeCamera
+    n, fps, size, min_pairs, lost = 78, 25, 26, 10, (30, 35)
+    w = W.walk(n, scale=0.6)
+    cam = FisheyeCamera.from_json(DEFAULT_CALIBRATION)
+    ix, iy = synth.heatmap_coords(cam.project_numpy(w["local"].reshape(-1, 3)).reshape(n, 15, 2))
+    centres = np.floor(np.stack([ix, iy], -1)) + np.array([0.3, 0.2])          # (no ties: the peak pixel is unique)
+    heat64 = R.paraboloid_heatmaps(centres, np.full((n, 15), 5.0))
+    hd, dd, traj, _ = R.write_recording(str(tmp_path / "rec"), heat64, w["depth"], ["f_%d.mat" % k for k in range(n)], None, None, w["rows"], None)
+    holed = _without_lines(traj, [lost], tmp_path / "holed.txt")
+    kw = dict(fps=fps, test_size=size, verbose=False)
+    with pytest.raises(ValueError, match=r"no line for frame ids \[30, 31, 32, 33, 34\]"):
+        P.prepare_sequence(holed, hd, dd, None, 0, n + 1, scale="auto", min_pairs=min_pairs, **kw)
+    rec = P.prepare_sequence(holed, hd, dd, None, 0, n + 1, scale="auto", min_pairs=min_pairs, bridge=True, **kw)
+    spans = P.chunk_spans(0, n + 1, size)
+    keep = np.ones(n, dtype=bool)
+    keep[lost[0]:lost[1]] = False
+    assert len(rec) == 3 and spans == [(0, 26), (26, 52), (52, 78)]
+    assert [len(b) for b in rec.bridged] == [size] * 3 and np.array_equal(np.concatenate(rec.bridged), ~keep)
+    assert (rec.bridge_report.lost, rec.bridge_report.gaps, rec.bridge_report.gap_ids) == (5, 1, [(30, 5)])
+    # the twin on the tracked frames' lifted poses, with the poses of the whole trajectory
+    with open(traj) as f:
+        Rm, c, ids = S.selected_poses(slam.trajectory_rows(f.read()), spans, fps)
+    x = np.concatenate([ch.est_local.cpu().numpy() for ch in rec.chunks])
+    cuts = np.concatenate([[0], np.cumsum([int(keep[a:b].sum()) for a, b in spans])])
+    want = ST.estimate(x[keep], Rm[keep], c[keep], ids[keep], S.default_lag(fps), min_pairs=min_pairs, chunk_starts=cuts)
+    m = want["margins"]
+    assert m["cost_gap"] > MARGIN and m["tau"] > MARGIN and m["sides"] > MARGIN and m["informative"] > MARGIN, m
+    est, tracked = rec.scale_report, np.flatnonzero(keep)
+    with capsys.disabled():
+        print("\nbridge + auto: %s; twin %r (relative difference %.3g), margins %s" % (est.line(), want["scale"], abs(est.scale / want["scale"] - 1), m))
+    assert est.pairs == int((tracked[LAG:] - tracked[:-LAG] == LAG).sum()) == n - (lost[1] - lost[0]) - 2 * LAG
+    assert (est.pairs, est.inliers, est.informative) == (want["pairs"], want["inliers"], want["informative"])
+    assert rec.scale == est.scale and abs(est.scale / want["scale"] - 1) <= RTOL
+    same = P.prepare_sequence(holed, hd, dd, None, 0, n + 1, scale=rec.scale, bridge=1.0, **kw)
+    assert same.scale is None and same.scale_report is None and np.array_equal(same.origins, rec.origins)
+    for a, b in zip(same.chunks, rec.chunks):
+        for k in ("heat", "est_local", "est_global", "cams"):
+            p, q = getattr(a, k), getattr(b, k)
+            assert p.dtype == q.dtype and torch.equal(p, q), k
