@@ -118,6 +118,7 @@ class GemBridgeRecord(C.Structure):
 
 BRIDGE_RECORD_DOUBLES, BRIDGE_MAX_GAP, BRIDGE_MAX_SPAN = 16, 64, 127
 BRIDGE_NOT_SOLVED = 2
+GLTF_LAYOUT = 40
 
 
 class GemWindowStats(C.Structure):
@@ -210,6 +211,9 @@ SIGNATURES = {
     "gem_bvh_rest": (C.c_int, [_P, C.c_int64, _P, _P, _P]),
     "gem_bvh_channels": (C.c_int, [_P, C.c_int64, _P, _P, C.c_double, _P, _P]),
     "gem_format_fields": (C.c_int, [_P, C.c_int64, C.c_int64, _P, _P, _P]),
+    "gem_gltf_layout": (C.c_int, [C.c_int64, C.POINTER(C.c_int64)]),
+    "gem_gltf_animation": (C.c_int, [_P, C.c_int64, _P, C.c_double, _P, _P, _P]),
+    "gem_gltf_rest_mesh": (C.c_int, [_P, _P, _P, _P]),
     "gem_jpeg_header": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, C.c_int64]),
     "gem_jpeg_bound": (C.c_int64, [C.c_int, C.c_int]),
     "gem_jpeg_encode": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, _P, C.c_int64, _P, _P, _P]),

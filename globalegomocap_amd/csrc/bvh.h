@@ -13,7 +13,8 @@
 // line and the spine, every other node turns its rest direction onto its one bone by the shortest arc; 15 points say nothing about
 // the twist about a bone.  The rest lengths are one workgroup's fixed-order sums (16 lanes per frame, one per bone): the same bits on
 // every call, no atomics, no scratch buffer.  For the channels one thread per frame walks the tree (float64, no fused multiply-adds), its joints and its channels in
-// LDS so that a workgroup's loads and stores are contiguous.  The text is one thread per field: the decimal digits come from the
+// LDS so that a workgroup's loads and stores are contiguous; the walk hands the root's position and every local rotation matrix to a
+// receiver (BvhEulerOut: the channels; gltf.h walks the same tree into quaternions).  The text is one thread per field: the decimal digits come from the
 // value's exact binary expansion in integer arithmetic (mantissa x 15625 in 128 bits, a shift, the remainder against one half, ties
 // to even), which is what C's printf and Python's % give; every field is one aligned 16-byte store.
 #pragma once
@@ -243,10 +244,30 @@ __device__ inline void bvh_matmul_tn(const double* A, const double* B, double* C
         for (int j = 0; j < 3; ++j) C[3 * i + j] = A[i] * B[j] + A[3 + i] * B[3 + j] + A[6 + i] * B[6 + j];
 }
 
+// What a frame's walk hands its results to: `position` the root's position, `rotation<N>` node N's local rotation matrix, `leaf<N>` a
+// node that has no rotation of its own.  BvhEulerOut makes the BVH file's channels of them (a thread's column in LDS): the position
+// times the unit scale, (Z, X, Y) Euler angles, three zeros for a leaf.  (gltf.h has the one that makes quaternions.)
+struct BvhEulerOut {
+    double* ch;
+    double unit_scale;
+    __device__ void position(const double* P) const {
+#pragma clang fp contract(off)
+#pragma unroll
+        for (int d = 0; d < 3; ++d) ch[d * BVH_FT] = P[d] * unit_scale;
+    }
+    template <int N>
+    __device__ void rotation(const double* R) const { bvh_euler(R, ch + bvh_channel(N) * BVH_FT); }
+    template <int N>
+    __device__ void leaf() const {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) ch[(bvh_channel(N) + k) * BVH_FT] = 0.0;
+    }
+};
+
 // Node N with its one child CHILD: G (on entry its parent's frame) becomes G S, S the shortest arc from CHILD's rest direction to
-// the bone as the parent's frame sees it; N's three angles go to ch (the thread's column of the channels).
-template <int N, int CHILD>
-__device__ inline void bvh_arc_node(const BvhLdsFrame& X, double* G, double* ch) {
+// the bone as the parent's frame sees it; S, N's local rotation, goes to out.
+template <int N, int CHILD, class Out>
+__device__ inline void bvh_arc_node(const BvhLdsFrame& X, double* G, Out& out) {
 #pragma clang fp contract(off)
     static_assert(BVH_PARENT[CHILD] == N && bvh_has_rest(CHILD), "CHILD hangs on N by a bone");
     const double r[3] = {BVH_REST[CHILD][0], BVH_REST[CHILD][1], BVH_REST[CHILD][2]};
@@ -265,30 +286,29 @@ __device__ inline void bvh_arc_node(const BvhLdsFrame& X, double* G, double* ch)
 #pragma unroll
         for (int i = 0; i < 9; ++i) G[i] = T[i];
     }
-    bvh_euler(S, ch + bvh_channel(N) * BVH_FT);
+    out.template rotation<N>(S);
 }
 
-// a limb: the three arc nodes A, A + 1, A + 2 under the frame G and the leaf A + 3 (no rotation of its own: three zeros)
-template <int A>
-__device__ inline void bvh_limb(const BvhLdsFrame& X, const double* G_parent, double* ch) {
+// a limb: the three arc nodes A, A + 1, A + 2 under the frame G and the leaf A + 3 (no rotation of its own)
+template <int A, class Out>
+__device__ inline void bvh_limb(const BvhLdsFrame& X, const double* G_parent, Out& out) {
     double G[9];
 #pragma unroll
     for (int i = 0; i < 9; ++i) G[i] = G_parent[i];
-    bvh_arc_node<A, A + 1>(X, G, ch);
-    bvh_arc_node<A + 1, A + 2>(X, G, ch);
-    bvh_arc_node<A + 2, A + 3>(X, G, ch);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) ch[(bvh_channel(A + 3) + k) * BVH_FT] = 0.0;
+    bvh_arc_node<A, A + 1>(X, G, out);
+    bvh_arc_node<A + 1, A + 2>(X, G, out);
+    bvh_arc_node<A + 2, A + 3>(X, G, out);
+    out.template leaf<A + 3>();
 }
 
-// One frame: X its moved joints, ch its 60 channels, both a thread's columns in LDS
-__device__ inline void bvh_walk_frame(const BvhLdsFrame& X, double unit_scale, double* ch) {
+// One frame: X its moved joints (a thread's columns in LDS), out what takes its position and local rotations
+template <class Out>
+__device__ inline void bvh_walk_frame(const BvhLdsFrame& X, Out& out) {
 #pragma clang fp contract(off)
     double P[3], a[3], b[3], G0[9], G1[9], G2[9], L[9];
     // Hips: its position, and the frame of the hip line (x, towards the left hip) and the direction to the neck
     bvh_pos<0>(X, P);
-#pragma unroll
-    for (int d = 0; d < 3; ++d) ch[d * BVH_FT] = P[d] * unit_scale;
+    out.position(P);
     bvh_pos<15>(X, a);
     bvh_pos<11>(X, b);
     double xd[3] = {a[0] - b[0], a[1] - b[1], a[2] - b[2]};
@@ -296,11 +316,11 @@ __device__ inline void bvh_walk_frame(const BvhLdsFrame& X, double unit_scale, d
     double up[3] = {a[0] - P[0], a[1] - P[1], a[2] - P[2]};
     bvh_identity(G0);
     bvh_frame_from(xd, up, G0);          // (degenerate: the identity stays)
-    bvh_euler(G0, ch + bvh_channel(0) * BVH_FT);
+    out.template rotation<0>(G0);
     // Spine: turns +Y onto the direction to the neck
 #pragma unroll
     for (int i = 0; i < 9; ++i) G1[i] = G0[i];
-    bvh_arc_node<1, 2>(X, G1, ch);
+    bvh_arc_node<1, 2>(X, G1, out);
     // Neck: the frame of the shoulder line (x, towards the left shoulder) and the spine's y axis
     bvh_pos<8>(X, a);
     bvh_pos<4>(X, b);
@@ -314,11 +334,11 @@ __device__ inline void bvh_walk_frame(const BvhLdsFrame& X, double unit_scale, d
         for (int i = 0; i < 9; ++i) G2[i] = G1[i];
         bvh_identity(L);
     }
-    bvh_euler(L, ch + bvh_channel(2) * BVH_FT);
-    bvh_limb<3>(X, G2, ch);           // right arm: collar, shoulder, elbow | wrist
-    bvh_limb<7>(X, G2, ch);           // left arm
-    bvh_limb<11>(X, G0, ch);          // right leg: hip, knee, ankle | foot
-    bvh_limb<15>(X, G0, ch);          // left leg
+    out.template rotation<2>(L);
+    bvh_limb<3>(X, G2, out);           // right arm: collar, shoulder, elbow | wrist
+    bvh_limb<7>(X, G2, out);           // left arm
+    bvh_limb<11>(X, G0, out);          // right leg: hip, knee, ankle | foot
+    bvh_limb<15>(X, G0, out);          // left leg
 }
 
 constexpr int BVH_XS = BVH_J * 3, BVH_CS = BVH_CHANNELS;    // numbers per frame in LDS, [number][thread]: conflict-free columns
@@ -339,7 +359,10 @@ __global__ __launch_bounds__(BVH_FT) void bvh_channels_kernel(const double* seq,
         for (int d = 0; d < 3; ++d) xs[(3 * j + d) * BVH_FT + fl] = q[d];
     }
     __syncthreads();
-    if (tx < nf) bvh_walk_frame(BvhLdsFrame{xs + tx}, unit_scale, cs + tx);
+    if (tx < nf) {
+        BvhEulerOut out{cs + tx, unit_scale};
+        bvh_walk_frame(BvhLdsFrame{xs + tx}, out);
+    }
     __syncthreads();
     double* out = channels + f0 * BVH_CHANNELS;
     for (int i = tx; i < nf * BVH_CHANNELS; i += BVH_FT) {

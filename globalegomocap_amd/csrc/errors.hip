@@ -446,6 +446,7 @@ int launch_lift(gem_handle* h, const float* heat, const double* depth, int F, co
 #include "latent_tools.h"              // gem_latent_paths, gem_latent_report
 #include "live.h"                      // gem_live_push, gem_live_window, gem_live_emit, gem_one_euro
 #include "bvh.h"                       // gem_bvh_rest, gem_bvh_channels, gem_format_fields
+#include "gltf.h"                      // gem_gltf_layout, gem_gltf_animation, gem_gltf_rest_mesh
 #include "jpeg.h"                      // gem_jpeg_header, gem_jpeg_bound, gem_jpeg_encode
 #include "keypoints.h"                 // gem_keypoint_heatmaps, gem_lift_keypoints, gem_fill_missing
 #include "slam_scale.h"                // gem_slam_scale_work, gem_slam_scale

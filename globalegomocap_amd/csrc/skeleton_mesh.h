@@ -80,6 +80,30 @@ struct MeshArgs {
     int lines[MESH_L][2];
 };
 
+// The cylinder of the line from joint s to joint e: bone = its rotation R (row-major, takes +z onto the line) and its centre, *bh its height
+__device__ inline void mesh_bone(const double* s, const double* e, double* bone, double* bh) {
+    const double d[3] = {e[0] - s[0], e[1] - s[1], e[2] - s[2]};
+    const double h = sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+    double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+    if (h != 0.0) {          // (a zero-length bone keeps the identity: the reference divides 0 by 0 here)
+        const double bx = d[0] / h, by = d[1] / h, bz = d[2] / h;
+        const double c1 = 1.0 + bz;
+        if (c1 <= 0x1p-40) {          // along -z: a half turn about x (the reference: 0 / 0)
+            R[4] = -1.0; R[8] = -1.0;
+        } else {
+            // rotation_matrix_from_vectors((0,0,1), b): v = z x b = (-by, bx, 0), K = [v]x, R = I + K + K K / (1 + c)
+            // (the reference's (1 - c) / s^2 is 1 / (1 + c), without its 0 / 0 on the axis); NaN passes through
+            const double k = 1.0 / c1;
+            R[0] = 1.0 - bx * bx * k; R[1] = -(bx * by) * k;     R[2] = bx;
+            R[3] = -(bx * by) * k;    R[4] = 1.0 - by * by * k;  R[5] = by;
+            R[6] = -bx;               R[7] = -by;                R[8] = 1.0 - (bx * bx + by * by) * k;
+        }
+    }
+    for (int i = 0; i < 9; ++i) bone[i] = R[i];
+    for (int i = 0; i < 3; ++i) bone[9 + i] = (s[i] + e[i]) / 2;
+    *bh = h;
+}
+
 // Vertex v of a frame: its position and its colour word.  jt: the frame's joints; bone: per line R (row-major) and the centre; bh: heights.
 __device__ inline void mesh_vertex(int v, const double (*jt)[3], const double (*bone)[12], const double* bh, double* o, uint32_t* rgb) {
     if (v < MESH_J * SPH_V) {
@@ -126,30 +150,7 @@ __global__ __launch_bounds__(MESH_THREADS) void skeleton_mesh_kernel(MeshArgs a)
         for (int d = 0; d < 3; ++d) jt[tid][d] = q[d];
     }
     __syncthreads();
-    if (tid < MESH_L) {
-        const double* s = jt[a.lines[tid][0]];
-        const double* e = jt[a.lines[tid][1]];
-        const double d[3] = {e[0] - s[0], e[1] - s[1], e[2] - s[2]};
-        const double h = sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-        double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-        if (h != 0.0) {          // (a zero-length bone keeps the identity: the reference divides 0 by 0 here)
-            const double bx = d[0] / h, by = d[1] / h, bz = d[2] / h;
-            const double c1 = 1.0 + bz;
-            if (c1 <= 0x1p-40) {          // along -z: a half turn about x (the reference: 0 / 0)
-                R[4] = -1.0; R[8] = -1.0;
-            } else {
-                // rotation_matrix_from_vectors((0,0,1), b): v = z x b = (-by, bx, 0), K = [v]x, R = I + K + K K / (1 + c)
-                // (the reference's (1 - c) / s^2 is 1 / (1 + c), without its 0 / 0 on the axis); NaN passes through
-                const double k = 1.0 / c1;
-                R[0] = 1.0 - bx * bx * k; R[1] = -(bx * by) * k;     R[2] = bx;
-                R[3] = -(bx * by) * k;    R[4] = 1.0 - by * by * k;  R[5] = by;
-                R[6] = -bx;               R[7] = -by;                R[8] = 1.0 - (bx * bx + by * by) * k;
-            }
-        }
-        for (int i = 0; i < 9; ++i) bone[tid][i] = R[i];
-        for (int i = 0; i < 3; ++i) bone[tid][9 + i] = (s[i] + e[i]) / 2;
-        bh[tid] = h;
-    }
+    if (tid < MESH_L) mesh_bone(jt[a.lines[tid][0]], jt[a.lines[tid][1]], bone[tid], &bh[tid]);
     __syncthreads();
     if (tid < MESH_SLICE_V / MESH_GROUP) {
         uint32_t w[MESH_GROUP * MESH_REC / 4 + 1];          // 27 words (+ one that only ever receives zeros)
@@ -205,6 +206,23 @@ inline void mesh_put_triangle(unsigned char*& p, uint32_t off, uint32_t a, uint3
     *p++ = 3;
     std::memcpy(p, v, 12);          // (little-endian host, like every reader of this library's files)
     p += 12;
+}
+
+// the unit templates on the current device: filled once on the host (libm), uploaded once per device
+inline int mesh_upload_table() {
+    static std::mutex mu;
+    static bool uploaded[64] = {};
+    static double table[MESH_TABLE];
+    static bool filled = false;
+    int dev = 0;
+    GEM_HIP(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lock(mu);
+    if (!filled) { mesh_fill_table(table); filled = true; }
+    if (dev < 0 || dev >= 64 || !uploaded[dev]) {
+        GEM_HIP(hipMemcpyToSymbol(HIP_SYMBOL(mesh_table), table, sizeof(table)));
+        if (dev >= 0 && dev < 64) uploaded[dev] = true;
+    }
+    return 0;
 }
 
 }  // namespace gem
@@ -281,21 +299,7 @@ int gem_skeleton_mesh(const double* d_seq, int64_t n_frames, const double* d_crt
     if (n_frames == 0) return 0;
     if (!d_seq || !d_vertex_blocks) { set_error("gem_skeleton_mesh: null argument"); return 1; }
     if (n_frames > 0x7fffffffll / MESH_SLICES) { set_error("gem_skeleton_mesh: too many frames for one launch"); return 1; }
-    // the unit templates: filled once on the host (libm), uploaded once per device
-    static std::mutex mu;
-    static bool uploaded[64] = {};
-    static double table[MESH_TABLE];
-    static bool filled = false;
-    int dev = 0;
-    GEM_HIP(hipGetDevice(&dev));
-    {
-        std::lock_guard<std::mutex> lock(mu);
-        if (!filled) { mesh_fill_table(table); filled = true; }
-        if (dev < 0 || dev >= 64 || !uploaded[dev]) {
-            GEM_HIP(hipMemcpyToSymbol(HIP_SYMBOL(mesh_table), table, sizeof(table)));
-            if (dev >= 0 && dev < 64) uploaded[dev] = true;
-        }
-    }
+    if (int rc = gem::mesh_upload_table()) return rc;
     MeshArgs a;
     a.seq = d_seq; a.crt = d_crt; a.out = static_cast<unsigned char*>(d_vertex_blocks); a.stride = frame_stride_bytes;
     for (int l = 0; l < MESH_L; ++l) { a.lines[l][0] = MESH_LINES[l][0]; a.lines[l][1] = MESH_LINES[l][1]; }

@@ -191,7 +191,7 @@ def main(data_id, camera_model_path, vae_weight, gmm_weight, smoothness_weight, 
          reproj_weight, visualization=False, final_smooth=False, merge=True, save=False, save_pose=False,
          global_vae_path=GLOBAL_VAE_PATH, local_vae_path=LOCAL_VAE_PATH, eps=None, optimizer=None, return_stats=False,
          device_metrics=False, mesh_root="out", render=None, render_camera=None, bvh=None, bvh_fps=None, *, upright=False, foot_height=None,
-         foot_lock=False, foot_lock_stretch=None, foot_lock_blend=None):
+         foot_lock=False, foot_lock_stretch=None, foot_lock_blend=None, gltf=None, gltf_fps=None):
     """pickle in, poses out -- the reference's `main` (optimizer.py:311-507) for one chunk directory.
 
     Returns (errors OrderedDict[18], final_estimated_seq, mid_local_pose_seq, final_optimized_seq, final_gt_seq): lists of [15,3]
@@ -213,6 +213,9 @@ def main(data_id, camera_model_path, vae_weight, gmm_weight, smoothness_weight, 
     sequence with its standing feet pinned to the floor and the legs re-solved (`foot_lock.lock_feet`); the
     errors then have the entry `foot_lock` (`FootLock.as_dict`), its line is printed, and with save_pose result_pose.pkl holds
     `foot_locked_pose`.  The returned poses and the 18 errors are those of the optimiser's own sequence.
+    gltf=DIR (keyword only, with gltf_fps) writes the three sequences as ONE glTF binary file of skinned, animated skeletons,
+    DIR/<dataset>/<chunk>/result.glb at `gltf_fps` keys per second (default 25), the first two aligned to the ground truth
+    (`gltf.write_result_gltf`); `upright` and `foot_lock` apply to it as to the BVH files.
     """
     if visualization:
         raise NotImplementedError("visualization opens open3d's viewer (optimizer.py:452-467), which this package does not have: "
@@ -250,7 +253,8 @@ def main(data_id, camera_model_path, vae_weight, gmm_weight, smoothness_weight, 
         final_optimized_seq = _smooth(final_optimized_seq)
     outputs = Outputs(mesh_root if save else None, render, render_camera, bvh, bvh_fps, upright=upright if upright else None,
                       upright_foot_height=foot_height if upright else None,
-                      **(dict(foot_lock=True, foot_lock_stretch=foot_lock_stretch, foot_lock_blend=foot_lock_blend) if foot_lock else {}))
+                      **(dict(foot_lock=True, foot_lock_stretch=foot_lock_stretch, foot_lock_blend=foot_lock_blend) if foot_lock else {}),
+                      **(dict(gltf=gltf, gltf_fps=gltf_fps) if gltf is not None else {}))
     lock = outputs.lock(opt.engine, final_optimized_d if device_metrics else np.asarray(final_optimized_seq))          # (None without foot_lock)
     if save_pose:
         # optimizer.py:469-483: out/<dataset>/<sequence>/result_pose.pkl under the working directory

@@ -4,12 +4,12 @@
 batch pipeline (`whole_sequence`) and the one-chunk `optimizer.main`; it imports neither."""
 import os
 from collections import OrderedDict
-from dataclasses import dataclass
+from dataclasses import FrozenInstanceError, dataclass
 
 import numpy as np
 import torch
 
-from . import bvh as animation, meshes, render as rendering, video as clips          # (`bvh`, `render` and `video` are also fields' names here)
+from . import bvh as animation, gltf as scenes, meshes, render as rendering, video as clips          # (`bvh`, `render` and `video` are also fields' names here)
 from .errors import calculate_errors
 from .sequence import cut_windows, merge_batches, merge_chunks, final_smooth, relative_global_numpy, to_global_numpy
 
@@ -218,7 +218,26 @@ def result_dir(root, data_id):
 
 
 @dataclass(frozen=True)
-class Outputs:
+class _OutputFields:
+    """The dataclass fields of `Outputs`, in their order."""
+    mesh_root: object = None
+    render: object = None
+    render_camera: object = None
+    bvh: object = None
+    bvh_fps: object = None
+    video: object = None
+    video_camera: object = None
+    video_fps: object = None
+    video_quality: object = None
+    foot_lock: object = None
+    foot_lock_stretch: object = None
+    foot_lock_blend: object = None
+    upright: object = None
+    upright_foot_height: object = None
+    upright_lag: object = None
+
+
+class Outputs(_OutputFields):
     """Which files a chunk's result is written to, and how: a root directory per kind (None: not asked for), each chunk's files
     under `result_dir` of that root.
       mesh_root      the skeleton meshes, <chunk>/{optimized,input,gt}_global_aligned/out_%04d.ply (`meshes.write_result_meshes`);
@@ -241,25 +260,40 @@ class Outputs:
                      files; the estimated sequence stays as it is, the "before".  `foot_lock_stretch`: how much longer a straight leg may
                      become to hold its pin (default 0.05); `foot_lock_blend`: frames over which a correction is eased in and out (default
                      0.12 s at `bvh_fps`); the contact rule's lag is `upright_lag`.  Ground truth, alignment and `upright` work as before,
-                     on the locked sequence."""
-    mesh_root: object = None
-    render: object = None
-    render_camera: object = None
-    bvh: object = None
-    bvh_fps: object = None
-    video: object = None
-    video_camera: object = None
-    video_fps: object = None
-    video_quality: object = None
-    foot_lock: object = None
-    foot_lock_stretch: object = None
-    foot_lock_blend: object = None
-    upright: object = None
-    upright_foot_height: object = None
-    upright_lag: object = None
+                     on the locked sequence.
+      gltf           the sequences as ONE file of skinned, animated skeletons, <chunk>/result.glb at `gltf_fps` keys per second (default
+                     25; `gltf.write_result_gltf`); `upright` and `foot_lock` apply to it as to the BVH files.
+    `gltf` and `gltf_fps` go by keyword only; the positional order, and with it the list of dataclass fields, is closed."""
+
+    def __init__(self, *args, gltf=None, gltf_fps=None, **kwargs):
+        super().__init__(*args, **kwargs)
+        object.__setattr__(self, "gltf", gltf)          # (the record is frozen: like the fields, set once, here)
+        object.__setattr__(self, "gltf_fps", gltf_fps)
+
+    def __setattr__(self, name, value):
+        raise FrozenInstanceError("cannot assign to field %r" % name)
+
+    def __delattr__(self, name):
+        raise FrozenInstanceError("cannot delete field %r" % name)
+
+    def _key(self):
+        return tuple(getattr(self, f) for f in self.__dataclass_fields__) + (self.gltf, self.gltf_fps)
+
+    def __eq__(self, other):
+        return self._key() == other._key() if other.__class__ is self.__class__ else NotImplemented
+
+    def __hash__(self):
+        return hash(self._key())
+
+    def __repr__(self):
+        return "Outputs(%s)" % ", ".join("%s=%r" % (f, getattr(self, f)) for f in list(self.__dataclass_fields__) + ["gltf", "gltf_fps"])
+
+    def _posed(self):
+        """The roots of the files that show the sequences in space: what `upright` and `foot_lock` apply to."""
+        return (self.mesh_root, self.render, self.bvh, self.video, self.gltf)
 
     def __bool__(self):
-        return any(root is not None for root in (self.mesh_root, self.render, self.render_camera, self.bvh, self.video, self.video_camera))
+        return any(root is not None for root in (self.mesh_root, self.render, self.render_camera, self.bvh, self.video, self.video_camera, self.gltf))
 
     @property
     def needs_frames(self):
@@ -294,12 +328,12 @@ class Outputs:
         est, opt, gt = sequences
         bvh_fps, video_fps, video_quality = self._rates()
         shown = opt          # (the camera's views show the optimiser's own result)
-        if self.foot_lock and any(r is not None for r in (self.mesh_root, self.render, self.bvh, self.video)):
+        if self.foot_lock and any(r is not None for r in self._posed()):
             opt = (self.lock(engine, opt) if locked is None else locked).sequence
         clip = dict(video_fps=video_fps, video_quality=video_quality, frames=False)
         frames = slice(first_frame, first_frame + len(est))
         found, extra = None, {}
-        if self.upright is not None and self.upright is not False and any(r is not None for r in (self.mesh_root, self.render, self.bvh, self.video)):
+        if self.upright is not None and self.upright is not False and any(r is not None for r in self._posed()):
             from . import ground
             options = {} if self.upright is not True else dict(fps=bvh_fps, lag=self.upright_lag,
                                                                 foot_height=0.0 if self.upright_foot_height is None else self.upright_foot_height)
@@ -313,6 +347,9 @@ class Outputs:
             rendering.write_result_camera_frames(engine, result_dir(self.render_camera, data_id), est, shown, cams[frames], heat[frames], gt)
         if self.bvh is not None:
             animation.write_result_bvh(engine, result_dir(self.bvh, data_id), est, opt, gt, fps=bvh_fps, **extra)
+        if self.gltf is not None:
+            scenes.write_result_gltf(engine, result_dir(self.gltf, data_id), est, opt, gt,
+                                     fps=scenes.DEFAULT_FPS if self.gltf_fps is None else self.gltf_fps, **extra)
         if self.video is not None:
             rendering.write_result_frames(engine, None, est, opt, gt, video=os.path.join(result_dir(self.video, data_id), "frames.avi"), **clip,
                                           **extra)

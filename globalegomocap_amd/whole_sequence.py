@@ -308,10 +308,10 @@ def _settings(camera_model_path, vae_weight=0.0, gmm_weight=0.0, smoothness_weig
               chunks_per_batch=None, optimizer=None, device_metrics=True, verbose=True, seq_len=SEQ_LEN, overlap=OVERLAP, timings=None,
               per_sequence=False, ground_truth=True, save_pose=None, save=False, mesh_root="out", render=None, render_camera=None, bvh=None,
               bvh_fps=None, *, video=None, video_camera=None, video_fps=None, video_quality=None, upright=False, foot_height=None,
-              foot_lock=False, foot_lock_stretch=None, foot_lock_blend=None):
+              foot_lock=False, foot_lock_stretch=None, foot_lock_blend=None, gltf=None, gltf_fps=None):
     """The arguments of `optimize_sequences` / `optimize_recordings` behind the sequences themselves, as one object; `outputs`: the
-    files asked for (`report.Outputs`, checked here).  The clip arguments, `upright` / `foot_height` and `foot_lock` with its two
-    options go by keyword only.
+    files asked for (`report.Outputs`, checked here).  The clip arguments, `upright` / `foot_height`, `foot_lock` with its two
+    options and `gltf` / `gltf_fps` go by keyword only.
     (`gmm_weight` and `merge` are accepted and unused, as in the reference: SURVEY D4.)"""
     if foot_height is not None and not np.isfinite(foot_height):
         raise ValueError("foot_height must be a finite number of metres, got %r" % (foot_height,))
@@ -319,9 +319,12 @@ def _settings(camera_model_path, vae_weight=0.0, gmm_weight=0.0, smoothness_weig
         raise ValueError("foot_lock_stretch must be a finite number that is not negative, got %r" % (foot_lock_stretch,))
     if foot_lock_blend is not None and not foot_lock_blend >= 1:
         raise ValueError("foot_lock_blend must be at least one frame, got %r" % (foot_lock_blend,))
+    if gltf_fps is not None and not (np.isfinite(gltf_fps) and gltf_fps > 0):
+        raise ValueError("gltf_fps must be a finite positive number, got %r" % (gltf_fps,))
     outputs = Outputs(mesh_root if save else None, render, render_camera, bvh, bvh_fps, video, video_camera, video_fps, video_quality,
                       upright=upright if upright else None, upright_foot_height=foot_height if upright else None,
-                      **(dict(foot_lock=True, foot_lock_stretch=foot_lock_stretch, foot_lock_blend=foot_lock_blend) if foot_lock else {}))
+                      **(dict(foot_lock=True, foot_lock_stretch=foot_lock_stretch, foot_lock_blend=foot_lock_blend) if foot_lock else {}),
+                      **(dict(gltf=gltf, gltf_fps=gltf_fps) if gltf is not None else {}))
     outputs.check()
     if not ground_truth and not device_metrics:
         raise ValueError("ground_truth=False: the report without ground truth is computed on the device only (device_metrics=True)")
@@ -587,7 +590,7 @@ def optimize_sequences(data_dirs, camera_model_path, *args, **kwargs):
     bone_length_weight, weight_3d, reproj_weight, final_smooth, merge, global_vae_path, local_vae_path, chunks_per_batch, optimizer,
     device_metrics, verbose, seq_len, overlap, timings, per_sequence, ground_truth, save_pose, save, mesh_root, render, render_camera,
     bvh, bvh_fps; and by keyword only: video, video_camera, video_fps, video_quality, upright, foot_height, foot_lock,
-    foot_lock_stretch, foot_lock_blend.
+    foot_lock_stretch, foot_lock_blend, gltf, gltf_fps.
 
     ground_truth=False: the chunks carry no ground truth (`prepare` with a scale).  Their pickles are not asked for
     `gt_global_skeleton`, every chunk's report is the seven entries of QUALITY_KEYS (`WindowEngine.sequence_quality` on the estimated
@@ -623,7 +626,12 @@ def optimize_sequences(data_dirs, camera_model_path, *args, **kwargs):
     a straight leg may become to hold its pin, default 0.05; foot_lock_blend: frames over which a correction is eased in and out,
     default 0.12 s at `bvh_fps`); the estimated sequence stays as it is.  Every chunk's report dict then has the entry `foot_lock`
     (`FootLock.as_dict`), one line per chunk is printed, and result_pose.pkl holds `foot_locked_pose`.  The returned poses, the
-    errors and the report are those of the optimiser's own sequence."""
+    errors and the report are those of the optimiser's own sequence.
+    gltf=DIR: every chunk as ONE glTF binary file, `DIR/<dataset>/<chunk>/result.glb`: the estimated (red), the optimised (blue) and the
+    ground-truth sequence (green) as skinned meshes on the BVH files' skeleton, the first two aligned to the third, all driven by one
+    animation keyed at every frame at `gltf_fps` keys per second (default 25; `gltf.write_result_gltf`, made on the device, DESIGN.md
+    section 6p).  With ground_truth=False: two skeletons, unaligned.  `upright` and `foot_lock` apply to it as to the BVH files.
+    Results and reports do not depend on it."""
     cfg = _settings(camera_model_path, *args, **kwargs)
     lap = Laps(cfg.timings, log=True)          # developer timing (tools/whole_sequence_timing.py): wall time of the main thread's phases
     groups = []
@@ -666,12 +674,13 @@ def release_pools():
     """Give back what this module keeps between calls: the per-device frame buffers the readers fill, the pinned noise
     blocks and the mesh and frame writers' buffers, then (`staging.release`) the streams and the reader threads with their pinned staging buffers and device images.
     Not to be called while another call is in flight."""
-    from . import bvh, meshes, render, video
+    from . import bvh, gltf, meshes, render, video
     _heat_pool.clear()
     _noise_pool.clear()
     meshes.release()
     render.release()
     bvh.release()
+    gltf.release()
     video.release()
     staging.release()
     if torch.cuda.is_available():
@@ -698,6 +707,9 @@ def _parser():
                    help="write every chunk as its camera saw it, DIR/<dataset>/<chunk>/camera_%%04d.png: heat-maps under the reprojected skeletons")
     p.add_argument("--bvh", default=None, metavar="DIR", help="write every chunk as animation, DIR/<dataset>/<chunk>/{estimated,optimized,gt}.bvh")
     p.add_argument("--bvh_fps", default=None, type=float, metavar="F", help="frames per second of the --bvh files (default 25)")
+    p.add_argument("--gltf", default=None, metavar="DIR",
+                   help="write every chunk as one glTF binary file of skinned, animated skeletons, DIR/<dataset>/<chunk>/result.glb")
+    p.add_argument("--gltf_fps", default=None, type=float, metavar="F", help="keys per second of the --gltf files (default 25)")
     p.add_argument("--video", default=None, metavar="DIR", help="write every chunk's frames as one Motion-JPEG clip, DIR/<dataset>/<chunk>/frames.avi")
     p.add_argument("--video_camera", default=None, metavar="DIR", help="write every chunk as its camera saw it as one clip, DIR/<dataset>/<chunk>/camera.avi")
     p.add_argument("--video_fps", default=None, type=float, metavar="F", help="frames per second of the clips (default 25)")
@@ -726,12 +738,15 @@ def _cli(argv=None):
         p.error("argument --video_fps: must be positive")
     if a.video_quality is not None and not 1 <= a.video_quality <= 100:
         p.error("argument --video_quality: a whole number 1 .. 100")
+    if a.gltf_fps is not None and not (np.isfinite(a.gltf_fps) and a.gltf_fps > 0):
+        p.error("argument --gltf_fps: must be positive")
     optimize_directory(a.data_path, a.camera, a.vae, a.gmm, a.smooth, a.bone_length, a.weight_3d, a.reproj_weight,
                        final_smooth=a.final_smooth, merge=a.merge, chunks_per_batch=a.chunks_per_batch, ground_truth=a.ground_truth,
                        save_pose=a.save_pose, save=a.save, mesh_root=a.mesh_root, render=a.render, render_camera=a.render_camera, bvh=a.bvh,
                        bvh_fps=a.bvh_fps, video=a.video, video_camera=a.video_camera, video_fps=a.video_fps, video_quality=a.video_quality,
                        **(dict(upright=True, foot_height=a.foot_height) if a.upright else {}),
-                       **(dict(foot_lock=True, foot_lock_stretch=a.foot_lock_stretch, foot_lock_blend=a.foot_lock_blend) if a.foot_lock else {}))
+                       **(dict(foot_lock=True, foot_lock_stretch=a.foot_lock_stretch, foot_lock_blend=a.foot_lock_blend) if a.foot_lock else {}),
+                       **(dict(gltf=a.gltf, gltf_fps=a.gltf_fps) if a.gltf is not None else {}))
 
 
 if __name__ == "__main__":

@@ -708,6 +708,42 @@ int gem_bvh_channels(const double* d_seq, int64_t n_frames, const double* d_crt,
  * back.  d_text must be 16-byte aligned: anything else is refused before the launch.  Works on the current device. */
 int gem_format_fields(const double* d_values, int64_t n_values, int64_t values_per_line, void* d_text, int64_t* d_bad, void* stream);
 
+/* ---- Results as one glTF 2.0 binary file: skinned, animated skeletons: `gltf=DIR` / `--gltf DIR` ----
+ * The file's skeleton is the BVH route's tree of 19 nodes above; its 15 rotating nodes are the root and every node with a child (all but
+ * the wrists and feet).  The mesh is the geometry of gem_skeleton_mesh: 12 960 vertices, 25 800 triangles.
+ * gem_gltf_layout: out[40] = nodes (19), rotating nodes (15), vertices, triangles, bytes per vertex (32), bytes of a vertex block
+ * (414 720); the 15 rotating nodes in node order; the byte offsets of the 17 arrays of an animation block of n_frames frames --
+ * times [F] f32, translation [F,3] f32, one rotation [F,4] f32 (x, y, z, w) per rotating node; every array tightly packed, every start
+ * a multiple of 16 --; the block's size; the payload per frame (256 bytes).  Needs no GPU. */
+int gem_gltf_layout(int64_t n_frames, int64_t* out);
+
+/* The animation block of d_seq [n_frames,15,3] float64 behind d_crt [13] (or NULL), as in gem_bvh_channels, into d_block (16-byte aligned,
+ * the size gem_gltf_layout gives): times[f] = (double)f / fps, translation[f] = the Hips' position P in metres, and per rotating node the
+ * local rotation matrix R that gem_bvh_channels turns into angles, with the same defined corners, as a quaternion:
+ *   1. Shepperd's method on the largest of (trace, R00, R11, R22), the first on ties: with r = sqrt(1 + trace), w = r / 2 and
+ *      (x, y, z) = (R21 - R12, R02 - R20, R10 - R01) / (2 r); with r = sqrt(1 + R00 - R11 - R22), x = r / 2 and
+ *      (w, y, z) = (R21 - R12, R01 + R10, R02 + R20) / (2 r); the other two likewise;
+ *   2. the canonical sign c: the first non-zero of (w, x, y, z) is positive;
+ *   3. the sign from key to key: s[0] = +1, s[f] = -s[f-1] where c[f] . c[f-1] < 0 and else s[f-1] (a dot of 0 or NaN does not flip);
+ *      s[f] c[f] is written.
+ * float64 without fused multiply-adds; every number is rounded once, to float32; nothing is renormalised.  The bytes are the same on
+ * every call.  Every frame with a number that is not finite adds one to d_bad[0] and lowers d_bad[1] to its index: the caller sets
+ * d_bad to {0, -1} beforehand.  Three launches on `stream`; no read-back, no synchronisation, no scratch memory.  n_frames < 0, an fps
+ * that is not finite and positive, a misaligned block and (with n_frames > 0) null pointers are refused before the launch;
+ * n_frames = 0 returns 0.  Works on the current device. */
+int gem_gltf_animation(const double* d_seq, int64_t n_frames, const double* d_crt, double fps, void* d_block, int64_t* d_bad, void* stream);
+
+/* The rest-pose mesh of the skeleton with the rest lengths d_rest [19] (gem_bvh_rest): the rest joints are the rest directions times
+ * the lengths, Hips at the origin; on them the 15 spheres and the 15 cylinders of gem_skeleton_mesh, same tables, same vertex order.
+ * d_vertices (16-byte aligned) takes 12 960 records of 32 bytes: position f32 x 3, normal f32 x 3 (a sphere's and a cylinder ring's
+ * radial, a cap centre's + or - the bone), JOINTS_0 u8 x 4, WEIGHTS_0 u8 x 4 (of 255).  A sphere is bound to its joint's node.  A
+ * cylinder is bound to the node its bone turns with: the parent of its second joint's node, Hips for the hip line (7, 11).  The torso
+ * lines (1, 7) and (4, 11) join two branches: their ring k of 5, counted from the line's SECOND joint as the vertices are, is bound to
+ * (the second joint's node, the first joint's node) with the weights (255 - w, w), w = 0, 64, 128, 191, 255, and each cap centre to its
+ * own end; a weight of 0 names node 0.  d_bounds [6] = the minimum (x, y, z) and the maximum of the float32 positions written.  One
+ * workgroup, the same bytes on every call.  Works on the current device. */
+int gem_gltf_rest_mesh(const double* d_rest, void* d_vertices, float* d_bounds, void* stream);
+
 /* ---- Rendered frames as baseline JPEG images and Motion-JPEG chunks: `video=PATH` / `--video DIR` ----
  * The format is fixed: 8-bit YCbCr (JFIF, full range), 4:4:4, one restart segment per MCU row, the Annex K quantisation tables scaled
  * by the IJG quality rule and the Annex K Huffman tables; integer arithmetic throughout, so the bytes are a function of the pixels
