@@ -10,6 +10,7 @@ from globalegomocap_amd import synth, vae as vae_schema
 from globalegomocap_amd.camera import FisheyeCamera, DEFAULT_CALIBRATION
 from oracle import np_oracle as O
 from helpers import TINY, FULL, oracle_camera, heat_from_centres, sd_from_npz, oracle_stage_losses
+from energy_f64 import terms64, bilinear
 
 pytestmark = pytest.mark.gpu
 
@@ -34,6 +35,20 @@ def _engine(shape, max_windows=16):
 def _ew(w):
     from globalegomocap_amd.engine import energy_weights
     return energy_weights(*w)
+
+
+def _check_parts_at_device_pose(parts_dev, X_dev, pose0, mb, heat_w, cam):
+    """The energy code alone, whatever the decoder's precision: the five parts against float64 (tests/energy_f64.py) AT THE POSE THE
+    DEVICE DECODED, 1e-5 relative per term (test_energy_terms_gpu.py, check (a)).  The reprojection term gets, on top, what the fp32
+    texel coordinate can cost on THESE heat-maps: the callers' random-weight decoders put the joints 5 .. 8 texels from their Gaussian
+    peaks (E_reproj ~ 1e-5 .. 1e-3), where a sample changes by r / sigma^2 ~ 3 of its value per texel; u = ux * rho + cx and the
+    three steps to the texel coordinate each round to half an ulp of a number below 1024 (6.1e-5 px): 4 * 0.5 * 6.1e-5 px * 63 / 1024
+    = 7.5e-6 texel per axis, times the sum of the samples' |slopes| (the fp32 oracle itself is 1.7e-5 of the term from float64 here)."""
+    p64, _, (ix, iy) = terms64(X_dev, pose0, mb, heat_w, cam, O.PARENTS)
+    np.testing.assert_allclose(parts_dev[:4], p64[:4], rtol=1e-5, atol=0)
+    _, dix, diy = bilinear(np.asarray(heat_w), ix.ravel(), iy.ravel())
+    slack = 7.5e-6 * float(np.sum(np.abs(dix) + np.abs(diy)))
+    assert abs(parts_dev[4] - p64[4]) <= 1e-5 * abs(p64[4]) + slack, (parts_dev[4], p64[4], slack)
 
 
 def test_library_is_the_hip_one(torch_cuda):
@@ -356,6 +371,7 @@ def test_precision_modes_energy_and_gradient(torch_cuda, mode, tol_x, tol_e, tol
         assert np.abs(X[b].cpu().numpy() - Xo[0]).max() <= tol_x * max(1.0, np.abs(Xo[0]).max())
         assert abs(float(E[b]) - f) <= tol_e * abs(f) + 1e-7
         assert np.abs(dz[b].cpu().numpy() - dzo).max() <= tol_g * np.abs(dzo).max() + 1e-8
+        _check_parts_at_device_pose(parts[b].cpu().numpy(), X[b].cpu().numpy(), pose[b], mb, heat[starts[b]:starts[b] + 10], cam)
 
 
 @pytest.mark.parametrize("mode,tol_mm", [("bf16x3", 0.5), ("bf16", 1.5)])
@@ -1055,6 +1071,7 @@ def test_large_batch_tile_kernels_against_oracle(torch_cuda, mode, tol_x, tol_e,
         assert np.abs(X[b].cpu().numpy() - Xo[0]).max() <= tol_x * max(1.0, np.abs(Xo[0]).max()), b
         assert abs(float(E[b]) - f) <= tol_e * abs(f) + 1e-7, b
         assert np.abs(dz[b].cpu().numpy() - dzo).max() <= tol_g * np.abs(dzo).max() + 1e-8, b
+        _check_parts_at_device_pose(parts[b].cpu().numpy(), X[b].cpu().numpy(), pose[b], mb, heat[starts[b]:starts[b] + 10], cam)
 
 
 @pytest.mark.parametrize("lr,max_iter,tol_change", [(1.0, 5, 1e-6), (2.0, 1, 1e-6), (0.5, 33, 1e-9), (2.0, 12, 1e-3)])
