@@ -198,6 +198,8 @@ SIGNATURES = {
     "gem_trainer_step": (C.c_int, [_P, C.c_int, _P, _P, C.POINTER(GemTrainOpts), C.c_int, _P, _P]),
     "gem_trainer_arena": (C.c_int, [_P, C.c_int, C.POINTER(_P), C.POINTER(C.c_int64)]),
     "gem_trainer_apply": (C.c_int, [_P, C.POINTER(GemTrainOpts), C.c_double, _P]),
+    "gem_trainer_route": (C.c_int, [_P, C.c_int, _P, C.c_int]),
+    "gem_trainer_layer_output": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(_P), C.POINTER(C.c_int)]),
     "gem_motion_cameras": (C.c_int, [_P, _P, C.c_int64, _P, _P]),
     "gem_motion_windows": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int64, C.c_int, C.c_int, _P, C.c_int64, _P, _P]),
     "gem_latent_paths": (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_int, C.c_int, _P, _P]),

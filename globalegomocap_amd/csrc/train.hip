@@ -427,8 +427,16 @@ __global__ __launch_bounds__(BN_THREADS) void colsum_kernel(const float* __restr
 
 constexpr int CONV_ROWS_MAX = 1 << 30;          // every batch: 1.18 -> 1.11 ms per step at batch 128, 2.17 -> 2.11 at 512, 3.48 -> 3.44 at 1024
 // 0 = launched; 1 = error; -1 = not applicable (the caller falls back to launch_gemm)
-static int conv_rows(gem_trainer* t, const float* W, const float* bias, const float* A, int lda, float* C, int ldc, int rows, int N, int K, hipStream_t s,
-                     const CrStats& st = CrStats{});
+static int conv_rows(gem_trainer* t, const float* W, const float* bias, const float* A, int lda, float* C, int ldc, int rows, int N, int K, int waves,
+                     hipStream_t s, const CrStats& st = CrStats{});
+// waves per workgroup of a conv_rows product = K cuts of whole 32-wide chunks (K = 64: two waves, 128: four); eight waves when the
+// tiles alone do not fill the chip.  One ring slot per wave (the refill of the slot just read runs under the sixteen MFMAs: a second
+// slot measured the same).  tools/conv_rows_bench: 4.8 us (K <= 128), 7 (N 128, K 256),
+// 11 (N 512, K 256 and N 256, K 512) at 640 rows, against 9 + 4.5 and 13.5 + 4.9 for the tiled kernel and its split-K reduce
+static inline int conv_rows_waves(int n_cu, int rows, int N, int K) {
+    if (K % 256 == 0 && (long)((rows + 31) / 32) * (N / 32) <= n_cu) return 8;
+    return K % 128 == 0 ? 4 : 2;
+}
 
 // ---- weight gradient: dW[tap][n][k] = sum_r dC[r][n] * A[r + tap - 1][k], slab z = rows [z * rps, (z + 1) * rps) --------------
 template <int TAPS>
@@ -1032,16 +1040,12 @@ static int launch_conv_rows(const dim3& grid, const float* W, const float* bias,
     GEM_HIP(hipGetLastError());
     return 0;
 }
-static int conv_rows(gem_trainer* t, const float* W, const float* bias, const float* A, int lda, float* C, int ldc, int rows, int N, int K, hipStream_t s,
-                     const CrStats& st) {
+static int conv_rows(gem_trainer* t, const float* W, const float* bias, const float* A, int lda, float* C, int ldc, int rows, int N, int K, int waves,
+                     hipStream_t s, const CrStats& st) {
     if (rows > CONV_ROWS_MAX || K % 64 || N % 32) return -1;
     const dim3 grid((rows + 31) / 32, N / 32);
-    // waves per workgroup = K cuts of whole 32-wide chunks (K = 64: two waves, 128: four); eight waves when the tiles alone
-    // do not fill the chip.  One ring slot per wave (the refill of the slot just read runs under the sixteen MFMAs: a second slot
-    // measured the same).  tools/conv_rows_bench: 4.8 us (K <= 128), 7 (N 128, K 256),
-    // 11 (N 512, K 256 and N 256, K 512) at 640 rows, against 9 + 4.5 and 13.5 + 4.9 for the tiled kernel and its split-K reduce
-    if (K % 256 == 0 && (long)grid.x * grid.y <= t->h->n_cu) return launch_conv_rows<8, 1>(grid, W, bias, A, lda, C, ldc, rows, N, K, t->T, s, st);
-    if (K % 128 == 0) return launch_conv_rows<4, 1>(grid, W, bias, A, lda, C, ldc, rows, N, K, t->T, s, st);
+    if (waves == 8) return launch_conv_rows<8, 1>(grid, W, bias, A, lda, C, ldc, rows, N, K, t->T, s, st);
+    if (waves == 4) return launch_conv_rows<4, 1>(grid, W, bias, A, lda, C, ldc, rows, N, K, t->T, s, st);
     return launch_conv_rows<2, 1>(grid, W, bias, A, lda, C, ldc, rows, N, K, t->T, s, st);
 }
 
@@ -1100,7 +1104,17 @@ static int linear_gemm(gem_trainer* t, const Layer& L, int epi, const float* A, 
 // layer (a 2 x 126 MB transpose of both linear layers' weights per step in round 3) and the few-rows product that read it.
 // bias_grad != nullptr: the layer's bias gradient (the column sums of dY) is wanted as well: formed by the transpose when the batch is one
 // row tile, by colsum_kernel otherwise
-static int linear_bwd_data(gem_trainer* t, const float* dY, const float* W, float* dX, int B, int N, int K, hipStream_t s, float* bias_grad) {
+// The n range of linear_bwd_data's product is cut into slabs of `rps` rows of W so that the tiles fill the chip; the count
+static int linear_bwd_slabs(const gem_trainer* t, int B, int N, int K, int* rps_out) {
+    const int tiles = (pad64(B) / 64) * (K / 64);
+    int nslab = (2 * t->h->n_cu + tiles - 1) / tiles;
+    nslab = std::max(1, std::min(nslab, std::min(N / 64, t->lin_slab_cap)));
+    const int rps = ((N + nslab - 1) / nslab + 31) / 32 * 32;
+    if (rps_out) *rps_out = rps;
+    return (N + rps - 1) / rps;
+}
+// (nslab: linear_bwd_slabs' count, from the step's route record)
+static int linear_bwd_data(gem_trainer* t, const float* dY, const float* W, float* dX, int B, int N, int K, int nslab, hipStream_t s, float* bias_grad) {
     const int Bp = pad64(B);
     const bool fold = bias_grad && Bp == 64;
     if (bias_grad && !fold) {
@@ -1110,15 +1124,15 @@ static int linear_bwd_data(gem_trainer* t, const float* dY, const float* W, floa
     hipLaunchKernelGGL(transpose_pad_kernel, dim3(N / 64, Bp / 64), dim3(256), 0, s, dY, B, N, Bp, t->dYT, fold ? bias_grad : nullptr);
     GEM_HIP(hipGetLastError());
     const int tiles = (Bp / 64) * (K / 64);
-    int nslab = (2 * t->h->n_cu + tiles - 1) / tiles;
-    nslab = std::max(1, std::min(nslab, std::min(N / 64, t->lin_slab_cap)));
-    int rps = ((N + nslab - 1) / nslab + 31) / 32 * 32;
-    nslab = (N + rps - 1) / rps;
-    float* out = nslab > 1 ? t->lin_slab : dX;
-    if (nslab == 1 && Bp != B) { set_error("train: linear backward-data without slabs needs a batch that is a multiple of 64"); return 1; }
+    int rps = 0;
+    if (linear_bwd_slabs(t, B, N, K, &rps) != nslab) { set_error("train: linear backward-data: the route record and the layer disagree"); return 1; }
+    // The product writes whole 64-row tiles, Bp rows: straight into dX (B rows) only when there is one slab AND the batch is a multiple
+    // of 64; a single slab of any other batch goes through the slab buffer like several do, and the "sum" copies its first B rows
+    const bool direct = nslab == 1 && Bp == B;
+    float* out = direct ? dX : t->lin_slab;
     hipLaunchKernelGGL(gemm_tn_kernel<1>, dim3(tiles, 1, nslab), dim3(256), 0, s, (const float*)t->dYT, Bp, W, K, out, N, Bp, K, t->T, rps);
     GEM_HIP(hipGetLastError());
-    if (nslab > 1) {
+    if (!direct) {
         const size_t n_out = (size_t)B * K;
         hipLaunchKernelGGL(slab_sum_kernel, dim3((unsigned)((n_out / 4 + 255) / 256)), dim3(256), 0, s, (const float*)t->lin_slab, nslab, (size_t)Bp * K, dX, n_out);
         GEM_HIP(hipGetLastError());
@@ -1154,6 +1168,46 @@ static int linear_fused_backward(gem_trainer* t, const TrainLinear& l, int tps, 
     hipLaunchKernelGGL(slab_sum_kernel, dim3((unsigned)((n_out / 4 + 255) / 256)), dim3(256), 0, s, (const float*)t->dx_slab, nstrip, (size_t)64 * l.K, dX, n_out);
     GEM_HIP(hipGetLastError());
     return 0;
+}
+
+// ---- every decision a step of B windows takes that depends on B, the widths or the CU count, in ONE record ---------------------
+// gem_trainer_step fills it once at its top and consults nothing else; gem_trainer_route hands the same record out, so that a test
+// can assert which kernels its case reaches (include/gem_hip.h: the int32 layout).
+struct TrainRoute {
+    int bn_fwd = 0;                 // 0 = sums from the conv's epilogue (bnf_*), 1 = register-resident, 2 = row blocks (bnl_*)
+    int bn_bwd = 0;                 // where no dz arrives: 1 = register-resident, 2 = row blocks
+    int enc_top_dz = 0;             // update = 2: the fc layer's backward leaves dz and the sums for the encoder's last block
+    int strip_dec_in = 0, strip_fc = 0;            // update = 2: n tiles per workgroup of gemm_tn_adam_dx_kernel, 0 = the separate kernels
+    int bwd_slabs_dec_in = 0, bwd_slabs_fc = 0;    // linear_bwd_data: slabs of W's rows (what runs where the strip is 0, and with update < 2)
+    int conv_wgrad_rps = 0, conv_wgrad_slabs = 0, lin_wgrad_slabs = 0;
+    int n_enc = 0, n_dec = 0;
+    int waves_fwd[TN_MAX_LAYERS] = {}, waves_bwd[TN_MAX_LAYERS] = {};      // conv_rows, encoder then decoder; 0 = no such product
+};
+static TrainRoute train_route(const gem_trainer* t, int B) {
+    TrainRoute r;
+    const int rows = B * t->T, n_cu = t->h->n_cu;
+    const bool bn_fused = rows <= BNF_ROWS_MAX;
+    const bool regs = rows <= BN_REGS * BN_GROUPS;
+    r.bn_fwd = bn_fused ? 0 : regs ? 1 : 2;
+    r.bn_bwd = regs ? 1 : 2;
+    r.strip_dec_in = fused_backward_strip(t, t->dec_in, B);
+    r.strip_fc = fused_backward_strip(t, t->fc, B);
+    const TrainConv& top = t->enc.back();
+    r.enc_top_dz = r.strip_fc && bn_fused && top.N % 32 == 0 && t->fc.K == t->T * top.N;
+    r.bwd_slabs_dec_in = linear_bwd_slabs(t, B, t->dec_in.N, t->dec_in.K, nullptr);
+    r.bwd_slabs_fc = linear_bwd_slabs(t, B, t->fc.N, t->fc.K, nullptr);
+    r.conv_wgrad_rps = conv_slab_rows(rows);
+    r.conv_wgrad_slabs = (rows + r.conv_wgrad_rps - 1) / r.conv_wgrad_rps;
+    r.lin_wgrad_slabs = (B + TN_ROWS_LINEAR - 1) / TN_ROWS_LINEAR;
+    r.n_enc = (int)t->enc.size(); r.n_dec = (int)t->dec.size();
+    int l = 0;
+    for (const auto* v : {&t->enc, &t->dec})
+        for (const TrainConv& c : *v) {
+            r.waves_fwd[l] = conv_rows_waves(n_cu, rows, c.N, c.K);
+            r.waves_bwd[l] = l == 0 ? 0 : conv_rows_waves(n_cu, rows, c.K, c.N);      // (nothing flows back through the first encoder conv)
+            ++l;
+        }
+    return r;
 }
 
 }  // namespace gem
@@ -1315,6 +1369,7 @@ int gem_trainer_step(gem_trainer* t, int B, const float* d_pose, const float* d_
     GEM_HIP(hipSetDevice(h->cfg.device));
     hipStream_t s = (hipStream_t)stream;
     const int T = t->T, rows = B * T;
+    const TrainRoute rt = train_route(t, B);          // every size-dependent decision below comes out of this record (gem_trainer_route)
     h->precision = GEM_PRECISION_F32;
     // update = 2: the linear layers' weight gradients are formed inside their Adam step (gemm_tn_adam_kernel) and NOT left in the
     // gradient arena -- the training loop's mode (networks/train.py:77-83 never looks at p.grad)
@@ -1336,20 +1391,20 @@ int gem_trainer_step(gem_trainer* t, int B, const float* d_pose, const float* d_
     GEM_HIP(hipGetLastError());
     // ---- forward (train mode)
     if (launch_pack_pose(d_pose, t->pose_p, rows, t->C, s)) return 1;
-    const bool bn_fused = rows <= BNF_ROWS_MAX;
-    auto conv_fwd = [&](TrainConv& c, const float* in) -> int {
+    const bool bn_fused = rt.bn_fwd == 0;
+    auto conv_fwd = [&](TrainConv& c, const float* in, int layer) -> int {
         Layer L; L.taps = 3; L.K = c.K; L.N = c.N; L.w = t->P + c.ow; L.bias = t->P + c.ob;
         // (bn_fused: the conv's epilogue leaves the BatchNorm sums per 32-row tile; the apply kernels are elementwise)
         CrStats st{};
         if (c.bn && bn_fused) st.part = t->bn_part;
-        const int rc = conv_rows(t, L.w, L.bias, in, c.K, c.bn ? c.Y : c.out, c.N, rows, c.N, c.K, s, st);
+        const int rc = conv_rows(t, L.w, L.bias, in, c.K, c.bn ? c.Y : c.out, c.N, rows, c.N, c.K, rt.waves_fwd[layer], s, st);
         if (rc > 0 || (rc < 0 && launch_gemm(h, L, EPI_BIAS, in, c.K, nullptr, c.bn ? c.Y : c.out, c.N, rows, T, s, -1))) return 1;
         if (c.bn) {
             if (rc == 0 && st.part) {
                 hipLaunchKernelGGL(bnf_fwd_apply_kernel, dim3(c.N / 64, (rows + 63) / 64), dim3(256), 0, s, (const float*)c.Y, rows, c.N,
                                    (const double*)t->bn_part, (rows + 31) / 32, (const float*)(t->P + c.og), (const float*)(t->P + c.obe), t->S + c.os,
                                    t->S + c.os + c.N, c.mean, c.invstd, c.out, (float)o->bn_momentum, (float)BN_EPS);
-            } else if (rows <= BN_REGS * BN_GROUPS) {
+            } else if (rt.bn_bwd == 1) {          // (the register-resident pair serves the same row counts forward and backward)
                 hipLaunchKernelGGL(bn_train_fwd_kernel, dim3(c.N / 16), dim3(BN_THREADS), 0, s, (const float*)c.Y, rows, c.N, (const float*)(t->P + c.og),
                                    (const float*)(t->P + c.obe), t->S + c.os, t->S + c.os + c.N, c.mean, c.invstd, c.out, (float)o->bn_momentum, (float)BN_EPS);
             } else {
@@ -1365,13 +1420,14 @@ int gem_trainer_step(gem_trainer* t, int B, const float* d_pose, const float* d_
         return 0;
     };
     const float* in = t->pose_p;
-    for (auto& c : t->enc) { if (conv_fwd(c, in)) return 1; in = c.out; }
+    int layer = 0;
+    for (auto& c : t->enc) { if (conv_fwd(c, in, layer++)) return 1; in = c.out; }
     { Layer L; L.taps = 1; L.K = t->fc.K; L.N = t->fc.N; L.w = t->P + t->fc.ow; L.bias = t->P + t->fc.ob;
       if (linear_gemm(t, L, EPI_BIAS, in, L.K, t->mulv, L.N, B, s, d_eps)) return 1; }
     { Layer L; L.taps = 1; L.K = t->dec_in.K; L.N = t->dec_in.N; L.w = t->P + t->dec_in.ow; L.bias = t->P + t->dec_in.ob;
       if (linear_gemm(t, L, EPI_BIAS, t->z, L.K, t->h0, L.N, B, s)) return 1; }
     in = t->h0;
-    for (auto& c : t->dec) { if (conv_fwd(c, in)) return 1; in = c.out; }
+    for (auto& c : t->dec) { if (conv_fwd(c, in, layer++)) return 1; in = c.out; }
     const float* X = t->dec.back().out;
     // ---- loss + its gradient w.r.t. the decoded pose
     const double n_recon = o->recon_sum ? 1.0 : (double)rows * t->C;
@@ -1382,7 +1438,7 @@ int gem_trainer_step(gem_trainer* t, int B, const float* d_pose, const float* d_
     GEM_HIP(hipGetLastError());
     // ---- backward: decoder
     auto bn_bwd = [&](const float* dOut, const TrainConv& c, float* dY) -> int {
-        if (rows <= BN_REGS * BN_GROUPS) {
+        if (rt.bn_bwd == 1) {
             hipLaunchKernelGGL(bn_train_bwd_kernel, dim3(c.N / 16), dim3(BN_THREADS), 0, s, dOut, (const float*)c.out, (const float*)c.Y, rows, c.N,
                                (const float*)(t->P + c.og), (const float*)c.mean, (const float*)c.invstd, dY, t->G + c.og, t->G + c.obe, t->G + c.ob);
         } else {
@@ -1402,11 +1458,11 @@ int gem_trainer_step(gem_trainer* t, int B, const float* d_pose, const float* d_
     // the ONE weight-gradient launch behind the chain.
     // bn_fused: the backward-data conv of a layer forms, in its epilogue, the BatchNorm-backward sums of the layer BELOW (whose dOut it
     // produces) and stores dz = dOut * LeakyReLU'(out) in dOut's place; that layer's BatchNorm backward is then elementwise
-    auto bwd_conv = [&](const TrainConv& c, const float* dY, float* dst, const TrainConv* below, bool* have_dz) -> int {
+    auto bwd_conv = [&](const TrainConv& c, int layer, const float* dY, float* dst, const TrainConv* below, bool* have_dz) -> int {
         Layer L; L.taps = 3; L.K = c.N; L.N = c.K; L.w = c.adj; L.bias = nullptr;
         CrStats st{};
         if (below && below->bn && bn_fused) st = CrStats{t->bn_part, below->out, below->Y, below->mean, below->invstd, LEAKY_SLOPE};
-        const int rc = conv_rows(t, L.w, nullptr, dY, c.N, dst, c.K, rows, c.K, c.N, s, st);
+        const int rc = conv_rows(t, L.w, nullptr, dY, c.N, dst, c.K, rows, c.K, c.N, rt.waves_bwd[layer], s, st);
         if (rc > 0 || (rc < 0 && launch_gemm(h, L, EPI_NONE, dY, c.N, nullptr, dst, c.K, rows, T, s, -1))) return 1;
         *have_dz = rc == 0 && st.part != nullptr;
         return 0;
@@ -1429,7 +1485,7 @@ int gem_trainer_step(gem_trainer* t, int B, const float* d_pose, const float* d_
             if (bn_bwd_any(dOut, have_dz, c)) return 1;
             dY = c.dY;
         }          // (no BatchNorm -- the last conv: its bias gradient, the column sums of dY, rides with the weight-gradient launch)
-        if (bwd_conv(c, dY, run, i > 0 ? &t->dec[i - 1] : nullptr, &have_dz)) return 1;
+        if (bwd_conv(c, rt.n_enc + i, dY, run, i > 0 ? &t->dec[i - 1] : nullptr, &have_dz)) return 1;
         dOut = run;
     }
     float* g = run;
@@ -1437,11 +1493,11 @@ int gem_trainer_step(gem_trainer* t, int B, const float* d_pose, const float* d_
     int dz_slabs = 0;          // > 0: dz is left as that many slabs for latent_bwd_kernel
     bool enc_top_dz = false;
     { const TrainLinear& l = t->dec_in;
-      const int tps = fused ? fused_backward_strip(t, l, B) : 0;
+      const int tps = fused ? rt.strip_dec_in : 0;
       if (tps) { if (linear_fused_backward(t, l, tps, g, t->z, nullptr, B, ad, s)) return 1; dz_slabs = l.N / 64 / tps; }
       else {
           if (!fused && weight_grad<1>(t, g, l.N, t->z, l.K, B, l.N, l.K, l.ow, l.slab, TN_ROWS_LINEAR, s)) return 1;
-          if (linear_bwd_data(t, g, t->P + l.ow, t->dz, B, l.N, l.K, s, t->G + l.ob)) return 1;
+          if (linear_bwd_data(t, g, t->P + l.ow, t->dz, B, l.N, l.K, rt.bwd_slabs_dec_in, s, t->G + l.ob)) return 1;
           if (fused && linear_step(l, g, t->z)) return 1;          // (behind the backward-data product: it reads the weights)
       } }
     hipLaunchKernelGGL(latent_bwd_kernel, dim3(n_pl), dim3(LOSS_BLOCK), 0, s, (const float*)t->mulv, d_eps, dz_slabs ? (const float*)t->dx_slab : (const float*)t->dz, B,
@@ -1451,9 +1507,9 @@ int gem_trainer_step(gem_trainer* t, int B, const float* d_pose, const float* d_
     { const TrainLinear& l = t->fc;
       const float* flat = t->enc.back().out;
       // (g = gB again: decoder_input's backward above has consumed dh0; gA still holds the last conv's dY)
-      const int tps = fused ? fused_backward_strip(t, l, B) : 0;
+      const int tps = fused ? rt.strip_fc : 0;
       const TrainConv& top = t->enc.back();
-      if (tps && bn_fused && top.N % 32 == 0 && l.K == T * top.N) {
+      if (tps && rt.enc_top_dz) {
           // dX = dOut of the encoder's last block: summed from the slabs together with that block's BatchNorm-backward sums
           if (linear_fused_backward(t, l, tps, t->dmulv, flat, nullptr, B, ad, s)) return 1;
           const CrStats st{t->bn_part, top.out, top.Y, top.mean, top.invstd, LEAKY_SLOPE};
@@ -1464,7 +1520,7 @@ int gem_trainer_step(gem_trainer* t, int B, const float* d_pose, const float* d_
       } else if (tps) { if (linear_fused_backward(t, l, tps, t->dmulv, flat, g, B, ad, s)) return 1; }
       else {
           if (!fused && weight_grad<1>(t, t->dmulv, l.N, flat, l.K, B, l.N, l.K, l.ow, l.slab, TN_ROWS_LINEAR, s)) return 1;
-          if (linear_bwd_data(t, t->dmulv, t->P + l.ow, g, B, l.N, l.K, s, t->G + l.ob)) return 1;
+          if (linear_bwd_data(t, t->dmulv, t->P + l.ow, g, B, l.N, l.K, rt.bwd_slabs_fc, s, t->G + l.ob)) return 1;
           if (fused && linear_step(l, t->dmulv, flat)) return 1;
       } }
     // encoder
@@ -1472,7 +1528,7 @@ int gem_trainer_step(gem_trainer* t, int B, const float* d_pose, const float* d_
     for (int i = (int)t->enc.size() - 1; i >= 0; --i) {
         TrainConv& c = t->enc[i];
         if (bn_bwd_any(g, have_dz, c)) return 1;
-        if (i > 0 && bwd_conv(c, c.dY, g, &t->enc[i - 1], &have_dz)) return 1;
+        if (i > 0 && bwd_conv(c, i, c.dY, g, &t->enc[i - 1], &have_dz)) return 1;
     }
     // every conv layer's weight gradient (slabs of conv_slab_rows(rows) rows, or straight into the gradient arena).  Measured and not
     // kept: the same tiles with the rows split over the eight waves of a 512-thread workgroup instead of over the grid (wave-private
@@ -1480,13 +1536,13 @@ int gem_trainer_step(gem_trainer* t, int B, const float* d_pose, const float* d_
     // against 25 + 10.6 for this launch and its slab sum at batch 64, 3.34 against 3.21 ms per step at batch 1024
     { const TrainConv& last = t->dec.back();
       StepTail tail{part_recon, part_latent, t->red + 4, d_losses, n_recon, o->kld_weight, n_pr, n_pl, B, t->gA, t->G + last.ob, last.N};
-      const int rps = conv_slab_rows(rows), nslab = (rows + rps - 1) / rps;
+      const int rps = rt.conv_wgrad_rps, nslab = rt.conv_wgrad_slabs;
       if (nslab > 1 && t->n_sum != t->n_tn) { set_error("train: weight-gradient slabs missing"); return 1; }
       hipLaunchKernelGGL(gemm_tn3_all_kernel, dim3(t->tn_tiles + 1 + last.N / 16, 3, nslab), dim3(256), 0, s, *static_cast<const TnTable*>(t->tn_tab), t->tn_tiles,
                          rows, T, rps, nslab, tail);
       GEM_HIP(hipGetLastError()); }
     // weight-gradient slabs -> the gradient arena (slab order: deterministic)
-    { const int ns_conv = (rows + conv_slab_rows(rows) - 1) / conv_slab_rows(rows), ns_lin = (B + TN_ROWS_LINEAR - 1) / TN_ROWS_LINEAR;
+    { const int ns_conv = rt.conv_wgrad_slabs, ns_lin = rt.lin_wgrad_slabs;
       // (every conv layer's entry was cut into the same slabs of conv_slab_rows(rows) rows: ONE slab count serves the whole table; the two
       // linear layers' entries sit behind the conv entries)
       if (ns_conv > 1 && t->n_sum > 0) {
@@ -1533,6 +1589,32 @@ int gem_trainer_arena(gem_trainer* t, int what, void** d_ptr, int64_t* n) {
     if (what == 1 && t->grads_partial) { set_error("gem_trainer_arena: the last step ran with update = 2, the gradient arena is incomplete"); return 1; }
     *d_ptr = p;
     if (n) *n = (int64_t)(what == 2 ? t->n_stats : t->n_params);
+    return 0;
+}
+
+int gem_trainer_route(gem_trainer* t, int B, int32_t* out, int cap) {
+    if (!t || !out) { set_error("gem_trainer_route: null argument"); return 1; }
+    if (B < 2 || B > t->Bmax) { set_error("gem_trainer_route: need 2 <= B <= max_windows"); return 1; }
+    const TrainRoute r = train_route(t, B);
+    const int n_conv = r.n_enc + r.n_dec, need = 12 + 2 * n_conv;
+    if (cap < need) { set_error("gem_trainer_route: the record of this network has " + std::to_string(need) + " entries, the buffer " + std::to_string(cap)); return 1; }
+    // (a single slab of a batch that is no multiple of 64 passes through the slab buffer: -1, not the direct path's 1)
+    const bool whole = B % 64 == 0;
+    const int head[12] = {r.bn_fwd, r.bn_bwd, r.enc_top_dz, r.strip_dec_in, r.strip_fc,
+                          r.bwd_slabs_dec_in == 1 && !whole ? -1 : r.bwd_slabs_dec_in, r.bwd_slabs_fc == 1 && !whole ? -1 : r.bwd_slabs_fc,
+                          r.conv_wgrad_slabs, r.lin_wgrad_slabs, r.n_enc, r.n_dec, t->h->n_cu};
+    for (int i = 0; i < 12; ++i) out[i] = head[i];
+    for (int l = 0; l < n_conv; ++l) { out[12 + 2 * l] = r.waves_fwd[l]; out[13 + 2 * l] = r.waves_bwd[l]; }
+    return 0;
+}
+
+int gem_trainer_layer_output(gem_trainer* t, int which, int index, void** d_ptr, int* ld) {
+    if (!t || !d_ptr || !ld) { set_error("gem_trainer_layer_output: null argument"); return 1; }
+    if (which < 0 || which > 1) { set_error("gem_trainer_layer_output: which is 0 (encoder) or 1 (decoder)"); return 1; }
+    const std::vector<TrainConv>& v = which == 0 ? t->enc : t->dec;
+    if (index < 0 || index >= (int)v.size()) { set_error("gem_trainer_layer_output: no such block"); return 1; }
+    *d_ptr = v[index].out;
+    *ld = v[index].N;
     return 0;
 }
 

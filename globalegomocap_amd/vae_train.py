@@ -219,6 +219,7 @@ class VAETrainer:
         self.forwards = 0
         self._fused_last = False         # the last step ran in the training-loop mode (gem_trainer_step update = 2)
         self._grad = None
+        self._last_batch = 0
         self._losses = torch.zeros(3, dtype=torch.float64, device=self.device)
         self._gen = torch.Generator(device=self.device)
         self._gen.manual_seed(seed)
@@ -364,6 +365,7 @@ class VAETrainer:
         s = torch.cuda.current_stream(self.device).cuda_stream
         _capi.check(self.lib.gem_trainer_step(self._t, B, x.data_ptr(), e.data_ptr(), C.byref(self.opts),
                                               (1 if keep_gradients else 2) if update else 0, self._losses.data_ptr(), C.c_void_p(s)), self.lib)
+        self._last_batch = B
         self.forwards += 1               # every train-mode forward updates the running statistics (like torch's BatchNorm)
         self._fused_last = bool(update) and not keep_gradients
         if update:
@@ -371,6 +373,45 @@ class VAETrainer:
         if not sync:
             return self._losses
         return tuple(float(v) for v in self._losses.cpu())
+
+    # ---- read-only views for tests and tools
+    ROUTE_FIELDS = ("bn_forward", "bn_backward", "encoder_top_dz", "strip_decoder_input", "strip_fc", "bwd_data_slabs_decoder_input",
+                    "bwd_data_slabs_fc", "conv_weight_grad_slabs", "linear_weight_grad_slabs", "n_encoder", "n_decoder", "n_cu")
+
+    def route(self, batch):
+        """The decisions a step of `batch` windows takes (gem_trainer_route, include/gem_hip.h: the record the step itself consults):
+        a dict of ROUTE_FIELDS plus 'conv_waves' = [(forward, backward-data) per conv layer, encoder then decoder]."""
+        from . import _capi
+        n_conv = 2 * len(self.shape.hidden) + 1
+        out = (C.c_int32 * (12 + 2 * n_conv))()
+        _capi.check(self.lib.gem_trainer_route(self._t, int(batch), out, len(out)), self.lib)
+        r = dict(zip(self.ROUTE_FIELDS, (int(v) for v in out[:12])))
+        r["conv_waves"] = [(int(out[12 + 2 * l]), int(out[13 + 2 * l])) for l in range(n_conv)]
+        return r
+
+    def layer_outputs(self):
+        """The block outputs of the last step's forward, unpadded, as float32 arrays [B, T, channels]: ([encoder blocks], [decoder
+        blocks..., final_layer's block, the reconstructed pose])."""
+        import torch
+        from . import _capi
+        if not self._last_batch:
+            raise _capi.GemError("layer_outputs: no step has run yet")
+        rows = self._last_batch * self.shape.seq_len
+        enc, dec = self.shape.conv_layers()
+        torch.cuda.synchronize(self.device)
+        res = []
+        for which, layers in enumerate((enc, dec)):
+            outs = []
+            for i, (_, _, _, co, _) in enumerate(layers):
+                ptr, ld = C.c_void_p(), C.c_int()
+                _capi.check(self.lib.gem_trainer_layer_output(self._t, which, i, C.byref(ptr), C.byref(ld)), self.lib)
+
+                class _View:
+                    __cuda_array_interface__ = {"shape": (rows, ld.value), "typestr": "<f4", "data": (ptr.value, False), "version": 2}
+                a = torch.as_tensor(_View(), device=self.device)[:, :co].cpu().numpy()
+                outs.append(a.reshape(self._last_batch, self.shape.seq_len, co))
+            res.append(outs)
+        return tuple(res)
 
     # ---- data parallel (one process per GPU; the reference itself trains on one device)
     def arena_tensor(self, what=1):

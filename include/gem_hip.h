@@ -561,6 +561,23 @@ int  gem_trainer_step(gem_trainer* t, int B, const float* d_pose, const float* d
  * on the fly.  BatchNorm statistics stay per rank, as under torch's DistributedDataParallel without SyncBatchNorm. */
 int  gem_trainer_arena(gem_trainer* t, int what, void** d_ptr, int64_t* n);
 int  gem_trainer_apply(gem_trainer* t, const gem_train_opts* opts, double grad_scale, void* stream);
+/* Two read-only views for tests and tools.
+ * gem_trainer_route: the decisions a step of B windows takes -- the very record gem_trainer_step fills at its top and consults
+ * -- as int32 (cap >= 12 + 2 * (number of conv layers); nothing is launched):
+ *   [0]  BatchNorm forward: 0 = sums from the producing conv's epilogue, 1 = register-resident kernel, 2 = row-block kernels
+ *   [1]  BatchNorm backward where no dz arrives from a conv's epilogue: 1 = register-resident, 2 = row-block kernels
+ *   [2]  update = 2: the encoder's last block gets dz (and its sums) from the fc layer's backward
+ *   [3], [4]  update = 2: strip length (n tiles per workgroup) of the fused backward of decoder_input, of fc; 0 = separate kernels
+ *   [5], [6]  the separate backward-data product of decoder_input, of fc: slabs summed behind it; 1 = none, the product writes dX
+ *        itself (batch a multiple of 64); -1 = one slab copied out of the slab buffer (any other batch)
+ *   [7], [8]  weight-gradient slabs of the conv layers, of the linear layers (update < 2)
+ *   [9], [10] conv layers of the encoder, of the decoder;  [11] compute units the decisions were made for
+ *   [12 + 2 l], [13 + 2 l]  conv layer l (encoder, then decoder): waves per workgroup of its forward product, of its backward-data
+ *        product (0: the first encoder conv has none)
+ * gem_trainer_layer_output: which = 0 encoder / 1 decoder, block `index`: the device address of the block's output [rows, *ld]
+ * (after LeakyReLU; the decoder's last index is the final conv = the reconstructed pose), valid after a step until the next one. */
+int  gem_trainer_route(gem_trainer* t, int B, int32_t* out, int cap);
+int  gem_trainer_layer_output(gem_trainer* t, int which, int index, void** d_ptr, int* ld);
 
 /* ---- Training windows of the motion VAEs cut on the device ----
  * gem_motion_cameras: d_loc [n,3], d_quat [n,4] (x, y, z, w; any non-zero norm) float64 -> d_cam34 [n,3,4] float64 = [R | loc] with

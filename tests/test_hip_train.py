@@ -345,10 +345,12 @@ def test_two_rank_data_parallel_steps_equal_the_mean_gradient_step(tmp_path):
 
 @pytest.mark.parametrize("batch", [4, 130, 300])
 def test_training_step_against_the_port_at_other_batch_sizes(batch):
-    """The code paths the golden batches (9, 12) do not reach: 4 windows = 40 rows, a single weight-gradient slab written
-    straight into the gradient arena; 130 windows = 1300 rows, the large-batch BatchNorm kernels (more rows than a thread keeps
-    in registers: per-row-block partial sums, two launches); 300 windows, the linear layers' weight gradients in two slabs and
-    the conv layers' in slabs of more than 64 rows."""
+    """The code paths the golden batches (9, 12) do not reach, each asserted through gem_trainer_route: 4 windows = 40 rows, a single
+    weight-gradient slab written straight into the gradient arena; 130 windows = 1300 rows, the row-block BatchNorm BACKWARD for the
+    encoder's last block (more rows than a thread keeps in registers: per-row-block partial sums, two launches) -- the forward
+    statistics still come out of the conv epilogues, as for every batch of at most 2560 rows; 300 windows = 3000 rows, the row-block
+    BatchNorm forward as well, the linear layers' weight gradients in two slabs and the conv layers' in 16 slabs of more than 64
+    rows."""
     from globalegomocap_amd.vae_train import VAETrainer, initial_state_dict
     from oracle.torch_port import TrainPort
     shape = vae_schema.VAEShape(latent_dim=72, hidden=(24, 40, 96))
@@ -358,6 +360,11 @@ def test_training_step_against_the_port_at_other_batch_sizes(batch):
     port = TrainPort(init, lr=1e-3, weight_decay=1e-4)
     tr = VAETrainer(shape, batch_size=batch, lr=1e-3, weight_decay=1e-4, state_dict=init)
     try:
+        route = tr.route(batch)
+        want = {4: dict(bn_forward=0, bn_backward=1, conv_weight_grad_slabs=1, linear_weight_grad_slabs=1),
+                130: dict(bn_forward=0, bn_backward=2, conv_weight_grad_slabs=14, linear_weight_grad_slabs=1),
+                300: dict(bn_forward=2, bn_backward=2, conv_weight_grad_slabs=16, linear_weight_grad_slabs=2)}[batch]
+        assert {k: route[k] for k in want} == want, route
         for s in range(2):
             ref = port.step(poses[s], eps[s], 0.02)
             out = tr.step(poses[s], 0.02, eps=eps[s])
