@@ -89,6 +89,11 @@ SCALE_CANDIDATES, SCALE_TILE, SCALE_REPORT_DOUBLES = 513, 256, 16
 SCALE_NO_PAIRS, SCALE_TOO_FEW, SCALE_BAD_SCALE = 2, 3, 4
 
 
+class GemBoneDepthOpts(C.Structure):
+    _fields_ = [("bone", C.c_double * GEM_MAX_JOINTS), ("dbar", C.c_double * GEM_MAX_JOINTS), ("neck_depth", C.c_double), ("w_n", C.c_double),
+                ("w_m", C.c_double), ("iters", C.c_int32), ("reserved", C.c_int32)]
+
+
 class GemGroundRecord(C.Structure):
     _fields_ = [("status", C.c_double), ("source", C.c_double), ("n", C.c_double * 3), ("d", C.c_double), ("u0", C.c_double * 3),
                 ("tilt_cos", C.c_double)] + \
@@ -222,6 +227,7 @@ SIGNATURES = {
     "gem_keypoint_heatmaps": (C.c_int, [_P, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_double, _P, _P]),
     "gem_lift_keypoints": (C.c_int, [_P, _P, _P, C.c_int64, C.POINTER(C.c_double), C.c_int, _P, _P, _P, _P, _P]),
     "gem_fill_missing": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P]),
+    "gem_bone_depths": (C.c_int, [_P, _P, C.c_int64, C.POINTER(C.c_double), C.c_int, C.POINTER(GemBoneDepthOpts), _P, _P, _P, _P]),
     "gem_slam_scale_work": (C.c_int64, [C.c_int64, C.c_int, C.c_int]),
     "gem_slam_scale": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(C.c_int), _P, _P, _P, C.c_int64, C.c_int, C.c_double, C.c_int, _P,
                                  C.c_int64, _P, _P, _P, _P]),

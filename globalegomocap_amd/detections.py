@@ -12,7 +12,7 @@ and u, v are finite; a joint that is unusable in a frame gets a blank heat-map t
 usable neighbours inside the chunk.  A joint with no usable detection in a whole chunk is a ValueError.
 
     python -m globalegomocap_amd.detections --slam traj.txt --keypoints det.npz --scale 1.0|auto --start 0 --end 2001 --fps 25 \\
-        [--depths DIR | --depth FILE.npy] [--sigma 1.5] [--first_id 0] [--test_size 100] [--out DIR] [--optimize] [--camera JSON]
+        [--depths DIR | --depth FILE.npy | --depth_from bones [--bones FILE.npy] [--neck_depth M]] [--sigma 1.5] [--first_id 0] [--test_size 100] [--out DIR] [--optimize] [--camera JSON]
 """
 import os
 
@@ -130,9 +130,13 @@ def detections_from_args(a):
 
 # ------------------------------------------------------------------------------------------------------------------ the device path
 def recording_from_detections(slam_result_path, detections, gt_path=None, scale=None, spans=(), fps=25, depth=None, sigma=1.5, first_id=0,
-                              camera_model_path=None, device=None, gt_start_frame=None, lag=None, tau=0.10, min_pairs=50, bridge=None):
+                              camera_model_path=None, device=None, gt_start_frame=None, lag=None, tau=0.10, min_pairs=50, bridge=None,
+                              bones=None, neck_depth=None):
     """Every (start_frame, end_frame) of `spans` as one chunk of a `prepare.Recording`, from 2-D detections: `detections` is a file
-    (`read_detections`), an array [N,15,2|3] or `as_detections`' dict; `depth` [N,15] unless the file carries it.  Exactly one of
+    (`read_detections`), an array [N,15,2|3] or `as_detections`' dict; `depth` [N,15] unless the file carries it, or "bones": the
+    depths are solved on the device from the bone lengths (`WindowEngine.bone_depths` with `bone_depth.options(bones,
+    neck_depth=neck_depth)`), a joint the solve could not reach is a lost detection from there on, and the
+    Recording carries the solve's `depth_report`.  Exactly one of
     `gt_path` (the ground truth fixes the SLAM scale per chunk, as `prepare` does; entry i - gt_start_frame of the pickle is frame id
     i, gt_start_frame defaulting to the first span's start) and `scale`: a number, or "auto" to estimate it from the foot contacts of
     the filled poses (`prepare.auto_scale` with `lag`, `tau`, `min_pairs`).  One upload, then on the device:
@@ -149,9 +153,17 @@ def recording_from_detections(slam_result_path, detections, gt_path=None, scale=
         det = as_detections(detections["keypoints"], detections.get("depth"), detections.get("frame_ids"), first_id)
     else:
         det = as_detections(detections, first_id=first_id)
-    if depth is not None:
+    from_bones = isinstance(depth, str)
+    if from_bones:
+        from . import bone_depth
+        if depth != "bones":
+            raise ValueError('recording_from_detections: depth is an array [N,%d] or "bones", got %r' % (N_JOINTS, depth))
+        bone_opts = bone_depth.options(bones, neck_depth=neck_depth)
+    elif bones is not None or neck_depth is not None:
+        raise ValueError('recording_from_detections: bones= and neck_depth= belong to depth="bones"')
+    elif depth is not None:
         det["depth"] = _depth_array(depth, len(det["keypoints"]), "recording_from_detections")
-    if det["depth"] is None:
+    if det["depth"] is None and not from_bones:
         raise ValueError("recording_from_detections: the joints' depths are needed (depth=, or `depth` in the .npz)")
     spans = stage.spans
     device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
@@ -164,16 +176,26 @@ def recording_from_detections(slam_result_path, detections, gt_path=None, scale=
     stage.bounds = bounds = [(int(lo), int(hi)) for lo, hi in zip(bounds[:-1], bounds[1:])]
     pick = np.concatenate(rows)
     kp = det["keypoints"][pick]
+    if from_bones:          # (what the solve will report unsolved counts as lost)
+        kp = np.concatenate([kp[..., :2], np.where(bone_depth.solved_mask(kp), kp[..., 2], 0.0)[..., None]], axis=2)
     check_chunks_have_every_joint(kp, bounds, spans)
     pose_gt = stage.read_gt()
     if pose_gt is not None:
         g0 = spans[0][0] if gt_start_frame is None else int(gt_start_frame)
         stage.gts = [prepare.gt_clip(pose_gt, a, b, g0) for a, b in spans]
-    packed = np.concatenate([kp, det["depth"][pick][..., None]], axis=2)          # [n,15,4]: ONE copy carries detections and depths
+    # [n,15,4]: ONE copy carries detections and depths; with depth="bones" the detections alone go up
+    packed = np.ascontiguousarray(kp) if from_bones else np.concatenate([kp, det["depth"][pick][..., None]], axis=2)
+    depth_report = None
     with torch.cuda.device(device):
         engine = prepare._lift_engine(camera_model_path or DEFAULT_CALIBRATION, device.index)
         packed_d = torch.from_numpy(packed).to(device)
-        kp_d, depth_d = packed_d[..., :3].contiguous(), packed_d[..., 3].contiguous()
+        if from_bones:
+            from .bone_depth import summarize
+            kp_d = packed_d
+            depth_d, solved, rms = engine.bone_depths(kp_d, opts=bone_opts)
+            depth_report = summarize(solved, rms)
+        else:
+            kp_d, depth_d = packed_d[..., :3].contiguous(), packed_d[..., 3].contiguous()
         est_local, _, valid = engine.lift_keypoints(kp_d, depth_d)
         lengths = {hi - lo for lo, hi in bounds}
         if len(lengths) == 1:
@@ -183,7 +205,9 @@ def recording_from_detections(slam_result_path, detections, gt_path=None, scale=
                 engine.fill_missing(est_local[lo:hi], valid[lo:hi], 1)
         stage.fix_scale(engine, est_local)          # (a recording that does not fix the scale is refused before the heat-maps are made)
         heat = engine.keypoint_heatmaps(kp_d, sigma)          # (enqueued ahead of the host's camera work and its blocking upload)
-        return stage.recording(est_local, heat)
+        rec = stage.recording(est_local, heat)
+        rec.depth_report = depth_report
+        return rec
 
 
 def _parser():
@@ -195,6 +219,10 @@ def _parser():
     dep = p.add_mutually_exclusive_group()
     dep.add_argument("--depths", default=None, metavar="DIR", help="directory of per-frame depth .mat files")
     dep.add_argument("--depth", default=None, metavar="FILE.npy", help="the joints' depths [N,15], row for row with the detections")
+    dep.add_argument("--depth_from", default=None, choices=("bones",), help="bones: no depths at all -- they are solved from the bone "
+                                                                           "lengths (DESIGN.md section 6q)")
+    from .bone_depth import add_bone_depth_options
+    add_bone_depth_options(p)
     p.add_argument("--sigma", type=float, default=1.5, help="the splatted Gaussians' width in heat-map pixels")
     p.add_argument("--first_id", type=int, default=0, help="frame id of the detections' first row (without frame_ids)")
     prepare.add_recording_options(p)
@@ -203,9 +231,14 @@ def _parser():
 
 def _cli(argv=None):
     from . import prepare
-    a = prepare.parse_recording_options(_parser(), argv)
+    from .bone_depth import bones_from_args
+    p = _parser()
+    a = prepare.parse_recording_options(p, argv)
+    if a.depth_from is None and (a.bones is not None or a.neck_depth is not None):
+        p.error("--bones and --neck_depth belong to --depth_from bones")
     rec = recording_from_detections(a.slam, detections_from_args(a), a.gt, a.scale, prepare.chunk_spans(a.start, a.end, a.test_size), a.fps,
-                                    sigma=a.sigma, camera_model_path=a.camera, gt_start_frame=a.mat_start, bridge=a.bridge)
+                                    depth=a.depth_from, sigma=a.sigma, camera_model_path=a.camera, gt_start_frame=a.mat_start, bridge=a.bridge,
+                                    bones=bones_from_args(a), neck_depth=a.neck_depth)
     prepare.print_report(rec)
     if a.out is not None:
         rec.write_chunks(a.out)

@@ -808,6 +808,30 @@ class WindowEngine:
         _capi.check(self.lib.gem_fill_missing(_ptr(seq), _ptr(valid), int(n_chunks), total // n_chunks, N_JOINTS, _stream()), self.lib)
         return seq
 
+    def bone_depths(self, kp, bones=None, rest=None, neck_depth=None, iters=None, out=None, opts=None):
+        """kp [F,15,2|3] -> (depth [F,15] f64, solved [F,15] u8, rms [F] f64), device tensors: per frame the depths along the
+        detections' rays that meet the bone lengths, the neck's anchor and the prior (gem_bone_depths).
+        `bones`, `rest`, `neck_depth`, `iters`: `bone_depth.options`; `opts`: its result, in their place.  An unsolved joint (solved 0)
+        keeps its prior depth.  rms: the frame's RMS bone-length residual in metres.  `out`: (depth, solved, rms) contiguous device
+        tensors of those shapes to write into (None entries are allocated).  No synchronisation."""
+        from . import bone_depth
+        if opts is None:
+            opts = bone_depth.options(bones, rest, neck_depth, iters)
+        t = self._keypoints("bone_depths", kp)
+        F = t.shape[0]
+        depth, solved, rms = out if out is not None else (None, None, None)
+        self._live_check("bone_depths", (depth, torch.float64, (F, N_JOINTS)), (solved, torch.uint8, (F, N_JOINTS)), (rms, torch.float64, (F,)))
+        depth = torch.empty(F, N_JOINTS, device=self.device, dtype=torch.float64) if depth is None else depth
+        solved = torch.empty(F, N_JOINTS, device=self.device, dtype=torch.uint8) if solved is None else solved
+        rms = torch.empty(F, device=self.device, dtype=torch.float64) if rms is None else rms
+        o = _capi.GemBoneDepthOpts(neck_depth=opts["neck_depth"], w_n=opts["w_n"], w_m=opts["w_m"], iters=opts["iters"], reserved=0)
+        for j in range(N_JOINTS):
+            o.bone[j], o.dbar[j] = float(opts["L"][j]), float(opts["dbar"][j])
+        poly = np.ascontiguousarray(self.camera.poly_c2w, dtype=np.float64)
+        _capi.check(self.lib.gem_bone_depths(self._h, _ptr(t), F, poly.ctypes.data_as(C.POINTER(C.c_double)), len(poly), C.byref(o),
+                                             _ptr(depth), _ptr(solved), _ptr(rms), _stream()), self.lib)
+        return depth, solved, rms
+
     # ------------------------------------------------------------------ profiling hook (bench.py)
     def profile_enable(self, on):
         _capi.check(self.lib.gem_profile_enable(self._h, 1 if on else 0), self.lib)

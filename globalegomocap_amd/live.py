@@ -111,10 +111,15 @@ class LiveOptimizer:
     graphs: replay one captured `optimize_windows` call for every window (the window's inputs lie in buffers of fixed address).
     scale: the SLAM scale applied to the translations of `rows=`.
     sigma: the width, in heat-map pixels, of the Gaussians that `push(keypoints=)` splats.
+    bones_for_depth, neck_depth: the wearer's 15 bone lengths in metres (entry 0 equal to 0; default: the mean skeleton's) and the neck's
+      distance from the camera, for `bone_depths` (`bone_depth.options`).
     """
 
     def __init__(self, camera_model_path, global_vae=GLOBAL_VAE_PATH, local_vae=LOCAL_VAE_PATH, *, scale=1.0, weights=None, bone="running",
-                 one_euro=None, eps=None, seed=0, graphs=True, lr=2, max_iter=25, heat_size=(64, 64), sigma=1.5):
+                 one_euro=None, eps=None, seed=0, graphs=True, lr=2, max_iter=25, heat_size=(64, 64), sigma=1.5, bones_for_depth=None,
+                 neck_depth=None):
+        from . import bone_depth
+        self._depth_opts = bone_depth.options(bones_for_depth, neck_depth=neck_depth)          # (refused before a device is touched)
         sd_g, sd_l = _as_state_dict(global_vae), _as_state_dict(local_vae)
         shape = infer_shape(sd_l, seq_len=SEQ_LEN)
         if infer_shape(sd_g, seq_len=SEQ_LEN) != shape:
@@ -208,6 +213,19 @@ class LiveOptimizer:
             self._row0 = rows[:1].copy()
         both = np.concatenate([self._row0, rows])
         return slam.scaled_trajectory(both[:, 1:4], both[:, 4:8], self.scale)[1:]
+
+    def bone_depths(self, keypoints):
+        """The depths of detections [k,15,2|3] that have none, for the frames about to be pushed: -> (depth [k,15] f64, solved [k,15]
+        u8, keypoints [k,15,3] f64 with the confidence of every unsolved joint set to 0), device tensors (`WindowEngine.bone_depths`
+        with the session's `bones_for_depth` and `neck_depth`).  Pushed as `push(keypoints=<the third>, depth=<the first>, ...)`, an
+        unsolved joint is a lost detection: its map is blank and it holds its last usable lift.  Every frame is solved on its own: the
+        depths do not depend on how the stream is cut into pushes.  No synchronisation."""
+        e = self._engine()
+        kp_d = e._keypoints("bone_depths", keypoints)
+        depth, solved, _ = e.bone_depths(kp_d, opts=self._depth_opts)
+        masked = kp_d.clone()
+        masked[..., 2] = torch.where(solved.bool(), kp_d[..., 2], torch.zeros_like(kp_d[..., 2]))
+        return depth, solved, masked
 
     def push(self, *, heat=None, depth=None, est_local=None, rows=None, cams=None, times=None, keypoints=None):
         """k >= 1 new frames: heat [k,H,W,15], or in its place keypoints [k,15,2|3] -- 2-D detections (u, v[, confidence]) in pixels of the
@@ -303,13 +321,14 @@ def step_summary(window_log):
 
 
 def replay(slam_result_path, heatmap_dir, depth_dir, start_frame, end_frame, camera_model_path, fps=25, pace="max", save_pose=None,
-           verbose=True, keypoints=None, first_id=0, **session):
+           verbose=True, keypoints=None, first_id=0, depth_from=None, **session):
     """A prepared recording pushed through a `LiveOptimizer` one frame at a time: the frames [start_frame, end_frame) of the listings
     come to the device with `prepare`'s reader, the trajectory's rows of those frame ids are the cameras.  pace "realtime" sleeps to
     the timestamps, "max" does not.  `session`: the keyword arguments of `LiveOptimizer`.  -> (result dict with "dropped", the
     session's window_log).  A replay of a recording: a rig calls `push` itself.  `keypoints` (with `heatmap_dir` None): a detections
     file (`detections.read_detections`; `first_id`: the frame id of its first row) pushed with `keypoints=` instead of heat-maps, the
-    depths from the file or from `depth_dir`."""
+    depths from the file or from `depth_dir`, or with depth_from="bones" solved per push from the bone lengths
+    (`LiveOptimizer.bone_depths`; the session's `bones_for_depth=` and `neck_depth=`)."""
     from . import prepare, slam
     if pace not in ("max", "realtime"):
         raise ValueError('pace is "max" or "realtime"')
@@ -320,14 +339,21 @@ def replay(slam_result_path, heatmap_dir, depth_dir, start_frame, end_frame, cam
     rows = rows[(ids >= start_frame) & (ids < end_frame)]
     if (keypoints is None) == (heatmap_dir is None):
         raise ValueError("replay: give exactly one of the heat-map directory and keypoints=")
+    if depth_from not in (None, "bones"):
+        raise ValueError('replay: depth_from is None or "bones"')
+    if depth_from is not None and (keypoints is None or depth_dir is not None):
+        raise ValueError('replay: depth_from="bones" goes with keypoints= and without a depth directory')
     if keypoints is not None:
         from . import detections
         det = detections.read_detections(keypoints, first_id)
         pick = detections.span_rows(det["frame_ids"], [(start_frame, end_frame)])[0]
-        if det["depth"] is None and depth_dir is None:
+        if det["depth"] is None and depth_dir is None and depth_from is None:
             raise ValueError("replay: the joints' depths are needed: `depth` in the detections file, or the depth directory")
         kp = det["keypoints"][pick]
-        depth = det["depth"][pick] if det["depth"] is not None else detections.depths_from_mat_dir(depth_dir, det["frame_ids"][pick])
+        if depth_from is not None:
+            depth = None
+        else:
+            depth = det["depth"][pick] if det["depth"] is not None else detections.depths_from_mat_dir(depth_dir, det["frame_ids"][pick])
         heat, live = None, LiveOptimizer(camera_model_path, **session)
     else:
         heat_paths, depth_paths = prepare.list_frames(heatmap_dir, start_frame, end_frame), prepare.list_frames(depth_dir, start_frame, end_frame)
@@ -343,7 +369,10 @@ def replay(slam_result_path, heatmap_dir, depth_dir, start_frame, end_frame, cam
                 wait = (rows[i, 0] - rows[0, 0]) - (time.perf_counter() - wall0)
                 if wait > 0:
                     time.sleep(wait)
-            if heat is None:
+            if heat is None and depth is None:
+                d, _, masked = live.bone_depths(kp[i:i + 1])
+                live.push(keypoints=masked, depth=d, rows=rows[i:i + 1])
+            elif heat is None:
                 live.push(keypoints=kp[i:i + 1], depth=depth[i:i + 1], rows=rows[i:i + 1])
             else:
                 live.push(heat=heat[i:i + 1], depth=depth[i:i + 1], rows=rows[i:i + 1])
@@ -386,6 +415,10 @@ def _parser():
     src.add_argument("--keypoints", default=None, metavar="FILE", help="2-D detections in place of heat-maps: .npy [N,15,2|3] or .npz with "
                                                                        "keypoints[, depth, frame_ids]; u, v in pixels of the fisheye image")
     p.add_argument("--depths", default=None, metavar="DIR", help="needed with --heatmaps, and with --keypoints unless the file carries `depth`")
+    p.add_argument("--depth_from", default=None, choices=("bones",), help="bones: with --keypoints and no depths at all, they are solved "
+                                                                         "from the bone lengths (DESIGN.md section 6q)")
+    from .bone_depth import add_bone_depth_options
+    add_bone_depth_options(p)
     p.add_argument("--first_id", type=int, default=0, help="frame id of the first row of --keypoints (without frame_ids)")
     p.add_argument("--sigma", type=float, default=1.5, help="the width of the Gaussians splatted from --keypoints, in heat-map pixels")
     p.add_argument("--scale", type=float, default=1.0, help="the SLAM scale applied to the trajectory's translations")
@@ -413,11 +446,16 @@ def _cli(argv=None):
     a = p.parse_args(argv)
     if a.heatmaps is not None and a.depths is None:
         p.error("--heatmaps needs --depths")
+    if a.depth_from is not None and (a.keypoints is None or a.depths is not None):
+        p.error("--depth_from bones goes with --keypoints and excludes --depths")
+    if a.depth_from is None and (a.bones is not None or a.neck_depth is not None):
+        p.error("--bones and --neck_depth belong to --depth_from bones")
+    from .bone_depth import bones_from_args
     weights = dict(vae_weight=a.vae, smoothness_weight=a.smooth, bone_length_weight=a.bone_length, weight_3d=a.weight_3d,
                    reproj_weight=a.reproj_weight)
     replay(a.slam, a.heatmaps, a.depths, a.start, a.end, a.camera, fps=a.fps, pace=a.pace, save_pose=a.save_pose, global_vae=a.global_vae,
            local_vae=a.local_vae, scale=a.scale, weights=weights, bone=a.bone, one_euro=a.one_euro, seed=a.seed, keypoints=a.keypoints,
-           first_id=a.first_id, sigma=a.sigma)
+           first_id=a.first_id, sigma=a.sigma, depth_from=a.depth_from, bones_for_depth=bones_from_args(a), neck_depth=a.neck_depth)
 
 
 if __name__ == "__main__":

@@ -229,9 +229,11 @@ class Recording:
     `to_recording_frame`); None for a recording with ground truth.  `scale` and `scale_report` (`slam_scale.ScaleEstimate`): the SLAM
     scale a recording prepared with scale="auto" was given and how it was found; None on the other routes.  `bridge_report`
     (`slam_bridge.BridgeReport`) and `bridged` (one bool array per chunk: the frames whose camera was invented) for a recording prepared
-    with `bridge=`; None without."""
+    with `bridge=`; None without.  `depth_report` (`bone_depth.BoneDepthReport`) for a recording of detections whose depths were solved
+    from the bone lengths; None on every other route."""
 
-    def __init__(self, chunks, origins=None, scale=None, scale_report=None, bridge_report=None):
+    def __init__(self, chunks, origins=None, scale=None, scale_report=None, bridge_report=None, depth_report=None):
+        self.depth_report = depth_report
         self.chunks = list(chunks)
         self.origins = origins
         self.scale, self.scale_report = scale, scale_report
@@ -636,7 +638,7 @@ def print_report(rec, sequence=True):
     """What a preparation tells about its recording: the scale estimate's line, the bridge's line, and per chunk the reference's
     `running test sequence from a to b` (its chunk loop's; not with `sequence` False) and `The initial mpjpe is: ...` (with ground
     truth)."""
-    for report in (rec.scale_report, rec.bridge_report):
+    for report in (rec.depth_report, rec.scale_report, rec.bridge_report):
         if report is not None:
             print(report.line())
     for c in rec.chunks:

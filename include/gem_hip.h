@@ -812,6 +812,32 @@ int gem_lift_keypoints(gem_handle* h, const double* d_kp, const double* d_depth,
  * frame in a chunk is left untouched (the caller refuses such a recording).  Works on the current device. */
 int gem_fill_missing(double* d_seq, const unsigned char* d_valid, int n_chunks, int frames_per_chunk, int n_joints, void* stream);
 
+/* ---- Depths from bone lengths: 2-D detections without a depth network ----
+ * A head-mounted camera fixes the joints' depths: the calibration makes every detection a unit ray r_j (camera2world at depth 1, the
+ * expressions of gem_lift_keypoints, so that depth * ray there has the bits of d_j r_j here), the wearer's bone lengths L_j are
+ * constant, and the neck sits at a nearly fixed distance from the camera.  Per frame, independently, the depths d_0 .. d_14 minimise
+ *     sum_bones (|d_j r_j - d_p r_p| - L_j)^2 + w_n (d_0 - neck_depth)^2 + w_m sum_j (d_j - dbar_j)^2,        p = parent of j,
+ * by Levenberg-Marquardt: `iters` iterations from d = dbar; a step solves (A + lambda diag A) delta = -g for the normal matrix A, whose
+ * graph is the skeleton's tree (eliminated leaf to root without fill, O(15)); the trial point max(d + delta, 0.01) is taken when it
+ * lowers the cost, lambda (1e-3 at first) then falls tenfold, else rises tenfold.  A bone of zero extent has a zero Jacobian row.
+ * A joint is SOLVED when it and every joint on its path to the neck are USABLE (above).  Only solved joints and the bones between
+ * them take part; every other joint keeps dbar_j, and a frame whose neck is unusable keeps every dbar_j.
+ * d_kp [n_frames,15,3] f64; h_poly_c2w as gem_lift_keypoints takes it; outputs (each may be NULL, not all) d_depth [n_frames,15] f64,
+ * d_solved [n_frames,15] u8, d_rms [n_frames] f64: sqrt of the mean squared bone residual, in metres, at the depths returned, over the
+ * bones that took part (0 without any) -- a large value says the detections contradict the skeleton.  The handle must have been
+ * created with the 15-joint egocentric tree.  bone[0] = 0, bone[j] >= 0, dbar[j] >= 0.01, neck_depth > 0, w_n >= 0, w_m > 0,
+ * 1 <= iters <= 1000, all finite: anything else is refused before any launch.  float64 without fused multiply-adds, every sum in a
+ * fixed order: two calls give the same bytes, and a frame's bytes do not depend on the other frames of its call.  Asynchronous on
+ * `stream`. */
+typedef struct gem_bone_depth_opts {
+    double bone[GEM_MAX_JOINTS];      /* L_j, metres; entries 0 and 15 unused (0) */
+    double dbar[GEM_MAX_JOINTS];      /* the prior depths and the start */
+    double neck_depth, w_n, w_m;
+    int32_t iters, reserved;
+} gem_bone_depth_opts;
+int gem_bone_depths(gem_handle* h, const double* d_kp, int64_t n_frames, const double* h_poly_c2w, int n_poly, const gem_bone_depth_opts* opts,
+                    double* d_depth, unsigned char* d_solved, double* d_rms, void* stream);
+
 /* ---- The SLAM scale of a recording without ground truth, from foot contacts: `--scale auto` ----
  * A monocular SLAM gives the camera's rotation R_t and its translation c_t up to one factor s; the lifted poses x_t are metric.  A
  * foot that stands does not move in the world, so R_t x_t,foot + s c_t is constant over a stance phase.  With q[t,side] =
