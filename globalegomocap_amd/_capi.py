@@ -228,6 +228,7 @@ SIGNATURES = {
     "gem_lift_keypoints": (C.c_int, [_P, _P, _P, C.c_int64, C.POINTER(C.c_double), C.c_int, _P, _P, _P, _P, _P]),
     "gem_fill_missing": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P]),
     "gem_bone_depths": (C.c_int, [_P, _P, C.c_int64, C.POINTER(C.c_double), C.c_int, C.POINTER(GemBoneDepthOpts), _P, _P, _P, _P]),
+    "gem_heatmap_peaks": (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_double, _P, _P, _P]),
     "gem_slam_scale_work": (C.c_int64, [C.c_int64, C.c_int, C.c_int]),
     "gem_slam_scale": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(C.c_int), _P, _P, _P, C.c_int64, C.c_int, C.c_double, C.c_int, _P,
                                  C.c_int64, _P, _P, _P, _P]),

@@ -450,6 +450,7 @@ int launch_lift(gem_handle* h, const float* heat, const double* depth, int F, co
 #include "jpeg.h"                      // gem_jpeg_header, gem_jpeg_bound, gem_jpeg_encode
 #include "keypoints.h"                 // gem_keypoint_heatmaps, gem_lift_keypoints, gem_fill_missing
 #include "bone_depth.h"                // gem_bone_depths
+#include "heat_peaks.h"                // gem_heatmap_peaks
 #include "slam_scale.h"                // gem_slam_scale_work, gem_slam_scale
 #include "ground.h"                    // gem_ground_plane_work, gem_ground_plane, gem_similarity_compose
 #include "foot_lock.h"                 // gem_foot_lock_work, gem_foot_lock

@@ -170,7 +170,7 @@ __global__ __launch_bounds__(256) void mat_frames_kernel(MatArgs m) {
     const int64_t payload = a.offsets[f];
     if (kind & GEM_MAT_HEAT_F64) tile_in<true, HC, WC, JC, WTC>(a, tile, payload, w0, wn);
     else tile_in<false, HC, WC, JC, WTC>(a, tile, payload, w0, wn);
-    if (t == 0 && (int)threadIdx.x < J) {
+    if (m.depth && t == 0 && (int)threadIdx.x < J) {          // (a recording without depth files: heat-maps only)
         const int64_t at = m.depth_offsets[f];
         m.depth[(int64_t)f * J + threadIdx.x] = (kind & GEM_MAT_DEPTH_F32) ? (double)__uint_as_float(word_at(a, at + 4 * threadIdx.x))      // widened exactly
                                                                             : double_at(a, at + 8 * threadIdx.x);
@@ -244,7 +244,7 @@ int gem_mat_read(const char* const* paths, int64_t n, const int64_t* at, const i
 int gem_mat_frames(const void* d_image, int64_t image_len, const int64_t* d_heat_offsets, const int64_t* d_depth_offsets,
                    const int32_t* d_kinds, int64_t n, int heat_h, int heat_w, int n_joints, float* d_heat, double* d_depth, void* stream) {
     if (n == 0) return 0;
-    if (!d_image || !d_heat_offsets || !d_depth_offsets || !d_kinds || !d_heat || !d_depth || n < 0 || heat_h < 1 || heat_w < 1 ||
+    if (!d_image || !d_heat_offsets || !d_depth_offsets != !d_depth || !d_kinds || !d_heat || n < 0 || heat_h < 1 || heat_w < 1 ||
         n_joints < 1 || n_joints > 256 || image_len < 4) {
         set_error("gem_mat_frames: bad argument (at most 256 joints)"); return 1;
     }

@@ -832,6 +832,27 @@ class WindowEngine:
                                              _ptr(depth), _ptr(solved), _ptr(rms), _stream()), self.lib)
         return depth, solved, rms
 
+    def heatmap_peaks(self, heat, min_peak=0.0, out=None, upscale=16, pad_x=128, pad_y=0):
+        """heat [F,H,W,15] f32 at the engine's `heat_size` -> (kp [F,15,3] f64, arg [F,15] int32), device tensors: per joint the
+        map's peak as a detection (u, v, confidence) -- the integer maximum refined by a Gaussian-windowed mean shift, in the pixels of
+        the fisheye image, confidence = min(peak, 1) -- and the flat index of the integer maximum (gem_heatmap_peaks, DESIGN.md section
+        6r).  A joint whose peak is NaN, not positive or below `min_peak` is (0, 0, 0): an unusable detection.  `out`: (kp, arg)
+        contiguous device tensors of those shapes to write into (a None entry is allocated).  No synchronisation."""
+        heat_t = self._f32(heat)
+        if heat_t.dim() != 4 or tuple(heat_t.shape[1:]) != (self.heat_size[0], self.heat_size[1], N_JOINTS):
+            raise ValueError("heatmap_peaks wants heat-maps [F,%d,%d,%d], got %s" % (self.heat_size[0], self.heat_size[1], N_JOINTS, tuple(heat_t.shape)))
+        min_peak = float(min_peak)
+        if not (np.isfinite(min_peak) and min_peak >= 0):
+            raise ValueError("heatmap_peaks: min_peak must be a finite number >= 0, got %r" % min_peak)
+        F = heat_t.shape[0]
+        kp, arg = out if out is not None else (None, None)
+        self._live_check("heatmap_peaks", (kp, torch.float64, (F, N_JOINTS, 3)), (arg, torch.int32, (F, N_JOINTS)))
+        kp = torch.empty(F, N_JOINTS, 3, device=self.device, dtype=torch.float64) if kp is None else kp
+        arg = torch.empty(F, N_JOINTS, device=self.device, dtype=torch.int32) if arg is None else arg
+        _capi.check(self.lib.gem_heatmap_peaks(self._h, _ptr(heat_t), F, int(upscale), int(pad_x), int(pad_y), min_peak, _ptr(kp), _ptr(arg),
+                                               _stream()), self.lib)
+        return kp, arg
+
     # ------------------------------------------------------------------ profiling hook (bench.py)
     def profile_enable(self, on):
         _capi.check(self.lib.gem_profile_enable(self._h, 1 if on else 0), self.lib)

@@ -64,13 +64,24 @@ def _pieces(n_pushed, k):
 def check_push(n_pushed_times, heat, depth, est_local, rows, cams, times, heat_size=(64, 64), keypoints=None):
     """The host-side checks of `LiveOptimizer.push`, before anything is enqueued: exactly one of heat / keypoints, of depth / est_local
     and of rows / cams + times, shapes that agree on k >= 1 frames, timestamps that increase strictly (also past `n_pushed_times`, the
-    last timestamp of the pushes before; None on the first).  -> (k, timestamps as a float64 array, the five other arguments as arrays or tensors).  ValueError otherwise."""
+    last timestamp of the pushes before; None on the first).  -> (k, timestamps as a float64 array, the five other arguments as arrays or tensors).  ValueError otherwise.
+    depth may be the string "bones" together with heat= (the depths are solved from the bone lengths at the maps' peaks, DESIGN.md
+    section 6r): it is handed back as it is; with est_local= or keypoints= it is refused."""
+    from_bones = isinstance(depth, str)
+    if from_bones:
+        if depth != "bones":
+            raise ValueError('push: depth is an array [k,%d] or "bones", got %r' % (N_JOINTS, depth))
+        if est_local is not None:
+            raise ValueError("push: give exactly one of depth= (lifted here) and est_local= (already lifted)")
+        if keypoints is not None or heat is None:
+            raise ValueError('push: depth="bones" goes with heat= (the depths of keypoints= come from `bone_depths`)')
+        depth = None
     if heat is None and keypoints is None:
         raise ValueError("push: heat= is needed")
     if heat is not None and keypoints is not None:
         raise ValueError("push: give exactly one of heat= (the pose network's maps) and keypoints= (2-D detections, splatted here)")
     heat, depth, est_local, rows, cams, times = (x if x is None or torch.is_tensor(x) else np.asarray(x) for x in (heat, depth, est_local, rows, cams, times))
-    if (depth is None) == (est_local is None):
+    if not from_bones and (depth is None) == (est_local is None):
         raise ValueError("push: give exactly one of depth= (lifted here) and est_local= (already lifted)")
     if (rows is None) == (cams is None):
         raise ValueError("push: give exactly one of rows= (trajectory rows) and cams= with times=")
@@ -95,7 +106,7 @@ def check_push(n_pushed_times, heat, depth, est_local, rows, cams, times, heat_s
     chain = t if n_pushed_times is None else np.concatenate([[n_pushed_times], t])
     if not np.isfinite(t).all() or not (np.diff(chain) > 0).all():
         raise ValueError("push: timestamps must be finite and increase strictly")
-    return k, t, (heat, depth, est_local, rows, cams)
+    return k, t, (heat, "bones" if from_bones else depth, est_local, rows, cams)
 
 
 class LiveOptimizer:
@@ -113,13 +124,17 @@ class LiveOptimizer:
     sigma: the width, in heat-map pixels, of the Gaussians that `push(keypoints=)` splats.
     bones_for_depth, neck_depth: the wearer's 15 bone lengths in metres (entry 0 equal to 0; default: the mean skeleton's) and the neck's
       distance from the camera, for `bone_depths` (`bone_depth.options`).
+    min_peak: with `push(heat=, depth="bones")`, a joint whose map peaks below it is treated as not detected.
     """
 
     def __init__(self, camera_model_path, global_vae=GLOBAL_VAE_PATH, local_vae=LOCAL_VAE_PATH, *, scale=1.0, weights=None, bone="running",
                  one_euro=None, eps=None, seed=0, graphs=True, lr=2, max_iter=25, heat_size=(64, 64), sigma=1.5, bones_for_depth=None,
-                 neck_depth=None):
+                 neck_depth=None, min_peak=0.0):
         from . import bone_depth
         self._depth_opts = bone_depth.options(bones_for_depth, neck_depth=neck_depth)          # (refused before a device is touched)
+        self.min_peak = float(min_peak)
+        if not (np.isfinite(self.min_peak) and self.min_peak >= 0):
+            raise ValueError("min_peak must be a finite number >= 0, got %r" % (min_peak,))
         sd_g, sd_l = _as_state_dict(global_vae), _as_state_dict(local_vae)
         shape = infer_shape(sd_l, seq_len=SEQ_LEN)
         if infer_shape(sd_g, seq_len=SEQ_LEN) != shape:
@@ -232,7 +247,11 @@ class LiveOptimizer:
         fisheye image, splatted into the maps on the device (`WindowEngine.keypoint_heatmaps`; with depth= they are lifted at the
         detection itself, `lift_keypoints`, a joint without a usable detection holding its last usable lift: the session's first frame
         must have every joint); either depth [k,15] (lifted with `WindowEngine.lift_skeleton`) or est_local [k,15,3]
-        (already lifted); either rows [k,8] trajectory rows `time tx ty tz qx qy qz qw` (made cameras by `slam`'s functions, relative
+        (already lifted), or with heat= the string depth="bones" for a pose network without a depth head: the maps' sub-pixel peaks
+        (`heatmap_peaks`, the session's `min_peak`) are given depths by `bone_depths` with the session's skeleton and lifted at the
+        peak, a joint the solve did not reach holding its last lift (the session's first frame must have every joint solved: one
+        15-byte read-back on the first push); the maps pushed are the caller's own;
+        either rows [k,8] trajectory rows `time tx ty tz qx qy qz qw` (made cameras by `slam`'s functions, relative
         to the session's first frame, translations times `scale`) or cams [k,4,4] with times [k].  Host or device arrays.  Every window
         these frames complete is optimised at once; the call blocks until they are done, reads their statistics and raises the
         reference's Exception("norm is zero!") for a degenerate one.  -> {"frames": index of the first returned frame, "optimized",
@@ -252,6 +271,16 @@ class LiveOptimizer:
             kp_d = e._keypoints("push", keypoints)
             heat_d = e.keypoint_heatmaps(kp_d, self.sigma)
             pose_d = self._device(est_local, torch.float32) if est_local is not None else e.lift_keypoints(kp_d, depth, prev=self._kp_prev, want_f64=False)[1]
+        elif isinstance(depth, str):
+            heat_d = self._device(heat, torch.float32)
+            kp_d, _ = e.heatmap_peaks(heat_d, min_peak=self.min_peak)
+            depth_d, solved, _ = e.bone_depths(kp_d, opts=self._depth_opts)
+            if self.n_pushed == 0:
+                lost = np.nonzero(solved[0].cpu().numpy() == 0)[0]
+                if len(lost):
+                    raise ValueError("push: joints %s of the session's first frame have no usable detection: nothing to hold" % lost.tolist())
+            kp_d[..., 2] = torch.where(solved.bool(), kp_d[..., 2], torch.zeros_like(kp_d[..., 2]))
+            pose_d = e.lift_keypoints(kp_d, depth_d, prev=self._kp_prev, want_f64=False)[1]
         else:
             heat_d = self._device(heat, torch.float32)
             pose_d = self._device(est_local, torch.float32) if est_local is not None else e.lift_skeleton(heat_d, depth, want_f64=False)[1]
@@ -328,7 +357,8 @@ def replay(slam_result_path, heatmap_dir, depth_dir, start_frame, end_frame, cam
     session's window_log).  A replay of a recording: a rig calls `push` itself.  `keypoints` (with `heatmap_dir` None): a detections
     file (`detections.read_detections`; `first_id`: the frame id of its first row) pushed with `keypoints=` instead of heat-maps, the
     depths from the file or from `depth_dir`, or with depth_from="bones" solved per push from the bone lengths
-    (`LiveOptimizer.bone_depths`; the session's `bones_for_depth=` and `neck_depth=`)."""
+    (`LiveOptimizer.bone_depths`; the session's `bones_for_depth=` and `neck_depth=`).  depth_from="bones" with `heatmap_dir` and no
+    depth directory: no depth file is read, every frame is pushed as `push(heat=, depth="bones")` (the session's `min_peak=`)."""
     from . import prepare, slam
     if pace not in ("max", "realtime"):
         raise ValueError('pace is "max" or "realtime"')
@@ -341,8 +371,8 @@ def replay(slam_result_path, heatmap_dir, depth_dir, start_frame, end_frame, cam
         raise ValueError("replay: give exactly one of the heat-map directory and keypoints=")
     if depth_from not in (None, "bones"):
         raise ValueError('replay: depth_from is None or "bones"')
-    if depth_from is not None and (keypoints is None or depth_dir is not None):
-        raise ValueError('replay: depth_from="bones" goes with keypoints= and without a depth directory')
+    if depth_from is not None and depth_dir is not None:
+        raise ValueError('replay: depth_from="bones" goes without a depth directory')
     if keypoints is not None:
         from . import detections
         det = detections.read_detections(keypoints, first_id)
@@ -356,10 +386,13 @@ def replay(slam_result_path, heatmap_dir, depth_dir, start_frame, end_frame, cam
             depth = det["depth"][pick] if det["depth"] is not None else detections.depths_from_mat_dir(depth_dir, det["frame_ids"][pick])
         heat, live = None, LiveOptimizer(camera_model_path, **session)
     else:
-        heat_paths, depth_paths = prepare.list_frames(heatmap_dir, start_frame, end_frame), prepare.list_frames(depth_dir, start_frame, end_frame)
-        if len(heat_paths) != end_frame - start_frame or len(depth_paths) != end_frame - start_frame:
+        if depth_dir is None and depth_from is None:
+            raise ValueError('replay: the joints\' depths are needed: the depth directory, or depth_from="bones"')
+        heat_paths = prepare.list_frames(heatmap_dir, start_frame, end_frame)
+        depth_paths = prepare.list_frames(depth_dir, start_frame, end_frame) if depth_from is None else None
+        if len(heat_paths) != end_frame - start_frame or (depth_paths is not None and len(depth_paths) != end_frame - start_frame):
             raise ValueError("frames [%d, %d) of the listings are asked for, but there are %d heat-map and %d depth files"
-                             % (start_frame, end_frame, len(heat_paths), len(depth_paths)))
+                             % (start_frame, end_frame, len(heat_paths), -1 if depth_paths is None else len(depth_paths)))
         heat, depth, _ = prepare.frames_to_device(heat_paths, depth_paths)
         live = LiveOptimizer(camera_model_path, heat_size=tuple(heat.shape[1:3]), **session)
     try:
@@ -374,6 +407,8 @@ def replay(slam_result_path, heatmap_dir, depth_dir, start_frame, end_frame, cam
                 live.push(keypoints=masked, depth=d, rows=rows[i:i + 1])
             elif heat is None:
                 live.push(keypoints=kp[i:i + 1], depth=depth[i:i + 1], rows=rows[i:i + 1])
+            elif depth is None:
+                live.push(heat=heat[i:i + 1], depth="bones", rows=rows[i:i + 1])
             else:
                 live.push(heat=heat[i:i + 1], depth=depth[i:i + 1], rows=rows[i:i + 1])
         tail = live.flush()
@@ -415,10 +450,13 @@ def _parser():
     src.add_argument("--keypoints", default=None, metavar="FILE", help="2-D detections in place of heat-maps: .npy [N,15,2|3] or .npz with "
                                                                        "keypoints[, depth, frame_ids]; u, v in pixels of the fisheye image")
     p.add_argument("--depths", default=None, metavar="DIR", help="needed with --heatmaps, and with --keypoints unless the file carries `depth`")
-    p.add_argument("--depth_from", default=None, choices=("bones",), help="bones: with --keypoints and no depths at all, they are solved "
-                                                                         "from the bone lengths (DESIGN.md section 6q)")
+    p.add_argument("--depth_from", default=None, choices=("bones",), help="bones: no depths at all -- they are solved from the bone "
+                                                                         "lengths, at the detections of --keypoints or at the sub-pixel "
+                                                                         "peaks of --heatmaps (DESIGN.md sections 6q, 6r)")
     from .bone_depth import add_bone_depth_options
     add_bone_depth_options(p)
+    p.add_argument("--min_peak", type=float, default=None, metavar="P", help="with --heatmaps --depth_from bones: a joint whose map peaks "
+                                                                             "below P is treated as not detected (default 0)")
     p.add_argument("--first_id", type=int, default=0, help="frame id of the first row of --keypoints (without frame_ids)")
     p.add_argument("--sigma", type=float, default=1.5, help="the width of the Gaussians splatted from --keypoints, in heat-map pixels")
     p.add_argument("--scale", type=float, default=1.0, help="the SLAM scale applied to the trajectory's translations")
@@ -444,18 +482,23 @@ def _parser():
 def _cli(argv=None):
     p = _parser()
     a = p.parse_args(argv)
-    if a.heatmaps is not None and a.depths is None:
-        p.error("--heatmaps needs --depths")
-    if a.depth_from is not None and (a.keypoints is None or a.depths is not None):
-        p.error("--depth_from bones goes with --keypoints and excludes --depths")
-    if a.depth_from is None and (a.bones is not None or a.neck_depth is not None):
-        p.error("--bones and --neck_depth belong to --depth_from bones")
+    if a.heatmaps is not None and a.depths is None and a.depth_from is None:
+        p.error("--heatmaps needs --depths or --depth_from bones")
+    if a.depth_from is not None and a.depths is not None:
+        p.error("--depth_from bones excludes --depths")
+    if a.depth_from is None and (a.bones is not None or a.neck_depth is not None or a.min_peak is not None):
+        p.error("--bones, --neck_depth and --min_peak belong to --depth_from bones")
+    if a.min_peak is not None and a.heatmaps is None:
+        p.error("--min_peak goes with --heatmaps: detections carry their own confidence")
+    if a.min_peak is not None and not (np.isfinite(a.min_peak) and a.min_peak >= 0):
+        p.error("--min_peak must be a finite number >= 0")
     from .bone_depth import bones_from_args
     weights = dict(vae_weight=a.vae, smoothness_weight=a.smooth, bone_length_weight=a.bone_length, weight_3d=a.weight_3d,
                    reproj_weight=a.reproj_weight)
     replay(a.slam, a.heatmaps, a.depths, a.start, a.end, a.camera, fps=a.fps, pace=a.pace, save_pose=a.save_pose, global_vae=a.global_vae,
            local_vae=a.local_vae, scale=a.scale, weights=weights, bone=a.bone, one_euro=a.one_euro, seed=a.seed, keypoints=a.keypoints,
-           first_id=a.first_id, sigma=a.sigma, depth_from=a.depth_from, bones_for_depth=bones_from_args(a), neck_depth=a.neck_depth)
+           first_id=a.first_id, sigma=a.sigma, depth_from=a.depth_from, bones_for_depth=bones_from_args(a), neck_depth=a.neck_depth,
+           min_peak=0.0 if a.min_peak is None else a.min_peak)
 
 
 if __name__ == "__main__":

@@ -41,6 +41,15 @@ no `gt_global_skeleton`, and since one scale holds for the whole recording its c
 A trajectory that lacks lines because SLAM lost tracking is still refused -- unless `--bridge [SECONDS]` (`bridge=`) is given on this
 route: the missing cameras are then invented kinematically, marked in `Recording.bridged` and accounted for in
 `Recording.bridge_report` (`slam_bridge`).
+
+A pose network without a depth head leaves heat-maps only.  `--depth_from bones` in place of `--depths` (`depth="bones"` with
+`depth_dir=None`) takes the maps' sub-pixel peaks (`gem_heatmap_peaks`) and solves the depths from the wearer's bone lengths
+(`gem_bone_depths`); no depth file is listed or read, and the Recording keeps the network's own maps:
+
+    python -m globalegomocap_amd.prepare --slam traj.txt --heatmaps DIR --depth_from bones [--bones FILE.npy] [--neck_depth M] \\
+        [--min_peak P] --scale auto --start 551 --end 3300 --optimize
+
+`--peaks subpixel` with `--depths` keeps the network's depths and lifts at the sub-pixel peak instead of the 16-pixel argmax.
 """
 import ctypes as C
 import io
@@ -384,19 +393,21 @@ def _read_files(lib, pool, readers, cpaths, at, room, sizes, n, block, found, rc
     return extra
 
 
-def payload_tables(n, paths, at, found, rcs, extra, block):
+def payload_tables(n, paths, at, found, rcs, extra, block, depths=True):
     """Where every frame's payloads lie and what they are -- host data only.  Files [0, n) hold the heat-maps, [n, 2n) the depths;
     `found` / `rcs` are what gem_mat_read left for the files at `at` in `block` (uint8 numpy array: the main block), `extra` the
     payloads `_read_range` made itself (rcs -1).  Payloads that are not in the files as they are get a place BEHIND the block:
     the extra ones, and the first row of a several-row depth (depth = loadmat(...)['depth'][0]).
     -> (where int64 [2n]: byte offsets; kinds int32 [n]: MAT_HEAT_F64 | MAT_DEPTH_F32; (H, W, J); heat_files [n]: None, or the
     heat-map as loadmat returns it where that is not float32 -- the pickle wants it as it is; parts [(offset, bytes)]: what goes
-    behind the block; end: the block's length with them)."""
+    behind the block; end: the block's length with them).  `depths` False: a recording without depth files -- there are n files, `where`
+    is [n] and no frame's kind has a depth bit."""
     total = block.size
-    where = np.zeros(2 * n, dtype=np.int64)
-    dtypes, dims = [None] * (2 * n), [None] * (2 * n)
+    m = 2 * n if depths else n
+    where = np.zeros(m, dtype=np.int64)
+    dtypes, dims = [None] * m, [None] * m
     heat_files = [None] * n
-    for i in range(2 * n):
+    for i in range(m):
         if rcs[i] == 0:
             a = found[i]
             where[i], dtypes[i], dims[i] = at[i] + a.offset, _NP_OF[a.storage], tuple(int(d) for d in a.dims[:a.ndim])
@@ -409,7 +420,7 @@ def payload_tables(n, paths, at, found, rcs, extra, block):
         end += padded(len(payload), _ALIGN)
         if i < n and (kept is not None or dt is not np.float32):
             heat_files[i] = kept if kept is not None else np.frombuffer(payload, dtype=dt).reshape(shape, order="F")
-    for i in range(n, 2 * n):          # a depth array of several rows inside the main block: its first row is strided there
+    for i in range(n, m):          # a depth array of several rows inside the main block: its first row is strided there
         if rcs[i] == 0 and (len(dims[i]) != 2 or dims[i][0] != 1):
             if len(dims[i]) != 2:
                 raise ValueError("%s: 'depth' is not a [1,J] array" % paths[i])
@@ -424,16 +435,16 @@ def payload_tables(n, paths, at, found, rcs, extra, block):
     if len(shapes) != 1 or len(next(iter(shapes))) != 3:
         raise ValueError("the heat-maps must all be [H,W,J] arrays of one shape, found %s" % sorted(shapes))
     J = next(iter(shapes))[2]
-    if any(dims[i] != (1, J) for i in range(n, 2 * n)):
+    if any(dims[i] != (1, J) for i in range(n, m)):
         raise ValueError("every depth file must hold a [1,%d] array" % J)
-    kinds = np.array([(_capi.MAT_HEAT_F64 if dtypes[f] is np.float64 else 0) | (_capi.MAT_DEPTH_F32 if dtypes[n + f] is np.float32 else 0)
+    kinds = np.array([(_capi.MAT_HEAT_F64 if dtypes[f] is np.float64 else 0) | (_capi.MAT_DEPTH_F32 if depths and dtypes[n + f] is np.float32 else 0)
                       for f in range(n)], dtype=np.int32)
     return where, kinds, next(iter(shapes)), heat_files, parts, end
 
 
-def _frames_from_arena(arena, total, in_block, where, kinds, shape, parts, end, device):
+def _frames_from_arena(arena, total, in_block, where, kinds, shape, parts, end, device, depths=True):
     """Upload + launch: the payloads of `parts` land behind the block's image (`total` bytes of `arena`; `in_block`: whether any
-    frame is read from it), in the same arena; the tables go up and ONE gem_mat_frames picks all frames out.  -> (heat, depth)."""
+    frame is read from it), in the same arena; the tables go up and ONE gem_mat_frames picks all frames out.  -> (heat, depth; None without `depths`)."""
     import torch
     n, (H, W, J) = len(kinds), shape
     if parts:
@@ -447,10 +458,10 @@ def _frames_from_arena(arena, total, in_block, where, kinds, shape, parts, end, 
         whole[total:end].copy_(side, non_blocking=True)
         arena = whole
     tables = torch.from_numpy(np.concatenate([where, kinds.astype(np.int64)])).to(device)
-    kinds_d = tables[2 * n:].to(torch.int32)
+    kinds_d = tables[len(where):].to(torch.int32)
     heat = torch.empty((n, H, W, J), dtype=torch.float32, device=device)
-    depth = torch.empty((n, J), dtype=torch.float64, device=device)
-    mat_frames(arena, end, tables[:n], tables[n:2 * n], kinds_d, heat, depth)
+    depth = torch.empty((n, J), dtype=torch.float64, device=device) if depths else None
+    mat_frames(arena, end, tables[:n], tables[n:2 * n] if depths else None, kinds_d, heat, depth)
     return heat, depth
 
 
@@ -459,27 +470,28 @@ def frames_to_device(heat_paths, depth_paths, device=None, readers=N_READERS, ti
     pinned block (reader threads, `gem_mat_read`), the block crosses PCIe range by range on the readers' two copy streams while
     the other ranges are still being read (one more copy for inflated or loadmat'ed payloads), and ONE launch of `gem_mat_frames`
     picks all frames out.  heat_files[f]: None, or the heat-map as loadmat returns it where the device copy (float32) is not the
-    file's own class."""
+    file's own class.  `depth_paths` None: a recording without depth files -- no such file is read or uploaded, `depth` is None."""
     import torch
     lib = _capi.load_library()
     device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     n = len(heat_paths)
-    if len(depth_paths) != n:
+    depths = depth_paths is not None
+    if depths and len(depth_paths) != n:
         raise ValueError("as many depth files as heat-map files are needed (%d / %d)" % (len(depth_paths), n))
     if n == 0:
-        return torch.empty((0, 64, 64, 15), device=device), torch.empty((0, 15), dtype=torch.float64, device=device), []
+        return torch.empty((0, 64, 64, 15), device=device), torch.empty((0, 15), dtype=torch.float64, device=device) if depths else None, []
     lap = Laps(timings)          # developer timing (tools/prepare_bench.py)
-    paths = list(heat_paths) + list(depth_paths)
+    paths = list(heat_paths) + (list(depth_paths) if depths else [])
     cpaths = _c_paths(paths)
-    readers = max(1, min(readers, 2 * n))
+    readers = max(1, min(readers, len(paths)))
     pool = reader_pool("mat", readers)
     sizes = _file_sizes(lib, pool, cpaths, readers)
     at, room, total = side_by_side(sizes, _ALIGN)
     lap("file sizes (one stat each)")
     pinned = torch.empty(total, dtype=torch.uint8, pin_memory=True)          # (torch keeps freed pinned blocks for the next call)
     block = pinned.numpy()
-    found = (_capi.GemMatArray * (2 * n))()
-    rcs = np.zeros(2 * n, dtype=np.int32)
+    found = (_capi.GemMatArray * len(paths))()
+    rcs = np.zeros(len(paths), dtype=np.int32)
     lap("pinned block")
     arena = torch.empty(total + 8, dtype=torch.uint8, device=device)
     cur = torch.cuda.current_stream()
@@ -499,22 +511,23 @@ def frames_to_device(heat_paths, depth_paths, device=None, readers=N_READERS, ti
         return ev
     extra = _read_files(lib, pool, readers, cpaths, at, room, sizes, n, block, found, rcs, paths, send, cur.wait_event)
     lap("read + scan (+ inflate / loadmat) on the reader threads")
-    where, kinds, shape, heat_files, parts, end = payload_tables(n, paths, at, found, rcs, extra, block)
+    where, kinds, shape, heat_files, parts, end = payload_tables(n, paths, at, found, rcs, extra, block, depths)
     lap("payload tables")
-    heat, depth = _frames_from_arena(arena, total, bool((rcs == 0).any()), where, kinds, shape, parts, end, device)
+    heat, depth = _frames_from_arena(arena, total, bool((rcs == 0).any()), where, kinds, shape, parts, end, device, depths)
     torch.cuda.current_stream().synchronize()          # (the pinned block is released on return)
     lap("copies' tail + gem_mat_frames")
     return heat, depth, heat_files
 
 
 def mat_frames(arena, image_len, heat_offsets, depth_offsets, kinds, heat, depth):
-    """gem_mat_frames on the current stream: arena (uint8 device tensor), int64 / int64 / int32 device tables -> heat, depth."""
+    """gem_mat_frames on the current stream: arena (uint8 device tensor), int64 / int64 / int32 device tables -> heat, depth.
+    `depth_offsets` and `depth` both None: the heat-maps alone."""
     import torch
     lib = _capi.load_library()
     n, H, W, J = heat.shape
     _capi.check(lib.gem_mat_frames(C.c_void_p(arena.data_ptr()), int(image_len), C.c_void_p(heat_offsets.data_ptr()),
-                                   C.c_void_p(depth_offsets.data_ptr()), C.c_void_p(kinds.data_ptr()), n, H, W, J,
-                                   C.c_void_p(heat.data_ptr()), C.c_void_p(depth.data_ptr()),
+                                   C.c_void_p(depth_offsets.data_ptr() if depth_offsets is not None else 0), C.c_void_p(kinds.data_ptr()), n, H, W, J,
+                                   C.c_void_p(heat.data_ptr()), C.c_void_p(depth.data_ptr() if depth is not None else 0),
                                    C.c_void_p(torch.cuda.current_stream().cuda_stream)), lib)
 
 
@@ -648,8 +661,65 @@ def print_report(rec, sequence=True):
             print("The initial mpjpe is: {}".format(c.initial_mpjpe))
 
 
+def depth_route(depth_dir, depth=None, bones=None, neck_depth=None, min_peak=None, peaks=None):
+    """The checks of `prepare_spans`' depth arguments, before a device is touched: exactly one of `depth_dir` (the pose network's depth
+    files) and depth="bones" (the depths are solved from the bone lengths at the maps' sub-pixel peaks, DESIGN.md section 6r);
+    `bones`, `neck_depth` (`bone_depth.options`) and `min_peak` (a finite number >= 0) belong to depth="bones"; `peaks` is None,
+    "argmax" (the reference's 16-pixel lift; with depth files only) or "subpixel" (what depth="bones" always uses).
+    -> (from_bones, subpixel, bone options or None, min_peak as a float).  ValueError otherwise."""
+    if depth is not None and not (isinstance(depth, str) and depth == "bones"):
+        raise ValueError('prepare: depth is None (the depth files of depth_dir) or "bones", got %r' % (depth,))
+    from_bones = depth is not None
+    if from_bones and depth_dir is not None:
+        raise ValueError('prepare: depth="bones" takes no depth directory (depth_dir=None)')
+    if not from_bones and depth_dir is None:
+        raise ValueError('prepare: the joints\' depths are needed: the depth directory, or depth="bones"')
+    if not from_bones and (bones is not None or neck_depth is not None or min_peak is not None):
+        raise ValueError('prepare: bones=, neck_depth= and min_peak= belong to depth="bones"')
+    if peaks not in (None, "argmax", "subpixel"):
+        raise ValueError('prepare: peaks is "argmax" or "subpixel", got %r' % (peaks,))
+    if from_bones and peaks == "argmax":
+        raise ValueError('prepare: depth="bones" needs the sub-pixel peaks (peaks="subpixel" or None)')
+    min_peak = 0.0 if min_peak is None else float(min_peak)
+    if not (np.isfinite(min_peak) and min_peak >= 0):
+        raise ValueError("prepare: min_peak must be a finite number >= 0, got %r" % min_peak)
+    bone_opts = None
+    if from_bones:
+        from . import bone_depth
+        bone_opts = bone_depth.options(bones, neck_depth=neck_depth)
+    return from_bones, from_bones or peaks == "subpixel", bone_opts, min_peak
+
+
+def lift_peaks(engine, heat, depth, bounds, spans, bone_opts=None, min_peak=0.0):
+    """The sub-pixel lift of heat-maps [n,H,W,15] on the device: `heatmap_peaks` -> (with `bone_opts`: `bone_depths`, the confidence
+    of every joint the solve did not reach set to 0) -> `lift_keypoints` -> `fill_missing` per chunk (rows bounds[k] of the frames).
+    `depth` [n,15]: the network's depths, unused with `bone_opts`.  -> (est_local [n,15,3] f64, `bone_depth.BoneDepthReport` or None).
+    A joint with no usable frame in a whole chunk is the detection route's ValueError: one read-back of an [n_chunks,15] mask."""
+    import torch
+    kp, _ = engine.heatmap_peaks(heat, min_peak=min_peak)
+    report = None
+    if bone_opts is not None:
+        from .bone_depth import summarize
+        depth, solved, rms = engine.bone_depths(kp, opts=bone_opts)
+        report = summarize(solved, rms)
+        kp[..., 2] = torch.where(solved.bool(), kp[..., 2], torch.zeros_like(kp[..., 2]))          # (unsolved: a lost detection from here on)
+    est_local, _, valid = engine.lift_keypoints(kp, depth)
+    seen = torch.stack([valid[lo:hi].bool().any(dim=0) for lo, hi in bounds]).cpu().numpy()
+    for row, (a, b) in zip(seen, spans):
+        lost = np.nonzero(~row)[0]
+        if len(lost):
+            raise ValueError("joints %s have no usable detection in the chunk [%d, %d): nothing to interpolate them from" % (lost.tolist(), a, b))
+    if len({hi - lo for lo, hi in bounds}) == 1:
+        engine.fill_missing(est_local, valid, len(bounds))
+    else:
+        for lo, hi in bounds:
+            engine.fill_missing(est_local[lo:hi], valid[lo:hi], 1)
+    return est_local, report
+
+
 def prepare_spans(slam_result_path, heatmap_dir, depth_dir, gt_path, spans, fps, mat_start_frame, camera_model_path=None, device=None,
-                  timings=None, scale=None, lag=None, tau=0.10, min_pairs=50, bridge=None):
+                  timings=None, scale=None, lag=None, tau=0.10, min_pairs=50, bridge=None, depth=None, bones=None, neck_depth=None,
+                  min_peak=None, peaks=None):
     """Every (start_frame, end_frame) of `spans` as one chunk, each prepared on its own as `main` does, all of them through the
     device together: stage -> gem_mat_frames -> lift -> head joints to the host -> per-chunk scale and cameras -> cameras up ->
     gem_prepare_global.  -> Recording.  `gt_path` None and `scale` given: a recording without ground truth -- the cameras come from
@@ -657,7 +727,13 @@ def prepare_spans(slam_result_path, heatmap_dir, depth_dir, gt_path, spans, fps,
     lifted poses first (`auto_scale` with `lag`, `tau`, `min_pairs`; one small record comes back), then the same path runs with it.
     `bridge`: None, or the longest stretch of lost SLAM tracking, in seconds, whose cameras are invented (True: 1 s; `slam_bridge`,
     DESIGN.md section 6o) -- only without ground truth, and the chunks must follow one another.  From the lifted poses on this is
-    `RecordingStage`."""
+    `RecordingStage`.
+    depth="bones" with depth_dir None: a pose network without a depth head.  No depth file is listed, read or
+    uploaded; the maps' sub-pixel peaks (`heatmap_peaks`, joints whose peak is below `min_peak` unusable) are given depths by the bone
+    solve (`bone_depths` with `bone_depth.options(bones, neck_depth=neck_depth)`), lifted and filled as detections are (`lift_peaks`),
+    and the Recording carries the solve's `depth_report`.  Its heat-maps are the files' own.  peaks="subpixel" with a depth directory:
+    the network's depths, lifted at the sub-pixel peak instead of the reference's 16-pixel argmax."""
+    from_bones, subpixel, bone_opts, min_peak = depth_route(depth_dir, depth, bones, neck_depth, min_peak, peaks)
     stage = RecordingStage(gt_path, scale, bridge, spans, fps, lag, tau, min_pairs)
     import torch
     from .camera import DEFAULT_CALIBRATION
@@ -666,12 +742,14 @@ def prepare_spans(slam_result_path, heatmap_dir, depth_dir, gt_path, spans, fps,
     stage.read_trajectory(slam_result_path)
     pose_gt = stage.read_gt()
     heat_names = sorted(os.listdir(heatmap_dir), key=natural_key)
-    depth_names = sorted(os.listdir(depth_dir), key=natural_key)
+    depth_names = sorted(os.listdir(depth_dir), key=natural_key) if not from_bones else None
     heat_paths, depth_paths, stage.gts, stage.bounds = [], [], [], []
     stage.check_trajectory()
     for a, b in spans:
-        hp, dp = heat_names[a:b], depth_names[a:b]
-        if len(hp) != b - a or len(dp) != b - a:
+        hp, dp = heat_names[a:b], depth_names[a:b] if not from_bones else []
+        if from_bones and len(hp) != b - a:
+            raise ValueError("frames [%d, %d) of the listing are asked for, but %s holds %d files" % (a, b, heatmap_dir, len(heat_names)))
+        if not from_bones and (len(hp) != b - a or len(dp) != b - a):
             raise ValueError("frames [%d, %d) of the listings are asked for, but %s holds %d files and %s holds %d" %
                              (a, b, heatmap_dir, len(heat_names), depth_dir, len(depth_names)))
         stage.bounds.append((len(heat_paths), len(heat_paths) + b - a))
@@ -682,25 +760,33 @@ def prepare_spans(slam_result_path, heatmap_dir, depth_dir, gt_path, spans, fps,
         return stage.empty()
     lap("listings, ground truth, trajectory")
     with torch.cuda.device(device):
-        heat, depth, heat_files = frames_to_device(heat_paths, depth_paths, device, timings=timings)
+        heat, depth_d, heat_files = frames_to_device(heat_paths, None if from_bones else depth_paths, device, timings=timings)
         lap = Laps(timings)          # (frames_to_device has timed its own phases)
         engine = _lift_engine(camera_model_path or DEFAULT_CALIBRATION, device.index)
         if tuple(heat.shape[1:3]) != tuple(engine.heat_size):
             raise ValueError("heat-maps of %d x %d: the lifting kernel is built for %d x %d" % (tuple(heat.shape[1:3]) + tuple(engine.heat_size)))
-        est_local, _ = engine.lift_skeleton(heat, depth)
+        depth_report = None
+        if subpixel:
+            est_local, depth_report = lift_peaks(engine, heat, depth_d, stage.bounds, stage.spans, bone_opts, min_peak)
+        else:
+            est_local, _ = engine.lift_skeleton(heat, depth_d)
         stage.fix_scale(engine, est_local, lap)
-        return stage.recording(est_local, heat, heat_files, lap)
+        rec = stage.recording(est_local, heat, heat_files, lap)
+        rec.depth_report = depth_report
+        return rec
 
 
 def main(slam_result_path, heatmap_dir, depth_dir, gt_path, start_frame, end_frame, out_dir, fps, mat_start_frame=None,
-         camera_model_path=None, scale=None, lag=None, tau=0.10, min_pairs=50, bridge=None):
+         camera_model_path=None, scale=None, lag=None, tau=0.10, min_pairs=50, bridge=None, depth=None, bones=None, neck_depth=None,
+         min_peak=None, peaks=None):
     """The reference's `main` (:126-165): one chunk [start_frame, end_frame) -> `<out_dir>/test_data.pkl`, and the line
     `The initial mpjpe is: ...`.  Returns the one-chunk Recording (the reference returns nothing).  Without ground truth (`gt_path`
     None, `scale` given) the pickle has four keys and there is no such line; with scale="auto" one line tells the estimate and its
-    counts, and a recording that does not fix the scale is a ValueError before anything is written."""
+    counts, and a recording that does not fix the scale is a ValueError before anything is written.  `depth`, `bones`, `neck_depth`,
+    `min_peak`, `peaks`: `prepare_spans`' (depth="bones" with depth_dir None: a recording without depth files)."""
     rec = prepare_spans(slam_result_path, heatmap_dir, depth_dir, gt_path, [(start_frame, end_frame)], fps,
                         start_frame if mat_start_frame is None else mat_start_frame, camera_model_path, scale=scale, lag=lag, tau=tau,
-                        min_pairs=min_pairs, bridge=bridge)
+                        min_pairs=min_pairs, bridge=bridge, depth=depth, bones=bones, neck_depth=neck_depth, min_peak=min_peak, peaks=peaks)
     print_report(rec, sequence=False)
     rec.write_chunk(0, out_dir)
     return rec
@@ -708,18 +794,20 @@ def main(slam_result_path, heatmap_dir, depth_dir, gt_path, start_frame, end_fra
 
 def prepare_sequence(slam_result_path, heatmap_dir, depth_dir, gt_path, total_start_frame, total_end_frame, fps=25, mat_start_frame=None,
                      test_size=100, out_root=None, camera_model_path=None, verbose=True, scale=None, lag=None, tau=0.10, min_pairs=50,
-                     bridge=None):
+                     bridge=None, depth=None, bones=None, neck_depth=None, min_peak=None, peaks=None):
     """The reference's chunk loop (:176-190): chunks of `test_size` frames from `total_start_frame` (see `chunk_spans` for the
     chunk it drops), `mat_start_frame` defaulting to `total_start_frame` as there.  All chunks go through the device together,
     each prepared on its own.  Returns the Recording; with `out_root`, `data_start_{a}_end_{b}/test_data.pkl` are written too.
     Exactly one of `gt_path` and `scale` is given (else ValueError, before anything else happens): with `scale` the recording has no
     ground truth (`prepare_spans`); scale="auto" estimates it from the foot contacts (`lag`, `tau`, `min_pairs`: `slam_scale`).  `bridge`:
-    seconds of lost SLAM tracking to bridge (`slam_bridge`), without ground truth only."""
+    seconds of lost SLAM tracking to bridge (`slam_bridge`), without ground truth only.  `depth`, `bones`, `neck_depth`, `min_peak`,
+    `peaks`: `prepare_spans`' (depth="bones" with depth_dir None: a recording without depth files)."""
     gt_or_scale(gt_path, scale)
+    depth_route(depth_dir, depth, bones, neck_depth, min_peak, peaks)
     spans = chunk_spans(total_start_frame, total_end_frame, test_size)
     rec = prepare_spans(slam_result_path, heatmap_dir, depth_dir, gt_path, spans, fps,
                         total_start_frame if mat_start_frame is None else mat_start_frame, camera_model_path, scale=scale, lag=lag, tau=tau,
-                        min_pairs=min_pairs, bridge=bridge)
+                        min_pairs=min_pairs, bridge=bridge, depth=depth, bones=bones, neck_depth=neck_depth, min_peak=min_peak, peaks=peaks)
     if verbose:
         print_report(rec)
     if out_root is not None:
@@ -759,19 +847,50 @@ def parse_recording_options(p, argv=None):
     return a
 
 
+def add_depth_route_options(p):
+    """Where a heat-map recording's depths come from (`prepare`, `slam_scale`): --depths DIR, or --depth_from bones with --bones,
+    --neck_depth and --min_peak; --peaks for the lift with depth files."""
+    from .bone_depth import add_bone_depth_options
+    p.add_argument("--depths", default=None, metavar="DIR", help="directory of per-frame depth .mat files")
+    p.add_argument("--depth_from", default=None, choices=("bones",), help="bones: a pose network without a depth head -- the depths are "
+                                                                         "solved from the bone lengths at the maps' sub-pixel peaks "
+                                                                         "(DESIGN.md section 6r); excludes --depths")
+    add_bone_depth_options(p)
+    p.add_argument("--min_peak", type=float, default=None, metavar="P", help="with --depth_from bones: a joint whose map peaks below P is "
+                                                                             "treated as not detected (default 0)")
+    p.add_argument("--peaks", default=None, choices=("argmax", "subpixel"), help="with --depths: lift at the reference's 16-pixel argmax "
+                                                                                 "(default) or at the sub-pixel peak")
+
+
+def check_depth_route_options(p, a):
+    """The rules of `add_depth_route_options`, as parser errors."""
+    if (a.depths is None) == (a.depth_from is None):
+        p.error("give exactly one of --depths DIR and --depth_from bones")
+    if a.depth_from is None and (a.bones is not None or a.neck_depth is not None or a.min_peak is not None):
+        p.error("--bones, --neck_depth and --min_peak belong to --depth_from bones")
+    if a.depth_from is not None and a.peaks == "argmax":
+        p.error("--depth_from bones uses the sub-pixel peaks: --peaks argmax goes with --depths")
+    if a.min_peak is not None and not (np.isfinite(a.min_peak) and a.min_peak >= 0):
+        p.error("--min_peak must be a finite number >= 0")
+
+
 def _parser():
     import argparse
     p = argparse.ArgumentParser(description="recording (.mat files of the pose network) -> chunks for the optimiser")
     p.add_argument("--heatmaps", required=True, help="directory of per-frame heatmap .mat files")
-    p.add_argument("--depths", required=True, help="directory of per-frame depth .mat files")
+    add_depth_route_options(p)
     add_recording_options(p)
     return p
 
 
 def _cli(argv=None):
-    a = parse_recording_options(_parser(), argv)
+    from .bone_depth import bones_from_args
+    p = _parser()
+    a = parse_recording_options(p, argv)
+    check_depth_route_options(p, a)
     rec = prepare_sequence(a.slam, a.heatmaps, a.depths, a.gt, a.start, a.end, a.fps, a.mat_start, a.test_size, a.out, a.camera,
-                           scale=a.scale, bridge=a.bridge)
+                           scale=a.scale, bridge=a.bridge, depth=a.depth_from, bones=bones_from_args(a), neck_depth=a.neck_depth,
+                           min_peak=a.min_peak, peaks=a.peaks)
     if a.optimize:
         from .whole_sequence import optimize_recording
         optimize_recording(rec, a.camera, ground_truth=a.scale is None)

@@ -7,7 +7,7 @@ stands does not move in the world -- so R_t x_t,foot + s c_t is constant over a 
 robust one-parameter fit on the device, over the lifted poses where they lie; one small record comes back.
 
     python -m globalegomocap_amd.slam_scale --slam traj.txt (--heatmaps DIR --depths DIR | --keypoints det.npz [--depths DIR | --depth FILE.npy]) \\
-        --start A --end B --fps 25 [--lag K] [--tau M] [--min_pairs P] [--test_size 100] [--json FILE] [--gt gt.pkl]
+        [--depth_from bones [--bones FILE.npy] [--neck_depth M] [--min_peak P] in place of the depths] --start A --end B --fps 25 [--lag K] [--tau M] [--min_pairs P] [--test_size 100] [--json FILE] [--gt gt.pkl]
 
 `prepare --scale auto` and `detections --scale auto` (`scale="auto"`) call `estimate_scale` on the lifted poses and go on as if the
 number had been given.  "The wearer did not walk enough to fix the scale" is an answer: a ValueError naming the counts.
@@ -222,6 +222,12 @@ def _parser():
     p.add_argument("--keypoints", default=None, metavar="FILE", help=".npy / .npz of 2-D detections (`detections`)")
     p.add_argument("--depths", default=None, metavar="DIR", help="directory of per-frame depth .mat files")
     p.add_argument("--depth", default=None, metavar="FILE.npy", help="the joints' depths [N,15], row for row with the detections")
+    p.add_argument("--depth_from", default=None, choices=("bones",), help="bones: no depths at all -- they are solved from the bone lengths "
+                                                                         "(DESIGN.md sections 6q, 6r); excludes --depths and --depth")
+    from .bone_depth import add_bone_depth_options
+    add_bone_depth_options(p)
+    p.add_argument("--min_peak", type=float, default=None, metavar="P", help="with --heatmaps --depth_from bones: a joint whose map peaks "
+                                                                             "below P is treated as not detected (default 0)")
     p.add_argument("--start", required=True, type=int)
     p.add_argument("--end", required=True, type=int)
     p.add_argument("--fps", type=float, default=25)
@@ -244,12 +250,21 @@ def _cli(argv=None):
     a = p.parse_args(argv)
     if (a.heatmaps is None) == (a.keypoints is None):
         p.error("give --heatmaps DIR --depths DIR, or --keypoints FILE")
-    if a.heatmaps is not None and (a.depths is None or a.depth is not None):
-        p.error("--heatmaps needs --depths DIR")
+    if a.depth_from is not None and (a.depths is not None or a.depth is not None):
+        p.error("--depth_from bones excludes --depths and --depth")
+    if a.heatmaps is not None and ((a.depths is None and a.depth_from is None) or a.depth is not None):
+        p.error("--heatmaps needs --depths DIR or --depth_from bones")
+    if a.depth_from is None and (a.bones is not None or a.neck_depth is not None or a.min_peak is not None):
+        p.error("--bones, --neck_depth and --min_peak belong to --depth_from bones")
+    if a.min_peak is not None and a.heatmaps is None:
+        p.error("--min_peak goes with --heatmaps: detections carry their own confidence")
+    from .bone_depth import bones_from_args
     spans = full_spans(a.start, a.end, a.test_size)
     options = dict(lag=a.lag, tau=a.tau, min_pairs=a.min_pairs)
+    if a.depth_from is not None:
+        options.update(depth=a.depth_from, bones=bones_from_args(a), neck_depth=a.neck_depth)
     if a.heatmaps is not None:
-        rec = prepare.prepare_spans(a.slam, a.heatmaps, a.depths, None, spans, a.fps, a.start, a.camera, scale="auto", **options)
+        rec = prepare.prepare_spans(a.slam, a.heatmaps, a.depths, None, spans, a.fps, a.start, a.camera, scale="auto", min_peak=a.min_peak, **options)
     else:
         rec = detections.recording_from_detections(a.slam, detections.detections_from_args(a), None, "auto", spans, a.fps,
                                                    camera_model_path=a.camera, **options)

@@ -389,7 +389,8 @@ int gem_mat_read(const char* const* paths, int64_t n, const int64_t* at, const i
  * `torch.from_numpy(loadmat(f)['heatmap']).float()`, and d_depth [n,n_joints] f64 = `loadmat(f)['depth'][0]`.  d_heat_offsets /
  * d_depth_offsets [n]: byte position of every frame's payloads in the image (any alignment; bytes outside the image read as zero);
  * d_kinds [n]: GEM_MAT_HEAT_F64 when the frame's heat-map is stored as double (rounded to nearest even), GEM_MAT_DEPTH_F32 when its
- * depths are stored as single (widened exactly).  Alignment requirements as gem_heat_gather. */
+ * depths are stored as single (widened exactly).  d_depth_offsets and d_depth both NULL: a recording without depth files, the
+ * heat-maps alone.  Alignment requirements as gem_heat_gather. */
 int gem_mat_frames(const void* d_image, int64_t image_len, const int64_t* d_heat_offsets, const int64_t* d_depth_offsets,
                    const int32_t* d_kinds, int64_t n, int heat_h, int heat_w, int n_joints, float* d_heat, double* d_depth, void* stream);
 
@@ -837,6 +838,23 @@ typedef struct gem_bone_depth_opts {
 } gem_bone_depth_opts;
 int gem_bone_depths(gem_handle* h, const double* d_kp, int64_t n_frames, const double* h_poly_c2w, int n_poly, const gem_bone_depth_opts* opts,
                     double* d_depth, unsigned char* d_solved, double* d_rms, void* stream);
+
+/* ---- Heat-maps without a depth network: the maps' peaks as sub-pixel detections ----
+ * d_heat [n_frames,H,W,J] f32 with the handle's heat_h, heat_w and J (float alignment is enough: 16-byte non-temporal loads when the
+ * tensor starts on a 16-byte boundary and a frame is a whole number of 16-byte words, a scalar scan otherwise) -> d_kp [n_frames,J,3]
+ * f64, detections (u, v, confidence) in the convention above, and d_arg [n_frames,J] int32, the flat row-major index sy W + sx of the
+ * map's integer maximum under numpy's argmax rule (NaN is maximal, the first occurrence wins).  Either output may be NULL, not both.
+ * From m = (sx, sy), eight iterations of m <- sum w k x / sum w k over the texels within 4 of (sx, sy) that lie inside the map, with
+ * w = max(value, 0) (a NaN texel weighs nothing) and k = exp(-(x - m_x)^2 / 2 tau^2) exp(-(y - m_y)^2 / 2 tau^2), tau = 1.5: a
+ * Gaussian-windowed mean shift, whose fixed point is the centre of a Gaussian blob whatever the blob's own width.  Then
+ * u = pad_x + m_x upscale W / (W - 1), v = pad_y + m_y upscale H / (H - 1) -- with upscale 16 and pads 128, 0 on a 64 x 64 map the
+ * inverse of the map at which the reprojection term samples and gem_keypoint_heatmaps splats -- and confidence = min(peak, 1), the
+ * float32 maximum widened.  A joint whose maximum is NaN, not positive or below min_peak is UNUSABLE and written as (0, 0, 0).
+ * n_frames >= 0, upscale >= 1, pads >= 0, min_peak finite and >= 0, at most 16 joints, maps of at least 2 x 2: anything else is
+ * refused before any launch.  One workgroup per frame; float64 without fused multiply-adds, every sum in a fixed order, no atomics:
+ * two calls give the same bytes, and a frame's bytes do not depend on the other frames of its call.  Asynchronous on `stream`. */
+int gem_heatmap_peaks(gem_handle* h, const float* d_heat, int64_t n_frames, int upscale, int pad_x, int pad_y, double min_peak,
+                      double* d_kp, int32_t* d_arg, void* stream);
 
 /* ---- The SLAM scale of a recording without ground truth, from foot contacts: `--scale auto` ----
  * A monocular SLAM gives the camera's rotation R_t and its translation c_t up to one factor s; the lifted poses x_t are metric.  A
