@@ -136,6 +136,11 @@ class GemLbfgsDebugState(C.Structure):
                [(k, C.c_double) for k in ("t", "loss", "gtd", "d_norm", "H_diag")]
 
 
+class GemGemmDebugArgs(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("route", "epi", "M", "T", "a_rows", "family", "out_bf16", "allow_split", "defer", "reserved")] + \
+               [(k, C.c_void_p) for k in ("d_A", "d_aux", "d_C", "d_rows", "d_row_map")]
+
+
 # name -> (restype, argtypes); every symbol include/gem_hip.h declares
 _P = C.c_void_p
 SIGNATURES = {
@@ -160,6 +165,9 @@ SIGNATURES = {
     "gem_lbfgs_debug_begin": (C.c_int, [_P, C.c_int, _P, C.c_int, _P]),
     "gem_lbfgs_debug_advance": (C.c_int, [_P, C.c_int, C.POINTER(GemLbfgsOpts), _P, _P, C.c_int, _P]),
     "gem_lbfgs_debug_read": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, _P]),
+    "gem_gemm_debug_layer_create": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, C.POINTER(_P)]),
+    "gem_gemm_debug_layer_destroy": (C.c_int, [_P, _P]),
+    "gem_gemm_debug_run": (C.c_int, [_P, _P, C.POINTER(GemGemmDebugArgs), C.c_char_p, C.c_int, C.POINTER(C.c_int32), _P]),
     "gem_merge_windows": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
     "gem_calculate_errors": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.POINTER(C.c_double), _P, _P]),
     "gem_calculate_errors_chunks": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.POINTER(C.c_double), _P, _P]),

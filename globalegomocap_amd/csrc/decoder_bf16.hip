@@ -128,8 +128,8 @@ static int launch_big(gem_handle* h, const Layer& L, int epi, const uint16_t* A,
 // C = epi(conv/linear(A)) with bf16 operands.  `out_bf16`: activation / gradient for the next bf16 layer; otherwise fp32.
 // allow_split: small row counts cut K over several workgroups (fp32 slabs in ws.splitk); with o.defer the slabs are left to
 // the consumer (described in *o.defer), otherwise a reduce pass applies the epilogue.
-static int gemm_bf16a(gem_handle* h, const Layer& L, int epi, const uint16_t* A, int lda, const uint16_t* aux, void* C, bool out_bf16,
-                      int ldc, int M, hipStream_t s, int family, bool allow_split, const GemmOpts& o = GemmOpts()) {
+int gemm_bf16a(gem_handle* h, const Layer& L, int epi, const uint16_t* A, int lda, const uint16_t* aux, void* C, bool out_bf16,
+               int ldc, int M, hipStream_t s, int family, bool allow_split, const GemmOpts& o) {
     Workspace& w = h->ws;
     if (o.defer) *o.defer = SlabSrc{};
     if (M <= 0) return 0;

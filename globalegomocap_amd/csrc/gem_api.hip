@@ -27,7 +27,7 @@ const char* dev_env(const char* name) {
 }
 
 void note_kernel(gem_handle* h, const void* host_fn) {
-    if (!h->prof.on) return;
+    if (!h->prof.on && !h->prof.capture) return;
     const char* m = hipKernelNameRefByPtr(host_fn, nullptr);
     if (!m) return;
     int st = 0;
@@ -182,6 +182,7 @@ void gem_destroy(gem_handle* h) {
         }
     }
     drop_graphs(h);
+    for (gem_gemm_debug_layer* l : h->dbg_layers) { free_all(l->allocs); delete l; }
     free_all(h->net[0].allocs);
     free_all(h->net[1].allocs);
     free_all(h->ws.allocs);

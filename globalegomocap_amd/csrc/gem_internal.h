@@ -236,6 +236,7 @@ struct Profile {
     // bench.py labels its roofline objects with what actually ran, not with what it expects to run
     std::set<std::string> names[4];
     std::set<std::string> pending;       // kernels launched since the current timed launcher began
+    std::set<std::string>* capture = nullptr;      // gem_gemm_debug_run: every launcher's names go here as well, profiling on or off
 };
 
 // Wavefront reductions on the DPP cross-lane path (no LDS traffic): quad swaps, half-row and row mirrors
@@ -309,6 +310,13 @@ struct gem_handle {
     int64_t graph_replays = 0, graph_captures = 0;
     int* d_parents = nullptr;
     int* d_children = nullptr;     // [J][J] child lists, -1 terminated
+    std::vector<gem_gemm_debug_layer*> dbg_layers;      // gem_gemm_debug_layer_create: freed one by one or with the handle
+};
+
+// One stand-alone layer of the GEMM debug entry (include/gem_hip.h): the images gem_load_vae's own code makes of host weights.
+struct gem_gemm_debug_layer {
+    gem::Layer L;
+    std::vector<void*> allocs;
 };
 
 namespace gem {
@@ -317,6 +325,7 @@ namespace gem {
 void note_kernel(gem_handle* h, const void* host_fn);
 inline void commit_kernel_names(gem_handle* h, int family) {
     if (family >= 0 && family < 4) h->prof.names[family].insert(h->prof.pending.begin(), h->prof.pending.end());
+    if (h->prof.capture) h->prof.capture->insert(h->prof.pending.begin(), h->prof.pending.end());
     h->prof.pending.clear();
 }
 
@@ -385,6 +394,11 @@ struct EnergyArgs;
 // One evaluation in the bf16 decoder mode (decoder_bf16.hip); returns the gradient's slabs in *grad like evaluate() (stage.hip)
 int evaluate_bf16(gem_handle* h, const Route& rt, int stage, int B, const EnergyArgs& ea, hipStream_t s, bool forward_only, const RoundSet* rs,
                   SlabSrc* grad);
+// C = epi(conv/linear(A)) with bf16 activations (decoder_bf16.hip): the dispatch function of the bf16 decoder mode
+int gemm_bf16a(gem_handle* h, const Layer& L, int epi, const uint16_t* A, int lda, const uint16_t* aux, void* C, bool out_bf16,
+               int ldc, int M, hipStream_t s, int family, bool allow_split, const GemmOpts& o = GemmOpts());
+// fp32 / bf16 hi / bf16 lo images of one packed layer [taps][N][K] + bias [N], as the loader makes them (weights.hip)
+int make_layer_images(std::vector<void*>& owner, Layer* L, int taps, int N, int K, const float* w, const float* bias);
 int launch_f32_to_bf16(const float* src, uint16_t* dst, size_t n, hipStream_t s);
 int launch_f32_split_bf16(const float* src, uint16_t* hi, uint16_t* lo, size_t n, hipStream_t s);
 

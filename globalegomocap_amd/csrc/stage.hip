@@ -3,7 +3,10 @@
 // window loop, hipGraph replay of whole calls, and the L-BFGS solver stepped alone for the parity tests.  Host code only: all
 // arithmetic runs in the kernels of gemm_f32.hip, gemm_bf16.hip, decoder_bf16.hip, tail.hip, tail_bf16.hip, energy.hip, lbfgs.hip.
 // No call leaves anything behind in the workspace for the next one except its buffers' contents and the n_log cursor.
+#include <algorithm>
+#include <cstdio>
 #include <cstring>
+#include <memory>
 
 #include "gem_internal.h"
 
@@ -616,6 +619,107 @@ int gem_lbfgs_debug_read(gem_handle* h, int B, gem_lbfgs_debug_state* d_state, f
     const RoundSet rs = round_set(w, w.dbg_log0, w.dbg_round, w.dbg_slots == 2 ? REPACK_ATOMIC : REPACK_KERNEL);
     if (d_slot_of) GEM_HIP(hipMemcpyAsync(d_slot_of, rs.slot_of, (size_t)B * sizeof(int), hipMemcpyDeviceToDevice, s));
     if (d_count) GEM_HIP(hipMemcpyAsync(d_count, rs.n_active, sizeof(int), hipMemcpyDeviceToDevice, s));
+    return 0;
+}
+
+// ---- for parity tests: one layer through launch_gemm / gemm_bf16a (include/gem_hip.h) ------------------------------------------
+int gem_gemm_debug_layer_create(gem_handle* h, int taps, int N, int K, const float* h_w, const float* h_bias,
+                                gem_gemm_debug_layer** out) {
+    if (!h || !h_w || !h_bias || !out) { set_error("gem_gemm_debug_layer_create: null argument"); return 1; }
+    if ((taps != 1 && taps != 3) || N < 64 || K < 32 || N % 64 != 0 || K % 32 != 0 || (size_t)taps * N * K > ((size_t)1 << 28)) {
+        set_error("gem_gemm_debug_layer_create: need taps 1 or 3, N % 64 == 0, K % 32 == 0, taps * N * K <= 2^28"); return 1;
+    }
+    GEM_HIP(hipSetDevice(h->cfg.device));
+    std::unique_ptr<gem_gemm_debug_layer> l(new gem_gemm_debug_layer());
+    if (make_layer_images(l->allocs, &l->L, taps, N, K, h_w, h_bias)) { free_all(l->allocs); return 1; }
+    h->dbg_layers.push_back(l.get());
+    *out = l.release();
+    return 0;
+}
+
+int gem_gemm_debug_layer_destroy(gem_handle* h, gem_gemm_debug_layer* layer) {
+    if (!h) { set_error("gem_gemm_debug_layer_destroy: null handle"); return 1; }
+    auto it = std::find(h->dbg_layers.begin(), h->dbg_layers.end(), layer);
+    if (!layer || it == h->dbg_layers.end()) { set_error("gem_gemm_debug_layer_destroy: not a layer of this handle"); return 1; }
+    GEM_HIP(hipSetDevice(h->cfg.device));
+    GEM_HIP(hipDeviceSynchronize());
+    h->dbg_layers.erase(it);
+    free_all(layer->allocs);
+    delete layer;
+    return 0;
+}
+
+int gem_gemm_debug_run(gem_handle* h, const gem_gemm_debug_layer* layer, const gem_gemm_debug_args* a, char* names, int names_len,
+                       int32_t* info, void* stream) {
+    const char* me = "gem_gemm_debug_run: ";
+    auto bad = [&](const char* what) { set_error(std::string(me) + what); return 1; };
+    if (!h || !layer || !a) return bad("null argument");
+    if (std::find(h->dbg_layers.begin(), h->dbg_layers.end(), layer) == h->dbg_layers.end()) return bad("not a layer of this handle");
+    if ((names && names_len < 1) || (!names && names_len != 0)) return bad("names buffer without a length (or the reverse)");
+    const Layer& L = layer->L;
+    Workspace& w = h->ws;
+    const bool b16a = a->route == 1;
+    if (a->route != 0 && a->route != 1) return bad("route must be 0 (launch_gemm) or 1 (gemm_bf16a)");
+    if (a->epi < 0 || a->epi > 3) return bad("epi must be 0 .. 3");
+    if (a->epi == EPI_MASK && (L.taps != 3 || !a->d_aux)) return bad("the mask epilogue belongs to conv layers and needs d_aux");
+    if (a->family < -1 || a->family > 3) return bad("family must be -1 .. 3");
+    if (!a->d_A || !a->d_C) return bad("null d_A or d_C");
+    if (a->M < 1 || (long)a->M > (long)w.Bmax * h->T) return bad("M must be 1 .. max_windows * seq_len");
+    if (a->T < 1 || (L.taps == 3 && a->M % a->T != 0)) return bad("need T >= 1, and M % T == 0 for conv layers");
+    if (L.taps == 3 && b16a && a->T != h->T) return bad("gemm_bf16a reads the handle's seq_len: T must equal it");
+    if (b16a && L.K % 64 != 0) return bad("the bf16 kernels need K % 64 == 0");
+    if (!b16a && h->precision != GEM_PRECISION_F32 && L.K % 64 != 0) return bad("the bf16 kernels need K % 64 == 0");
+    if (a->d_row_map && L.taps != 1) return bad("a row map gathers the rows of linear layers only");
+    if (a->a_rows < 1 || (!a->d_row_map && a->a_rows < a->M)) return bad("a_rows must cover M (or the row map's targets)");
+    if (!b16a && (a->out_bf16 || a->allow_split)) return bad("out_bf16 and allow_split belong to gemm_bf16a");
+    if (b16a && a->defer && !a->allow_split) return bad("gemm_bf16a leaves slabs only where it may split");
+    if ((a->defer || a->allow_split) && (!w.splitk || (size_t)a->M * L.N > w.splitk_elems)) return bad("one slab of M x N does not fit the split-K scratch");
+    GEM_HIP(hipSetDevice(h->cfg.device));
+    hipStream_t s = (hipStream_t)stream;
+    GEM_HIP(hipStreamSynchronize(s));
+    if (a->d_row_map) {
+        std::vector<int> map((size_t)a->M);
+        GEM_HIP(hipMemcpy(map.data(), a->d_row_map, map.size() * sizeof(int), hipMemcpyDeviceToHost));
+        for (int r : map) if (r < 0 || r >= a->a_rows) return bad("row map entry outside d_A");
+    }
+    const int T = L.taps == 3 ? a->T : 1;
+    if (a->d_rows) {
+        int m[2];
+        GEM_HIP(hipMemcpy(m, a->d_rows, sizeof(m), hipMemcpyDeviceToHost));
+        if (m[0] < 1 || (long)m[0] * T > a->M || m[1] != m[0] * a->T) return bad("d_rows must hold {m, m * T} with 1 <= m and m (* T for convs) <= M");
+    }
+    RoundSet rs;
+    rs.n_active = const_cast<int*>(a->d_rows);
+    SlabSrc slab;
+    const GemmOpts o(a->d_rows ? &rs : nullptr, a->d_row_map, a->defer ? &slab : nullptr);
+    std::set<std::string> seen;
+    std::vector<void*> tmp;
+    h->prof.capture = &seen;
+    int rc;
+    if (b16a) {
+        uint16_t *A16 = nullptr, *aux16 = nullptr;
+        const size_t na = (size_t)a->a_rows * L.K, nx = (size_t)a->M * L.N;
+        rc = dev_alloc(tmp, &A16, na) || launch_f32_to_bf16(a->d_A, A16, na, s);
+        if (!rc && a->d_aux) rc = dev_alloc(tmp, &aux16, nx) || launch_f32_to_bf16(a->d_aux, aux16, nx, s);
+        if (!rc) rc = gemm_bf16a(h, L, a->epi, A16, L.K, aux16, a->d_C, a->out_bf16 != 0, L.N, a->M, s, a->family, a->allow_split != 0, o);
+    } else {
+        rc = launch_gemm(h, L, a->epi, a->d_A, L.K, a->d_aux, static_cast<float*>(a->d_C), L.N, a->M, T, s, a->family, o);
+    }
+    h->prof.capture = nullptr;
+    h->prof.pending.clear();
+    const bool deferred = !rc && slab.base != nullptr;
+    if (deferred)          // the consumer's part: sum the slabs, apply the epilogue
+        rc = launch_splitk_reduce(h, a->epi, slab.nslab, slab.stride, L.bias, a->d_aux, static_cast<float*>(a->d_C), a->M, L.N, L.N,
+                                  slab.m_dev, s, slab.dyn_W, slab.n_tiles);
+    const bool synced = hip_ok(hipStreamSynchronize(s), "hipStreamSynchronize");
+    free_all(tmp);
+    if (rc || !synced) return 1;
+    if (names) {
+        std::string out;
+        for (const auto& n : seen) { if (!out.empty()) out += "; "; out += n; }
+        snprintf(names, (size_t)names_len, "%s", out.c_str());
+    }
+    if (info) { info[0] = deferred ? slab.nslab : 0; info[1] = deferred ? slab.dyn_W : 0; info[2] = (b16a && a->out_bf16 && !deferred) ? 1 : 0; info[3] = 0; }
     return 0;
 }
 

@@ -29,6 +29,12 @@ static int upload_bf16(std::vector<void*>& owner, Layer* L, const std::vector<fl
     return upload(owner, &L->wb_hi, hi) || upload(owner, &L->wb_lo, lo);
 }
 
+int make_layer_images(std::vector<void*>& owner, Layer* L, int taps, int N, int K, const float* w, const float* bias) {
+    const std::vector<float> wv(w, w + (size_t)taps * N * K), bv(bias, bias + N);
+    L->taps = taps; L->N = N; L->K = K;
+    return upload(owner, &L->w, wv) || upload(owner, &L->bias, bv) || upload_bf16(owner, L, wv);
+}
+
 // taps[k][ci][co] in double, BatchNorm folded
 struct FoldedConv {
     int ci, co;

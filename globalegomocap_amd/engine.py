@@ -341,6 +341,37 @@ class WindowEngine:
         out.update(x=x, d=d, trial=trial, slot_of=slot_of.cpu().numpy(), count=int(count.item()))
         return out
 
+    # ------------------------------------------------------------------ one layer through a GEMM dispatch function (parity tests)
+    def gemm_debug_layer(self, w, bias):
+        """A stand-alone layer from host weights w [taps,N,K] and bias [N], padded (gem_gemm_debug_layer_create): the handle to
+        give `gemm_debug_run`.  Freed by `gemm_debug_layer_free` or with the engine."""
+        w = np.ascontiguousarray(w, dtype=np.float32)
+        bias = np.ascontiguousarray(bias, dtype=np.float32)
+        if w.ndim != 3 or bias.shape != (w.shape[1],):
+            raise ValueError("gemm_debug_layer: w must be [taps,N,K] and bias [N]")
+        out = C.c_void_p()
+        _capi.check(self.lib.gem_gemm_debug_layer_create(self._h, w.shape[0], w.shape[1], w.shape[2], w.ctypes.data_as(C.c_void_p),
+                                                         bias.ctypes.data_as(C.c_void_p), C.byref(out)), self.lib)
+        return out
+
+    def gemm_debug_layer_free(self, layer):
+        _capi.check(self.lib.gem_gemm_debug_layer_destroy(self._h, layer), self.lib)
+
+    def gemm_debug_run(self, layer, A, C_out, M, epi, route=0, T=1, aux=None, rows=None, row_map=None, defer=False, out_bf16=False,
+                       allow_split=False, family=-1):
+        """One layer through launch_gemm (route 0) or gemm_bf16a (route 1) (gem_gemm_debug_run): A [a_rows,K] f32, C_out [>=M,N]
+        f32 (or bf16 storage), aux [M,N] f32, rows int32 {m, m*T}, row_map int32 [M], all device tensors.  Returns (kernel
+        names, info) with info = (slabs left to the consumer, workgroups of a device-side cut, 1 if C_out holds bf16)."""
+        a = _capi.GemGemmDebugArgs(route=int(route), epi=int(epi), M=int(M), T=int(T), a_rows=int(A.shape[0]), family=int(family),
+                                   out_bf16=int(bool(out_bf16)), allow_split=int(bool(allow_split)), defer=int(bool(defer)), reserved=0,
+                                   d_A=A.data_ptr(), d_aux=aux.data_ptr() if aux is not None else None, d_C=C_out.data_ptr(),
+                                   d_rows=rows.data_ptr() if rows is not None else None,
+                                   d_row_map=row_map.data_ptr() if row_map is not None else None)
+        names = C.create_string_buffer(2048)
+        info = (C.c_int32 * 4)()
+        _capi.check(self.lib.gem_gemm_debug_run(self._h, layer, C.byref(a), names, len(names), info, _stream()), self.lib)
+        return [n for n in names.value.decode().split("; ") if n], tuple(info)[:3]
+
     # ------------------------------------------------------------------ sequence post-processing (SURVEY 8f.1)
     def _f64(self, a):
         t = torch.as_tensor(np.asarray(a) if not torch.is_tensor(a) else a)

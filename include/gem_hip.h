@@ -186,6 +186,46 @@ int gem_lbfgs_debug_advance(gem_handle* h, int B, const gem_lbfgs_opts* opt, con
 int gem_lbfgs_debug_read(gem_handle* h, int B, gem_lbfgs_debug_state* d_state, float* d_x, float* d_d, float* d_trial,
                          int32_t* d_slot_of, int32_t* d_count, void* stream);
 
+/* ---- For parity tests: ONE layer through one of the two GEMM dispatch functions -------------------------------------------
+ *   C[M,N] = epi( sum_tap shift_tap(A)[M,K] . W[tap][N][K]^T + bias ),  row = window * T + frame, lda = K, ldc = N
+ * launch_gemm (csrc/gemm_f32.hip, forwards to launch_gemm_bf16 in the bf16x3 / bf16 precision modes) or gemm_bf16a
+ * (csrc/decoder_bf16.hip).  The entry adds no kernel and changes no dispatch rule: which kernel runs is decided by the
+ * dispatch function from the shape, the epilogue, the handle's precision mode and compute-unit count and the options below,
+ * as in a stage.  A test hook, not part of the reference's surface; it needs no VAE weights.
+ *
+ * gem_gemm_debug_layer_create: taps 1 | 3, N % 64 == 0, K % 32 == 0 (already padded), h_w [taps][N][K] and h_bias [N] host
+ * fp32.  The fp32 image and the bf16 hi / lo images are made and uploaded by the code gem_load_vae uses.  The layer lives until
+ * gem_gemm_debug_layer_destroy or gem_destroy.
+ *
+ * gem_gemm_debug_run is synchronous.  Every argument is checked before anything is launched (the row map and the device row
+ * count are read back for that); a bad argument is an error return.  When a.defer is set and the dispatch function leaves
+ * split-K slabs to its consumer, the entry plays the consumer with the library's own reduce pass (epilogue included), which
+ * writes fp32.  names gets the launched kernels' names ("; " separated, as gem_profile_kernels prints them; the reduce passes
+ * are not listed), info[0..3] = {slabs left to the consumer (0: none), workgroup count of a device-side cut (0: static cut),
+ * 1 when d_C holds bf16 / 0 for fp32, 0}. */
+typedef struct gem_gemm_debug_layer gem_gemm_debug_layer;
+typedef struct gem_gemm_debug_args {
+    int32_t route;           /* 0 launch_gemm, 1 gemm_bf16a */
+    int32_t epi;             /* 0 bias, 1 bias + LeakyReLU, 2 mask (conv layers only; needs d_aux), 3 none */
+    int32_t M, T;            /* rows; frames per window (conv layers: M % T == 0; gemm_bf16a: T == seq_len) */
+    int32_t a_rows;          /* rows of d_A (>= M unless a row map gathers them) */
+    int32_t family;          /* profiling family of the call site, -1 .. 3 (0 = the front products: picks some instantiations) */
+    int32_t out_bf16;        /* gemm_bf16a: d_C bf16 (unless slabs are left to the consumer, see above) */
+    int32_t allow_split;     /* gemm_bf16a */
+    int32_t defer;           /* "the consumer takes slabs" (gemm_bf16a: only with allow_split) */
+    int32_t reserved;
+    const float* d_A;        /* [a_rows, K] fp32; gemm_bf16a: converted to bf16 first */
+    const float* d_aux;      /* [M, N] fp32 or NULL (same conversion) */
+    void* d_C;               /* [M, N] fp32 or bf16 */
+    const int32_t* d_rows;   /* NULL or device {m, m * T}, 0 <= m <= M: the row count of an evaluation round */
+    const int32_t* d_row_map;/* NULL or device [M] rows of d_A (linear layers only) */
+} gem_gemm_debug_args;
+int gem_gemm_debug_layer_create(gem_handle* h, int taps, int N, int K, const float* h_w, const float* h_bias,
+                                gem_gemm_debug_layer** out);
+int gem_gemm_debug_layer_destroy(gem_handle* h, gem_gemm_debug_layer* layer);
+int gem_gemm_debug_run(gem_handle* h, const gem_gemm_debug_layer* layer, const gem_gemm_debug_args* a, char* names, int names_len,
+                       int32_t* info, void* stream);
+
 /* The window loop body of main() (optimizer.py:370-423) for B windows at once: local stage,
  * relative-global transform X_rel[t] = C0^-1 C_t X_loc[t] in float64 (utils/utils.py:99-112), global
  * stage, X_glob = C0 X_rel (optimizer.py:302-308).
