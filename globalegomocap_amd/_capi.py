@@ -74,6 +74,7 @@ class GemLiveBuffers(C.Structure):
 
 
 LIVE_WINDOW, LIVE_STRIDE, LIVE_RING, LIVE_PUSH_MAX, LIVE_STATE_DOUBLES = 10, 8, 32, 8, 320
+LIVE_DENSE_SLOTS, LIVE_DENSE_DOUBLES = 16, 1664          # include/gem_live_dense.h
 
 MAT_UNSUPPORTED, MAT_NOT_FOUND = 2, 3
 MAT_HEAT_F64, MAT_DEPTH_F32 = 1, 2
@@ -249,6 +250,13 @@ SIGNATURES = {
     "gem_slam_bridge": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, _P, _P, C.c_int, C.c_int64, _P, _P, _P, _P, _P, C.c_int64, _P, _P]),
 }
 
+# every symbol include/gem_live_dense.h declares (the header gem_hip.h includes for dense live mode)
+DENSE_SIGNATURES = {
+    "gem_live_window_at": (C.c_int, [_P, C.POINTER(GemLiveBuffers), C.c_int64, C.c_int64, _P, _P, _P, _P, _P, _P]),
+    "gem_live_emit_dense": (C.c_int, [_P, C.POINTER(GemLiveBuffers), _P, C.c_int, C.c_int64, C.c_int, _P, _P, _P, C.POINTER(C.c_double), _P, _P]),
+    "gem_merge_dense": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
+}
+
 _lib = None
 
 
@@ -266,7 +274,7 @@ def load_library(path=None):
     # DT_NEEDED entry of libgem_hip.so then binds to that copy by soname.
     import torch  # noqa: F401
     lib = C.CDLL(p)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(DENSE_SIGNATURES.items()):
         fn = getattr(lib, name)           # AttributeError here = header and library out of sync
         fn.restype, fn.argtypes = res, args
     if path is None:

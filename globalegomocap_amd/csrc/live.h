@@ -6,6 +6,7 @@
 //   gem_live_emit    the window's result merged with the two frames held from the window before (sequence.merge_batches' expression),
 //                    the estimated sequence cams . pose, the causal One-Euro filter, 8 final frames out, two frames held
 //   gem_one_euro     the same filter over whole sequences (chunks x coordinates in parallel, frames in order)
+//   gem_live_window_at, gem_live_emit_dense, gem_merge_dense   a window every k <= 8 frames and dense merging: the file's second half
 //
 // A frame of heat-maps is 245 KB and a window 2.4 MB: the two copy kernels move 16-byte vectors with one workgroup per (frame, row).
 // Everything else is a few hundred doubles handled by one workgroup; all state lives in the caller's block (gem_hip.h has its
@@ -233,6 +234,18 @@ inline int live_args(gem_handle* h, const gem_live_buffers* b, const char* who, 
     return 0;
 }
 
+// the launch of gem_live_window and gem_live_window_at for the frames [first, first + T): the caller has checked them against the ring
+inline int live_window_launch(gem_handle* h, LiveArgs& a, int64_t first, const float* d_bone_fixed, float* d_win_pose, double* d_win_cams,
+                              float* d_win_heat, float* d_mean_bone, void* stream) {
+    GEM_HIP(hipSetDevice(h->cfg.device));
+    a.first = first; a.bone_fixed = d_bone_fixed; a.mean_bone = d_mean_bone;
+    a.vec = a.vec && (reinterpret_cast<uintptr_t>(d_win_heat) & 15) == 0;
+    hipLaunchKernelGGL(live_window_kernel, dim3((unsigned)LIVE_T, (unsigned)a.H + 1), dim3(LIVE_THREADS), 0, static_cast<hipStream_t>(stream), a,
+                       d_win_heat, d_win_pose, d_win_cams);
+    GEM_HIP(hipGetLastError());
+    return 0;
+}
+
 }  // namespace gem
 
 extern "C" {
@@ -280,13 +293,7 @@ int gem_live_window(gem_handle* h, const gem_live_buffers* b, int64_t window, in
                   " frames pushed, " + std::to_string(LIVE_RING) + " slots)");
         return 1;
     }
-    GEM_HIP(hipSetDevice(h->cfg.device));
-    a.first = first; a.bone_fixed = d_bone_fixed; a.mean_bone = d_mean_bone;
-    a.vec = a.vec && (reinterpret_cast<uintptr_t>(d_win_heat) & 15) == 0;
-    hipLaunchKernelGGL(live_window_kernel, dim3((unsigned)LIVE_T, (unsigned)a.H + 1), dim3(LIVE_THREADS), 0, static_cast<hipStream_t>(stream), a,
-                       d_win_heat, d_win_pose, d_win_cams);
-    GEM_HIP(hipGetLastError());
-    return 0;
+    return live_window_launch(h, a, first, d_bone_fixed, d_win_pose, d_win_cams, d_win_heat, d_mean_bone, stream);
 }
 
 int gem_live_emit(gem_handle* h, const gem_live_buffers* b, int64_t window, int final, const double* d_global, const float* d_win_pose,
@@ -327,6 +334,202 @@ int gem_one_euro(const double* d_seq, const double* d_times, int n_chunks, int64
     }
     const int64_t n = (int64_t)n_chunks * n_coords;
     hipLaunchKernelGGL(one_euro_kernel, dim3((unsigned)((n + LIVE_THREADS - 1) / LIVE_THREADS)), dim3(LIVE_THREADS), 0,
+                       static_cast<hipStream_t>(stream), a);
+    GEM_HIP(hipGetLastError());
+    return 0;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------- dense live mode
+// Live mode at a stride k below 8, and the `now` stream ("Dense live mode"; gem_live_dense.h has the layout of
+// the dense state block).
+//
+//   gem_live_window_at    gem_live_window for any first frame (the same kernel, the same ring checks)
+//   gem_live_emit_dense   the window's 10 frames onto the per-frame sums, the `now` frames (the window's newest k, all 10 of window 0;
+//                         One-Euro filtered in frame order when asked), the k frames no later window covers as sum / count, their
+//                         estimated frames; `final`: the 10 - k frames still held, each over its own count
+//   gem_merge_dense       the offline twin: every frame the mean of all windows that cover it, at any stride 1 .. T
+//
+// Sums run over the covering windows oldest first, one thread per coordinate, no atomics: the same bits on every call.
+namespace gem {
+
+constexpr int LIVE_SLOTS = GEM_LIVE_DENSE_SLOTS;
+constexpr int LD_TPREV = 0, LD_HAVE_PREV = 1, LD_WINDOWS = 2, LD_SETTLED = 3, LD_NOW = 4, LD_COUNT = 16, LD_XPREV = LD_COUNT + LIVE_SLOTS,
+              LD_DXPREV = LD_XPREV + LIVE_MAXC, LD_SUM = LD_DXPREV + LIVE_MAXC, LD_EST = LD_SUM + LIVE_SLOTS * LIVE_MAXC;
+static_assert(LD_EST + LIVE_SLOTS * LIVE_MAXC == GEM_LIVE_DENSE_DOUBLES, "the dense state block's layout and its size disagree");
+static_assert((LIVE_SLOTS & (LIVE_SLOTS - 1)) == 0 && LIVE_T <= LIVE_SLOTS, "a window's frames lie in distinct slots, slot = frame mod a power of two");
+
+struct LiveDenseArgs {
+    const double* ring_times;  // the session's ring of timestamps
+    double* st;                // the dense state block
+    const double* global;      // [T,J,3] the window's result
+    const float* pose;         // [T,J,3] the window buffer
+    const double* cams;        // [T,4,4] the window buffer
+    double* out;               // [3][T][JC]: settled, estimated, now
+    int64_t first;             // the window's first frame, stride * window
+    int stride, J, final, filter, all_now;
+    double euro[3];
+};
+
+// One workgroup; thread c owns coordinate c = 3 j + d of every frame.
+__global__ __launch_bounds__(64) void live_emit_dense_kernel(LiveDenseArgs a) {
+    const int c = threadIdx.x, J = a.J, JC = J * 3, k = a.stride;
+    double* st = a.st;
+    const bool have_prev0 = st[LD_HAVE_PREV] != 0.0;
+    const double t_prev0 = st[LD_TPREV];
+    const int n_frames = a.final ? LIVE_T - k : LIVE_T;
+    double cnt[LIVE_T];
+    for (int i = 0; i < n_frames; ++i) cnt[i] = st[LD_COUNT + (int)((a.first + i) & (LIVE_SLOTS - 1))];
+    __syncthreads();          // (thread 0 writes the counts and the filter's two scalars at the end)
+    double t_last = t_prev0;
+    bool have_prev = have_prev0;
+    const int n_now = a.final ? 0 : (a.all_now ? LIVE_T : k);
+    if (c < JC) {
+        const int j = c / 3, d = c % 3;
+        double* out_set = a.out + c;
+        double* out_est = a.out + (size_t)LIVE_T * JC + c;
+        double* out_now = a.out + (size_t)2 * LIVE_T * JC + c;
+        if (a.final) {
+            for (int i = 0; i < n_frames; ++i) {
+                const int slot = (int)((a.first + i) & (LIVE_SLOTS - 1));
+                out_set[(size_t)i * JC] = st[LD_SUM + slot * LIVE_MAXC + c] / cnt[i];
+                out_est[(size_t)i * JC] = st[LD_EST + slot * LIVE_MAXC + c];
+                st[LD_SUM + slot * LIVE_MAXC + c] = 0.0;
+            }
+        } else {
+            double x_prev = st[LD_XPREV + c], dx_prev = st[LD_DXPREV + c], t_prev = t_prev0;
+            for (int i = 0; i < LIVE_T; ++i) {
+#pragma clang fp contract(off)
+                const int slot = (int)((a.first + i) & (LIVE_SLOTS - 1));
+                const double* M = a.cams + (size_t)i * 16 + 4 * d;
+                const float* p = a.pose + ((size_t)i * J + j) * 3;
+                const double e = M[0] * (double)p[0] + M[1] * (double)p[1] + M[2] * (double)p[2] + M[3];
+                double x = a.global[(size_t)i * JC + c];
+                // the covering windows oldest first: the first one is taken as it is (no 0 + x, which would lose the sign of -0)
+                const double sum = cnt[i] == 0.0 ? x : st[LD_SUM + slot * LIVE_MAXC + c] + x;
+                if (i < k) {          // no later window covers frame first + i
+                    out_set[(size_t)i * JC] = sum / (cnt[i] + 1.0);
+                    out_est[(size_t)i * JC] = e;
+                    st[LD_SUM + slot * LIVE_MAXC + c] = 0.0;
+                } else {
+                    st[LD_SUM + slot * LIVE_MAXC + c] = sum;
+                    st[LD_EST + slot * LIVE_MAXC + c] = e;
+                }
+                if (i >= LIVE_T - n_now) {
+                    if (a.filter) {
+                        const double t = a.ring_times[(a.first + i) % LIVE_RING];
+                        if (!have_prev) { x_prev = x; dx_prev = 0.0; have_prev = true; }          // the first frame passes through
+                        else x = one_euro_step(a.euro, t, t_prev, x, x_prev, dx_prev);
+                        t_prev = t;
+                    }
+                    out_now[(size_t)(i - (LIVE_T - n_now)) * JC] = x;
+                }
+            }
+            t_last = t_prev;
+            st[LD_XPREV + c] = x_prev;
+            st[LD_DXPREV + c] = dx_prev;
+        }
+    }
+    if (c == 0) {
+        for (int i = 0; i < n_frames; ++i)
+            st[LD_COUNT + (int)((a.first + i) & (LIVE_SLOTS - 1))] = (a.final || i < k) ? 0.0 : cnt[i] + 1.0;
+        st[LD_TPREV] = t_last;
+        st[LD_HAVE_PREV] = have_prev ? 1.0 : 0.0;
+        st[LD_SETTLED] += (double)(a.final ? LIVE_T - k : k);
+        st[LD_NOW] += (double)n_now;
+        if (!a.final) st[LD_WINDOWS] += 1.0;
+    }
+}
+
+struct MergeDenseArgs {
+    const double* win;
+    double* out;
+    int64_t n;                 // n_chunks * frames_per_chunk * JC
+    int64_t fpc;
+    int wpc, T, JC, stride;
+};
+
+// one thread per (chunk, frame, coordinate): the covering windows in ascending order
+__global__ __launch_bounds__(LIVE_THREADS) void merge_dense_kernel(MergeDenseArgs a) {
+    const int64_t id = (int64_t)blockIdx.x * LIVE_THREADS + threadIdx.x;
+    if (id >= a.n) return;
+    const int c = (int)(id % a.JC);
+    const int64_t f = (id / a.JC) % a.fpc, chunk = id / a.JC / a.fpc;
+    const int64_t lo = f < a.T ? 0 : (f - a.T) / a.stride + 1;          // the first window with lo * stride + T > f
+    const int64_t hi = f / a.stride < a.wpc - 1 ? f / a.stride : a.wpc - 1;
+    const double* w = a.win + (size_t)chunk * a.wpc * a.T * a.JC + c;
+    double sum = w[((size_t)lo * a.T + (size_t)(f - lo * a.stride)) * a.JC];
+    for (int64_t i = lo + 1; i <= hi; ++i) sum += w[((size_t)i * a.T + (size_t)(f - i * a.stride)) * a.JC];
+    a.out[id] = sum / (double)(hi - lo + 1);
+}
+
+}  // namespace gem
+
+extern "C" {
+
+int gem_live_window_at(gem_handle* h, const gem_live_buffers* b, int64_t first_frame, int64_t n_pushed, const float* d_bone_fixed,
+                       float* d_win_pose, double* d_win_cams, float* d_win_heat, float* d_mean_bone, void* stream) {
+    using namespace gem;
+    LiveArgs a;
+    if (live_args(h, b, "gem_live_window_at", &a)) return 1;
+    if (!d_win_pose || !d_win_cams || !d_win_heat || !d_mean_bone) { set_error("gem_live_window_at: null argument"); return 1; }
+    if (first_frame < 0 || first_frame > INT64_MAX - LIVE_T) { set_error("gem_live_window_at: first frame out of range"); return 1; }
+    if (n_pushed < first_frame + LIVE_T) {
+        set_error("gem_live_window_at: the window ends at frame " + std::to_string(first_frame + LIVE_T - 1) + ", only " +
+                  std::to_string(n_pushed) + " frames have been pushed");
+        return 1;
+    }
+    if (n_pushed - first_frame > LIVE_RING) {
+        set_error("gem_live_window_at: ring overrun: frame " + std::to_string(first_frame) + " has been overwritten (" +
+                  std::to_string(n_pushed) + " frames pushed, " + std::to_string(LIVE_RING) + " slots)");
+        return 1;
+    }
+    return live_window_launch(h, a, first_frame, d_bone_fixed, d_win_pose, d_win_cams, d_win_heat, d_mean_bone, stream);
+}
+
+int gem_live_emit_dense(gem_handle* h, const gem_live_buffers* b, double* d_dense_state, int stride, int64_t window, int final,
+                        const double* d_global, const float* d_win_pose, const double* d_win_cams, const double* h_one_euro, double* d_out,
+                        void* stream) {
+    using namespace gem;
+    LiveArgs la;
+    if (live_args(h, b, "gem_live_emit_dense", &la)) return 1;
+    if (!d_dense_state || !d_out || (!final && (!d_global || !d_win_pose || !d_win_cams))) { set_error("gem_live_emit_dense: null argument"); return 1; }
+    if (stride < 1 || stride > LIVE_STRIDE) {
+        set_error("gem_live_emit_dense: the stride is between 1 and " + std::to_string(LIVE_STRIDE) + " frames, got " + std::to_string(stride)); return 1;
+    }
+    if (window < 0 || window > (INT64_MAX - LIVE_T) / LIVE_STRIDE) { set_error("gem_live_emit_dense: window out of range"); return 1; }
+    LiveDenseArgs a = LiveDenseArgs();
+    if (h_one_euro) {
+        for (int i = 0; i < 3; ++i) {
+            if (!(h_one_euro[i] >= 0.0) || h_one_euro[i] > 1e300) { set_error("gem_live_emit_dense: the filter's parameters must be finite and not negative"); return 1; }
+            a.euro[i] = h_one_euro[i];
+        }
+        a.filter = 1;
+    }
+    GEM_HIP(hipSetDevice(h->cfg.device));
+    a.ring_times = b->ring_times; a.st = d_dense_state; a.global = d_global; a.pose = d_win_pose; a.cams = d_win_cams; a.out = d_out;
+    a.first = window * stride; a.stride = stride; a.J = la.J; a.final = final ? 1 : 0; a.all_now = window == 0;
+    hipLaunchKernelGGL(live_emit_dense_kernel, dim3(1), dim3(64), 0, static_cast<hipStream_t>(stream), a);
+    GEM_HIP(hipGetLastError());
+    return 0;
+}
+
+int gem_merge_dense(const double* d_windows, int n_chunks, int windows_per_chunk, int T, int n_coords, int stride, double* d_out, void* stream) {
+    using namespace gem;
+    if (n_chunks < 0 || windows_per_chunk < 1 || T < 1 || n_coords < 1 || stride < 1 || stride > T) {
+        set_error("gem_merge_dense: need n_chunks >= 0, windows_per_chunk >= 1, n_coords >= 1 and 1 <= stride <= T"); return 1;
+    }
+    if (n_chunks == 0) return 0;
+    if (!d_windows || !d_out) { set_error("gem_merge_dense: null argument"); return 1; }
+    MergeDenseArgs a;
+    a.win = d_windows; a.out = d_out; a.wpc = windows_per_chunk; a.T = T; a.JC = n_coords; a.stride = stride;
+    a.fpc = (int64_t)(windows_per_chunk - 1) * stride + T;
+    // (the input is the larger of the two arrays: with it below 2^40 doubles no index above overflows)
+    if ((int64_t)n_chunks * windows_per_chunk > (((int64_t)1 << 40) / T) / n_coords) { set_error("gem_merge_dense: too many windows for one call"); return 1; }
+    a.n = (int64_t)n_chunks * a.fpc * n_coords;
+    if ((a.n + LIVE_THREADS - 1) / LIVE_THREADS > 0x7fffffffLL) { set_error("gem_merge_dense: too many frames x coordinates for one call"); return 1; }
+    hipLaunchKernelGGL(merge_dense_kernel, dim3((unsigned)((a.n + LIVE_THREADS - 1) / LIVE_THREADS)), dim3(LIVE_THREADS), 0,
                        static_cast<hipStream_t>(stream), a);
     GEM_HIP(hipGetLastError());
     return 0;

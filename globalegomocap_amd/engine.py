@@ -742,6 +742,50 @@ class WindowEngine:
                                            _ptr(win_cams), euro, _ptr(out), _stream()), self.lib)
         return out
 
+    def live_dense_state(self):
+        """The second block of a dense live session (include/gem_live_dense.h): the per-frame sums and counts, the estimated frames
+        still held and the `now` stream's filter state, zeroed."""
+        return torch.zeros(_capi.LIVE_DENSE_DOUBLES, device=self.device, dtype=torch.float64)
+
+    def live_window_at(self, bufs, first_frame, n_pushed, win_pose, win_cams, win_heat, mean_bone, bone_fixed=None):
+        """`live_window` for the frames [first_frame, first_frame + 10) (gem_live_window_at).  No synchronisation."""
+        self._live_check("live_window_at", (win_pose, torch.float32, (self.T, N_JOINTS, 3)), (win_cams, torch.float64, (self.T, 4, 4)),
+                         (win_heat, torch.float32, (self.T,) + self.heat_size + (N_JOINTS,)), (mean_bone, torch.float32, (1, N_JOINTS)),
+                         (bone_fixed, torch.float32, (N_JOINTS,)))
+        _capi.check(self.lib.gem_live_window_at(self._h, C.byref(bufs["c"]), int(first_frame), int(n_pushed), _ptr(bone_fixed), _ptr(win_pose),
+                                                _ptr(win_cams), _ptr(win_heat), _ptr(mean_bone), _stream()), self.lib)
+
+    def live_emit_dense(self, bufs, dense_state, stride, window, out, glob=None, win_pose=None, win_cams=None, final=False, one_euro=None):
+        """The result `glob` [1,10,15,3] f64 of window `window` at `stride` (1..8) -> out [3,10,15,3] f64 (gem_live_emit_dense):
+        out[0, :stride] the frames no later window covers, each the mean of the windows that covered it (oldest first, never
+        filtered); out[1, :stride] their estimated frames; out[2] the `now` frames -- all 10 of window 0, else the window's last
+        `stride` -- unaveraged, One-Euro filtered when `one_euro` = (min_cutoff, beta, d_cutoff).  final=True (`window` = the number of
+        windows emitted): the 10 - stride frames still held into out[0] and out[1] instead.  `dense_state`: `live_dense_state()`.
+        No synchronisation."""
+        self._live_check("live_emit_dense", (dense_state, torch.float64, (_capi.LIVE_DENSE_DOUBLES,)), (out, torch.float64, (3, self.T, N_JOINTS, 3)),
+                         (glob, torch.float64, (1, self.T, N_JOINTS, 3)), (win_pose, torch.float32, (self.T, N_JOINTS, 3)),
+                         (win_cams, torch.float64, (self.T, 4, 4)))
+        if dense_state is None:
+            raise TypeError("live_emit_dense wants the session's dense state block")
+        euro = (C.c_double * 3)(*[float(v) for v in one_euro]) if one_euro is not None else None
+        _capi.check(self.lib.gem_live_emit_dense(self._h, C.byref(bufs["c"]), _ptr(dense_state), int(stride), int(window), 1 if final else 0,
+                                                 _ptr(glob), _ptr(win_pose), _ptr(win_cams), euro, _ptr(out), _stream()), self.lib)
+        return out
+
+    def merge_dense(self, windows, n_chunks, stride):
+        """Every frame the mean of all windows that cover it, per chunk (gem_merge_dense; `sequence.merge_dense` on the device):
+        windows [n_chunks*wpc,T,15,3] at `stride` (1..T) frames from one another -> [n_chunks, (wpc-1)*stride + T, 15, 3] f64.  Overlaps
+        above T / 2, which `merge_windows` does not serve, included.  No synchronisation."""
+        w = self._f64(windows).reshape(-1, self.T, N_JOINTS, 3)
+        if n_chunks < 1 or w.shape[0] == 0 or w.shape[0] % n_chunks:
+            raise ValueError("merge_dense: %d windows do not split into %d chunks" % (w.shape[0], n_chunks))
+        if not 1 <= int(stride) <= self.T:
+            raise ValueError("merge_dense: the stride is between 1 and %d frames, got %r" % (self.T, stride))
+        wpc = w.shape[0] // n_chunks
+        out = torch.empty(n_chunks, (wpc - 1) * int(stride) + self.T, N_JOINTS, 3, device=self.device, dtype=torch.float64)
+        _capi.check(self.lib.gem_merge_dense(_ptr(w), n_chunks, wpc, self.T, N_JOINTS * 3, int(stride), _ptr(out), _stream()), self.lib)
+        return out
+
     def one_euro_filter(self, seq, times, n_chunks, params):
         """The reference's utils/one_euro_filter.py over `n_chunks` equally long sequences laid end to end (gem_one_euro): seq
         [n_chunks*F,15,3] f64 (any trailing shape), times [n_chunks*F] f64, params (min_cutoff, beta, d_cutoff) -> a device tensor

@@ -19,6 +19,10 @@ here; `one_euro=(min_cutoff, beta, d_cutoff)` runs the causal One-Euro filter of
 `optimized` instead (off by default, as the reference's `main()` never calls it: with the filter off a session reproduces the
 engine's own window results bit for bit).
 
+`LiveOptimizer(..., stride=k, now=True)` is the dense session (section 6h, "Dense live mode"): a window every k <= 8 frames, a second
+stream `now` that hands every frame back with no look-ahead (at k = 1 in the push that brought it), and `optimized` the mean of all
+windows that cover a frame.  stride=8, now=False is the session described above, untouched.
+
 `replay` / `python -m globalegomocap_amd.live` push the frames of a prepared recording one at a time: a replay of a recording, for
 looking at live mode's results and step times.
 """
@@ -42,19 +46,28 @@ STRIDE = SEQ_LEN - OVERLAP
 DEFAULT_WEIGHTS = dict(vae_weight=0.0, smoothness_weight=0.001, bone_length_weight=0.01, weight_3d=0.01, reproj_weight=0.01)
 
 
-def dropped_frames(n_pushed):
-    """How many of `n_pushed` frames belong to no complete window (the reference's range(0, len - 10 + 1, 8) drops them)."""
-    n_windows = (n_pushed - SEQ_LEN) // STRIDE + 1 if n_pushed >= SEQ_LEN else 0
-    return n_pushed - (n_windows * STRIDE + OVERLAP if n_windows else 0)
+def check_stride(stride):
+    """The stride of a session, an int in 1 .. 8; ValueError otherwise."""
+    if isinstance(stride, bool) or not isinstance(stride, (int, np.integer)) or not 1 <= stride <= STRIDE:
+        raise ValueError("stride is a whole number of frames between 1 and %d, got %r" % (STRIDE, stride))
+    return int(stride)
 
 
-def _pieces(n_pushed, k):
+def dropped_frames(n_pushed, stride=STRIDE):
+    """How many of `n_pushed` frames belong to no complete window (the reference's range(0, len - 10 + 1, 8) drops them; `stride`: the
+    8 of that range): (n - 10) mod stride from ten frames on, all of them below."""
+    n_windows = (n_pushed - SEQ_LEN) // stride + 1 if n_pushed >= SEQ_LEN else 0
+    return n_pushed - ((n_windows - 1) * stride + SEQ_LEN if n_windows else 0)
+
+
+def _pieces(n_pushed, k, stride=STRIDE):
     """A push of k frames behind n_pushed, cut into pieces of at most 8 frames none of which goes past the frame that completes a
-    window: the window is optimised -- and its mean bone length taken -- before the frames behind it arrive."""
+    window: the window is optimised -- and its mean bone length taken -- before the frames behind it arrive.  With windows every
+    `stride` frames the completing frames are stride * w + 9."""
     out, at = [], 0
     while at < k:
         n = n_pushed + at
-        completing = SEQ_LEN - 1 if n < SEQ_LEN else n + (SEQ_LEN - 1 - n) % STRIDE          # the next frame 8w + 9 at or behind n
+        completing = SEQ_LEN - 1 if n < SEQ_LEN else n + (SEQ_LEN - 1 - n) % stride          # the next frame stride * w + 9 at or behind n
         step = min(k - at, _capi.LIVE_PUSH_MAX, completing - n + 1)
         out.append((at, at + step))
         at += step
@@ -125,12 +138,21 @@ class LiveOptimizer:
     bones_for_depth, neck_depth: the wearer's 15 bone lengths in metres (entry 0 equal to 0; default: the mean skeleton's) and the neck's
       distance from the camera, for `bone_depths` (`bone_depth.options`).
     min_peak: with `push(heat=, depth="bones")`, a joint whose map peaks below it is treated as not detected.
+    stride, now: a window every `stride` frames (1..8) and a second stream `now` with no look-ahead.  stride=8, now=False is the session
+      described above.  Anything else is the dense session ("Dense live mode"): window w covers the frames
+      [stride w, stride w + 10) and runs when frame stride w + 9 arrives; `push` also returns "now" -- all 10 frames of window 0, then the
+      newest `stride` frames of every window as that window left them, every frame once, at stride 1 in the push that brought it;
+      `optimized` is the settled stream: the frames [stride w, stride w + stride), which no later window covers, each the mean of all
+      windows that covered it (oldest first, in float64); `flush` emits the 10 - stride frames still held.  `one_euro` then filters
+      `now`, the stream without look-ahead, and `optimized` is never filtered.
     """
 
     def __init__(self, camera_model_path, global_vae=GLOBAL_VAE_PATH, local_vae=LOCAL_VAE_PATH, *, scale=1.0, weights=None, bone="running",
                  one_euro=None, eps=None, seed=0, graphs=True, lr=2, max_iter=25, heat_size=(64, 64), sigma=1.5, bones_for_depth=None,
-                 neck_depth=None, min_peak=0.0):
+                 neck_depth=None, min_peak=0.0, stride=STRIDE, now=False):
         from . import bone_depth
+        self.stride, self.now = check_stride(stride), bool(now)          # (refused before a device is touched)
+        self.dense = self.stride != STRIDE or self.now
         self._depth_opts = bone_depth.options(bones_for_depth, neck_depth=neck_depth)          # (refused before a device is touched)
         self.min_peak = float(min_peak)
         if not (np.isfinite(self.min_peak) and self.min_peak >= 0):
@@ -173,9 +195,12 @@ class LiveOptimizer:
         self._eps_l, self._eps_g = (torch.zeros(1, e.D, device=dev, dtype=torch.float32) for _ in range(2))
         self._out = torch.zeros(2, STRIDE, N_JOINTS, 3, device=dev, dtype=torch.float64)
         self._kp_prev = torch.zeros(N_JOINTS, 3, device=dev, dtype=torch.float64)          # push(keypoints=, depth=): the last usable lift of every joint
-        self.n_pushed = self.n_windows = self.n_emitted = 0
+        # the dense session's own: the sums / counts / filter block and its output block (settled, estimated, now)
+        self._dense_state = e.live_dense_state() if self.dense else None
+        self._out_dense = torch.zeros(3, SEQ_LEN, N_JOINTS, 3, device=dev, dtype=torch.float64) if self.dense else None
+        self.n_pushed = self.n_windows = self.n_emitted = self.n_now = 0
         self._last_time, self._row0, self._flushed = None, None, False
-        self.window_log, self._optimized, self._estimated = [], [], []
+        self.window_log, self._optimized, self._estimated, self._now = [], [], [], []
 
     # ------------------------------------------------------------------ state
     def close(self):
@@ -185,6 +210,7 @@ class LiveOptimizer:
             self.engine.close()
         self.engine = self._bufs = self._win_pose = self._win_cams = self._win_heat = self._out = None
         self._mean_bone = self._eps_l = self._eps_g = self._frame0 = self._bone_fixed = self._kp_prev = None
+        self._dense_state = self._out_dense = None
 
     def __enter__(self):
         return self
@@ -201,9 +227,11 @@ class LiveOptimizer:
         return self.engine
 
     def result(self):
-        """Everything emitted so far: {"frames": 0, "optimized", "estimated"} with numpy f64 arrays [n_emitted,15,3]."""
+        """Everything emitted so far: {"frames": 0, "optimized", "estimated"} with numpy f64 arrays [n_emitted,15,3]; a dense session
+        adds "now_frames": 0 and "now" [n_now,15,3]."""
         cat = lambda parts: np.concatenate(parts) if parts else np.empty((0, N_JOINTS, 3))          # noqa: E731
-        return {"frames": 0, "optimized": cat(self._optimized), "estimated": cat(self._estimated)}
+        r = {"frames": 0, "optimized": cat(self._optimized), "estimated": cat(self._estimated)}
+        return dict(r, now_frames=0, now=cat(self._now)) if self.dense else r
 
     def save_pose(self, out_dir):
         """`<out_dir>/result_pose.pkl` with `estimated_pose` and `optimized_pose` (lists of [15,3] frames): the schema of the
@@ -255,8 +283,9 @@ class LiveOptimizer:
         to the session's first frame, translations times `scale`) or cams [k,4,4] with times [k].  Host or device arrays.  Every window
         these frames complete is optimised at once; the call blocks until they are done, reads their statistics and raises the
         reference's Exception("norm is zero!") for a degenerate one.  -> {"frames": index of the first returned frame, "optimized",
-        "estimated"}: numpy f64 [m,15,3], m = 8 x the windows completed (possibly 0).  ValueError (before anything is enqueued) for
-        timestamps that do not increase strictly, wrong shapes, or contradictory arguments."""
+        "estimated"}: numpy f64 [m,15,3], m = 8 x the windows completed (possibly 0); a dense session (`stride`, `now`): m = stride x the
+        windows completed, plus "now_frames", the index of the first `now` frame returned, and "now" [m',15,3] f64.  ValueError (before
+        anything is enqueued) for timestamps that do not increase strictly, wrong shapes, or contradictory arguments."""
         e = self._engine()
         if self._flushed:
             raise _capi.GemError("this live session has been flushed: its held frames are out, a new stream needs a new session")
@@ -287,53 +316,76 @@ class LiveOptimizer:
         cams_d = self._device(self._cameras(rows) if rows is not None else cams, torch.float64)
         times_d = self._device(t, torch.float64)
         self._last_time = float(t[-1])
-        first, done = self.n_emitted, []
-        for a, b in _pieces(self.n_pushed, k):
+        first, first_now, done = self.n_emitted, self.n_now, []
+        for a, b in _pieces(self.n_pushed, k, self.stride):
             t0 = time.perf_counter()
-            e.live_push(self._bufs, self.n_pushed, self.n_windows * STRIDE, heat_d[a:b], pose_d[a:b], cams_d[a:b], times_d[a:b])
+            e.live_push(self._bufs, self.n_pushed, self.n_windows * self.stride, heat_d[a:b], pose_d[a:b], cams_d[a:b], times_d[a:b])
             self.n_pushed += b - a
-            if self.n_pushed == self.n_windows * STRIDE + SEQ_LEN:
+            if self.n_pushed == self.n_windows * self.stride + SEQ_LEN:
                 done.append(self._window(t0))
-        return self._emitted(first, done, STRIDE)
+        return self._emitted(first, done, self.stride, first_now)
 
     def _window(self, t0):
         """Window self.n_windows is complete: gather, optimise (both stages, B = 1), emit; blocks on the statistics."""
         e, w = self.engine, self.n_windows
-        e.live_window(self._bufs, w, self.n_pushed, self._win_pose, self._win_cams, self._win_heat, self._mean_bone, self._bone_fixed)
+        if self.dense:
+            e.live_window_at(self._bufs, w * self.stride, self.n_pushed, self._win_pose, self._win_cams, self._win_heat, self._mean_bone, self._bone_fixed)
+        else:
+            e.live_window(self._bufs, w, self.n_pushed, self._win_pose, self._win_cams, self._win_heat, self._mean_bone, self._bone_fixed)
         eps = self._eps(w) if self._eps is not None else torch.randn(2, e.D, generator=self._gen)
         eps = torch.as_tensor(np.asarray(eps) if not torch.is_tensor(eps) else eps, dtype=torch.float32).reshape(2, e.D)
         self._eps_l.copy_(eps[0:1])
         self._eps_g.copy_(eps[1:2])
         _, glob, stats = e.optimize_windows(self._win_pose, self._win_cams, self._win_heat, self._frame0, self._mean_bone, self._eps_l,
                                             self._eps_g, self.w_local, self.w_global, self.opts)
-        e.live_emit(self._bufs, w, self._out, glob, self._win_pose, self._win_cams, one_euro=self.one_euro)
-        out = self._out.cpu().numpy()                                   # (behind the emit kernel: the window is done)
+        if self.dense:
+            e.live_emit_dense(self._bufs, self._dense_state, self.stride, w, self._out_dense, glob, self._win_pose, self._win_cams, one_euro=self.one_euro)
+            out = self._out_dense.cpu().numpy()
+        else:
+            e.live_emit(self._bufs, w, self._out, glob, self._win_pose, self._win_cams, one_euro=self.one_euro)
+            out = self._out.cpu().numpy()                               # (behind the emit kernel: the window is done)
         st = stats_to_numpy(stats)
-        self.window_log.append({"window": w, "local": st[0].copy(), "global": st[1].copy(), "mean_bone": self._mean_bone[0].cpu().numpy(),
-                                "step_ms": (time.perf_counter() - t0) * 1e3})
+        self.window_log.append({"window": w, "stride": self.stride, "local": st[0].copy(), "global": st[1].copy(),
+                                "mean_bone": self._mean_bone[0].cpu().numpy(), "step_ms": (time.perf_counter() - t0) * 1e3})
         self.n_windows += 1
         raise_if_degenerate(st)
         return out
 
-    def _emitted(self, first, done, n):
+    def _emitted(self, first, done, n, first_now=0, final=False):
+        """The output blocks of the windows `done` (n settled frames each) as push's dict; a dense session's blocks carry the `now`
+        frames too: all 10 of window 0, the newest `stride` of every other window, none at the flush."""
         opt = np.concatenate([o[0, :n] for o in done]) if done else np.empty((0, N_JOINTS, 3))
         est = np.concatenate([o[1, :n] for o in done]) if done else np.empty((0, N_JOINTS, 3))
         if done:
             self._optimized.append(opt)
             self._estimated.append(est)
             self.n_emitted += len(opt)
-        return {"frames": first, "optimized": opt, "estimated": est}
+        got = {"frames": first, "optimized": opt, "estimated": est}
+        if self.dense:
+            w0 = self.n_windows - len(done)          # the first of these windows
+            parts = [] if final else [o[2, :SEQ_LEN if w0 + i == 0 else self.stride] for i, o in enumerate(done)]
+            now = np.concatenate(parts) if parts else np.empty((0, N_JOINTS, 3))
+            if len(now):
+                self._now.append(now)
+                self.n_now += len(now)
+            got.update(now_frames=first_now, now=now)
+        return got
 
     def flush(self):
         """The end of the stream: emits the two frames still held, as they are (`merge_batches`' last window; filtered when the filter
-        is on), and reports as "dropped" how many pushed frames belonged to no complete window.  -> push's dict plus "dropped"."""
+        is on), and reports as "dropped" how many pushed frames belonged to no complete window.  -> push's dict plus "dropped".  A
+        dense session emits the 10 - stride frames still held, each the mean of the windows that covered it, and no `now` frame."""
         e = self._engine()
         first, done = self.n_emitted, []
         if self.n_windows and not self._flushed:
-            e.live_emit(self._bufs, self.n_windows, self._out, final=True, one_euro=self.one_euro)
-            done.append(self._out.cpu().numpy())
+            if self.dense:
+                e.live_emit_dense(self._bufs, self._dense_state, self.stride, self.n_windows, self._out_dense, final=True, one_euro=self.one_euro)
+                done.append(self._out_dense.cpu().numpy())
+            else:
+                e.live_emit(self._bufs, self.n_windows, self._out, final=True, one_euro=self.one_euro)
+                done.append(self._out.cpu().numpy())
         self._flushed = True
-        return dict(self._emitted(first, done, OVERLAP), dropped=dropped_frames(self.n_pushed))
+        return dict(self._emitted(first, done, SEQ_LEN - self.stride, self.n_now, final=True), dropped=dropped_frames(self.n_pushed, self.stride))
 
 
 # ---------------------------------------------------------------------------------------------------------------------- replay
@@ -420,7 +472,7 @@ def replay(slam_result_path, heatmap_dir, depth_dir, start_frame, end_frame, cam
             print("live: {} frames pushed, {} emitted, {} dropped, {} windows".format(live.n_pushed, live.n_emitted, tail["dropped"], s["windows"]))
             if s["windows"]:
                 print("step time per window (ms): median {:.3f}, 99th percentile {:.3f}, max {:.3f}; budget {:.1f} ms at {:g} fps".format(
-                    s["step_ms_median"], s["step_ms_p99"], s["step_ms_max"], 1e3 * STRIDE / fps, fps))
+                    s["step_ms_median"], s["step_ms_p99"], s["step_ms_max"], 1e3 * live.stride / fps, fps))
                 print("L-BFGS per window: local {:.1f} iterations / {:.1f} evaluations, global {:.1f} / {:.1f}".format(
                     s["local_iters_mean"], s["local_evals_mean"], s["global_iters_mean"], s["global_evals_mean"]))
         return res, live.window_log
@@ -476,6 +528,9 @@ def _parser():
     p.add_argument("--weight_3d", type=float, default=DEFAULT_WEIGHTS["weight_3d"])
     p.add_argument("--reproj_weight", type=float, default=DEFAULT_WEIGHTS["reproj_weight"])
     p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--stride", type=int, default=STRIDE, metavar="K", help="a window every K frames, 1..8 (default 8); below 8 every frame "
+                                                                           "is the mean of all windows that cover it")
+    p.add_argument("--now", action="store_true", help="also keep the stream without look-ahead: every window's newest K frames, as it left them")
     return p
 
 
@@ -492,13 +547,15 @@ def _cli(argv=None):
         p.error("--min_peak goes with --heatmaps: detections carry their own confidence")
     if a.min_peak is not None and not (np.isfinite(a.min_peak) and a.min_peak >= 0):
         p.error("--min_peak must be a finite number >= 0")
+    if not 1 <= a.stride <= STRIDE:
+        p.error("--stride is between 1 and %d" % STRIDE)
     from .bone_depth import bones_from_args
     weights = dict(vae_weight=a.vae, smoothness_weight=a.smooth, bone_length_weight=a.bone_length, weight_3d=a.weight_3d,
                    reproj_weight=a.reproj_weight)
     replay(a.slam, a.heatmaps, a.depths, a.start, a.end, a.camera, fps=a.fps, pace=a.pace, save_pose=a.save_pose, global_vae=a.global_vae,
            local_vae=a.local_vae, scale=a.scale, weights=weights, bone=a.bone, one_euro=a.one_euro, seed=a.seed, keypoints=a.keypoints,
            first_id=a.first_id, sigma=a.sigma, depth_from=a.depth_from, bones_for_depth=bones_from_args(a), neck_depth=a.neck_depth,
-           min_peak=0.0 if a.min_peak is None else a.min_peak)
+           min_peak=0.0 if a.min_peak is None else a.min_peak, stride=a.stride, now=a.now)
 
 
 if __name__ == "__main__":

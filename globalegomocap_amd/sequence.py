@@ -52,6 +52,40 @@ def merge_chunks(windows, n_chunks, overlap=OVERLAP):
     return out
 
 
+def dense_counts(n_windows, stride, seq_len=SEQ_LEN):
+    """How many of `n_windows` windows, `stride` frames from one another, cover each of the (n_windows - 1) * stride + seq_len frames."""
+    count = np.zeros((n_windows - 1) * stride + seq_len, dtype=np.int64)
+    for i in range(n_windows):
+        count[i * stride:i * stride + seq_len] += 1
+    return count
+
+
+def merge_dense(windows, stride, n_chunks=None):
+    """Every frame the mean of ALL windows that cover it, for windows `stride` frames from one another (1 <= stride <= T; live mode's
+    dense path and `WindowEngine.merge_dense`): ((G_a[i_a] + G_b[i_b]) + ...) / count over the covering windows
+    oldest first, in float64.  [n, T, ...] -> [(n - 1) * stride + T, ...]; with n_chunks, [n_chunks*wpc, T, ...] -> [n_chunks, fpc, ...]
+    per chunk.  For stride >= T / 2 these are the bits of merge_batches / merge_chunks with overlap = T - stride."""
+    w = np.asarray(windows, dtype=np.float64)
+    chunks = 1 if n_chunks is None else int(n_chunks)
+    if w.ndim < 2 or chunks < 1 or w.shape[0] == 0 or w.shape[0] % chunks:
+        raise ValueError("merge_dense: windows of shape %s do not split into %d chunks" % (w.shape, chunks))
+    wpc, T, stride = w.shape[0] // chunks, w.shape[1], int(stride)
+    if not 1 <= stride <= T:
+        raise ValueError("merge_dense: the stride is between 1 and %d frames, got %d" % (T, stride))
+    w = w.reshape((chunks, wpc, T) + w.shape[2:])
+    count = dense_counts(wpc, stride, T)
+    out = np.empty((chunks, len(count)) + w.shape[3:], dtype=np.float64)
+    seen = 0          # frames below `seen` have been reached by a window before this one
+    for i in range(wpc):
+        a = i * stride
+        old = max(0, min(seen - a, T))
+        out[:, a:a + old] += w[:, i, :old]
+        out[:, a + old:a + T] = w[:, i, old:]          # (taken as it is: 0 + x would lose the sign of -0)
+        seen = a + T
+    out /= count.reshape((1, -1) + (1,) * (out.ndim - 2))
+    return out[0] if n_chunks is None else out
+
+
 def final_smooth(seq):
     """scipy gaussian_filter1d(sigma=1, axis=0) (optimizer.py:448-450)."""
     from scipy.ndimage import gaussian_filter1d

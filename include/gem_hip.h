@@ -717,6 +717,9 @@ int gem_live_emit(gem_handle* h, const gem_live_buffers* b, int64_t window, int 
                   const double* d_win_cams, const double* h_one_euro, double* d_out, void* stream);
 int gem_one_euro(const double* d_seq, const double* d_times, int n_chunks, int64_t frames_per_chunk, int n_coords, const double* h_params,
                  double* d_out, void* stream);
+/* Live mode at a stride below 8 with a zero-look-ahead stream, and the dense merge of recorded windows: their declarations and the
+ * layout of their state block are in the header of their own, next to this one. */
+#include "gem_live_dense.h"
 
 /* ---- Skeleton sequences as BVH animation: `bvh=DIR` / `--bvh DIR` ----
  * The file's skeleton has 19 nodes on the 15 joints (node: parent, rest direction, joint; Y up, Z forward, +X the character's left):

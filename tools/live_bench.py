@@ -20,6 +20,18 @@ resident on the device (`synth.make_sequence_device`, bench.py's camera noise), 
                     route on the same frames as one chunk: `SequenceOptimizer.run` on all windows at once, `merge_batches`, no final
                     smoothing.  B = 1 and B = 124 may choose different GEMM slices: an observation, not an assertion.
 
+With `--stride K` (1..8) and / or `--now` the variants time the DENSE session instead ("Dense live mode"):
+
+    python tools/live_bench.py --stride 1 --now --out profiles/live_dense.json
+
+Three things take turns on the same frames in one process: the dense session (a window every K frames), today's stride-8 session, and
+the direct B = 1 floor on the dense session's window.  Per variant: `step_ms` / `pair_step_ms` / `floor_ms` (median, 99th percentile,
+maximum of the window-completing pushes, the first two left out as above), the captures and replays of each, `budget_ms` = 1e3 K / fps
+and `within_budget` (EVERY dense step, the eager first two included, below the budget; the tool's exit status is 1 otherwise),
+`step_over_pair` (reported, not gated: both run the same optimiser call and differ by one 64-thread kernel), and as an observation on
+these synthetic frames, whose true poses are known: `mpjpe_mm` and `accel_mm` (the mean norm of the second difference, mm per
+frame^2) of the dense average, the `now` stream, the pair merge, the estimated input and the truth.
+
 The parent process never opens the GPU: the fit and every variant run in a fresh child process with a time limit of its own, once,
 and nothing is started after a child that failed.
 """
@@ -150,8 +162,99 @@ def child_variant(a):
     print(json.dumps(rec), flush=True)
 
 
+def child_dense(a):
+    import torch
+    import bench
+    from globalegomocap_amd import synth
+    from globalegomocap_amd.camera import FisheyeCamera, DEFAULT_CALIBRATION
+    from globalegomocap_amd.engine import WindowEngine, stats_to_numpy
+    from globalegomocap_amd.live import LiveOptimizer, STRIDE
+    torch.cuda.set_device(0)
+    dev = torch.device("cuda", 0)
+    sd_l, _, sd_g, _ = torch.load(a.weights, weights_only=False)
+    cam = FisheyeCamera.from_json(DEFAULT_CALIBRATION)
+    n, k = a.frames, a.stride
+    seq = synth.make_sequence_device(n, seed=SEED, device=dev, camera=cam, cam_jitter=bench.CAM_JITTER)
+    est, cams, heat = seq["est_local"], seq["cams"], seq["heat"]
+    rng = np.random.default_rng(SEED)
+    times = np.arange(n) / FPS + rng.uniform(-0.004, 0.004, n)
+    n_dense = (n - 10) // k + 1
+    eps = torch.randn(n_dense, 2, 2048, generator=torch.Generator().manual_seed(SEED))
+    dense = LiveOptimizer(DEFAULT_CALIBRATION, sd_g, sd_l, eps=lambda w: eps[w], graphs=True, stride=k, now=a.now)
+    pair = LiveOptimizer(DEFAULT_CALIBRATION, sd_g, sd_l, eps=lambda w: eps[min(STRIDE * w // k, n_dense - 1)], graphs=True)          # (the noise of the dense window nearest in time)
+    floor = WindowEngine(dense.engine.shape, cam, max_windows=1)
+    floor.load_vae(0, sd_l)
+    floor.load_vae(1, sd_g)
+    floor.enable_graphs(True)
+    for e in (dense.engine, pair.engine, floor):
+        e.set_precision(a.variant)
+    fb = {"pose": torch.zeros(10, 15, 3, device=dev), "cams": torch.zeros(10, 4, 4, device=dev, dtype=torch.float64),
+          "heat": torch.zeros(10, 64, 64, 15, device=dev), "f0": torch.zeros(1, device=dev, dtype=torch.int32),
+          "mb": torch.zeros(1, 15, device=dev), "el": torch.zeros(1, 2048, device=dev), "eg": torch.zeros(1, 2048, device=dev)}
+    step_ms, push_ms, pair_ms, floor_ms, mismatches = [], [], [], [], 0
+
+    def timed_push(live, i, steps, pushes):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        got = live.push(heat=heat[i:i + 1], est_local=est[i:i + 1], cams=cams[i:i + 1], times=times[i:i + 1])
+        if len(got["optimized"]):
+            steps.append((time.perf_counter() - t0) * 1e3)
+            return True
+        torch.cuda.synchronize()
+        pushes.append((time.perf_counter() - t0) * 1e3)
+        return False
+
+    for i in range(n):
+        completed = timed_push(dense, i, step_ms, push_ms)
+        timed_push(pair, i, pair_ms, [])
+        if not completed:
+            continue
+        w = dense.n_windows - 1
+        sl = slice(k * w, k * w + 10)
+        fb["pose"].copy_(est[sl]); fb["cams"].copy_(cams[sl]); fb["heat"].copy_(heat[sl])          # noqa: E702
+        fb["mb"].copy_(torch.from_numpy(dense.window_log[w]["mean_bone"]).reshape(1, 15))
+        fb["el"].copy_(eps[w, 0:1]); fb["eg"].copy_(eps[w, 1:2])          # noqa: E702
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        _, _, st = floor.optimize_windows(fb["pose"], fb["cams"], fb["heat"], fb["f0"], fb["mb"], fb["el"], fb["eg"], dense.w_local, dense.w_global,
+                                          dense.opts)
+        st = stats_to_numpy(st)
+        floor_ms.append((time.perf_counter() - t0) * 1e3)
+        row = dense.window_log[w]
+        mismatches += int((st["func_evals"] != [row["local"]["func_evals"], row["global"]["func_evals"]]).any())
+    tail, _ = dense.flush(), pair.flush()
+    res, res_pair = dense.result(), pair.result()
+    log = dense.window_log
+    rec = {"leg": a.variant, "stride": k, "now": bool(a.now), "frames": n, "windows": len(step_ms), "pair_windows": len(pair_ms), "fps": FPS,
+           "graphs": dense.graph_stats(), "graphs_pair": pair.graph_stats(), "graphs_floor": floor.graph_stats(),
+           "step_ms": pct(step_ms[2:]), "pair_step_ms": pct(pair_ms[2:]), "floor_ms": pct(floor_ms[2:]), "push_ms": pct(push_ms) if push_ms else None,
+           "first_two_steps_ms": step_ms[:2], "floor_mismatches": mismatches, "dropped": tail["dropped"],
+           "local_evals_mean": float(np.mean([r["local"]["func_evals"] for r in log])),
+           "global_evals_mean": float(np.mean([r["global"]["func_evals"] for r in log]))}
+    dense.close()
+    pair.close()
+    floor.close()
+    rec["bookkeeping_ms"] = rec["step_ms"]["median"] - rec["floor_ms"]["median"]
+    rec["step_over_pair"] = rec["step_ms"]["median"] / rec["pair_step_ms"]["median"]
+    rec["budget_ms"] = 1e3 * k / FPS
+    rec["step_ms_max_all"] = float(max(step_ms))
+    rec["within_budget"] = bool(rec["step_ms_max_all"] < rec["budget_ms"])
+    rec["real_time_share"] = rec["step_ms"]["median"] / rec["budget_ms"]
+    # ---- an observation: the dense average and the pair merge against the known poses, on the frames both emitted
+    m = min(len(res["optimized"]), len(res_pair["optimized"]))
+    gt = np.asarray(seq["gt_global"], dtype=np.float64)[:m]
+    streams = {"dense": res["optimized"][:m], "now": res["now"][:m], "pair": res_pair["optimized"][:m], "estimated": res["estimated"][:m], "truth": gt}
+    rec["compared_frames"] = int(m)
+    rec["mpjpe_mm"] = {name: float(np.linalg.norm(x - gt, axis=-1).mean() * 1e3) for name, x in streams.items() if name != "truth"}
+    rec["accel_mm"] = {name: float(np.linalg.norm(x[2:] - 2 * x[1:-1] + x[:-2], axis=-1).mean() * 1e3) for name, x in streams.items()}
+    print(json.dumps(rec), flush=True)
+    return 0 if rec["within_budget"] else 1
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--stride", type=int, default=8, choices=range(1, 9), metavar="K", help="a window every K frames (1..8): below 8, or with --now, the dense session is timed")
+    ap.add_argument("--now", action="store_true", help="the dense session with its stream without look-ahead")
     ap.add_argument("--frames", type=int, default=1000)
     ap.add_argument("--fit-steps", type=int, default=2000)
     ap.add_argument("--precisions", nargs="+", default=["f32", "bf16"], choices=["f32", "bf16x3", "bf16"])
@@ -162,12 +265,14 @@ def main():
     a = ap.parse_args()
     if a.child == "fit":
         return child_fit(a)
+    dense = a.stride != 8 or a.now
     if a.child == "variant":
-        return child_variant(a)
+        return child_dense(a) if dense else child_variant(a)
     records = []
     with tempfile.TemporaryDirectory(prefix="live_bench_") as tmp:
         weights = os.path.join(tmp, "vae.pt")
-        base = [sys.executable, os.path.abspath(__file__), "--frames", str(a.frames), "--fit-steps", str(a.fit_steps), "--weights", weights]
+        base = [sys.executable, os.path.abspath(__file__), "--frames", str(a.frames), "--fit-steps", str(a.fit_steps), "--weights", weights,
+                "--stride", str(a.stride)] + (["--now"] if a.now else [])
         legs = [("fit", ["--child", "fit"], LIMITS["fit"])] + [(p, ["--child", "variant", "--variant", p], LIMITS["variant"]) for p in a.precisions]
         for name, extra, limit in legs:
             try:
