@@ -248,6 +248,7 @@ SIGNATURES = {
     "gem_foot_lock": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, C.c_double, _P, C.c_int64, _P, _P]),
     "gem_slam_bridge_work": (C.c_int64, [C.c_int64]),
     "gem_slam_bridge": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, _P, _P, C.c_int, C.c_int64, _P, _P, _P, _P, _P, C.c_int64, _P, _P]),
+    "gem_merge_cover": (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_int, C.c_int64, _P, _P, _P, _P, _P]),
 }
 
 # every symbol include/gem_live_dense.h declares (the header gem_hip.h includes for dense live mode)

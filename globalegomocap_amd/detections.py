@@ -210,6 +210,13 @@ def recording_from_detections(slam_result_path, detections, gt_path=None, scale=
         return rec
 
 
+def continuous_from_detections(slam_result_path, detections, gt_path=None, scale=None, start_frame=0, end_frame=0, fps=25, **kwargs):
+    """`recording_from_detections` for a recording that is optimised as one motion (`continuous.optimize_continuous`, DESIGN.md section
+    6s): the ONE span [start_frame, end_frame) as one chunk; the other arguments, by keyword, as there.  -> a Recording that is
+    continuous already."""
+    return recording_from_detections(slam_result_path, detections, gt_path, scale, [(int(start_frame), int(end_frame))], fps, **kwargs)
+
+
 def _parser():
     import argparse
     from . import prepare

@@ -786,6 +786,36 @@ class WindowEngine:
         _capi.check(self.lib.gem_merge_dense(_ptr(w), n_chunks, wpc, self.T, N_JOINTS * 3, int(stride), _ptr(out), _stream()), self.lib)
         return out
 
+    def merge_cover(self, windows, starts, smooth=False, want_spread=False):
+        """Every frame the mean of all windows that cover it, for windows that are not equally spaced (gem_merge_cover;
+        `sequence.merge_cover` on the device): windows [B,T,J,3] at `starts` [B] -> (merged [N,J,3] f64, its
+        Gaussian-smoothed copy with `smooth` else None, count [N] i32, spread [N] f64 with `want_spread` else None), N = starts[-1] + T,
+        device tensors.  `starts`: host integers, checked with `sequence.check_cover` and uploaded, or an int32 device tensor the caller
+        vouches for (its last entry is read back for N).  No other synchronisation."""
+        from .sequence import check_cover
+        w = self._f64(windows)
+        if w.dim() != 4 or w.shape[3] != 3 or not 1 <= w.shape[2] <= 16 or w.shape[1] < 1 or w.shape[0] < 1:
+            raise ValueError("merge_cover: windows must be [B,T,J,3] with J <= 16, got %s" % (tuple(w.shape),))
+        B, T, J = w.shape[0], w.shape[1], w.shape[2]
+        if torch.is_tensor(starts) and starts.is_cuda:
+            if starts.dtype != torch.int32 or not starts.is_contiguous() or tuple(starts.shape) != (B,):
+                raise TypeError("merge_cover: device starts must be a contiguous int32 tensor [%d]" % B)
+            s_d, n = starts, int(starts[-1].item()) + T
+        else:
+            s = check_cover(starts.cpu().numpy() if torch.is_tensor(starts) else starts, T)
+            if len(s) != B:
+                raise ValueError("merge_cover: %d starts for %d windows" % (len(s), B))
+            if int(s[-1]) + T > 2 ** 31 - 1:
+                raise ValueError("merge_cover: window starts are 32-bit frame numbers")
+            s_d, n = torch.from_numpy(s.astype(np.int32)).to(self.device), int(s[-1]) + T
+        merged = torch.empty(n, J, 3, device=self.device, dtype=torch.float64)
+        smoothed = torch.empty_like(merged) if smooth else None
+        count = torch.empty(n, device=self.device, dtype=torch.int32)
+        spread = torch.empty(n, device=self.device, dtype=torch.float64) if want_spread else None
+        _capi.check(self.lib.gem_merge_cover(_ptr(w), _ptr(s_d), B, T, J, n, _ptr(merged), _ptr(smoothed), _ptr(count), _ptr(spread), _stream()),
+                    self.lib)
+        return merged, smoothed, count, spread
+
     def one_euro_filter(self, seq, times, n_chunks, params):
         """The reference's utils/one_euro_filter.py over `n_chunks` equally long sequences laid end to end (gem_one_euro): seq
         [n_chunks*F,15,3] f64 (any trailing shape), times [n_chunks*F] f64, params (min_cutoff, beta, d_cutoff) -> a device tensor

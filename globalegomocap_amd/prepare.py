@@ -264,6 +264,46 @@ class Recording:
     cams = property(lambda self: [c.cams for c in self.chunks])
     gt = property(lambda self: [c.gt for c in self.chunks])
 
+    def continuous(self):
+        """The recording as ONE chunk over [first start_frame, last end_frame) in the recording's frame: cameras
+        origins[k] @ cams_k[f] and `est_global` moved by origins[k] (float64, with torch where the chunks lie), `est_local` and the
+        heat-maps laid end to end as they are; `scale`, `scale_report`, `bridge_report` and `depth_report` carried over, `origins` one
+        identity.  Needs `origins` (a recording without ground truth: ValueError otherwise, as `to_recording_frame`) and chunks that
+        follow one another (ValueError).  A recording of one chunk is returned as it is."""
+        import torch
+        if len(self.chunks) == 1:
+            return self
+        if not self.chunks:
+            raise ValueError("a recording without chunks")
+        if self.origins is None:
+            raise ValueError("a recording with ground truth has no common frame: every chunk has its own SLAM scale")
+        for p, q in zip(self.chunks[:-1], self.chunks[1:]):
+            if p.end_frame != q.start_frame:
+                raise ValueError("the chunks must follow one another: [%d, %d) is followed by [%d, %d)" % (p.start_frame, p.end_frame, q.start_frame, q.end_frame))
+        origins = np.asarray(self.origins, dtype=np.float64)
+        if origins.shape != (len(self.chunks), 4, 4):
+            raise ValueError("%s origins for a recording of %d chunks" % (origins.shape, len(self.chunks)))
+        first = self.chunks[0]
+        tensor = lambda x, dtype: torch.as_tensor(x).to(dtype=dtype)      # noqa: E731
+        cams, est_global = [], []
+        for c, o in zip(self.chunks, origins):
+            k = tensor(c.cams, torch.float64)
+            o = torch.from_numpy(o).to(k.device)
+            cams.append(torch.matmul(o, k))
+            g = tensor(c.est_global, torch.float64).to(k.device)
+            est_global.append(torch.matmul(g, o[:3, :3].T) + o[:3, 3])
+
+        def cat(parts, like):          # (an array the chunks hold as numpy stays numpy)
+            whole = torch.cat([torch.as_tensor(p) for p in parts]).contiguous()
+            return whole if torch.is_tensor(like) else whole.cpu().numpy()
+        cams, est_global = cat(cams, first.cams), cat(est_global, first.est_global)
+        est_local, heat = cat(self.est_local, first.est_local), cat(self.heat, first.heat)
+        files = None
+        if any(c.heat_files is not None for c in self.chunks):
+            files = [x for c in self.chunks for x in (c.heat_files if c.heat_files is not None else [None] * c.n)]
+        one = RecordingChunk(self.chunks[0].start_frame, self.chunks[-1].end_frame, heat, est_local, est_global, cams, None, heat_files=files)
+        return Recording([one], np.eye(4)[None], self.scale, self.scale_report, self.bridge_report, self.depth_report)
+
     def chunk_dict(self, i):
         """Chunk i as the reference pickles it (:149-155): five keys in its order, every value a list of per-frame arrays;
         estimated_local_skeleton Fortran-ordered float64, estimated_global_skeleton and camera_pose_list C-ordered float64,
@@ -812,6 +852,22 @@ def prepare_sequence(slam_result_path, heatmap_dir, depth_dir, gt_path, total_st
         print_report(rec)
     if out_root is not None:
         rec.write_chunks(out_root)
+    return rec
+
+
+def prepare_continuous(slam_result_path, heatmap_dir, depth_dir, gt_path, total_start_frame, total_end_frame, fps=25, mat_start_frame=None,
+                       camera_model_path=None, verbose=True, scale=None, lag=None, tau=0.10, min_pairs=50, bridge=None, depth=None, bones=None,
+                       neck_depth=None, min_peak=None, peaks=None):
+    """`prepare_sequence` for a recording that is optimised as one motion (`continuous.optimize_continuous`): the
+    ONE span [total_start_frame, total_end_frame) as one chunk -- no chunk loop, so no tail is lost, and with a ground truth one Umeyama
+    scale over the whole span.  The other arguments as there.  -> a Recording that is continuous already."""
+    gt_or_scale(gt_path, scale)
+    depth_route(depth_dir, depth, bones, neck_depth, min_peak, peaks)
+    rec = prepare_spans(slam_result_path, heatmap_dir, depth_dir, gt_path, [(total_start_frame, total_end_frame)], fps,
+                        total_start_frame if mat_start_frame is None else mat_start_frame, camera_model_path, scale=scale, lag=lag, tau=tau,
+                        min_pairs=min_pairs, bridge=bridge, depth=depth, bones=bones, neck_depth=neck_depth, min_peak=min_peak, peaks=peaks)
+    if verbose:
+        print_report(rec)
     return rec
 
 

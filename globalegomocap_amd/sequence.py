@@ -86,6 +86,71 @@ def merge_dense(windows, stride, n_chunks=None):
     return out[0] if n_chunks is None else out
 
 
+def cover_starts(n_frames, seq_len=SEQ_LEN, stride=SEQ_LEN - OVERLAP):
+    """The window table of a recording optimised as one motion: range(0, N - seq_len + 1, stride), plus
+    N - seq_len when the last regular window ends before N, so that EVERY frame lies in a window.  1 <= stride <= seq_len - 2 and
+    N >= seq_len, else ValueError.  For N = stride * k + seq_len this is the regular table alone (`window_starts` at stride 8)."""
+    n_frames, seq_len, stride = int(n_frames), int(seq_len), int(stride)
+    if not 1 <= stride <= seq_len - 2:
+        raise ValueError("cover_starts: the stride is between 1 and %d frames, got %d" % (seq_len - 2, stride))
+    if n_frames < seq_len:
+        raise ValueError("cover_starts: %d frames cannot hold a %d-frame window" % (n_frames, seq_len))
+    starts = list(range(0, n_frames - seq_len + 1, stride))
+    if starts[-1] + seq_len < n_frames:
+        starts.append(n_frames - seq_len)
+    return np.asarray(starts, dtype=np.int32)
+
+
+def check_cover(starts, seq_len=SEQ_LEN):
+    """ValueError unless the windows [s, s + seq_len) of `starts` cover [0, starts[-1] + seq_len) without a hole, each start once and in
+    order: starts[0] == 0, strictly ascending, no step longer than seq_len.  -> the starts as an int64 array."""
+    s = np.asarray(starts).reshape(-1).astype(np.int64)
+    if len(s) == 0 or s[0] != 0:
+        raise ValueError("a window table starts at frame 0, got %s" % (s[:1].tolist(),))
+    step = np.diff(s)
+    if (step <= 0).any():
+        raise ValueError("window starts must be strictly ascending (starts %s are not)" % s[1:][step <= 0][:4].tolist())
+    if (step > seq_len).any():
+        raise ValueError("no %d-frame window covers the frames before the starts %s" % (seq_len, s[1:][step > seq_len][:4].tolist()))
+    return s
+
+
+def merge_cover(windows, starts, want_spread=False):
+    """Every frame the mean of ALL windows that cover it, for windows at any starts `check_cover` accepts (the definition
+    `WindowEngine.merge_cover` is held to): ((G_a + G_b) + ...) / count over the covering windows oldest first, in
+    float64; a frame's first window is taken as it is (0 + x would lose the sign of -0).  [B, T, J, 3] -> (merged [starts[-1] + T, J, 3],
+    count [N] int32); with want_spread also spread [N]: the largest Euclidean distance, over joints and covering windows, between a
+    window's joint and the merged joint -- how far the windows that cover a frame disagree about it; 0.0 where count is 1.  At
+    `window_starts` these are the bits of merge_batches, at a constant stride those of merge_dense."""
+    w = np.asarray(windows, dtype=np.float64)
+    if w.ndim != 4 or w.shape[3] != 3:
+        raise ValueError("merge_cover: windows must be [B, T, J, 3], got %s" % (w.shape,))
+    T = w.shape[1]
+    s = check_cover(starts, T)
+    if len(s) != w.shape[0]:
+        raise ValueError("merge_cover: %d starts for %d windows" % (len(s), w.shape[0]))
+    n = int(s[-1]) + T
+    out = np.empty((n,) + w.shape[2:], dtype=np.float64)
+    count = np.zeros(n, dtype=np.int32)
+    seen = 0          # frames below `seen` have been reached by a window before this one
+    for i, a in enumerate(s.tolist()):
+        old = max(0, min(seen - a, T))
+        out[a:a + old] += w[i, :old]
+        out[a + old:a + T] = w[i, old:]
+        count[a:a + T] += 1
+        seen = a + T
+    out /= count.reshape(-1, 1, 1)
+    if not want_spread:
+        return out, count
+    spread = np.zeros(n, dtype=np.float64)
+    for i, a in enumerate(s.tolist()):
+        d = w[i] - out[a:a + T]
+        d = d * d
+        spread[a:a + T] = np.maximum(spread[a:a + T], np.sqrt((d[..., 0] + d[..., 1]) + d[..., 2]).max(axis=1))
+    spread[count == 1] = 0.0
+    return out, count, spread
+
+
 def final_smooth(seq):
     """scipy gaussian_filter1d(sigma=1, axis=0) (optimizer.py:448-450)."""
     from scipy.ndimage import gaussian_filter1d

@@ -22,6 +22,9 @@ chunk to `DIR/<chunk name>/result_pose.pkl` on either route; `save=True` / `--sa
 under the reprojected skeletons; `bvh=DIR` / `--bvh DIR` writes every chunk's sequences as BVH animation files
 (`bvh`); `video=DIR` / `--video DIR` and `video_camera=DIR` / `--video_camera DIR` write the frames of `render` and
 of `render_camera` as one Motion-JPEG clip per chunk, encoded on the device (`video`).
+
+A chunk is the unit of everything here, as in the reference.  A recording as ONE motion -- every frame optimised, one world, one set of
+files -- is `continuous.optimize_continuous` (`optimize_recording(..., continuous=True)`).
 """
 import ctypes as C
 import os
@@ -665,8 +668,15 @@ def optimize_recordings(recordings, camera_model_path, *args, **kwargs):
     return _Pipeline(groups, cfg, lap).run(titles)
 
 
-def optimize_recording(recording, camera_model_path, *args, **kwargs):
-    """One `prepare.Recording` = `optimize_directory` on the chunks it would write.  Arguments and result as there."""
+def optimize_recording(recording, camera_model_path, *args, continuous=False, stride=None, **kwargs):
+    """One `prepare.Recording` = `optimize_directory` on the chunks it would write.  Arguments and result as there.  continuous=True (by
+    keyword, with `stride`): the recording as ONE motion instead, every frame optimised in one world (`continuous.optimize_continuous`,
+    DESIGN.md section 6s)."""
+    if continuous:
+        from .continuous import optimize_continuous
+        return optimize_continuous(recording, camera_model_path, *args, **({} if stride is None else {"stride": stride}), **kwargs)
+    if stride is not None:
+        raise ValueError("stride belongs to continuous=True")
     return optimize_recordings([recording], camera_model_path, *args, **kwargs)[0]
 
 
@@ -687,20 +697,41 @@ def release_pools():
         torch.cuda.empty_cache()
 
 
+def _truthy(x):
+    """The reference's own flag parser."""
+    return str(x).lower() == "true"
+
+
 def _parser():
     import argparse
     from .camera import DEFAULT_CALIBRATION
-    truthy = lambda x: str(x).lower() == "true"          # noqa: E731  (the reference's own flag parser)
     p = argparse.ArgumentParser(description="Data directory number")
     p.add_argument("--data_path", required=True, type=str)
     p.add_argument("--camera", type=str, default=DEFAULT_CALIBRATION)
+    add_weight_options(p)
+    add_output_options(p)
+    p.add_argument("--final_smooth", default=True, type=_truthy)
+    p.add_argument("--merge", default=True, type=_truthy)
+    p.add_argument("--chunks_per_batch", type=int, default=None, help="chunks optimised per device call (default: all)")
+    p.add_argument("--ground_truth", default=True, type=_truthy, help="false: chunks without gt_global_skeleton, the report without ground truth")
+    p.add_argument("--save_pose", default=None, metavar="DIR", help="write DIR/<chunk name>/result_pose.pkl per chunk")
+    return p
+
+
+def add_weight_options(p):
+    """The energy weights of a command line that optimises (`whole_sequence`, `continuous`), the reference's flags."""
     p.add_argument("--vae", type=float, default=0.00)
     p.add_argument("--gmm", type=float, default=0.00)
     p.add_argument("--smooth", type=float, default=0.001)
     p.add_argument("--bone_length", type=float, default=0.01)
     p.add_argument("--weight_3d", type=float, default=0.01)
     p.add_argument("--reproj_weight", type=float, default=0.01)
-    p.add_argument("--save", default=False, type=truthy, help="true: write every chunk's skeleton meshes (PLY) under --mesh_root")
+
+
+def add_output_options(p):
+    """The files a command line that optimises may write, and how: the options of `report.Outputs` (`check_output_options`,
+    `output_arguments`)."""
+    p.add_argument("--save", default=False, type=_truthy, help="true: write every chunk's skeleton meshes (PLY) under --mesh_root")
     p.add_argument("--mesh_root", default="out", metavar="DIR", help="where --save true writes <dataset>/<chunk>/<folder>/out_%%04d.ply")
     p.add_argument("--render", default=None, metavar="DIR", help="write every chunk's frames as DIR/<dataset>/<chunk>/frame_%%04d.png")
     p.add_argument("--render_camera", default=None, metavar="DIR",
@@ -714,39 +745,43 @@ def _parser():
     p.add_argument("--video_camera", default=None, metavar="DIR", help="write every chunk as its camera saw it as one clip, DIR/<dataset>/<chunk>/camera.avi")
     p.add_argument("--video_fps", default=None, type=float, metavar="F", help="frames per second of the clips (default 25)")
     p.add_argument("--video_quality", default=None, type=int, metavar="Q", help="JPEG quality of the clips, 1 .. 100 (default 90)")
-    p.add_argument("--upright", default=False, type=truthy,
+    p.add_argument("--upright", default=False, type=_truthy,
                    help="true: the meshes, frames, clip and BVH files stand upright on the ground estimated from every chunk's foot contacts")
     p.add_argument("--foot_height", default=None, type=float, metavar="M", help="with --upright true: metres a standing foot point lies above the floor (default 0)")
-    p.add_argument("--foot_lock", default=False, type=truthy,
+    p.add_argument("--foot_lock", default=False, type=_truthy,
                    help="true: the meshes, frames, clip and BVH files show the optimised sequence with its standing feet pinned and the legs re-solved")
     p.add_argument("--foot_lock_stretch", default=None, type=float, metavar="S",
                    help="with --foot_lock true: how much longer a straight leg may become to hold its pin (default 0.05)")
     p.add_argument("--foot_lock_blend", default=None, type=int, metavar="FRAMES",
                    help="with --foot_lock true: frames over which a correction is eased in and out (default: 0.12 s)")
-    p.add_argument("--final_smooth", default=True, type=truthy)
-    p.add_argument("--merge", default=True, type=truthy)
-    p.add_argument("--chunks_per_batch", type=int, default=None, help="chunks optimised per device call (default: all)")
-    p.add_argument("--ground_truth", default=True, type=truthy, help="false: chunks without gt_global_skeleton, the report without ground truth")
-    p.add_argument("--save_pose", default=None, metavar="DIR", help="write DIR/<chunk name>/result_pose.pkl per chunk")
-    return p
 
 
-def _cli(argv=None):
-    p = _parser()
-    a = p.parse_args(argv)
+def check_output_options(p, a):
+    """The rules of `add_output_options`, as parser errors."""
     if a.video_fps is not None and not a.video_fps > 0:
         p.error("argument --video_fps: must be positive")
     if a.video_quality is not None and not 1 <= a.video_quality <= 100:
         p.error("argument --video_quality: a whole number 1 .. 100")
     if a.gltf_fps is not None and not (np.isfinite(a.gltf_fps) and a.gltf_fps > 0):
         p.error("argument --gltf_fps: must be positive")
+
+
+def output_arguments(a):
+    """The parsed options of `add_output_options` as keyword arguments of `optimize_sequences`."""
+    return dict(save=a.save, mesh_root=a.mesh_root, render=a.render, render_camera=a.render_camera, bvh=a.bvh, bvh_fps=a.bvh_fps, video=a.video,
+                video_camera=a.video_camera, video_fps=a.video_fps, video_quality=a.video_quality,
+                **(dict(upright=True, foot_height=a.foot_height) if a.upright else {}),
+                **(dict(foot_lock=True, foot_lock_stretch=a.foot_lock_stretch, foot_lock_blend=a.foot_lock_blend) if a.foot_lock else {}),
+                **(dict(gltf=a.gltf, gltf_fps=a.gltf_fps) if a.gltf is not None else {}))
+
+
+def _cli(argv=None):
+    p = _parser()
+    a = p.parse_args(argv)
+    check_output_options(p, a)
     optimize_directory(a.data_path, a.camera, a.vae, a.gmm, a.smooth, a.bone_length, a.weight_3d, a.reproj_weight,
                        final_smooth=a.final_smooth, merge=a.merge, chunks_per_batch=a.chunks_per_batch, ground_truth=a.ground_truth,
-                       save_pose=a.save_pose, save=a.save, mesh_root=a.mesh_root, render=a.render, render_camera=a.render_camera, bvh=a.bvh,
-                       bvh_fps=a.bvh_fps, video=a.video, video_camera=a.video_camera, video_fps=a.video_fps, video_quality=a.video_quality,
-                       **(dict(upright=True, foot_height=a.foot_height) if a.upright else {}),
-                       **(dict(foot_lock=True, foot_lock_stretch=a.foot_lock_stretch, foot_lock_blend=a.foot_lock_blend) if a.foot_lock else {}),
-                       **(dict(gltf=a.gltf, gltf_fps=a.gltf_fps) if a.gltf is not None else {}))
+                       save_pose=a.save_pose, **output_arguments(a))
 
 
 if __name__ == "__main__":

@@ -1086,6 +1086,22 @@ int gem_slam_bridge(const double* d_poses, const unsigned char* h_tracked, const
                     int64_t n, double* d_G, double* d_cams, double* d_origins, unsigned char* d_bridged, double* d_work, int64_t work_bytes,
                     double* d_record, void* stream);
 
+/* ---- A recording optimised as one continuous motion: merging windows that are not equally spaced ----
+ * d_windows [n_windows,T,n_joints,3] float64, d_starts [n_windows] the windows' first frames, ascending.  d_merged [n_frames,n_joints,3]:
+ * every frame the mean of ALL windows that cover it, ((G_a + G_b) + ...) / count over the covering windows oldest first, a frame's
+ * first window taken as it is (a -0.0 survives); at equally spaced starts these are the bits of gem_merge_windows (smoothing off) and
+ * of gem_merge_dense.  d_count [n_frames] (may be NULL): the number of covering windows.  d_spread [n_frames] (may be NULL): the
+ * largest Euclidean distance, over joints and covering windows, between a window's joint and the merged joint, 0 where count is 1.
+ * d_smooth (may be NULL; the shape of d_merged, another buffer): gaussian_filter1d(sigma=1, mode='reflect', truncate=4) of d_merged along
+ * the frames, by the kernel gem_merge_windows smooths with, in a second launch.  A frame no window covers gets NaN, count 0 and spread
+ * NaN.  The kernel is safe whatever the table holds (every read is guarded, a frame looks at no more than T windows); that the table
+ * covers the frames without a hole is the caller's to check (sequence.check_cover).  Refused before any launch, with the reason in
+ * gem_last_error: NULL d_windows, d_starts or d_merged, T < 1, n_joints outside 1 .. GEM_MAX_JOINTS, a negative size, more than 2^40
+ * / (3 T n_joints) windows, more than 2^33 frames (2^30 with d_smooth).  One wavefront per frame, no atomics: a frame's bytes do not
+ * depend on the launch.  Asynchronous on `stream`; works on the current device. */
+int gem_merge_cover(const double* d_windows, const int32_t* d_starts, int64_t n_windows, int T, int n_joints, int64_t n_frames,
+                    double* d_merged, double* d_smooth, int32_t* d_count, double* d_spread, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
