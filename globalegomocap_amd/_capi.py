@@ -90,6 +90,14 @@ SCALE_CANDIDATES, SCALE_TILE, SCALE_REPORT_DOUBLES = 513, 256, 16
 SCALE_NO_PAIRS, SCALE_TOO_FEW, SCALE_BAD_SCALE = 2, 3, 4
 
 
+class GemDriftReport(C.Structure):
+    _fields_ = [(k, C.c_double) for k in ("status", "n_knots", "knot", "stiffness", "inliers", "informative", "residual_rms", "scale_min",
+                                          "scale_max", "scale_mean", "metric_length", "slam_length", "lam", "first_id", "bad_pivot", "informed")]
+
+
+DRIFT_MAX_KNOTS, DRIFT_REPORT_DOUBLES, DRIFT_NOT_SOLVED = 2048, 16, 5
+
+
 class GemBoneDepthOpts(C.Structure):
     _fields_ = [("bone", C.c_double * GEM_MAX_JOINTS), ("dbar", C.c_double * GEM_MAX_JOINTS), ("neck_depth", C.c_double), ("w_n", C.c_double),
                 ("w_m", C.c_double), ("iters", C.c_int32), ("reserved", C.c_int32)]
@@ -241,6 +249,9 @@ SIGNATURES = {
     "gem_slam_scale_work": (C.c_int64, [C.c_int64, C.c_int, C.c_int]),
     "gem_slam_scale": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(C.c_int), _P, _P, _P, C.c_int64, C.c_int, C.c_double, C.c_int, _P,
                                  C.c_int64, _P, _P, _P, _P]),
+    "gem_slam_drift_work": (C.c_int64, [C.c_int64, C.c_int, C.c_int]),
+    "gem_slam_drift": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(C.c_int), _P, _P, _P, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_double,
+                                 C.c_int, C.c_int, C.c_double, _P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "gem_ground_plane_work": (C.c_int64, [_P, C.c_int, _P]),
     "gem_ground_plane": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, C.c_double, _P, C.c_int64, _P, _P]),
     "gem_similarity_compose": (C.c_int, [_P, _P, _P, C.c_int64, _P]),

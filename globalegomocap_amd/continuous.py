@@ -163,7 +163,10 @@ def _parser():
     how = p.add_mutually_exclusive_group(required=True)
     how.add_argument("--gt", default=None, help="ground-truth pickle: ONE scale is fitted over the whole span, and the 18 errors are reported")
     how.add_argument("--scale", type=scale_arg, default=None, help="the SLAM scale of a recording without ground truth (a metric SLAM: 1), "
-                                                                  "or `auto`: estimate it from the foot contacts")
+                                                                  "`auto`: estimate it from the foot contacts, or `drift`: follow a "
+                                                                  "scale that creeps over the recording")
+    from .slam_scale import add_drift_options
+    add_drift_options(p)
     p.add_argument("--bridge", nargs="?", type=float, const=1.0, default=None, metavar="SECONDS",
                    help="with --scale: invent the cameras of stretches of lost SLAM tracking up to this long (default 1 s)")
     p.add_argument("--start", required=True, type=int)
@@ -200,6 +203,8 @@ def parse_args(argv=None):
         if a.depth_from is None and (a.bones is not None or a.neck_depth is not None):
             p.error("--bones and --neck_depth belong to --depth_from bones")
     ws.check_output_options(p, a)
+    from .slam_scale import drift_options
+    a.drift = drift_options(p, a)
     return a
 
 
@@ -209,12 +214,12 @@ def _cli(argv=None):
     a = parse_args(argv)
     if a.heatmaps is not None:
         rec = prepare.prepare_continuous(a.slam, a.heatmaps, a.depths, a.gt, a.start, a.end, a.fps, a.mat_start, a.camera, scale=a.scale, bridge=a.bridge,
-                                         depth=a.depth_from, bones=bones_from_args(a), neck_depth=a.neck_depth, min_peak=a.min_peak, peaks=a.peaks)
+                                         depth=a.depth_from, bones=bones_from_args(a), neck_depth=a.neck_depth, min_peak=a.min_peak, peaks=a.peaks, **a.drift)
     else:
         a.first_id = 0 if a.first_id is None else a.first_id
         rec = detections.continuous_from_detections(a.slam, detections.detections_from_args(a), a.gt, a.scale, a.start, a.end, a.fps, depth=a.depth_from,
                                                     sigma=1.5 if a.sigma is None else a.sigma, camera_model_path=a.camera, gt_start_frame=a.mat_start,
-                                                    bridge=a.bridge, bones=bones_from_args(a), neck_depth=a.neck_depth)
+                                                    bridge=a.bridge, bones=bones_from_args(a), neck_depth=a.neck_depth, **a.drift)
         prepare.print_report(rec)
     optimize_continuous(rec, a.camera, a.vae, a.gmm, a.smooth, a.bone_length, a.weight_3d, a.reproj_weight, final_smooth=a.final_smooth,
                         ground_truth=a.scale is None, save_pose=a.save_pose, stride=a.stride, **ws.output_arguments(a))

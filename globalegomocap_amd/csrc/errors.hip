@@ -452,6 +452,7 @@ int launch_lift(gem_handle* h, const float* heat, const double* depth, int F, co
 #include "bone_depth.h"                // gem_bone_depths
 #include "heat_peaks.h"                // gem_heatmap_peaks
 #include "slam_scale.h"                // gem_slam_scale_work, gem_slam_scale
-#include "ground.h"                    // gem_ground_plane_work, gem_ground_plane, gem_similarity_compose
+#include "slam_drift.h"                // gem_slam_drift_work, gem_slam_drift
+#include "ground.h"                  // gem_ground_plane_work, gem_ground_plane, gem_similarity_compose
 #include "foot_lock.h"                 // gem_foot_lock_work, gem_foot_lock
 #include "merge_cover.h"               // gem_merge_cover

@@ -11,7 +11,7 @@ u, v are pixels of the fisheye image the calibration describes (1280 x 1024).  A
 and u, v are finite; a joint that is unusable in a frame gets a blank heat-map there and the pose interpolated in time from its
 usable neighbours inside the chunk.  A joint with no usable detection in a whole chunk is a ValueError.
 
-    python -m globalegomocap_amd.detections --slam traj.txt --keypoints det.npz --scale 1.0|auto --start 0 --end 2001 --fps 25 \\
+    python -m globalegomocap_amd.detections --slam traj.txt --keypoints det.npz --scale 1.0|auto|drift --start 0 --end 2001 --fps 25 \\
         [--depths DIR | --depth FILE.npy | --depth_from bones [--bones FILE.npy] [--neck_depth M]] [--sigma 1.5] [--first_id 0] [--test_size 100] [--out DIR] [--optimize] [--camera JSON]
 """
 import os
@@ -131,7 +131,7 @@ def detections_from_args(a):
 # ------------------------------------------------------------------------------------------------------------------ the device path
 def recording_from_detections(slam_result_path, detections, gt_path=None, scale=None, spans=(), fps=25, depth=None, sigma=1.5, first_id=0,
                               camera_model_path=None, device=None, gt_start_frame=None, lag=None, tau=0.10, min_pairs=50, bridge=None,
-                              bones=None, neck_depth=None):
+                              bones=None, neck_depth=None, knot=None, stiffness=1.0):
     """Every (start_frame, end_frame) of `spans` as one chunk of a `prepare.Recording`, from 2-D detections: `detections` is a file
     (`read_detections`), an array [N,15,2|3] or `as_detections`' dict; `depth` [N,15] unless the file carries it, or "bones": the
     depths are solved on the device from the bone lengths (`WindowEngine.bone_depths` with `bone_depth.options(bones,
@@ -139,12 +139,13 @@ def recording_from_detections(slam_result_path, detections, gt_path=None, scale=
     Recording carries the solve's `depth_report`.  Exactly one of
     `gt_path` (the ground truth fixes the SLAM scale per chunk, as `prepare` does; entry i - gt_start_frame of the pickle is frame id
     i, gt_start_frame defaulting to the first span's start) and `scale`: a number, or "auto" to estimate it from the foot contacts of
-    the filled poses (`prepare.auto_scale` with `lag`, `tau`, `min_pairs`).  One upload, then on the device:
+    the filled poses (`prepare.auto_scale` with `lag`, `tau`, `min_pairs`), or "drift" to follow a scale that creeps
+    over the recording (`knot` frames between the curve's knots, `stiffness`).  One upload, then on the device:
     lift -> fill -> heat-maps -> cameras -> gem_prepare_global; from the filled poses on this is `prepare.RecordingStage`.  `bridge`:
     None, or the seconds of lost SLAM tracking whose cameras are invented (`slam_bridge`), without ground truth
     only."""
     from . import prepare
-    stage = prepare.RecordingStage(gt_path, scale, bridge, spans, fps, lag, tau, min_pairs)
+    stage = prepare.RecordingStage(gt_path, scale, bridge, spans, fps, lag, tau, min_pairs, knot, stiffness)
     import torch
     from .camera import DEFAULT_CALIBRATION
     if isinstance(detections, (str, os.PathLike)):
@@ -240,12 +241,13 @@ def _cli(argv=None):
     from . import prepare
     from .bone_depth import bones_from_args
     p = _parser()
+    from .slam_scale import drift_options
     a = prepare.parse_recording_options(p, argv)
     if a.depth_from is None and (a.bones is not None or a.neck_depth is not None):
         p.error("--bones and --neck_depth belong to --depth_from bones")
     rec = recording_from_detections(a.slam, detections_from_args(a), a.gt, a.scale, prepare.chunk_spans(a.start, a.end, a.test_size), a.fps,
                                     depth=a.depth_from, sigma=a.sigma, camera_model_path=a.camera, gt_start_frame=a.mat_start, bridge=a.bridge,
-                                    bones=bones_from_args(a), neck_depth=a.neck_depth)
+                                    bones=bones_from_args(a), neck_depth=a.neck_depth, **drift_options(p, a))
     prepare.print_report(rec)
     if a.out is not None:
         rec.write_chunks(a.out)

@@ -30,7 +30,8 @@ listing with fewer files than the range asks for.
 
 A recording without ground truth gives the SLAM scale instead -- 1 for a metric SLAM, a number the user
 knows, or `auto` for a monocular SLAM, whose scale is then estimated from the recording's own foot contacts before the cameras are
-made (`slam_scale`): `--scale S|auto` in place of `--gt`, `scale=` in place of `gt_path=`.  The cameras of a chunk are then the reference's
+made (`slam_scale`), or `drift` for one whose scale creeps over the recording: the scale is then a curve and the
+trajectory is rebuilt in metres first: `--scale S|auto|drift` in place of `--gt`, `scale=` in place of `gt_path=`.  The cameras of a chunk are then the reference's
 `SLAMReader.read_trajectory(path, start, end, scale)` (`slam.scaled_trajectory`), the chunks carry no ground truth, their pickles
 no `gt_global_skeleton`, and since one scale holds for the whole recording its chunks share a world: `Recording.origins`,
 `to_recording_frame`.
@@ -119,8 +120,8 @@ def gt_or_scale(gt_path, scale):
         raise ValueError("give exactly one of gt_path (the ground truth fixes the SLAM scale) and scale (a recording without ground truth)")
     if scale is None:
         return None
-    if isinstance(scale, str) and scale == "auto":
-        return "auto"
+    if isinstance(scale, str) and scale in ("auto", "drift"):
+        return scale
     scale = float(scale)
     if not (np.isfinite(scale) and scale > 0):
         raise ValueError("the SLAM scale must be a positive number, got %r" % scale)
@@ -236,7 +237,8 @@ class Recording:
     """The chunks of one recording, device-resident.  `heat`, `est_local`, `est_global`, `cams`, `gt`: one tensor per chunk.
     `origins` [n_chunks,4,4] float64 (numpy) for a recording without ground truth, whose chunks share a world (`scaled_cameras`,
     `to_recording_frame`); None for a recording with ground truth.  `scale` and `scale_report` (`slam_scale.ScaleEstimate`): the SLAM
-    scale a recording prepared with scale="auto" was given and how it was found; None on the other routes.  `bridge_report`
+    scale a recording prepared with scale="auto" was given and how it was found; with scale="drift" the `slam_scale.DriftEstimate` and
+    its `scale_mean`; None on the other routes.  `bridge_report`
     (`slam_bridge.BridgeReport`) and `bridged` (one bool array per chunk: the frames whose camera was invented) for a recording prepared
     with `bridge=`; None without.  `depth_report` (`bone_depth.BoneDepthReport`) for a recording of detections whose depths were solved
     from the bone lengths; None on every other route."""
@@ -586,10 +588,14 @@ def prepare_global(est_local, cams, gt):
     return out, err
 
 
-def auto_scale(est_local, rows, spans, fps, scale, lag=None, tau=0.10, min_pairs=50, tracked=False):
+def auto_scale(est_local, rows, spans, fps, scale, lag=None, tau=0.10, min_pairs=50, tracked=False, knot=None, stiffness=1.0):
     """`scale` as a number -> (scale, None).  "auto" -> (the estimate, its `slam_scale.ScaleEstimate`): `gem_slam_scale` on the lifted
     poses where they lie (`tracked`: on the tracked frames of a trajectory that lacks lines), one small record back; ValueError when
-    the recording does not fix the scale."""
+    the recording does not fix the scale.  "drift" -> (1.0, a `slam_scale.DriftEstimate`): the scale as a curve with knots `knot` frames
+    apart, whose `metric_rows()` are the trajectory in metres -- the caller goes on with those rows at scale 1."""
+    if isinstance(scale, str) and scale == "drift":
+        from .slam_scale import estimate_drift
+        return 1.0, estimate_drift(est_local, rows, spans, fps, knot=knot, stiffness=stiffness, lag=lag, tau=tau, min_pairs=min_pairs, tracked=tracked)
     if not (isinstance(scale, str) and scale == "auto"):
         return scale, None
     from .slam_scale import estimate_scale
@@ -604,12 +610,12 @@ class RecordingStage:
     without ground truth) for its chunks, and then calls `fix_scale` and `recording` -- two steps, because a route may enqueue device
     work between them that the host's camera work then overlaps (the detection route's heat-maps)."""
 
-    def __init__(self, gt_path, scale, bridge, spans, fps, lag=None, tau=0.10, min_pairs=50):
+    def __init__(self, gt_path, scale, bridge, spans, fps, lag=None, tau=0.10, min_pairs=50, knot=None, stiffness=1.0):
         from .slam_bridge import bridge_arg
         self.gt_path, self.scale = gt_path, gt_or_scale(gt_path, scale)
         self.bridge = bridge_arg(bridge, gt_path)
         self.spans, self.fps = [(int(a), int(b)) for a, b in spans], fps
-        self.lag, self.tau, self.min_pairs = lag, tau, min_pairs
+        self.lag, self.tau, self.min_pairs, self.knot, self.stiffness = lag, tau, min_pairs, knot, stiffness
         self.rows = self.systems = self.bounds = self.gts = None
         self.cams = self.origins = self.scale_report = self.bridge_report = None
 
@@ -640,12 +646,16 @@ class RecordingStage:
     def fix_scale(self, engine, est_local, lap=Laps(None)):
         """Everything that can still refuse the recording, and everything that needs a read-back before the cameras exist: "auto"
         becomes a number and a `slam_scale.ScaleEstimate` (with `bridge` from the tracked frames only; ValueError when the recording
-        does not fix the scale), and with `bridge` the bridged cameras, the origins and the `slam_bridge.BridgeReport` are made; the
-        cameras stay on the device.  Nothing to do with ground truth."""
+        does not fix the scale), "drift" becomes the number 1, a `slam_scale.DriftEstimate` and the trajectory in metres in place of
+        `rows` (DESIGN.md section 6t), and with `bridge` the bridged cameras, the origins and the `slam_bridge.BridgeReport` are made;
+        the cameras stay on the device.  Nothing to do with ground truth."""
         if self.scale is None:
             return
+        drift = isinstance(self.scale, str) and self.scale == "drift"
         self.scale, self.scale_report = auto_scale(est_local, self.rows, self.spans, self.fps, self.scale, self.lag, self.tau, self.min_pairs,
-                                                   tracked=self.bridge is not None)
+                                                   tracked=self.bridge is not None, knot=self.knot, stiffness=self.stiffness)
+        if drift:          # from here on the trajectory is the metric one, at scale 1
+            self.rows = self.scale_report.metric_rows()
         if self.bridge is not None:
             from .slam_bridge import bridge_cameras
             self.cams, self.origins, self.bridge_report = bridge_cameras(engine, self.rows, self.spans, self.fps, self.scale, self.bridge,
@@ -684,7 +694,8 @@ class RecordingStage:
                                          gt_list=None if gt_d is None else self.gts[k],
                                          heat_files=kept if kept is not None and any(x is not None for x in kept) else None,
                                          initial_mpjpe=None if err is None else float(np.mean(err[lo:hi]))))
-        return Recording(chunks, self.origins, self.scale if self.scale_report is not None else None, self.scale_report, self.bridge_report)
+        return Recording(chunks, self.origins, float(self.scale_report.scale) if self.scale_report is not None else None, self.scale_report,
+                         self.bridge_report)
 
 
 def print_report(rec, sequence=True):
@@ -759,12 +770,14 @@ def lift_peaks(engine, heat, depth, bounds, spans, bone_opts=None, min_peak=0.0)
 
 def prepare_spans(slam_result_path, heatmap_dir, depth_dir, gt_path, spans, fps, mat_start_frame, camera_model_path=None, device=None,
                   timings=None, scale=None, lag=None, tau=0.10, min_pairs=50, bridge=None, depth=None, bones=None, neck_depth=None,
-                  min_peak=None, peaks=None):
+                  min_peak=None, peaks=None, knot=None, stiffness=1.0):
     """Every (start_frame, end_frame) of `spans` as one chunk, each prepared on its own as `main` does, all of them through the
     device together: stage -> gem_mat_frames -> lift -> head joints to the host -> per-chunk scale and cameras -> cameras up ->
     gem_prepare_global.  -> Recording.  `gt_path` None and `scale` given: a recording without ground truth -- the cameras come from
     `scaled_cameras`, nothing goes to the host in between, `mat_start_frame` is not used.  scale="auto": the scale is estimated from the
     lifted poses first (`auto_scale` with `lag`, `tau`, `min_pairs`; one small record comes back), then the same path runs with it.
+    scale="drift": the scale is a curve with knots `knot` frames apart (`stiffness`: of its second differences); the trajectory is rebuilt
+    in metres (`slam_scale.DriftEstimate.metric_rows`) and the same path runs with it at scale 1.
     `bridge`: None, or the longest stretch of lost SLAM tracking, in seconds, whose cameras are invented (True: 1 s; `slam_bridge`,
     DESIGN.md section 6o) -- only without ground truth, and the chunks must follow one another.  From the lifted poses on this is
     `RecordingStage`.
@@ -774,7 +787,7 @@ def prepare_spans(slam_result_path, heatmap_dir, depth_dir, gt_path, spans, fps,
     and the Recording carries the solve's `depth_report`.  Its heat-maps are the files' own.  peaks="subpixel" with a depth directory:
     the network's depths, lifted at the sub-pixel peak instead of the reference's 16-pixel argmax."""
     from_bones, subpixel, bone_opts, min_peak = depth_route(depth_dir, depth, bones, neck_depth, min_peak, peaks)
-    stage = RecordingStage(gt_path, scale, bridge, spans, fps, lag, tau, min_pairs)
+    stage = RecordingStage(gt_path, scale, bridge, spans, fps, lag, tau, min_pairs, knot, stiffness)
     import torch
     from .camera import DEFAULT_CALIBRATION
     lap = Laps(timings)          # developer timing (tools/prepare_bench.py)
@@ -818,7 +831,7 @@ def prepare_spans(slam_result_path, heatmap_dir, depth_dir, gt_path, spans, fps,
 
 def main(slam_result_path, heatmap_dir, depth_dir, gt_path, start_frame, end_frame, out_dir, fps, mat_start_frame=None,
          camera_model_path=None, scale=None, lag=None, tau=0.10, min_pairs=50, bridge=None, depth=None, bones=None, neck_depth=None,
-         min_peak=None, peaks=None):
+         min_peak=None, peaks=None, knot=None, stiffness=1.0):
     """The reference's `main` (:126-165): one chunk [start_frame, end_frame) -> `<out_dir>/test_data.pkl`, and the line
     `The initial mpjpe is: ...`.  Returns the one-chunk Recording (the reference returns nothing).  Without ground truth (`gt_path`
     None, `scale` given) the pickle has four keys and there is no such line; with scale="auto" one line tells the estimate and its
@@ -826,7 +839,7 @@ def main(slam_result_path, heatmap_dir, depth_dir, gt_path, start_frame, end_fra
     `min_peak`, `peaks`: `prepare_spans`' (depth="bones" with depth_dir None: a recording without depth files)."""
     rec = prepare_spans(slam_result_path, heatmap_dir, depth_dir, gt_path, [(start_frame, end_frame)], fps,
                         start_frame if mat_start_frame is None else mat_start_frame, camera_model_path, scale=scale, lag=lag, tau=tau,
-                        min_pairs=min_pairs, bridge=bridge, depth=depth, bones=bones, neck_depth=neck_depth, min_peak=min_peak, peaks=peaks)
+                        min_pairs=min_pairs, knot=knot, stiffness=stiffness, bridge=bridge, depth=depth, bones=bones, neck_depth=neck_depth, min_peak=min_peak, peaks=peaks)
     print_report(rec, sequence=False)
     rec.write_chunk(0, out_dir)
     return rec
@@ -834,7 +847,7 @@ def main(slam_result_path, heatmap_dir, depth_dir, gt_path, start_frame, end_fra
 
 def prepare_sequence(slam_result_path, heatmap_dir, depth_dir, gt_path, total_start_frame, total_end_frame, fps=25, mat_start_frame=None,
                      test_size=100, out_root=None, camera_model_path=None, verbose=True, scale=None, lag=None, tau=0.10, min_pairs=50,
-                     bridge=None, depth=None, bones=None, neck_depth=None, min_peak=None, peaks=None):
+                     bridge=None, depth=None, bones=None, neck_depth=None, min_peak=None, peaks=None, knot=None, stiffness=1.0):
     """The reference's chunk loop (:176-190): chunks of `test_size` frames from `total_start_frame` (see `chunk_spans` for the
     chunk it drops), `mat_start_frame` defaulting to `total_start_frame` as there.  All chunks go through the device together,
     each prepared on its own.  Returns the Recording; with `out_root`, `data_start_{a}_end_{b}/test_data.pkl` are written too.
@@ -847,7 +860,7 @@ def prepare_sequence(slam_result_path, heatmap_dir, depth_dir, gt_path, total_st
     spans = chunk_spans(total_start_frame, total_end_frame, test_size)
     rec = prepare_spans(slam_result_path, heatmap_dir, depth_dir, gt_path, spans, fps,
                         total_start_frame if mat_start_frame is None else mat_start_frame, camera_model_path, scale=scale, lag=lag, tau=tau,
-                        min_pairs=min_pairs, bridge=bridge, depth=depth, bones=bones, neck_depth=neck_depth, min_peak=min_peak, peaks=peaks)
+                        min_pairs=min_pairs, knot=knot, stiffness=stiffness, bridge=bridge, depth=depth, bones=bones, neck_depth=neck_depth, min_peak=min_peak, peaks=peaks)
     if verbose:
         print_report(rec)
     if out_root is not None:
@@ -857,7 +870,7 @@ def prepare_sequence(slam_result_path, heatmap_dir, depth_dir, gt_path, total_st
 
 def prepare_continuous(slam_result_path, heatmap_dir, depth_dir, gt_path, total_start_frame, total_end_frame, fps=25, mat_start_frame=None,
                        camera_model_path=None, verbose=True, scale=None, lag=None, tau=0.10, min_pairs=50, bridge=None, depth=None, bones=None,
-                       neck_depth=None, min_peak=None, peaks=None):
+                       neck_depth=None, min_peak=None, peaks=None, knot=None, stiffness=1.0):
     """`prepare_sequence` for a recording that is optimised as one motion (`continuous.optimize_continuous`): the
     ONE span [total_start_frame, total_end_frame) as one chunk -- no chunk loop, so no tail is lost, and with a ground truth one Umeyama
     scale over the whole span.  The other arguments as there.  -> a Recording that is continuous already."""
@@ -865,7 +878,7 @@ def prepare_continuous(slam_result_path, heatmap_dir, depth_dir, gt_path, total_
     depth_route(depth_dir, depth, bones, neck_depth, min_peak, peaks)
     rec = prepare_spans(slam_result_path, heatmap_dir, depth_dir, gt_path, [(total_start_frame, total_end_frame)], fps,
                         total_start_frame if mat_start_frame is None else mat_start_frame, camera_model_path, scale=scale, lag=lag, tau=tau,
-                        min_pairs=min_pairs, bridge=bridge, depth=depth, bones=bones, neck_depth=neck_depth, min_peak=min_peak, peaks=peaks)
+                        min_pairs=min_pairs, knot=knot, stiffness=stiffness, bridge=bridge, depth=depth, bones=bones, neck_depth=neck_depth, min_peak=min_peak, peaks=peaks)
     if verbose:
         print_report(rec)
     return rec
@@ -880,7 +893,10 @@ def add_recording_options(p):
     how = p.add_mutually_exclusive_group(required=True)
     how.add_argument("--gt", default=None, help="ground-truth pickle (it fixes the SLAM scale)")
     how.add_argument("--scale", type=scale_arg, default=None, help="the SLAM scale of a recording without ground truth (a metric SLAM: 1), "
-                                                                  "or `auto`: estimate it from the foot contacts")
+                                                                  "`auto`: estimate it from the foot contacts, or `drift`: follow a "
+                                                                  "scale that creeps over the recording")
+    from .slam_scale import add_drift_options
+    add_drift_options(p)
     p.add_argument("--bridge", nargs="?", type=float, const=1.0, default=None, metavar="SECONDS",
                    help="with --scale: invent the cameras of stretches of lost SLAM tracking up to this long (default 1 s)")
     p.add_argument("--start", required=True, type=int)
@@ -944,9 +960,10 @@ def _cli(argv=None):
     p = _parser()
     a = parse_recording_options(p, argv)
     check_depth_route_options(p, a)
+    from .slam_scale import drift_options
     rec = prepare_sequence(a.slam, a.heatmaps, a.depths, a.gt, a.start, a.end, a.fps, a.mat_start, a.test_size, a.out, a.camera,
                            scale=a.scale, bridge=a.bridge, depth=a.depth_from, bones=bones_from_args(a), neck_depth=a.neck_depth,
-                           min_peak=a.min_peak, peaks=a.peaks)
+                           min_peak=a.min_peak, peaks=a.peaks, **drift_options(p, a))
     if a.optimize:
         from .whole_sequence import optimize_recording
         optimize_recording(rec, a.camera, ground_truth=a.scale is None)

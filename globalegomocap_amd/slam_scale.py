@@ -7,10 +7,13 @@ stands does not move in the world -- so R_t x_t,foot + s c_t is constant over a 
 robust one-parameter fit on the device, over the lifted poses where they lie; one small record comes back.
 
     python -m globalegomocap_amd.slam_scale --slam traj.txt (--heatmaps DIR --depths DIR | --keypoints det.npz [--depths DIR | --depth FILE.npy]) \\
-        [--depth_from bones [--bones FILE.npy] [--neck_depth M] [--min_peak P] in place of the depths] --start A --end B --fps 25 [--lag K] [--tau M] [--min_pairs P] [--test_size 100] [--json FILE] [--gt gt.pkl]
+        [--depth_from bones [--bones FILE.npy] [--neck_depth M] [--min_peak P] in place of the depths] --start A --end B --fps 25 [--scale auto|drift [--knot S] [--stiffness W]] [--lag K] [--tau M] [--min_pairs P] [--test_size 100] [--json FILE] [--gt gt.pkl]
 
 `prepare --scale auto` and `detections --scale auto` (`scale="auto"`) call `estimate_scale` on the lifted poses and go on as if the
-number had been given.  "The wearer did not walk enough to fix the scale" is an answer: a ValueError naming the counts.
+number had been given.  `--scale drift [--knot SECONDS] [--stiffness W]` (`scale="drift"`) is for a SLAM whose
+scale creeps over the recording: `estimate_drift` fits a piecewise-linear scale curve to the same stance pairs with `gem_slam_drift`,
+rebuilds the camera track in metres, and the routes go on with that track as a metric SLAM's at scale 1.  "The wearer did not walk enough to fix the scale" is an answer: a ValueError naming
+the counts.
 """
 import ctypes as C
 import os
@@ -78,41 +81,53 @@ def selected_poses(rows_or_text, spans, fps):
     return slam.pose_matrix(rt, rq)[:, :3, :3], rt, ids
 
 
-def scale_call(chunks, R, c, ids, lag, tau=0.10, min_pairs=50, feet=None, stream=None, read_back=True):
-    """gem_slam_scale.  chunks: device tensors [n_k,J,3] f64, each its own allocation or not; R [N,3,3], c [N,3], ids [N] (host).
-    -> (return code, report as numpy [16 + 3 n_chunks] or the device tensor when not read_back, costs device tensor [513], message)."""
+def _call_inputs(chunks, R, c, ids, feet, who):
+    """What a device call checks of its inputs and lays out for its one upload -> (chunks, J, device, N, n_chunks, R, c, ids, feet,
+    table: the chunks' addresses and first rows)."""
     import torch
-    lib = _capi.load_library()
     chunks = list(chunks)
     for x in chunks:
         if not (x.is_cuda and x.dtype == torch.float64 and x.dim() == 3 and x.shape[2] == 3 and x.is_contiguous()):
-            raise ValueError("estimate_scale: the poses must be contiguous float64 device tensors [n,J,3]")
+            raise ValueError("%s: the poses must be contiguous float64 device tensors [n,J,3]" % who)
     J = int(chunks[0].shape[1])
     if any(int(x.shape[1]) != J for x in chunks):
-        raise ValueError("estimate_scale: the chunks differ in their number of joints")
-    device = chunks[0].device
+        raise ValueError("%s: the chunks differ in their number of joints" % who)
     starts = np.concatenate([[0], np.cumsum([len(x) for x in chunks])]).astype(np.int64)
     N, nc = int(starts[-1]), len(chunks)
     R, c = np.ascontiguousarray(R, dtype=np.float64), np.ascontiguousarray(c, dtype=np.float64)
     ids = np.ascontiguousarray(ids, dtype=np.int64)
     if R.shape != (N, 3, 3) or c.shape != (N, 3) or ids.shape != (N,):
-        raise ValueError("estimate_scale: %d frames of poses, but SLAM poses %s %s and frame ids %s" % (N, R.shape, c.shape, ids.shape))
+        raise ValueError("%s: %d frames of poses, but SLAM poses %s %s and frame ids %s" % (who, N, R.shape, c.shape, ids.shape))
     if not (np.isfinite(R).all() and np.isfinite(c).all()):
-        raise ValueError("estimate_scale: the SLAM poses hold values that are not finite")
+        raise ValueError("%s: the SLAM poses hold values that are not finite" % who)
     feet = FEET if feet is None else tuple(int(j) for j in feet)
     if len(feet) != 4:
-        raise ValueError("estimate_scale: feet = (right ankle, right foot, left ankle, left foot)")
+        raise ValueError("%s: feet = (right ankle, right foot, left ankle, left foot)" % who)
     table = np.concatenate([np.array([x.data_ptr() if len(x) else 0 for x in chunks], dtype=np.int64), starts])
+    return chunks, J, chunks[0].device, N, nc, R, c, ids, feet, table
+
+
+def _upload(table, ids, R, c, device):
+    """ONE upload: the chunk table, the frame ids and the SLAM poses -> (the tensor, and in it d_chunks, d_ids, d_rot, d_trans)"""
+    import torch
+    N = len(ids)
+    up = torch.from_numpy(np.concatenate([table, ids, R.reshape(-1).view(np.int64), c.reshape(-1).view(np.int64)])).to(device)
+    return up, up[:len(table)], up[len(table):len(table) + N], up[len(table) + N:len(table) + 10 * N], up[len(table) + 10 * N:]
+
+
+def scale_call(chunks, R, c, ids, lag, tau=0.10, min_pairs=50, feet=None, stream=None, read_back=True):
+    """gem_slam_scale.  chunks: device tensors [n_k,J,3] f64, each its own allocation or not; R [N,3,3], c [N,3], ids [N] (host).
+    -> (return code, report as numpy [16 + 3 n_chunks] or the device tensor when not read_back, costs device tensor [513], message)."""
+    import torch
+    lib = _capi.load_library()
+    chunks, J, device, N, nc, R, c, ids, feet, table = _call_inputs(chunks, R, c, ids, feet, "estimate_scale")
     need = int(lib.gem_slam_scale_work(max(N, 1), int(lag), nc))
     if need < 0:          # (sizes out of range: gem_slam_scale itself refuses them, with its own text)
         need = 8
     with torch.cuda.device(device):
         st = torch.cuda.current_stream() if stream is None else stream
         with torch.cuda.stream(st):
-            # ONE upload: the chunk table, the frame ids and the SLAM poses
-            up = torch.from_numpy(np.concatenate([table, ids, R.reshape(-1).view(np.int64), c.reshape(-1).view(np.int64)])).to(device)
-            d_chunks, d_ids = up[:len(table)], up[len(table):len(table) + N]
-            d_rot, d_trans = up[len(table) + N:len(table) + 10 * N], up[len(table) + 10 * N:]
+            up, d_chunks, d_ids, d_rot, d_trans = _upload(table, ids, R, c, device)
             work = torch.empty(need // 8 + 1, dtype=torch.float64, device=device)
             n_rep = _capi.SCALE_REPORT_DOUBLES + 3 * nc
             report = torch.zeros(n_rep, dtype=torch.float64, device=device)
@@ -146,6 +161,25 @@ def tracked_poses(est_local, rows, spans, fps):
     return [kept[lo:hi] for lo, hi in zip(cuts[:-1], cuts[1:])], R, rt, ids
 
 
+def _recording_inputs(est_local, rows_or_text, spans, fps, tracked, who):
+    """The estimators' inputs from a recording's lifted poses and trajectory -> ([poses per span], R, c, ids)."""
+    import torch
+    spans = [(int(a), int(b)) for a, b in spans]
+    if tracked:
+        return tracked_poses(est_local, rows_or_text, spans, fps)
+    if torch.is_tensor(est_local):
+        cuts = np.concatenate([[0], np.cumsum([b - a for a, b in spans])])
+        if int(cuts[-1]) != len(est_local):
+            raise ValueError("%s: %d frames of poses for spans of %d frames" % (who, len(est_local), int(cuts[-1])))
+        est_local = [est_local[lo:hi] for lo, hi in zip(cuts[:-1], cuts[1:])]
+    est_local = list(est_local)
+    if len(est_local) != len(spans) or any(len(x) != b - a for x, (a, b) in zip(est_local, spans)):
+        raise ValueError("%s: one tensor of end - start frames per span is needed" % who)
+    if not spans:
+        raise ValueError("%s: no frames, so no pairs (0 pairs, 0 inliers, 0 informative)" % who)
+    return (est_local,) + tuple(selected_poses(rows_or_text, spans, fps))
+
+
 def estimate_scale(est_local, rows_or_text, spans, fps, *, lag=None, tau=0.10, min_pairs=50, feet=None, stream=None, tracked=False):
     """The SLAM scale of the recording whose lifted poses are `est_local` -- one device tensor [n,15,3] float64 per span of `spans`
     [(start_frame, end_frame)], or ONE tensor holding them all in order -- and whose trajectory is `rows_or_text`
@@ -153,22 +187,7 @@ def estimate_scale(est_local, rows_or_text, spans, fps, *, lag=None, tau=0.10, m
     `tracked`: the trajectory lacks lines (`slam_bridge`); only the tracked rows and their poses are passed (`tracked_poses`), and
     since the estimator pairs rows where their frame ids lie `lag` apart, no pair reaches across a gap.
     -> ScaleEstimate; ValueError naming the counts when the recording does not fix the scale."""
-    import torch
-    spans = [(int(a), int(b)) for a, b in spans]
-    if tracked:
-        est_local, R, c, ids = tracked_poses(est_local, rows_or_text, spans, fps)
-    else:
-        if torch.is_tensor(est_local):
-            cuts = np.concatenate([[0], np.cumsum([b - a for a, b in spans])])
-            if int(cuts[-1]) != len(est_local):
-                raise ValueError("estimate_scale: %d frames of poses for spans of %d frames" % (len(est_local), int(cuts[-1])))
-            est_local = [est_local[lo:hi] for lo, hi in zip(cuts[:-1], cuts[1:])]
-        est_local = list(est_local)
-        if len(est_local) != len(spans) or any(len(x) != b - a for x, (a, b) in zip(est_local, spans)):
-            raise ValueError("estimate_scale: one tensor of end - start frames per span is needed")
-        if not spans:
-            raise ValueError("estimate_scale: no frames, so no pairs (0 pairs, 0 inliers, 0 informative)")
-        R, c, ids = selected_poses(rows_or_text, spans, fps)
+    est_local, R, c, ids = _recording_inputs(est_local, rows_or_text, spans, fps, tracked, "estimate_scale")
     lag = default_lag(fps) if lag is None else int(lag)
     rc, report, costs, msg = scale_call(est_local, R, c, ids, lag, tau, min_pairs, feet, stream)
     if rc in (_capi.SCALE_NO_PAIRS, _capi.SCALE_TOO_FEW, _capi.SCALE_BAD_SCALE):
@@ -178,19 +197,175 @@ def estimate_scale(est_local, rows_or_text, spans, fps, *, lag=None, tau=0.10, m
     return ScaleEstimate(report, costs)
 
 
+# ------------------------------------------------------------------------------------- a scale that drifts
+def default_knot(fps):
+    """Frames between two knots of the scale curve: 10 s."""
+    return max(1, int(round(10.0 * fps)))
+
+
+class DriftEstimate:
+    """A scale that drifts within the recording, as a piecewise-linear curve: `global_estimate` (the `ScaleEstimate` it started from),
+    `knot_ids` [K] frame ids and `knot_scale` [K] the curve there, `interval_count` / `interval_bb` [K-1] the inlier pairs between two
+    knots and their sum <b,b> (0: the curve is interpolated there), the record's `inliers`, `informative`, `residual_rms`, `scale_min`,
+    `scale_max`, `scale_mean` (metric path length / SLAM path length: the one number a reader may quote), `metric_length`,
+    `slam_length`, `lam`, the call's `knot`, `stiffness`, `lag`, `tau`; `frame_ids` [N] and `metric` [N,3] the camera track in metres
+    relative to the first frame, with `quats` [N,4] the relative rotations, which the curve leaves alone."""
+
+    def __init__(self, report, knots, metric, global_estimate, frame_ids, fps, quats):
+        self.report = np.asarray(report, dtype=np.float64)
+        head = _capi.GemDriftReport.from_buffer_copy(self.report[:_capi.DRIFT_REPORT_DOUBLES].tobytes())
+        self.status, self.n_knots, self.knot, self.stiffness = int(head.status), int(head.n_knots), int(head.knot), head.stiffness
+        self.inliers, self.informative, self.residual_rms = int(head.inliers), int(head.informative), head.residual_rms
+        self.scale_min, self.scale_max, self.scale_mean = head.scale_min, head.scale_max, head.scale_mean
+        self.metric_length, self.slam_length, self.lam = head.metric_length, head.slam_length, head.lam
+        knots = np.asarray(knots, dtype=np.float64).reshape(-1, 4)
+        self.knot_ids = int(head.first_id) + self.knot * np.arange(len(knots), dtype=np.int64)
+        self.knot_scale = knots[:, 0].copy()
+        self.interval_count, self.interval_bb = knots[:-1, 1].astype(np.int64), knots[:-1, 2].copy()
+        self.metric = np.asarray(metric, dtype=np.float64)
+        self.global_estimate = global_estimate
+        self.frame_ids, self.fps, self.quats = np.asarray(frame_ids, dtype=np.int64), fps, np.asarray(quats, dtype=np.float64)
+        self.lag, self.tau, self.min_pairs = global_estimate.lag, global_estimate.tau, global_estimate.min_pairs
+        self.per_chunk = global_estimate.per_chunk
+        self.scale = self.scale_mean
+
+    def metric_rows(self):
+        """Trajectory rows `time tx ty tz qx qy qz qw` of the frames the estimate covers: the metric track and the relative rotations.
+        The first row is the identity pose, so `slam.relative_poses` of these rows gives the metric track back as it is, and a recording
+        prepared from them with scale 1 is the one this estimate describes."""
+        quats = self.quats.copy()
+        quats[0] = (0.0, 0.0, 0.0, 1.0)          # (exactly: the first frame relative to itself)
+        return np.concatenate([(self.frame_ids / self.fps)[:, None], self.metric, quats], axis=1)
+
+    def as_dict(self):
+        """Plain numbers and lists (JSON)."""
+        d = self.global_estimate.as_dict()
+        d.update({"global_scale": self.global_estimate.scale, "scale": self.scale_mean, "scale_mean": self.scale_mean, "scale_min": self.scale_min,
+                  "scale_max": self.scale_max, "knot": self.knot, "stiffness": self.stiffness, "knot_ids": self.knot_ids.tolist(),
+                  "knot_scale": [float(v) for v in self.knot_scale], "interval_count": self.interval_count.tolist(),
+                  "interval_bb": [float(v) for v in self.interval_bb], "inliers": self.inliers, "informative": self.informative,
+                  "residual_rms": self.residual_rms, "metric_length": self.metric_length, "slam_length": self.slam_length})
+        return d
+
+    def knot_lines(self):
+        """One line per knot: where, the curve there, and what informed the interval to its right."""
+        out = []
+        for k, (i, s) in enumerate(zip(self.knot_ids, self.knot_scale)):
+            right = "" if k == self.n_knots - 1 else ("   %d inlier pairs to its right" % self.interval_count[k] if self.interval_count[k]
+                                                       else "   interpolated: no inlier pairs to its right")
+            out.append("knot %d at frame %d: scale %.9g%s" % (k, i, s, right))
+        return out
+
+    def line(self):
+        return ("SLAM scale drift: %.9g .. %.9g over %d knots %d frames apart (mean %.9g, one scale for all: %.9g; %d inliers, %d informative, "
+                "residual RMS %.4f m, path %.2f m)" % (self.scale_min, self.scale_max, self.n_knots, self.knot, self.scale_mean,
+                                                       self.global_estimate.scale, self.inliers, self.informative, self.residual_rms, self.metric_length))
+
+
+def drift_call(chunks, R, c, ids, lag, knot, stiffness=1.0, tau=0.10, min_pairs=50, feet=None, stream=None, read_back=True, work_bytes=None,
+               outputs=None):
+    """gem_slam_drift.  The inputs as `scale_call` takes them; knot: frames between knots.  outputs: (scale report, knots, metric,
+    report) device tensors to write into (default: zeros).  -> (return code, {"scale_report", "costs", "knots", "metric", "report"}:
+    numpy arrays, or the device tensors when not read_back, message)."""
+    import torch
+    lib = _capi.load_library()
+    chunks, J, device, N, nc, R, c, ids, feet, table = _call_inputs(chunks, R, c, ids, feet, "estimate_drift")
+    if N < 1 or (np.diff(ids) <= 0).any():
+        raise ValueError("estimate_drift: at least one frame is needed, and the frame ids must rise")
+    knot = int(knot)
+    K = max(2, -(-int(ids[-1] - ids[0]) // knot) + 1) if knot >= 1 else 2
+    K_alloc = min(K, _capi.DRIFT_MAX_KNOTS)
+    need = int(lib.gem_slam_drift_work(N, int(lag), K_alloc))
+    if need < 0:          # (sizes out of range: the call itself refuses them, with its own text)
+        need = 8
+    need = need if work_bytes is None else int(work_bytes)
+    n_rep = _capi.SCALE_REPORT_DOUBLES + 3 * nc
+    with torch.cuda.device(device):
+        st = torch.cuda.current_stream() if stream is None else stream
+        with torch.cuda.stream(st):
+            up, d_chunks, d_ids, d_rot, d_trans = _upload(table, ids, R, c, device)
+            work = torch.empty(need // 8 + 1, dtype=torch.float64, device=device)
+            costs = torch.zeros(_capi.SCALE_CANDIDATES, dtype=torch.float64, device=device)
+            if outputs is None:
+                outputs = (torch.zeros(n_rep, dtype=torch.float64, device=device), torch.zeros(K_alloc, 4, dtype=torch.float64, device=device),
+                           torch.zeros(N, 3, dtype=torch.float64, device=device), torch.zeros(_capi.DRIFT_REPORT_DOUBLES, dtype=torch.float64, device=device))
+            host =[np.zeros(tuple(t.shape), dtype=np.float64) if t is not None else None for t in outputs]
+            hp = [C.c_void_p(h.ctypes.data if (read_back and h is not None) else 0) for h in host]
+            dp = [C.c_void_p(t.data_ptr() if t is not None else 0) for t in outputs]
+            rc = lib.gem_slam_drift(C.c_void_p(table.ctypes.data), C.c_void_p(d_chunks.data_ptr()), nc, J, (C.c_int * 4)(*feet),
+                                    C.c_void_p(d_rot.data_ptr()), C.c_void_p(d_trans.data_ptr()), C.c_void_p(d_ids.data_ptr()), N, int(ids[0]),
+                                    int(ids[-1]), int(lag), float(tau), int(min_pairs), knot, float(stiffness), C.c_void_p(work.data_ptr()), need,
+                                    dp[0], C.c_void_p(costs.data_ptr()), dp[1], dp[2], dp[3], hp[0], hp[1], hp[2], hp[3], C.c_void_p(st.cuda_stream))
+            for t in (up, work):
+                t.record_stream(st)
+    msg = (lib.gem_last_error() or b"").decode() if rc else ""
+    got = host if read_back else list(outputs)
+    return rc, {"scale_report": got[0], "costs": costs, "knots": got[1], "metric": got[2], "report": got[3]}, msg
+
+
+def estimate_drift(est_local, rows_or_text, spans, fps, *, knot=None, stiffness=1.0, lag=None, tau=0.10, min_pairs=50, feet=None, stream=None,
+                   tracked=False):
+    """`estimate_scale` for a SLAM whose scale creeps over the recording: the same inputs, `knot` frames between
+    the knots of the curve (default 10 s) and `stiffness` of its second differences.  -> DriftEstimate, whose `metric_rows()` are the
+    trajectory in metres; ValueError when the recording does not fix one scale (`estimate_scale`'s refusals, with their counts) or
+    does not fix the curve (the knot intervals without inlier pairs are named)."""
+    from . import slam
+    rows = rows_or_text if isinstance(rows_or_text, np.ndarray) else slam.trajectory_rows(rows_or_text)
+    est_local, R, c, ids = _recording_inputs(est_local, rows, spans, fps, tracked, "estimate_drift")
+    lag = default_lag(fps) if lag is None else int(lag)
+    knot = default_knot(fps) if knot is None else int(knot)
+    if not (np.isfinite(stiffness) and stiffness >= 0):
+        raise ValueError("estimate_drift: stiffness must be a finite number >= 0, got %r" % (stiffness,))
+    if knot < lag + 1:
+        raise ValueError("estimate_drift: knots %d frames apart, but a pair alone is %d frames long" % (knot, lag))
+    rc, out, msg = drift_call(est_local, R, c, ids, lag, knot, stiffness, tau, min_pairs, feet, stream)
+    if rc in (_capi.SCALE_NO_PAIRS, _capi.SCALE_TOO_FEW, _capi.SCALE_BAD_SCALE):
+        raise ValueError(msg.replace("gem_slam_scale: ", "the SLAM scale cannot be estimated: "))
+    if rc == _capi.DRIFT_NOT_SOLVED:
+        counts = out["knots"][:-1, 1]
+        empty = ", ".join("%d-%d" % (k, k + 1) for k in np.flatnonzero(counts == 0)) or "none"
+        raise ValueError(msg.replace("gem_slam_drift: ", "the SLAM scale's drift cannot be estimated: ") + "; no inlier pairs between knots " + empty)
+    if rc:
+        raise _capi.GemError(msg or "gem_slam_drift failed")
+    # the relative rotations of the frames the estimate covers, as quaternions: what `slam.relative_poses` makes of their lines
+    line_ids = slam.frame_ids(rows, fps)
+    order = np.argsort(line_ids, kind="stable")
+    picked = rows[order[np.searchsorted(line_ids[order], ids, side="left")]]
+    _, rq = slam.relative_poses(picked[:, 1:4], picked[:, 4:8])
+    return DriftEstimate(out["report"], out["knots"], out["metric"], ScaleEstimate(out["scale_report"], out["costs"]), ids, fps, rq)
+
+
 # ------------------------------------------------------------------------------------------------------------------ command line
 def scale_arg(text):
-    """argparse type of `--scale`: a positive number (-> float, as before) or the word `auto`."""
+    """argparse type of `--scale`: a positive number (-> float, as before), the word `auto`, or the word `drift`."""
     import argparse
-    if text == "auto":
-        return "auto"
+    if text in ("auto", "drift"):
+        return text
     try:
         v = float(text)
     except ValueError:
-        raise argparse.ArgumentTypeError("a positive number or `auto` is needed, got %r" % text)
+        raise argparse.ArgumentTypeError("a positive number, `auto` or `drift` is needed, got %r" % text)
     if not (np.isfinite(v) and v > 0):
         raise argparse.ArgumentTypeError("the SLAM scale must be a positive number, got %r" % text)
     return v
+
+
+def add_drift_options(p):
+    """`--knot` and `--stiffness` of `--scale drift` (`prepare`, `detections`, `continuous`, `slam_scale`)."""
+    p.add_argument("--knot", type=float, default=None, metavar="SECONDS", help="with --scale drift: seconds between two knots of the scale "
+                                                                               "curve (default 10)")
+    p.add_argument("--stiffness", type=float, default=None, help="with --scale drift: weight of the curve's second differences (default 1)")
+
+
+def drift_options(p, a):
+    """The rules of `add_drift_options`, as parser errors -> {knot: frames or None, stiffness}."""
+    if (a.knot is not None or a.stiffness is not None) and a.scale != "drift":
+        p.error("--knot and --stiffness belong to --scale drift")
+    if a.knot is not None and not (np.isfinite(a.knot) and a.knot > 0):
+        p.error("--knot must be a positive number of seconds")
+    if a.stiffness is not None and not (np.isfinite(a.stiffness) and a.stiffness >= 0):
+        p.error("--stiffness must be a finite number >= 0")
+    return {"knot": None if a.knot is None else max(1, int(round(a.knot * a.fps))), "stiffness": 1.0 if a.stiffness is None else a.stiffness}
 
 
 def full_spans(start, end, test_size):
@@ -234,6 +409,9 @@ def _parser():
     p.add_argument("--lag", type=int, default=None, help="frames between the two frames of a pair (default: 0.2 s)")
     p.add_argument("--tau", type=float, default=0.10, help="metres a standing foot may seem to move")
     p.add_argument("--min_pairs", type=int, default=50)
+    p.add_argument("--scale", default="auto", choices=("auto", "drift"), help="auto: one scale for the recording; drift: a curve over it "
+                                                                              "(DESIGN.md section 6t)")
+    add_drift_options(p)
     p.add_argument("--test_size", type=int, default=100, help="frames per chunk of the per-chunk scales")
     p.add_argument("--first_id", type=int, default=0, help="frame id of the detections' first row (without frame_ids)")
     p.add_argument("--json", default=None, metavar="FILE", help="write the report there too")
@@ -260,13 +438,13 @@ def _cli(argv=None):
         p.error("--min_peak goes with --heatmaps: detections carry their own confidence")
     from .bone_depth import bones_from_args
     spans = full_spans(a.start, a.end, a.test_size)
-    options = dict(lag=a.lag, tau=a.tau, min_pairs=a.min_pairs)
+    options = dict(lag=a.lag, tau=a.tau, min_pairs=a.min_pairs, **drift_options(p, a))
     if a.depth_from is not None:
         options.update(depth=a.depth_from, bones=bones_from_args(a), neck_depth=a.neck_depth)
     if a.heatmaps is not None:
-        rec = prepare.prepare_spans(a.slam, a.heatmaps, a.depths, None, spans, a.fps, a.start, a.camera, scale="auto", min_peak=a.min_peak, **options)
+        rec = prepare.prepare_spans(a.slam, a.heatmaps, a.depths, None, spans, a.fps, a.start, a.camera, scale=a.scale, min_peak=a.min_peak, **options)
     else:
-        rec = detections.recording_from_detections(a.slam, detections.detections_from_args(a), None, "auto", spans, a.fps,
+        rec = detections.recording_from_detections(a.slam, detections.detections_from_args(a), None, a.scale, spans, a.fps,
                                                    camera_model_path=a.camera, **options)
     est = rec.scale_report
     print(est.line())
@@ -279,6 +457,8 @@ def _cli(argv=None):
         out["umeyama_per_chunk"] = umeyama_per_chunk
     for k, ((s, e), v) in enumerate(zip(spans, est.per_chunk)):
         print("chunk %d [%d, %d): scale %.9g%s" % (k, s, e, v, "" if umeyama_per_chunk is None else "   Umeyama against the ground truth %.9g" % umeyama_per_chunk[k]))
+    if a.scale == "drift":
+        print("\n".join(est.knot_lines()))
     if a.json is not None:
         os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
         with open(a.json, "w") as f:

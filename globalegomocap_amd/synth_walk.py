@@ -64,7 +64,8 @@ def walk(n_frames, scale=1.0, fps=25.0, stance=14, step=10, speed=1.2, stand=(),
     [m step, m step + stance], both ends included (step <= stance < 2 step: both feet stand for stance - step frames in between),
     so that of any two frames no more than stance - step + 1 apart one foot stands in both; speed: metres per second, a number or one
     per frame; stand: [(a, b)] frame ranges [a, b) with speed 0 -- the wearer keeps stepping on the spot; noise: sigma in metres on
-    every coordinate of `local`."""
+    every coordinate of `local`; scale: a number, or one per frame for a SLAM whose scale drifts -- the
+    trajectory is then the running sum of the head's steps, each divided by the mean of its two frames' scales."""
     S, P, n = int(stance), int(step), int(n_frames)
     if n < 1 or P < 1 or not P <= S < 2 * P:
         raise ValueError("walk: need at least one frame and 1 <= step <= stance < 2 step")
@@ -129,9 +130,19 @@ def walk(n_frames, scale=1.0, fps=25.0, stance=14, step=10, speed=1.2, stand=(),
     cams[:, :3, :3], cams[:, :3, 3] = R[cut], head[cut]
     Q = _rotvec_matrix(world_rotation)
     ids = np.arange(n, dtype=np.int64) + int(first_id)
-    rows = np.concatenate([(ids / fps)[:, None], head[cut] @ Q.T / scale + np.asarray(world_offset, dtype=np.float64), _quat_xyzw(Q @ R[cut])], 1)
+    if np.ndim(scale):                                   # a drifting scale: every step of the head at the mean of its two frames' scales
+        scale = np.asarray(scale, dtype=np.float64)
+        if scale.shape != (n,):
+            raise ValueError("walk: scale is a number or one per frame")
+        moved = head[cut] @ Q.T
+        first = moved[:1] / scale[0]
+        track = np.concatenate([first, first + np.cumsum((moved[1:] - moved[:-1]) / (0.5 * (scale[1:] + scale[:-1]))[:, None], axis=0)])
+    else:
+        track = head[cut] @ Q.T / scale
+    rows = np.concatenate([(ids / fps)[:, None], track + np.asarray(world_offset, dtype=np.float64), _quat_xyzw(Q @ R[cut])], 1)
     return {"feet": feet[cut], "head": head[cut], "cams": cams, "local": local, "depth": np.sqrt((local * local).sum(-1)), "rows": rows,
-            "frame_ids": ids, "standing": standing[cut], "world": world[cut], "scale": float(scale), "fps": float(fps), "stance": S, "step": P}
+            "frame_ids": ids, "standing": standing[cut], "world": world[cut], "scale": scale if np.ndim(scale) else float(scale), "fps": float(fps),
+            "stance": S, "step": P}
 
 
 def slam_inputs(w, lo=0, hi=None):

@@ -943,6 +943,51 @@ int gem_slam_scale(const int64_t* h_chunks, const int64_t* d_chunks, int n_chunk
                    const double* d_trans, const int64_t* d_ids, int64_t n_frames, int lag, double tau, int min_pairs, void* d_work,
                    int64_t work_bytes, double* d_report, double* d_costs, double* h_report, void* stream);
 
+/* ---- A SLAM scale that drifts within a recording, and the camera track in metres: `--scale drift` ----
+ * The scale is a piecewise-linear curve over K = max(2, ceil((last_id - first_id) / knot) + 1) knots at frame ids first_id + k knot.
+ * A pair whose first row is t lives at ids[t] + lag / 2, in interval k_p = min(floor((that - first_id) / knot), K - 2) with the fraction
+ * u_p inside it.  Start: s_k = gem_slam_scale's estimate, whose refusals are this call's.  Four rounds of: with the current curve every
+ * pair takes the side of the smaller residual |a + s(tau_p) b|^2 (a tie: the right foot) and is an inlier when that is < tau^2; then
+ * minimise sum_inl |a_p + ((1 - u_p) s_k + u_p s_k+1) b_p|^2 + lambda sum_{k=1..K-2} (s_k-1 - 2 s_k + s_k+1)^2 with
+ * lambda = stiffness sum_inl <b,b> / (K - 1): a symmetric pentadiagonal system, factored L D L^T in index order.  A pivot that is not
+ * positive and finite, or (K > 2) fewer than two intervals whose inliers have sum <b,b> > 0 -- one interval's pairs fix a line, which
+ * the penalty would only extrapolate over the whole recording -- keeps the curve of the round before and gives GEM_DRIFT_NOT_SOLVED.
+ * The metric track: C_0 = 0, C_i = C_i-1 + s((ids[i-1] + ids[i]) / 2) (c_i - c_i-1), summed as an inclusive scan within blocks of 256
+ * rows plus the blocks' totals in order, so the bytes up to row i do not depend on rows behind the block that holds i.  Everything is
+ * float64 without fused multiply-adds, every sum has a fixed order, there are no floating-point atomics: two calls give the same bytes. */
+#define GEM_DRIFT_MAX_KNOTS 2048
+#define GEM_DRIFT_REPORT_DOUBLES 16
+#define GEM_DRIFT_NOT_SOLVED 5      /* the recording does not fix the curve */
+typedef struct gem_drift_report {
+    double status;                                  /* 0, a GEM_SCALE_* refusal of the global estimate, or GEM_DRIFT_NOT_SOLVED */
+    double n_knots, knot, stiffness;                /* K and the call's parameters */
+    double inliers, informative, residual_rms;      /* under the last curve; informative: s(tau_p) |b| > tau */
+    double scale_min, scale_max, scale_mean;        /* over the knots; scale_mean = metric_length / slam_length */
+    double metric_length, slam_length;              /* sum of the scaled steps' lengths, metres; sum of the steps' lengths, SLAM units */
+    double lam;                                     /* the last round's lambda */
+    double first_id;
+    double bad_pivot, informed;                     /* index of the first failed pivot or -1; intervals with inlier sum <b,b> > 0 */
+} gem_drift_report;
+
+/* Bytes of d_work a call with these sizes needs; -1 with the reason in gem_last_error for sizes out of range.  Needs no GPU. */
+int64_t gem_slam_drift_work(int64_t n_frames, int lag, int n_knots);
+
+/* gem_slam_scale's inputs (which see), the first and the last of the frame ids (d_ids must rise), `knot` >= lag + 1 frames between
+ * knots and `stiffness` >= 0.  d_scale_report [16 + 3 n_chunks] and d_costs [513] or NULL: gem_slam_scale's outputs, computed once
+ * here by its own kernels.  d_knots [K][4]: value, inlier count and inlier sum <b,b> of the interval to the knot's right (0 for the
+ * last knot), reserved; d_metric [n_frames,3]; d_report: a gem_drift_report.  All arguments are checked before any launch (more than
+ * GEM_DRIFT_MAX_KNOTS knots, knot < lag + 1, a stiffness that is negative or not finite, a null output, d_work too small: return 1
+ * with the reason in gem_last_error and nothing written).  A refusal of the global estimate writes the two reports and leaves
+ * d_knots and d_metric untouched; GEM_DRIFT_NOT_SOLVED writes d_knots too (the counts tell which intervals held no inliers).
+ * h_report NULL: everything is enqueued on `stream` and the verdict is the report's status.  h_report [16] (host): the stream is
+ * waited for, h_scale_report, h_knots and h_metric are filled where given (they need h_report), and a status other than 0 is the
+ * return value with its text in gem_last_error.  Works on the current device. */
+int gem_slam_drift(const int64_t* h_chunks, const int64_t* d_chunks, int n_chunks, int n_joints, const int* h_feet, const double* d_rot,
+                   const double* d_trans, const int64_t* d_ids, int64_t n_frames, int64_t first_id, int64_t last_id, int lag, double tau,
+                   int min_pairs, int knot, double stiffness, void* d_work, int64_t work_bytes, double* d_scale_report, double* d_costs,
+                   double* d_knots, double* d_metric, double* d_report, double* h_scale_report, double* h_knots, double* h_metric,
+                   double* h_report, void* stream);
+
 /* ---- The ground plane of a pose sequence from its foot contacts, and the upright frame: `--upright` ----
  * A foot that stands does not move, and the places where the feet stand lie on the floor.  With q[f,side] = (x[f,ankle] + x[f,foot]) / 2
  * (right: joints 9 and 10, left: 13 and 14), foot point (f, side) is a candidate when f + lag < n_frames and
