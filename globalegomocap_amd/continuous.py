@@ -149,8 +149,6 @@ def _stride_arg(text):
 def _parser():
     import argparse
     from . import prepare, whole_sequence as ws
-    from .camera import DEFAULT_CALIBRATION
-    from .slam_scale import scale_arg
     p = argparse.ArgumentParser(description="recording -> ONE optimised motion: every frame, one world, one set of files")
     src = p.add_mutually_exclusive_group(required=True)
     src.add_argument("--heatmaps", default=None, metavar="DIR", help="directory of per-frame heatmap .mat files (`prepare`'s route)")
@@ -159,21 +157,7 @@ def _parser():
     p.add_argument("--depth", default=None, metavar="FILE.npy", help="with --keypoints: the joints' depths [N,15], row for row with the detections")
     p.add_argument("--sigma", type=float, default=None, help="with --keypoints: the splatted Gaussians' width in heat-map pixels (default 1.5)")
     p.add_argument("--first_id", type=int, default=None, help="with --keypoints: frame id of the detections' first row (default 0)")
-    p.add_argument("--slam", required=True, help="SLAM trajectory: lines `time tx ty tz qx qy qz qw`")
-    how = p.add_mutually_exclusive_group(required=True)
-    how.add_argument("--gt", default=None, help="ground-truth pickle: ONE scale is fitted over the whole span, and the 18 errors are reported")
-    how.add_argument("--scale", type=scale_arg, default=None, help="the SLAM scale of a recording without ground truth (a metric SLAM: 1), "
-                                                                  "`auto`: estimate it from the foot contacts, or `drift`: follow a "
-                                                                  "scale that creeps over the recording")
-    from .slam_scale import add_drift_options
-    add_drift_options(p)
-    p.add_argument("--bridge", nargs="?", type=float, const=1.0, default=None, metavar="SECONDS",
-                   help="with --scale: invent the cameras of stretches of lost SLAM tracking up to this long (default 1 s)")
-    p.add_argument("--start", required=True, type=int)
-    p.add_argument("--end", required=True, type=int)
-    p.add_argument("--fps", type=float, default=25)
-    p.add_argument("--mat_start", type=int, default=None, help="frame id of the GT pickle's first entry (default: --start)")
-    p.add_argument("--camera", default=DEFAULT_CALIBRATION)
+    prepare.add_track_options(p, gt_help="ground-truth pickle: ONE scale is fitted over the whole span, and the 18 errors are reported")
     p.add_argument("--stride", type=_stride_arg, default=8, metavar="K", help="frames between two windows, 1 .. 8 (default 8)")
     ws.add_weight_options(p)
     ws.add_output_options(p)
@@ -203,23 +187,22 @@ def parse_args(argv=None):
         if a.depth_from is None and (a.bones is not None or a.neck_depth is not None):
             p.error("--bones and --neck_depth belong to --depth_from bones")
     ws.check_output_options(p, a)
-    from .slam_scale import drift_options
-    a.drift = drift_options(p, a)
+    a.track = prepare.track_arguments(p, a)          # (the rules of --scale drift are checked here)
+    a.drift = {k: a.track[k] for k in ("knot", "stiffness")}
     return a
 
 
 def _cli(argv=None):
     from . import detections, prepare, whole_sequence as ws
-    from .bone_depth import bones_from_args
     a = parse_args(argv)
     if a.heatmaps is not None:
-        rec = prepare.prepare_continuous(a.slam, a.heatmaps, a.depths, a.gt, a.start, a.end, a.fps, a.mat_start, a.camera, scale=a.scale, bridge=a.bridge,
-                                         depth=a.depth_from, bones=bones_from_args(a), neck_depth=a.neck_depth, min_peak=a.min_peak, peaks=a.peaks, **a.drift)
+        rec = prepare.prepare_continuous(a.slam, a.heatmaps, a.depths, total_start_frame=a.start, total_end_frame=a.end, fps=a.fps,
+                                         mat_start_frame=a.mat_start, camera_model_path=a.camera, **a.track, **prepare.depth_route_arguments(a))
     else:
         a.first_id = 0 if a.first_id is None else a.first_id
-        rec = detections.continuous_from_detections(a.slam, detections.detections_from_args(a), a.gt, a.scale, a.start, a.end, a.fps, depth=a.depth_from,
+        rec = detections.continuous_from_detections(a.slam, detections.detections_from_args(a), start_frame=a.start, end_frame=a.end, fps=a.fps,
                                                     sigma=1.5 if a.sigma is None else a.sigma, camera_model_path=a.camera, gt_start_frame=a.mat_start,
-                                                    bridge=a.bridge, bones=bones_from_args(a), neck_depth=a.neck_depth, **a.drift)
+                                                    **a.track, **prepare.depth_route_arguments(a, maps=False))
         prepare.print_report(rec)
     optimize_continuous(rec, a.camera, a.vae, a.gmm, a.smooth, a.bone_length, a.weight_3d, a.reproj_weight, final_smooth=a.final_smooth,
                         ground_truth=a.scale is None, save_pose=a.save_pose, stride=a.stride, **ws.output_arguments(a))

@@ -139,13 +139,13 @@ def recording_from_detections(slam_result_path, detections, gt_path=None, scale=
     Recording carries the solve's `depth_report`.  Exactly one of
     `gt_path` (the ground truth fixes the SLAM scale per chunk, as `prepare` does; entry i - gt_start_frame of the pickle is frame id
     i, gt_start_frame defaulting to the first span's start) and `scale`: a number, or "auto" to estimate it from the foot contacts of
-    the filled poses (`prepare.auto_scale` with `lag`, `tau`, `min_pairs`), or "drift" to follow a scale that creeps
+    the filled poses (`slam_scale.estimate_scale` with `lag`, `tau`, `min_pairs`), or "drift" to follow a scale that creeps
     over the recording (`knot` frames between the curve's knots, `stiffness`).  One upload, then on the device:
     lift -> fill -> heat-maps -> cameras -> gem_prepare_global; from the filled poses on this is `prepare.RecordingStage`.  `bridge`:
     None, or the seconds of lost SLAM tracking whose cameras are invented (`slam_bridge`), without ground truth
     only."""
     from . import prepare
-    stage = prepare.RecordingStage(gt_path, scale, bridge, spans, fps, lag, tau, min_pairs, knot, stiffness)
+    stage = prepare.RecordingStage(prepare.CameraRoute(gt_path, scale, bridge, lag, tau, min_pairs, knot, stiffness), spans, fps)
     import torch
     from .camera import DEFAULT_CALIBRATION
     if isinstance(detections, (str, os.PathLike)):
@@ -191,19 +191,12 @@ def recording_from_detections(slam_result_path, detections, gt_path=None, scale=
         engine = prepare._lift_engine(camera_model_path or DEFAULT_CALIBRATION, device.index)
         packed_d = torch.from_numpy(packed).to(device)
         if from_bones:
-            from .bone_depth import summarize
             kp_d = packed_d
-            depth_d, solved, rms = engine.bone_depths(kp_d, opts=bone_opts)
-            depth_report = summarize(solved, rms)
+            depth_d, _, depth_report = prepare.solve_bone_depths(engine, kp_d, bone_opts)
         else:
             kp_d, depth_d = packed_d[..., :3].contiguous(), packed_d[..., 3].contiguous()
         est_local, _, valid = engine.lift_keypoints(kp_d, depth_d)
-        lengths = {hi - lo for lo, hi in bounds}
-        if len(lengths) == 1:
-            engine.fill_missing(est_local, valid, len(bounds))
-        else:
-            for lo, hi in bounds:
-                engine.fill_missing(est_local[lo:hi], valid[lo:hi], 1)
+        prepare.fill_chunks(engine, est_local, valid, bounds)
         stage.fix_scale(engine, est_local)          # (a recording that does not fix the scale is refused before the heat-maps are made)
         heat = engine.keypoint_heatmaps(kp_d, sigma)          # (enqueued ahead of the host's camera work and its blocking upload)
         rec = stage.recording(est_local, heat)
@@ -211,11 +204,11 @@ def recording_from_detections(slam_result_path, detections, gt_path=None, scale=
         return rec
 
 
-def continuous_from_detections(slam_result_path, detections, gt_path=None, scale=None, start_frame=0, end_frame=0, fps=25, **kwargs):
+def continuous_from_detections(slam_result_path, detections, gt_path=None, scale=None, start_frame=0, end_frame=0, fps=25, **options):
     """`recording_from_detections` for a recording that is optimised as one motion (`continuous.optimize_continuous`, DESIGN.md section
-    6s): the ONE span [start_frame, end_frame) as one chunk; the other arguments, by keyword, as there.  -> a Recording that is
-    continuous already."""
-    return recording_from_detections(slam_result_path, detections, gt_path, scale, [(int(start_frame), int(end_frame))], fps, **kwargs)
+    6s): the ONE span [start_frame, end_frame) as one chunk; `options`: its other keywords, handed on as they are.  -> a Recording that
+    is continuous already."""
+    return recording_from_detections(slam_result_path, detections, gt_path, scale, [(int(start_frame), int(end_frame))], fps, **options)
 
 
 def _parser():
@@ -239,15 +232,13 @@ def _parser():
 
 def _cli(argv=None):
     from . import prepare
-    from .bone_depth import bones_from_args
     p = _parser()
-    from .slam_scale import drift_options
     a = prepare.parse_recording_options(p, argv)
     if a.depth_from is None and (a.bones is not None or a.neck_depth is not None):
         p.error("--bones and --neck_depth belong to --depth_from bones")
-    rec = recording_from_detections(a.slam, detections_from_args(a), a.gt, a.scale, prepare.chunk_spans(a.start, a.end, a.test_size), a.fps,
-                                    depth=a.depth_from, sigma=a.sigma, camera_model_path=a.camera, gt_start_frame=a.mat_start, bridge=a.bridge,
-                                    bones=bones_from_args(a), neck_depth=a.neck_depth, **drift_options(p, a))
+    rec = recording_from_detections(a.slam, detections_from_args(a), spans=prepare.chunk_spans(a.start, a.end, a.test_size), fps=a.fps, sigma=a.sigma,
+                                    camera_model_path=a.camera, gt_start_frame=a.mat_start, **prepare.track_arguments(p, a),
+                                    **prepare.depth_route_arguments(a, maps=False))
     prepare.print_report(rec)
     if a.out is not None:
         rec.write_chunks(a.out)

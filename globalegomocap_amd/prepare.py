@@ -57,6 +57,7 @@ import io
 import os
 import pickle
 import zlib
+from collections import namedtuple
 
 import numpy as np
 
@@ -126,6 +127,22 @@ def gt_or_scale(gt_path, scale):
     if not (np.isfinite(scale) and scale > 0):
         raise ValueError("the SLAM scale must be a positive number, got %r" % scale)
     return scale
+
+
+class CameraRoute:
+    """How a recording's SLAM track becomes cameras, fixed once per call from the route's keywords of the same names: `gt_path` or
+    `scale` as `gt_or_scale` leaves it, `bridge` as `slam_bridge.bridge_arg` leaves it, and what the estimators of scale="auto" /
+    "drift" take (`slam_scale.estimate_scale`, `estimate_drift`).  ValueError for arguments that do not go together."""
+    TAU, MIN_PAIRS, STIFFNESS = 0.10, 50, 1.0          # the estimators' defaults, for this record and the .mat route's signature
+
+    def __init__(self, gt_path=None, scale=None, bridge=None, lag=None, tau=TAU, min_pairs=MIN_PAIRS, knot=None, stiffness=STIFFNESS):
+        from .slam_bridge import bridge_arg
+        self.gt_path, self.scale, self.bridge = gt_path, gt_or_scale(gt_path, scale), bridge_arg(bridge, gt_path)
+        self.lag, self.tau, self.min_pairs, self.knot, self.stiffness = lag, tau, min_pairs, knot, stiffness
+
+    has_gt = property(lambda self: self.scale is None)
+    auto = property(lambda self: self.scale == "auto")
+    drift = property(lambda self: self.scale == "drift")
 
 
 def scaled_cameras(rows, spans, fps, scale):
@@ -588,34 +605,16 @@ def prepare_global(est_local, cams, gt):
     return out, err
 
 
-def auto_scale(est_local, rows, spans, fps, scale, lag=None, tau=0.10, min_pairs=50, tracked=False, knot=None, stiffness=1.0):
-    """`scale` as a number -> (scale, None).  "auto" -> (the estimate, its `slam_scale.ScaleEstimate`): `gem_slam_scale` on the lifted
-    poses where they lie (`tracked`: on the tracked frames of a trajectory that lacks lines), one small record back; ValueError when
-    the recording does not fix the scale.  "drift" -> (1.0, a `slam_scale.DriftEstimate`): the scale as a curve with knots `knot` frames
-    apart, whose `metric_rows()` are the trajectory in metres -- the caller goes on with those rows at scale 1."""
-    if isinstance(scale, str) and scale == "drift":
-        from .slam_scale import estimate_drift
-        return 1.0, estimate_drift(est_local, rows, spans, fps, knot=knot, stiffness=stiffness, lag=lag, tau=tau, min_pairs=min_pairs, tracked=tracked)
-    if not (isinstance(scale, str) and scale == "auto"):
-        return scale, None
-    from .slam_scale import estimate_scale
-    report = estimate_scale(est_local, rows, spans, fps, lag=lag, tau=tau, min_pairs=min_pairs, tracked=tracked)
-    return float(report.scale), report
-
-
 class RecordingStage:
     """What every route into a `Recording` does once it has the lifted poses `est_local`: fix the SLAM scale, build the cameras, apply
-    them (`gem_prepare_global`) and cut the chunks.  One per call.  The route makes it first (the argument checks), reads and checks
-    the trajectory through it, sets `bounds` [(first row, row behind the last)] and `gts` (per chunk the ground-truth arrays; unused
-    without ground truth) for its chunks, and then calls `fix_scale` and `recording` -- two steps, because a route may enqueue device
-    work between them that the host's camera work then overlaps (the detection route's heat-maps)."""
+    them (`gem_prepare_global`) and cut the chunks.  One per call.  The route makes it first from its `CameraRoute` (the argument checks),
+    reads and checks the trajectory through it, sets `bounds` [(first row, row behind the last)] and `gts` (per chunk the ground-truth
+    arrays; unused without ground truth) for its chunks, and then calls `fix_scale` and `recording` -- two steps, because a route may
+    enqueue device work between them that the host's camera work then overlaps (the detection route's heat-maps)."""
 
-    def __init__(self, gt_path, scale, bridge, spans, fps, lag=None, tau=0.10, min_pairs=50, knot=None, stiffness=1.0):
-        from .slam_bridge import bridge_arg
-        self.gt_path, self.scale = gt_path, gt_or_scale(gt_path, scale)
-        self.bridge = bridge_arg(bridge, gt_path)
+    def __init__(self, route, spans, fps):
+        self.route, self.scale, self.bridge = route, route.scale, route.bridge          # (`scale`: a number once `fix_scale` has run)
         self.spans, self.fps = [(int(a), int(b)) for a, b in spans], fps
-        self.lag, self.tau, self.min_pairs, self.knot, self.stiffness = lag, tau, min_pairs, knot, stiffness
         self.rows = self.systems = self.bounds = self.gts = None
         self.cams = self.origins = self.scale_report = self.bridge_report = None
 
@@ -626,7 +625,7 @@ class RecordingStage:
 
     def read_gt(self):
         """The ground-truth pickle's poses; None for a recording without ground truth."""
-        return read_gt(self.gt_path) if self.scale is None else None
+        return read_gt(self.route.gt_path) if self.route.has_gt else None
 
     def check_trajectory(self):
         """Every span's frame ids have their trajectory line (`check_trajectory`) -- or, with `bridge`, the lost ones can be bridged
@@ -641,7 +640,7 @@ class RecordingStage:
 
     def empty(self):
         """The recording of no spans."""
-        return Recording([], None if self.scale is None else np.empty((0, 4, 4)))
+        return Recording([], None if self.route.has_gt else np.empty((0, 4, 4)))
 
     def fix_scale(self, engine, est_local, lap=Laps(None)):
         """Everything that can still refuse the recording, and everything that needs a read-back before the cameras exist: "auto"
@@ -649,13 +648,18 @@ class RecordingStage:
         does not fix the scale), "drift" becomes the number 1, a `slam_scale.DriftEstimate` and the trajectory in metres in place of
         `rows` (DESIGN.md section 6t), and with `bridge` the bridged cameras, the origins and the `slam_bridge.BridgeReport` are made;
         the cameras stay on the device.  Nothing to do with ground truth."""
-        if self.scale is None:
+        route = self.route
+        if route.has_gt:
             return
-        drift = isinstance(self.scale, str) and self.scale == "drift"
-        self.scale, self.scale_report = auto_scale(est_local, self.rows, self.spans, self.fps, self.scale, self.lag, self.tau, self.min_pairs,
-                                                   tracked=self.bridge is not None, knot=self.knot, stiffness=self.stiffness)
-        if drift:          # from here on the trajectory is the metric one, at scale 1
-            self.rows = self.scale_report.metric_rows()
+        if route.auto or route.drift:
+            from .slam_scale import estimate_drift, estimate_scale
+            pairs = dict(lag=route.lag, tau=route.tau, min_pairs=route.min_pairs, tracked=self.bridge is not None)
+            if route.drift:          # from here on the trajectory is the metric one, at scale 1
+                self.scale_report = estimate_drift(est_local, self.rows, self.spans, self.fps, knot=route.knot, stiffness=route.stiffness, **pairs)
+                self.scale, self.rows = 1.0, self.scale_report.metric_rows()
+            else:
+                self.scale_report = estimate_scale(est_local, self.rows, self.spans, self.fps, **pairs)
+                self.scale = float(self.scale_report.scale)
         if self.bridge is not None:
             from .slam_bridge import bridge_cameras
             self.cams, self.origins, self.bridge_report = bridge_cameras(engine, self.rows, self.spans, self.fps, self.scale, self.bridge,
@@ -670,7 +674,7 @@ class RecordingStage:
         import torch
         from . import slam
         spans, bounds, gt_all = self.spans, self.bounds, None
-        if self.scale is None:
+        if self.route.has_gt:
             heads = est_local[:, 0].cpu().numpy()
             lap("lift + head joints to the host")
             gt_all = np.concatenate([np.asarray(g, dtype=np.float64) for g in self.gts])
@@ -712,12 +716,15 @@ def print_report(rec, sequence=True):
             print("The initial mpjpe is: {}".format(c.initial_mpjpe))
 
 
+DepthRoute = namedtuple("DepthRoute", "from_bones subpixel bone_opts min_peak")          # what `depth_route` decides
+
+
 def depth_route(depth_dir, depth=None, bones=None, neck_depth=None, min_peak=None, peaks=None):
     """The checks of `prepare_spans`' depth arguments, before a device is touched: exactly one of `depth_dir` (the pose network's depth
     files) and depth="bones" (the depths are solved from the bone lengths at the maps' sub-pixel peaks, DESIGN.md section 6r);
     `bones`, `neck_depth` (`bone_depth.options`) and `min_peak` (a finite number >= 0) belong to depth="bones"; `peaks` is None,
     "argmax" (the reference's 16-pixel lift; with depth files only) or "subpixel" (what depth="bones" always uses).
-    -> (from_bones, subpixel, bone options or None, min_peak as a float).  ValueError otherwise."""
+    -> DepthRoute(from_bones, subpixel, bone options or None, min_peak as a float).  ValueError otherwise."""
     if depth is not None and not (isinstance(depth, str) and depth == "bones"):
         raise ValueError('prepare: depth is None (the depth files of depth_dir) or "bones", got %r' % (depth,))
     from_bones = depth is not None
@@ -738,7 +745,23 @@ def depth_route(depth_dir, depth=None, bones=None, neck_depth=None, min_peak=Non
     if from_bones:
         from . import bone_depth
         bone_opts = bone_depth.options(bones, neck_depth=neck_depth)
-    return from_bones, from_bones or peaks == "subpixel", bone_opts, min_peak
+    return DepthRoute(from_bones, from_bones or peaks == "subpixel", bone_opts, min_peak)
+
+
+def solve_bone_depths(engine, kp, bone_opts):
+    """Both routes' bone solve with its report: `WindowEngine.bone_depths` of `kp` [n,15,3] -> (depth, solved [n,15], `BoneDepthReport`)."""
+    from .bone_depth import summarize
+    depth, solved, rms = engine.bone_depths(kp, opts=bone_opts)
+    return depth, solved, summarize(solved, rms)
+
+
+def fill_chunks(engine, est_local, valid, bounds):
+    """`fill_missing` within every chunk (rows bounds[k] of the frames), in place: ONE call for chunks of one length, else one per chunk."""
+    if len({hi - lo for lo, hi in bounds}) == 1:
+        engine.fill_missing(est_local, valid, len(bounds))
+    else:
+        for lo, hi in bounds:
+            engine.fill_missing(est_local[lo:hi], valid[lo:hi], 1)
 
 
 def lift_peaks(engine, heat, depth, bounds, spans, bone_opts=None, min_peak=0.0):
@@ -750,9 +773,7 @@ def lift_peaks(engine, heat, depth, bounds, spans, bone_opts=None, min_peak=0.0)
     kp, _ = engine.heatmap_peaks(heat, min_peak=min_peak)
     report = None
     if bone_opts is not None:
-        from .bone_depth import summarize
-        depth, solved, rms = engine.bone_depths(kp, opts=bone_opts)
-        report = summarize(solved, rms)
+        depth, solved, report = solve_bone_depths(engine, kp, bone_opts)
         kp[..., 2] = torch.where(solved.bool(), kp[..., 2], torch.zeros_like(kp[..., 2]))          # (unsolved: a lost detection from here on)
     est_local, _, valid = engine.lift_keypoints(kp, depth)
     seen = torch.stack([valid[lo:hi].bool().any(dim=0) for lo, hi in bounds]).cpu().numpy()
@@ -760,22 +781,18 @@ def lift_peaks(engine, heat, depth, bounds, spans, bone_opts=None, min_peak=0.0)
         lost = np.nonzero(~row)[0]
         if len(lost):
             raise ValueError("joints %s have no usable detection in the chunk [%d, %d): nothing to interpolate them from" % (lost.tolist(), a, b))
-    if len({hi - lo for lo, hi in bounds}) == 1:
-        engine.fill_missing(est_local, valid, len(bounds))
-    else:
-        for lo, hi in bounds:
-            engine.fill_missing(est_local[lo:hi], valid[lo:hi], 1)
+    fill_chunks(engine, est_local, valid, bounds)
     return est_local, report
 
 
 def prepare_spans(slam_result_path, heatmap_dir, depth_dir, gt_path, spans, fps, mat_start_frame, camera_model_path=None, device=None,
-                  timings=None, scale=None, lag=None, tau=0.10, min_pairs=50, bridge=None, depth=None, bones=None, neck_depth=None,
-                  min_peak=None, peaks=None, knot=None, stiffness=1.0):
+                  timings=None, scale=None, lag=None, tau=CameraRoute.TAU, min_pairs=CameraRoute.MIN_PAIRS, bridge=None, depth=None, bones=None,
+                  neck_depth=None, min_peak=None, peaks=None, knot=None, stiffness=CameraRoute.STIFFNESS):
     """Every (start_frame, end_frame) of `spans` as one chunk, each prepared on its own as `main` does, all of them through the
     device together: stage -> gem_mat_frames -> lift -> head joints to the host -> per-chunk scale and cameras -> cameras up ->
     gem_prepare_global.  -> Recording.  `gt_path` None and `scale` given: a recording without ground truth -- the cameras come from
     `scaled_cameras`, nothing goes to the host in between, `mat_start_frame` is not used.  scale="auto": the scale is estimated from the
-    lifted poses first (`auto_scale` with `lag`, `tau`, `min_pairs`; one small record comes back), then the same path runs with it.
+    lifted poses first (`slam_scale.estimate_scale` with `lag`, `tau`, `min_pairs`; one small record comes back), then the same path runs with it.
     scale="drift": the scale is a curve with knots `knot` frames apart (`stiffness`: of its second differences); the trajectory is rebuilt
     in metres (`slam_scale.DriftEstimate.metric_rows`) and the same path runs with it at scale 1.
     `bridge`: None, or the longest stretch of lost SLAM tracking, in seconds, whose cameras are invented (True: 1 s; `slam_bridge`,
@@ -785,9 +802,11 @@ def prepare_spans(slam_result_path, heatmap_dir, depth_dir, gt_path, spans, fps,
     uploaded; the maps' sub-pixel peaks (`heatmap_peaks`, joints whose peak is below `min_peak` unusable) are given depths by the bone
     solve (`bone_depths` with `bone_depth.options(bones, neck_depth=neck_depth)`), lifted and filled as detections are (`lift_peaks`),
     and the Recording carries the solve's `depth_report`.  Its heat-maps are the files' own.  peaks="subpixel" with a depth directory:
-    the network's depths, lifted at the sub-pixel peak instead of the reference's 16-pixel argmax."""
-    from_bones, subpixel, bone_opts, min_peak = depth_route(depth_dir, depth, bones, neck_depth, min_peak, peaks)
-    stage = RecordingStage(gt_path, scale, bridge, spans, fps, lag, tau, min_pairs, knot, stiffness)
+    the network's depths, lifted at the sub-pixel peak instead of the reference's 16-pixel argmax.  Every argument is checked before a
+    file or the device is touched: the camera route's (`CameraRoute`), then the depth route's (`depth_route`)."""
+    stage = RecordingStage(CameraRoute(gt_path, scale, bridge, lag, tau, min_pairs, knot, stiffness), spans, fps)
+    depths = depth_route(depth_dir, depth, bones, neck_depth, min_peak, peaks)
+    from_bones = depths.from_bones
     import torch
     from .camera import DEFAULT_CALIBRATION
     lap = Laps(timings)          # developer timing (tools/prepare_bench.py)
@@ -819,8 +838,8 @@ def prepare_spans(slam_result_path, heatmap_dir, depth_dir, gt_path, spans, fps,
         if tuple(heat.shape[1:3]) != tuple(engine.heat_size):
             raise ValueError("heat-maps of %d x %d: the lifting kernel is built for %d x %d" % (tuple(heat.shape[1:3]) + tuple(engine.heat_size)))
         depth_report = None
-        if subpixel:
-            est_local, depth_report = lift_peaks(engine, heat, depth_d, stage.bounds, stage.spans, bone_opts, min_peak)
+        if depths.subpixel:
+            est_local, depth_report = lift_peaks(engine, heat, depth_d, stage.bounds, stage.spans, depths.bone_opts, depths.min_peak)
         else:
             est_local, _ = engine.lift_skeleton(heat, depth_d)
         stage.fix_scale(engine, est_local, lap)
@@ -830,37 +849,27 @@ def prepare_spans(slam_result_path, heatmap_dir, depth_dir, gt_path, spans, fps,
 
 
 def main(slam_result_path, heatmap_dir, depth_dir, gt_path, start_frame, end_frame, out_dir, fps, mat_start_frame=None,
-         camera_model_path=None, scale=None, lag=None, tau=0.10, min_pairs=50, bridge=None, depth=None, bones=None, neck_depth=None,
-         min_peak=None, peaks=None, knot=None, stiffness=1.0):
+         camera_model_path=None, **options):
     """The reference's `main` (:126-165): one chunk [start_frame, end_frame) -> `<out_dir>/test_data.pkl`, and the line
     `The initial mpjpe is: ...`.  Returns the one-chunk Recording (the reference returns nothing).  Without ground truth (`gt_path`
     None, `scale` given) the pickle has four keys and there is no such line; with scale="auto" one line tells the estimate and its
-    counts, and a recording that does not fix the scale is a ValueError before anything is written.  `depth`, `bones`, `neck_depth`,
-    `min_peak`, `peaks`: `prepare_spans`' (depth="bones" with depth_dir None: a recording without depth files)."""
+    counts, and a recording that does not fix the scale is a ValueError before anything is written.  `options`: `prepare_spans`'."""
     rec = prepare_spans(slam_result_path, heatmap_dir, depth_dir, gt_path, [(start_frame, end_frame)], fps,
-                        start_frame if mat_start_frame is None else mat_start_frame, camera_model_path, scale=scale, lag=lag, tau=tau,
-                        min_pairs=min_pairs, knot=knot, stiffness=stiffness, bridge=bridge, depth=depth, bones=bones, neck_depth=neck_depth, min_peak=min_peak, peaks=peaks)
+                        start_frame if mat_start_frame is None else mat_start_frame, camera_model_path, **options)
     print_report(rec, sequence=False)
     rec.write_chunk(0, out_dir)
     return rec
 
 
 def prepare_sequence(slam_result_path, heatmap_dir, depth_dir, gt_path, total_start_frame, total_end_frame, fps=25, mat_start_frame=None,
-                     test_size=100, out_root=None, camera_model_path=None, verbose=True, scale=None, lag=None, tau=0.10, min_pairs=50,
-                     bridge=None, depth=None, bones=None, neck_depth=None, min_peak=None, peaks=None, knot=None, stiffness=1.0):
+                     test_size=100, out_root=None, camera_model_path=None, verbose=True, **options):
     """The reference's chunk loop (:176-190): chunks of `test_size` frames from `total_start_frame` (see `chunk_spans` for the
     chunk it drops), `mat_start_frame` defaulting to `total_start_frame` as there.  All chunks go through the device together,
     each prepared on its own.  Returns the Recording; with `out_root`, `data_start_{a}_end_{b}/test_data.pkl` are written too.
-    Exactly one of `gt_path` and `scale` is given (else ValueError, before anything else happens): with `scale` the recording has no
-    ground truth (`prepare_spans`); scale="auto" estimates it from the foot contacts (`lag`, `tau`, `min_pairs`: `slam_scale`).  `bridge`:
-    seconds of lost SLAM tracking to bridge (`slam_bridge`), without ground truth only.  `depth`, `bones`, `neck_depth`, `min_peak`,
-    `peaks`: `prepare_spans`' (depth="bones" with depth_dir None: a recording without depth files)."""
-    gt_or_scale(gt_path, scale)
-    depth_route(depth_dir, depth, bones, neck_depth, min_peak, peaks)
+    `options`: `prepare_spans`' keywords, handed on as they are; what does not go together is its ValueError, before anything else happens."""
     spans = chunk_spans(total_start_frame, total_end_frame, test_size)
     rec = prepare_spans(slam_result_path, heatmap_dir, depth_dir, gt_path, spans, fps,
-                        total_start_frame if mat_start_frame is None else mat_start_frame, camera_model_path, scale=scale, lag=lag, tau=tau,
-                        min_pairs=min_pairs, knot=knot, stiffness=stiffness, bridge=bridge, depth=depth, bones=bones, neck_depth=neck_depth, min_peak=min_peak, peaks=peaks)
+                        total_start_frame if mat_start_frame is None else mat_start_frame, camera_model_path, **options)
     if verbose:
         print_report(rec)
     if out_root is not None:
@@ -869,33 +878,29 @@ def prepare_sequence(slam_result_path, heatmap_dir, depth_dir, gt_path, total_st
 
 
 def prepare_continuous(slam_result_path, heatmap_dir, depth_dir, gt_path, total_start_frame, total_end_frame, fps=25, mat_start_frame=None,
-                       camera_model_path=None, verbose=True, scale=None, lag=None, tau=0.10, min_pairs=50, bridge=None, depth=None, bones=None,
-                       neck_depth=None, min_peak=None, peaks=None, knot=None, stiffness=1.0):
+                       camera_model_path=None, verbose=True, **options):
     """`prepare_sequence` for a recording that is optimised as one motion (`continuous.optimize_continuous`): the
     ONE span [total_start_frame, total_end_frame) as one chunk -- no chunk loop, so no tail is lost, and with a ground truth one Umeyama
     scale over the whole span.  The other arguments as there.  -> a Recording that is continuous already."""
-    gt_or_scale(gt_path, scale)
-    depth_route(depth_dir, depth, bones, neck_depth, min_peak, peaks)
     rec = prepare_spans(slam_result_path, heatmap_dir, depth_dir, gt_path, [(total_start_frame, total_end_frame)], fps,
-                        total_start_frame if mat_start_frame is None else mat_start_frame, camera_model_path, scale=scale, lag=lag, tau=tau,
-                        min_pairs=min_pairs, knot=knot, stiffness=stiffness, bridge=bridge, depth=depth, bones=bones, neck_depth=neck_depth, min_peak=min_peak, peaks=peaks)
+                        total_start_frame if mat_start_frame is None else mat_start_frame, camera_model_path, **options)
     if verbose:
         print_report(rec)
     return rec
 
 
-def add_recording_options(p):
-    """The options every preparation command line has (`prepare`, `detections`): the trajectory, what fixes the SLAM scale, the
-    frames, the chunks and what to do with them."""
+def add_track_options(p, gt_help="ground-truth pickle (it fixes the SLAM scale)", camera=True):
+    """The options of every command line that makes a recording's cameras (`prepare`, `detections`, `continuous`): the trajectory, what
+    fixes the SLAM scale (`gt_help`: what the command does with a ground truth), the frames and the calibration (camera=False: the
+    caller declares `--camera` itself, further down its help).  `track_arguments` turns them into the camera route's keywords."""
     from .camera import DEFAULT_CALIBRATION
-    from .slam_scale import scale_arg
+    from .slam_scale import add_drift_options, scale_arg
     p.add_argument("--slam", required=True, help="SLAM trajectory: lines `time tx ty tz qx qy qz qw`")
     how = p.add_mutually_exclusive_group(required=True)
-    how.add_argument("--gt", default=None, help="ground-truth pickle (it fixes the SLAM scale)")
+    how.add_argument("--gt", default=None, help=gt_help)
     how.add_argument("--scale", type=scale_arg, default=None, help="the SLAM scale of a recording without ground truth (a metric SLAM: 1), "
                                                                   "`auto`: estimate it from the foot contacts, or `drift`: follow a "
                                                                   "scale that creeps over the recording")
-    from .slam_scale import add_drift_options
     add_drift_options(p)
     p.add_argument("--bridge", nargs="?", type=float, const=1.0, default=None, metavar="SECONDS",
                    help="with --scale: invent the cameras of stretches of lost SLAM tracking up to this long (default 1 s)")
@@ -903,9 +908,24 @@ def add_recording_options(p):
     p.add_argument("--end", required=True, type=int)
     p.add_argument("--fps", type=float, default=25)
     p.add_argument("--mat_start", type=int, default=None, help="frame id of the GT pickle's first entry (default: --start)")
+    if camera:
+        p.add_argument("--camera", default=DEFAULT_CALIBRATION)
+
+
+def track_arguments(p, a):
+    """The parsed options that decide the camera route, as the routes' keywords: `gt_path`, `scale`, `knot` in FRAMES and `stiffness`
+    (`slam_scale.drift_options`: the rules of --scale drift, as parser errors), and of `bridge`, `lag`, `tau`, `min_pairs` what the command has."""
+    from .slam_scale import drift_options
+    return dict({k: getattr(a, k) for k in ("bridge", "lag", "tau", "min_pairs") if hasattr(a, k)}, gt_path=a.gt, scale=a.scale, **drift_options(p, a))
+
+
+def add_recording_options(p):
+    """The options every preparation command line has (`prepare`, `detections`): the track's, the chunks and what to do with them."""
+    from .camera import DEFAULT_CALIBRATION
+    add_track_options(p, camera=False)
     p.add_argument("--test_size", type=int, default=100)
     p.add_argument("--out", default=None, help="directory for data_start_{a}_end_{b}/test_data.pkl")
-    p.add_argument("--camera", default=DEFAULT_CALIBRATION)
+    p.add_argument("--camera", default=DEFAULT_CALIBRATION)          # (where these commands' help has always listed it)
     p.add_argument("--optimize", action="store_true", help="optimise the recording right away (no pickle in between)")
 
 
@@ -919,19 +939,31 @@ def parse_recording_options(p, argv=None):
     return a
 
 
-def add_depth_route_options(p):
-    """Where a heat-map recording's depths come from (`prepare`, `slam_scale`): --depths DIR, or --depth_from bones with --bones,
-    --neck_depth and --min_peak; --peaks for the lift with depth files."""
+def add_depth_route_options(p, depth_file=None, peaks=True,
+                            depth_from="bones: a pose network without a depth head -- the depths are solved from the bone lengths at the maps' "
+                                       "sub-pixel peaks (DESIGN.md section 6r); excludes --depths",
+                            min_peak="with --depth_from bones: a joint whose map peaks below P is treated as not detected (default 0)"):
+    """Where a heat-map recording's depths come from (`prepare`, `continuous`, `slam_scale`): --depths DIR, or --depth_from bones with
+    --bones, --neck_depth and --min_peak; --peaks for the lift with depth files (not with peaks=False).  `depth_file`: the help of a
+    `--depth FILE.npy` behind --depths, for a command that takes detections too; `depth_from`, `min_peak`: their help texts."""
     from .bone_depth import add_bone_depth_options
     p.add_argument("--depths", default=None, metavar="DIR", help="directory of per-frame depth .mat files")
-    p.add_argument("--depth_from", default=None, choices=("bones",), help="bones: a pose network without a depth head -- the depths are "
-                                                                         "solved from the bone lengths at the maps' sub-pixel peaks "
-                                                                         "(DESIGN.md section 6r); excludes --depths")
+    if depth_file is not None:
+        p.add_argument("--depth", default=None, metavar="FILE.npy", help=depth_file)
+    p.add_argument("--depth_from", default=None, choices=("bones",), help=depth_from)
     add_bone_depth_options(p)
-    p.add_argument("--min_peak", type=float, default=None, metavar="P", help="with --depth_from bones: a joint whose map peaks below P is "
-                                                                             "treated as not detected (default 0)")
-    p.add_argument("--peaks", default=None, choices=("argmax", "subpixel"), help="with --depths: lift at the reference's 16-pixel argmax "
-                                                                                 "(default) or at the sub-pixel peak")
+    p.add_argument("--min_peak", type=float, default=None, metavar="P", help=min_peak)
+    if peaks:
+        p.add_argument("--peaks", default=None, choices=("argmax", "subpixel"), help="with --depths: lift at the reference's 16-pixel argmax "
+                                                                                     "(default) or at the sub-pixel peak")
+
+
+def depth_route_arguments(a, maps=True):
+    """The parsed options that decide where the depths come from, as the keywords of the two routes: `depth`, `bones` (the file's array),
+    `neck_depth`, and for heat-maps (`maps`; detections have neither) `min_peak` and `peaks`."""
+    from .bone_depth import bones_from_args
+    kw = dict(depth=a.depth_from, bones=bones_from_args(a), neck_depth=a.neck_depth)
+    return dict(kw, min_peak=a.min_peak, peaks=getattr(a, "peaks", None)) if maps else kw
 
 
 def check_depth_route_options(p, a):
@@ -956,14 +988,11 @@ def _parser():
 
 
 def _cli(argv=None):
-    from .bone_depth import bones_from_args
     p = _parser()
     a = parse_recording_options(p, argv)
     check_depth_route_options(p, a)
-    from .slam_scale import drift_options
-    rec = prepare_sequence(a.slam, a.heatmaps, a.depths, a.gt, a.start, a.end, a.fps, a.mat_start, a.test_size, a.out, a.camera,
-                           scale=a.scale, bridge=a.bridge, depth=a.depth_from, bones=bones_from_args(a), neck_depth=a.neck_depth,
-                           min_peak=a.min_peak, peaks=a.peaks, **drift_options(p, a))
+    rec = prepare_sequence(a.slam, a.heatmaps, a.depths, total_start_frame=a.start, total_end_frame=a.end, fps=a.fps, mat_start_frame=a.mat_start,
+                           test_size=a.test_size, out_root=a.out, camera_model_path=a.camera, **track_arguments(p, a), **depth_route_arguments(a))
     if a.optimize:
         from .whole_sequence import optimize_recording
         optimize_recording(rec, a.camera, ground_truth=a.scale is None)

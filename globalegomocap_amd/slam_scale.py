@@ -391,18 +391,15 @@ def umeyama_scales(rows, rec, gt_path, fps, gt_start):
 def _parser():
     import argparse
     from .camera import DEFAULT_CALIBRATION
+    from .prepare import add_depth_route_options
     p = argparse.ArgumentParser(description="estimate the SLAM scale of a recording from its foot contacts")
     p.add_argument("--slam", required=True, help="SLAM trajectory: lines `time tx ty tz qx qy qz qw`")
     p.add_argument("--heatmaps", default=None, metavar="DIR", help="directory of per-frame heatmap .mat files (with --depths)")
     p.add_argument("--keypoints", default=None, metavar="FILE", help=".npy / .npz of 2-D detections (`detections`)")
-    p.add_argument("--depths", default=None, metavar="DIR", help="directory of per-frame depth .mat files")
-    p.add_argument("--depth", default=None, metavar="FILE.npy", help="the joints' depths [N,15], row for row with the detections")
-    p.add_argument("--depth_from", default=None, choices=("bones",), help="bones: no depths at all -- they are solved from the bone lengths "
-                                                                         "(DESIGN.md sections 6q, 6r); excludes --depths and --depth")
-    from .bone_depth import add_bone_depth_options
-    add_bone_depth_options(p)
-    p.add_argument("--min_peak", type=float, default=None, metavar="P", help="with --heatmaps --depth_from bones: a joint whose map peaks "
-                                                                             "below P is treated as not detected (default 0)")
+    add_depth_route_options(p, depth_file="the joints' depths [N,15], row for row with the detections", peaks=False,
+                            depth_from="bones: no depths at all -- they are solved from the bone lengths (DESIGN.md sections 6q, 6r); excludes "
+                                       "--depths and --depth",
+                            min_peak="with --heatmaps --depth_from bones: a joint whose map peaks below P is treated as not detected (default 0)")
     p.add_argument("--start", required=True, type=int)
     p.add_argument("--end", required=True, type=int)
     p.add_argument("--fps", type=float, default=25)
@@ -436,16 +433,14 @@ def _cli(argv=None):
         p.error("--bones, --neck_depth and --min_peak belong to --depth_from bones")
     if a.min_peak is not None and a.heatmaps is None:
         p.error("--min_peak goes with --heatmaps: detections carry their own confidence")
-    from .bone_depth import bones_from_args
     spans = full_spans(a.start, a.end, a.test_size)
-    options = dict(lag=a.lag, tau=a.tau, min_pairs=a.min_pairs, **drift_options(p, a))
-    if a.depth_from is not None:
-        options.update(depth=a.depth_from, bones=bones_from_args(a), neck_depth=a.neck_depth)
+    track = dict(prepare.track_arguments(p, a), gt_path=None)          # (--gt is only compared with here: it never fixes the scale)
     if a.heatmaps is not None:
-        rec = prepare.prepare_spans(a.slam, a.heatmaps, a.depths, None, spans, a.fps, a.start, a.camera, scale=a.scale, min_peak=a.min_peak, **options)
+        rec = prepare.prepare_spans(a.slam, a.heatmaps, a.depths, spans=spans, fps=a.fps, mat_start_frame=a.start, camera_model_path=a.camera,
+                                    **track, **prepare.depth_route_arguments(a))
     else:
-        rec = detections.recording_from_detections(a.slam, detections.detections_from_args(a), None, a.scale, spans, a.fps,
-                                                   camera_model_path=a.camera, **options)
+        rec = detections.recording_from_detections(a.slam, detections.detections_from_args(a), spans=spans, fps=a.fps, camera_model_path=a.camera,
+                                                   **track, **prepare.depth_route_arguments(a, maps=False))
     est = rec.scale_report
     print(est.line())
     out = est.as_dict()

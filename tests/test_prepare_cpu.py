@@ -427,6 +427,16 @@ def test_the_preparation_parsers_share_their_options():
                 optimize=True)
     for m in parsers:
         assert {d: parsed[m][d] for d in SHARED_OPTIONS} == want, m
+    # the commands that take both routes declare the same options: `continuous` the track's, `slam_scale` the depth route's
+    from globalegomocap_amd import continuous, slam_scale
+    declared = lambda x: (x.option_strings, x.default, x.required, x.nargs, x.const, x.metavar, x.type, x.choices)      # noqa: E731
+    other = {x.dest: x for x in continuous._parser()._actions}
+    for dest in ("slam", "gt", "scale", "knot", "stiffness", "bridge", "start", "end", "fps", "mat_start", "camera"):
+        assert declared(a[dest]) == declared(other[dest]), dest
+        assert dest == "gt" or a[dest].help == other[dest].help, dest
+    other = {x.dest: x for x in slam_scale._parser()._actions}
+    for dest in ("depths", "depth_from", "bones", "neck_depth", "min_peak"):
+        assert declared(a[dest]) == declared(other[dest]), dest
 
 
 @pytest.mark.parametrize("module", ["prepare", "detections"])

@@ -148,15 +148,27 @@ def test_without_lost_frames_the_twin_gives_the_cameras_of_today():
 
 
 # ------------------------------------------------------------------------------------------------------------------ wiring
-def test_without_the_option_a_missing_id_is_still_refused():
+def test_without_the_option_a_missing_id_is_still_refused(monkeypatch, tmp_path):
     from globalegomocap_amd import prepare
     w, rows = T.walker_rows(30, lost=((11, 13),))
     with pytest.raises(ValueError, match=r"no line for frame ids \[11, 12\]"):
         prepare.check_trajectory(rows, 0, 30, 25.0)
-    for fn in (prepare.prepare_spans, prepare.prepare_sequence, prepare.main):
-        assert inspect.signature(fn).parameters["bridge"].default is None
+    spans_signature = inspect.signature(prepare.prepare_spans)
+    assert spans_signature.parameters["bridge"].default is None
     from globalegomocap_amd import detections
     assert inspect.signature(detections.recording_from_detections).parameters["bridge"].default is None
+    # the wrappers have no default of their own: what they are not given, `prepare_spans` is not given either
+    got = []
+
+    def spans(*args, **kwargs):
+        got.append(kwargs)
+        spans_signature.bind(*args, **kwargs)
+        return prepare.Recording([])
+    monkeypatch.setattr(prepare, "prepare_spans", spans)
+    prepare.prepare_sequence("t", "h", "d", None, 0, 30, scale=1.0)
+    with pytest.raises(IndexError):          # (`main` writes chunk 0 of what it is given back)
+        prepare.main("t", "h", "d", None, 0, 30, str(tmp_path), 25, scale=1.0)
+    assert got == [{"scale": 1.0}] * 2
 
 
 def test_the_option_is_refused_with_ground_truth_and_parsed_on_both_command_lines(tmp_path):

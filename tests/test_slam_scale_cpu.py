@@ -142,7 +142,9 @@ def test_gt_or_scale_passes_auto_through():
     for gt, scale in (("g", "auto"), (None, None), (None, "Auto"), (None, -1.0), (None, float("nan"))):
         with pytest.raises(ValueError):
             prepare.gt_or_scale(gt, scale)
-    assert prepare.auto_scale(None, None, [], 25, 1.25) == (1.25, None)
+    stage = prepare.RecordingStage(prepare.CameraRoute(scale=1.25), [], 25)
+    stage.fix_scale(None, None)
+    assert (stage.scale, stage.scale_report) == (1.25, None)
     rec = prepare.Recording([])
     assert rec.scale is None and rec.scale_report is None
 

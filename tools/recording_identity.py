@@ -6,7 +6,10 @@
 A 208-frame walker (`synth_walk`, SLAM scale 0.6) as eight 26-frame chunks: once as the pose network's .mat files (heat-maps with one
 paraboloid per joint) through `prepare.prepare_sequence` and, for its first chunk, `prepare.main`; once as 2-D detections through
 `detections.recording_from_detections` and the `detections` command line.  Both under five settings: ground truth, a number,
-"auto", bridge + number and bridge + "auto" -- the bridge on a trajectory without the lines of frame ids 36 .. 40.  Hashed: every
+"auto", bridge + number and bridge + "auto" -- the bridge on a trajectory without the lines of frame ids 36 .. 40 -- and then with
+"drift" and a knot distance, with the depths from the bone lengths (no depth file, no depth array), with the sub-pixel lift of the .mat
+route beside depth files, and once as ONE span through `prepare.prepare_continuous` and `detections.continuous_from_detections`.  Every
+option is given by keyword, or as the command line spells it.  Hashed: every
 chunk's heat, est_local, est_global, cams and gt, the origins, the scale, both reports' as_dict(), what was printed, and the pickles
 `write_chunks` / `write_chunk` left.  A refusal is hashed as its type and text.  With --parent the sums are compared with those file
 holds and both runs are written to --json (`profiles/recording_identity.json`); the exit status tells whether they are equal.
@@ -28,7 +31,12 @@ sys.path.insert(0, REPO)
 
 N, SIZE, FPS, SCALE, LOST = 208, 26, 25, 0.6, (36, 41)
 SETTINGS = {"ground truth": dict(gt=True), "number": dict(scale=0.6), "auto": dict(scale="auto"),
-            "bridge + number": dict(scale=0.6, bridge=1.0, holed=True), "bridge + auto": dict(scale="auto", bridge=1.0, holed=True)}
+            "bridge + number": dict(scale=0.6, bridge=1.0, holed=True), "bridge + auto": dict(scale="auto", bridge=1.0, holed=True),
+            # `more`: keywords of every route (`more_cli`: as the command line spells them); `mat`: of the .mat route alone
+            "drift": dict(scale="drift", more=dict(knot=52), more_cli=["--knot", "2.08"]),
+            "bones": dict(scale=0.6, more=dict(depth="bones"), more_cli=["--depth_from", "bones"], no_depth_dir=True),
+            "subpixel": dict(scale=0.6, mat=dict(peaks="subpixel")),
+            "one span": dict(scale="auto", one_span=True)}
 
 
 def sha(x):
@@ -46,6 +54,7 @@ def recording_sums(rec):
            "scale_report": sha(None if rec.scale_report is None else rec.scale_report.as_dict()),
            "bridge_report": sha(None if rec.bridge_report is None else rec.bridge_report.as_dict()),
            "bridged": sha(None if rec.bridged is None else np.concatenate(rec.bridged)),
+           "depth_report": sha(None if rec.depth_report is None else rec.depth_report.as_dict()),
            "initial_mpjpe": sha([c.initial_mpjpe for c in rec.chunks])}
     for i, c in enumerate(rec.chunks):
         for k in ("heat", "est_local", "est_global", "cams", "gt"):
@@ -107,15 +116,23 @@ def main():
         for name, s in SETTINGS.items():
             t = holed if s.get("holed") else traj
             g, scale, bridge = (gtp if s.get("gt") else None), s.get("scale"), s.get("bridge")
-            how = (["--gt", gtp] if g else ["--scale", str(scale)]) + (["--bridge", str(bridge)] if bridge else [])
+            how = (["--gt", gtp] if g else ["--scale", str(scale)]) + (["--bridge", str(bridge)] if bridge else []) + s.get("more_cli", [])
+            more = s.get("more", {})
+            mat = dict(more, **s.get("mat", {}))
+            depths = None if s.get("no_depth_dir") else dd
             routes = {
-                "prepare_sequence": lambda o: P.prepare_sequence(t, hd, dd, g, 0, N + 1, fps=FPS, test_size=SIZE, out_root=o, scale=scale,
-                                                                 min_pairs=10, bridge=bridge),
-                "prepare.main": lambda o: P.main(t, hd, dd, g, 0, SIZE, o, FPS, scale=scale, min_pairs=5, bridge=bridge),
-                "recording_from_detections": lambda o: D.recording_from_detections(t, det, g, scale, spans, FPS, min_pairs=30, bridge=bridge),
+                "prepare_sequence": lambda o: P.prepare_sequence(t, hd, depths, g, 0, N + 1, fps=FPS, test_size=SIZE, out_root=o, scale=scale,
+                                                                 min_pairs=10, bridge=bridge, **mat),
+                "prepare.main": lambda o: P.main(t, hd, depths, g, 0, SIZE, o, FPS, scale=scale, min_pairs=5, bridge=bridge, **mat),
+                "recording_from_detections": lambda o: D.recording_from_detections(t, det, g, scale, spans, FPS, min_pairs=30, bridge=bridge, **more),
                 "detections command line": lambda o: D._cli(["--slam", t, "--keypoints", det, "--start", "0", "--end", str(N + 1), "--fps", str(FPS),
                                                             "--test_size", str(SIZE), "--out", o] + how),
             }
+            if s.get("one_span"):
+                routes = {
+                    "prepare_continuous": lambda o: P.prepare_continuous(t, hd, dd, g, 0, N, fps=FPS, scale=scale, min_pairs=10),
+                    "continuous_from_detections": lambda o: D.continuous_from_detections(t, det, g, scale, 0, N, FPS, min_pairs=30),
+                }
             for route, fn in routes.items():
                 out_root = os.path.join(work, "out")
                 sums["%s / %s" % (name, route)] = run(lambda: fn(out_root), out_root)
@@ -123,7 +140,7 @@ def main():
                 torch.cuda.synchronize()
     finally:
         shutil.rmtree(work, ignore_errors=True)
-    result = {"what": "sha256 of what the two routes into a Recording compute, print and write from one synthetic 208-frame walker under five "
+    result = {"what": "sha256 of what the two routes into a Recording compute, print and write from one synthetic 208-frame walker under nine "
                       "settings (tools/recording_identity.py)", "device": torch.cuda.get_device_name(0), "sums": sums}
     same = None
     if a.parent is not None:
