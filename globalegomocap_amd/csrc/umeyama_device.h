@@ -11,6 +11,14 @@ namespace gem {
 // ---------------------------------------------------------------------------------------------------
 // 3x3 SVD by one-sided Jacobi (Hestenes): A = U diag(S) V^T, columns of U/V orthonormal, S >= 0 unsorted.
 // Accurate to eps * cond(A) (no A^T A squaring).  Row-major 3x3 arrays.
+// U is orthonormal for every finite A and no element of it is read before it is written.  A column k of U is a[:,k] / S[k] where
+// S[k] > 1e-14 * max(S) and S[k] > 0; the others are completed by a fixed rule:
+//   rank 3  nothing to complete
+//   rank 2  the missing column is the cross product of the other two in cyclic order (det U = +1)
+//   rank 1  with u the one column there is, at k: column k+1 = u x e / |u x e|, e the coordinate axis with the smallest |u . e| (the
+//           first of equals), column k+2 = u x column k+1, indices mod 3 (det U = +1)
+//   rank 0  U = I
+// V is a product of plane rotations: orthonormal, det V = +1.  (tests/umeyama_twin.py is the float64 twin, step for step.)
 __device__ inline void svd3(const double* A, double* U, double* S, double* V) {
     double a[9];
     for (int i = 0; i < 9; ++i) { a[i] = A[i]; V[i] = (i % 4 == 0) ? 1.0 : 0.0; }
@@ -44,20 +52,41 @@ __device__ inline void svd3(const double* A, double* U, double* S, double* V) {
         S[k] = sqrt(a[k] * a[k] + a[3 + k] * a[3 + k] + a[6 + k] * a[6 + k]);
         smax = S[k] > smax ? S[k] : smax;
     }
-    int bad = -1;
+    int bad = -1, good = -1, n_good = 0;
     for (int k = 0; k < 3; ++k) {
         if (S[k] > 1e-14 * smax && S[k] > 0.0) {
             for (int r = 0; r < 3; ++r) U[3 * r + k] = a[3 * r + k] / S[k];
+            good = k;
+            ++n_good;
         } else {
             bad = k;
         }
     }
-    if (bad >= 0) {          // rank-deficient (coplanar points): complete U with the cross product of the other two
+    if (bad >= 0) S[bad] = 0.0;          // (the last one below the threshold; an earlier one keeps its value, at most 1e-14 * smax)
+    if (n_good == 2) {       // rank 2 (coplanar points): complete U with the cross product of the other two
         const int i = (bad + 1) % 3, j = (bad + 2) % 3;
         U[bad] = U[3 + i] * U[6 + j] - U[6 + i] * U[3 + j];
         U[3 + bad] = U[6 + i] * U[j] - U[i] * U[6 + j];
         U[6 + bad] = U[i] * U[3 + j] - U[3 + i] * U[j];
-        S[bad] = 0.0;
+    } else if (n_good == 1) {          // rank 1 (collinear points): u, then u x e normalised (e: the first axis least aligned with u), then their cross product
+        const int i = (good + 1) % 3, j = (good + 2) % 3;
+        const double u[3] = {U[good], U[3 + good], U[6 + good]};
+        int e = 0;
+        for (int r = 1; r < 3; ++r)
+            if (fabs(u[r]) < fabs(u[e])) e = r;
+        const int e1 = (e + 1) % 3, e2 = (e + 2) % 3;
+        double v[3];                   // u x e: zero along e, and at least sqrt(2/3) long
+        v[e] = 0.0;
+        v[e1] = u[e2];
+        v[e2] = -u[e1];
+        const double n = sqrt(v[e1] * v[e1] + v[e2] * v[e2]);
+        for (int r = 0; r < 3; ++r) v[r] /= n;
+        U[i] = v[0]; U[3 + i] = v[1]; U[6 + i] = v[2];
+        U[j] = u[1] * v[2] - u[2] * v[1];
+        U[3 + j] = u[2] * v[0] - u[0] * v[2];
+        U[6 + j] = u[0] * v[1] - u[1] * v[0];
+    } else if (n_good == 0) {          // rank 0 (the zero matrix): U = I
+        for (int r = 0; r < 9; ++r) U[r] = (r % 4 == 0) ? 1.0 : 0.0;
     }
 }
 
