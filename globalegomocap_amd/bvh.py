@@ -17,6 +17,7 @@ from collections import namedtuple
 import numpy as np
 
 from . import _capi
+from ._binding import _ptr, _stream, check_tensor
 from .meshes import _alignment, _sequence, _upright, result_poses
 
 Layout = namedtuple("Layout", "nodes channels field_bytes frame_bytes")
@@ -58,22 +59,13 @@ def tables():
     return _tables
 
 
-def _call(engine, fn, *args):
-    from .engine import _stream
-    _capi.check(fn(*(args + (_stream(),))), engine.lib)
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-
-
 def rest_lengths(engine, seq_d, crt=None):
     """The rest length of every node's bone (gem_bvh_rest): the mean of |pos(node) - pos(parent)| over the frames of `seq_d` [F,15,3]
     (contiguous float64 device tensor, F >= 1), the joints moved by `crt` ([13] from `engine.sequence_align`) first when given ->
     [19] f64 on the device, 0 for the root and the helpers.  No synchronisation; the same bits on every call."""
     import torch
     out = torch.empty(layout().nodes, device=seq_d.device, dtype=torch.float64)
-    _call(engine, engine.lib.gem_bvh_rest, _ptr(seq_d), seq_d.shape[0], _ptr(crt), _ptr(out))
+    _capi.check(engine.lib.gem_bvh_rest(_ptr(seq_d), seq_d.shape[0], _ptr(crt), _ptr(out), _stream()), engine.lib)
     return out
 
 
@@ -82,7 +74,8 @@ def channels(engine, seq_d, crt, rest, unit_scale=100.0):
     19 nodes' (Z, X, Y) Euler angles in degrees.  Arguments as `rest_lengths`; `rest` is its result.  No synchronisation."""
     import torch
     out = torch.empty(seq_d.shape[0], layout().channels, device=seq_d.device, dtype=torch.float64)
-    _call(engine, engine.lib.gem_bvh_channels, _ptr(seq_d), seq_d.shape[0], _ptr(crt), _ptr(rest), C.c_double(float(unit_scale)), _ptr(out))
+    _capi.check(engine.lib.gem_bvh_channels(_ptr(seq_d), seq_d.shape[0], _ptr(crt), _ptr(rest), C.c_double(float(unit_scale)), _ptr(out), _stream()),
+                engine.lib)
     return out
 
 
@@ -98,16 +91,14 @@ def format_fields(engine, values, values_per_line, bad, out=None):
     after every `values_per_line`-th -> uint8 device tensor [values.numel() * 16], `out` when given (16-byte aligned).  nan, inf and
     values beyond +-9999999.999999 raise `bad` (`new_counter`).  No synchronisation."""
     import torch
-    if not (torch.is_tensor(values) and values.is_cuda and values.dtype == torch.float64 and values.is_contiguous()):
-        raise TypeError("format_fields wants a contiguous float64 device tensor")
+    check_tensor(values, torch.float64, error=TypeError("format_fields wants a contiguous float64 device tensor"))
     n, fb = values.numel(), layout().field_bytes
     if out is None:
         out = torch.empty(n * fb, device=values.device, dtype=torch.uint8)
-    if not (torch.is_tensor(out) and out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.numel() >= n * fb):
-        raise ValueError("format_fields: out must be a contiguous uint8 device tensor of at least %d bytes" % (n * fb))
-    if not (torch.is_tensor(bad) and bad.is_cuda and bad.dtype == torch.int64 and bad.is_contiguous() and bad.numel() == 2):
-        raise TypeError("format_fields: bad must be an int64 device tensor of 2 values (new_counter)")
-    _call(engine, engine.lib.gem_format_fields, _ptr(values), n, int(values_per_line), _ptr(out), _ptr(bad))
+    check_tensor(out, torch.uint8, at_least=n * fb,
+                 error=ValueError("format_fields: out must be a contiguous uint8 device tensor of at least %d bytes" % (n * fb)))
+    check_tensor(bad, torch.int64, numel=2, error=TypeError("format_fields: bad must be an int64 device tensor of 2 values (new_counter)"))
+    _capi.check(engine.lib.gem_format_fields(_ptr(values), n, int(values_per_line), _ptr(out), _ptr(bad), _stream()), engine.lib)
     return out[:n * fb]
 
 

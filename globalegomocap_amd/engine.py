@@ -9,6 +9,7 @@ import numpy as np
 import torch
 
 from . import _capi
+from ._binding import _ptr, _stream, check_tensor, check_tensors          # noqa: F401 (_ptr, _stream: the tests' way in)
 from .camera import FisheyeCamera, DEFAULT_CALIBRATION
 from .skeleton import KINEMATIC_PARENTS, N_JOINTS
 from .vae import VAEShape, flatten_state_dict
@@ -16,12 +17,14 @@ from .vae import VAEShape, flatten_state_dict
 LOCAL_STAGE, GLOBAL_STAGE = _capi.STAGE_LOCAL, _capi.STAGE_GLOBAL
 
 
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+def _check_seq_crt(what, frames, seq, crt):
+    """What `skeleton_mesh`, `skeleton_capsules` and `project_sequence` ask of their sequence [`frames`,15,3] f64 and of the (c, R, t) it
+    is moved by, where one is given."""
+    check_tensor(seq, torch.float64, error=TypeError("%s wants a contiguous float64 device tensor" % what))
+    check_tensor(seq, torch.float64, (None, N_JOINTS, 3),
+                 error=ValueError("%s: seq must be [%s,%d,3], got %s" % (what, frames, N_JOINTS, tuple(seq.shape))))
+    if crt is not None:
+        check_tensor(crt, torch.float64, numel=13, error=TypeError("%s: crt must be a contiguous float64 device tensor of 13 values" % what))
 
 
 def energy_weights(w3d, smooth, bone, vae, reproj):
@@ -412,9 +415,10 @@ class WindowEngine:
         """calculate_errors for each of `n_chunks` equally long sequences laid end to end (device f64 tensors [n_chunks*F,J,3]):
         [n_chunks, 17+J] f64 on the device, one library call, no synchronisation."""
         from .skeleton import mean_bone_length_mm
-        for x in (est, mid, opt, gt):
-            if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float64 and x.is_contiguous() and x.shape == est.shape):
-                raise TypeError("calculate_errors_chunks wants equally shaped contiguous float64 device tensors")
+        wrong = TypeError("calculate_errors_chunks wants equally shaped contiguous float64 device tensors")
+        check_tensor(est, torch.float64, error=wrong)
+        for x in (mid, opt, gt):
+            check_tensor(x, torch.float64, tuple(est.shape), error=wrong)
         total = est.numel() // (N_JOINTS * 3)
         if n_chunks < 1 or total % n_chunks:
             raise ValueError("calculate_errors_chunks: %d frames do not split into %d chunks" % (total, n_chunks))
@@ -431,10 +435,8 @@ class WindowEngine:
         seq (and ref, optional) [n_chunks*fpc,J,3] f64, cams [F,4,4] f64 and heat [F,H,W,J] f32 the frame buffers, frame0 [n_chunks]
         i64 each chunk's first frame in them, mean_bone [n_chunks,J] f32 -- contiguous device tensors.  -> [n_chunks,4] f64 on the
         device in the order of QUALITY_KEYS (displacement NaN without `ref`), one library call, no synchronisation."""
-        for x, dt in ((seq, torch.float64), (ref, torch.float64), (cams, torch.float64), (heat, torch.float32), (frame0, torch.int64),
-                      (mean_bone, torch.float32)):
-            if x is not None and not (torch.is_tensor(x) and x.is_cuda and x.dtype == dt and x.is_contiguous()):
-                raise TypeError("sequence_quality wants contiguous device tensors of the documented dtypes")
+        check_tensors("sequence_quality", (seq, torch.float64, None), (ref, torch.float64, None), (cams, torch.float64, None),
+                      (heat, torch.float32, None), (frame0, torch.int64, None), (mean_bone, torch.float32, None))
         total = seq.numel() // (N_JOINTS * 3)
         if n_chunks < 1 or total % n_chunks or total == 0 or seq.numel() != total * N_JOINTS * 3:
             raise ValueError("sequence_quality: %d frames do not split into %d chunks" % (total, n_chunks))
@@ -455,8 +457,7 @@ class WindowEngine:
         src, dst [F,J,3] (or [N,3]) f64 contiguous device tensors of one shape -> [13] f64 on the device: c, R (row-major), t with
         dst ~ c * (src @ R) + t.  No synchronisation; the same bits on every call."""
         for x in (src, dst):
-            if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float64 and x.is_contiguous()):
-                raise TypeError("sequence_align wants contiguous float64 device tensors")
+            check_tensor(x, torch.float64, error=TypeError("sequence_align wants contiguous float64 device tensors"))
         if src.shape != dst.shape or src.numel() == 0 or src.shape[-1] != 3:
             raise ValueError("sequence_align: src and dst must be equally shaped, non-empty [...,3], got %s and %s" % (tuple(src.shape), tuple(dst.shape)))
         out = torch.empty(13, device=self.device, dtype=torch.float64)
@@ -468,18 +469,12 @@ class WindowEngine:
         ([13] from `sequence_align`) first when given (gem_skeleton_mesh) -> uint8 [F, stride] on the device, `out` when given (its
         row stride is the frame stride: at least the vertex block, a multiple of 16, 16-byte aligned rows).  No synchronisation."""
         from . import meshes
-        if not (torch.is_tensor(seq) and seq.is_cuda and seq.dtype == torch.float64 and seq.is_contiguous()):
-            raise TypeError("skeleton_mesh wants a contiguous float64 device tensor")
-        if seq.dim() != 3 or tuple(seq.shape[1:]) != (N_JOINTS, 3):
-            raise ValueError("skeleton_mesh: seq must be [F,%d,3], got %s" % (N_JOINTS, tuple(seq.shape)))
-        if crt is not None and not (torch.is_tensor(crt) and crt.is_cuda and crt.dtype == torch.float64 and crt.is_contiguous() and crt.numel() == 13):
-            raise TypeError("skeleton_mesh: crt must be a contiguous float64 device tensor of 13 values")
+        _check_seq_crt("skeleton_mesh", "F", seq, crt)
         F, block = seq.shape[0], meshes.layout().vertex_bytes
         if out is None:
             out = torch.empty(F, block, device=self.device, dtype=torch.uint8)
-        if not (torch.is_tensor(out) and out.is_cuda and out.dtype == torch.uint8 and out.dim() == 2 and out.shape[0] == F
-                and out.shape[1] >= block and out.stride(1) == 1):
-            raise ValueError("skeleton_mesh: out must be a uint8 device tensor [%d, >= %d] with contiguous rows" % (F, block))
+        check_tensor(out, torch.uint8, rows=(F, block),
+                     error=ValueError("skeleton_mesh: out must be a uint8 device tensor [%d, >= %d] with contiguous rows" % (F, block)))
         _capi.check(self.lib.gem_skeleton_mesh(_ptr(seq), F, _ptr(crt), _ptr(out), out.stride(0), _stream()), self.lib)
         return out
 
@@ -487,12 +482,7 @@ class WindowEngine:
         """The 30 capsules of every frame of `seq` [F,J,3] f64 (contiguous device tensor), behind `crt` ([13] from `sequence_align`)
         when given (gem_skeleton_capsules): geometry [F*30,7] f64 (a, b, r) and colours [F*30] int32 (0x00BBGGRR; `rgb_joint` for the
         15 joints, `rgb_line` for the 15 lines), on the device.  No synchronisation."""
-        if not (torch.is_tensor(seq) and seq.is_cuda and seq.dtype == torch.float64 and seq.is_contiguous()):
-            raise TypeError("skeleton_capsules wants a contiguous float64 device tensor")
-        if seq.dim() != 3 or tuple(seq.shape[1:]) != (N_JOINTS, 3):
-            raise ValueError("skeleton_capsules: seq must be [F,%d,3], got %s" % (N_JOINTS, tuple(seq.shape)))
-        if crt is not None and not (torch.is_tensor(crt) and crt.is_cuda and crt.dtype == torch.float64 and crt.is_contiguous() and crt.numel() == 13):
-            raise TypeError("skeleton_capsules: crt must be a contiguous float64 device tensor of 13 values")
+        _check_seq_crt("skeleton_capsules", "F", seq, crt)
         F = seq.shape[0]
         geom = torch.empty(F * 30, 7, device=self.device, dtype=torch.float64)
         rgb = torch.empty(F * 30, device=self.device, dtype=torch.int32)
@@ -506,23 +496,19 @@ class WindowEngine:
         (rows at least the image's bytes, 16-byte aligned, a row stride that is a multiple of 16).  `first`: ascending integers
         (a sequence, or an int32 device tensor).  want_ids: -> (out, ids int32 [n_images,H,W], depth f64 [n_images,H,W]).  Waits for
         the stream once (the library reads `first` back before it launches)."""
-        if not (torch.is_tensor(geom) and geom.is_cuda and geom.dtype == torch.float64 and geom.is_contiguous() and geom.dim() == 2
-                and geom.shape[1] == 7):
-            raise TypeError("render_capsules: geom must be a contiguous float64 device tensor [n,7]")
-        if not (torch.is_tensor(rgb) and rgb.is_cuda and rgb.dtype == torch.int32 and rgb.is_contiguous() and tuple(rgb.shape) == (geom.shape[0],)):
-            raise TypeError("render_capsules: rgb must be a contiguous int32 device tensor [n]")
+        check_tensor(geom, torch.float64, (None, 7), error=TypeError("render_capsules: geom must be a contiguous float64 device tensor [n,7]"))
+        check_tensor(rgb, torch.int32, (geom.shape[0],), error=TypeError("render_capsules: rgb must be a contiguous int32 device tensor [n]"))
         if not torch.is_tensor(first):
             first = torch.tensor([int(f) for f in first], dtype=torch.int32).to(self.device)
-        if not (first.is_cuda and first.dtype == torch.int32 and first.is_contiguous() and first.dim() == 1 and first.numel() >= 1):
-            raise TypeError("render_capsules: first must be a contiguous int32 device tensor [n_images + 1]")
+        check_tensor(first, torch.int32, (None,), at_least=1,
+                     error=TypeError("render_capsules: first must be a contiguous int32 device tensor [n_images + 1]"))
         n = first.numel() - 1
         lay = (C.c_int64 * 3)()
         _capi.check(self.lib.gem_render_layout(view.width, view.height, lay), self.lib)
         if out is None:
             out = torch.empty(n, lay[2], device=self.device, dtype=torch.uint8)
-        if not (torch.is_tensor(out) and out.is_cuda and out.dtype == torch.uint8 and out.dim() == 2 and out.shape[0] == n
-                and out.shape[1] >= lay[1] and out.stride(1) == 1):
-            raise ValueError("render_capsules: out must be a uint8 device tensor [%d, >= %d] with contiguous rows" % (n, lay[1]))
+        check_tensor(out, torch.uint8, rows=(n, lay[1]),
+                     error=ValueError("render_capsules: out must be a uint8 device tensor [%d, >= %d] with contiguous rows" % (n, lay[1])))
         ids = torch.empty(n, view.height, view.width, device=self.device, dtype=torch.int32) if want_ids else None
         depth = torch.empty(n, view.height, view.width, device=self.device, dtype=torch.float64) if want_ids else None
         _capi.check(self.lib.gem_render_capsules(_ptr(geom), _ptr(rgb), geom.shape[0], _ptr(first), n, C.byref(view), _ptr(out),
@@ -534,18 +520,11 @@ class WindowEngine:
         when given, seen through `cams` [n,4,4] f64 (rigid camera-to-world; None: the points are in the camera's frame) with the
         arithmetic of the reprojection term (gem_project_sequence) -> [n,J,2] f32 on the device, pixels of the
         1280 x 1024 image; a joint on the optical axis gives a pair that is not finite.  No synchronisation."""
-        if not (torch.is_tensor(seq) and seq.is_cuda and seq.dtype == torch.float64 and seq.is_contiguous()):
-            raise TypeError("project_sequence wants a contiguous float64 device tensor")
-        if seq.dim() != 3 or tuple(seq.shape[1:]) != (N_JOINTS, 3):
-            raise ValueError("project_sequence: seq must be [n,%d,3], got %s" % (N_JOINTS, tuple(seq.shape)))
-        if crt is not None and not (torch.is_tensor(crt) and crt.is_cuda and crt.dtype == torch.float64 and crt.is_contiguous() and crt.numel() == 13):
-            raise TypeError("project_sequence: crt must be a contiguous float64 device tensor of 13 values")
+        _check_seq_crt("project_sequence", "n", seq, crt)
         n = seq.shape[0]
         if cams is not None:
-            if not (torch.is_tensor(cams) and cams.is_cuda and cams.dtype == torch.float64 and cams.is_contiguous()):
-                raise TypeError("project_sequence: cams must be a contiguous float64 device tensor")
-            if tuple(cams.shape) != (n, 4, 4):
-                raise ValueError("project_sequence: cams must be [%d,4,4], got %s" % (n, tuple(cams.shape)))
+            check_tensor(cams, torch.float64, error=TypeError("project_sequence: cams must be a contiguous float64 device tensor"))
+            check_tensor(cams, torch.float64, (n, 4, 4), error=ValueError("project_sequence: cams must be [%d,4,4], got %s" % (n, tuple(cams.shape))))
         uv = torch.empty(n, N_JOINTS, 2, device=self.device, dtype=torch.float32)
         _capi.check(self.lib.gem_project_sequence(self._h, _ptr(seq), _ptr(crt), _ptr(cams), n, _ptr(uv), _stream()), self.lib)
         return uv
@@ -556,24 +535,20 @@ class WindowEngine:
         0x00BBGGRR), through `view` (a `_capi.GemCameraView`), as PNG scanline streams -> uint8 [n, stride] on the device, `out` when
         given (rows at least the image's bytes, 16-byte aligned, a row stride that is a multiple of 16).  want_ids: -> (out, ids
         int32 [n,N,N], response f32 [n,N,N]).  No synchronisation."""
-        if not (torch.is_tensor(uv) and uv.is_cuda and uv.dtype == torch.float32 and uv.is_contiguous() and uv.dim() == 4
-                and tuple(uv.shape[2:]) == (N_JOINTS, 2)):
-            raise TypeError("render_camera: uv must be a contiguous float32 device tensor [S,n,%d,2]" % N_JOINTS)
+        check_tensor(uv, torch.float32, (None, None, N_JOINTS, 2),
+                     error=TypeError("render_camera: uv must be a contiguous float32 device tensor [S,n,%d,2]" % N_JOINTS))
         S, n = uv.shape[0], uv.shape[1]
-        if not (torch.is_tensor(rgb) and rgb.is_cuda and rgb.dtype == torch.int32 and rgb.is_contiguous() and tuple(rgb.shape) == (S,)):
-            raise TypeError("render_camera: rgb must be a contiguous int32 device tensor [%d]" % S)
+        check_tensor(rgb, torch.int32, (S,), error=TypeError("render_camera: rgb must be a contiguous int32 device tensor [%d]" % S))
         if heat is not None:
-            if not (torch.is_tensor(heat) and heat.is_cuda and heat.dtype == torch.float32 and heat.is_contiguous()):
-                raise TypeError("render_camera: heat must be a contiguous float32 device tensor")
-            if tuple(heat.shape) != (n, self.heat_size[0], self.heat_size[1], N_JOINTS):
-                raise ValueError("render_camera: heat must be [%d,%d,%d,%d], got %s" % ((n,) + tuple(self.heat_size) + (N_JOINTS, tuple(heat.shape))))
+            check_tensor(heat, torch.float32, error=TypeError("render_camera: heat must be a contiguous float32 device tensor"))
+            check_tensor(heat, torch.float32, (n,) + tuple(self.heat_size) + (N_JOINTS,),
+                         error=ValueError("render_camera: heat must be [%d,%d,%d,%d], got %s" % ((n,) + tuple(self.heat_size) + (N_JOINTS, tuple(heat.shape)))))
         lay = (C.c_int64 * 3)()
         _capi.check(self.lib.gem_render_layout(view.size, view.size, lay), self.lib)
         if out is None:
             out = torch.empty(n, lay[2], device=self.device, dtype=torch.uint8)
-        if not (torch.is_tensor(out) and out.is_cuda and out.dtype == torch.uint8 and out.dim() == 2 and out.shape[0] == n
-                and out.shape[1] >= lay[1] and out.stride(1) == 1):
-            raise ValueError("render_camera: out must be a uint8 device tensor [%d, >= %d] with contiguous rows" % (n, lay[1]))
+        check_tensor(out, torch.uint8, rows=(n, lay[1]),
+                     error=ValueError("render_camera: out must be a uint8 device tensor [%d, >= %d] with contiguous rows" % (n, lay[1])))
         ids = torch.empty(n, view.size, view.size, device=self.device, dtype=torch.int32) if want_ids else None
         response = torch.empty(n, view.size, view.size, device=self.device, dtype=torch.float32) if want_ids else None
         _capi.check(self.lib.gem_render_camera(self._h, _ptr(heat), _ptr(uv), _ptr(rgb), S, n, C.byref(view), _ptr(out), out.stride(0),
@@ -602,17 +577,14 @@ class WindowEngine:
         if not (torch.is_tensor(scan) and scan.is_cuda and scan.dtype == torch.uint8 and scan.dim() == 2 and (scan.shape[0] == 0 or scan.stride(1) == 1)):
             raise TypeError("jpeg_encode: scan must be a uint8 device tensor [n, stride] with contiguous rows")
         n = scan.shape[0]
-        if not (torch.is_tensor(out) and out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous()):
-            raise TypeError("jpeg_encode: out must be a contiguous uint8 device tensor")
-        if not (torch.is_tensor(offsets) and offsets.is_cuda and offsets.dtype == torch.int64 and offsets.is_contiguous() and offsets.numel() == n + 1):
-            raise TypeError("jpeg_encode: offsets must be a contiguous int64 device tensor [%d]" % (n + 1))
+        check_tensor(out, torch.uint8, error=TypeError("jpeg_encode: out must be a contiguous uint8 device tensor"))
+        check_tensor(offsets, torch.int64, numel=n + 1, error=TypeError("jpeg_encode: offsets must be a contiguous int64 device tensor [%d]" % (n + 1)))
         if scan.shape[1] < int(height) * (1 + 3 * int(width)):
             raise ValueError("jpeg_encode: %d x %d pixels are %d scanline bytes, the rows of scan hold %d" %
                              (width, height, int(height) * (1 + 3 * int(width)), scan.shape[1]))
         if coef is not None:
             shape = (n, 3, (int(height) + 7) // 8, (int(width) + 7) // 8, 64)
-            if not (torch.is_tensor(coef) and coef.is_cuda and coef.dtype == torch.int16 and coef.is_contiguous() and tuple(coef.shape) == shape):
-                raise TypeError("jpeg_encode: coef must be a contiguous int16 device tensor %s" % (shape,))
+            check_tensor(coef, torch.int16, shape, error=TypeError("jpeg_encode: coef must be a contiguous int16 device tensor %s" % (shape,)))
         _capi.check(self.lib.gem_jpeg_encode(self._h, _ptr(scan), n, int(width), int(height), scan.stride(0) if n else scan.shape[1], int(quality),
                                              1 if avi else 0, _ptr(out), out.numel(), _ptr(offsets), _ptr(coef), _stream()), self.lib)
 
@@ -666,10 +638,8 @@ class WindowEngine:
         max_windows.  No synchronisation."""
         if (x is None) != (rec is None):
             raise ValueError("latent_report: x and rec come together")
-        for t, dt in ((mu, torch.float32), (logvar, torch.float32), (x, torch.float32), (rec, torch.float32), (cols, torch.float64),
-                      (count, torch.int64), (out, torch.float64)):
-            if t is not None and not (torch.is_tensor(t) and t.is_cuda and t.dtype == dt and t.is_contiguous()):
-                raise TypeError("latent_report wants contiguous device tensors of the documented dtypes")
+        check_tensors("latent_report", (mu, torch.float32, None), (logvar, torch.float32, None), (x, torch.float32, None), (rec, torch.float32, None),
+                      (cols, torch.float64, None), (count, torch.int64, None), (out, torch.float64, None))
         B = mu.shape[0]
         if mu.dim() != 2 or tuple(mu.shape) != (B, self.D) or tuple(logvar.shape) != (B, self.D) or B < 1:
             raise ValueError("latent_report: mu and logvar must be [B,%d] with B >= 1, got %s and %s" % (self.D, tuple(mu.shape), tuple(logvar.shape)))
@@ -701,22 +671,13 @@ class WindowEngine:
         t["c"] = _capi.GemLiveBuffers(*[t[k].data_ptr() for k, _ in _capi.GemLiveBuffers._fields_])
         return t
 
-    def _live_check(self, what, *pairs):
-        for x, dt, shape in pairs:
-            if x is None:
-                continue
-            if not (torch.is_tensor(x) and x.is_cuda and x.dtype == dt and x.is_contiguous()):
-                raise TypeError("%s wants contiguous device tensors of the documented dtypes" % what)
-            if tuple(x.shape) != tuple(shape):
-                raise ValueError("%s: a tensor of shape %s where %s is expected" % (what, tuple(x.shape), tuple(shape)))
-
     def live_push(self, bufs, first_frame, oldest_needed, heat, pose, cams, times):
         """k <= 8 frames into the rings of `bufs` (`live_buffers`) as the frames first_frame .. first_frame + k - 1 (gem_live_push):
         heat [k,H,W,15] f32, pose [k,15,3] f32, cams [k,4,4] f64, times [k] f64, contiguous device tensors.  oldest_needed: the
         oldest frame a window still to come reads.  No synchronisation."""
         k = int(times.shape[0]) if torch.is_tensor(times) and times.dim() == 1 else -1
-        self._live_check("live_push", (heat, torch.float32, (k,) + self.heat_size + (N_JOINTS,)), (pose, torch.float32, (k, N_JOINTS, 3)),
-                         (cams, torch.float64, (k, 4, 4)), (times, torch.float64, (k,)))
+        check_tensors("live_push", (heat, torch.float32, (k,) + self.heat_size + (N_JOINTS,)), (pose, torch.float32, (k, N_JOINTS, 3)),
+                      (cams, torch.float64, (k, 4, 4)), (times, torch.float64, (k,)))
         _capi.check(self.lib.gem_live_push(self._h, C.byref(bufs["c"]), int(first_frame), k, int(oldest_needed), _ptr(heat), _ptr(pose),
                                            _ptr(cams), _ptr(times), _stream()), self.lib)
 
@@ -724,9 +685,9 @@ class WindowEngine:
         """The frames [8 window, 8 window + 10) from the rings into the window buffers win_pose [10,15,3] f32, win_cams [10,4,4] f64,
         win_heat [10,H,W,15] f32, and the call's mean bone lengths into mean_bone [1,15] f32: `bone_fixed` [15] f32 when given, else
         the running mean over the frames pushed so far (gem_live_window).  No synchronisation."""
-        self._live_check("live_window", (win_pose, torch.float32, (self.T, N_JOINTS, 3)), (win_cams, torch.float64, (self.T, 4, 4)),
-                         (win_heat, torch.float32, (self.T,) + self.heat_size + (N_JOINTS,)), (mean_bone, torch.float32, (1, N_JOINTS)),
-                         (bone_fixed, torch.float32, (N_JOINTS,)))
+        check_tensors("live_window", (win_pose, torch.float32, (self.T, N_JOINTS, 3)), (win_cams, torch.float64, (self.T, 4, 4)),
+                      (win_heat, torch.float32, (self.T,) + self.heat_size + (N_JOINTS,)), (mean_bone, torch.float32, (1, N_JOINTS)),
+                      (bone_fixed, torch.float32, (N_JOINTS,)))
         _capi.check(self.lib.gem_live_window(self._h, C.byref(bufs["c"]), int(window), int(n_pushed), _ptr(bone_fixed), _ptr(win_pose),
                                              _ptr(win_cams), _ptr(win_heat), _ptr(mean_bone), _stream()), self.lib)
 
@@ -735,8 +696,8 @@ class WindowEngine:
         the window makes final, optimised (out[0]; merged with the two held frames, One-Euro filtered when `one_euro` = (min_cutoff,
         beta, d_cutoff)) and estimated (out[1]); the window's last two frames are held (gem_live_emit).  final=True: the two held
         frames into out[:, :2] instead.  No synchronisation."""
-        self._live_check("live_emit", (out, torch.float64, (2, _capi.LIVE_STRIDE, N_JOINTS, 3)), (glob, torch.float64, (1, self.T, N_JOINTS, 3)),
-                         (win_pose, torch.float32, (self.T, N_JOINTS, 3)), (win_cams, torch.float64, (self.T, 4, 4)))
+        check_tensors("live_emit", (out, torch.float64, (2, _capi.LIVE_STRIDE, N_JOINTS, 3)), (glob, torch.float64, (1, self.T, N_JOINTS, 3)),
+                      (win_pose, torch.float32, (self.T, N_JOINTS, 3)), (win_cams, torch.float64, (self.T, 4, 4)))
         euro = (C.c_double * 3)(*[float(v) for v in one_euro]) if one_euro is not None else None
         _capi.check(self.lib.gem_live_emit(self._h, C.byref(bufs["c"]), int(window), 1 if final else 0, _ptr(glob), _ptr(win_pose),
                                            _ptr(win_cams), euro, _ptr(out), _stream()), self.lib)
@@ -749,9 +710,9 @@ class WindowEngine:
 
     def live_window_at(self, bufs, first_frame, n_pushed, win_pose, win_cams, win_heat, mean_bone, bone_fixed=None):
         """`live_window` for the frames [first_frame, first_frame + 10) (gem_live_window_at).  No synchronisation."""
-        self._live_check("live_window_at", (win_pose, torch.float32, (self.T, N_JOINTS, 3)), (win_cams, torch.float64, (self.T, 4, 4)),
-                         (win_heat, torch.float32, (self.T,) + self.heat_size + (N_JOINTS,)), (mean_bone, torch.float32, (1, N_JOINTS)),
-                         (bone_fixed, torch.float32, (N_JOINTS,)))
+        check_tensors("live_window_at", (win_pose, torch.float32, (self.T, N_JOINTS, 3)), (win_cams, torch.float64, (self.T, 4, 4)),
+                      (win_heat, torch.float32, (self.T,) + self.heat_size + (N_JOINTS,)), (mean_bone, torch.float32, (1, N_JOINTS)),
+                      (bone_fixed, torch.float32, (N_JOINTS,)))
         _capi.check(self.lib.gem_live_window_at(self._h, C.byref(bufs["c"]), int(first_frame), int(n_pushed), _ptr(bone_fixed), _ptr(win_pose),
                                                 _ptr(win_cams), _ptr(win_heat), _ptr(mean_bone), _stream()), self.lib)
 
@@ -762,9 +723,9 @@ class WindowEngine:
         `stride` -- unaveraged, One-Euro filtered when `one_euro` = (min_cutoff, beta, d_cutoff).  final=True (`window` = the number of
         windows emitted): the 10 - stride frames still held into out[0] and out[1] instead.  `dense_state`: `live_dense_state()`.
         No synchronisation."""
-        self._live_check("live_emit_dense", (dense_state, torch.float64, (_capi.LIVE_DENSE_DOUBLES,)), (out, torch.float64, (3, self.T, N_JOINTS, 3)),
-                         (glob, torch.float64, (1, self.T, N_JOINTS, 3)), (win_pose, torch.float32, (self.T, N_JOINTS, 3)),
-                         (win_cams, torch.float64, (self.T, 4, 4)))
+        check_tensors("live_emit_dense", (dense_state, torch.float64, (_capi.LIVE_DENSE_DOUBLES,)), (out, torch.float64, (3, self.T, N_JOINTS, 3)),
+                      (glob, torch.float64, (1, self.T, N_JOINTS, 3)), (win_pose, torch.float32, (self.T, N_JOINTS, 3)),
+                      (win_cams, torch.float64, (self.T, 4, 4)))
         if dense_state is None:
             raise TypeError("live_emit_dense wants the session's dense state block")
         euro = (C.c_double * 3)(*[float(v) for v in one_euro]) if one_euro is not None else None
@@ -880,7 +841,7 @@ class WindowEngine:
         F, (H, W) = t.shape[0], self.heat_size
         if out is None:
             out = torch.empty(F, H, W, N_JOINTS, device=self.device, dtype=torch.float32)
-        self._live_check("keypoint_heatmaps", (out, torch.float32, (F, H, W, N_JOINTS)))
+        check_tensors("keypoint_heatmaps", (out, torch.float32, (F, H, W, N_JOINTS)))
         _capi.check(self.lib.gem_keypoint_heatmaps(_ptr(t), F, N_JOINTS, H, W, sigma, _ptr(out), _stream()), self.lib)
         return out
 
@@ -893,7 +854,7 @@ class WindowEngine:
         dep = self._f64(depth)
         if dep.numel() != F * N_JOINTS:
             raise ValueError("lift_keypoints wants depth [F,%d] for these %d frames, got %s" % (N_JOINTS, F, tuple(dep.shape)))
-        self._live_check("lift_keypoints", (prev, torch.float64, (N_JOINTS, 3)))
+        check_tensors("lift_keypoints", (prev, torch.float64, (N_JOINTS, 3)))
         poly = np.ascontiguousarray(self.camera.poly_c2w, dtype=np.float64)
         o64 = torch.empty(F, N_JOINTS, 3, device=self.device, dtype=torch.float64) if want_f64 else None
         o32 = torch.empty(F, N_JOINTS, 3, device=self.device, dtype=torch.float32)
@@ -909,7 +870,7 @@ class WindowEngine:
         total = int(seq.shape[0]) if torch.is_tensor(seq) and seq.dim() == 3 else -1
         if n_chunks < 1 or total < 0 or total % n_chunks:
             raise ValueError("fill_missing: a sequence [n,%d,3] of %d equal chunks is wanted" % (N_JOINTS, n_chunks))
-        self._live_check("fill_missing", (seq, torch.float64, (total, N_JOINTS, 3)), (valid, torch.uint8, (total, N_JOINTS)))
+        check_tensors("fill_missing", (seq, torch.float64, (total, N_JOINTS, 3)), (valid, torch.uint8, (total, N_JOINTS)))
         _capi.check(self.lib.gem_fill_missing(_ptr(seq), _ptr(valid), int(n_chunks), total // n_chunks, N_JOINTS, _stream()), self.lib)
         return seq
 
@@ -925,7 +886,7 @@ class WindowEngine:
         t = self._keypoints("bone_depths", kp)
         F = t.shape[0]
         depth, solved, rms = out if out is not None else (None, None, None)
-        self._live_check("bone_depths", (depth, torch.float64, (F, N_JOINTS)), (solved, torch.uint8, (F, N_JOINTS)), (rms, torch.float64, (F,)))
+        check_tensors("bone_depths", (depth, torch.float64, (F, N_JOINTS)), (solved, torch.uint8, (F, N_JOINTS)), (rms, torch.float64, (F,)))
         depth = torch.empty(F, N_JOINTS, device=self.device, dtype=torch.float64) if depth is None else depth
         solved = torch.empty(F, N_JOINTS, device=self.device, dtype=torch.uint8) if solved is None else solved
         rms = torch.empty(F, device=self.device, dtype=torch.float64) if rms is None else rms
@@ -951,7 +912,7 @@ class WindowEngine:
             raise ValueError("heatmap_peaks: min_peak must be a finite number >= 0, got %r" % min_peak)
         F = heat_t.shape[0]
         kp, arg = out if out is not None else (None, None)
-        self._live_check("heatmap_peaks", (kp, torch.float64, (F, N_JOINTS, 3)), (arg, torch.int32, (F, N_JOINTS)))
+        check_tensors("heatmap_peaks", (kp, torch.float64, (F, N_JOINTS, 3)), (arg, torch.int32, (F, N_JOINTS)))
         kp = torch.empty(F, N_JOINTS, 3, device=self.device, dtype=torch.float64) if kp is None else kp
         arg = torch.empty(F, N_JOINTS, device=self.device, dtype=torch.int32) if arg is None else arg
         _capi.check(self.lib.gem_heatmap_peaks(self._h, _ptr(heat_t), F, int(upscale), int(pad_x), int(pad_y), min_peak, _ptr(kp), _ptr(arg),

@@ -19,6 +19,7 @@ import os
 import numpy as np
 
 from . import _capi, ground as grounds
+from ._binding import _ptr, call_stream, check_tensor, staged_call
 from .ground import DEFAULT_FPS, TAU_H, TAU_V, default_lag
 
 MIN_RUN, STRETCH = 3, 0.05
@@ -74,31 +75,17 @@ def lock_call(engine, sequences, ground_records, lag, tau_v=TAU_V, tau_h=TAU_H, 
     to.  ONE upload (the table), no synchronisation."""
     import torch
     lib, n = engine.lib, len(sequences)
-    for x in sequences:
-        if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float64 and x.dim() == 3 and tuple(x.shape[1:]) == (15, 3) and x.is_contiguous()):
-            raise ValueError("lock_feet: a sequence must be a contiguous float64 device tensor [F,15,3]")
-    if not (torch.is_tensor(ground_records) and ground_records.is_cuda and ground_records.dtype == torch.float64 and ground_records.is_contiguous()
-            and tuple(ground_records.shape) == (n, _capi.GROUND_RECORD_DOUBLES)):
-        raise ValueError("lock_feet: the ground records must be a contiguous float64 device tensor [%d,%d]" % (n, _capi.GROUND_RECORD_DOUBLES))
-    frames = np.array([len(x) for x in sequences], dtype=np.int64)
-    offsets = np.full(max(n, 1), -1, dtype=np.int64)
-    need = int(lib.gem_foot_lock_work(C.c_void_p(frames.ctypes.data), n, C.c_void_p(offsets.ctypes.data))) if n else 0
-    if need < 0:
-        raise _capi.GemError((lib.gem_last_error() or b"").decode())
-    with torch.cuda.device(engine.device):
-        st = torch.cuda.current_stream() if stream is None else stream
-        with torch.cuda.stream(st):
-            outs = [torch.empty_like(x) for x in sequences] if outputs is None else list(outputs)
-            table = np.concatenate([np.array([x.data_ptr() if len(x) else 0 for x in sequences], dtype=np.int64), frames,
-                                    np.array([y.data_ptr() if len(y) else 0 for y in outs], dtype=np.int64), offsets[:n]])
-            d_table = torch.from_numpy(table).to(engine.device) if n else torch.empty(0, dtype=torch.int64, device=engine.device)
-            work = torch.empty(max(need // 8, 1), dtype=torch.float64, device=engine.device)
-            records = torch.empty(max(n, 1), _capi.FOOT_LOCK_RECORD_DOUBLES, dtype=torch.float64, device=engine.device)
-            rc = lib.gem_foot_lock(C.c_void_p(table.ctypes.data), C.c_void_p(d_table.data_ptr()), n, C.c_void_p(ground_records.data_ptr()), int(lag),
-                                   float(tau_v), float(tau_h), int(min_run), int(blend), 1 if snap else 0, float(stretch),
-                                   C.c_void_p(work.data_ptr()), need, C.c_void_p(records.data_ptr()), C.c_void_p(st.cuda_stream))
-            for t in (d_table, work):
-                t.record_stream(st)
+    grounds.check_sequences("lock_feet", sequences)
+    check_tensor(ground_records, torch.float64, (n, _capi.GROUND_RECORD_DOUBLES),
+                 error=ValueError("lock_feet: the ground records must be a contiguous float64 device tensor [%d,%d]" % (n, _capi.GROUND_RECORD_DOUBLES)))
+    addresses, frames, offsets, need = grounds.sequence_table(lib, lib.gem_foot_lock_work, sequences)
+    with staged_call(lib, engine.device, stream) as call:
+        outs = [torch.empty_like(x) for x in sequences] if outputs is None else list(outputs)
+        table = np.concatenate([addresses, frames, np.array([y.data_ptr() if len(y) else 0 for y in outs], dtype=np.int64), offsets])
+        d_table, = call.upload(table)
+        records = torch.empty(max(n, 1), _capi.FOOT_LOCK_RECORD_DOUBLES, dtype=torch.float64, device=engine.device)
+        rc, _ = call.run(lib.gem_foot_lock, C.c_void_p(table.ctypes.data), _ptr(d_table), n, _ptr(ground_records), int(lag), float(tau_v),
+                         float(tau_h), int(min_run), int(blend), 1 if snap else 0, float(stretch), _ptr(call.work(need)), need, _ptr(records))
     _capi.check(rc, lib)
     return outs, records[:n]
 
@@ -131,9 +118,8 @@ def lock_feet(engine, sequences, fps=DEFAULT_FPS, lag=None, tau_v=TAU_V, tau_h=T
     else:
         g_records = grounds.ground_call(engine, seqs, lag, tau_v, tau_h, stream=stream)
     outs, records = lock_call(engine, seqs, g_records, lag, tau_v, tau_h, min_run, blend, snap, stretch, stream)
-    with torch.cuda.device(engine.device):
-        with torch.cuda.stream(torch.cuda.current_stream() if stream is None else stream):
-            host = torch.cat([g_records.reshape(-1), records.reshape(-1)]).cpu().numpy()          # (the one read-back)
+    with torch.cuda.device(engine.device), torch.cuda.stream(call_stream(engine.device, stream)):
+        host = torch.cat([g_records.reshape(-1), records.reshape(-1)]).cpu().numpy()          # (the one read-back)
     n = len(seqs)
     g_host, l_host = host[:n * _capi.GROUND_RECORD_DOUBLES].reshape(n, -1), host[n * _capi.GROUND_RECORD_DOUBLES:].reshape(n, -1)
     found = []
@@ -156,10 +142,7 @@ def _parser():
     p.add_argument("pose_pickle", help="result_pose.pkl as --save_pose writes it: estimated_pose and optimized_pose")
     p.add_argument("--out", required=True, metavar="FILE", help="the pose pickle to write, the chosen sequences replaced by their locked versions")
     p.add_argument("--sequence", default="optimized", choices=("optimized", "estimated", "both"), help="which sequence to lock (default optimized)")
-    p.add_argument("--fps", type=float, default=DEFAULT_FPS, help="frames per second of the sequences (default 25)")
-    p.add_argument("--lag", type=int, default=None, help="frames between the two frames of a still pair (default: 0.2 s)")
-    p.add_argument("--tau_v", type=float, default=TAU_V, help="metres a standing foot may seem to move over the lag")
-    p.add_argument("--tau_h", type=float, default=TAU_H, help="metres a contact may lie off the plane")
+    grounds.add_contact_arguments(p)
     p.add_argument("--min_run", type=int, default=MIN_RUN, help="the fewest consecutive contact frames that make a stance (default 3)")
     p.add_argument("--blend", type=int, default=None, help="frames over which the correction is eased in and out (default: 0.12 s)")
     p.add_argument("--stretch", type=float, default=STRETCH, help="how much longer a straight leg may become to hold its pin (default 0.05)")
@@ -180,35 +163,16 @@ def report_text(names, locks, before, after):
 
 
 def _cli(argv=None):
-    import json
     import pickle
-    import torch
     p = _parser()
     a = p.parse_args(argv)
-    if not a.fps > 0:
-        p.error("argument --fps: must be positive")
-    for name in ("lag", "blend"):
-        if getattr(a, name) is not None and getattr(a, name) < 1:
-            p.error("argument --%s: at least one frame" % name)
+    rule = grounds.contact_arguments(p, a, frame_counts=("lag", "blend"))
     if a.min_run < 1:
         p.error("argument --min_run: at least one frame")
-    for name in ("tau_v", "tau_h"):
-        if not (np.isfinite(getattr(a, name)) and getattr(a, name) > 0):
-            p.error("argument --%s: a positive number of metres" % name)
     if not (np.isfinite(a.stretch) and a.stretch >= 0):
         p.error("argument --stretch: a number that is not negative")
-    with open(a.pose_pickle, "rb") as f:
-        d = pickle.load(f)
     names = ["optimized", "estimated"] if a.sequence == "both" else [a.sequence]
-    for key in names:
-        if key + "_pose" not in d:
-            p.error("%s has no %s_pose" % (a.pose_pickle, key))
-    if not torch.cuda.is_available():
-        raise _capi.GemError("no HIP device visible: the feet are locked on the device")
-    from .camera import DEFAULT_CALIBRATION
-    from .prepare import _lift_engine
-    engine = _lift_engine(DEFAULT_CALIBRATION, torch.cuda.current_device())
-    rule = dict(fps=a.fps, lag=a.lag, tau_v=a.tau_v, tau_h=a.tau_h)
+    d, engine = grounds.cli_inputs(p, a.pose_pickle, [k + "_pose" for k in names], "no HIP device visible: the feet are locked on the device")
     locks = lock_feet(engine, [np.asarray(d[k + "_pose"], dtype=np.float64) for k in names], min_run=a.min_run, blend=a.blend, snap=not a.no_snap,
                       stretch=a.stretch, **rule)
     after = grounds.estimate_ground(engine, [l.sequence for l in locks], **rule)
@@ -222,11 +186,8 @@ def _cli(argv=None):
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "wb") as f:
         pickle.dump(out, f)
-    if a.json is not None:
-        os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
-        with open(a.json, "w") as f:
-            json.dump({name: dict(l.as_dict(), ground_before=l.ground.as_dict(), ground_after=g.as_dict()) for name, l, g in zip(names, locks, after)},
-                      f, indent=1)
+    grounds.write_json(a.json, {name: dict(l.as_dict(), ground_before=l.ground.as_dict(), ground_after=g.as_dict())
+                                for name, l, g in zip(names, locks, after)})
     return dict(zip(names, locks))
 
 

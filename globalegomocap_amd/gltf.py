@@ -21,6 +21,7 @@ import numpy as np
 
 from . import _capi
 from . import bvh
+from ._binding import _ptr, _stream, check_tensor
 from .bvh import DEFAULT_FPS, NODE_NAMES, new_counter
 from .meshes import _alignment, _sequence, _upright, result_poses
 
@@ -58,11 +59,10 @@ def animation(engine, seq_d, crt, fps, bad=None, out=None):
     n = layout(F).block_bytes
     if out is None:
         out = torch.zeros(n, device=seq_d.device, dtype=torch.uint8)          # (zeros: the padding between the arrays is file content)
-    if not (torch.is_tensor(out) and out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.numel() >= n):
-        raise ValueError("animation: out must be a contiguous uint8 device tensor of at least %d bytes" % n)
+    check_tensor(out, torch.uint8, at_least=n, error=ValueError("animation: out must be a contiguous uint8 device tensor of at least %d bytes" % n))
     if bad is None:
         bad = new_counter(seq_d.device)
-    bvh._call(engine, engine.lib.gem_gltf_animation, bvh._ptr(seq_d), F, bvh._ptr(crt), C.c_double(float(fps)), bvh._ptr(out), bvh._ptr(bad))
+    _capi.check(engine.lib.gem_gltf_animation(_ptr(seq_d), F, _ptr(crt), C.c_double(float(fps)), _ptr(out), _ptr(bad), _stream()), engine.lib)
     return out[:n], bad
 
 
@@ -74,10 +74,9 @@ def rest_mesh(engine, rest, out=None):
     n = layout(0).vertex_bytes
     if out is None:
         out = torch.empty(n, device=rest.device, dtype=torch.uint8)
-    if not (torch.is_tensor(out) and out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.numel() >= n):
-        raise ValueError("rest_mesh: out must be a contiguous uint8 device tensor of at least %d bytes" % n)
+    check_tensor(out, torch.uint8, at_least=n, error=ValueError("rest_mesh: out must be a contiguous uint8 device tensor of at least %d bytes" % n))
     bounds = torch.empty(6, device=rest.device, dtype=torch.float32)
-    bvh._call(engine, engine.lib.gem_gltf_rest_mesh, bvh._ptr(rest), bvh._ptr(out), bvh._ptr(bounds))
+    _capi.check(engine.lib.gem_gltf_rest_mesh(_ptr(rest), _ptr(out), _ptr(bounds), _stream()), engine.lib)
     return out[:n], bounds
 
 

@@ -18,6 +18,7 @@ import os
 import numpy as np
 
 from . import _capi
+from ._binding import _ptr, _stream, check_tensor, staged_call
 
 TAU_V, TAU_H, MIN_SPREAD, MIN_POINTS = 0.10, 0.05, 0.05, 8
 DEFAULT_FPS = 25.0
@@ -67,22 +68,41 @@ class GroundEstimate:
 
 def _transform(engine, t, what):
     import torch
-    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and t.numel() and t.shape[-1] == 13):
-        raise TypeError("%s must be a contiguous float64 device tensor [13] or [n,13]" % what)
+    wrong = TypeError("%s must be a contiguous float64 device tensor [13] or [n,13]" % what)
+    check_tensor(t, torch.float64, at_least=1, error=wrong)
+    if t.shape[-1] != 13:
+        raise wrong
     return t
+
+
+def check_sequences(who, sequences):
+    """What `ground_call` and `foot_lock.lock_call` ask of every sequence: a contiguous float64 device tensor [F,15,3], any F."""
+    import torch
+    for x in sequences:
+        check_tensor(x, torch.float64, (None, 15, 3), error=ValueError("%s: a sequence must be a contiguous float64 device tensor [F,15,3]" % who))
+
+
+def sequence_table(lib, work_fn, sequences):
+    """The head of the tables of `gem_ground_plane` and `gem_foot_lock` -> (the sequences' addresses, their frames, their offsets in
+    the work buffer, its bytes as `work_fn` fixes them); GemError with the library's text where it refuses the sizes."""
+    n = len(sequences)
+    frames = np.array([len(x) for x in sequences], dtype=np.int64)
+    offsets = np.full(max(n, 1), -1, dtype=np.int64)
+    need = int(work_fn(C.c_void_p(frames.ctypes.data), n, C.c_void_p(offsets.ctypes.data))) if n else 0
+    if need < 0:
+        raise _capi.GemError((lib.gem_last_error() or b"").decode())
+    return np.array([x.data_ptr() if len(x) else 0 for x in sequences], dtype=np.int64), frames, offsets[:n], need
 
 
 def compose(engine, a, b):
     """The similarity `a`, then `b` (gem_similarity_compose): device tensors [13] or [n,13] of (c, R row-major, t), as
     `WindowEngine.sequence_align` and `GroundEstimate.crt` give them -> one of the same shape.  No synchronisation."""
     import torch
-    from .engine import _stream
     a, b = _transform(engine, a, "compose: a"), _transform(engine, b, "compose: b")
     if a.shape != b.shape:
         raise ValueError("compose: a and b must have one shape, got %s and %s" % (tuple(a.shape), tuple(b.shape)))
     out = torch.empty_like(a)
-    _capi.check(engine.lib.gem_similarity_compose(C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()), C.c_void_p(out.data_ptr()),
-                                                  a.numel() // 13, _stream()), engine.lib)
+    _capi.check(engine.lib.gem_similarity_compose(_ptr(a), _ptr(b), _ptr(out), a.numel() // 13, _stream()), engine.lib)
     return out
 
 
@@ -96,30 +116,17 @@ def ground_call(engine, sequences, lag, tau_v=TAU_V, tau_h=TAU_H, min_spread=MIN
     moved_by = [None] * n if moved_by is None else list(moved_by)
     if len(moved_by) != n:
         raise ValueError("estimate_ground: %d transforms for %d sequences" % (len(moved_by), n))
-    for x in sequences:
-        if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float64 and x.dim() == 3 and tuple(x.shape[1:]) == (15, 3) and x.is_contiguous()):
-            raise ValueError("estimate_ground: a sequence must be a contiguous float64 device tensor [F,15,3]")
+    check_sequences("estimate_ground", sequences)
     for m in moved_by:
         if m is not None and _transform(engine, m, "estimate_ground: moved_by").numel() != 13:
             raise TypeError("estimate_ground: moved_by holds one [13] transform per sequence")
-    frames = np.array([len(x) for x in sequences], dtype=np.int64)
-    offsets = np.full(max(n, 1), -1, dtype=np.int64)
-    need = int(lib.gem_ground_plane_work(C.c_void_p(frames.ctypes.data), n, C.c_void_p(offsets.ctypes.data))) if n else 0
-    if need < 0:
-        raise _capi.GemError((lib.gem_last_error() or b"").decode())
-    table = np.concatenate([np.array([x.data_ptr() if len(x) else 0 for x in sequences], dtype=np.int64), frames,
-                            np.array([0 if m is None else m.data_ptr() for m in moved_by], dtype=np.int64), offsets[:n]])
-    with torch.cuda.device(engine.device):
-        st = torch.cuda.current_stream() if stream is None else stream
-        with torch.cuda.stream(st):
-            d_table = torch.from_numpy(table).to(engine.device) if n else torch.empty(0, dtype=torch.int64, device=engine.device)
-            work = torch.empty(max(need // 8, 1), dtype=torch.float64, device=engine.device)
-            records = torch.empty(max(n, 1), _capi.GROUND_RECORD_DOUBLES, dtype=torch.float64, device=engine.device)
-            rc = lib.gem_ground_plane(C.c_void_p(table.ctypes.data), C.c_void_p(d_table.data_ptr()), n, int(lag), float(tau_v), float(tau_h),
-                                      float(min_spread), int(min_points), float(foot_height), C.c_void_p(work.data_ptr()), need,
-                                      C.c_void_p(records.data_ptr()), C.c_void_p(st.cuda_stream))
-            for t in (d_table, work):
-                t.record_stream(st)
+    addresses, frames, offsets, need = sequence_table(lib, lib.gem_ground_plane_work, sequences)
+    table = np.concatenate([addresses, frames, np.array([0 if m is None else m.data_ptr() for m in moved_by], dtype=np.int64), offsets])
+    with staged_call(lib, engine.device, stream) as call:
+        d_table, = call.upload(table)
+        records = torch.empty(max(n, 1), _capi.GROUND_RECORD_DOUBLES, dtype=torch.float64, device=engine.device)
+        rc, _ = call.run(lib.gem_ground_plane, C.c_void_p(table.ctypes.data), _ptr(d_table), n, int(lag), float(tau_v), float(tau_h),
+                         float(min_spread), int(min_points), float(foot_height), _ptr(call.work(need)), need, _ptr(records))
     _capi.check(rc, lib)
     return records[:n]
 
@@ -180,14 +187,59 @@ def resolve(engine, upright, reference, **options):
 
 
 # ------------------------------------------------------------------------------------------------------------------ command line
-def _parser():
-    import argparse
-    p = argparse.ArgumentParser(description="the ground plane and the foot-contact figures of a saved result_pose.pkl")
-    p.add_argument("pose_pickle", help="result_pose.pkl as --save_pose writes it: estimated_pose, optimized_pose and, optionally, gt_pose")
+def add_contact_arguments(p):
+    """`--fps`, `--lag`, `--tau_v` and `--tau_h`: the contact rule, as this module's and `foot_lock`'s command lines take it."""
     p.add_argument("--fps", type=float, default=DEFAULT_FPS, help="frames per second of the sequences (default 25)")
     p.add_argument("--lag", type=int, default=None, help="frames between the two frames of a still pair (default: 0.2 s)")
     p.add_argument("--tau_v", type=float, default=TAU_V, help="metres a standing foot may seem to move over the lag")
     p.add_argument("--tau_h", type=float, default=TAU_H, help="metres a contact may lie off the plane")
+
+
+def contact_arguments(p, a, frame_counts=("lag",)):
+    """The rules of `add_contact_arguments`, as parser errors -> the contact rule as keyword arguments.  frame_counts: the options
+    that count frames, --lag and the caller's own."""
+    if not a.fps > 0:
+        p.error("argument --fps: must be positive")
+    for name in frame_counts:
+        if getattr(a, name) is not None and getattr(a, name) < 1:
+            p.error("argument --%s: at least one frame" % name)
+    for name in ("tau_v", "tau_h"):
+        if not (np.isfinite(getattr(a, name)) and getattr(a, name) > 0):
+            p.error("argument --%s: a positive number of metres" % name)
+    return dict(fps=a.fps, lag=a.lag, tau_v=a.tau_v, tau_h=a.tau_h)
+
+
+def cli_inputs(p, path, keys, no_device):
+    """What a command line on a pose pickle starts from -> (the pickle at `path`, which must hold every one of `keys`: a parser error
+    names the one it lacks; an engine that needs no VAE, on the current device: GemError(`no_device`) where there is none)."""
+    import pickle
+    import torch
+    with open(path, "rb") as f:
+        d = pickle.load(f)
+    for key in keys:
+        if key not in d:
+            p.error("%s has no %s" % (path, key))
+    if not torch.cuda.is_available():
+        raise _capi.GemError(no_device)
+    from .camera import DEFAULT_CALIBRATION
+    from .prepare import _lift_engine
+    return d, _lift_engine(DEFAULT_CALIBRATION, torch.cuda.current_device())
+
+
+def write_json(path, data):
+    """`data` as JSON into `path` (its directory is made), unless `path` is None."""
+    import json
+    if path is not None:
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        with open(path, "w") as f:
+            json.dump(data, f, indent=1)
+
+
+def _parser():
+    import argparse
+    p = argparse.ArgumentParser(description="the ground plane and the foot-contact figures of a saved result_pose.pkl")
+    p.add_argument("pose_pickle", help="result_pose.pkl as --save_pose writes it: estimated_pose, optimized_pose and, optionally, gt_pose")
+    add_contact_arguments(p)
     p.add_argument("--foot_height", type=float, default=0.0, help="metres a standing foot point lies above the floor")
     p.add_argument("--json", default=None, metavar="FILE", help="write the reports there too")
     return p
@@ -219,39 +271,18 @@ def normal_angle(a, b):
 
 
 def _cli(argv=None):
-    import json
-    import pickle
-    import torch
     p = _parser()
     a = p.parse_args(argv)
-    if not a.fps > 0:
-        p.error("argument --fps: must be positive")
-    if a.lag is not None and a.lag < 1:
-        p.error("argument --lag: at least one frame")
-    for name in ("tau_v", "tau_h"):
-        if not (np.isfinite(getattr(a, name)) and getattr(a, name) > 0):
-            p.error("argument --%s: a positive number of metres" % name)
-    with open(a.pose_pickle, "rb") as f:
-        d = pickle.load(f)
-    for key in ("estimated_pose", "optimized_pose"):
-        if key not in d:
-            p.error("%s has no %s" % (a.pose_pickle, key))
-    if not torch.cuda.is_available():
-        raise _capi.GemError("no HIP device visible: the ground plane is estimated on the device")
-    from .camera import DEFAULT_CALIBRATION
-    from .prepare import _lift_engine
-    engine = _lift_engine(DEFAULT_CALIBRATION, torch.cuda.current_device())
+    rule = contact_arguments(p, a)
+    d, engine = cli_inputs(p, a.pose_pickle, ("estimated_pose", "optimized_pose"), "no HIP device visible: the ground plane is estimated on the device")
     names = ["estimated", "optimized"] + (["gt"] if d.get("gt_pose") is not None else [])
     seqs = [np.asarray(d[k + "_pose"], dtype=np.float64) for k in names]
-    found = estimate_ground(engine, seqs, fps=a.fps, lag=a.lag, tau_v=a.tau_v, tau_h=a.tau_h, foot_height=a.foot_height)
+    found = estimate_ground(engine, seqs, foot_height=a.foot_height, **rule)
     estimates = dict(zip(names, found))
     print(report_text(estimates))
     angle = normal_angle(estimates["estimated"], estimates["optimized"])
     print("angle between the normals of the estimated and the optimised sequence: %.3f deg" % angle)
-    if a.json is not None:
-        os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
-        with open(a.json, "w") as f:
-            json.dump(dict({k: e.as_dict() for k, e in estimates.items()}, normal_angle_deg=angle), f, indent=1)
+    write_json(a.json, dict({k: e.as_dict() for k, e in estimates.items()}, normal_angle_deg=angle))
     return estimates
 
 

@@ -73,9 +73,9 @@ def _alignment(engine, seq_d, align_to, move=None):
     if move is None:
         return crt
     import torch
+    from ._binding import check_tensor
     from .ground import compose
-    if not (torch.is_tensor(move) and move.is_cuda and move.dtype == torch.float64 and move.is_contiguous() and tuple(move.shape) == (13,)):
-        raise TypeError("move must be a contiguous float64 device tensor of 13 values (c, R, t)")
+    check_tensor(move, torch.float64, (13,), error=TypeError("move must be a contiguous float64 device tensor of 13 values (c, R, t)"))
     return move if crt is None else compose(engine, crt, move)
 
 

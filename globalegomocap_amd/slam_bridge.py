@@ -12,11 +12,11 @@ prints the gaps of a trajectory without touching a device.
 """
 import ctypes as C
 import math
-import os
 
 import numpy as np
 
 from . import _capi
+from ._binding import _ptr, staged_call
 
 MAX_GAP = _capi.BRIDGE_MAX_GAP
 DEFAULT_MAX_GAP_SECONDS = 1.0
@@ -174,32 +174,20 @@ def bridge_call(device, poses, mask, systems, chunk_starts, stream=None, outputs
     if need < 0:          # (n out of range: gem_slam_bridge itself refuses it, with its own text)
         need = 8
     device = torch.device(device)
-    with torch.cuda.device(device):
-        st = torch.cuda.current_stream() if stream is None else stream
-        with torch.cuda.stream(st):
-            # ONE upload: the poses, the system table, the chunk starts, the mask
-            up = torch.from_numpy(np.concatenate([poses.reshape(-1).view(np.uint8), sys32.reshape(-1).view(np.uint8), starts32.view(np.uint8),
-                                                  mask8])).to(device)
-            at = np.cumsum([0, 56 * n, 8 * ns, 4 * nc])
-            d_poses, d_sys, d_starts, d_mask = (up[at[0]:], up[at[1]:], up[at[2]:], up[at[3]:])
-            work = torch.empty(need // 8 + 1, dtype=torch.float64, device=device)
-            if outputs is None:
-                outputs = (torch.empty((n, 4, 4), dtype=torch.float64, device=device), torch.empty((n, 4, 4), dtype=torch.float64, device=device),
-                           torch.empty((nc, 4, 4), dtype=torch.float64, device=device), torch.empty(n, dtype=torch.uint8, device=device),
-                           torch.empty(_capi.BRIDGE_RECORD_DOUBLES, dtype=torch.float64, device=device))
-            G, cams, origins, bridged, record = outputs
-            if tuple(G.shape) != (n, 4, 4) or tuple(cams.shape) != (n, 4, 4) or tuple(origins.shape) != (nc, 4, 4) or tuple(bridged.shape) != (n,) \
-                    or record.numel() != _capi.BRIDGE_RECORD_DOUBLES or not all(t.is_contiguous() for t in outputs):
-                raise ValueError("bridge_call: the outputs do not have the shapes of %d frames in %d chunks" % (n, nc))
-            rc = lib.gem_slam_bridge(C.c_void_p(d_poses.data_ptr()), C.c_void_p(mask8.ctypes.data), C.c_void_p(d_mask.data_ptr()),
-                                     C.c_void_p(sys32.ctypes.data if ns else 0), C.c_void_p(d_sys.data_ptr() if ns else 0), ns,
-                                     C.c_void_p(starts32.ctypes.data if nc else 0), C.c_void_p(d_starts.data_ptr() if nc else 0), nc, n,
-                                     C.c_void_p(G.data_ptr()), C.c_void_p(cams.data_ptr()), C.c_void_p(origins.data_ptr()),
-                                     C.c_void_p(bridged.data_ptr()), C.c_void_p(work.data_ptr()), need, C.c_void_p(record.data_ptr()),
-                                     C.c_void_p(st.cuda_stream))
-            for t in (up, work):
-                t.record_stream(st)
-    msg = (lib.gem_last_error() or b"").decode() if rc else ""
+    with staged_call(lib, device, stream) as call:
+        d_poses, d_sys, d_starts, d_mask = call.upload(poses, sys32, starts32, mask8)          # (ONE upload, the 8-byte items first)
+        if outputs is None:
+            outputs = (torch.empty((n, 4, 4), dtype=torch.float64, device=device), torch.empty((n, 4, 4), dtype=torch.float64, device=device),
+                       torch.empty((nc, 4, 4), dtype=torch.float64, device=device), torch.empty(n, dtype=torch.uint8, device=device),
+                       torch.empty(_capi.BRIDGE_RECORD_DOUBLES, dtype=torch.float64, device=device))
+        G, cams, origins, bridged, record = outputs
+        if tuple(G.shape) != (n, 4, 4) or tuple(cams.shape) != (n, 4, 4) or tuple(origins.shape) != (nc, 4, 4) or tuple(bridged.shape) != (n,) \
+                or record.numel() != _capi.BRIDGE_RECORD_DOUBLES or not all(t.is_contiguous() for t in outputs):
+            raise ValueError("bridge_call: the outputs do not have the shapes of %d frames in %d chunks" % (n, nc))
+        rc, msg = call.run(lib.gem_slam_bridge, _ptr(d_poses), C.c_void_p(mask8.ctypes.data), _ptr(d_mask),
+                           C.c_void_p(sys32.ctypes.data if ns else 0), _ptr(d_sys if ns else None), ns,
+                           C.c_void_p(starts32.ctypes.data if nc else 0), _ptr(d_starts if nc else None), nc, n,
+                           _ptr(G), _ptr(cams), _ptr(origins), _ptr(bridged), _ptr(call.work(need)), need, _ptr(record))
     if not check:
         return rc, msg, G, cams, origins, bridged, record
     if rc:
@@ -252,8 +240,8 @@ def _parser():
 
 
 def _cli(argv=None):
-    import json
     from . import slam
+    from .ground import write_json
     a = _parser().parse_args(argv)
     with open(a.slam) as f:
         ids = slam.frame_ids(slam.trajectory_rows(f.read()), a.fps)
@@ -278,10 +266,7 @@ def _cli(argv=None):
         except ValueError as e:
             out["accepted"], out["refusal"] = False, str(e)
             print("--bridge %g refuses the span: %s" % (a.max_gap, e))
-    if a.json is not None:
-        os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
-        with open(a.json, "w") as f:
-            json.dump(out, f, indent=1)
+    write_json(a.json, out)
     return out
 
 

@@ -16,12 +16,12 @@ rebuilds the camera track in metres, and the routes go on with that track as a m
 the counts.
 """
 import ctypes as C
-import os
 
 import numpy as np
 
 from . import _capi
-from .ground import default_lag
+from ._binding import _ptr, check_tensor, staged_call
+from .ground import default_lag, write_json
 from .skeleton import JOINT_NAMES
 
 FEET = tuple(JOINT_NAMES.index(k) for k in ("Right_ankle", "Right_foot", "Left_ankle", "Left_foot"))
@@ -87,8 +87,7 @@ def _call_inputs(chunks, R, c, ids, feet, who):
     import torch
     chunks = list(chunks)
     for x in chunks:
-        if not (x.is_cuda and x.dtype == torch.float64 and x.dim() == 3 and x.shape[2] == 3 and x.is_contiguous()):
-            raise ValueError("%s: the poses must be contiguous float64 device tensors [n,J,3]" % who)
+        check_tensor(x, torch.float64, (None, None, 3), error=ValueError("%s: the poses must be contiguous float64 device tensors [n,J,3]" % who))
     J = int(chunks[0].shape[1])
     if any(int(x.shape[1]) != J for x in chunks):
         raise ValueError("%s: the chunks differ in their number of joints" % who)
@@ -107,14 +106,6 @@ def _call_inputs(chunks, R, c, ids, feet, who):
     return chunks, J, chunks[0].device, N, nc, R, c, ids, feet, table
 
 
-def _upload(table, ids, R, c, device):
-    """ONE upload: the chunk table, the frame ids and the SLAM poses -> (the tensor, and in it d_chunks, d_ids, d_rot, d_trans)"""
-    import torch
-    N = len(ids)
-    up = torch.from_numpy(np.concatenate([table, ids, R.reshape(-1).view(np.int64), c.reshape(-1).view(np.int64)])).to(device)
-    return up, up[:len(table)], up[len(table):len(table) + N], up[len(table) + N:len(table) + 10 * N], up[len(table) + 10 * N:]
-
-
 def scale_call(chunks, R, c, ids, lag, tau=0.10, min_pairs=50, feet=None, stream=None, read_back=True):
     """gem_slam_scale.  chunks: device tensors [n_k,J,3] f64, each its own allocation or not; R [N,3,3], c [N,3], ids [N] (host).
     -> (return code, report as numpy [16 + 3 n_chunks] or the device tensor when not read_back, costs device tensor [513], message)."""
@@ -124,22 +115,15 @@ def scale_call(chunks, R, c, ids, lag, tau=0.10, min_pairs=50, feet=None, stream
     need = int(lib.gem_slam_scale_work(max(N, 1), int(lag), nc))
     if need < 0:          # (sizes out of range: gem_slam_scale itself refuses them, with its own text)
         need = 8
-    with torch.cuda.device(device):
-        st = torch.cuda.current_stream() if stream is None else stream
-        with torch.cuda.stream(st):
-            up, d_chunks, d_ids, d_rot, d_trans = _upload(table, ids, R, c, device)
-            work = torch.empty(need // 8 + 1, dtype=torch.float64, device=device)
-            n_rep = _capi.SCALE_REPORT_DOUBLES + 3 * nc
-            report = torch.zeros(n_rep, dtype=torch.float64, device=device)
-            costs = torch.zeros(_capi.SCALE_CANDIDATES, dtype=torch.float64, device=device)
-            host = np.zeros(n_rep, dtype=np.float64)
-            rc = lib.gem_slam_scale(C.c_void_p(table.ctypes.data), C.c_void_p(d_chunks.data_ptr()), nc, J, (C.c_int * 4)(*feet),
-                                    C.c_void_p(d_rot.data_ptr()), C.c_void_p(d_trans.data_ptr()), C.c_void_p(d_ids.data_ptr()), N, int(lag),
-                                    float(tau), int(min_pairs), C.c_void_p(work.data_ptr()), need, C.c_void_p(report.data_ptr()),
-                                    C.c_void_p(costs.data_ptr()), C.c_void_p(host.ctypes.data if read_back else 0), C.c_void_p(st.cuda_stream))
-            for t in (up, work):
-                t.record_stream(st)
-    msg = (lib.gem_last_error() or b"").decode() if rc else ""
+    with staged_call(lib, device, stream) as call:
+        d_chunks, d_ids, d_rot, d_trans = call.upload(table, ids, R, c)          # (ONE upload: the chunk table, the frame ids, the SLAM poses)
+        n_rep = _capi.SCALE_REPORT_DOUBLES + 3 * nc
+        report = torch.zeros(n_rep, dtype=torch.float64, device=device)
+        costs = torch.zeros(_capi.SCALE_CANDIDATES, dtype=torch.float64, device=device)
+        host = np.zeros(n_rep, dtype=np.float64)
+        rc, msg = call.run(lib.gem_slam_scale, C.c_void_p(table.ctypes.data), _ptr(d_chunks), nc, J, (C.c_int * 4)(*feet), _ptr(d_rot), _ptr(d_trans),
+                           _ptr(d_ids), N, int(lag), float(tau), int(min_pairs), _ptr(call.work(need)), need, _ptr(report), _ptr(costs),
+                           C.c_void_p(host.ctypes.data if read_back else 0))
     return rc, (host if read_back else report), costs, msg
 
 
@@ -280,25 +264,18 @@ def drift_call(chunks, R, c, ids, lag, knot, stiffness=1.0, tau=0.10, min_pairs=
         need = 8
     need = need if work_bytes is None else int(work_bytes)
     n_rep = _capi.SCALE_REPORT_DOUBLES + 3 * nc
-    with torch.cuda.device(device):
-        st = torch.cuda.current_stream() if stream is None else stream
-        with torch.cuda.stream(st):
-            up, d_chunks, d_ids, d_rot, d_trans = _upload(table, ids, R, c, device)
-            work = torch.empty(need // 8 + 1, dtype=torch.float64, device=device)
-            costs = torch.zeros(_capi.SCALE_CANDIDATES, dtype=torch.float64, device=device)
-            if outputs is None:
-                outputs = (torch.zeros(n_rep, dtype=torch.float64, device=device), torch.zeros(K_alloc, 4, dtype=torch.float64, device=device),
-                           torch.zeros(N, 3, dtype=torch.float64, device=device), torch.zeros(_capi.DRIFT_REPORT_DOUBLES, dtype=torch.float64, device=device))
-            host =[np.zeros(tuple(t.shape), dtype=np.float64) if t is not None else None for t in outputs]
-            hp = [C.c_void_p(h.ctypes.data if (read_back and h is not None) else 0) for h in host]
-            dp = [C.c_void_p(t.data_ptr() if t is not None else 0) for t in outputs]
-            rc = lib.gem_slam_drift(C.c_void_p(table.ctypes.data), C.c_void_p(d_chunks.data_ptr()), nc, J, (C.c_int * 4)(*feet),
-                                    C.c_void_p(d_rot.data_ptr()), C.c_void_p(d_trans.data_ptr()), C.c_void_p(d_ids.data_ptr()), N, int(ids[0]),
-                                    int(ids[-1]), int(lag), float(tau), int(min_pairs), knot, float(stiffness), C.c_void_p(work.data_ptr()), need,
-                                    dp[0], C.c_void_p(costs.data_ptr()), dp[1], dp[2], dp[3], hp[0], hp[1], hp[2], hp[3], C.c_void_p(st.cuda_stream))
-            for t in (up, work):
-                t.record_stream(st)
-    msg = (lib.gem_last_error() or b"").decode() if rc else ""
+    with staged_call(lib, device, stream) as call:
+        d_chunks, d_ids, d_rot, d_trans = call.upload(table, ids, R, c)          # (ONE upload, as in `scale_call`)
+        costs = torch.zeros(_capi.SCALE_CANDIDATES, dtype=torch.float64, device=device)
+        if outputs is None:
+            outputs = (torch.zeros(n_rep, dtype=torch.float64, device=device), torch.zeros(K_alloc, 4, dtype=torch.float64, device=device),
+                       torch.zeros(N, 3, dtype=torch.float64, device=device), torch.zeros(_capi.DRIFT_REPORT_DOUBLES, dtype=torch.float64, device=device))
+        host = [np.zeros(tuple(t.shape), dtype=np.float64) if t is not None else None for t in outputs]
+        hp = [C.c_void_p(h.ctypes.data if (read_back and h is not None) else 0) for h in host]
+        dp = [_ptr(t) for t in outputs]
+        rc, msg = call.run(lib.gem_slam_drift, C.c_void_p(table.ctypes.data), _ptr(d_chunks), nc, J, (C.c_int * 4)(*feet), _ptr(d_rot), _ptr(d_trans),
+                           _ptr(d_ids), N, int(ids[0]), int(ids[-1]), int(lag), float(tau), int(min_pairs), knot, float(stiffness),
+                           _ptr(call.work(need)), need, dp[0], _ptr(costs), dp[1], dp[2], dp[3], hp[0], hp[1], hp[2], hp[3])
     got = host if read_back else list(outputs)
     return rc, {"scale_report": got[0], "costs": costs, "knots": got[1], "metric": got[2], "report": got[3]}, msg
 
@@ -419,7 +396,6 @@ def _parser():
 
 
 def _cli(argv=None):
-    import json
     from . import detections, prepare, slam
     p = _parser()
     a = p.parse_args(argv)
@@ -454,10 +430,7 @@ def _cli(argv=None):
         print("chunk %d [%d, %d): scale %.9g%s" % (k, s, e, v, "" if umeyama_per_chunk is None else "   Umeyama against the ground truth %.9g" % umeyama_per_chunk[k]))
     if a.scale == "drift":
         print("\n".join(est.knot_lines()))
-    if a.json is not None:
-        os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
-        with open(a.json, "w") as f:
-            json.dump(out, f, indent=1)
+    write_json(a.json, out)
     return est
 
 
